@@ -32,7 +32,14 @@ batch of min/max AND one batch of histogram + epilogue (nothing is skipped or re
 bit-identical to the unchained order, tests/test_gpu_parity.py::test_chained_minmax_is_bit_identical);
 the stand-alone min/max launch merely disappears.  `--no-chain` runs K1 then K3 per step.
 
-After the timed region rank 0's line also carries (all outside the timed region, all parity-checked):
+A plain run sets up, warms up, times the K steps and prints the line (with `roofline`, read from the HIP events of the timed
+region).  `--dump-outputs DIR` also writes what the last timed step computed -- the result vectors a caller of the pipeline
+receives (KeffPlan.fetch), all ranks' slabs in rank order -- as DIR/<name>.npy in float64, all finite (non-finite entries, such
+as the NaN of a masked nkeff, as 0 plus a code in DIR/<name>_nonfinite.npy: see dump_outputs), for output-by-output comparison
+of two builds (the inputs are seeded: the same arguments give the same slabs; levels and counts are then bit-identical, the
+float64 atomic sums agree to rounding, and bit for bit with `--deterministic`).
+
+With `--full`, after the timed region rank 0's line also carries (all outside the timed region, all parity-checked):
   * `variants.slab_dA` -- the same chained schedule with per-slab (time-varying) weights: every byte of the 16 B/cell
     numerator is then unique HBM traffic, so `frac == hbm_unique_frac` is a genuine HBM fraction;
   * `variants.f32` -- the same schedule on float32 tracers and float32 contours (the dtype of every file the reference ships
@@ -43,10 +50,11 @@ After the timed region rank 0's line also carries (all outside the timed region,
     send buffer, ONE gather of all nine result vectors inside its own timed region (barrier + sync on both sides, max over
     ranks) and a `budget` of where each rank's job time goes.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel = the histogram pass, timed
-with HIP events on its own stream around every launch of the timed region) and
-`cpu_baseline` (the numpy oracle = a port of the reference's xarray/xhistogram call
-sequence, timed on this host's cores by rank 0 on a bounded sample of the same slabs).
+  * `cpu_baseline` -- the numpy oracle (a port of the reference's xarray/xhistogram call sequence), timed on this host's
+    cores by rank 0 on a bounded sample of the same slabs, whose vectors are compared with the last timed step's;
+  * `unchained`, `variants.f32`, `single_slab`, `facade_demo`, and the self-checks of the last step.
+Rank 0 prints ONE JSON line; its `roofline` (dominant kernel = the histogram pass, timed with HIP events on its own stream
+around every launch of the timed region) is there in a plain run too.
 """
 import argparse
 import json
@@ -61,6 +69,7 @@ NY, NX, NCONT = 1801, 3600, 201
 SEED = 20241008
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 BYTES_PER_CELL = 16              # algorithmic: tracer f64 once + dA f64 once; 8 with --row-dA
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: all files together
 
 
 # ----------------------------------------------------------------------------- CPU baseline worker
@@ -795,17 +804,50 @@ def parse_args(argv=None):
     ap.add_argument('--dtype', default='f64', choices=['f64', 'f32'],
                     help='tracer dtype: f64 (default: the headline configuration BASELINE.json names) or f32 -- float32 tracer AND float32 '
                          'contours, the dtype of the files the reference ships and its default `dtype` (core.py:21); algorithmic bytes 4 + 8 per cell')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also run the self-checks, the CPU baseline, the variants / long_run / unchained / '
+                         'single_slab / facade_demo blocks and the cfg4 strong-scaling job (the --no-* options below drop single parts)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write the result vectors of the last timed step (all ranks\' slabs) to DIR/<name>.npy, float64 and finite '
+                         '(non-finite entries as 0, coded in DIR/<name>_nonfinite.npy); a seeded sample of the slabs if they exceed %d MB' % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument('--no-cpu', action='store_true', help='(--full) skip the CPU baseline leg')
     ap.add_argument('--cpu-slabs', type=int, default=0, help='distinct slabs in the CPU sample, all parity-checked (0: 8)')
     ap.add_argument('--cpu-workers', type=int, default=0, help='upper bound on the CPU sample\'s concurrent processes (0: as many as cores and memory allow)')
-    ap.add_argument('--no-extras', action='store_true', help='skip variants / long_run / unchained after the timed region')
+    ap.add_argument('--no-extras', action='store_true', help='(--full) skip variants / long_run / unchained / single_slab / facade_demo after the timed region')
     ap.add_argument('--long-run-s', type=float, default=4.0, help='seconds of extra steps with per-launch events (long_run)')
-    ap.add_argument('--no-cfg4', action='store_true', help='skip the cfg4 strong-scaling block')
+    ap.add_argument('--no-cfg4', action='store_true', help='(--full) skip the cfg4 strong-scaling block')
     ap.add_argument('--cfg4-slabs', type=int, default=512 * 37)
     ap.add_argument('--cfg4-chunk', type=int, default=0, help='slabs per launch set of the cfg4 sweep (0: chosen by cfg4_launch_set: a size that tiles the rank\'s block and fills whole rounds of workgroups)')
     ap.add_argument('--cfg4-reps', type=int, default=2, help='timed cfg4 jobs (sweep + gather)')
-    ap.add_argument('--dump-cfg4', default='', help='rank 0 saves the gathered (S, 9, N) cfg4 result to this .npy file')
+    ap.add_argument('--dump-cfg4', default='', help='(--full) rank 0 saves the gathered (S, 9, N) cfg4 result to this .npy file')
     return ap.parse_args(argv)
+
+
+def dump_outputs(d, out):
+    """--dump-outputs: one float64 .npy per result vector of the last timed step (`out`: name -> array with the slabs on axis 0,
+    as KeffPlan.fetch returns it).  Every file holds finite numbers: a floating-point vector goes out with its non-finite entries
+    set to 0 beside <name>_nonfinite.npy, which codes each entry 0 finite, 1 NaN, 2 +inf, 3 -inf (nkeff is NaN wherever the
+    reference masks it, core.py:964).  Above DUMP_MAX_BYTES, a fixed seeded sample of the slabs, whose indices go to slab_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    enc = {}
+    for k, v in out.items():
+        v = np.asarray(v)
+        if np.issubdtype(v.dtype, np.floating):
+            code = np.where(np.isnan(v), 1.0, np.where(v == np.inf, 2.0, np.where(v == -np.inf, 3.0, 0.0)))
+            enc[k] = np.where(code == 0, v, 0.0).astype(np.float64)
+            enc[k + '_nonfinite'] = code
+        else:
+            enc[k] = v.astype(np.float64)
+    out = enc
+    S = len(out['ctr'])
+    per_slab = sum(v[0].nbytes for v in out.values())
+    room = DUMP_MAX_BYTES - 256 * (len(out) + 1)                  # less the .npy headers
+    if S * per_slab > room:
+        idx = np.sort(np.random.default_rng(SEED).choice(S, room // (per_slab + 8), replace=False))
+        out = {k: v[idx] for k, v in out.items()}
+        out['slab_index'] = idx.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + '.npy'), np.ascontiguousarray(v))
 
 
 def main():
@@ -943,12 +985,18 @@ def main():
     mine_info = {'rank': rank, 'sweep_ms': ctx.elapsed_ms(es0, es1), 'wall_ms': t_mine * 1e3, 'device': ctx.device, 'comm': ctx.comm_info()}
     per_rank = [json.loads(p.decode()) for p in group.allgather_bytes(json.dumps(mine_info).encode())]
     stage('checks')
-    if world > 1 and rank == 0:
-        # every rank's block arrived, in rank order, and rank r's slabs differ from rank 0's (seed + r*2B + s)
+    last = None                                                   # --dump-outputs: what the last timed step computed, every rank's slabs
+    if world > 1 and rank == 0 and (a.full or a.dump_outputs):
         g = gather.fetch(rb)
-        mine = res.download((nres,), np.uint8)
-        assert np.array_equal(g[0], mine) and all(not np.array_equal(g[r], g[0]) for r in range(1, world)), 'gathered blocks are not in rank order'
-        del g, mine
+        if a.full:
+            # every rank's block arrived, in rank order, and rank r's slabs differ from rank 0's (seed + r*2B + s)
+            mine = res.download((nres,), np.uint8)
+            assert np.array_equal(g[0], mine) and all(not np.array_equal(g[r], g[0]) for r in range(1, world)), 'gathered blocks are not in rank order'
+            del mine
+        if a.dump_outputs:
+            parts = [plan.unpack(g[r][(K - 1) * slot:K * slot]) for r in range(world)]
+            last = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+        del g
     if world > 1:
         gather.free_block(rb)
 
@@ -1012,15 +1060,18 @@ def main():
                                         'slab although the %d slabs of a launch share it (cache-served after the first fetch) -- '
                                         'hbm_unique_frac counts only bytes that must come from HBM.  variants.slab_dA is the '
                                         'configuration where the two coincide' % B}
-        # self-check of the last step: every cell lands in exactly one bin (xhistogram rule: last edge + 1e-8 keeps the max cell)
-        out = plan.fetch(slot=K - 1)
-        # (float32 contours: the last level is the float32 rounding of the maximum and `+ 1e-8` is below its resolution, so the
-        #  maximum cell itself may fall outside the last edge -- reference behaviour; the oracle check below is exact)
-        csum = out['counts'].sum(axis=1).astype(np.int64)
-        lost = NX if a.variant == 2 else 4                           # (sin(lat): the whole pole row holds the maximum)
-        if not ((csum == NY * NX).all() if a.dtype == 'f64' else ((csum <= NY * NX) & (csum >= NY * NX - lost)).all()) or out['status'].any():
-            raise RuntimeError('bench self-check failed: counts %r status %r' % (out['counts'].sum(axis=1), out['status']))
-        extras = world == 1 and grp == B and not a.no_extras
+        out = plan.fetch(slot=K - 1) if (a.full or a.dump_outputs) else None
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, last if world > 1 else out)
+        if a.full:
+            # self-check of the last step: every cell lands in exactly one bin (xhistogram rule: last edge + 1e-8 keeps the max cell)
+            # (float32 contours: the last level is the float32 rounding of the maximum and `+ 1e-8` is below its resolution, so the
+            #  maximum cell itself may fall outside the last edge -- reference behaviour; the oracle check below is exact)
+            csum = out['counts'].sum(axis=1).astype(np.int64)
+            lost = NX if a.variant == 2 else 4                       # (sin(lat): the whole pole row holds the maximum)
+            if not ((csum == NY * NX).all() if a.dtype == 'f64' else ((csum <= NY * NX) & (csum >= NY * NX - lost)).all()) or out['status'].any():
+                raise RuntimeError('bench self-check failed: counts %r status %r' % (out['counts'].sum(axis=1), out['status']))
+        extras = a.full and world == 1 and grp == B and not a.no_extras
         if extras and chain:
             # transparency: the same work in the plain order (stand-alone K1 launch, then K3), a short extra run
             # AFTER the timed region (identical per-step outputs; tests/test_gpu_parity.py::test_chained_minmax_is_bit_identical)
@@ -1106,7 +1157,7 @@ def main():
             finally:
                 if p2 is not None:
                     p2.free()
-        if not a.no_cpu:
+        if a.full and not a.no_cpu:
             # the oracle on slabs of the LAST timed step's batch; their vectors are compared with that step's GPU result.  N > 1: rank 0
             # alone, a smaller sample (the other ranks wait at a barrier whose timeout covers it, below): a line without a CPU
             # baseline beside it reads as unmeasured
@@ -1121,7 +1172,7 @@ def main():
         group.barrier(timeout=900.0)                              # rank 0 has been timing the CPU baseline meanwhile
     plan.free()
     res.free(); wres.free()
-    if rank == 0 and world == 1 and a.dtype == 'f64' and grp == B and not a.no_extras and not (a.slab_dA or a.row_dA or a.deterministic):
+    if a.full and rank == 0 and world == 1 and a.dtype == 'f64' and grp == B and not a.no_extras and not (a.slab_dA or a.row_dA or a.deterministic):
         # float32 tracers and contours -- the reference's default `dtype` and the dtype of the files it ships -- through the same
         # chained schedule, so that the driver's line carries them; two slabs of its last step against the oracle
         v32 = variant_f32(ctx, nat, a, lat, lon, dA, tbl, chain)
@@ -1132,7 +1183,7 @@ def main():
                              'sin_lat': variant_f32(ctx, nat, a, lat, lon, dA, tbl, chain, variant=2, ncheck=0, brief=True),
                              'barotropic_vorticity_interpolated': variant_f32(ctx, nat, a, lat, lon, dA, tbl, chain, variant=3, ncheck=1, brief=True)}
         line.setdefault('variants', {})['f32'] = v32
-    if rank == 0 and world == 1 and a.dtype == 'f64' and not a.no_extras and not (a.slab_dA or a.row_dA):
+    if a.full and rank == 0 and world == 1 and a.dtype == 'f64' and not a.no_extras and not (a.slab_dA or a.row_dA):
         # ONE cfg2 slab through the pipeline, a sync before every call: north_star's literal unit and what a caller with one (time, level)
         # field gets (the reference's callers hand planes over one at a time, tests/LWA.py:40-43) -- four dependent launches
         # (K1, K3, reduce, finalize), nothing to overlap them with
@@ -1143,7 +1194,7 @@ def main():
         stage('facade_demo')
         line['facade_demo'] = facade_demo()
     # ---- cfg4 strong scaling: every rank takes part (its own timed region, after the cfg2 buffers are gone)
-    if not a.no_cfg4 and a.dtype == 'f64':
+    if a.full and not a.no_cfg4 and a.dtype == 'f64':
         stage('cfg4')
         blk = cfg4_strong(ctx, nat, a, group, gather)
         if rank == 0:

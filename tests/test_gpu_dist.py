@@ -160,7 +160,7 @@ def test_bench_launches_two_ranks_by_itself_on_one_gpu():
     arrived in rank order (asserted inside) and the cfg4 block's checks hold -- rank 1's first slab recomputed on rank 0, two
     slabs against the oracle; no torch in any of the three processes"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1',
-                        '--batch', '4', '--cfg4-slabs', '64', '--cfg4-reps', '1', '--cpu-slabs', '1', '--cpu-workers', '2'],
+                        '--batch', '4', '--full', '--cfg4-slabs', '64', '--cfg4-reps', '1', '--cpu-slabs', '1', '--cpu-workers', '2'],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=_clean_env(), timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -180,6 +180,34 @@ def test_bench_launches_two_ranks_by_itself_on_one_gpu():
     pr = d['per_rank']
     assert len(pr['sweep_ms']) == 2 and all(x > 0 for x in pr['sweep_ms']) and len(pr['wall_ms']) == 2 and pr['device'] == [0, 0]
     assert d['config']['rccl'] is None and 'carrier host' in d['config']['parallelism']
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain `bench.py --gpus N` (no --full): the line has the headline fields and none of the --full blocks; --dump-outputs
+    writes the last timed step's vectors as finite float64 (non-finite entries coded beside them), and the 2-rank job's dump is the 1-rank job's slabs bit for bit
+    (deterministic sums; rank 0 owns the same seeded slabs) followed by rank 1's"""
+    dumps = {}
+    for w in (1, 2):
+        d = tmp_path / ('d%d' % w)
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(w), '--steps', '3', '--warmup', '1', '--batch', '2',
+               '--deterministic', '--dump-outputs', str(d)]
+        if w > 1:
+            cmd += ['--backend', 'ipc']
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=_clean_env(), timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+        assert line['n_gpus'] == w and line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert line['unit'] == 'cells*contours/s' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+        assert not {'cpu_baseline', 'cfg4_strong', 'variants', 'long_run', 'unchained', 'single_slab', 'facade_demo'} & set(line)
+        dumps[w] = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    one, two = dumps[1], dumps[2]
+    assert set(one) == set(NINE) | {k + '_nonfinite' for k in NINE} | {'counts', 'status'} and set(two) == set(one)
+    for k, v in one.items():
+        assert v.dtype == np.float64 and two[k].dtype == np.float64 and len(v) == 2 and len(two[k]) == 4
+        assert np.isfinite(v).all() and np.isfinite(two[k]).all(), k
+        assert np.array_equal(bits(two[k][:2]), bits(v)), k
+    assert not np.array_equal(two['ctr'][2:], one['ctr'])
+    assert (two['counts'].sum(axis=1) == 1801 * 3600).all() and not two['status'].any()
 
 
 def test_bench_refuses_a_world_that_disagrees_with_gpus():
@@ -274,7 +302,7 @@ def test_bench_ipc_ranks_on_one_gpu_equal_the_one_rank_job(world, tmp_path):
     for w in (1, world):
         f = str(tmp_path / ('cfg4_%d.npy' % w))
         cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(w), '--steps', '2', '--warmup', '1', '--batch', '2', '--deterministic',
-               '--cfg4-slabs', '100', '--cfg4-chunk', '8', '--cfg4-reps', '1', '--dump-cfg4', f, '--no-extras', '--cpu-slabs', '1', '--cpu-workers', '2']
+               '--full', '--cfg4-slabs', '100', '--cfg4-chunk', '8', '--cfg4-reps', '1', '--dump-cfg4', f, '--no-extras', '--cpu-slabs', '1', '--cpu-workers', '2']
         if w > 1:
             cmd += ['--backend', 'ipc']
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=_clean_env(), timeout=900, cwd=ROOT)
@@ -386,7 +414,7 @@ def test_a_rank_that_never_joins_rccl_does_not_hang_the_job():
     env.update({'XC_TEST_SKIP_COMM_INIT_RANK': '1', 'XC_COMM_TIMEOUT_S': '5'})
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2', '--no-cpu',
-                        '--cfg4-slabs', '32', '--cfg4-reps', '1', '--deadline-s', '240'],
+                        '--full', '--cfg4-slabs', '32', '--cfg4-reps', '1', '--deadline-s', '240'],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=env, timeout=400, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     assert time.time() - t0 < 200

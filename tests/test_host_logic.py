@@ -215,6 +215,39 @@ def test_cfg4_launch_sets_tile_the_blocks_of_every_rank_count():
     assert m.cfg4_launch_set(11) == 256 and m.cfg4_launch_set(3157) == 256       # no divisor that fills the rounds: ragged sets of 256
 
 
+def test_bench_dump_outputs_writes_float64_within_its_budget(tmp_path):
+    """bench.dump_outputs: one finite float64 .npy per result vector -- a floating-point vector's NaN / +inf / -inf go out as 0
+    with a code per entry in <name>_nonfinite.npy, from which the vector comes back exactly; above the byte budget a seeded
+    sample of the slabs (the same one every run) and its indices.  A plain run leaves --full off."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(ROOT, 'bench.py'))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    a = m.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert not a.full and a.dump_outputs == '' and a.steps == 3
+    rng = np.random.default_rng(0)
+    ctr = rng.random((40, 201))
+    ctr[3, :7] = np.nan; ctr[5, 9] = np.inf; ctr[6, 0] = -np.inf
+    out = {'ctr': ctr, 'counts': rng.integers(0, 1 << 20, (40, 201)).astype(np.uint64), 'status': np.zeros(40, np.int32)}
+    m.dump_outputs(str(tmp_path / 'all'), out)
+    got = {f.name[:-4]: np.load(str(f)) for f in (tmp_path / 'all').iterdir()}
+    assert set(got) == {'ctr', 'ctr_nonfinite', 'counts', 'status'}
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in got.values())
+    code = got['ctr_nonfinite']
+    back = np.where(code == 1, np.nan, np.where(code == 2, np.inf, np.where(code == 3, -np.inf, got['ctr'])))
+    assert np.array_equal(back, ctr, equal_nan=True) and (code != 0).sum() == 9 and (got['ctr'][code != 0] == 0).all()
+    for k in ('counts', 'status'):
+        assert np.array_equal(got[k], out[k].astype(np.float64))
+    m.DUMP_MAX_BYTES = 20 * (201 * 8 * 3 + 8) + 4096
+    for d in ('s1', 's2'):
+        m.dump_outputs(str(tmp_path / d), out)
+    idx = np.load(str(tmp_path / 's1' / 'slab_index.npy')).astype(np.int64)
+    assert np.array_equal(idx, np.load(str(tmp_path / 's2' / 'slab_index.npy'))) and 0 < len(idx) <= 20
+    assert np.array_equal(np.load(str(tmp_path / 's1' / 'ctr_nonfinite.npy')), code[idx])
+    assert np.array_equal(np.load(str(tmp_path / 's1' / 'ctr.npy')), got['ctr'][idx])
+    assert sum(f.stat().st_size for f in (tmp_path / 's1').iterdir()) <= m.DUMP_MAX_BYTES
+
+
 def test_xarray_branch_of_labeled_runs_with_a_test_double():
     """xarray is the reference's in/out type (core.py:8-13) and is absent from both boxes: tests/fake_xarray/xarray.py is a
     60-line double that makes `labeled.is_xarray` true, so unwrap (coords filter included) / wrap / merge run for real

@@ -12,8 +12,8 @@ done
 echo "== secondary configs"
 for c in cfg3 cfg4 cfg5; do timeout -k 10 300 python3 bench.py --config $c --steps 50 --warmup 5 2>/dev/null | grep '^{' > $O/${RD}_bench_$c.json || exit 1; done
 echo "== 2 and 4 ranks on this one GPU, the driver's own command form (the N > 1 path of bench.py incl. cfg4_strong: RCCL refuses a shared GPU, the ladder lands on HIP IPC; correctness + gather evidence, not a speed)"
-timeout -k 10 500 python3 bench.py --gpus 2 --cpu-slabs 2 2> $O/${RD}_bench_2ranks_ipc_1gpu.err | grep '^{' > $O/${RD}_bench_2ranks_ipc_1gpu.json || exit 1
-timeout -k 10 500 python3 bench.py --gpus 4 --steps 6 --batch 16 --cfg4-slabs 4736 --cpu-slabs 2 2> $O/${RD}_bench_4ranks_ipc_1gpu.err | grep '^{' > $O/${RD}_bench_4ranks_ipc_1gpu.json || exit 1
+timeout -k 10 500 python3 bench.py --gpus 2 --full --cpu-slabs 2 2> $O/${RD}_bench_2ranks_ipc_1gpu.err | grep '^{' > $O/${RD}_bench_2ranks_ipc_1gpu.json || exit 1
+timeout -k 10 500 python3 bench.py --gpus 4 --steps 6 --batch 16 --full --cfg4-slabs 4736 --cpu-slabs 2 2> $O/${RD}_bench_4ranks_ipc_1gpu.err | grep '^{' > $O/${RD}_bench_4ranks_ipc_1gpu.json || exit 1
 echo "== kernel timings"
 timeout -k 10 500 python3 tools/kernel_times.py sort lwa cross pipe land single > $O/${RD}_kernel_times.jsonl 2>&1 || exit 1
 XC_FACADE_STACK=128 XC_FACADE_SMALL=1 timeout -k 10 300 python3 tools/facade_time.py 2>/dev/null | grep '^{' > $O/${RD}_facade_time.jsonl || exit 1
@@ -37,10 +37,10 @@ bash tools/pmc_lwa.sh > $O/${RD}_pmc_k7_instruction_mix.txt 2>&1 || exit 1
 bash tools/pmc_cross.sh > $O/${RD}_pmc_k9_instruction_mix.txt 2>&1 || exit 1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_sort -o kt -- python3 tools/kernel_times.py sort > /dev/null 2>&1
 cp $O/kt_sort/*/kt_kernel_stats.csv $O/${RD}_k8_sort_kernel_stats.csv 2>/dev/null || cp $O/kt_sort/kt_kernel_stats.csv $O/${RD}_k8_sort_kernel_stats.csv
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_cfg4 -o kt -- python3 bench.py --steps 3 --warmup 1 --no-cpu --no-extras > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_cfg4 -o kt -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu --no-extras > /dev/null 2>&1
 cp $O/kt_cfg4/*/kt_kernel_stats.csv $O/${RD}_bench_cfg4_strong_kernel_stats.csv 2>/dev/null || cp $O/kt_cfg4/kt_kernel_stats.csv $O/${RD}_bench_cfg4_strong_kernel_stats.csv
 echo "== bench default (last: it quotes the PMC traffic just measured)"
 cp $O/hist_traffic.json $R/profiles/hist_traffic.json
-timeout -k 10 500 python3 bench.py > $O/${RD}_bench_n1.json 2> $O/${RD}_bench_n1.err || exit 1
+timeout -k 10 500 python3 bench.py --full > $O/${RD}_bench_n1.json 2> $O/${RD}_bench_n1.err || exit 1
 ;; esac
 echo "== done"; ls -la $O/${RD}_*
