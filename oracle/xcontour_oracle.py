@@ -270,10 +270,21 @@ def histogram_cdf(q, b, weights, lt, right_edge='xhistogram', deterministic=Fals
     q = np.asarray(q)
     w = np.broadcast_to(np.asarray(weights), q.shape)
     pdf, counts = weighted_histogram(q, edges, w, right_edge, deterministic, det_top, det_limbs)
-    cdf = np.cumsum(pdf)                                     # core.py:1320
+    return cdf_from_pdf(pdf, lt), pdf, counts, bincrease
+
+
+def cdf_from_pdf(pdf, lt):
+    """The tail of `_histogram` (core.py:1320-1323) on given per-bin sums in ASCENDING-VALUE order: the sequential
+    np.cumsum, then the `lt` flip.  The result stays in ascending-value order (`level_order` puts it in level order)."""
+    cdf = np.cumsum(np.asarray(pdf))                         # core.py:1320
     if not lt:
         cdf = cdf[-1] - cdf                                  # core.py:1322-1323
-    return cdf, pdf, counts, bincrease
+    return cdf
+
+
+def level_order(v, bincrease):
+    """core.py:454-455: a vector in ascending-value bin order -> level order (reversed when the levels decrease)."""
+    return v if bincrease else v[::-1]
 
 
 # ---------------------------------------------------------------------------
@@ -296,8 +307,7 @@ def cal_integral_within_contours_hist(q, ctr, dA, integrand=None, lt=False,
     q = np.asarray(q)
     wei = _weights(dA, integrand, q.shape)
     cdf, pdf, counts, binc = histogram_cdf(q, ctr, wei, lt, right_edge, deterministic, det_top, det_limbs)
-    if not binc:                                             # core.py:454-455
-        cdf, pdf, counts = cdf[::-1], pdf[::-1], counts[::-1]
+    cdf, pdf, counts = level_order(cdf, binc), level_order(pdf, binc), level_order(counts, binc)    # core.py:454-455
     if return_counts:
         return cdf, counts
     return cdf
@@ -832,17 +842,27 @@ def keff_pipeline(q, dA, lat, N, grdS=None, lon=None, mask=None, increase=True,
     area, counts = cal_integral_within_contours_hist(q, ctr, dA, None, lt, right_edge, return_counts=True,
                                                      deterministic=deterministic, det_top=top0)
     intgrdS = cal_integral_within_contours_hist(q, ctr, dA, grdS, lt, right_edge, deterministic=deterministic, det_top=top1)
-    latEq = lookup_coordinates(area, tbl, cs)
+    out = dict(ctr=ctr, counts=counts, area=area, intgrdS=intgrdS, tbl=tbl, tbl_coord=cs)
+    out.update(keff_epilogue(ctr, area, intgrdS, tbl, cs, preLats, nkeff_mask))
+    return out
+
+
+EQ_NAMES = ('ctr', 'area', 'intgrdS', 'latEq', 'dintSdA', 'dqdA', 'Leq2', 'Lmin', 'nkeff')
+
+
+def keff_epilogue(ctr, area, intgrdS, tbl, tbl_coord, preLats=None, nkeff_mask=1e5):
+    """Steps 5-10 of SURVEY 3.1 for one slab, from the conditional integrals onwards.  `ctr` in its contour dtype
+    (np.gradient of float32 levels stays in float32), `area` / `intgrdS` in level order, (`tbl`, `tbl_coord`) the A(Yeq)
+    table.  Returns latEq, Lmin, dintSdA, dqdA, Leq2, nkeff (+ '<name>_eq' of EQ_NAMES on `preLats` if given)."""
+    latEq = lookup_coordinates(area, tbl, tbl_coord)
     Lmin = latitude_lengths_at(latEq)
     dintSdA = cal_gradient_wrt_area(intgrdS, area)
     dqdA = cal_gradient_wrt_area(ctr, area)
     Leq2 = cal_sqared_equivalent_length(dintSdA, dqdA)
     nkeff = cal_normalized_Keff(Leq2, Lmin, nkeff_mask)
-    out = dict(ctr=ctr, counts=counts, area=area, intgrdS=intgrdS, tbl=tbl,
-               tbl_coord=cs, latEq=latEq, Lmin=Lmin, dintSdA=dintSdA,
-               dqdA=dqdA, Leq2=Leq2, nkeff=nkeff)
+    out = dict(latEq=latEq, Lmin=Lmin, dintSdA=dintSdA, dqdA=dqdA, Leq2=Leq2, nkeff=nkeff)
     if preLats is not None:
-        for name in ('ctr', 'area', 'intgrdS', 'latEq', 'dintSdA', 'dqdA',
-                     'Leq2', 'Lmin', 'nkeff'):
-            out[name + '_eq'] = interp_to_coords(preLats, latEq, out[name])
+        v = dict(out, ctr=ctr, area=area, intgrdS=intgrdS)
+        for name in EQ_NAMES:
+            out[name + '_eq'] = interp_to_coords(preLats, latEq, v[name])
     return out

@@ -12,7 +12,7 @@ import pytest
 
 import xcontour_oracle as O
 from test_gpu_parity import rel, RTOL, TIGHT, LMIN_FLOOR, _baro_da
-from gpu_common import GOLD, NINE, ROOT, bits, check_nine, check_nine_det, _clean_env
+from gpu_common import GOLD, NINE, ROOT, bits, check_epilogue, check_nine, check_nine_det, _clean_env
 
 pytestmark = pytest.mark.gpu
 
@@ -128,6 +128,7 @@ def test_keff_ocean_call_sequence_with_land_mask(ctx, dt):
     assert np.array_equal(ds['ctr'].values, o_ctr.astype(np.float64))
     assert rel(ds['area'].values, o_area) < TIGHT and rel(ds['intgrdS'].values, o_S) < TIGHT
     assert rel(ds['latEq'].values, o_Yeq) < 1e-9
+    check_epilogue({k: ds[k].values[None] for k in NINE}, 0, table._table.values, table._coord, None, np.float32)   # the reference's default contour dtype
 
 
 def test_keff_table_length_and_order(ctx, baro):

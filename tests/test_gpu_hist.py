@@ -12,7 +12,7 @@ import pytest
 
 import xcontour_oracle as O
 from test_gpu_parity import rel, RTOL, TIGHT, LMIN_FLOOR, _baro_da
-from gpu_common import GOLD, NINE, ROOT, bits, check_nine, check_nine_det, _clean_env
+from gpu_common import GOLD, NINE, ROOT, bits, check_epilogue, check_epilogue_equals, check_nine, check_nine_det, same_bits, _clean_env
 
 pytestmark = pytest.mark.gpu
 
@@ -76,6 +76,14 @@ def test_keff_epilogue_alone(ctx, baro, increase, lt, cd):
     names = ('ctr', 'area', 'intgrdS', 'latEq', 'dintSdA', 'dqdA', 'Leq2', 'Lmin', 'nkeff')
     for v in (0, 1, 3):
         assert rel(out['interp'][0, v], r[names[v] + '_eq']) < RTOL, names[v]
+    # the same PDFs through the oracle's PDF -> CDF tail: the sums bit for bit (sequential np.cumsum, the lt flip, the reversal
+    # for decreasing levels), then the epilogue stage by stage on the kernel's own sums, and against the oracle's epilogue of them
+    _, binc = O.hist_edges(ctr)
+    area, ints = (O.level_order(O.cdf_from_pdf(pdf[0, c], lt), binc) for c in (0, 1))
+    same_bits(out['area'][0], area, 'area'); same_bits(out['intgrdS'][0], ints, 'intgrdS')
+    pre = lat.astype(np.float64)
+    check_epilogue(out, 0, r['tbl'], r['tbl_coord'], pre, cd, ctr=ctr)
+    check_epilogue_equals(out, 0, O.keff_epilogue(ctr, area, ints, r['tbl'], r['tbl_coord'], pre))
     with pytest.raises(Exception):
         ctx.keff_epilogue(pdf, ctr[None].astype(np.float64), r['tbl'][:1], r['tbl_coord'][:1])      # a table needs >= 2 entries
 
@@ -110,7 +118,7 @@ def test_cfg4_shape_chained_launch_sets(ctx):
         assert np.array_equal(b['counts'][s].astype(np.int64), cnt), s
     for s in (0, 1, 36, 37, 55, 73):
         r = O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=np.float64, preLats=preY)
-        check_nine(b, s, r, with_eq=True)
+        check_nine(b, s, r, with_eq=True, tbl=tbl, tbl_coord=lat, preY=preY)
     plan.free()
 
 
@@ -141,7 +149,7 @@ def test_float32_tracers_four_cells_per_lane(ctx, nx):
             _, cnt = O.cal_integral_within_contours_hist(q[s], ctr, dA, None, True, return_counts=True)
             assert np.array_equal(b['counts'][s].astype(np.int64), cnt), s
         for s in (0, 2, 7):
-            check_nine(b, s, O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=cd))
+            check_nine(b, s, O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=cd), tbl=tbl, tbl_coord=lat)
         plan.free()
     # the reference's own workflow: a SUPPLIED float32 squared gradient (its notebooks pass grdSpv) -- same variant, other layout
     g2 = np.stack([O.grad2_sphere(q[s], lat, lon) for s in range(S)]).astype(np.float32)
@@ -154,7 +162,7 @@ def test_float32_tracers_four_cells_per_lane(ctx, nx):
     assert np.array_equal(b['counts'], ref['counts']) and rel(b['intgrdS'], ref['intgrdS']) < 1e-13
     for s in (0, 3, 9):
         r = O.keff_pipeline(q[s], dA, lat, N, grdS=g2[s], increase=True, lt=True, dtype=np.float32)
-        check_nine(b, s, r)
+        check_nine(b, s, r, tbl=tbl, tbl_coord=lat)
     plan.free()
 
 
@@ -304,12 +312,25 @@ def test_deterministic_pipeline_is_order_free(ctx, dt, cd):
     d = outs[0]
     assert np.array_equal(d['ctr'], ref['ctr']) and np.array_equal(d['counts'], ref['counts'])
     assert rel(d['area'], ref['area']) < 1e-12 and rel(d['intgrdS'], ref['intgrdS']) < 1e-12
+    # the same pass given the ORACLE's A(Yeq) table (the row-sum table above differs from it in the last bits): equal sums and an
+    # equal table, so everything derived must equal the deterministic oracle's as well
+    pre = np.concatenate([lat[::4], [-90.0, 90.0]])
+    rd0 = O.keff_pipeline(q[0], dA, lat, N, lon=lon, increase=True, lt=True, dtype=cd, deterministic=True)
+    det_o = KeffPlan(ctx, S, ny, nx, N, dt, cd, deterministic=True, alloc_q=False, preY=pre, **dict(kw, tbl=rd0['tbl'], tbl_coord=rd0['tbl_coord']))
+    det_o.set_q_device(plain._q_ptr)
+    det_o.run(0)
+    o = det_o.fetch(slot=0)
     for s in range(S):
         r = O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=cd)
-        check_nine_det(d, s, r)
+        check_nine_det(d, s, r, tbl=tbl, tbl_coord=lat)
         # the oracle's own restatement of the fixed-point rule (deterministic_bin_sums): the SAME BITS, sums included
-        rd = O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=cd, deterministic=True)
+        rd = O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=cd, deterministic=True, preLats=pre)
         assert np.array_equal(bits(d['area'][s]), bits(rd['area'])) and np.array_equal(bits(d['intgrdS'][s]), bits(rd['intgrdS']))
+        same_bits(rd['tbl'], rd0['tbl'], 'table'); same_bits(rd['tbl_coord'], lat, 'table coordinates')
+        same_bits(o['area'][s], rd['area'], 'area'); same_bits(o['intgrdS'][s], rd['intgrdS'], 'intgrdS')
+        check_epilogue(o, s, rd['tbl'], rd['tbl_coord'], pre, cd, what='slab %d' % s)
+        check_epilogue_equals(o, s, rd, what='slab %d' % s)
+    det_o.free()
     det.free(); plain.free()
 
 
@@ -403,9 +424,11 @@ def test_cfg2_full_size_deterministic(ctx):
         assert np.array_equal(bits(a[k]), bits(b[k])), k
     q = plan.download_q()
     r = O.keff_pipeline(q[1], dA, lat, N, lon=lon, increase=True, lt=True, dtype=np.float64)
-    check_nine_det(a, 1, r)
+    check_nine_det(a, 1, r, tbl=tbl, tbl_coord=lat)
     rd = O.keff_pipeline(q[1], dA, lat, N, lon=lon, increase=True, lt=True, dtype=np.float64, deterministic=True)
     assert np.array_equal(bits(a['area'][1]), bits(rd['area'])) and np.array_equal(bits(a['intgrdS'][1]), bits(rd['intgrdS']))   # 6.5 M cells, bit for bit
+    if np.array_equal(bits(tbl), bits(rd['tbl'])):                 # (the device row-sum table: equal to the oracle's only by chance)
+        check_epilogue_equals(a, 1, rd)
     plan.free()
 
 
@@ -530,6 +553,10 @@ def test_slab_major_layout_is_the_dense_result_rearranged(ctx, dt, cd, inc):
     r = O.keff_pipeline(q[4], dA, lat, N, lon=lon, increase=inc, lt=True, dtype=cd)
     assert np.array_equal(blk[4, 0], r['ctr'].astype(np.float64)) and np.array_equal(got['counts'][4].astype(np.int64), r['counts'])
     assert rel(blk[4, 1], r['area']) < TIGHT and rel(blk[4, 3], r['latEq']) < RTOL
+    block = {k: blk[:, i, :] for i, k in enumerate(OUT_NAMES)}
+    block.update({k: got[k] for k in got if k.endswith('_eq')})
+    for s in range(S):
+        check_epilogue(block, s, tbl, lat, pre, cd, what='slab %d' % s)
     dense.free(); sm.free()
 
 
@@ -712,7 +739,7 @@ def test_one_slab_alone_equals_the_same_slab_in_a_stack(ctx, dt, counts, single)
         r = O.keff_pipeline(q[s], dA, lat, N, lon=lon, increase=True, lt=True, dtype=dt)
         if not counts:
             got['counts'] = r['counts'][None]                  # (not produced: nothing to compare)
-        check_nine(got, 0, r)
+        check_nine(got, 0, r, tbl=tbl, tbl_coord=lat)
     one.free(); stack.free()
 
 

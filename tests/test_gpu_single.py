@@ -13,7 +13,7 @@ import pytest
 
 import xcontour_oracle as O
 from test_gpu_parity import rel, RTOL, TIGHT, LMIN_FLOOR
-from gpu_common import NINE, ROOT, check_nine, _clean_env
+from gpu_common import NINE, ROOT, check_epilogue, check_nine, _clean_env
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +41,9 @@ def _close(x, y, tol=1e-13):
     return bool(np.abs(x[m] - y[m]).max() <= tol * max(scale, 1e-300))
 
 
-def _same(a, b, counts=True, tol=1e-13):
+def _same(a, b, counts=True, tol=1e-13, epi=None):
+    """`epi`: check_epilogue's arguments after the slab (table, coordinates, preY, contour dtype[, nkeff mask]) -- the epilogue of
+    both paths, stage by stage on each path's own sums, slab by slab"""
     assert np.array_equal(a['status'], b['status'])
     assert np.array_equal(a['ctr'], b['ctr'], equal_nan=True)
     if counts:
@@ -51,6 +53,11 @@ def _same(a, b, counts=True, tol=1e-13):
     for k in NINE[3:]:
         x, y = a[k], b[k]
         assert np.array_equal(np.isnan(x), np.isnan(y)), k
+    if epi is not None:
+        for s in range(len(a['status'])):
+            if a['status'][s] != 2:                                    # (2: the single-read kernel gave up, nothing of it is valid)
+                check_epilogue(a, s, *epi, what='single-read slab %d' % s)
+                check_epilogue(b, s, *epi, what='chain slab %d' % s)
 
 
 @pytest.mark.parametrize('dt', [np.float64, np.float32])
@@ -73,7 +80,7 @@ def test_cfg2_slab_single_read_against_the_oracle(ctx, dt):
         assert ctx.last_keff_path() == 1
         got = p.fetch()
         assert p.replays == 0 and not got['status'].any()
-        check_nine(got, 0, r, with_eq=True)
+        check_nine(got, 0, r, with_eq=True, tbl=tbl, tbl_coord=lat, preY=lat[::50])
         assert int(got['counts'][0].sum()) == ny * nx - (dt == np.float32)     # (float32 levels: max + 1e-8 == max, the max cell falls on the open last edge)
         if first is None:
             first = got
@@ -138,7 +145,7 @@ def test_single_read_equals_the_chain(ctx, case, nslab):
     a.run(); pa = ctx.last_keff_path(); ra = a.fetch()
     b.run(); pb = ctx.last_keff_path(); rb = b.fetch()
     assert (pa, pb) == (1, 0) and a.replays == 0
-    _same(ra, rb, counts=counts)
+    _same(ra, rb, counts=counts, epi=(tbl, lat, None, cdt or dt))
     if mode in ('plane', 'row') and kw.get('periodic_x', True):
         r = O.keff_pipeline(q[0], dA_tbl, lat, N, lon=lon, increase=inc, lt=kw.get('lt', True), dtype=np.dtype(cdt or dt).type,
                             right_edge=kw.get('right_edge', 'xhistogram'))
@@ -277,6 +284,7 @@ def test_facade_keff_takes_the_single_read_kernel(ctx, baro):
     assert np.array_equal(ds['ctr'].values, r['ctr'].astype(np.float64))
     for k in ('area', 'intgrdS', 'latEq'):
         assert np.allclose(ds[k].values, r[k], rtol=1e-6, atol=0, equal_nan=True), k
+    check_epilogue({k: ds[k].values[None] for k in NINE}, 0, table._table.values, table._coord, None, np.float32)   # the reference's default contour dtype
 
 
 def test_single_read_fuzz_against_the_chain(ctx):
@@ -308,8 +316,11 @@ def test_single_read_fuzz_against_the_chain(ctx):
         elif mode == 3:
             dA = None
         tbl = table_from_rowsums(ctx.rowsum(None, cell_area(lat, lon), ny, nx), True, last_row_included(lat))
-        a = KeffPlan(ctx, 1, ny, nx, N, dt, cdt, dA=dA, lat=lat, lon=lon, tbl=tbl, tbl_coord=lat, single_read=True, **kw)
-        b = KeffPlan(ctx, 1, ny, nx, N, dt, cdt, dA=dA, lat=lat, lon=lon, tbl=tbl, tbl_coord=lat, single_read=False, **kw)
+        # every third case interpolates to latitudes taken from `lat` (no draw from rng: the cases stay what they were) -- a few
+        # hundred, some past the poles of latEq, some on its nodes -- more than 256 of them take the 1024-thread workgroup
+        pre = None if case % 3 else np.concatenate([lat[::1 + case % 4], [-90.0, 90.0, 0.0]])
+        a = KeffPlan(ctx, 1, ny, nx, N, dt, cdt, dA=dA, lat=lat, lon=lon, tbl=tbl, tbl_coord=lat, single_read=True, preY=pre, **kw)
+        b = KeffPlan(ctx, 1, ny, nx, N, dt, cdt, dA=dA, lat=lat, lon=lon, tbl=tbl, tbl_coord=lat, single_read=False, preY=pre, **kw)
         a.synth(lat, lon, 1000 + case, int(rng.integers(3)))
         q = a.download_q()
         if rng.random() < 0.5:
@@ -333,6 +344,9 @@ def test_single_read_fuzz_against_the_chain(ctx):
             assert _close(x, y), (tag, k)
         for k in NINE[3:]:
             assert np.array_equal(np.isnan(ra[k]), np.isnan(rb[k])), (tag, k)
+        if ra['status'][0] != 2:
+            check_epilogue(ra, 0, tbl, lat, pre, cdt, what='single-read %r' % (tag,))
+        check_epilogue(rb, 0, tbl, lat, pre, cdt, what='chain %r' % (tag,))
         a.free(); b.free()
     assert taken >= 110                                               # (nearly every case fits the register tiles)
 

@@ -295,3 +295,58 @@ def test_deterministic_bin_sums_rule():
     assert O.deterministic_bin_sums(np.ones(1000, dtype=int), vals, 1)[0] == float(exact)          # = the exact sum of the rounded weights, rounded once
     lost = O.deterministic_bin_sums(np.ones(2, dtype=int), np.array([1.0, 2.0 ** -60]), 1, top=O.det_window_top(1.0), nlimb=1)
     assert lost[0] == 1.0                                                                          # one limb: 2^-60 lies under the window
+
+
+@pytest.mark.parametrize('name', sorted(f for f in os.listdir(GOLD) if f.startswith('baro_keff_') and f.endswith('.npz')))
+def test_keff_epilogue_reproduces_the_golden_epilogue(baro, name):
+    """keff_epilogue (steps 5-10 on their own) applied to a fixture's own levels, sums and table gives its derived and
+    '_eq' vectors bit for bit (the fixtures were made with preLats = lat)"""
+    from gpu_common import same_bits
+    d = np.load(os.path.join(GOLD, name))
+    lat = baro[1]
+    assert d['ctr'].dtype == np.float32                     # np.gradient of the levels in float32 (make_golden.py)
+    e = O.keff_epilogue(d['ctr'], d['area'], d['intgrdS'], d['tbl'], d['tbl_coord'], preLats=lat)
+    for k in ('latEq', 'Lmin', 'dintSdA', 'dqdA', 'Leq2', 'nkeff'):
+        same_bits(e[k], d[k], k)
+    for k in O.EQ_NAMES:
+        same_bits(e[k + '_eq'], d[k + '_eq'], k + '_eq')
+    assert set(e) == {k for k in d.files if k not in ('ctr', 'counts', 'area', 'intgrdS', 'tbl', 'tbl_coord')}
+
+
+def test_cdf_from_pdf_and_level_order():
+    """the PDF -> CDF tail of histogram_cdf and the reversal of its a4 caller, on their own"""
+    p = np.array([1.0, 2.0 ** -60, 3.0, 0.0, 5.0])
+    assert np.array_equal(O.cdf_from_pdf(p, True), np.cumsum(p))
+    assert np.array_equal(O.cdf_from_pdf(p, False), np.cumsum(p)[-1] - np.cumsum(p))
+    assert np.array_equal(O.level_order(p, True), p) and np.array_equal(O.level_order(p, False), p[::-1])
+    q = np.linspace(0, 1, 64).reshape(8, 8) ** 2
+    for lt in (True, False):
+        for ctr in (np.linspace(0.1, 0.9, 5), np.linspace(0.9, 0.1, 5)):
+            cdf, pdf, _, binc = O.histogram_cdf(q, ctr, np.ones_like(q), lt)
+            assert np.array_equal(cdf, O.cdf_from_pdf(pdf, lt))
+            assert np.array_equal(O.cal_integral_within_contours_hist(q, ctr, np.ones_like(q), None, lt),
+                                  O.level_order(cdf, binc))
+
+
+def test_ulp_distance_and_same_bits():
+    from gpu_common import same_bits, ulp_distance
+    nan, inf, big = np.nan, np.inf, np.finfo(np.float64).max
+    tiny = np.finfo(np.float64).smallest_subnormal
+    a = np.array([1.0, 1.0, 0.0, 0.0, -0.0, tiny, -tiny, nan, nan, 1.0, inf, inf, -inf, big, -big, 2.0])
+    b = np.array([1.0, np.nextafter(1.0, 2.0), -0.0, tiny, tiny, -tiny, tiny, nan, 1.0, nan, inf, -inf, -big, inf, big,
+                  np.nextafter(np.nextafter(2.0, 0.0), 0.0)])
+    d = ulp_distance(a, b)
+    assert d.dtype == np.uint64
+    top = np.uint64(2 ** 64 - 1)
+    want = [0, 1, 0, 1, 1, 2, 2, 0, top, top, 0, 2 * 0x7ff0000000000000, 1, 1, 2 * 0x7fefffffffffffff, 2]
+    assert [int(x) for x in d] == [int(x) for x in want]
+    assert np.array_equal(d, ulp_distance(b, a))                             # symmetric
+    assert int(ulp_distance(1.0, 1.0 + 2 ** -52 * 5)) == 5 and int(ulp_distance(-1.0, -np.nextafter(1.0, 0.0))) == 1
+    same_bits(a, a.copy())
+    same_bits([nan, -0.0, inf], [-nan, -0.0, inf])                            # NaN payload / sign aside
+    for x, y in (([0.0], [-0.0]), ([nan], [1.0]), ([1.0], [nan]), ([inf], [-inf]), ([1.0], [np.nextafter(1.0, 2.0)]),
+                 ([inf], [big])):
+        with pytest.raises(AssertionError):
+            same_bits(x, y)
+    with pytest.raises(AssertionError, match=r'first at \[2\]'):
+        same_bits([1.0, 2.0, 3.0, 4.0], [1.0, 2.0, 3.5, 4.5], 'v')

@@ -43,6 +43,33 @@ __device__ __forceinline__ double interp_eval(double x, int j, const double* __r
     return r;
 }
 
+// numpy's binary_search_with_guess (the bracket np.interp takes, `guess` = its previous answer), for an xp that is NOT sorted (latEq
+// with NaN from a NaN sum): there the bracket depends on the guess, i.e. on the x before.  Returns j as interp_locate does except
+// n for the right (numpy's own code; the caller maps it).  x must not be NaN.
+__device__ __forceinline__ int interp_locate_guess(double x, const double* __restrict__ xp, int n, int rev, int guess)
+{
+    auto X = [&](int i) { return rev ? xp[n - 1 - i] : xp[i]; };
+    constexpr int kCache = 8;                                  // LIKELY_IN_CACHE_SIZE
+    int imin = 0, imax = n;
+    if (x > X(n - 1)) return n;
+    if (x < X(0)) return -1;
+    if (n <= 4) { int i = 1; while (i < n && x >= X(i)) ++i; return i - 1; }
+    if (guess > n - 3) guess = n - 3;
+    if (guess < 1) guess = 1;
+    if (x < X(guess)) {
+        if (!(x < X(guess - 1))) return guess - 1;
+        imax = guess - 1;
+        if (guess > kCache && x >= X(guess - kCache)) imin = guess - kCache;
+    } else {
+        if (x < X(guess + 1)) return guess;
+        if (x < X(guess + 2)) return guess + 1;
+        imin = guess + 2;
+        if (guess < n - kCache - 1 && x < X(guess + kCache)) imax = guess + kCache;
+    }
+    while (imin < imax) { const int imid = imin + ((imax - imin) >> 1); if (x >= X(imid)) imin = imid + 1; else imax = imid; }
+    return imin - 1;
+}
+
 // np.gradient(f, uniform unit spacing, edge_order=1) at index k, f64
 __device__ __forceinline__ double grad_f64(const double* f, int k, int N)
 {
@@ -251,24 +278,40 @@ __device__ __forceinline__ void finalize_body(const FinalArgs& a, const int slab
     }
     __syncthreads();
     dstamp(3);
+    // interp_to_coords (core.py:1050-1100): direction from latEq[0] < latEq[-1]
+    const int rev = !(s_lat[0] < s_lat[N - 1]);
+    int unsorted = 0;                                                              // latEq out of order (NaN) in that direction
     for (int k = tid; k < N; k += nthr) {
         double nk = __ddiv_rn(__ddiv_rn(s_leq[k], s_lmin[k]), s_lmin[k]);         // core.py:963
         if (!(nk < a.nkeff_mask)) nk = dnan();                                    // core.py:964
         s_nk[k] = nk;
         if (a.o_nkeff) a.o_nkeff[(size_t)slab * a.vstride + k] = nk;
+        if (k + 1 < N && !(rev ? s_lat[k] >= s_lat[k + 1] : s_lat[k] <= s_lat[k + 1])) unsorted = 1;
     }
     dstamp(4);
     if (a.o_interp && a.npre > 0) {
         __syncthreads();
-        // interp_to_coords (core.py:1050-1100): direction from latEq[0] < latEq[-1]
-        const int rev = !(s_lat[0] < s_lat[N - 1]);
         const double* vars[9] = {s_ctr, area, intS, s_lat, s_dS, s_dq, s_leq, s_lmin, s_nk};
-        for (int p = tid; p < a.npre; p += nthr) {
-            const double x = a.preY[p];
-            const int j = interp_locate(x, s_lat, N, rev);        // one search shared by the 9 variables
+        if (!__syncthreads_or(unsorted)) {
+            // sorted latEq: np.interp's bracket is unique, every preY on its own
+            for (int p = tid; p < a.npre; p += nthr) {
+                const double x = a.preY[p];
+                const int j = interp_locate(x, s_lat, N, rev);        // one search shared by the 9 variables
 #pragma unroll
-            for (int v = 0; v < 9; ++v)
-                a.o_interp[((size_t)slab * 9 + v) * a.npre + p] = interp_eval(x, j, s_lat, vars[v], N, rev);
+                for (int v = 0; v < 9; ++v)
+                    a.o_interp[((size_t)slab * 9 + v) * a.npre + p] = interp_eval(x, j, s_lat, vars[v], N, rev);
+            }
+        } else if (tid == 0) {
+            // unsorted: numpy's bracket depends on the one of the x before (arr_interp passes it on as the guess; a NaN x
+            // leaves it): one thread walks preY in numpy's order
+            int g = 0;
+            for (int p = 0; p < a.npre; ++p) {
+                const double x = a.preY[p];
+                int j = -3;
+                if (x == x) { g = interp_locate_guess(x, s_lat, N, rev, g); j = g == N ? -2 : g; }
+                for (int v = 0; v < 9; ++v)
+                    a.o_interp[((size_t)slab * 9 + v) * a.npre + p] = interp_eval(x, j, s_lat, vars[v], N, rev);
+            }
         }
     }
 }
