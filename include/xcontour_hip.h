@@ -415,6 +415,17 @@ int xc_keff_epilogue(xc_ctx* ctx, const double* pdf, const double* ctr, int ctr_
  * Enable with xc_set_kernel_timing(ctx, 1); xc_last_hist_ms waits for the launch.     */
 int xc_set_kernel_timing(xc_ctx* ctx, int enable);
 int xc_last_hist_ms(xc_ctx* ctx, float* out_ms);
+/* which histogram kernel the last xc_hist / xc_hist_dev / xc_keff_dev call launched: its template arguments and its launch geometry, as
+ * the launcher chose them on the host.  All zero when the last such call failed.                                                        */
+typedef struct xc_hist_variant {
+    int32_t kernel;     /* 0 none, 1 K3 (k_hist), 2 K3 with deterministic sums (k_hist, DET = 3), 3 K3S (k_keff_single, the single-read kernel) */
+    int32_t q_dtype;    /* XC_F32 / XC_F64 */
+    int32_t vec, nint, grad, da2d, next, fast, e32, det, wcnt;   /* template arguments (K3S: vec 2, grad 1, wcnt = counts wanted) */
+    int32_t threads, ncopy, nstrip;                              /* both kernels: threads per block, LDS histogram copies, column strips */
+    int32_t bps, xcd_map, nchunk;                                /* K3: blocks per slab, XCD-aware block order, row chunks of the strip-fastest order (0: off) */
+    int32_t G, cps, rpc;                                         /* K3S: workgroups, chunks per strip, rows per chunk */
+} xc_hist_variant;
+int xc_last_hist_variant(xc_ctx* ctx, xc_hist_variant* out);
 /* One-shot: record the caller's events (from xc_event_create) immediately before and after
  * the NEXT histogram launch instead of the context's own pair -- lets a benchmark time every
  * launch of a timed region without synchronising inside it.                              */

@@ -53,6 +53,15 @@ class CommInfo(C.Structure):
                 ('rccl_version', _i32), ('reserved0', _i32), ('rccl_path', C.c_char * 256)]
 
 
+class HistVariant(C.Structure):
+    """xc_hist_variant: the histogram instantiation and geometry the last xc_hist / xc_keff_dev call launched"""
+    _fields_ = [(n, _i32) for n in ('kernel', 'q_dtype', 'vec', 'nint', 'grad', 'da2d', 'next', 'fast', 'e32', 'det', 'wcnt',
+                                    'threads', 'ncopy', 'nstrip', 'bps', 'xcd_map', 'nchunk', 'G', 'cps', 'rpc')]
+
+
+HIST_KERNELS = {0: None, 1: 'K3', 2: 'K3-det', 3: 'K3S'}
+
+
 class KeffDesc(C.Structure):
     """struct xc_keff_desc (include/xcontour_hip.h)"""
     _fields_ = [
@@ -144,6 +153,7 @@ PROTOTYPES = {
     'xc_host_edges_from_levels': (C.c_int, [_vp, C.c_int, _i64, _i64, C.c_int, _vp, C.POINTER(C.c_int)]),
     'xc_set_kernel_timing': (C.c_int, [_vp, C.c_int]),
     'xc_last_hist_ms': (C.c_int, [_vp, C.POINTER(C.c_float)]),
+    'xc_last_hist_variant': (C.c_int, [_vp, C.POINTER(HistVariant)]),
     'xc_set_hist_events': (C.c_int, [_vp, _vp, _vp]),
     'xc_comm_unique_id': (C.c_int, [_vp, _vp]),
     'xc_comm_init': (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -426,6 +436,16 @@ class Context(object):
         p = C.c_int()
         self._check(self.lib.xc_last_keff_path(self.handle, C.byref(p)))
         return p.value
+
+    def last_hist_variant(self):
+        """the histogram kernel of the last hist / keff call and how it was launched (xc_last_hist_variant): a dict of the record's
+        fields, 'kernel' named ('K3', 'K3-det', 'K3S'; None after a failed call) and 'q_dtype' a numpy dtype"""
+        v = HistVariant()
+        self._check(self.lib.xc_last_hist_variant(self.handle, C.byref(v)))
+        out = {f[0]: getattr(v, f[0]) for f in HistVariant._fields_}
+        out['kernel'] = HIST_KERNELS[out['kernel']]
+        out['q_dtype'] = np.dtype(np.float32 if out['q_dtype'] == XC_F32 else np.float64) if out['kernel'] else None
+        return out
 
     def single_stamps(self, enable=True):
         """diagnostics: (device pointer, slots) of the single-read kernel's phase stamps; enable=False frees them"""

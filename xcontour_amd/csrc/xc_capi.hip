@@ -834,9 +834,15 @@ static int det_one_pass(xc_ctx* ctx, int q_dtype, int nint, int grad, const Hist
     return XC_OK;
 }
 
-int xc_hist_dev(xc_ctx* ctx, const xc_hist_desc* d)
+// xc_last_hist_variant: launch_three / launch_s4 write the record where they launch; a call that fails leaves it cleared
+static int hist_recorded(xc_ctx* ctx, int rc)
 {
-    XC_CTX(ctx);
+    if (rc != XC_OK && ctx) ctx->last_hist = xc_hist_variant{};
+    return rc;
+}
+
+static int hist_dev(xc_ctx* ctx, const xc_hist_desc* d)
+{
     XC_TRY(check_hist_desc(ctx, d));
     const int nbin = (int)(d->nedge - 1), nch = 1 + d->nint + (d->grad ? 1 : 0);
     HistGeom g;
@@ -876,9 +882,15 @@ int xc_hist_dev(xc_ctx* ctx, const xc_hist_desc* d)
     return launch_finalize(ctx, d->nslab, f);
 }
 
-int xc_hist(xc_ctx* ctx, const xc_hist_desc* hd)
+int xc_hist_dev(xc_ctx* ctx, const xc_hist_desc* d)
 {
     XC_CTX(ctx);
+    ctx->last_hist = xc_hist_variant{};
+    return hist_recorded(ctx, hist_dev(ctx, d));
+}
+
+static int hist_host(xc_ctx* ctx, const xc_hist_desc* hd)
+{
     XC_TRY(check_hist_desc(ctx, hd));
     const int64_t S = hd->nslab, ny = hd->ny, nx = hd->nx, ne = hd->nedge;
     const int nbin = (int)(ne - 1), nch = 1 + hd->nint + (hd->grad ? 1 : 0);
@@ -923,6 +935,13 @@ int xc_hist(xc_ctx* ctx, const xc_hist_desc* hd)
     if (hd->cdf && !pcd) XC_TRY(d2h(ctx, hd->cdf, d.cdf, pb));
     if (hd->counts && !pn) XC_TRY(d2h(ctx, hd->counts, d.counts, cb));
     return xc_sync(ctx);
+}
+
+int xc_hist(xc_ctx* ctx, const xc_hist_desc* hd)
+{
+    XC_CTX(ctx);
+    ctx->last_hist = xc_hist_variant{};
+    return hist_recorded(ctx, hist_host(ctx, hd));
 }
 
 // ------------------------------------------------------------------------------------ K2
@@ -1320,9 +1339,24 @@ int xc_dbg_single_stamps(xc_ctx* ctx, int enable, void** out_dev, int* out_slots
     return XC_OK;
 }
 
+int xc_last_hist_variant(xc_ctx* ctx, xc_hist_variant* out)
+{
+    if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_hist_variant: bad arguments");
+    *out = ctx->last_hist;
+    return XC_OK;
+}
+
+static int keff_dev(xc_ctx* ctx, const xc_keff_desc* d);
+
 int xc_keff_dev(xc_ctx* ctx, const xc_keff_desc* d)
 {
     XC_CTX(ctx);
+    ctx->last_hist = xc_hist_variant{};
+    return hist_recorded(ctx, keff_dev(ctx, d));
+}
+
+static int keff_dev(xc_ctx* ctx, const xc_keff_desc* d)
+{
     if (!d) return fail(ctx, XC_EBADARG, "xc_keff: desc is NULL");
     if (!d->q || !d->ctr || !d->area || !d->tbl || !d->tbl_coord) return fail(ctx, XC_EBADARG, "xc_keff: q/ctr/area/tbl/tbl_coord must be given");
     if (d->q_dtype != XC_F32 && d->q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_keff: bad q_dtype");

@@ -637,6 +637,13 @@ int launch_three(xc_ctx* ctx, const HistGeom& g, int64_t nslab, const HistArgs& 
     }
     const int64_t nblk = b.xcd_map ? (int64_t)8 * ((g.bps + 7) / 8) * nslab : (int64_t)g.bps * nslab;
     if (nblk > 0x7fffffff) return fail(ctx, XC_EBADARG, "xc_hist: grid too large");
+    {
+        xc_hist_variant& v = ctx->last_hist;                       // (xc_last_hist_variant)
+        v = xc_hist_variant{};
+        v.kernel = DET == 3 ? 2 : 1; v.q_dtype = std::is_same<TQ, float>::value ? XC_F32 : XC_F64;
+        v.vec = VEC; v.nint = NINT; v.grad = GRAD; v.da2d = DA2D; v.next = NEXT; v.fast = FAST; v.e32 = E32; v.det = DET;
+        v.threads = g.threads; v.ncopy = g.ncopy; v.nstrip = g.nstrip; v.bps = g.bps; v.xcd_map = b.xcd_map; v.nchunk = b.nchunk;
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(g.threads), g.lds, ctx->stream, b);
     XC_HIP(ctx, hipGetLastError());
     return XC_OK;

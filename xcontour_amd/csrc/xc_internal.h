@@ -92,6 +92,7 @@ struct xc_ctx {
     // and clears what launch n - 1 left in the other one (the kernel boundary orders the two), so no memset launch sits in the chain
     void* single_ws = nullptr;  unsigned single_launches = 0;  int single_dirty_bins[2] = {0, 0};
     int last_keff_path = 0;     // last xc_keff_dev call: 0 min/max pass + histogram pass (two reads of the tracer), 1 the single-read kernel
+    xc_hist_variant last_hist = {};   // last xc_hist(_dev) / xc_keff_dev call: the histogram instantiation and geometry launched (launch_three, launch_s4)
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 

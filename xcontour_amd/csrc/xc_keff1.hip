@@ -417,6 +417,13 @@ int launch_s4(xc_ctx* ctx, const SingleArgs& a, const SingleGeom& g)
 {
     auto kern = k_keff_single<TQ, DA2D, FAST, WCNT>;
     { const int rc = ensure_big_lds(ctx, reinterpret_cast<const void*>(kern), (int)kLdsBudget + 4096); if (rc != XC_OK) return rc; }
+    {
+        xc_hist_variant& v = ctx->last_hist;                       // (xc_last_hist_variant)
+        v = xc_hist_variant{};
+        v.kernel = 3; v.q_dtype = std::is_same<TQ, float>::value ? XC_F32 : XC_F64;
+        v.vec = 2; v.grad = 1; v.da2d = DA2D; v.fast = FAST; v.wcnt = WCNT;
+        v.threads = NT; v.ncopy = g.ncopy; v.nstrip = g.nstrip; v.G = g.G; v.cps = g.cps; v.rpc = g.rpc;
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)g.G), dim3(NT), g.lds, ctx->stream, a);
     XC_HIP(ctx, hipGetLastError());
     return XC_OK;
