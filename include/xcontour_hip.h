@@ -323,6 +323,32 @@ int xc_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t 
                 const void* area, int area_dtype, int area_per_slab, int stride, int full_width,
                 double* out_len, uint64_t* out_cnt);
 
+/* ------------------------------------------------------------------ K10 marching-squares contour lengths
+ * Replaces Contour2D.cal_contour_lengths (core.py:969-1014), _contour_lengths (core.py:1437-1487) and
+ * utils.contour_length / __segment_length_latlon / __segment_length_cartesian / __geodist (utils.py:565-761):
+ * the total length of every contour traced by skimage's find_contours(slab, c) (defaults), for ALL contours
+ * of a slab in one pass.  Rows are ycoord (ny), columns xcoord (nx); no wrap across the X seam.
+ *   a cell with a NaN corner contributes nothing; case = (ul>c) + 2(ur>c) + 4(ll>c) + 8(lr>c);
+ *   saddles 6 and 9 pair their points like fully_connected='low'; a segment whose two end points are
+ *   equal is dropped; end points map to coordinates like np.interp(x, arange(n), coord).
+ *   radius > 0: coordinates in radians, segment = haversine (__geodist), total * radius;
+ *   radius == 0: Cartesian, segment = hypot(dx, dy).
+ *   out_len[slab][k]  = total length, NaN where the total is 0 (utils.py:603-604): a level outside the
+ *                       field's range, at its minimum or maximum;
+ *   out_nseg[slab][k] = number of segments (exact; may be NULL).
+ * Totals are bit-reproducible (fixed-point sums, independent of launch geometry and slabs per call).
+ * contours: double[ncont] or double[nslab][ncont] (contours_per_slab), ASCENDING, no NaN (the host entry
+ * point checks; callers with other orders sort and un-permute).  Coordinates must be finite (checked by
+ * the host entry point).  Any ncont is accepted.                                                  */
+int xc_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                           const double* ycoord, const double* xcoord, double radius,
+                           const double* contours, int ncont, int contours_per_slab,
+                           double* out_len, uint64_t* out_nseg);
+int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                       const double* ycoord, const double* xcoord, double radius,
+                       const double* contours, int ncont, int contours_per_slab,
+                       double* out_len, uint64_t* out_nseg);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -1,0 +1,93 @@
+"""numpy restatement of the contour-length rule of K10 (xc_clen.hip) -- a helper for the tests, no tests here.
+
+skimage's find_contours(image, level) with its defaults, restated (build-defined: skimage is not a dependency):
+float64 arithmetic; a cell with a NaN corner emits nothing; case = (ul>c) + 2 (ur>c) + 4 (ll>c) + 8 (lr>c), 0 and 15
+emit nothing; frac(a, b) = 0 if a == b else (c - a) / (b - a); edge points top (r0, c0 + frac(ul, ur)), bottom
+(r0+1, c0 + frac(ll, lr)), left (r0 + frac(ul, ll), c0), right (r0 + frac(ur, lr), c0+1); saddles 6 and 9 pair like
+fully_connected='low'; a segment with two equal end points is dropped.  End points map through np.interp onto the
+coordinates; lengths are haversine (reference utils.__geodist) or hypot; a total of 0 is NaN (utils.py:603-604).
+"""
+import numpy as np
+
+RADIUS = 6371200.0
+
+T, B, L, R = 0, 1, 2, 3
+# case -> the segments' end point ids (skimage _get_contour_segments, fully_connected='low')
+PAIRS = {1: [(T, L)], 2: [(R, T)], 3: [(R, L)], 4: [(L, B)], 5: [(T, B)], 6: [(R, T), (L, B)], 7: [(R, B)],
+         8: [(B, R)], 9: [(T, L), (B, R)], 10: [(B, T)], 11: [(B, L)], 12: [(L, R)], 13: [(T, R)], 14: [(L, T)]}
+PAIRS_HIGH = dict(PAIRS)
+PAIRS_HIGH.update({6: [(L, T), (R, B)], 9: [(T, R), (B, L)]})
+
+
+def _frac(a, b, c):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(a == b, 0.0, (c - a) / np.where(a == b, 1.0, b - a))
+
+
+def segments(q, c, pairs=PAIRS):
+    """index-space segments of level c on the 2-D field q: (r1, c1, r2, c2) arrays, degenerate ones dropped"""
+    q = np.asarray(q, dtype=np.float64)
+    c = float(c)
+    ul, ur, ll, lr = q[:-1, :-1], q[:-1, 1:], q[1:, :-1], q[1:, 1:]
+    with np.errstate(invalid='ignore'):
+        mn = np.fmin(np.fmin(ul, ur), np.fmin(ll, lr))
+        mx = np.fmax(np.fmax(ul, ur), np.fmax(ll, lr))
+        sel = (mn <= c) & (c < mx) & ~(np.isnan(ul) | np.isnan(ur) | np.isnan(ll) | np.isnan(lr))
+    r0, c0 = np.nonzero(sel)
+    a, b, d, e = ul[sel], ur[sel], ll[sel], lr[sel]
+    case = (a > c) * 1 + (b > c) * 2 + (d > c) * 4 + (e > c) * 8
+    r0f, c0f = r0.astype(np.float64), c0.astype(np.float64)
+    pts = {T: (r0f, c0f + _frac(a, b, c)), B: (r0f + 1.0, c0f + _frac(d, e, c)),
+           L: (r0f + _frac(a, d, c), c0f), R: (r0f + _frac(b, e, c), c0f + 1.0)}
+    out = [[], [], [], []]
+    for cs, prs in pairs.items():
+        m = case == cs
+        if not m.any():
+            continue
+        for p, s in prs:
+            out[0].append(pts[p][0][m]); out[1].append(pts[p][1][m])
+            out[2].append(pts[s][0][m]); out[3].append(pts[s][1][m])
+    if not out[0]:
+        return tuple(np.zeros(0) for _ in range(4))
+    r1, c1, r2, c2 = (np.concatenate(v) for v in out)
+    keep = ~((r1 == r2) & (c1 == c2))
+    return r1[keep], c1[keep], r2[keep], c2[keep]
+
+
+def haversine(x1, y1, x2, y2):
+    """utils.__geodist, in its operation order (radians; unit sphere)"""
+    dlon = x2 - x1
+    dlat = y2 - y1
+    a = np.sin(dlat / 2.0) ** 2.0 + np.cos(y1) * np.cos(y2) * np.sin(dlon / 2) ** 2.0
+    return 2.0 * np.arcsin(np.sqrt(a))
+
+
+def segment_lengths(q, c, ycoord, xcoord, latlon, pairs=PAIRS):
+    r1, c1, r2, c2 = segments(q, c, pairs)
+    yi, xi = np.arange(len(ycoord)), np.arange(len(xcoord))
+    y1, y2 = np.interp(r1, yi, ycoord), np.interp(r2, yi, ycoord)
+    x1, x2 = np.interp(c1, xi, xcoord), np.interp(c2, xi, xcoord)
+    return haversine(x1, y1, x2, y2) if latlon else np.hypot(x1 - x2, y1 - y2)
+
+
+def contour_lengths(q2d, levels, ycoord, xcoord, latlon=False, pairs=PAIRS):
+    """-> (totals f64 (N,), segment counts int64 (N,)) for one slab; ycoord / xcoord: float64 coordinate arrays (radians when
+    latlon), i.e. what the library receives"""
+    tot = np.empty(len(levels)); cnt = np.zeros(len(levels), dtype=np.int64)
+    for k, c in enumerate(levels):
+        if np.isnan(c):
+            tot[k] = np.nan
+            continue
+        s = segment_lengths(q2d, c, ycoord, xcoord, latlon, pairs)
+        cnt[k] = s.size
+        t = float(np.sum(s))
+        tot[k] = np.nan if t == 0 else (t * RADIUS if latlon else t)
+    return tot, cnt
+
+
+def plane_coords(ycoord, xcoord, latlon):
+    """the float64 coordinate arrays the facade builds (reference core.py:1003-1004: float32 first, then radians in float32)"""
+    y, x = np.asarray(ycoord).astype(np.float32), np.asarray(xcoord).astype(np.float32)
+    if latlon:
+        y, x = np.deg2rad(y), np.deg2rad(x)
+    return y.astype(np.float64), x.astype(np.float64)

@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""K10 timing: xc_contour_lengths_dev on synthetic 3600 x 1801 float64 slabs made on the device (xc_synth_dev variant 0:
+PV-like, 1: pure noise), N levels from the field's range, lat / lon in radians.  Prints the event time per call; run it under
+`rocprofv3 --kernel-trace --stats -- python tools/clen_time.py ...` for the per-kernel times.
+
+    python tools/clen_time.py --slabs 64 --variant 0 --ncont 121 --reps 5
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--slabs', type=int, default=1)
+    ap.add_argument('--variant', type=int, default=0)
+    ap.add_argument('--ncont', type=int, default=121)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--ny', type=int, default=1801)
+    ap.add_argument('--nx', type=int, default=3600)
+    a = ap.parse_args()
+    from xcontour_amd import _native as nat
+    ctx = nat.Context(0)
+    S, ny, nx = a.slabs, a.ny, a.nx
+    lat = np.linspace(-90.0, 90.0, ny)
+    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
+    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
+    q = ctx.alloc(S * ny * nx * 8)
+    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
+    mm = ctx.minmax(q.download((1, ny * nx), np.float64))[0]
+    lv = np.linspace(mm[0], mm[1], a.ncont)
+    y = np.deg2rad(lat.astype(np.float32)).astype(np.float64)
+    x = np.deg2rad(lon.astype(np.float32)).astype(np.float64)
+    dy, dx, dc = ctx.to_device(y), ctx.to_device(x), ctx.to_device(lv)
+    out, cnt = ctx.alloc(S * a.ncont * 8), ctx.alloc(S * a.ncont * 8)
+
+    def call():
+        ctx._check(ctx.lib.xc_contour_lengths_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, 6371200.0,
+                                                  dc.ptr, a.ncont, 0, out.ptr, cnt.ptr))
+    call()
+    ctx.sync()
+    e0, e1 = ctx.event(), ctx.event()
+    ctx.record(e0)
+    for _ in range(a.reps):
+        call()
+    ctx.record(e1)
+    ctx.sync()
+    ms = ctx.elapsed_ms(e0, e1) / a.reps
+    n = cnt.download((S, a.ncont), np.uint64)
+    cells = S * (ny - 1) * (nx - 1)
+    print('slabs %d variant %d ncont %d: %.1f us per call, %.2f us per slab, %.2f segments per cell, %.0f GB/s of tracer'
+          % (S, a.variant, a.ncont, ms * 1e3, ms * 1e3 / S, float(n.sum()) / cells, S * ny * nx * 8 / (ms * 1e-3) / 1e9))
+    ctx.close()
+
+
+if __name__ == '__main__':
+    main()

@@ -131,6 +131,8 @@ PROTOTYPES = {
                                   _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'xc_crossing': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp, C.c_int, C.c_int,
                               _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    'xc_contour_lengths_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -797,6 +799,56 @@ class Context(object):
                                          PAD_MODES[pad_mode], _ptr(contours), N, 1 if per_slab else 0,
                                          _ptr(area), dtype_code(area.dtype), 1 if area.ndim == 3 else 0,
                                          int(stride), 1 if full_width else 0, _ptr(lens), _ptr(cnts)))
+        return lens, cnts
+
+    def contour_lengths(self, q, contours, ycoord, xcoord, radius=0.0):
+        """Marching-squares contour lengths (xc_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours (N,) or
+        (nslab, N) ASCENDING f64; ycoord (ny,) / xcoord (nx,) the coordinates of rows / columns (radians when radius > 0).
+        radius > 0: great-circle lengths times radius; 0: Cartesian.  Returns (lengths f64 (nslab, N), NaN where the total is 0;
+        segment counts uint64 (nslab, N)).  A tracer with a device mirror (keep_resident) is read in place through the _dev
+        entry point."""
+        q = _stack_in(q)
+        if len(q.shape) != 3:
+            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
+        nslab, ny, nx = q.shape
+        contours = _contig(contours, np.float64)
+        per_slab = contours.ndim == 2
+        if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
+            raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
+        ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
+        if ycoord.shape != (ny,) or xcoord.shape != (nx,):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates of length (%d, %d) for a (%d, %d) plane'
+                                   % (ycoord.size, xcoord.size, ny, nx))
+        radius = float(radius)
+        N = contours.shape[-1]
+        bt = self._batches(nslab, ny * nx * q.dtype.itemsize)
+        if len(bt) > 1:
+            parts = [self.contour_lengths(q[s0:s1], contours[s0:s1] if per_slab else contours, ycoord, xcoord, radius)
+                     for s0, s1 in bt]
+            return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        q = _stack_now(q)
+        lens = np.empty((nslab, N), dtype=np.float64)
+        cnts = np.empty((nslab, N), dtype=np.uint64)
+        qp = self.resident_ptr(q) if isinstance(q, np.ndarray) and q.flags.c_contiguous else None
+        if qp:
+            # the tracer is on the device already: only the small arrays cross (the device entry point trusts its caller)
+            if np.isnan(contours).any() or (np.diff(contours, axis=-1) < 0).any():
+                raise XContourHipError(XC_EEDGES, 'xc_contour_lengths: contours must be ascending without NaN')
+            if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
+                raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
+            bufs = [self.to_device(ycoord), self.to_device(xcoord), self.to_device(contours),
+                    self.alloc(lens.nbytes), self.alloc(cnts.nbytes)]
+            try:
+                self._check(self.lib.xc_contour_lengths_dev(self.handle, qp, dtype_code(q.dtype), nslab, ny, nx, bufs[0].ptr,
+                                                            bufs[1].ptr, radius, bufs[2].ptr, N, 1 if per_slab else 0,
+                                                            bufs[3].ptr, bufs[4].ptr))
+                return bufs[3].download((nslab, N), np.float64), bufs[4].download((nslab, N), np.uint64)
+            finally:
+                for b in bufs:
+                    b.free()
+        self._check(self.lib.xc_contour_lengths(self.handle, _ptr(q), dtype_code(q.dtype), nslab, ny, nx, _ptr(ycoord),
+                                                _ptr(xcoord), radius, _ptr(contours), N, 1 if per_slab else 0,
+                                                _ptr(lens), _ptr(cnts)))
         return lens, cnts
 
     def lwa(self, q, Q, coord, dA, dA_max, M=None, increase=True, part=0, mask_idx=None, variant=0, exact=None):

@@ -682,6 +682,50 @@ class Contour2D(object):
             re.append(self._wrap_contour(out.astype(self.dtype), lead, lshape, coords, None, self.tracer, ccoord))
         return re if isiterable else re[0]
 
+    # ------------------------------------------------------------------ contour lengths
+    def cal_contour_lengths(self, contours, tracer=None, latlon=False):
+        """
+        Perimeter of every contour (reference core.py:969-1014, _contour_lengths 1437-1487 and
+        utils.contour_length 565-608): the total length of what skimage's find_contours(plane, c)
+        traces, one GPU pass per slab for all contours (K10, xc_contour_lengths).
+
+        `contours`: an int or list goes through cal_contours; a labelled array over (..., contour)
+        may differ per slab.  Rows are the equivalent dim and columns the other plane dim; their
+        coordinates are cast to float32 as the reference does (core.py:1003-1004) and, with
+        latlon=True, converted to radians in float32; segments are then great-circle arcs times
+        Rearth, else Cartesian distances.  A cell with a NaN corner contributes nothing, and
+        contours do not wrap across the X seam (skimage does neither).  A contour of total length 0
+        -- a level outside the field's range, at its minimum or maximum, or NaN -- gives NaN
+        (utils.py:603-604).  With latlon=True the latitude is the plane's real latitude whatever the
+        tracer's dim order (the reference would read longitude as latitude on an (X, Y) tracer).
+        Sums are bit-reproducible.  Returns (..., contour) in `self.dtype`.
+        """
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        data = self.tracer if tracer is None else tracer
+        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
+        for d in (self.dimEqV, self._xdim):
+            if d not in dcoords:
+                raise Exception('cal_contour_lengths needs coordinate values for the plane dim %s' % d)
+        fdef = []
+        for d in (self.dimEqV, self._xdim):
+            v = np.asarray(dcoords[d]).astype(np.float32)                      # core.py:1003-1004
+            fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
+        q, lead, lshape, coords = self._plane(data)
+        q = self._float(q)
+        nslab = q.shape[0]
+        b = np.array(self._contour_values(contours, nslab, list(lead), list(lshape)), dtype=np.float64)
+        b[np.isnan(b)] = np.inf                        # a NaN level crosses no cell
+        order = np.argsort(b, axis=1, kind='stable')
+        bs = np.take_along_axis(b, order, axis=1)
+        lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0)
+        out = np.empty_like(lens)
+        np.put_along_axis(out, order, lens, axis=1)
+        ccoord = lb.unwrap(contours, lazy=True)[2].get('contour') if lb.is_labeled(contours) else None
+        if ccoord is None:
+            ccoord = np.arange(b.shape[1]).astype(self.dtype)
+        return self._wrap_contour(out.astype(self.dtype), lead, lshape, coords, None, data, ccoord)
+
     # ------------------------------------------------------------------ local wave activity
     def cal_local_wave_activity(self, q, Q, mask_idx=None, part='all', metric=None, exact=None):
         """

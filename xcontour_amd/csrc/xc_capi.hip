@@ -1047,6 +1047,54 @@ int xc_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t 
     return xc_sync(ctx);
 }
 
+// ------------------------------------------------------------------------------------ K10
+int xc_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                           const double* ycoord, const double* xcoord, double radius,
+                           const double* contours, int ncont, int contours_per_slab,
+                           double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    return launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont, contours_per_slab,
+                                  out_len, out_nseg);
+}
+
+int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                       const double* ycoord, const double* xcoord, double radius,
+                       const double* contours, int ncont, int contours_per_slab,
+                       double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
+        return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad dtype");
+    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: radius must be >= 0");
+    for (int64_t i = 0; i < ny; ++i)
+        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
+    for (int64_t i = 0; i < nx; ++i)
+        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
+    const int64_t nc = contours_per_slab ? nslab : 1;
+    for (int64_t s = 0; s < nc; ++s)
+        for (int k = 0; k < ncont; ++k) {
+            const double c = contours[s * ncont + k];
+            if (c != c || (k > 0 && c < contours[s * ncont + k - 1]))
+                return fail(ctx, XC_EEDGES, "xc_contour_lengths: contours must be ascending without NaN");
+        }
+    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
+    const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + al(cb) + 2 * al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb); double* dc = (double*)st.take(cb);
+    double* dl = (double*)st.take(ob);
+    uint64_t* dn = out_nseg ? (uint64_t*)st.take(ob) : nullptr;
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, radius, dc, ncont, contours_per_slab, dl, dn));
+    XC_TRY(d2h(ctx, out_len, dl, ob));
+    if (out_nseg) XC_TRY(d2h(ctx, out_nseg, dn, ob));
+    return xc_sync(ctx);
+}
+
 // ------------------------------------------------------------------------------------ K7
 int xc_lwa_dev(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const double* coord,
                const double* dA, int dA_rank, double dA_max, const double* M, int M_rank,

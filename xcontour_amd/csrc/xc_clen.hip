@@ -1,0 +1,325 @@
+// K10 -- marching-squares contour lengths (gfx950).
+//
+// Replaces Contour2D.cal_contour_lengths (reference core.py:969-1014), its per-slab loop _contour_lengths (1437-1487) and
+// utils.contour_length / __segment_length_* / __geodist (utils.py:565-761), which trace every contour with skimage's
+// find_contours and walk the polylines.  What the method returns is the TOTAL length of each contour, and that total does not
+// depend on how segments are joined into polylines: it is a sum over grid cells of a function of the cell's four corners and
+// the level.  The rule (skimage find_contours(image, level) with its defaults, restated; build-defined, float64 throughout):
+//   cell (r0, c0): corners ul = q[r0][c0], ur = q[r0][c0+1], ll = q[r0+1][c0], lr = q[r0+1][c0+1]; a NaN corner: no segment;
+//   case = (ul > c) + 2 (ur > c) + 4 (ll > c) + 8 (lr > c); 0 and 15: no segment;
+//   frac(a, b) = a == b ? 0 : (c - a) / (b - a);  edge points (row, column):
+//     top (r0, c0 + frac(ul, ur))   bottom (r0+1, c0 + frac(ll, lr))   left (r0 + frac(ul, ll), c0)   right (r0 + frac(ur, lr), c0+1)
+//   one segment joining the two crossed edges, except the saddles (fully_connected='low'): 6 -> (right, top), (left, bottom);
+//   9 -> (top, left), (bottom, right).  A segment whose two points are equal is dropped (find_contours' assembly).
+//   A point maps to coordinates like np.interp(x, arange(n), fdef); the segment length is the haversine of __geodist
+//   (radius > 0, radian coordinates) or hypot (radius == 0); total == 0 -> NaN (utils.py:603-604), else total * radius.
+//
+// Mapping (like K9 at stride 1): tiles of 32 cell rows x 252 cell columns, 4 waves of 63 cells; lanes along X; every lane
+// loads ONE corner per row and takes its right neighbour from the next lane (DPP), carrying the previous row, so every tracer
+// row is read from HBM once per tile.  A NaN-free cell crosses exactly the levels with mn <= c < mx: the index range between
+// the two lower bounds (xc_levels.h).  Each crossed (cell, level) adds its 0..2 segment lengths.
+//
+// Sums are deterministic (independent of arrival order, block geometry and slabs per launch): every length is cut once to
+// 49 bits and added as two integer chunks to the limbs of a fixed-point accumulator per level (xc_binning.h det_split), on a
+// window fixed before the pass by a bound on one segment (pi on the unit sphere, else the largest cell diagonal, k_clen_window);
+// the blocks' limbs are carried and summed exactly and converted once (k_det3_reduce of xc_hist_det.hip).
+// Capacity: a limb word takes at most one chunk (< 2^48) per segment; a block gives each of its `ncopy` LDS copies at most
+// 32767 cells (launcher), i.e. at most 65534 chunks (< 2^64), and carries before it writes.  Levels that do not fit the LDS
+// budget are split over gridDim.z (each group a full pass: any N is accepted).
+#include "xc_internal.h"
+
+namespace xc {
+namespace {
+
+#include "xc_binning.h"
+#include "xc_levels.h"
+
+constexpr int CLEN_RB = 32;                 // cell rows per tile
+constexpr int CLEN_TPB = 256;               // threads per block
+constexpr int CLEN_W = 252;                 // cell columns per tile: 4 waves x 63 cells
+constexpr int CLEN_COPY_CELLS = 32767;      // cells one LDS copy of a block may receive (2 segments x 2^48 per cell < 2^64 per word)
+constexpr size_t CLEN_LDS = 48 * 1024;      // LDS per block (several blocks per CU)
+constexpr int CLEN_WORDS = kDetWords;       // limbs + the trash word of a low chunk under the window
+constexpr unsigned CLEN_FLAG = 1u << 28;    // count word: a non-finite length was seen (k_det3_reduce channel-0 flag)
+
+__device__ __forceinline__ double frac_of(double a, double b, double c) { return a == b ? 0.0 : __ddiv_rn(__dsub_rn(c, a), __dsub_rn(b, a)); }
+
+// np.interp(x, arange(n), F) for x = i0 + f, f in [0, 1]: F[j] on a node (the last node included), else the slope formula
+__device__ __forceinline__ double interp_at(double x, double i0, double F0, double F1)
+{
+    if (x == i0) return F0;
+    if (x == i0 + 1.0) return F1;
+    return __dadd_rn(__dmul_rn(__dsub_rn(F1, F0), __dsub_rn(x, i0)), F0);
+}
+
+template <bool LATLON>
+__device__ __forceinline__ double seg_len(double x1, double y1, double x2, double y2)
+{
+    if constexpr (LATLON) {                                       // __geodist (utils.py:741-761), in its operation order
+        const double sa = sin(__dmul_rn(__dsub_rn(y2, y1), 0.5)), sb = sin(__dmul_rn(__dsub_rn(x2, x1), 0.5));
+        const double a = __dadd_rn(__dmul_rn(sa, sa), __dmul_rn(__dmul_rn(cos(y1), cos(y2)), __dmul_rn(sb, sb)));
+        return __dmul_rn(2.0, asin(__dsqrt_rn(a)));
+    } else {
+        return hypot(__dsub_rn(x1, x2), __dsub_rn(y1, y2));
+    }
+}
+
+__device__ __forceinline__ void add_len(unsigned long long* acc, unsigned* cnt, double w, int c0w)
+{
+    unsigned long long hi, lo; int E;
+    const int j = det_split(w, c0w, hi, lo, E);
+    lds_add(acc + (j - 1), hi);
+    lds_add(acc + j, lo);
+    lds_add(cnt, E == 2047 ? CLEN_FLAG | 1u : 1u);
+}
+
+// One NaN-free cell and one crossed level: its (up to two) segments.  (rT, rB): the cell's rows as doubles, (cL, cR) its
+// columns; (yT, yB) / (xL, xR) the coordinates of those nodes.
+template <bool LATLON>
+__device__ __forceinline__ void cell_level(double ul, double ur, double ll, double lr, double c, double rT, double cL,
+                                           double yT, double yB, double xL, double xR,
+                                           unsigned long long* acc, unsigned* cnt, int c0w)
+{
+    const bool a = ul > c, b = ur > c, d = ll > c, e = lr > c;
+    const int cs = (int)a | ((int)b << 1) | ((int)d << 2) | ((int)e << 3);
+    const double rB = rT + 1.0, cR = cL + 1.0;
+    // the four edge points in index space, then in coordinates
+    const double tc = __dadd_rn(cL, frac_of(ul, ur, c)), bc = __dadd_rn(cL, frac_of(ll, lr, c));
+    const double lr_ = __dadd_rn(rT, frac_of(ul, ll, c)), rr = __dadd_rn(rT, frac_of(ur, lr, c));
+    const double tx = interp_at(tc, cL, xL, xR), bx = interp_at(bc, cL, xL, xR);
+    const double ly = interp_at(lr_, rT, yT, yB), ry = interp_at(rr, rT, yT, yB);
+    // point ids: 0 top, 1 bottom, 2 left, 3 right
+    const bool eT = a != b, eB = d != e, eL = a != d, eR = b != e;
+    const int p = eT ? 0 : (eB ? 1 : 2);
+    const int q = cs == 9 ? 2 : (eR ? 3 : (eL ? 2 : 1));
+    auto row = [&](int i) { return i == 0 ? rT : i == 1 ? rB : i == 2 ? lr_ : rr; };
+    auto col = [&](int i) { return i == 0 ? tc : i == 1 ? bc : i == 2 ? cL : cR; };
+    auto ycd = [&](int i) { return i == 0 ? yT : i == 1 ? yB : i == 2 ? ly : ry; };
+    auto xcd = [&](int i) { return i == 0 ? tx : i == 1 ? bx : i == 2 ? xL : xR; };
+    // the first segment joins p and q; the saddles 6 / 9 add (bottom, left) / (bottom, right).  One loop body: the length
+    // arithmetic (sin / cos / asin on the sphere) is emitted once
+    const int nseg = (cs == 6 || cs == 9) ? 2 : 1;
+#pragma unroll 1
+    for (int t = 0; t < nseg; ++t) {
+        const int u = t == 0 ? p : 1, v = t == 0 ? q : (cs == 6 ? 2 : 3);
+        if (!(row(u) == row(v) && col(u) == col(v))) add_len(acc, cnt, seg_len<LATLON>(xcd(u), ycd(u), xcd(v), ycd(v)), c0w);
+    }
+}
+
+// The window constant of every slab from a bound on one segment: pi on the unit sphere, else the largest cell diagonal.
+__global__ __launch_bounds__(256)
+void k_clen_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon,
+                   int64_t nslab, int* __restrict__ c0)
+{
+    const int tid = threadIdx.x;
+    double my = 0.0, mx = 0.0;
+    for (int64_t i = tid; i + 1 < ny; i += 256) my = fmax(my, fabs(fy[i + 1] - fy[i]));
+    for (int64_t i = tid; i + 1 < nx; i += 256) mx = fmax(mx, fabs(fx[i + 1] - fx[i]));
+    for (int o = 32; o > 0; o >>= 1) { my = fmax(my, __shfl_xor(my, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
+    __shared__ double s_m[2][4];
+    if ((tid & 63) == 0) { s_m[0][tid >> 6] = my; s_m[1][tid >> 6] = mx; }
+    __syncthreads();
+    my = fmax(fmax(s_m[0][0], s_m[0][1]), fmax(s_m[0][2], s_m[0][3]));
+    mx = fmax(fmax(s_m[1][0], s_m[1][1]), fmax(s_m[1][2], s_m[1][3]));
+    const double bound = latlon ? 3.2 : 1.0000001 * hypot(mx, my);
+    const int w = det_c0_from_bound(bound);
+    for (int64_t s = tid; s < nslab; s += 256) c0[s] = w;
+}
+
+// grid (bps, nslab, level groups of G).  LDS: levels [G + 2] (-inf, the group's levels, +inf), then per (level, copy)
+// CLEN_WORDS limb words and one count word.
+template <typename TQ, bool LATLON>
+__global__ __launch_bounds__(CLEN_TPB)
+void k_clen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx,
+            const double* __restrict__ contours, int N, int contours_per_slab, int G, const int* __restrict__ c0s,
+            int64_t ntj, int64_t nti, int bps, int ncopy, unsigned long long* __restrict__ part_l, unsigned* __restrict__ part_c)
+{
+    extern __shared__ double sm[];
+    const int tid = threadIdx.x;
+    const int64_t slab = blockIdx.y;
+    const int g0 = blockIdx.z * G, ng = (N - g0 < G) ? N - g0 : G;
+    double* s_cx = sm;                                                                    // [ng + 2]
+    unsigned long long* s_acc = (unsigned long long*)(sm + ng + 2);                       // [ng][ncopy][CLEN_WORDS]
+    unsigned* s_cnt = (unsigned*)(s_acc + (size_t)ng * ncopy * CLEN_WORDS);              // [ng][ncopy]
+    const double* cs = contours + (contours_per_slab ? (size_t)slab * N : 0) + g0;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    for (int k = tid; k < ng; k += CLEN_TPB) s_cx[k + 1] = cs[k];
+    if (tid == 0) { s_cx[0] = -inf; s_cx[ng + 1] = inf; }
+    for (int k = tid; k < ng * ncopy * CLEN_WORDS; k += CLEN_TPB) s_acc[k] = 0ull;
+    for (int k = tid; k < ng * ncopy; k += CLEN_TPB) s_cnt[k] = 0u;
+    __syncthreads();
+    const int c0w = c0s[slab];
+    const double c_first = s_cx[1];
+    double inv_step = (ng > 1) ? (double)(ng - 1) / (s_cx[ng] - c_first) : 0.0;
+    if (!(inv_step > 0.0 && inv_step < inf)) inv_step = 0.0;
+    double zlo = 0.5;
+    {   // equally spaced levels?  (block-uniform answer, as in K9) -- and how far the levels sit from their ideal positions
+        int ok = inv_step > 0.0;
+        double dev = 0.0;
+        for (int k = tid; k < ng && ok; k += CLEN_TPB) {
+            const double d = fabs((s_cx[k + 1] - c_first) * inv_step - (double)k);
+            ok = d < 0.01; dev = fmax(dev, d);
+        }
+        if (!__syncthreads_and(ok)) inv_step = 0.0;
+        for (int o = 32; o > 0; o >>= 1) dev = fmax(dev, __shfl_xor(dev, o));
+        __shared__ double s_dev[CLEN_TPB / 64];
+        if ((tid & 63) == 0) s_dev[tid >> 6] = dev;
+        __syncthreads();
+        dev = s_dev[0];
+        for (int w = 1; w < CLEN_TPB / 64; ++w) dev = fmax(dev, s_dev[w]);
+        zlo = 2.0 * dev + 1e-9;
+    }
+    const int cshift = __builtin_ctz((unsigned)ncopy), copy = tid & (ncopy - 1);
+    const TQ* qs = q + (size_t)slab * ny * nx;
+    const int64_t ncx = nx - 1, ncy = ny - 1;
+    const int lane = tid & 63, wave = tid >> 6;
+
+    for (int64_t tile = blockIdx.x; tile < ntj * nti; tile += bps) {
+        const int64_t tj = tile / nti, ti = tile - tj * nti;
+        const int64_t i = ti * CLEN_W + wave * 63 + lane;                                // this lane's cell column
+        const int64_t j0 = tj * CLEN_RB, j1 = (j0 + CLEN_RB < ncy) ? j0 + CLEN_RB : ncy;
+        const bool cell = lane < 63 && i < ncx;                                          // lanes without a cell still load and shift
+        const int64_t c = i < nx - 1 ? i : nx - 1;                                       // corner column loaded by this lane
+        const double xL = fx[c], xR = lane_shift_keep<DPP_WAVE_SHL1>(xL, xL);
+        const double cL = (double)c;
+        double ul = (double)qs[(size_t)j0 * nx + c];
+        double ur = lane_shift_keep<DPP_WAVE_SHL1>(ul, ul);
+        constexpr int B = 4;
+        for (int64_t jb = j0; jb < j1; jb += B) {
+            TQ v[B];
+#pragma unroll
+            for (int b = 0; b < B; ++b) {                                                // all loads of the batch in flight together
+                const int64_t jj = (jb + b < j1) ? jb + b : j1 - 1;
+                v[b] = qs[(size_t)(jj + 1) * nx + c];
+            }
+#pragma unroll
+            for (int b = 0; b < B; ++b) {
+                const int64_t r = jb + b;
+                if (r >= j1) break;                                                      // wave-uniform
+                const double ll = (double)v[b], lr = lane_shift_keep<DPP_WAVE_SHL1>(ll, ll);
+                const bool hasnan = (ul != ul) | (ur != ur) | (ll != ll) | (lr != lr);
+                if (cell && !hasnan) {
+                    const double mn = fmin(fmin(ul, ur), fmin(ll, lr)), mx = fmax(fmax(ul, ur), fmax(ll, lr));
+                    int klo, khi;
+                    if (inv_step > 0.0) {
+                        klo = count_below_uniform(s_cx, ng, mn, c_first, inv_step, zlo);
+                        khi = count_below_uniform(s_cx, ng, mx, c_first, inv_step, zlo);
+                    } else {
+                        klo = count_below(s_cx, ng, mn);
+                        khi = count_below(s_cx, ng, mx);
+                    }
+                    if (khi > klo) {
+                        const double yT = fy[r], yB = fy[r + 1];
+                        for (int k = klo; k < khi; ++k)
+                            cell_level<LATLON>(ul, ur, ll, lr, s_cx[k + 1], (double)r, cL, yT, yB, xL, xR,
+                                               s_acc + ((size_t)((k << cshift) + copy)) * CLEN_WORDS, s_cnt + (k << cshift) + copy, c0w);
+                    }
+                }
+                ul = ll; ur = lr;
+            }
+        }
+    }
+    __syncthreads();
+    // per level: the copies carried into canonical limbs (words 1..3 < 2^48 plus carries, word 0 the rest) and summed, carried
+    // once more, written as this block's partial; the trash word is dropped
+    const size_t pb = ((size_t)slab * bps + blockIdx.x);
+    for (int k = tid; k < ng; k += CLEN_TPB) {
+        unsigned long long acc[kDetLimbsX] = {0ull, 0ull, 0ull, 0ull};
+        unsigned n = 0u;
+        for (int cp = 0; cp < ncopy; ++cp) {
+            const unsigned long long* w = s_acc + ((size_t)((k << cshift) + cp)) * CLEN_WORDS;
+#pragma unroll
+            for (int l = 0; l < kDetLimbsX; ++l) {
+                const unsigned long long x = w[l];
+                acc[l] += x & 0xffffffffffffull;
+                if (l > 0) acc[l - 1] += x >> kDetLimbBits; else acc[0] += x & ~0xffffffffffffull;
+            }
+            const unsigned m = s_cnt[(k << cshift) + cp];
+            n = ((n & 0x0fffffffu) + (m & 0x0fffffffu)) | ((n | m) & CLEN_FLAG);
+        }
+#pragma unroll
+        for (int l = kDetLimbsX - 1; l > 0; --l) { acc[l - 1] += acc[l] >> kDetLimbBits; acc[l] &= 0xffffffffffffull; }
+        const int kg = g0 + k;
+#pragma unroll
+        for (int l = 0; l < kDetLimbsX; ++l) part_l[(pb * kDetLimbsX + l) * N + kg] = acc[l];
+        part_c[pb * N + kg] = n;
+    }
+}
+
+// total == 0 -> NaN (utils.py:603-604); else times the radius once (utils.py:606-607)
+__global__ __launch_bounds__(256)
+void k_clen_finish(double* __restrict__ out, int64_t n, double radius)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double t = out[i];
+    out[i] = t == 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : (radius > 0.0 ? __dmul_rn(t, radius) : t);
+}
+
+}  // namespace
+
+int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                           const double* ycoord, const double* xcoord, double radius,
+                           const double* contours, int N, int contours_per_slab, double* out_len, uint64_t* out_nseg)
+{
+    if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || N < 1)
+        return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_lengths: q_dtype must be XC_F32 or XC_F64");
+    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: radius must be >= 0");
+    if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_contour_lengths: nslab too large");
+    // LDS: level values 8 B + per copy CLEN_WORDS x 8 + 4 B.  As many copies (up to 8) as the budget takes for all levels;
+    // one copy and groups of G levels past it
+    auto lds_of = [](int g, int nc) { return (size_t)(g + 2) * 8 + (size_t)g * nc * (CLEN_WORDS * 8 + 4) + 16; };
+    int ncopy = 8;
+    while (ncopy > 1 && lds_of(N, ncopy) > CLEN_LDS) ncopy >>= 1;
+    int G = N;
+    if (lds_of(N, ncopy) > CLEN_LDS) G = (int)((CLEN_LDS - 32) / (8 + CLEN_WORDS * 8 + 4));
+    const int ngroup = (N + G - 1) / G;
+    const size_t lds = lds_of(G, ncopy);
+    const int64_t ncx = nx - 1, ncy = ny - 1;
+    const int64_t ntj = ncy > 0 ? (ncy + CLEN_RB - 1) / CLEN_RB : 0, nti = ncx > 0 ? (ncx + CLEN_W - 1) / CLEN_W : 0;
+    const int64_t ntile = ntj * nti;
+    // blocks per slab: ~2048 blocks per launch, and at most CLEN_COPY_CELLS cells per copy: a tile gives a copy
+    // CLEN_RB * CLEN_TPB / ncopy of them
+    const int64_t max_tiles = (int64_t)CLEN_COPY_CELLS * ncopy / (CLEN_RB * CLEN_TPB);
+    int64_t bps = 0;
+    if (ntile > 0) {
+        bps = 2048 / nslab; if (bps < 8) bps = 8;
+        const int64_t need = (ntile + max_tiles - 1) / max_tiles;
+        if (bps < need) bps = need;
+        if (bps > ntile) bps = ntile;
+    }
+    const size_t al = 256;
+    auto up = [&](size_t b) { return (b + al - 1) & ~(al - 1); };
+    const size_t pl = up((size_t)nslab * bps * kDetLimbsX * N * 8), pc = up((size_t)nslab * bps * N * 4);
+    const size_t pw = up((size_t)nslab * 4), pn = out_nseg ? 0 : up((size_t)nslab * N * 8);
+    {
+        const int rc = ensure_scratch(ctx, pl + pc + pw + pn + al);
+        if (rc != XC_OK) return rc;
+    }
+    char* sc = (char*)ctx->scratch;
+    unsigned long long* part_l = (unsigned long long*)sc;
+    unsigned* part_c = (unsigned*)(sc + pl);
+    int* c0 = (int*)(sc + pl + pc);
+    unsigned long long* nseg = out_nseg ? (unsigned long long*)out_nseg : (unsigned long long*)(sc + pl + pc + pw);
+    const int latlon = radius > 0.0;
+    hipLaunchKernelGGL(k_clen_window, dim3(1), dim3(256), 0, ctx->stream, ycoord, ny, xcoord, nx, latlon, nslab, c0);
+    XC_HIP(ctx, hipGetLastError());
+    if (bps > 0) {
+        const dim3 grid((unsigned)bps, (unsigned)nslab, (unsigned)ngroup);
+#define XC_CLEN(TQ_, LL_) hipLaunchKernelGGL((k_clen<TQ_, LL_>), grid, dim3(CLEN_TPB), lds, ctx->stream, (const TQ_*)q, ny, nx, \
+                                             ycoord, xcoord, contours, N, contours_per_slab, G, c0, ntj, nti, (int)bps, ncopy, part_l, part_c)
+        if (q_dtype == XC_F64) { if (latlon) XC_CLEN(double, true); else XC_CLEN(double, false); }
+        else { if (latlon) XC_CLEN(float, true); else XC_CLEN(float, false); }
+#undef XC_CLEN
+        XC_HIP(ctx, hipGetLastError());
+    }
+    const int rc = launch_det3_reduce(ctx, nslab, (int)bps, 1, N, reinterpret_cast<const double*>(part_l), part_c, c0, out_len, nseg);
+    if (rc != XC_OK) return rc;
+    const int64_t n = nslab * (int64_t)N;
+    hipLaunchKernelGGL(k_clen_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, out_len, n, latlon ? radius : 0.0);
+    XC_HIP(ctx, hipGetLastError());
+    return XC_OK;
+}
+
+}  // namespace xc

@@ -295,6 +295,9 @@ int launch_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int6
                     int pad_x, int pad_mode, const double* contours, int N, int contours_per_slab,
                     const void* area, int area_dtype, int area_per_slab, int stride, int full_width,
                     double* out_len, uint64_t* out_cnt);
+int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                           const double* ycoord, const double* xcoord, double radius,
+                           const double* contours, int N, int contours_per_slab, double* out_len, uint64_t* out_nseg);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 
