@@ -452,6 +452,25 @@ typedef struct xc_hist_variant {
     int32_t G, cps, rpc;                                         /* K3S: workgroups, chunks per strip, rows per chunk */
 } xc_hist_variant;
 int xc_last_hist_variant(xc_ctx* ctx, xc_hist_variant* out);
+/* how the last xc_contour_lengths / xc_contour_lengths_dev call launched K10, as the launcher chose it on the host.  All zero
+ * when the last such call failed; bps = 0 (and bps_rule 0) when the plane has no cells.                                      */
+#define XC_CLEN_BPS_SHARE    1   /* bps = 2048 / nslab: the launch's share of ~2048 blocks */
+#define XC_CLEN_BPS_FLOOR    2   /* bps = 8: the floor under that share */
+#define XC_CLEN_BPS_CAPACITY 3   /* bps = ceil(ntile / max_tiles): no LDS copy may receive more than 32767 cells */
+#define XC_CLEN_BPS_NTILE    4   /* bps = ntile: no more blocks than tiles */
+typedef struct xc_clen_geometry {
+    int32_t q_dtype;    /* XC_F32 / XC_F64 */
+    int32_t latlon;     /* 1 haversine (radius > 0), 0 hypot */
+    int32_t N;          /* levels per slab */
+    int32_t ncopy;      /* LDS accumulator copies per level: 8 / 4 / 2 / 1 */
+    int32_t G;          /* levels per group (gridDim.z) */
+    int32_t ngroup;     /* level groups: ceil(N / G) */
+    int64_t ntile;      /* 32 x 252-cell tiles per slab */
+    int32_t bps;        /* blocks per slab (gridDim.x) */
+    int32_t bps_rule;   /* which XC_CLEN_BPS_* rule set bps; 0 when bps = 0 */
+    int64_t nslab;      /* slabs in the launch (gridDim.y) */
+} xc_clen_geometry;
+int xc_last_clen_geometry(xc_ctx* ctx, xc_clen_geometry* out);
 /* One-shot: record the caller's events (from xc_event_create) immediately before and after
  * the NEXT histogram launch instead of the context's own pair -- lets a benchmark time every
  * launch of a timed region without synchronising inside it.                              */

@@ -1,7 +1,8 @@
 /* Plain-C client of the C ABI (include/xcontour_hip.h): what a cgo / JNI / C++ host would do.
  * Built with gcc only (no HIP headers): tests/test_gpu_parity.py::test_c_client compiles it against
  * xcontour_amd/libxcontour_hip.so and runs it on the GPU box.
- * min/max -> levels/edges -> weighted histogram + CDF of a small field, checked against loops written here. */
+ * min/max -> levels/edges -> weighted histogram + CDF of a small field, checked against loops written here; contour lengths
+ * against a closed form. */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -152,6 +153,28 @@ int main(void)
         if (total != (uint64_t)KY * KX || !(r[0][1][KN - 1] > 0.99 * acc)) { fprintf(stderr, "FAIL keff totals\n"); return 1; }
         void* bufs[] = {dq, dd, dx, dy, dt, dc, dout, dcnt, dst};
         for (unsigned i = 0; i < sizeof bufs / sizeof bufs[0]; ++i) xc_free(ctx, bufs[i]);
+    }
+    /* contour lengths (K10): q = column index on a 13 x 21 plane, rows 50 apart: every level between two columns is one vertical
+       line of 12 segments and length 600; a level past the last column traces nothing (NaN, 0 segments) */
+    {
+        enum { CY = 13, CX = 21 };
+        static double cq[CY][CX], cy[CY], cx[CX], clen[3];
+        uint64_t cn[3];
+        const double lv[3] = {3.25, 17.5, 25.0};
+        for (int j = 0; j < CY; ++j) { cy[j] = 50.0 * j; for (int i = 0; i < CX; ++i) cq[j][i] = (double)i; }
+        for (int i = 0; i < CX; ++i) cx[i] = 100.0 * i;
+        if (xc_contour_lengths(ctx, cq, XC_F64, 1, CY, CX, cy, cx, 0.0, lv, 3, 0, clen, cn) != XC_OK) return fail("xc_contour_lengths", ctx);
+        if (cn[0] != CY - 1 || cn[1] != CY - 1 || cn[2] != 0 || clen[0] != 600.0 || clen[1] != 600.0 || clen[2] == clen[2]) {
+            fprintf(stderr, "FAIL contour lengths %g %g %g (%llu %llu %llu)\n", clen[0], clen[1], clen[2],
+                    (unsigned long long)cn[0], (unsigned long long)cn[1], (unsigned long long)cn[2]);
+            return 1;
+        }
+        xc_clen_geometry g;
+        if (xc_last_clen_geometry(ctx, &g) != XC_OK) return fail("xc_last_clen_geometry", ctx);
+        if (g.N != 3 || g.ncopy != 8 || g.ngroup != 1 || g.ntile != 1 || g.bps != 1 || g.bps_rule != XC_CLEN_BPS_NTILE || g.nslab != 1) {
+            fprintf(stderr, "FAIL contour length geometry\n");
+            return 1;
+        }
     }
     /* error path: non-ascending edges must be refused with a message, not crash */
     edges[0][5] = edges[0][4];

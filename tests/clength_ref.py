@@ -91,3 +91,101 @@ def plane_coords(ycoord, xcoord, latlon):
     if latlon:
         y, x = np.deg2rad(y), np.deg2rad(x)
     return y.astype(np.float64), x.astype(np.float64)
+
+
+# ---- the same rule for every level at once (the GPU tests and tools/gpu_fuzz.py need it fast)
+def segments_fast(q2d, levels, ycoord, xcoord, latlon=False, pairs=PAIRS, chunk=1 << 21):
+    """Every segment of every level in one vectorised pass: for each NaN-free cell the crossed levels, mn <= c < mx, are the
+    index range between two searchsorted lower bounds (what K10 computes), and every (cell, level) pair emits its segments at
+    once.  Levels in any order; a NaN level crosses nothing.  -> (k level index, r1, c1, r2, c2, length) arrays, degenerate
+    segments dropped.  `chunk`: (cell, level) pairs per step (bounds the memory)."""
+    q = np.asarray(q2d, dtype=np.float64)
+    lv = np.asarray(levels, dtype=np.float64)
+    srt = np.where(np.isnan(lv), np.inf, lv)
+    order = np.argsort(srt, kind='stable')
+    ls = srt[order]
+    ny, nx = q.shape
+    yi, xi = np.arange(ny), np.arange(nx)
+    ul, ur, ll, lr = (a.ravel() for a in (q[:-1, :-1], q[:-1, 1:], q[1:, :-1], q[1:, 1:]))
+    with np.errstate(invalid='ignore'):
+        ok = ~(np.isnan(ul) | np.isnan(ur) | np.isnan(ll) | np.isnan(lr))
+    cell = np.nonzero(ok)[0]
+    mn = np.fmin(np.fmin(ul[cell], ur[cell]), np.fmin(ll[cell], lr[cell]))
+    mx = np.fmax(np.fmax(ul[cell], ur[cell]), np.fmax(ll[cell], lr[cell]))
+    klo, khi = np.searchsorted(ls, mn, 'left'), np.searchsorted(ls, mx, 'left')
+    n = np.maximum(khi - klo, 0)
+    cell, klo, n = cell[n > 0], klo[n > 0], n[n > 0]
+    ends = np.cumsum(n)
+    out = [[] for _ in range(6)]
+    i0 = 0
+    while i0 < cell.size:                                   # whole cells per step, about `chunk` pairs each
+        i1 = max(int(np.searchsorted(ends, (ends[i0 - 1] if i0 else 0) + chunk, 'right')), i0 + 1)
+        cc, kl, nn = cell[i0:i1], klo[i0:i1], n[i0:i1]
+        rep = np.repeat(np.arange(cc.size), nn)
+        ks = kl[rep] + (np.arange(rep.size) - np.repeat(np.cumsum(nn) - nn, nn))
+        ci = cc[rep]
+        c = ls[ks]
+        a, b, d, e = ul[ci], ur[ci], ll[ci], lr[ci]
+        r0f, c0f = (ci // (nx - 1)).astype(np.float64), (ci % (nx - 1)).astype(np.float64)
+        case = (a > c) * 1 + (b > c) * 2 + (d > c) * 4 + (e > c) * 8
+        pts = {T: (r0f, c0f + _frac(a, b, c)), B: (r0f + 1.0, c0f + _frac(d, e, c)),
+               L: (r0f + _frac(a, d, c), c0f), R: (r0f + _frac(b, e, c), c0f + 1.0)}
+        for cs, prs in pairs.items():
+            m = case == cs
+            if not m.any():
+                continue
+            for p, s in prs:
+                r1, c1, r2, c2 = pts[p][0][m], pts[p][1][m], pts[s][0][m], pts[s][1][m]
+                keep = ~((r1 == r2) & (c1 == c2))
+                r1, c1, r2, c2 = r1[keep], c1[keep], r2[keep], c2[keep]
+                y1, y2 = np.interp(r1, yi, ycoord), np.interp(r2, yi, ycoord)
+                x1, x2 = np.interp(c1, xi, xcoord), np.interp(c2, xi, xcoord)
+                ln = haversine(x1, y1, x2, y2) if latlon else np.hypot(x1 - x2, y1 - y2)
+                for o, v in zip(out, (order[ks[m][keep]], r1, c1, r2, c2, ln)):
+                    o.append(v)
+        i0 = i1
+    if not out[0]:
+        return (np.zeros(0, dtype=np.int64),) + tuple(np.zeros(0) for _ in range(5))
+    return tuple(np.concatenate(o) for o in out)
+
+
+def contour_lengths_fast(q2d, levels, ycoord, xcoord, latlon=False, pairs=PAIRS):
+    """contour_lengths from segments_fast: the same counts and segment lengths, summed per level in another order"""
+    N = len(levels)
+    k, *_, ln = segments_fast(q2d, levels, ycoord, xcoord, latlon, pairs)
+    cnt = np.bincount(k, minlength=N).astype(np.int64)
+    t = np.bincount(k, weights=ln, minlength=N)
+    tot = np.where(t == 0, np.nan, t * RADIUS if latlon else t)
+    tot[np.isnan(np.asarray(levels, dtype=np.float64))] = np.nan
+    return tot, cnt
+
+
+def clen_bound(ycoord, xcoord, latlon):
+    """K10's bound on one segment (k_clen_window): 3.2 on the unit sphere, else 1.0000001 x the largest cell diagonal"""
+    if latlon:
+        return 3.2
+    my = float(np.max(np.abs(np.diff(ycoord)))) if len(ycoord) > 1 else 0.0
+    mx = float(np.max(np.abs(np.diff(xcoord)))) if len(xcoord) > 1 else 0.0
+    return 1.0000001 * float(np.hypot(mx, my))
+
+
+def det_totals(q2d, levels, ycoord, xcoord, latlon=False):
+    """K10's sum, modelled: the restatement's segment lengths through the oracle's fixed-point rule (deterministic_bin_sums) on
+    the window of clen_bound, times the radius on the sphere, NaN for a total of 0 -> totals f64 (N,).  Levels ascending."""
+    import xcontour_oracle as O
+    N = len(levels)
+    k, *_, ln = segments_fast(q2d, levels, ycoord, xcoord, latlon)
+    t = O.deterministic_bin_sums(k + 1, ln, N, top=O.det_window_top(clen_bound(ycoord, xcoord, latlon)), nlimb=4)
+    with np.errstate(invalid='ignore'):
+        return np.where(t == 0, np.nan, t * RADIUS if latlon else t)
+
+
+def hashed_coords(n, salt=0, start=0.0, scale=1.0, descending=False):
+    """n coordinates whose spacings scale (1 + 0.25 f(i)) differ in every cell (f hashed into [-1, 1), as in
+    test_gpu_hist_variants.hashed); descending=True runs them from the top down"""
+    i = np.arange(max(n - 1, 0), dtype=np.uint64)
+    h = (i * np.uint64(40503) + np.uint64(salt) * np.uint64(97) + np.uint64(12345)) * np.uint64(2246822519)
+    h = (h ^ (h >> np.uint64(13))) & np.uint64(0xffffffff)
+    d = scale * (1.0 + 0.25 * (h.astype(np.float64) / 2.0 ** 31 - 1.0))
+    c = start + np.concatenate([[0.0], np.cumsum(d)])
+    return c[::-1].copy() if descending else c

@@ -28,11 +28,11 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_struct_layouts_match_header(tmp_path):
-    """sizeof / offsetof of the two descriptor structs and the variant record as gcc sees them in include/xcontour_hip.h == the ctypes mirrors"""
+    """sizeof / offsetof of the two descriptor structs and the two launch records as gcc sees them in include/xcontour_hip.h == the ctypes mirrors"""
     import subprocess
     from xcontour_amd import _native as nat
     fields = {'xc_hist_desc': [f[0] for f in nat.HistDesc._fields_], 'xc_keff_desc': [f[0] for f in nat.KeffDesc._fields_],
-              'xc_hist_variant': [f[0] for f in nat.HistVariant._fields_]}
+              'xc_hist_variant': [f[0] for f in nat.HistVariant._fields_], 'xc_clen_geometry': [f[0] for f in nat.ClenGeometry._fields_]}
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % os.path.join(ROOT, 'include', 'xcontour_hip.h'), 'int main(void){']
     for st, fl in fields.items():
         src.append('printf("%s %%zu\\n", sizeof(struct %s));' % (st, st))
@@ -44,7 +44,8 @@ def test_struct_layouts_match_header(tmp_path):
     exe = str(tmp_path / 'layout')
     subprocess.run(['gcc', '-std=c99', '-o', exe, str(c)], check=True)
     got = dict(line.split() for line in subprocess.run([exe], check=True, stdout=subprocess.PIPE, universal_newlines=True).stdout.splitlines())
-    for st, cls in (('xc_hist_desc', nat.HistDesc), ('xc_keff_desc', nat.KeffDesc), ('xc_hist_variant', nat.HistVariant)):
+    for st, cls in (('xc_hist_desc', nat.HistDesc), ('xc_keff_desc', nat.KeffDesc), ('xc_hist_variant', nat.HistVariant),
+                    ('xc_clen_geometry', nat.ClenGeometry)):
         assert int(got[st]) == C.sizeof(cls), st
         for f in fields[st]:
             assert int(got['%s.%s' % (st, f)]) == getattr(cls, f).offset, '%s.%s' % (st, f)

@@ -114,3 +114,89 @@ def test_level_on_node_values_drops_degenerate_and_keeps_duplicates():
     q = np.array([[1.0, 0.0], [1.0, 1.0]])
     t, n = CR.contour_lengths(q, [0.0], np.arange(2.0), np.arange(2.0))
     assert n[0] == 0 and np.isnan(t[0])
+
+
+def _inputs(kind, ny=23, nx=31, seed=0):
+    rng = np.random.default_rng(seed)
+    if kind == 'saddle':
+        q = np.indices((ny, nx)).sum(0) % 2 * 2.0 - 1.0 + 0.3 * rng.standard_normal((ny, nx))
+    elif kind == 'node':
+        q = rng.integers(0, 6, size=(ny, nx)).astype(np.float64)
+    else:
+        q = rng.standard_normal((ny, nx))
+    if kind == 'nan':
+        q[rng.random(q.shape) < 0.08] = np.nan
+    levels = {'node': np.array([-1.0, 0.0, 1.0, 2.0, 2.0, 2.5, 3.0, 5.0, 6.0])}.get(kind, np.linspace(-2.0, 2.0, 17))
+    return q, levels
+
+
+@pytest.mark.parametrize('latlon', [False, True])
+@pytest.mark.parametrize('kind', ['random', 'saddle', 'nan', 'node'])
+def test_fast_restatement_equals_the_level_loop(kind, latlon):
+    """segments_fast / contour_lengths_fast emit the per-level loop's segments: the same end points and the same lengths, bit for
+    bit, level by level (in another order); counts equal, totals to rounding.  Coordinates that differ in every cell, latitude
+    descending on the sphere."""
+    q, levels = _inputs(kind, seed=len(kind))
+    ny, nx = q.shape
+    if latlon:
+        y = np.deg2rad(CR.hashed_coords(ny, 1, -80.0, 160.0 / ny, descending=True))
+        x = np.deg2rad(CR.hashed_coords(nx, 2, 0.0, 300.0 / nx))
+    else:
+        y, x = CR.hashed_coords(ny, 3, 5.0, 7.0), CR.hashed_coords(nx, 4, -3.0, 2.0)
+    lv = levels[::-1].copy() if kind == 'random' else levels               # any order
+    k, r1, c1, r2, c2, ln = CR.segments_fast(q, lv, y, x, latlon)
+    tot, cnt = CR.contour_lengths_fast(q, lv, y, x, latlon)
+    rt, rn = CR.contour_lengths(q, lv, y, x, latlon)
+    assert np.array_equal(cnt, rn) and cnt.sum() > 0
+    assert np.array_equal(np.isnan(tot), np.isnan(rt))
+    ok = ~np.isnan(rt)
+    assert np.all(np.abs(tot[ok] - rt[ok]) <= 1e-13 * np.abs(rt[ok]))
+    for j, c in enumerate(lv):
+        m = k == j
+        a, b, e, d = CR.segments(q, c)
+        want = sorted(zip(a, b, e, d, CR.segment_lengths(q, c, y, x, latlon)))
+        got = sorted(zip(r1[m], c1[m], r2[m], c2[m], ln[m]))
+        assert np.array_equal(np.array(got).view(np.int64), np.array(want).view(np.int64)) if want else not got, (kind, j)
+
+
+def test_fast_restatement_small_chunks_and_empty_planes():
+    q, lv = _inputs('saddle', 9, 12)
+    y, x = np.arange(9.0), CR.hashed_coords(12)
+    a = CR.segments_fast(q, lv, y, x)
+    b = CR.segments_fast(q, lv, y, x, chunk=7)
+    assert a[0].size > 100 and sorted(zip(*a)) == sorted(zip(*b))
+    for shape in ((1, 12), (9, 1)):
+        t, n = CR.contour_lengths_fast(np.zeros(shape), [0.5, 1.0], np.arange(shape[0] * 1.0), np.arange(shape[1] * 1.0))
+        assert np.isnan(t).all() and (n == 0).all()
+
+
+def test_det_totals_exact_where_the_window_holds_every_bit():
+    """a tracer varying along x only: every segment is vertical, |y[r+1] - y[r]|; with spacings of 20 significant bits the
+    fixed-point sum is the exact sum, so det_totals is math.fsum bit for bit"""
+    ny, nx = 40, 9
+    dy = np.floor(np.diff(CR.hashed_coords(ny, 5)) * 2 ** 12) / 2 ** 12
+    y = np.concatenate([[0.0], np.cumsum(dy)])
+    x = CR.hashed_coords(nx, 6)
+    q = np.repeat(np.arange(nx, dtype=np.float64)[None, :], ny, axis=0)
+    lv = np.array([0.5, 3.25, 7.75, 8.0, 9.0])
+    t = CR.det_totals(q, lv, y, x)
+    exact = math.fsum(dy)
+    assert [t[0], t[1], t[2]] == [exact] * 3 and np.isnan(t[3:]).all()
+    tl = CR.det_totals(q, lv, y * 0.01, x * 0.01, latlon=True)
+    assert tl[0] == tl[1] == tl[2] and abs(tl[0] / (0.01 * exact * CR.RADIUS) - 1.0) < 1e-12
+
+
+def test_det_totals_drops_what_falls_under_the_window():
+    """one very wide column lifts the window: segments 2^-150 of it lose their low chunk (and the shortest all of it), the model
+    follows the chunk rule of the oracle, not the exact sum"""
+    import xcontour_oracle as O
+    ny = 3
+    y = np.array([0.0, 3 * 2.0 ** -140, 3 * 2.0 ** -140 + 2.0 ** -160])                 # the window ends at 2^-139
+    x = np.array([0.0, 2.0 ** 40, 2.0 ** 40 + 1.0])
+    q = np.repeat(np.array([[0.0, 1.0, 2.0]]), ny, axis=0)
+    lv = np.array([1.5])
+    t = CR.det_totals(q, lv, y, x)
+    top = O.det_window_top(CR.clen_bound(y, x, False))
+    want = sum(O.det_chunks(w, top, 4) for w in np.diff(y))
+    assert t[0] == math.ldexp(float(want), top - 48 * 4)
+    assert t[0] == 2.0 ** -139 and math.fsum(np.diff(y)) == 3 * 2.0 ** -140 + 2.0 ** -160

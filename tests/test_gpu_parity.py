@@ -1158,7 +1158,7 @@ def test_keff_thousands_of_contours(ctx, baro):
 
 def test_differential_fuzz_short(ctx):
     """8 s of tools/gpu_fuzz.py (random shapes / dtypes / flags / NaNs; HIP path vs oracle for hist, the fused pipeline,
-    crossing, LWA, sort and the facade call sequence); the long runs are logged in profiles/r01_notes.md"""
+    crossing, LWA, sort, contour lengths and the facade call sequence); the long runs are logged in profiles/r01_notes.md"""
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location('gpu_fuzz', os.path.join(root, 'tools', 'gpu_fuzz.py'))
@@ -1166,3 +1166,4 @@ def test_differential_fuzz_short(ctx):
     spec.loader.exec_module(fz)
     n, checked = fz.run(8.0, seed=2024)
     assert sum(n.values()) > 200 and all(v > 0 for v in checked.values()) and len(checked) >= 6
+    assert checked.get('clen', 0) > 0

@@ -4,8 +4,9 @@
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle')); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import xcontour_oracle as O
+import clength_ref as CR
 from xcontour_amd import _native as nat
 from xcontour_amd.pipeline import KeffPlan
 from xcontour_amd.utils import table_from_rowsums, last_row_included
@@ -147,6 +148,31 @@ def case_crossing():
         tick('crossing')
 
 
+def case_clen():
+    S, ny, nx = int(rng.integers(1, 4)), int(rng.integers(1, 90 * SC)), int(rng.integers(1, 600 * SC))
+    N = int(rng.choice([1, 3, 17, 60, 140, 300, 600, 1000]))          # 8 / 4 / 2 / 1 LDS copies, two level groups
+    ny = max(1, min(ny, 100000 * SC // (nx * N)))                    # (keeps the per-level host restatement quick)
+    if N > 300:
+        S = 1
+    dt = rng.choice([np.float32, np.float64])
+    q = field(S, ny, nx, dt)
+    latlon = bool(rng.random() < 0.5)
+    y = np.cumsum(rng.uniform(0.2, 3.0, ny)) * (0.01 if latlon else 1e3)
+    x = np.cumsum(rng.uniform(0.2, 3.0, nx)) * (0.005 if latlon else 1e3)
+    if rng.random() < 0.3:
+        y = y[::-1].copy()
+    per_slab = bool(rng.random() < 0.3)
+    cs = np.sort(rng.uniform(-2.5, 2.5, (S, N) if per_slab else N), axis=-1)
+    if rng.random() < 0.3:
+        cs = np.sort(np.linspace(-2, 2, N) + 0 * cs, axis=-1)          # equally spaced: the arithmetic level search
+    lens, cnts = ctx.contour_lengths(q, cs, y, x, radius=CR.RADIUS if latlon else 0.0)
+    for s in range(S):
+        rt, rn = CR.contour_lengths(q[s].astype(np.float64), cs[s] if per_slab else cs, y, x, latlon)
+        assert np.array_equal(cnts[s].astype(np.int64), rn), 'clen counts %r' % ((S, ny, nx, N, latlon, per_slab),)
+        assert relerr(lens[s], rt) < 1e-12, 'clen lengths'
+        tick('clen')
+
+
 def case_lwa():
     S, ny, nx = int(rng.integers(1, 3)), int(rng.integers(2, 90 * min(SC, 3))), int(rng.integers(1, 200 * SC))
     dt = rng.choice([np.float32, np.float64])
@@ -281,7 +307,7 @@ def case_facade():
     tick('facade')
 
 
-cases = [case_lwa_interval, case_hist, case_keff, case_crossing, case_lwa, case_sort, case_facade]
+cases = [case_lwa_interval, case_hist, case_keff, case_crossing, case_lwa, case_sort, case_facade, case_clen]
 
 
 def run(seconds, seed=None):

@@ -62,6 +62,15 @@ class HistVariant(C.Structure):
 HIST_KERNELS = {0: None, 1: 'K3', 2: 'K3-det', 3: 'K3S'}
 
 
+class ClenGeometry(C.Structure):
+    """xc_clen_geometry: how the last xc_contour_lengths(_dev) call launched K10"""
+    _fields_ = [('q_dtype', _i32), ('latlon', _i32), ('N', _i32), ('ncopy', _i32), ('G', _i32), ('ngroup', _i32),
+                ('ntile', _i64), ('bps', _i32), ('bps_rule', _i32), ('nslab', _i64)]
+
+
+CLEN_BPS_RULES = {0: None, 1: 'share', 2: 'floor', 3: 'capacity', 4: 'ntile'}
+
+
 class KeffDesc(C.Structure):
     """struct xc_keff_desc (include/xcontour_hip.h)"""
     _fields_ = [
@@ -156,6 +165,7 @@ PROTOTYPES = {
     'xc_set_kernel_timing': (C.c_int, [_vp, C.c_int]),
     'xc_last_hist_ms': (C.c_int, [_vp, C.POINTER(C.c_float)]),
     'xc_last_hist_variant': (C.c_int, [_vp, C.POINTER(HistVariant)]),
+    'xc_last_clen_geometry': (C.c_int, [_vp, C.POINTER(ClenGeometry)]),
     'xc_set_hist_events': (C.c_int, [_vp, _vp, _vp]),
     'xc_comm_unique_id': (C.c_int, [_vp, _vp]),
     'xc_comm_init': (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -447,6 +457,17 @@ class Context(object):
         out = {f[0]: getattr(v, f[0]) for f in HistVariant._fields_}
         out['kernel'] = HIST_KERNELS[out['kernel']]
         out['q_dtype'] = np.dtype(np.float32 if out['q_dtype'] == XC_F32 else np.float64) if out['kernel'] else None
+        return out
+
+    def last_clen_geometry(self):
+        """how the last contour_lengths call (its last batch) launched K10 (xc_last_clen_geometry): a dict of the record's fields,
+        'bps_rule' named ('share', 'floor', 'capacity', 'ntile'; None when the plane has no cells) and 'q_dtype' a numpy dtype (None
+        after a failed call: then every field is 0)"""
+        g = ClenGeometry()
+        self._check(self.lib.xc_last_clen_geometry(self.handle, C.byref(g)))
+        out = {f[0]: getattr(g, f[0]) for f in ClenGeometry._fields_}
+        out['bps_rule'] = CLEN_BPS_RULES[out['bps_rule']]
+        out['q_dtype'] = np.dtype(np.float32 if out['q_dtype'] == XC_F32 else np.float64) if out['N'] else None
         return out
 
     def single_stamps(self, enable=True):

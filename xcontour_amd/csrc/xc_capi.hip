@@ -1048,15 +1048,28 @@ int xc_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t 
 }
 
 // ------------------------------------------------------------------------------------ K10
+// xc_last_clen_geometry: launch_contour_lengths writes the record where it picks the geometry; a call that fails leaves it cleared
+static int clen_recorded(xc_ctx* ctx, int rc)
+{
+    if (rc != XC_OK) ctx->last_clen = xc_clen_geometry{};
+    return rc;
+}
+
 int xc_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                            const double* ycoord, const double* xcoord, double radius,
                            const double* contours, int ncont, int contours_per_slab,
                            double* out_len, uint64_t* out_nseg)
 {
     XC_CTX(ctx);
-    return launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont, contours_per_slab,
-                                  out_len, out_nseg);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont,
+                                                     contours_per_slab, out_len, out_nseg));
 }
+
+static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                const double* ycoord, const double* xcoord, double radius,
+                                const double* contours, int ncont, int contours_per_slab,
+                                double* out_len, uint64_t* out_nseg);
 
 int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                        const double* ycoord, const double* xcoord, double radius,
@@ -1064,6 +1077,16 @@ int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, i
                        double* out_len, uint64_t* out_nseg)
 {
     XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont,
+                                                   contours_per_slab, out_len, out_nseg));
+}
+
+static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                const double* ycoord, const double* xcoord, double radius,
+                                const double* contours, int ncont, int contours_per_slab,
+                                double* out_len, uint64_t* out_nseg)
+{
     if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
         return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad arguments");
     if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad dtype");
@@ -1391,6 +1414,13 @@ int xc_last_hist_variant(xc_ctx* ctx, xc_hist_variant* out)
 {
     if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_hist_variant: bad arguments");
     *out = ctx->last_hist;
+    return XC_OK;
+}
+
+int xc_last_clen_geometry(xc_ctx* ctx, xc_clen_geometry* out)
+{
+    if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_clen_geometry: bad arguments");
+    *out = ctx->last_clen;
     return XC_OK;
 }
 

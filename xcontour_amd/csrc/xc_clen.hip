@@ -283,11 +283,19 @@ int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
     // CLEN_RB * CLEN_TPB / ncopy of them
     const int64_t max_tiles = (int64_t)CLEN_COPY_CELLS * ncopy / (CLEN_RB * CLEN_TPB);
     int64_t bps = 0;
+    int bps_rule = 0;
     if (ntile > 0) {
-        bps = 2048 / nslab; if (bps < 8) bps = 8;
+        bps = 2048 / nslab; bps_rule = XC_CLEN_BPS_SHARE;
+        if (bps < 8) { bps = 8; bps_rule = XC_CLEN_BPS_FLOOR; }
         const int64_t need = (ntile + max_tiles - 1) / max_tiles;
-        if (bps < need) bps = need;
-        if (bps > ntile) bps = ntile;
+        if (bps < need) { bps = need; bps_rule = XC_CLEN_BPS_CAPACITY; }
+        if (bps > ntile) { bps = ntile; bps_rule = XC_CLEN_BPS_NTILE; }
+    }
+    {   // (xc_last_clen_geometry; the C entry points clear it when the call fails)
+        xc_clen_geometry& g = ctx->last_clen;
+        g = xc_clen_geometry{};
+        g.q_dtype = q_dtype; g.latlon = radius > 0.0; g.N = N; g.ncopy = ncopy; g.G = G; g.ngroup = ngroup;
+        g.ntile = ntile; g.bps = (int32_t)bps; g.bps_rule = bps_rule; g.nslab = nslab;
     }
     const size_t al = 256;
     auto up = [&](size_t b) { return (b + al - 1) & ~(al - 1); };

@@ -93,6 +93,7 @@ struct xc_ctx {
     void* single_ws = nullptr;  unsigned single_launches = 0;  int single_dirty_bins[2] = {0, 0};
     int last_keff_path = 0;     // last xc_keff_dev call: 0 min/max pass + histogram pass (two reads of the tracer), 1 the single-read kernel
     xc_hist_variant last_hist = {};   // last xc_hist(_dev) / xc_keff_dev call: the histogram instantiation and geometry launched (launch_three, launch_s4)
+    xc_clen_geometry last_clen = {};  // last xc_contour_lengths(_dev) call: K10's launch geometry (launch_contour_lengths)
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
