@@ -1,0 +1,336 @@
+// C ABI, part 4: the host forms of the kernels outside the Keff chain -- row sums (K2), the squared gradient (K4), the local wave
+// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip),
+// synthetic slabs -- and the records of what they launched.
+#include "xc_capi.h"
+#include <cmath>
+
+using namespace xc;
+
+// the levels of K9 / K10, [nc][ncont]: ascending (ties allowed), no NaN
+static bool check_ascending(const double* contours, int64_t nc, int ncont)
+{
+    for (int64_t s = 0; s < nc; ++s)
+        for (int k = 0; k < ncont; ++k) {
+            const double c = contours[s * ncont + k];
+            if (c != c || (k > 0 && c < contours[s * ncont + k - 1])) return false;
+        }
+    return true;
+}
+
+// xc_last_clen_geometry: launch_contour_lengths writes the record where it picks the geometry; a call that fails leaves it cleared
+static int clen_recorded(xc_ctx* ctx, int rc)
+{
+    if (rc != XC_OK) ctx->last_clen = xc_clen_geometry{};
+    return rc;
+}
+
+static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                const double* ycoord, const double* xcoord, double radius,
+                                const double* contours, int ncont, int contours_per_slab,
+                                double* out_len, uint64_t* out_nseg)
+{
+    if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
+        return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad dtype");
+    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: radius must be >= 0");
+    for (int64_t i = 0; i < ny; ++i)
+        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
+    for (int64_t i = 0; i < nx; ++i)
+        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
+    const int64_t nc = contours_per_slab ? nslab : 1;
+    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_lengths: contours must be ascending without NaN");
+    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
+    const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + al(cb) + 2 * al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb); double* dc = (double*)st.take(cb);
+    double* dl = st.out(out_len, ob); uint64_t* dn = st.out(out_nseg, ob);
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, radius, dc, ncont, contours_per_slab, dl, dn));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------ K2
+int xc_rowsum_dev(xc_ctx* ctx, const void* mask, int mask_dtype, const double* dA, int dA_rank,
+                  int64_t ny, int64_t nx, int multiply, double* out_rows)
+{
+    XC_CTX(ctx);
+    return launch_rowsum(ctx, mask, mask_dtype, dA, dA_rank, ny, nx, multiply, out_rows);
+}
+
+int xc_rowsum(xc_ctx* ctx, const void* mask, int mask_dtype, const double* dA, int dA_rank,
+              int64_t ny, int64_t nx, int multiply, double* out_rows)
+{
+    XC_CTX(ctx);
+    if (!out_rows || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_rowsum: bad arguments");
+    if (mask && mask_dtype != XC_F32 && mask_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_rowsum: bad mask dtype");
+    const size_t mb = mask ? (size_t)ny * nx * esize(mask_dtype) : 0;
+    const size_t dab = dA_rank == XC_DA_SLAB ? 0 : dA_bytes(dA_rank, 1, ny, nx);     // (per-slab weights: left to the launcher to reject)
+    if (dab && !dA) return fail(ctx, XC_EBADARG, "xc_rowsum: dA is NULL");
+    XC_TRY(ensure_arena(ctx, al(mb) + al(dab) + al((size_t)ny * 8)));
+    Stage st(ctx);
+    void* dm = nullptr; double* dd = nullptr;
+    // (resident inputs are read where they are: no device-to-device copy into the arena)
+    if (mb) { const void* p; XC_TRY(stage_in(ctx, st.take(mb), mask, mb, &p)); dm = const_cast<void*>(p); }
+    if (dab) { const void* p; XC_TRY(stage_in(ctx, st.take(dab), dA, dab, &p)); dd = (double*)const_cast<void*>(p); }
+    double* dout = st.out(out_rows, (size_t)ny * 8, true);
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_rowsum(ctx, dm, mask_dtype, dd, dA_rank, ny, nx, multiply, dout));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// ------------------------------------------------------------------------------------ K4
+int xc_grad2_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                 const double* rdx, const double* rdy, int periodic_x, double* out)
+{
+    XC_CTX(ctx);
+    return launch_grad2(ctx, q, q_dtype, nslab, ny, nx, rdx, rdy, periodic_x, out);
+}
+
+int xc_grad2(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+             const double* rdx, const double* rdy, int periodic_x, double* out)
+{
+    XC_CTX(ctx);
+    if (!q || !rdx || !rdy || !out || nslab < 1 || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_grad2: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_grad2: bad dtype");
+    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype), ob = cells * 8, rb = (size_t)ny * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(ob) + 2 * al(rb)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dx = (double*)st.take(rb); double* dy = (double*)st.take(rb); double* dout = st.out(out, ob);
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dx, rdx, rb)); XC_TRY(h2d(ctx, dy, rdy, rb));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_grad2(ctx, pq, q_dtype, nslab, ny, nx, dx, dy, periodic_x, dout));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// ------------------------------------------------------------------------------------ K9
+int xc_crossing_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                    int pad_x, int pad_mode, const double* contours, int ncont, int contours_per_slab,
+                    const void* area, int area_dtype, int area_per_slab, int stride, int full_width,
+                    double* out_len, uint64_t* out_cnt)
+{
+    XC_CTX(ctx);
+    return launch_crossing(ctx, q, q_dtype, nslab, ny, nx, pad_x, pad_mode, contours, ncont, contours_per_slab,
+                           area, area_dtype, area_per_slab, stride, full_width, out_len, out_cnt);
+}
+
+int xc_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                int pad_x, int pad_mode, const double* contours, int ncont, int contours_per_slab,
+                const void* area, int area_dtype, int area_per_slab, int stride, int full_width,
+                double* out_len, uint64_t* out_cnt)
+{
+    XC_CTX(ctx);
+    if (!q || !contours || !area || (!out_len && !out_cnt) || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
+        return fail(ctx, XC_EBADARG, "xc_crossing: bad arguments");
+    if ((q_dtype != XC_F32 && q_dtype != XC_F64) || (area_dtype != XC_F32 && area_dtype != XC_F64))
+        return fail(ctx, XC_EBADARG, "xc_crossing: bad dtype");
+    const int64_t nc = contours_per_slab ? nslab : 1;
+    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_crossing: contours must be ascending without NaN");
+    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
+    const size_t ab = (area_per_slab ? cells : (size_t)ny * nx) * esize(area_dtype);
+    const size_t cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(ab) + al(cb) + 2 * al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); void* da = st.take(ab); double* dc = (double*)st.take(cb);
+    double* dl = st.out(out_len, ob); uint64_t* dn = st.out(out_cnt, ob);
+    const void* pq; const void* pa;                          // (tracer / areas with a device mirror are read where they are)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(stage_in(ctx, da, area, ab, &pa)); XC_TRY(h2d(ctx, dc, contours, cb));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_crossing(ctx, pq, q_dtype, nslab, ny, nx, pad_x, pad_mode, dc, ncont, contours_per_slab,
+                           pa, area_dtype, area_per_slab, stride, full_width, dl, dn));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// ------------------------------------------------------------------------------------ K10
+int xc_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                           const double* ycoord, const double* xcoord, double radius,
+                           const double* contours, int ncont, int contours_per_slab,
+                           double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont,
+                                                     contours_per_slab, out_len, out_nseg));
+}
+
+int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                       const double* ycoord, const double* xcoord, double radius,
+                       const double* contours, int ncont, int contours_per_slab,
+                       double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont,
+                                                   contours_per_slab, out_len, out_nseg));
+}
+
+int xc_last_clen_geometry(xc_ctx* ctx, xc_clen_geometry* out)
+{
+    if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_clen_geometry: bad arguments");
+    *out = ctx->last_clen;
+    return XC_OK;
+}
+
+// ------------------------------------------------------------------------------------ K7
+int xc_lwa_dev(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const double* coord,
+               const double* dA, int dA_rank, double dA_max, const double* M, int M_rank,
+               int64_t nslab, int64_t ny, int64_t nx, int increase, int part, int variant,
+               const int32_t* mask_idx, int nmask, double* out_lwa, int8_t* out_masks)
+{
+    XC_CTX(ctx);
+    return launch_lwa(ctx, q, q_dtype, Q, coord, dA, dA_rank, dA_max, M, M_rank, nslab, ny, nx,
+                      increase, part, variant, mask_idx, nmask, out_lwa, out_masks);
+}
+
+int xc_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const double* coord,
+           const double* dA, int dA_rank, double dA_max, const double* M, int M_rank,
+           int64_t nslab, int64_t ny, int64_t nx, int increase, int part, int variant,
+           const int32_t* mask_idx, int nmask, double* out_lwa, int8_t* out_masks)
+{
+    XC_CTX(ctx);
+    if (!q || !Q || !coord || !dA || !out_lwa || nslab < 1 || ny < 2 || nx < 1) return fail(ctx, XC_EBADARG, "xc_lwa: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_lwa: bad dtype");
+    if (nmask < 0 || (nmask > 0 && (!mask_idx || !out_masks))) return fail(ctx, XC_EBADARG, "xc_lwa: mask arguments");
+    for (int i = 0; i < nmask; ++i)
+        if (mask_idx[i] < 0 || mask_idx[i] >= ny) return fail(ctx, XC_EBADARG, "indices in mask_idx out of boundary");
+    const size_t cells = (size_t)nslab * ny * nx;
+    const size_t qb = cells * esize(q_dtype), Qb = (size_t)nslab * ny * 8, cb = (size_t)ny * 8;
+    const size_t dab = dA_bytes(dA_rank, 1, ny, nx), Mb = dA_bytes(M_rank, 1, ny, nx);      // (ROW or PLANE, checked by the launcher; M: or none)
+    const size_t ob = cells * 8, mib = (size_t)nmask * 4, mob = (size_t)nmask * cells;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(Qb) + al(cb) + al(dab) + al(Mb) + al(ob) + al(mib) + al(mob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dQ = (double*)st.take(Qb); double* dc = (double*)st.take(cb);
+    double* dd = (double*)st.take(dab); double* dM = Mb ? (double*)st.take(Mb) : nullptr;
+    double* dout = st.out(out_lwa, ob);
+    int32_t* dmi = nmask ? (int32_t*)st.take(mib) : nullptr; int8_t* dmo = nmask ? st.out(out_masks, mob) : nullptr;
+    // the read-only planes are used where they are when they have a device mirror (the weights of a resident object: no device-to-device
+    // copy per call); Q and the coordinate are small (pinned buffer + copy kernel)
+    const void* pq; const void* pd; const void* pM = nullptr;
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dQ, Q, Qb)); XC_TRY(h2d(ctx, dc, coord, cb)); XC_TRY(stage_in(ctx, dd, dA, dab, &pd));
+    if (Mb) XC_TRY(stage_in(ctx, dM, M, Mb, &pM));
+    if (nmask) XC_TRY(h2d(ctx, dmi, mask_idx, mib));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_lwa(ctx, pq, q_dtype, dQ, dc, (const double*)pd, dA_rank, dA_max, (const double*)pM, M_rank, nslab, ny, nx, increase, part, variant,
+                      dmi, nmask, dout, dmo));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// ------------------------------------------------------------------------------------ K8
+int xc_sort_profile_batch_dev(xc_ctx* ctx, const void* q, int q_dtype, const void* mask, int mask_dtype, int mask_per_slab,
+                              const double* dA, int dA_rank, int64_t nslab, int64_t ny, int64_t nx, int negate,
+                              const double* targets, int J, const double* tbl, const double* coord, int ntbl,
+                              double* out_Q, double* out_qsorted, double* out_acum, uint32_t* out_nvalid, double* out_bpe)
+{
+    XC_CTX(ctx);
+    if (ny < 1 || nx < 1 || nslab < 1) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad shape");
+    XC_TRY(ensure_scratch(ctx, sort_workspace_bytes(ny * nx, nslab)));
+    return launch_sort_profile(ctx, q, q_dtype, mask, mask_dtype, mask_per_slab, dA, dA_rank, nslab, ny, nx, negate,
+                               targets, J, tbl, coord, ntbl, ctx->scratch, out_Q, out_qsorted, out_acum, out_nvalid, out_bpe);
+}
+
+int xc_sort_profile_batch(xc_ctx* ctx, const void* q, int q_dtype, const void* mask, int mask_dtype, int mask_per_slab,
+                          const double* dA, int dA_rank, int64_t nslab, int64_t ny, int64_t nx, int negate,
+                          const double* targets, int J, const double* tbl, const double* coord, int ntbl,
+                          double* out_Q, double* out_qsorted, double* out_acum, uint32_t* out_nvalid, double* out_bpe)
+{
+    XC_CTX(ctx);
+    if (!q || ny < 1 || nx < 1 || nslab < 1 || J < 0) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad dtype");
+    if (mask && mask_dtype != XC_F32 && mask_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad mask dtype");
+    const size_t S = (size_t)nslab, n = (size_t)ny * nx;
+    const size_t qb = S * n * esize(q_dtype), mb = mask ? (mask_per_slab ? S : 1) * n * esize(mask_dtype) : 0;
+    const size_t dab = dA_bytes(dA_rank, nslab, ny, nx);
+    if (dab && !dA) return fail(ctx, XC_EBADARG, "xc_sort_profile: dA is NULL");
+    const size_t tb = (size_t)J * 8, Qb = S * tb, tbb = (out_bpe ? (size_t)ntbl * 8 : 0);
+    XC_TRY(ensure_arena(ctx, al(qb) + al(mb) + al(dab) + al(tb) + al(Qb) + 2 * al(tbb) + 2 * al(S * n * 8) + al(S * 4) + al(S * 8)));
+    Stage st(ctx);
+    void* dq = st.take(qb); XC_TRY(h2d(ctx, dq, q, qb));
+    void* dm = nullptr; if (mb) { dm = st.take(mb); XC_TRY(h2d(ctx, dm, mask, mb)); }
+    double* dd = nullptr; if (dab) { dd = (double*)st.take(dab); XC_TRY(h2d(ctx, dd, dA, dab)); }
+    double* dt = nullptr; double* dQ = nullptr;
+    if (J > 0 && out_Q) { dt = (double*)st.take(tb); dQ = st.out(out_Q, Qb); XC_TRY(h2d(ctx, dt, targets, tb)); }
+    double *dtbl = nullptr, *dcrd = nullptr;
+    if (out_bpe) {
+        if (!tbl || !coord || ntbl < 2) return fail(ctx, XC_EBADARG, "xc_sort_profile: BPE needs tbl/coord");
+        dtbl = (double*)st.take(tbb); dcrd = (double*)st.take(tbb);
+        XC_TRY(h2d(ctx, dtbl, tbl, tbb)); XC_TRY(h2d(ctx, dcrd, coord, tbb));
+    }
+    double* dqs = st.out(out_qsorted, S * n * 8); double* dac = st.out(out_acum, S * n * 8);
+    uint32_t* dnv = st.keep(out_nvalid, S * 4);              // (the kernel counts whether the caller asks or not)
+    double* dbpe = st.out(out_bpe, S * 8);
+    XC_TRY(flush_in(ctx));
+    XC_TRY(xc_sort_profile_batch_dev(ctx, dq, q_dtype, dm, mask_dtype, mask_per_slab, dd, dA_rank, nslab, ny, nx, negate,
+                                     dt, dQ ? J : 0, dtbl, dcrd, ntbl, dQ, dqs, dac, dnv, dbpe));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+int xc_sort_profile_dev(xc_ctx* ctx, const void* q, int q_dtype, const void* mask, int mask_dtype,
+                        const double* dA, int dA_rank, int64_t ny, int64_t nx, int negate,
+                        const double* targets, int J, const double* tbl, const double* coord, int ntbl,
+                        double* out_Q, double* out_qsorted, double* out_acum, uint32_t* out_nvalid, double* out_bpe)
+{
+    if (dA_rank == XC_DA_SLAB) return fail(ctx, XC_EBADARG, "xc_sort_profile: dA_rank must be NONE, ROW or PLANE");
+    return xc_sort_profile_batch_dev(ctx, q, q_dtype, mask, mask_dtype, 0, dA, dA_rank, 1, ny, nx, negate, targets, J, tbl, coord, ntbl,
+                                     out_Q, out_qsorted, out_acum, out_nvalid, out_bpe);
+}
+
+int xc_sort_profile(xc_ctx* ctx, const void* q, int q_dtype, const void* mask, int mask_dtype,
+                    const double* dA, int dA_rank, int64_t ny, int64_t nx, int negate,
+                    const double* targets, int J, const double* tbl, const double* coord, int ntbl,
+                    double* out_Q, double* out_qsorted, double* out_acum, uint32_t* out_nvalid, double* out_bpe)
+{
+    if (dA_rank == XC_DA_SLAB) return fail(ctx, XC_EBADARG, "xc_sort_profile: dA_rank must be NONE, ROW or PLANE");
+    return xc_sort_profile_batch(ctx, q, q_dtype, mask, mask_dtype, 0, dA, dA_rank, 1, ny, nx, negate, targets, J, tbl, coord, ntbl,
+                                 out_Q, out_qsorted, out_acum, out_nvalid, out_bpe);
+}
+
+int xc_set_lwa_exact(xc_ctx* ctx, int exact)
+{
+    if (!ctx) return fail(nullptr, XC_EBADARG, "null context");
+    if (exact < 0 || exact > 3) return fail(ctx, XC_EBADARG, "xc_set_lwa_exact: mode must be 0 (automatic), 1 (band walk), 2 (interval kernel, checked) or 3 (interval kernel, premises vouched for)");
+    ctx->lwa_exact = exact;
+    return XC_OK;
+}
+
+int xc_last_lwa_path(xc_ctx* ctx, int* out_path)
+{
+    if (!ctx || !out_path) return fail(ctx, XC_EBADARG, "xc_last_lwa_path: bad arguments");
+    if (ctx->last_lwa_path < 0) {                                      // decided by the device-side check of the last call: read its flag
+        unsigned f = 0;
+        XC_HIP(ctx, hipSetDevice(ctx->device));
+        XC_HIP(ctx, hipMemcpyAsync(&f, ctx->lwa_flag, sizeof(f), hipMemcpyDeviceToHost, ctx->stream));
+        XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->last_lwa_path = (f == ctx->lwa_epoch) ? 2 : 1;
+    }
+    *out_path = ctx->last_lwa_path;
+    return XC_OK;
+}
+
+int xc_last_sort_path(xc_ctx* ctx, int* out_path)
+{
+    if (!ctx || !out_path) return fail(ctx, XC_EBADARG, "xc_last_sort_path: bad arguments");
+    *out_path = ctx->last_sort_path;
+    return XC_OK;
+}
+
+// ------------------------------------------------------------------------------------ synthetic slabs
+int xc_synth_dev(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                 const double* lat_deg, const double* lon_deg, uint64_t seed, int variant)
+{
+    XC_CTX(ctx);
+    if (out && nslab > 0 && ny > 0 && nx > 0) mm_touch(ctx, out, (size_t)nslab * ny * nx * esize(q_dtype));
+    return launch_synth(ctx, out, q_dtype, nslab, ny, nx, lat_deg, lon_deg, seed, variant);
+}
+
+}  // extern "C"
