@@ -7,6 +7,7 @@ is visible, every compute entry point raises.  `load()` only dlopen()s the
 library (works on a GPU-less build box so that symbol / ABI checks can run);
 `Context()` is what needs the device.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -257,9 +258,55 @@ def _stack_in(q):
     return q if _is_lazy(q) else _contig(q)
 
 
-def _stack_now(q):
-    """the batch is about to be staged on the device: a lazy stack is read now (this one batch, nothing more)"""
-    return np.ascontiguousarray(q[:]) if _is_lazy(q) else q
+def _stack_now(q, s0, s1):
+    """slabs [s0, s1) of a stack, about to be staged on the device: a lazy stack is read now (this one batch, nothing more)"""
+    if _is_lazy(q):
+        return np.ascontiguousarray(q[s0:s1])
+    return q if s1 - s0 == q.shape[0] else q[s0:s1]
+
+
+def _part(a, slab_ndim, s0, s1):
+    """what batch [s0, s1) sees of an argument: its own slabs when the argument rides on the slab axis (it has `slab_ndim` dims, the
+    first of them the slabs), all of it when every slab shares it (fewer dims, or None)"""
+    return a[s0:s1] if a is not None and a.ndim == slab_ndim else a
+
+
+def _join(parts):
+    """the results of the batches of one call, in order -> the result of the call: ndarrays are joined along axis 0 (the slabs), a
+    tuple / list / dict is joined member by member (so is the list over strides of `crossing`), None stays None"""
+    p0 = parts[0]
+    if p0 is None:
+        return None
+    if isinstance(p0, dict):
+        return {k: _join([p[k] for p in parts]) for k in p0}
+    if isinstance(p0, (tuple, list)):
+        return type(p0)(_join([p[i] for p in parts]) for i in range(len(p0)))
+    return np.concatenate(parts)
+
+
+def _f48(a):
+    """float32 / float64 arrays as they are, anything else as float64"""
+    return a if a.dtype in _DT_CODES else a.astype(np.float64)
+
+
+def _weight_rank(shape, ny, nx, nslab=None, text=None):
+    """XC_DA_* of a weight array from its shape: (ny,) / (ny, nx) / (nslab, ny, nx) -- the last only for callers that take per-slab
+    weights (they pass `nslab`).  Any other shape raises the caller's own complaint `text` (callers without one asserted)"""
+    if shape == (ny,):
+        return XC_DA_ROW
+    if shape == (ny, nx):
+        return XC_DA_PLANE
+    if nslab is not None and shape == (nslab, ny, nx):
+        return XC_DA_SLAB
+    if text is None:
+        raise AssertionError()
+    raise XContourHipError(XC_EBADARG, text)
+
+
+def _check_ascending(contours, who):
+    """the host entry points validate the contours; the device ones trust their caller"""
+    if np.isnan(contours).any() or (np.diff(contours, axis=-1) < 0).any():
+        raise XContourHipError(XC_EEDGES, '%s: contours must be ascending without NaN' % who)
 
 
 class DeviceBuffer(object):
@@ -586,32 +633,54 @@ class Context(object):
         b = max(1, min(int(nslab), MAX_SLABS_PER_LAUNCH, int(self.max_batch_bytes) // max(1, int(per_slab_bytes))))
         return [(s0, min(int(nslab), s0 + b)) for s0 in range(0, int(nslab), b)]
 
-    def minmax(self, q):
-        """q: (nslab, ny, nx) or (nslab, ncell) f32/f64 -> (nslab, 2) f64"""
-        q = _stack_in(q)
+    def _batched(self, nslab, per_slab_bytes, one):
+        """the batching of every host-form call: the slab axis is cut into batches of whole slabs (`_batches`) from the bytes a slab
+        stages, `one(s0, s1)` does the batch of slabs [s0, s1) -- it is what reads a lazy stack -- and the results of the batches, run
+        in order, are joined along the slab axis (`_join`)"""
+        bt = self._batches(nslab, per_slab_bytes)
+        if len(bt) <= 1:
+            return one(0, nslab)
+        return _join([one(s0, s1) for s0, s1 in bt])
+
+    @contextlib.contextmanager
+    def _temporaries(self, inputs, out_nbytes):
+        """device copies of `inputs` and allocations of `out_nbytes` bytes for one call of a `_dev` entry point (freed on the way out)"""
+        bufs = [self.to_device(a) for a in inputs] + [self.alloc(n) for n in out_nbytes]
+        try:
+            yield bufs
+        finally:
+            for b in bufs:
+                b.free()
+
+    def _minmax_of(self, q):
         nslab = q.shape[0]
-        bt = self._batches(nslab, q.nbytes // max(1, nslab))
-        if len(bt) > 1:
-            return np.concatenate([self.minmax(q[s0:s1]) for s0, s1 in bt])
-        q = _stack_now(q)
         out = np.empty((nslab, 2), dtype=np.float64)
         self._check(self.lib.xc_minmax(self.handle, _ptr(q), dtype_code(q.dtype), nslab,
                                        int(q.size // nslab), _ptr(out)))
         return out
 
+    def minmax(self, q):
+        """q: (nslab, ny, nx) or (nslab, ncell) f32/f64 -> (nslab, 2) f64"""
+        q = _stack_in(q)
+        nslab = q.shape[0]
+        return self._batched(nslab, q.nbytes // max(1, nslab), lambda s0, s1: self._minmax_of(_stack_now(q, s0, s1)))
+
     def contours(self, q, N, increase, ctr_dtype, right_edge=XC_EDGE_XHISTOGRAM, want_minmax=False):
         """cal_contours(int) in one call (xc_contours): q (nslab, ny, nx) -> levels (nslab, N) float64 [, minmax (nslab, 2)]"""
         q = _stack_in(q)
         nslab = q.shape[0]
-        bt = self._batches(nslab, q.nbytes // max(1, nslab))
-        if len(bt) > 1 or _is_lazy(q):
-            mm = self.minmax(q)
+
+        def one(s0, s1):
+            if s1 - s0 < nslab or _is_lazy(q):                   # a part of the stack (or a lazy one): its min/max alone, the
+                return None, self._minmax_of(_stack_now(q, s0, s1))      # levels follow from the joined min/max below
+            ctr = np.empty((nslab, N), dtype=np.float64)
+            mm = np.empty((nslab, 2), dtype=np.float64) if want_minmax else None
+            self._check(self.lib.xc_contours(self.handle, _ptr(q), dtype_code(q.dtype), nslab, int(q.size // nslab), int(N),
+                                             int(bool(increase)), dtype_code(ctr_dtype), int(right_edge), _ptr(mm), _ptr(ctr), None, None))
+            return ctr, mm
+        ctr, mm = self._batched(nslab, q.nbytes // max(1, nslab), one)
+        if ctr is None:
             ctr = self.levels(mm, q.dtype, N, increase, ctr_dtype, right_edge)[0]
-            return (ctr, mm) if want_minmax else ctr
-        ctr = np.empty((nslab, N), dtype=np.float64)
-        mm = np.empty((nslab, 2), dtype=np.float64) if want_minmax else None
-        self._check(self.lib.xc_contours(self.handle, _ptr(q), dtype_code(q.dtype), nslab, int(q.size // nslab), int(N),
-                                         int(bool(increase)), dtype_code(ctr_dtype), int(right_edge), _ptr(mm), _ptr(ctr), None, None))
         return (ctr, mm) if want_minmax else ctr
 
     def trace(self, reset=True):
@@ -641,87 +710,65 @@ class Context(object):
         assert q.ndim == 3
         nslab, ny, nx = q.shape
         integrands = [v if _is_lazy(v) else np.asarray(v) for v in integrands]     # (nested lists are fine, as for q)
-        per = ny * nx * (q.dtype.itemsize + sum(np.dtype(v.dtype).itemsize for v in integrands) + (8 if dA is not None and np.ndim(dA) == 3 else 0))
-        bt = self._batches(nslab, per)
-        if len(bt) > 1:                                      # more than one launch / one arena takes: batches of whole slabs
-            parts = []
-            for s0, s1 in bt:
-                sl = slice(s0, s1)
-                e = np.asarray(edges)
-                d3 = dA is not None and np.ndim(dA) == 3
-                parts.append(self.hist(q[sl], e[sl] if e.ndim == 2 else e, dA[sl] if d3 else dA,
-                                       [v[sl] for v in integrands], grad, last_closed, lt, reverse,
-                                       prod_f32, negate, want, deterministic))
-            return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-        q = _stack_now(q)
-        integrands = [_stack_now(v) for v in integrands]
-        edges = _contig(edges, np.float64)
         d = HistDesc()
-        keep = [q, edges]
-        d.q, d.q_dtype = _ptr(q), dtype_code(q.dtype)
-        d.nslab, d.ny, d.nx = nslab, ny, nx
-        d.edges, d.nedge = _ptr(edges), edges.shape[-1]
+        d.q_dtype = dtype_code(q.dtype)
+        d.ny, d.nx = ny, nx
+        edges = _contig(edges, np.float64)
+        d.nedge = edges.shape[-1]
         d.edges_per_slab = 1 if edges.ndim == 2 else 0
         if edges.ndim == 2 and edges.shape[0] != nslab:
             raise XContourHipError(XC_EBADARG, 'edges must be (nedge,) or (nslab, nedge)')
         d.last_closed = 1 if last_closed else 0
-        if dA is None:
-            d.dA, d.dA_rank = None, XC_DA_NONE
-        else:
+        if dA is not None:                                   # (else XC_DA_NONE, a null pointer: the descriptor's zeros)
             dA = _contig(dA, np.float64)
-            keep.append(dA)
-            if dA.shape == (ny,):
-                d.dA_rank = XC_DA_ROW
-            elif dA.shape == (ny, nx):
-                d.dA_rank = XC_DA_PLANE
-            elif dA.shape == (nslab, ny, nx):
-                d.dA_rank = XC_DA_SLAB
-            else:
-                raise XContourHipError(XC_EBADARG, 'dA must be (ny,), (ny,nx) or (nslab,ny,nx)')
-            d.dA = _ptr(dA)
+            d.dA_rank = _weight_rank(dA.shape, ny, nx, nslab, 'dA must be (ny,), (ny,nx) or (nslab,ny,nx)')
         d.prod_f32 = 1 if prod_f32 else 0
         d.nint = len(integrands)
         if d.nint > XC_MAX_INTEGRANDS:
             raise XContourHipError(XC_EBADARG, 'at most %d integrands per pass' % XC_MAX_INTEGRANDS)
+        per = q.dtype.itemsize + (8 if d.dA_rank == XC_DA_SLAB else 0)        # bytes per cell that a batch stages
         for i, v in enumerate(integrands):
-            v = _contig(v)
             if v.shape != q.shape:
                 raise XContourHipError(XC_EBADARG, 'integrand shape must equal tracer shape')
-            keep.append(v)
-            d.integrand[i], d.integrand_dtype[i] = v.ctypes.data, dtype_code(v.dtype)
+            d.integrand_dtype[i] = dtype_code(v.dtype)
+            per += np.dtype(v.dtype).itemsize
         if grad is not None:
             rdx = np.ascontiguousarray(grad[0], dtype=np.float64)
             rdy = np.ascontiguousarray(grad[1], dtype=np.float64)
             assert rdx.shape == (ny,) and rdy.shape == (ny,)
-            keep += [rdx, rdy]
             d.grad, d.rdx, d.rdy, d.periodic_x = 1, _ptr(rdx), _ptr(rdy), 1 if grad[2] else 0
         d.lt, d.reverse, d.negate = 1 if lt else 0, 1 if reverse else 0, 1 if negate else 0
         d.deterministic = 1 if deterministic else 0
         nch, nbin = 1 + d.nint + d.grad, d.nedge - 1
-        out = {}
-        if 'pdf' in want:
-            out['pdf'] = np.empty((nslab, nch, nbin), dtype=np.float64)
-            d.pdf = _ptr(out['pdf'])
-        if 'cdf' in want:
-            out['cdf'] = np.empty((nslab, nch, nbin), dtype=np.float64)
-            d.cdf = _ptr(out['cdf'])
-        if 'counts' in want:
-            out['counts'] = np.empty((nslab, nbin), dtype=np.uint64)
-            d.counts = _ptr(out['counts'])
-        self._check(self.lib.xc_hist(self.handle, C.byref(d)))
-        return out
+
+        def one(s0, s1):
+            qb, eb, db = _stack_now(q, s0, s1), _part(edges, 2, s0, s1), _part(dA, 3, s0, s1)
+            vb = [_contig(_stack_now(v, s0, s1)) for v in integrands]
+            d.q, d.nslab, d.edges, d.dA = _ptr(qb), s1 - s0, _ptr(eb), _ptr(db)
+            for i, v in enumerate(vb):
+                d.integrand[i] = v.ctypes.data
+            out = {}
+            if 'pdf' in want:
+                out['pdf'] = np.empty((s1 - s0, nch, nbin), dtype=np.float64)
+                d.pdf = _ptr(out['pdf'])
+            if 'cdf' in want:
+                out['cdf'] = np.empty((s1 - s0, nch, nbin), dtype=np.float64)
+                d.cdf = _ptr(out['cdf'])
+            if 'counts' in want:
+                out['counts'] = np.empty((s1 - s0, nbin), dtype=np.uint64)
+                d.counts = _ptr(out['counts'])
+            self._check(self.lib.xc_hist(self.handle, C.byref(d)))
+            return out
+        return self._batched(nslab, ny * nx * per, one)      # more than one launch / one arena takes: batches of whole slabs
 
     def rowsum(self, mask, dA, ny, nx, multiply=False):
         if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            if mask.dtype not in (np.float32, np.float64):
-                mask = mask.astype(np.float64)
+            mask = _f48(np.ascontiguousarray(mask))
             assert mask.shape == (ny, nx)
         rank = XC_DA_NONE
         if dA is not None:
             dA = np.ascontiguousarray(dA, dtype=np.float64)
-            rank = XC_DA_ROW if dA.shape == (ny,) else XC_DA_PLANE
-            assert dA.shape in ((ny,), (ny, nx))
+            rank = _weight_rank(dA.shape, ny, nx)
         out = np.empty(ny, dtype=np.float64)
         self._check(self.lib.xc_rowsum(self.handle, _ptr(mask), dtype_code(mask.dtype) if mask is not None else XC_F64,
                                        _ptr(dA), rank, ny, nx, 1 if multiply else 0, _ptr(out)))
@@ -752,16 +799,16 @@ class Context(object):
         q = _stack_in(q)
         assert q.ndim == 3
         nslab, ny, nx = q.shape
-        bt = self._batches(nslab, ny * nx * (q.dtype.itemsize + 8))
-        if len(bt) > 1:
-            return np.concatenate([self.grad2(q[s0:s1], rdx, rdy, periodic_x) for s0, s1 in bt])
-        q = _stack_now(q)
         rdx = np.ascontiguousarray(rdx, dtype=np.float64)
         rdy = np.ascontiguousarray(rdy, dtype=np.float64)
-        out = np.empty(q.shape, dtype=np.float64)
-        self._check(self.lib.xc_grad2(self.handle, _ptr(q), dtype_code(q.dtype), nslab, ny, nx,
-                                      _ptr(rdx), _ptr(rdy), 1 if periodic_x else 0, _ptr(out)))
-        return out
+
+        def one(s0, s1):
+            qb = _stack_now(q, s0, s1)
+            out = np.empty(qb.shape, dtype=np.float64)
+            self._check(self.lib.xc_grad2(self.handle, _ptr(qb), dtype_code(q.dtype), s1 - s0, ny, nx,
+                                          _ptr(rdx), _ptr(rdy), 1 if periodic_x else 0, _ptr(out)))
+            return out
+        return self._batched(nslab, ny * nx * (q.dtype.itemsize + 8), one)
 
     def crossing(self, q, contours, area, stride=1, pad_x=0, pad_mode='edge', full_width=False):
         """Box-counting contour crossing (xc_crossing).  q (nslab, ny, nx) f32/f64; contours (N,) or
@@ -774,53 +821,41 @@ class Context(object):
         per_slab = contours.ndim == 2
         if per_slab and contours.shape[0] != nslab:
             raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
-        area = np.ascontiguousarray(area)
-        if area.dtype not in (np.float32, np.float64):
-            area = area.astype(np.float64)
+        area = _f48(np.ascontiguousarray(area))
         if area.shape not in ((ny, nx), (nslab, ny, nx)):
             raise XContourHipError(XC_EBADARG, 'area must be (ny, nx) or (nslab, ny, nx)')
         if pad_mode not in PAD_MODES:
             raise XContourHipError(XC_EBADARG, 'pad mode must be one of %s' % sorted(PAD_MODES))
         N = contours.shape[-1]
-        bt = self._batches(nslab, ny * nx * (q.dtype.itemsize + (area.dtype.itemsize if area.ndim == 3 else 0)))
-        if len(bt) > 1:
-            parts = [self.crossing(q[s0:s1], contours[s0:s1] if per_slab else contours, area[s0:s1] if area.ndim == 3 else area,
-                                   stride, pad_x, pad_mode, full_width) for s0, s1 in bt]
-            if np.ndim(stride) > 0:
-                return [(np.concatenate([p[i][0] for p in parts]), np.concatenate([p[i][1] for p in parts])) for i in range(len(parts[0]))]
-            return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
-        q = _stack_now(q)
         if np.ndim(stride) > 0:
-            # several strides on the same padded slab: one upload, one device call per stride
-            # (`stride` may be a list; returns lists of results in the same order)
             for t in stride:
                 if int(t) < 1:
                     raise XContourHipError(XC_EBADARG, 'stride must be >= 1')
-            # the host entry point validates the contours; the device one trusts its caller
-            c2 = contours.reshape(-1, N)
-            if np.isnan(c2).any() or (np.diff(c2, axis=1) < 0).any():
-                raise XContourHipError(XC_EEDGES, 'xc_crossing: contours must be ascending without NaN')
-            bufs = [self.to_device(q), self.to_device(contours), self.to_device(area),
-                    self.alloc(nslab * N * 8), self.alloc(nslab * N * 8)]
-            try:
-                out = []
-                for t in stride:
-                    self._check(self.lib.xc_crossing_dev(self.handle, bufs[0].ptr, dtype_code(q.dtype), nslab, ny, nx, int(pad_x),
-                                                         PAD_MODES[pad_mode], bufs[1].ptr, N, 1 if per_slab else 0,
-                                                         bufs[2].ptr, dtype_code(area.dtype), 1 if area.ndim == 3 else 0,
-                                                         int(t), 1 if full_width else 0, bufs[3].ptr, bufs[4].ptr))
-                    out.append((bufs[3].download((nslab, N), np.float64), bufs[4].download((nslab, N), np.uint64)))
-            finally:
-                for b in bufs:
-                    b.free()
-            return out
-        lens = np.empty((nslab, N), dtype=np.float64)
-        cnts = np.empty((nslab, N), dtype=np.uint64)
-        self._check(self.lib.xc_crossing(self.handle, _ptr(q), dtype_code(q.dtype), nslab, ny, nx, int(pad_x),
-                                         PAD_MODES[pad_mode], _ptr(contours), N, 1 if per_slab else 0,
-                                         _ptr(area), dtype_code(area.dtype), 1 if area.ndim == 3 else 0,
-                                         int(stride), 1 if full_width else 0, _ptr(lens), _ptr(cnts)))
-        return lens, cnts
+            _check_ascending(contours, 'xc_crossing')
+        # what every batch hands to xc_crossing / xc_crossing_dev between the tracer and the stride
+        shape = (ny, nx, int(pad_x), PAD_MODES[pad_mode])
+        flags = (N, 1 if per_slab else 0)
+        aflags = (dtype_code(area.dtype), 1 if area.ndim == 3 else 0)
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, cb, ab = _stack_now(q, s0, s1), _part(contours, 2, s0, s1), _part(area, 3, s0, s1)
+            if np.ndim(stride) > 0:
+                # several strides on the same padded slab: one upload, one device call per stride
+                # (`stride` may be a list; returns lists of results in the same order)
+                with self._temporaries([qb, cb, ab], [n * N * 8, n * N * 8]) as (dq, dc, da, dl, dn):
+                    out = []
+                    for t in stride:
+                        self._check(self.lib.xc_crossing_dev(self.handle, dq.ptr, dtype_code(q.dtype), n, *shape, dc.ptr, *flags,
+                                                             da.ptr, *aflags, int(t), 1 if full_width else 0, dl.ptr, dn.ptr))
+                        out.append((dl.download((n, N), np.float64), dn.download((n, N), np.uint64)))
+                return out
+            lens = np.empty((n, N), dtype=np.float64)
+            cnts = np.empty((n, N), dtype=np.uint64)
+            self._check(self.lib.xc_crossing(self.handle, _ptr(qb), dtype_code(q.dtype), n, *shape, _ptr(cb), *flags,
+                                             _ptr(ab), *aflags, int(stride), 1 if full_width else 0, _ptr(lens), _ptr(cnts)))
+            return lens, cnts
+        return self._batched(nslab, ny * nx * (q.dtype.itemsize + (area.dtype.itemsize if area.ndim == 3 else 0)), one)
 
     def contour_lengths(self, q, contours, ycoord, xcoord, radius=0.0):
         """Marching-squares contour lengths (xc_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours (N,) or
@@ -842,35 +877,27 @@ class Context(object):
                                    % (ycoord.size, xcoord.size, ny, nx))
         radius = float(radius)
         N = contours.shape[-1]
-        bt = self._batches(nslab, ny * nx * q.dtype.itemsize)
-        if len(bt) > 1:
-            parts = [self.contour_lengths(q[s0:s1], contours[s0:s1] if per_slab else contours, ycoord, xcoord, radius)
-                     for s0, s1 in bt]
-            return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
-        q = _stack_now(q)
-        lens = np.empty((nslab, N), dtype=np.float64)
-        cnts = np.empty((nslab, N), dtype=np.uint64)
-        qp = self.resident_ptr(q) if isinstance(q, np.ndarray) and q.flags.c_contiguous else None
-        if qp:
-            # the tracer is on the device already: only the small arrays cross (the device entry point trusts its caller)
-            if np.isnan(contours).any() or (np.diff(contours, axis=-1) < 0).any():
-                raise XContourHipError(XC_EEDGES, 'xc_contour_lengths: contours must be ascending without NaN')
-            if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
-                raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
-            bufs = [self.to_device(ycoord), self.to_device(xcoord), self.to_device(contours),
-                    self.alloc(lens.nbytes), self.alloc(cnts.nbytes)]
-            try:
-                self._check(self.lib.xc_contour_lengths_dev(self.handle, qp, dtype_code(q.dtype), nslab, ny, nx, bufs[0].ptr,
-                                                            bufs[1].ptr, radius, bufs[2].ptr, N, 1 if per_slab else 0,
-                                                            bufs[3].ptr, bufs[4].ptr))
-                return bufs[3].download((nslab, N), np.float64), bufs[4].download((nslab, N), np.uint64)
-            finally:
-                for b in bufs:
-                    b.free()
-        self._check(self.lib.xc_contour_lengths(self.handle, _ptr(q), dtype_code(q.dtype), nslab, ny, nx, _ptr(ycoord),
-                                                _ptr(xcoord), radius, _ptr(contours), N, 1 if per_slab else 0,
-                                                _ptr(lens), _ptr(cnts)))
-        return lens, cnts
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
+            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+            if qp:
+                # the tracer is on the device already: only the small arrays cross (the device entry point trusts its caller)
+                _check_ascending(cb, 'xc_contour_lengths')
+                if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
+                    raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
+                with self._temporaries([ycoord, xcoord, cb], [n * N * 8, n * N * 8]) as (dy, dx, dc, dl, dn):
+                    self._check(self.lib.xc_contour_lengths_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr,
+                                                                dx.ptr, radius, dc.ptr, N, 1 if per_slab else 0, dl.ptr, dn.ptr))
+                    return dl.download((n, N), np.float64), dn.download((n, N), np.uint64)
+            lens = np.empty((n, N), dtype=np.float64)
+            cnts = np.empty((n, N), dtype=np.uint64)
+            self._check(self.lib.xc_contour_lengths(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord),
+                                                    _ptr(xcoord), radius, _ptr(cb), N, 1 if per_slab else 0,
+                                                    _ptr(lens), _ptr(cnts)))
+            return lens, cnts
+        return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
     def lwa(self, q, Q, coord, dA, dA_max, M=None, increase=True, part=0, mask_idx=None, variant=0, exact=None):
         """`exact`: None (default) -- planes of up to 512 rows are summed in numpy's own order (bit-exact band walk), larger ones by
@@ -883,43 +910,39 @@ class Context(object):
         assert q.ndim == 3
         nslab, ny, nx = q.shape
         Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(nslab, ny)
-        bt = self._batches(nslab, ny * nx * (q.dtype.itemsize + 8 + (0 if mask_idx is None else len(mask_idx))))
-        if len(bt) > 1:
-            parts = [self.lwa(q[s0:s1], Q[s0:s1], coord, dA, dA_max, M, increase, part, mask_idx, variant, exact) for s0, s1 in bt]
-            return (np.concatenate([p[0] for p in parts]),
-                    None if parts[0][1] is None else np.concatenate([p[1] for p in parts]))
-        q = _stack_now(q)
         coord = np.ascontiguousarray(coord, dtype=np.float64)
         dA = np.ascontiguousarray(dA, dtype=np.float64)
-        dr = XC_DA_ROW if dA.shape == (ny,) else XC_DA_PLANE
-        assert dA.shape in ((ny,), (ny, nx))
+        dr = _weight_rank(dA.shape, ny, nx)
         mr = XC_DA_NONE
         if M is not None:
             M = np.ascontiguousarray(M, dtype=np.float64)
-            mr = XC_DA_ROW if M.shape == (ny,) else XC_DA_PLANE
-            assert M.shape in ((ny,), (ny, nx))
-        out = np.empty(q.shape, dtype=np.float64)
+            mr = _weight_rank(M.shape, ny, nx)
         nmask = 0 if mask_idx is None else len(mask_idx)
         mi = np.ascontiguousarray(mask_idx, dtype=np.int32) if nmask else None
-        mo = np.empty((nslab, nmask, ny, nx), dtype=np.int8) if nmask else None
-        mode = 0 if exact is None else (1 if exact else 0)
-        if exact is not None and not exact and variant == 0:
+        vouch = exact is not None and not exact and variant == 0
+        if vouch:
             sg = 1.0 if increase else -1.0
-            c64 = np.asarray(coord, dtype=np.float64)
-            dq, dc = np.diff(sg * Q, axis=1), np.diff(c64)
-            # FINITE, not only NaN-free: an infinite Q_j would make (Q'_j - c) * S0 = inf * 0 = NaN where the reference sums to 0
-            ok = bool(np.isfinite(Q).all()) and bool((dq >= 0).all()) and bool((dc > 0).all() or (dc < 0).all()) and not bool(np.isinf(q).any())
-            mode = 3 if ok else 1
-        self._check(self.lib.xc_set_lwa_exact(self.handle, mode))
-        try:
-            self._check(self.lib.xc_lwa(self.handle, _ptr(q), dtype_code(q.dtype), _ptr(Q), _ptr(coord),
-                                        _ptr(dA), dr, float(dA_max), _ptr(M), mr, nslab, ny, nx,
-                                        1 if increase else 0, int(part), int(variant), _ptr(mi), nmask, _ptr(out), _ptr(mo)))
-        finally:
-            self.lib.xc_set_lwa_exact(self.handle, 0)
-        return out, mo
+            dc = np.diff(coord)
+            dc_ok = bool((dc > 0).all() or (dc < 0).all())
 
-
+        def one(s0, s1):
+            qb, Qb = _stack_now(q, s0, s1), Q[s0:s1]
+            out = np.empty(qb.shape, dtype=np.float64)
+            mo = np.empty((s1 - s0, nmask, ny, nx), dtype=np.int8) if nmask else None
+            mode = 0 if exact is None else (1 if exact else 0)
+            if vouch:
+                # FINITE, not only NaN-free: an infinite Q_j would make (Q'_j - c) * S0 = inf * 0 = NaN where the reference sums to 0
+                ok = bool(np.isfinite(Qb).all()) and bool((np.diff(sg * Qb, axis=1) >= 0).all()) and dc_ok and not bool(np.isinf(qb).any())
+                mode = 3 if ok else 1
+            self._check(self.lib.xc_set_lwa_exact(self.handle, mode))
+            try:
+                self._check(self.lib.xc_lwa(self.handle, _ptr(qb), dtype_code(q.dtype), _ptr(Qb), _ptr(coord),
+                                            _ptr(dA), dr, float(dA_max), _ptr(M), mr, s1 - s0, ny, nx,
+                                            1 if increase else 0, int(part), int(variant), _ptr(mi), nmask, _ptr(out), _ptr(mo)))
+            finally:
+                self.lib.xc_set_lwa_exact(self.handle, 0)
+            return out, mo
+        return self._batched(nslab, ny * nx * (q.dtype.itemsize + 8 + nmask), one)
 
     def sort_profile(self, q, dA=None, mask=None, targets=None, tbl=None, coord=None,
                      want_sorted=False, want_acum=False, negate=False):
@@ -933,67 +956,50 @@ class Context(object):
             q = q[None]
         assert q.ndim == 3
         nslab, ny, nx = q.shape
-        # staged per slab: the tracer, per-slab mask / dA, the requested full-length outputs and the sort's own four work arrays
-        per = ny * nx * (q.dtype.itemsize + 32 + (8 if want_sorted else 0) + (8 if want_acum else 0) +
-                         (8 if dA is not None and np.ndim(dA) == 3 else 0) + (8 if mask is not None and np.ndim(mask) == 3 else 0))
-        bt = self._batches(nslab, per)
-        if len(bt) > 1:
-            parts = [self.sort_profile(q[s0:s1], dA[s0:s1] if dA is not None and np.ndim(dA) == 3 else dA,
-                                       mask[s0:s1] if mask is not None and np.ndim(mask) == 3 else mask,
-                                       targets, tbl, coord, want_sorted, want_acum, negate) for s0, s1 in bt]
-            return {k: np.concatenate([np.atleast_1d(p[k]) for p in parts]) for k in parts[0]}
-        q = _stack_now(q)
         rank = XC_DA_NONE
         if dA is not None:
             dA = np.ascontiguousarray(dA, dtype=np.float64)
-            if dA.shape == (ny,):
-                rank = XC_DA_ROW
-            elif dA.shape == (ny, nx):
-                rank = XC_DA_PLANE
-            elif dA.shape == (nslab, ny, nx):
-                rank = XC_DA_SLAB
-            else:
-                raise XContourHipError(XC_EBADARG, 'dA must be (ny,), (ny, nx) or (nslab, ny, nx)')
+            rank = _weight_rank(dA.shape, ny, nx, nslab, 'dA must be (ny,), (ny, nx) or (nslab, ny, nx)')
         per_slab = 0
         if mask is not None:
-            mask = np.ascontiguousarray(mask)
-            if mask.dtype not in (np.float32, np.float64):
-                mask = mask.astype(np.float64)
+            mask = _f48(np.ascontiguousarray(mask))
             if mask.shape == (nslab, ny, nx) and not (single and mask.ndim == 2):
                 per_slab = 1
             elif mask.shape != (ny, nx):
                 raise XContourHipError(XC_EBADARG, 'mask must be (ny, nx) or (nslab, ny, nx)')
-        out = {}
-        J = 0
-        Q = None
+        J = ntbl = 0
         if targets is not None:
             targets = np.ascontiguousarray(targets, dtype=np.float64)
             J = len(targets)
-            Q = np.empty((nslab, J), dtype=np.float64)
-        qs = np.empty((nslab, ny * nx), dtype=np.float64) if want_sorted else None
-        ac = np.empty((nslab, ny * nx), dtype=np.float64) if want_acum else None
-        nv = np.zeros(nslab, dtype=np.uint32)
-        bpe = None
-        ntbl = 0
         if tbl is not None:
             tbl = np.ascontiguousarray(tbl, dtype=np.float64)
             coord = np.ascontiguousarray(coord, dtype=np.float64)
             ntbl = len(tbl)
-            bpe = np.zeros(nslab, dtype=np.float64)
-        self._check(self.lib.xc_sort_profile_batch(self.handle, _ptr(q), dtype_code(q.dtype), _ptr(mask),
-                                                   dtype_code(mask.dtype) if mask is not None else XC_F64, per_slab,
-                                                   _ptr(dA), rank, nslab, ny, nx, 1 if negate else 0, _ptr(targets), J,
-                                                   _ptr(tbl), _ptr(coord), ntbl,
-                                                   _ptr(Q), _ptr(qs), _ptr(ac), _ptr(nv), _ptr(bpe)))
-        out['nvalid'] = int(nv[0]) if single else nv.astype(np.int64)
-        if Q is not None:
-            out['Q'] = Q[0] if single else Q
-        if qs is not None:
-            out['q_sorted'] = qs[0] if single else qs
-        if ac is not None:
-            out['acum'] = ac[0] if single else ac
-        if bpe is not None:
-            out['bpe'] = float(bpe[0]) if single else bpe
+        # staged per slab: the tracer, per-slab mask / dA, the requested full-length outputs and the sort's own four work arrays
+        per = ny * nx * (q.dtype.itemsize + 32 + (8 if want_sorted else 0) + (8 if want_acum else 0) +
+                         (8 if rank == XC_DA_SLAB else 0) + (8 if per_slab else 0))
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, db, mb = _stack_now(q, s0, s1), _part(dA, 3, s0, s1), _part(mask, 3, s0, s1)
+            Q = np.empty((n, J), dtype=np.float64) if targets is not None else None
+            qs = np.empty((n, ny * nx), dtype=np.float64) if want_sorted else None
+            ac = np.empty((n, ny * nx), dtype=np.float64) if want_acum else None
+            nv = np.zeros(n, dtype=np.uint32)
+            bpe = np.zeros(n, dtype=np.float64) if tbl is not None else None
+            self._check(self.lib.xc_sort_profile_batch(self.handle, _ptr(qb), dtype_code(q.dtype), _ptr(mb),
+                                                       dtype_code(mask.dtype) if mask is not None else XC_F64, per_slab,
+                                                       _ptr(db), rank, n, ny, nx, 1 if negate else 0, _ptr(targets), J,
+                                                       _ptr(tbl), _ptr(coord), ntbl,
+                                                       _ptr(Q), _ptr(qs), _ptr(ac), _ptr(nv), _ptr(bpe)))
+            out = {'nvalid': nv.astype(np.int64), 'Q': Q, 'q_sorted': qs, 'acum': ac, 'bpe': bpe}
+            return {k: v for k, v in out.items() if v is not None}
+        out = self._batched(nslab, per, one)
+        if single:                                           # a plane in: scalars / 1-D arrays out
+            out = {k: v[0] for k, v in out.items()}
+            out['nvalid'] = int(out['nvalid'])
+            if 'bpe' in out:
+                out['bpe'] = float(out['bpe'])
         return out
 
 

@@ -171,9 +171,7 @@ class Contour2D(object):
     def _float(self, v):
         if getattr(v, '_xc_lazy_stack', False):
             return v                                                    # converts as it reads
-        if v.dtype not in (np.float32, np.float64):
-            v = v.astype(np.float64)
-        return v
+        return nat._f48(v)
 
     def _dA_array(self, ny, nx, nslab):
         """self.dA -> (float64 ndarray of shape (ny,), (ny,nx) or (nslab,ny,nx), was_f32)"""
@@ -228,6 +226,13 @@ class Contour2D(object):
             c = {d: np.asarray(coords[d]) for d in lead if d in coords}
             c['contour'] = np.asarray(ccoord)
         return lb.wrap(out, tuple(lead) + ('contour',), c, name, like, trusted=True)
+
+    def _in_dim_order(self, v, like, lead, lshape):
+        """a plane-shaped result `v` (S, ny, nx) of the labelled input `like` -> (the input's dims, `v` with the leading dims
+        unfolded and the axes in the input's own order)"""
+        dims = lb.unwrap(like, lazy=True)[1]
+        full = tuple(lead) + (self.dimEqV, self._xdim)
+        return dims, np.transpose(v.reshape(tuple(lshape) + v.shape[-2:]), [full.index(d) for d in dims])
 
     # ------------------------------------------------------------------ A(Yeq) table
     def _table_rows(self, mask, multiply):
@@ -373,21 +378,42 @@ class Contour2D(object):
         return lb.wrap(v, dims, coords, name, qIntp)
 
     # ------------------------------------------------------------------ conditional integrals
-    def _hist_inputs(self, tracer, integrand):
-        if tracer is None:
-            tracer = self.tracer
+    def _hist_inputs(self, tracer, integrands, fused=False):
+        """tracer, weights and integrands as a histogram pass takes them -> (q (S, ny, nx), lead dims, lead shape, coords, dA,
+        [integrand (S, ny, nx), ...], [its product with dA stays float32?, ...]).  An integrand on its own goes through
+        `_integrand_plane` (resident objects register it as THE ('integrand',) mirror); the integrands of a `fused` pass register nothing"""
         q, lead, lshape, coords = self._plane(tracer)
         q = self._float(q)
         nslab, ny, nx = q.shape
         dA, dA_f32 = self._dA_array(ny, nx, nslab)
-        integ, prod_f32 = [], False
-        if integrand is not None:
-            g = self._integrand_plane(integrand)
+        gs, flags = [], []
+        for it in integrands:
+            g = self._float(self._plane(it)[0]) if fused else self._integrand_plane(it)
             if g.shape != q.shape:
                 g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
-            integ = [g]
-            prod_f32 = bool(g.dtype == np.float32 and dA_f32)         # f32*f32 stays f32 (core.py:444)
-        return tracer, q, lead, lshape, coords, dA, integ, prod_f32
+            gs.append(g)
+            flags.append(bool(g.dtype == np.float32 and dA_f32))           # f32*f32 stays f32 (core.py:444)
+        return q, lead, lshape, coords, dA, gs, flags
+
+    def _hist_cdfs(self, contour, tracer, integrands, channels, fused=False):
+        """CDF of dA (channel 0) and of every integrand*dA (channel 1 + i) within the contours in ONE K3 pass -> the `channels` asked
+        for, each wrapped as cal_integral_within_contours_hist returns it; None when the integrands cannot share a launch (more than
+        XC_MAX_INTEGRANDS, or mixed f32/f64 products)."""
+        q, lead, lshape, coords, dA, gs, flags = self._hist_inputs(tracer, integrands, fused)
+        if len(gs) > nat.XC_MAX_INTEGRANDS or len(set(flags)) > 1:
+            return None
+        b = self._contour_values(contour, q.shape[0], list(lead), list(lshape))
+        edges, binc, last_closed = _edges_from_levels(b, self.right_edge)
+        out = self.ctx.hist(q, edges, dA=dA, integrands=gs, last_closed=last_closed, lt=self.lt,
+                            reverse=not binc, prod_f32=bool(flags and flags[0]), want=('cdf',), deterministic=self.deterministic)
+        binNum = np.arange(b.shape[1]).astype(np.float32)                  # core.py:1255-1257
+        name = 'histogram_%s' % lb.unwrap(tracer, lazy=True)[3]
+        res = []
+        for c in channels:
+            res.append(self._wrap_contour(out['cdf'][:, c, :], lead, lshape, coords, name, tracer, binNum))
+            if self.check_mono:
+                _check_monotonicity(res[-1], 'contour')
+        return res
 
     def _integrand_plane(self, integrand):
         """(S, ny, nx) values of an integrand.  resident=True: the LAST integrand handed to this object keeps a device mirror too, keyed
@@ -405,20 +431,8 @@ class Contour2D(object):
         One GPU pass: weights `dA` (or `integrand*dA`, fillna(0)), CDF by cumsum,
         `cdf[-1]-cdf` if not lt, flipped so that out[k] <-> contour[k].
         """
-        tracer, q, lead, lshape, coords, dA, integ, prod_f32 = self._hist_inputs(tracer, integrand)
-        nslab = q.shape[0]
-        b = self._contour_values(contour, nslab, list(lead), list(lshape))
-        edges, binc, last_closed = _edges_from_levels(b, self.right_edge)
-        out = self.ctx.hist(q, edges, dA=dA, integrands=integ, last_closed=last_closed, lt=self.lt,
-                            reverse=not binc, prod_f32=prod_f32, want=('cdf',), deterministic=self.deterministic)
-        cdf = out['cdf'][:, 1 if integ else 0, :]
-        N = b.shape[1]
-        binNum = np.arange(N).astype(np.float32)                      # core.py:1255-1257
-        name = lb.unwrap(tracer, lazy=True)[3]
-        CDF = self._wrap_contour(cdf, lead, lshape, coords, 'histogram_%s' % name, tracer, binNum)
-        if self.check_mono:
-            _check_monotonicity(CDF, 'contour')
-        return CDF
+        integ = [] if integrand is None else [integrand]
+        return self._hist_cdfs(contour, self.tracer if tracer is None else tracer, integ, [len(integ)])[0]
 
     def cal_integral_within_contours(self, contour, tracer=None, integrand=None):
         """
@@ -427,8 +441,10 @@ class Contour2D(object):
         Evaluated with the same GPU histogram: half-open bins below each sorted level
         (the tracer is negated in-kernel for the '>' case).
         """
-        tracer, q, lead, lshape, coords, dA, integ, prod_f32 = self._hist_inputs(tracer, integrand)
-        nslab = q.shape[0]
+        if tracer is None:
+            tracer = self.tracer
+        q, lead, lshape, coords, dA, integ, flags = self._hist_inputs(tracer, [] if integrand is None else [integrand])
+        nslab, prod_f32 = q.shape[0], bool(flags and flags[0])
         if type(contour) in [np.ndarray]:
             contour = _as_labeled_1d(contour, 'contour')
         b = self._contour_values(contour, nslab, list(lead), list(lshape)).astype(np.float64)
@@ -543,31 +559,8 @@ class Contour2D(object):
         """CDF of dA and of every integrand*dA within the contours in ONE K3 pass ->
         (area, [integral_i]), each exactly what cal_integral_within_contours_hist returns; None when
         the integrands cannot share a launch (more than XC_MAX_INTEGRANDS, or mixed f32/f64 products)."""
-        q, lead, lshape, coords = self._plane(self.tracer)
-        q = self._float(q)
-        nslab, ny, nx = q.shape
-        dA, dA_f32 = self._dA_array(ny, nx, nslab)
-        gs, flags = [], []
-        for it in integrands:
-            g = self._float(self._plane(it)[0])
-            if g.shape != q.shape:
-                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
-            gs.append(g)
-            flags.append(bool(g.dtype == np.float32 and dA_f32))           # f32*f32 stays f32 (core.py:444)
-        if len(gs) > nat.XC_MAX_INTEGRANDS or len(set(flags)) > 1:
-            return None
-        b = self._contour_values(contour, nslab, list(lead), list(lshape))
-        edges, binc, last_closed = _edges_from_levels(b, self.right_edge)
-        out = self.ctx.hist(q, edges, dA=dA, integrands=gs, last_closed=last_closed, lt=self.lt,
-                            reverse=not binc, prod_f32=flags[0], want=('cdf',), deterministic=self.deterministic)
-        binNum = np.arange(b.shape[1]).astype(np.float32)                  # core.py:1255-1257
-        name = 'histogram_%s' % lb.unwrap(self.tracer, lazy=True)[3]
-        res = [self._wrap_contour(np.ascontiguousarray(out['cdf'][:, c, :]), lead, lshape, coords, name, self.tracer, binNum)
-               for c in range(1 + len(gs))]
-        if self.check_mono:
-            for r in res:
-                _check_monotonicity(r, 'contour')
-        return res[0], res[1:]
+        res = self._hist_cdfs(contour, self.tracer, integrands, range(1 + len(integrands)), fused=True)
+        return None if res is None else (res[0], res[1:])
 
     def cal_sqared_equivalent_length(self, dgrdSdA, dqdA):
         """Leq2 = d[int |grad q|^2]/dA / (dq/dA)^2 (reference core.py:619-637)."""
@@ -666,21 +659,26 @@ class Contour2D(object):
             area = np.broadcast_to(area[:, None], (ny, nx))
         if was_f32:
             area = area.astype(np.float32)             # the reference takes np.sqrt in the area's own dtype
-        b = np.array(self._contour_values(ctr, nslab, list(lead), list(lshape)), dtype=np.float64)
-        b[np.isnan(b)] = np.inf                        # a NaN level is never crossed; neither is +inf
-        order = np.argsort(b, axis=1, kind='stable')
-        bs = np.take_along_axis(b, order, axis=1)
-        ccoord = lb.unwrap(ctr, lazy=True)[2].get('contour') if lb.is_labeled(ctr) else None
-        if ccoord is None:
-            ccoord = np.arange(b.shape[1]).astype(self.dtype)
+        bs, order, ccoord = self._sorted_levels(ctr, nslab, lead, lshape)
         re = []
         results = self.ctx.crossing(q, bs, area, stride=strides, pad_x=maxStride if has_x else 0,
                                     pad_mode=mode, full_width=full_width)      # one upload for all strides
         for lens, _ in results:
-            out = np.empty_like(lens)
-            np.put_along_axis(out, order, lens, axis=1)
+            out = _level_order(lens, order)
             re.append(self._wrap_contour(out.astype(self.dtype), lead, lshape, coords, None, self.tracer, ccoord))
         return re if isiterable else re[0]
+
+    def _sorted_levels(self, ctr, nslab, lead, lshape):
+        """the levels of every slab as the contour kernels take them: float64, ascending, a NaN level as +inf (it is never crossed --
+        it crosses no cell --; neither is +inf) -> (sorted levels (nslab, N), the stable order that sorted them -- `_level_order`
+        undoes it --, the 'contour' coordinate of the result)"""
+        b = np.array(self._contour_values(ctr, nslab, list(lead), list(lshape)), dtype=np.float64)
+        b[np.isnan(b)] = np.inf
+        order = np.argsort(b, axis=1, kind='stable')
+        ccoord = lb.unwrap(ctr, lazy=True)[2].get('contour') if lb.is_labeled(ctr) else None
+        if ccoord is None:
+            ccoord = np.arange(b.shape[1]).astype(self.dtype)
+        return np.take_along_axis(b, order, axis=1), order, ccoord
 
     # ------------------------------------------------------------------ contour lengths
     def cal_contour_lengths(self, contours, tracer=None, latlon=False):
@@ -714,17 +712,9 @@ class Contour2D(object):
         q, lead, lshape, coords = self._plane(data)
         q = self._float(q)
         nslab = q.shape[0]
-        b = np.array(self._contour_values(contours, nslab, list(lead), list(lshape)), dtype=np.float64)
-        b[np.isnan(b)] = np.inf                        # a NaN level crosses no cell
-        order = np.argsort(b, axis=1, kind='stable')
-        bs = np.take_along_axis(b, order, axis=1)
+        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
         lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0)
-        out = np.empty_like(lens)
-        np.put_along_axis(out, order, lens, axis=1)
-        ccoord = lb.unwrap(contours, lazy=True)[2].get('contour') if lb.is_labeled(contours) else None
-        if ccoord is None:
-            ccoord = np.arange(b.shape[1]).astype(self.dtype)
-        return self._wrap_contour(out.astype(self.dtype), lead, lshape, coords, None, data, ccoord)
+        return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
 
     # ------------------------------------------------------------------ local wave activity
     def cal_local_wave_activity(self, q, Q, mask_idx=None, part='all', metric=None, exact=None):
@@ -790,10 +780,7 @@ class Contour2D(object):
             exact = True         # deterministic=True promises run-to-run identical bits: the interval kernel's LDS atomics add in arrival order
         lwa, masks = self.ctx.lwa(qv, Qv, eq.astype(np.float64), dA, dmax, M=M, increase=self.increase,
                                   part=pcode, mask_idx=mask_idx, variant=variant, exact=exact)
-        qdims = lb.unwrap(q, lazy=True)[1]
-        full = tuple(lead) + (self.dimEqV, self._xdim)
-        out = lwa.reshape(tuple(lshape) + (ny, nx))
-        out = np.transpose(out, [full.index(d) for d in qdims])                # .transpose(*q.dims), core.py:793
+        qdims, out = self._in_dim_order(lwa, q, lead, lshape)                  # .transpose(*q.dims), core.py:793
         c = dict(coords)
         c[self.dimEqV] = eq
         LWA = lb.wrap(out, qdims, c, name, q)
@@ -803,8 +790,7 @@ class Contour2D(object):
         Ql_coords = {d: coords[d] for d in lead if d in coords}
         for i, j in enumerate(mask_idx):
             contours.append(lb.wrap(Qv[:, j].reshape(lshape) if lshape else Qv[0, j], tuple(lead), Ql_coords, lb.unwrap(Q, lazy=True)[3], q))
-            m = masks[:, i].reshape(tuple(lshape) + (ny, nx)).astype(np.int64)
-            mlist.append(lb.wrap(np.transpose(m, [full.index(d) for d in qdims]), qdims, c, None, q))
+            mlist.append(lb.wrap(self._in_dim_order(masks[:, i].astype(np.int64), q, lead, lshape)[1], qdims, c, None, q))
         return LWA, contours, mlist
 
     # ------------------------------------------------------------------ extensions
@@ -819,9 +805,7 @@ class Contour2D(object):
             rdx, rdy = grad_metrics(lat if lat is not None else coords[self.dimEqV],
                                     lon if lon is not None else coords[self._xdim])
         g = self.ctx.grad2(q, rdx, rdy, periodic_x)
-        full = tuple(lead) + (self.dimEqV, self._xdim)
-        tdims = lb.unwrap(tracer, lazy=True)[1]
-        g = np.transpose(g.reshape(tuple(lshape) + q.shape[1:]), [full.index(d) for d in tdims])
+        tdims, g = self._in_dim_order(g, tracer, lead, lshape)
         name = lb.unwrap(tracer, lazy=True)[3]
         return lb.wrap(g, tdims, coords, 'grdS' + (name or ''), tracer)
 
@@ -878,6 +862,29 @@ class Contour2D(object):
             return Q, (sorted_[0] if nslab == 1 and not lead else sorted_)
         return Q
 
+    def _keff_key(self, batch, nbuf, N, q, g, dA, periodic_x, nkeff_mask, tbl, tbl_coord, preY, rdx, rdy):
+        """The plan owns the device copies of everything static (dA, metrics, table, preY) and the work buffers:
+        it is kept between calls, so a second keff() on the same grid only uploads the tracer.  Key = the
+        configuration + the bytes of the small arrays + a fingerprint of dA (shape, ends and a strided sample:
+        dA is the grid metric, not something callers edit in place between calls)."""
+        def small(a):
+            return None if a is None else np.ascontiguousarray(a, dtype=np.float64).tobytes()
+        flat = dA.reshape(-1)
+        slab_dA = dA.ndim == 3
+        # a per-slab dA travels with every batch (like the tracer): only its shape enters the key
+        dkey = ('slab',) if slab_dA else (flat[::max(1, flat.size // 512)].tobytes(), float(flat[0]), float(flat[-1]))       # (hashing a 32 KB sample was 20 us per call)
+        return (batch, nbuf) + q.shape[1:] + (int(N), q.dtype.str, np.dtype(self.dtype).str, None if g is None else g.dtype.str,
+                bool(periodic_x), float(nkeff_mask), bool(self.increase), bool(self.lt), self.right_edge, self.device, self.deterministic,
+                dA.shape[-2:] if slab_dA else dA.shape, dkey,
+                small(tbl), small(tbl_coord), small(preY), small(rdx), small(rdy))
+
+    def _keff_keep(self, key, plan):
+        """`_keff_plans`: key -> the plan keff() took out for this call, back in as the most recently used (last) of at most two"""
+        plans = self.__dict__['_keff_plans']
+        plans[key] = plan
+        while len(plans) > 2:
+            plans.pop(next(iter(plans))).free()
+
     def keff(self, N, table, grdS=None, preY=None, lat=None, lon=None, rdx=None, rdy=None,
              periodic_x=True, nkeff_mask=1e5, max_batch_bytes=8 << 30):
         """
@@ -904,9 +911,11 @@ class Contour2D(object):
                   self.increase, self.lt, self.right_edge, self.device, self.deterministic, np.dtype(self.dtype).str) if self.resident else None
         last = self.__dict__.get('_keff_last') if self.resident else None
         fast = last is not None and len(last[0]) == len(idents) and all(a is b or (type(a) in (int, float, bool, str) and type(a) is type(b) and a == b) for a, b in zip(last[0], idents))
+        plans = self.__dict__.setdefault('_keff_plans', {})
+        key = last[1] if fast and last[1] in plans else None
         if grdS is not None:
             g = self._integrand_plane(grdS)
-        elif rdx is None and not fast:
+        elif rdx is None and key is None:                    # (a plan that is still there holds the metrics on the device; an evicted one is rebuilt from them)
             la = np.ascontiguousarray(lat if lat is not None else coords[self.dimEqV])
             lo = np.ascontiguousarray(lon if lon is not None else coords[self._xdim])
             mk = (la.tobytes(), lo.tobytes(), la.dtype.str, lo.dtype.str)
@@ -914,12 +923,6 @@ class Contour2D(object):
             if memo is None or memo[0] != mk:                    # the metrics of a grid are computed once per object and grid
                 memo = self.__dict__['_metrics_memo'] = (mk, grad_metrics(la, lo))
             rdx, rdy = memo[1]
-        # The plan owns the device copies of everything static (dA, metrics, table, preY) and the work buffers:
-        # it is kept between calls, so a second keff() on the same grid only uploads the tracer.  Key = the
-        # configuration + the bytes of the small arrays + a fingerprint of dA (shape, ends and a strided sample:
-        # dA is the grid metric, not something callers edit in place between calls).
-        def small(a):
-            return None if a is None else np.ascontiguousarray(a, dtype=np.float64).tobytes()
         per_slab = ny * nx * (q.dtype.itemsize + (0 if g is None else g.dtype.itemsize) + (8 if slab_dA else 0))
         batch = int(min(nslab, max(1, int(max_batch_bytes) // per_slab), 65535))
         # more than one batch: the device holds TWO (half the budget each), the upload of batch k + 1 runs on the copy
@@ -928,23 +931,8 @@ class Contour2D(object):
         if batch < nslab:
             nbuf = 2
             batch = int(min(nslab, max(1, int(max_batch_bytes) // (2 * per_slab)), 65535))
-        plans = self.__dict__.setdefault('_keff_plans', {})
-        if fast and last[1] in plans:
-            key = last[1]
-        else:
-            flat = dA.reshape(-1)
-            # a per-slab dA travels with every batch (like the tracer): only its shape enters the key
-            dkey = ('slab',) if slab_dA else (flat[::max(1, flat.size // 512)].tobytes(), float(flat[0]), float(flat[-1]))       # (hashing a 32 KB sample was 20 us per call)
-            if fast:                                         # (the plan was evicted: the metrics were skipped above, derive them now)
-                fast = False
-                if grdS is None and rdx is None:
-                    la = np.ascontiguousarray(lat if lat is not None else coords[self.dimEqV])
-                    lo = np.ascontiguousarray(lon if lon is not None else coords[self._xdim])
-                    rdx, rdy = grad_metrics(la, lo)
-            key = (batch, nbuf, ny, nx, int(N), q.dtype.str, np.dtype(self.dtype).str, None if g is None else g.dtype.str,
-                   bool(periodic_x), float(nkeff_mask), bool(self.increase), bool(self.lt), self.right_edge, self.device, self.deterministic,
-                   dA.shape[-2:] if slab_dA else dA.shape, dkey,
-                   small(tv), small(tcoords[table._dimEq]), small(preY), small(rdx), small(rdy))
+        if key is None:
+            key = self._keff_key(batch, nbuf, N, q, g, dA, periodic_x, nkeff_mask, tv, tcoords[table._dimEq], preY, rdx, rdy)
         if self.resident:
             self.__dict__['_keff_last'] = (idents, key)
         plan = plans.pop(key, None)
@@ -961,69 +949,12 @@ class Contour2D(object):
             plan.desc.dA_pos_finite = int(bool(np.isfinite(dA).all() and (dA >= 0).all()))
             fin = np.abs(dA[np.isfinite(dA)])
             plan.desc.dA_max = float(fin.max()) if fin.size else 0.0      # over EVERY slab: a valid bound for each batch uploaded below
-        ctx = self.ctx
-        qb, gb, db = ny * nx * q.dtype.itemsize, 0 if g is None else ny * nx * g.dtype.itemsize, ny * nx * 8
-
-        direct = {}                                          # batch -> (tracer mirror, grdS mirror): resident inputs are read where they are
-        uploaded = [False]                                   # anything on the copy stream since the last wait?
-
-        def upload(k):
-            """batch k -> half k % nbuf of the device buffers, on the copy stream.  A batch whose tracer (and supplied gradient) lie inside
-            resident mirrors is not copied at all: the descriptor points at the mirrors (a 52 MB cfg2 slab: ~50 us of device-to-device
-            copy per array and call saved)"""
-            s0 = k * batch
-            m = min(batch, nslab - s0)
-            off = (k % nbuf) * batch
-            if self.resident and not slab_dA:
-                qp = ctx.resident_ptr(q[s0:s0 + m])
-                gp = None if g is None else ctx.resident_ptr(g[s0:s0 + m])
-                if qp and (g is None or gp):
-                    direct[k] = (qp, gp)
-                    return
-            uploaded[0] = True
-            plan.q_buf.upload_async(q[s0:s0 + m], off * qb)
-            if slab_dA:
-                plan.dA_buf.upload_async(dA[s0:s0 + m], off * db)
-            if g is not None:
-                plan.grdS_buf.upload_async(g[s0:s0 + m], off * gb)
-
         try:
-            parts = []
-            nb = -(-nslab // batch)
-            upload(0)
-            for k in range(nb):
-                h = k % nbuf
-                m = min(batch, nslab - k * batch)
-                if uploaded[0]:
-                    ctx.stream_wait_copies()                          # the kernels of batch k wait for its upload (7 us of host time: not
-                    uploaded[0] = False                               # paid by a call whose inputs are all resident mirrors)
-                plan.touch()
-                if k in direct:
-                    qp, gp = direct.pop(k)
-                    own = plan._q_ptr
-                    plan.set_q_device(qp)
-                    plan.set_grdS_device(gp)
-                    try:
-                        plan.run_range(h, 0, m, None, out_s0=0)
-                    finally:
-                        plan.set_q_device(own)
-                        plan.set_grdS_device(0)
-                else:
-                    plan.run_range(h, h * batch, m, None, out_s0=0)
-                if k + 1 < nb:
-                    upload(k + 1)                                     # overlaps the kernels just enqueued (the other half is free:
-                                                                      # batch k - 1 was fetched, i.e. synchronised, last turn)
-                r = plan.fetch(check=False, slot=h)
-                if r['status'][:m].any():
-                    raise Exception('non monotonic bins')          # reference core.py:1233-1251
-                parts.append({k_: v[:m] for k_, v in r.items()})   # (views of this fetch's own buffer: nothing else writes it)
-            res = parts[0] if len(parts) == 1 else {k_: np.concatenate([p[k_] for p in parts]) for k_ in parts[0]}
+            res = plan.run_stack(q, batch, nbuf, g=g, dA=dA if slab_dA else None, mirrors=self.resident)
         except Exception:
             plan.free()
             raise
-        plans[key] = plan                                  # most recently used last
-        while len(plans) > 2:
-            plans.pop(next(iter(plans))).free()
+        self._keff_keep(key, plan)
         ccoord = np.arange(N, dtype=np.float64).astype(self.dtype)      # = np.linspace(0.0, N - 1.0, N, dtype): its step is exactly 1
         out = []
         shared = {d: np.asarray(coords[d]) for d in lead if d in coords}
@@ -1155,6 +1086,13 @@ def _edges_from_levels(b, right_edge):
         edges[:, -1] += 1e-8                                           # in the levels' own dtype, like `edge + 1e-8` on the array
         last_closed = False
     return edges.astype(np.float64), binc, last_closed
+
+
+def _level_order(vals, order):
+    """results per SORTED level (`Contour2D._sorted_levels`) -> in the order the levels were given"""
+    out = np.empty_like(vals)
+    np.put_along_axis(out, order, vals, axis=1)
+    return out
 
 
 def _align(v, vdims, dims):

@@ -348,6 +348,61 @@ class KeffPlan(object):
             raise Exception('non monotonic bins')          # reference core.py:1233-1251
         return out
 
+    def _stage(self, k, q, g, dA, batch, nbuf, mirrors):
+        """batch k -> half k % nbuf of the device buffers, on the copy stream.  A batch whose tracer (and supplied gradient) lie inside
+        resident mirrors is not copied at all: the descriptor points at the mirrors (a 52 MB cfg2 slab: ~50 us of device-to-device
+        copy per array and call saved).  Returns (tracer mirror, grdS mirror), or None after a real upload"""
+        s0 = k * batch
+        s1 = min(q.shape[0], s0 + batch)
+        off = (k % nbuf) * batch * self.ny * self.nx
+        if mirrors and dA is None:
+            qp = self.ctx.resident_ptr(q[s0:s1])
+            gp = None if g is None else self.ctx.resident_ptr(g[s0:s1])
+            if qp and (g is None or gp):
+                return qp, gp
+        self.q_buf.upload_async(q[s0:s1], off * q.dtype.itemsize)
+        if dA is not None:
+            self.dA_buf.upload_async(dA[s0:s1], off * 8)
+        if g is not None:
+            self.grdS_buf.upload_async(g[s0:s1], off * g.dtype.itemsize)
+        return None
+
+    def run_stack(self, q, batch, nbuf=1, g=None, dA=None, mirrors=False):
+        """The host stack `q` (S, ny, nx) -- with the supplied gradient `g` and per-slab weights `dA` (S, ny, nx), if any -- through
+        a plan of `nbuf` halves of `batch` slabs each (nslots=nbuf, out_slabs=batch), `batch` slabs at a time: the upload of batch
+        k + 1 runs on the copy stream while batch k computes.  `mirrors`: batches that lie inside resident mirrors of the context are
+        read where they are.  Returns the dict of `fetch()` for all S slabs; raises 'non monotonic bins' like the reference."""
+        nslab = q.shape[0]
+        nb = -(-nslab // batch)
+        parts = []
+        direct = self._stage(0, q, g, dA, batch, nbuf, mirrors)
+        for k in range(nb):
+            h = k % nbuf
+            m = min(batch, nslab - k * batch)
+            if direct is None:
+                self.ctx.stream_wait_copies()                     # the kernels of batch k wait for its upload (7 us of host time: not
+                                                                  # paid by a call whose inputs are all resident mirrors)
+            self.touch()
+            if direct is not None:
+                own = self._q_ptr
+                self.set_q_device(direct[0])
+                self.set_grdS_device(direct[1])
+                try:
+                    self.run_range(h, 0, m, None, out_s0=0)
+                finally:
+                    self.set_q_device(own)
+                    self.set_grdS_device(0)
+            else:
+                self.run_range(h, h * batch, m, None, out_s0=0)
+            if k + 1 < nb:
+                direct = self._stage(k + 1, q, g, dA, batch, nbuf, mirrors)   # overlaps the kernels just enqueued (the other half is
+                                                                              # free: batch k - 1 was fetched, i.e. synchronised, last turn)
+            r = self.fetch(check=False, slot=h)
+            if r['status'][:m].any():
+                raise Exception('non monotonic bins')          # reference core.py:1233-1251
+            parts.append({k_: v[:m] for k_, v in r.items()})   # (views of this fetch's own buffer: nothing else writes it)
+        return parts[0] if len(parts) == 1 else {k_: np.concatenate([p[k_] for p in parts]) for k_ in parts[0]}
+
     def download_q(self):
         return self.q_buf.download((self.nslab, self.ny, self.nx), self.q_dtype)
 
