@@ -349,6 +349,33 @@ int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, i
                        const double* contours, int ncont, int contours_per_slab,
                        double* out_len, uint64_t* out_nseg);
 
+/* ------------------------------------------------------------------ K11 local (sliding-window) contour lengths
+ * Replaces the loop of the reference's tests/test_localLength.py (rolling(center=True).construct(stride=), one
+ * find_contours call per window): per window, the length of ONE contour traced on the window alone.
+ *   windows: centres are the nodes (j, i), j = 0, sy, 2 sy, ... < ny and i = 0, sx, ... < nx, so
+ *     nwy = ceil(ny / sy), nwx = ceil(nx / sx); window (j, i) owns node rows [j - wy/2, j - wy/2 + wy - 1]
+ *     (integer division) and likewise columns, clipped to the plane; no wrap across the X seam.  wy, wx >= 2;
+ *   level: levels[slab][wj][wi] when `levels` is given; else (levels == NULL) the window's NaN-skipping mean in
+ *     float64, in a fixed order: per window row the valid nodes left to right from 0.0 (a NaN node adds nothing
+ *     and does not count), the row sums top to bottom, one IEEE division by the valid count; fewer than
+ *     min_periods valid nodes give a NaN level;
+ *   length: the window is a plane of its own -- cell indices count from its first row and column, coordinates are
+ *     its slice of ycoord / xcoord -- under exactly the rule of K10 above (case table, frac, saddle pairing,
+ *     dropped degenerate segments, np.interp end points, radius > 0 haversine x radius / radius == 0 hypot,
+ *     a total of 0 -> NaN).  A NaN level gives a NaN length and 0 segments.
+ *   out_len[slab][wj][wi], out_level[slab][wj][wi] (the level used; may be NULL), out_nseg[slab][wj][wi] (may be NULL).
+ * Totals use K10's fixed-point sums on K10's window constant (from the whole plane's coordinates): a window's bits
+ * do not depend on the launch geometry, the stride or the slabs per call.  Coordinates must be finite and sizes
+ * positive (checked by the host entry point).  One launch set for all windows of all slabs.              */
+int xc_local_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                 const double* ycoord, const double* xcoord, double radius,
+                                 int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                 const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
+int xc_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                             const double* ycoord, const double* xcoord, double radius,
+                             int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                             const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -143,6 +143,8 @@ PROTOTYPES = {
                               _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'xc_contour_lengths_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
     'xc_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_local_contour_lengths_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'xc_local_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -898,6 +900,59 @@ class Context(object):
                                                     _ptr(lens), _ptr(cnts)))
             return lens, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+
+    def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0):
+        """Sliding-window contour lengths (xc_local_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); ycoord (ny,) /
+        xcoord (nx,) as for contour_lengths; window (wy, wx) nodes, both >= 2; stride (sy, sx), both >= 1: the windows are centred
+        on the nodes (0, sy, 2 sy, ...) x (0, sx, ...) and clipped to the plane.  levels: None -- every window is traced at its
+        NaN-skipping mean (NaN with fewer than `min_periods` valid nodes) --, a scalar, or an array over (nslab, nwy, nwx) /
+        (nwy, nwx).  Returns (lengths f64 (nslab, nwy, nwx), NaN where the total is 0; the levels used f64; segment counts
+        uint64).  A tracer with a device mirror (keep_resident) is read in place through the _dev entry point."""
+        q = _stack_in(q)
+        if len(q.shape) != 3:
+            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
+        nslab, ny, nx = q.shape
+        (wy, wx), (sy, sx) = (int(v) for v in window), (int(v) for v in stride)
+        if wy < 2 or wx < 2:
+            raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: the window must be at least 2 x 2 nodes')
+        if sy < 1 or sx < 1:
+            raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: strides must be >= 1')
+        ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
+        if ycoord.shape != (ny,) or xcoord.shape != (nx,):
+            raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: coordinates of length (%d, %d) for a (%d, %d) plane'
+                                   % (ycoord.size, xcoord.size, ny, nx))
+        if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
+            raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: coordinates must be finite')
+        nwy, nwx = -(-ny // sy), -(-nx // sx)
+        if levels is not None:
+            levels = np.asarray(levels, dtype=np.float64)
+            if levels.shape not in ((), (nwy, nwx), (nslab, nwy, nwx)):
+                raise XContourHipError(XC_EBADARG, 'levels must be a scalar, (nwy, nwx) or (nslab, nwy, nwx)')
+            levels = np.ascontiguousarray(np.broadcast_to(levels, (nslab, nwy, nwx)))
+        shape = (ny, nx)
+        rest = (float(radius), wy, wx, sy, sx, int(min_periods))
+        ob = nwy * nwx * 8
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, lb = _stack_now(q, s0, s1), _part(levels, 3, s0, s1)
+            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+            if qp:
+                # the tracer is on the device already: only the small arrays cross
+                with self._temporaries([ycoord, xcoord] + ([lb] if lb is not None else []), [n * ob] * 3) as bufs:
+                    dy, dx = bufs[:2]
+                    dl, de, dn = bufs[-3:]
+                    self._check(self.lib.xc_local_contour_lengths_dev(self.handle, qp, dtype_code(q.dtype), n, *shape, dy.ptr, dx.ptr,
+                                                                      *rest, bufs[2].ptr if lb is not None else None,
+                                                                      dl.ptr, de.ptr, dn.ptr))
+                    return (dl.download((n, nwy, nwx), np.float64), de.download((n, nwy, nwx), np.float64),
+                            dn.download((n, nwy, nwx), np.uint64))
+            lens, lvls = np.empty((n, nwy, nwx), dtype=np.float64), np.empty((n, nwy, nwx), dtype=np.float64)
+            cnts = np.empty((n, nwy, nwx), dtype=np.uint64)
+            self._check(self.lib.xc_local_contour_lengths(self.handle, _ptr(qb), dtype_code(q.dtype), n, *shape, _ptr(ycoord),
+                                                          _ptr(xcoord), *rest, _ptr(lb), _ptr(lens), _ptr(lvls), _ptr(cnts)))
+            return lens, lvls, cnts
+        return self._batched(nslab, ny * nx * q.dtype.itemsize + 4 * ob, one)
 
     def lwa(self, q, Q, coord, dA, dA_max, M=None, increase=True, part=0, mask_idx=None, variant=0, exact=None):
         """`exact`: None (default) -- planes of up to 512 rows are summed in numpy's own order (bit-exact band walk), larger ones by

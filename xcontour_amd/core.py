@@ -716,6 +716,74 @@ class Contour2D(object):
         lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0)
         return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
 
+    def cal_local_contour_lengths(self, window, stride=1, levels=None, min_periods=None, tracer=None, latlon=False,
+                                  return_levels=False):
+        """
+        Contour length in a sliding window (the loop of the reference's tests/test_localLength.py: rolling(center=True)
+        .construct(stride=) and one find_contours call per window), all windows of all slabs in one GPU pass (K11,
+        xc_local_contour_lengths).
+
+        `window` and `stride`: an int, or a {dim: int} dict over the two plane dims (window >= 2 nodes, stride >= 1).  Windows
+        are centred on the nodes 0, stride, 2 stride, ... of each plane dim, own the nodes [centre - window // 2,
+        centre - window // 2 + window - 1] and are clipped at the plane's edges (no wrap across the X seam).  Every window is
+        traced on its own, as a small plane, at ONE level: `levels` -- a scalar, or an array over (..., windows along the
+        equivalent dim, windows along the other plane dim) -- or, by default, the window's NaN-skipping mean, NaN when the
+        window holds fewer than `min_periods` valid nodes (None: the full window, as xarray's rolling does).  The length
+        follows cal_contour_lengths: the same coordinates (float32 first, radians in float32 with latlon=True), the same
+        segments, NaN for a total of 0 or a NaN level; sums are bit-reproducible.  `tracer`: another field on the same
+        dims, e.g. the latitude itself for the length of a latitude arc across each window.
+        Returns (..., equivalent dim, other plane dim) labelled with the centre nodes' coordinates, in `self.dtype`; with
+        return_levels=True also the levels used (float64, same shape).
+        """
+        pdims = (self.dimEqV, self._xdim)
+
+        def pair(v, what, least):
+            if isinstance(v, dict):
+                if set(v) != set(pdims):
+                    raise Exception('%s should give a value for each of the plane dims %s' % (what, list(pdims)))
+                v = tuple(int(v[d]) for d in pdims)
+            else:
+                v = (int(v), int(v))
+            if min(v) < least:
+                raise Exception('%s should be at least %d' % (what, least))
+            return v
+        win, st = pair(window, 'window', 2), pair(stride, 'stride', 1)
+        data = self.tracer if tracer is None else tracer
+        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
+        for d in pdims:
+            if d not in dcoords:
+                raise Exception('cal_local_contour_lengths needs coordinate values for the plane dim %s' % d)
+        fdef = []
+        for d in pdims:
+            v = np.asarray(dcoords[d]).astype(np.float32)                      # as cal_contour_lengths
+            fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
+        q, lead, lshape, coords = self._plane(data)
+        q = self._float(q)
+        nslab, ny, nx = q.shape
+        nw = (-(-ny // st[0]), -(-nx // st[1]))
+        if levels is not None:
+            if lb.is_labeled(levels):
+                lv, ldims, _, _ = lb.unwrap(levels)
+                if set(ldims) != set(lead + pdims):
+                    raise Exception('levels should be defined on %s' % list(lead + pdims))
+                levels = np.transpose(lv, [ldims.index(d) for d in lead + pdims])
+            levels = np.asarray(levels, dtype=np.float64)
+            if levels.ndim > 2:
+                if levels.shape != tuple(lshape) + nw:
+                    raise Exception('levels of shape %r do not match the %r windows of %r slabs' % (levels.shape, nw, tuple(lshape)))
+                levels = levels.reshape((nslab,) + nw)
+        mp = win[0] * win[1] if min_periods is None else int(min_periods)
+        lens, lvls, _ = self.ctx.local_contour_lengths(q, fdef[0], fdef[1], win, st, mp, levels=levels,
+                                                       radius=Rearth if latlon else 0.0)
+        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
+        for d, t in zip(pdims, st):
+            c[d] = np.asarray(dcoords[d])[::t]
+        dims = tuple(lead) + pdims
+        out = lb.wrap(lens.astype(self.dtype).reshape(tuple(lshape) + nw), dims, c, 'local_length', data)
+        if return_levels:
+            return out, lb.wrap(lvls.reshape(tuple(lshape) + nw), dims, c, 'level', data)
+        return out
+
     # ------------------------------------------------------------------ local wave activity
     def cal_local_wave_activity(self, q, Q, mask_idx=None, part='all', metric=None, exact=None):
         """

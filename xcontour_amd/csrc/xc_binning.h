@@ -194,6 +194,61 @@ __host__ __device__ inline int det_c0_from_bound(double bound)           // boun
     if (top < kDetTopFloor) top = kDetTopFloor;
     return top + 1023 + 52 - (53 - kDetPrecBits);
 }
+// An accumulator's limbs (any carry state; the top limb signed), summed exactly elsewhere, converted ONCE: the integer (up to ~200 bits) ->
+// float64, round half to even, times 2^(window bottom).  kc0: the window constant the chunks were split on.  `acc` is left carried.
+__device__ __forceinline__ double det_limbs_to_double(long long (&acc)[kDetLimbsX], int kc0)
+{
+    constexpr int M = kDetLimbsX;
+    // carries from the last limb up; then sign + magnitude digits D[0] (any size) , D[1..] < 2^48
+    long long carry = 0;
+#pragma unroll
+    for (int i = kDetLimbsX - 1; i >= 0; --i) {
+        long long t = acc[i] + carry; carry = 0;
+        if (i > 0) { carry = t >> kDetLimbBits; t -= carry << kDetLimbBits; }
+        acc[i] = t;
+    }
+    const bool neg = acc[0] < 0;
+    if (neg) {
+        long long borrow = 0;
+#pragma unroll
+        for (int i = kDetLimbsX - 1; i >= 0; --i) {
+            long long t = -acc[i] - borrow; borrow = 0;
+            if (i > 0 && t < 0) { t += 1ll << kDetLimbBits; borrow = 1; }
+            acc[i] = t;
+        }
+    }
+    // the top (up to) 64 significant bits of the digit string + a sticky bit for everything below them
+    int first = -1;
+#pragma unroll
+    for (int i = 0; i < kDetLimbsX; ++i) if (first < 0 && acc[i] != 0) first = i;
+    if (first < 0) return 0.0;
+    unsigned long long top = 0ull; int nb = 0, below = 0; bool sticky = false;     // nb: bits in `top`; below: bits of the string under top's last bit
+#pragma unroll
+    for (int i = 0; i < kDetLimbsX; ++i) {
+        const unsigned long long D = (unsigned long long)acc[i];
+        if (i == first) { top = D; nb = 64 - __clzll((long long)D); below = kDetLimbBits * (M - 1 - first); }
+        else if (i > first) {
+            if (nb + kDetLimbBits <= 64) { top = (top << kDetLimbBits) | D; nb += kDetLimbBits; below -= kDetLimbBits; }
+            else if (nb < 64) {
+                const int take = 64 - nb, rest = kDetLimbBits - take;
+                top = (top << take) | (D >> rest);
+                sticky = sticky || (D & ((1ull << rest) - 1ull)) != 0ull;
+                nb = 64; below -= take;
+            } else sticky = sticky || D != 0ull;
+        }
+    }
+    // the window: c0 = top_exponent + 1023 + 52 - (53 - P); the string's last bit is worth 2^(top_exponent - S M)
+    int e = (kc0 - (1023 + 52 - (53 - kDetPrecBits))) - kDetLimbBits * M + below;
+    if (nb > 53) {
+        const int drop = nb - 53;
+        const unsigned long long rem = top & ((1ull << drop) - 1ull), half = 1ull << (drop - 1);
+        top >>= drop;
+        if (rem > half || (rem == half && (sticky || (top & 1ull)))) ++top;      // (2^53 after the increment is still exact)
+        e += drop;
+    }
+    const double out = ldexp((double)top, e);
+    return neg ? -out : out;
+}
 
 // copy slot of a lane.  (Rotating the slot by the bin index to spread LDS banks was measured
 // 10 % SLOWER on MI355X -- profiles/r01_notes.md -- so the slot is simply lane % ncopy.)

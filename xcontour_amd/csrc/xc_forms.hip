@@ -1,5 +1,5 @@
 // C ABI, part 4: the host forms of the kernels outside the Keff chain -- row sums (K2), the squared gradient (K4), the local wave
-// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip),
+// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip; K11, xc_lclen.hip),
 // synthetic slabs -- and the records of what they launched.
 #include "xc_capi.h"
 #include <cmath>
@@ -178,6 +178,48 @@ int xc_last_clen_geometry(xc_ctx* ctx, xc_clen_geometry* out)
     if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_clen_geometry: bad arguments");
     *out = ctx->last_clen;
     return XC_OK;
+}
+
+// ------------------------------------------------------------------------------------ K11
+int xc_local_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                 const double* ycoord, const double* xcoord, double radius,
+                                 int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                 const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    return launch_local_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, wy, wx, sy, sx, min_periods,
+                                        levels, out_len, out_level, out_nseg);
+}
+
+int xc_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                             const double* ycoord, const double* xcoord, double radius,
+                             int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                             const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    if (!q || !ycoord || !xcoord || !out_len || nslab < 1 || ny < 1 || nx < 1)
+        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad dtype");
+    if (wy < 2 || wx < 2) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: the window must be at least 2 x 2 nodes");
+    if (sy < 1 || sx < 1) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: strides must be >= 1");
+    for (int64_t i = 0; i < ny; ++i)
+        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
+    for (int64_t i = 0; i < nx; ++i)
+        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
+    const size_t nwin = (size_t)((ny + sy - 1) / sy) * (size_t)((nx + sx - 1) / sx);
+    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, ob = (size_t)nslab * nwin * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + 4 * al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb);
+    double* dv = levels ? (double*)st.take(ob) : nullptr;
+    double* dl = st.out(out_len, ob); double* de = st.out(out_level, ob); uint64_t* dn = st.out(out_nseg, ob);
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb));
+    if (levels) XC_TRY(h2d(ctx, dv, levels, ob));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_local_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, radius, wy, wx, sy, sx, min_periods, dv, dl, de, dn));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
 }
 
 // ------------------------------------------------------------------------------------ K7

@@ -73,14 +73,13 @@ void k_det3_reduce(const unsigned long long* __restrict__ part_l, const unsigned
     const int v = blockIdx.x * 8 + (tid >> 5);
     if (v >= nvh) return;
     const int ch = v / nbin, k = v - ch * nbin;
-    constexpr int M = kDetLimbsX;
     const int base = kDetLimbsX * ch;
     long long acc[kDetLimbsX] = {0, 0, 0, 0};
     unsigned long long cnt = 0ull; unsigned fl = 0u;
     for (int b = l; b < bps; b += 32) {
         const unsigned long long* p = part_l + ((size_t)slab * bps + b) * NL * nbin + (size_t)base * nbin + k;
 #pragma unroll
-        for (int i = 0; i < kDetLimbsX; ++i) if (i < M) acc[i] += (long long)p[(size_t)i * nbin];
+        for (int i = 0; i < kDetLimbsX; ++i) acc[i] += (long long)p[(size_t)i * nbin];
         const unsigned w = part_c[((size_t)slab * bps + b) * nbin + k];
         cnt += w & 0x0fffffffu; fl |= w >> 28;
     }
@@ -95,59 +94,7 @@ void k_det3_reduce(const unsigned long long* __restrict__ part_l, const unsigned
     if ((fl >> ch) & 1u) {
         out = __longlong_as_double(0x7ff8000000000000LL);                  // the bin saw an infinite weight
     } else {
-        // carries from the last limb up; then sign + magnitude digits D[0] (any size) , D[1..] < 2^48
-        long long carry = 0;
-#pragma unroll
-        for (int i = kDetLimbsX - 1; i >= 0; --i) if (i < M) {
-            long long t = acc[i] + carry; carry = 0;
-            if (i > 0) { carry = t >> kDetLimbBits; t -= carry << kDetLimbBits; }
-            acc[i] = t;
-        }
-        const bool neg = acc[0] < 0;
-        if (neg) {
-            long long borrow = 0;
-#pragma unroll
-            for (int i = kDetLimbsX - 1; i >= 0; --i) if (i < M) {
-                long long t = -acc[i] - borrow; borrow = 0;
-                if (i > 0 && t < 0) { t += 1ll << kDetLimbBits; borrow = 1; }
-                acc[i] = t;
-            }
-        }
-        // the top (up to) 64 significant bits of the digit string + a sticky bit for everything below them
-        int first = -1;
-#pragma unroll
-        for (int i = 0; i < kDetLimbsX; ++i) if (i < M && first < 0 && acc[i] != 0) first = i;
-        if (first < 0) {
-            out = 0.0;
-        } else {
-            unsigned long long top = 0ull; int nb = 0, below = 0; bool sticky = false;     // nb: bits in `top`; below: bits of the string under top's last bit
-#pragma unroll
-            for (int i = 0; i < kDetLimbsX; ++i) if (i < M) {
-                const unsigned long long D = (unsigned long long)acc[i];
-                if (i == first) { top = D; nb = 64 - __clzll((long long)D); below = kDetLimbBits * (M - 1 - first); }
-                else if (i > first) {
-                    if (nb + kDetLimbBits <= 64) { top = (top << kDetLimbBits) | D; nb += kDetLimbBits; below -= kDetLimbBits; }
-                    else if (nb < 64) {
-                        const int take = 64 - nb, rest = kDetLimbBits - take;
-                        top = (top << take) | (D >> rest);
-                        sticky = sticky || (D & ((1ull << rest) - 1ull)) != 0ull;
-                        nb = 64; below -= take;
-                    } else sticky = sticky || D != 0ull;
-                }
-            }
-            // the window: c0 = top_exponent + 1023 + 52 - (53 - P); the string's last bit is worth 2^(top_exponent - S M)
-            const int kc0 = c0[(size_t)slab * nch + ch];
-            int e = (kc0 - (1023 + 52 - (53 - kDetPrecBits))) - kDetLimbBits * M + below;
-            if (nb > 53) {
-                const int drop = nb - 53;
-                const unsigned long long rem = top & ((1ull << drop) - 1ull), half = 1ull << (drop - 1);
-                top >>= drop;
-                if (rem > half || (rem == half && (sticky || (top & 1ull)))) ++top;      // (2^53 after the increment is still exact)
-                e += drop;
-            }
-            out = ldexp((double)top, e);
-            if (neg) out = -out;
-        }
+        out = det_limbs_to_double(acc, c0[(size_t)slab * nch + ch]);
     }
     red_h[(size_t)slab * nvh + v] = out;
 }
