@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import xcontour_oracle as O
+import sort_ref as R
 from test_gpu_parity import rel, RTOL, TIGHT, LMIN_FLOOR, _baro_da
 from gpu_common import GOLD, NINE, ROOT, bits, check_nine, check_nine_det, _clean_env
 
@@ -154,3 +155,19 @@ def test_sort_tile_choice_both_sides_of_the_switch(ctx, dt):
             assert int(r['nvalid'][s]) == n
             assert np.array_equal(r['q_sorted'][s][:n], xs.astype(np.float64)), (S, s)
             assert rel(r['acum'][s][:n], ac) < 1e-12, (S, s)
+
+
+@pytest.mark.parametrize('shape,dt,path', [((257, 255), np.float64, 1), ((256, 257), np.float64, 1), ((256, 257), np.float32, 0)])
+def test_sort_inline_scan_both_sides_of_the_switch(ctx, shape, dt, path):
+    """xc_sort.hip launch_pass(): a plane of at most 32 tiles has its tile counts scanned inside the scatter, a larger one by a
+    k_block_exscan launch of its own.  One plane on half tiles (2048 pairs): 257 x 255 = 65535 cells = 32 tiles (inline),
+    256 x 257 = 65792 = 33 tiles with a ragged last one (scan launch; float32 too: the four key passes run the same scan).
+    The integer payload makes the applied permutation itself visible (sort_ref): it is the stable argsort's, NaNs dropped."""
+    rng = np.random.default_rng(78)
+    ny, nx = shape
+    q = rng.standard_normal(shape).astype(dt)
+    q.ravel()[rng.permutation(q.size)[:7]] = np.nan
+    r = ctx.sort_profile(q, dA=R.int_payload(ny, nx), want_sorted=True, want_acum=True)
+    R.assert_permutation(r, q, what='%r %s' % (shape, np.dtype(dt).name))
+    assert int(r['nvalid']) == q.size - 7
+    assert ctx.last_sort_path() == path

@@ -7,8 +7,8 @@ tolerance.  Each figure a later change may want (paths, deviations) is printed b
 Which gap each test closes:
   1. what only switches on at size (1801 x 3600 = 6 483 600 cells; 1777 x 3607 = 6 409 639):
        k_range_hist samples one chunk in 16 above 262 144 cells; k_range_bounds folds K1 blocks into groups (per = 2) above
-       512 blocks; k_scan_bsums carries over 1024-sum rounds above 2.1 M cells; k_radix_scan_rows over 1024-tile rounds above
-       4.2 M cells -- test_full_size_* (all four on every one of them), test_full_size_stack_of_two (per-slab offsets of every
+       512 blocks; k_block_exscan carries over 1024-sum rounds above 2.1 M cells (block sums) and over 1024-tile rounds above
+       4.2 M cells (tile counts) -- test_full_size_* (all four on every one of them), test_full_size_stack_of_two (per-slab offsets of every
        work array), test_full_size_real_weights_long_double (acum / BPE against a long-double sum)
   2. stability without a tolerance: assert_permutation in every test; test_signed_zeros_keep_their_order
   3. nvalid out of k_fix_runs on block edges: test_nvalid_on_every_edge, test_nvalid_edges_at_full_size

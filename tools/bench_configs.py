@@ -131,7 +131,7 @@ def run_cfg5(ctx, steps, warmup):
                    'device': ctx.device_name()},
         'roofline': {'bound': 'hbm', 'achieved': alg / (ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                      'frac': alg / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 'traffic': None,
-                     'kernel': '(k_radix_hist + k_radix_scan_rows + k_radix_scatter) x %d passes%s' % (passes, ' over the range key + k_fix_runs' if path == 1 else ''),
+                     'kernel': '(k_radix_hist + k_block_exscan + k_radix_scatter) x %d passes%s' % (passes, ' over the range key + k_fix_runs' if path == 1 else ''),
                      'launch_ms': ms, 'algorithmic_bytes_per_launch': alg, 'sort_path': path,
                      'note': 'pass traffic of the LSD radix sort (40 B per valid pair and pass; float64 tracers: three passes over a monotone '
                              '24-bit range key, in-LDS repair of the short runs, eight key passes only as the fallback); at 0.4 M pairs per '

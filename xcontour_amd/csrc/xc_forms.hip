@@ -276,8 +276,9 @@ int xc_sort_profile_batch_dev(xc_ctx* ctx, const void* q, int q_dtype, const voi
     XC_CTX(ctx);
     if (ny < 1 || nx < 1 || nslab < 1) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad shape");
     XC_TRY(ensure_scratch(ctx, sort_workspace_bytes(ny * nx, nslab)));
-    return launch_sort_profile(ctx, q, q_dtype, mask, mask_dtype, mask_per_slab, dA, dA_rank, nslab, ny, nx, negate,
-                               targets, J, tbl, coord, ntbl, ctx->scratch, out_Q, out_qsorted, out_acum, out_nvalid, out_bpe);
+    const SortArgs a = {q, q_dtype, mask, mask_dtype, mask_per_slab, dA, dA_rank, nslab, ny, nx, negate, targets, J, tbl, coord, ntbl,
+                        ctx->scratch, out_Q, out_qsorted, out_acum, out_nvalid, out_bpe};
+    return launch_sort_profile(ctx, a);
 }
 
 int xc_sort_profile_batch(xc_ctx* ctx, const void* q, int q_dtype, const void* mask, int mask_dtype, int mask_per_slab,

@@ -287,11 +287,19 @@ int launch_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const d
                int64_t nslab, int64_t ny, int64_t nx, int increase, int part, int variant,
                const int32_t* mask_idx, int nmask, double* out_lwa, int8_t* out_masks);
 size_t sort_workspace_bytes(int64_t n, int64_t nslab);
-int launch_sort_profile(xc_ctx* ctx, const void* q, int q_dtype, const void* mask, int mask_dtype, int mask_per_slab,
-                        const double* dA, int dA_rank, int64_t nslab, int64_t ny, int64_t nx, int negate,
-                        const double* targets, int J, const double* tbl, const double* coord, int ntbl,
-                        void* workspace, double* out_Q, double* out_qsorted, double* out_acum,
-                        unsigned* out_nvalid, double* out_bpe);
+// K8: one sort_profile call.  Device pointers; `workspace` holds sort_workspace_bytes(ny * nx, nslab) bytes; the out_* may be null
+struct SortArgs {
+    const void*   q;     int q_dtype;
+    const void*   mask;  int mask_dtype, mask_per_slab;
+    const double* dA;    int dA_rank;
+    int64_t       nslab, ny, nx;
+    int           negate;
+    const double* targets;  int J;
+    const double* tbl;   const double* coord;  int ntbl;
+    void*         workspace;
+    double *out_Q, *out_qsorted, *out_acum;  unsigned* out_nvalid;  double* out_bpe;
+};
+int launch_sort_profile(xc_ctx* ctx, const SortArgs& a);
 int launch_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                     int pad_x, int pad_mode, const double* contours, int N, int contours_per_slab,
                     const void* area, int area_dtype, int area_per_slab, int stride, int full_width,
