@@ -246,3 +246,54 @@ def test_lwa_interval_kernel_at_the_full_cfg2_size(ctx):
     assert err <= 1e-12, err
     # and every row is finite and non-negative up to rounding where the plane is (LWA >= 0 for a sorted reference state)
     assert np.isfinite(got[0]).all() and got[0].min() > -1e-9 * scale
+
+
+def _streaming_walk_case(dt):
+    """four distinct 131 x 70 slabs built like those of test_lwa_band_skipping_is_invisible: a sharp meandering front, a row of NaN,
+    +-inf cells, a constant row; one reference state per slab, one of them not monotone"""
+    rng = np.random.default_rng(131)
+    ny, nx = 131, 70                                                      # no multiple of 8, 16 or 64 rows; two strips, the second ragged
+    coord = np.linspace(-80, 80, ny)
+    front = np.tanh((coord[:, None] - 10 * np.sin(np.linspace(0, 6.28, nx))[None, :]) / 4.0)
+    a, b = (front + 0.01 * rng.standard_normal((2, ny, nx))).astype(dt)
+    q = np.stack([a, a[::-1], b, -b])
+    q[0, ny // 3, :] = np.nan
+    q[0, ny // 2, 2] = np.inf; q[1, 1, 1] = -np.inf; q[3, ny - 2, nx - 2] = np.inf
+    q[1, ny // 4, :] = 0.25
+    Q = np.stack([np.sort(q[0, :, 0].astype(np.float64)), rng.standard_normal(ny), np.sort(q[2, :, 5].astype(np.float64)),
+                  np.sort(q[3, :, 69].astype(np.float64))[::-1]])
+    Q[np.isnan(Q)] = 0.0
+    return coord, q, Q, rng.random((ny, nx)) + 0.5
+
+
+def run_streaming_walk(ctx):
+    """the body of test_lwa_streaming_walk_both_sides_of_the_four_targets_switch, run in its child process"""
+    H = 168
+    for dt in (np.float64, np.float32):
+        coord, q, Q, dA = _streaming_walk_case(dt)
+        for variant in (0, 1):
+            fn = O.cal_local_wave_activity2 if variant else O.cal_local_wave_activity
+            for increase in (True, False):
+                for part, pc in (('all', 0), ('upper', 1), ('lower', 2)):
+                    with np.errstate(invalid='ignore'):                   # inf * 0 inside the oracle's products
+                        ref = [fn(q[s], Q[s], coord, dA, increase, part) for s in range(4)]
+                    for S in (2, H):
+                        idx = np.arange(S) % 4
+                        out, _ = ctx.lwa(q[idx], Q[idx], coord, dA, dA.max(), M=None, increase=increase, part=pc, variant=variant)
+                        assert ctx.last_lwa_path() == 0
+                        for s in range(S):
+                            assert np.array_equal(out[s], ref[idx[s]], equal_nan=True), (np.dtype(dt).name, variant, increase, part, S, s)
+
+
+def test_lwa_streaming_walk_both_sides_of_the_four_targets_switch():
+    """k_lwa_prep + k_lwa on a small plane (XC_LWA_STRIP=0 in a child process: such planes otherwise take k_lwa_strip), on both sides of
+    the threshold ny^2 nx nslab = 2e8 between one and four target rows per thread: 131 x 70 as a stack of 2 slabs (2.4e6: JT = 1) and
+    as the same four distinct slabs repeated to 168 (2.02e8: JT = 4; a block walks 16 target rows, so the ninth block has three rows
+    in its first wave and three waves past the end).  float32 and float64, both variants, both directions, every `part`; every slab
+    bit for bit the oracle of its distinct slab."""
+    env = _clean_env()
+    env['XC_LWA_STRIP'] = '0'
+    src = 'import sys; sys.path[:0] = [%r, %r, %r]\n' % (ROOT, os.path.join(ROOT, 'oracle'), os.path.join(ROOT, 'tests')) \
+        + 'import test_gpu_lwa as T\nfrom xcontour_amd import _native as nat\nctx = nat.Context(0)\nT.run_streaming_walk(ctx)\nctx.close()\nprint("OK")\n'
+    p = subprocess.run([sys.executable, '-c', src], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
+    assert p.returncode == 0 and 'OK' in p.stdout, p.stdout[-3000:]

@@ -229,8 +229,8 @@ int xc_lwa_dev(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const d
                const int32_t* mask_idx, int nmask, double* out_lwa, int8_t* out_masks)
 {
     XC_CTX(ctx);
-    return launch_lwa(ctx, q, q_dtype, Q, coord, dA, dA_rank, dA_max, M, M_rank, nslab, ny, nx,
-                      increase, part, variant, mask_idx, nmask, out_lwa, out_masks);
+    const LwaArgs a = {q, q_dtype, Q, coord, dA, dA_rank, dA_max, M, M_rank, nslab, ny, nx, increase, part, variant, mask_idx, nmask, out_lwa, out_masks};
+    return launch_lwa(ctx, a);
 }
 
 int xc_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const double* coord,
@@ -261,8 +261,9 @@ int xc_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const doubl
     if (Mb) XC_TRY(stage_in(ctx, dM, M, Mb, &pM));
     if (nmask) XC_TRY(h2d(ctx, dmi, mask_idx, mib));
     XC_TRY(flush_in(ctx));
-    XC_TRY(launch_lwa(ctx, pq, q_dtype, dQ, dc, (const double*)pd, dA_rank, dA_max, (const double*)pM, M_rank, nslab, ny, nx, increase, part, variant,
-                      dmi, nmask, dout, dmo));
+    const LwaArgs a = {pq, q_dtype, dQ, dc, (const double*)pd, dA_rank, dA_max, (const double*)pM, M_rank, nslab, ny, nx, increase, part, variant,
+                       dmi, nmask, dout, dmo};
+    XC_TRY(launch_lwa(ctx, a));
     XC_TRY(st.deliver());
     return xc_sync(ctx);
 }

@@ -282,10 +282,18 @@ int launch_rowsum(xc_ctx* ctx, const void* mask, int mask_dtype, const double* d
                   int64_t ny, int64_t nx, int multiply, double* out_rows);
 int launch_grad2(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* rdx, const double* rdy, int periodic_x, double* out);
-int launch_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const double* coord,
-               const double* dA, int dA_rank, double dA_max, const double* M, int M_rank,
-               int64_t nslab, int64_t ny, int64_t nx, int increase, int part, int variant,
-               const int32_t* mask_idx, int nmask, double* out_lwa, int8_t* out_masks);
+// K7: one xc_lwa call.  Device pointers; M may be null with M_rank == XC_DA_NONE (the weight itself); mask_idx / out_masks only with nmask > 0
+struct LwaArgs {
+    const void*    q;      int q_dtype;
+    const double*  Q;      const double* coord;
+    const double*  dA;     int dA_rank;  double dA_max;
+    const double*  M;      int M_rank;
+    int64_t        nslab, ny, nx;
+    int            increase, part, variant;
+    const int32_t* mask_idx;  int nmask;
+    double*        out_lwa;   int8_t* out_masks;
+};
+int launch_lwa(xc_ctx* ctx, const LwaArgs& a);
 size_t sort_workspace_bytes(int64_t n, int64_t nslab);
 // K8: one sort_profile call.  Device pointers; `workspace` holds sort_workspace_bytes(ny * nx, nslab) bytes; the out_* may be null
 struct SortArgs {
