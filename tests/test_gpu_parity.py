@@ -814,8 +814,9 @@ def test_crossing_random_vs_oracle(ctx, dt, stride, mode):
 
 @pytest.mark.parametrize('adt', [np.float32, np.float64])
 def test_crossing_stack_sharing_one_area_plane(ctx, adt):
-    """>= 8 slabs with a shared area plane take the square roots once (k_cross_weights); equally spaced levels go through the
-    difference-array accumulation, other levels through the scan: counts exact, lengths to summation order, per level"""
+    """a stack of 9 slabs sharing one area plane (k_crossing takes the square root of a box's area where the box is crossed);
+    equally spaced levels go through the difference-array accumulation, other levels through the scan: counts exact, lengths to
+    summation order, per level"""
     rng = np.random.default_rng(77)
     ny, nx, S = 61, 200, 9
     lat = np.linspace(-1, 1, ny)

@@ -128,6 +128,9 @@ def case_keff():
 
 def case_crossing():
     S, ny, nx = int(rng.integers(1, 4)), int(rng.integers(2, 80 * SC)), int(rng.integers(2, 300 * SC))
+    N = int(rng.choice([1, 3, 17, 60, 300, 500, 900, 1500]))          # 8 / 4 / 2 / 1 LDS copies, several compaction chunks, prefix-only epilogue
+    if N > 300:
+        S = 1
     dt = rng.choice([np.float32, np.float64])
     q = field(S, ny, nx, dt)
     stride = int(rng.choice([1, 1, 2, 3, 4, 6, 7, 9, 16, 33]))
@@ -137,8 +140,14 @@ def case_crossing():
         return
     if mode == 'symmetric' and pad > nx:
         return
-    cs = np.sort(rng.uniform(-2, 2, int(rng.integers(1, 40))))
-    area = (rng.random((ny, nx)) + 0.2).astype(rng.choice([np.float32, np.float64]))
+    kind = int(rng.integers(0, 3))
+    if kind == 0 or N < 3:
+        cs = np.sort(rng.uniform(-2, 2, N))                          # the scan route
+    else:
+        cs = np.linspace(-2, 2, N)                                   # equally spaced: the arithmetic level search, difference array
+        if kind == 2:
+            cs = cs + rng.uniform(-0.004, 0.004, N) * (4.0 / (N - 1))     # still equally spaced to the kernel, wide verification zone
+    area =(rng.random((ny, nx)) + 0.2).astype(rng.choice([np.float32, np.float64]))
     full = bool(rng.random() < 0.5)
     lens, cnts = ctx.crossing(q, cs, area, stride=stride, pad_x=pad, pad_mode=mode, full_width=full)
     for s in range(S):
