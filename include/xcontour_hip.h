@@ -327,7 +327,8 @@ int xc_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t 
  * Replaces Contour2D.cal_contour_lengths (core.py:969-1014), _contour_lengths (core.py:1437-1487) and
  * utils.contour_length / __segment_length_latlon / __segment_length_cartesian / __geodist (utils.py:565-761):
  * the total length of every contour traced by skimage's find_contours(slab, c) (defaults), for ALL contours
- * of a slab in one pass.  Rows are ycoord (ny), columns xcoord (nx); no wrap across the X seam.
+ * of a slab in one pass.  Rows are ycoord (ny), columns xcoord (nx); no wrap across the X seam unless the
+ * _periodic entry points below are used.
  *   a cell with a NaN corner contributes nothing; case = (ul>c) + 2(ur>c) + 4(ll>c) + 8(lr>c);
  *   saddles 6 and 9 pair their points like fully_connected='low'; a segment whose two end points are
  *   equal is dropped; end points map to coordinates like np.interp(x, arange(n), coord).
@@ -349,12 +350,36 @@ int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, i
                        const double* contours, int ncont, int contours_per_slab,
                        double* out_len, uint64_t* out_nseg);
 
+/* K10 with a periodic X direction (a longitude ring).  The Y direction is never periodic.
+ *   period: a float64, finite and non-zero, of the sign of xcoord[nx-1] - xcoord[0], with
+ *     |period| > |xcoord[nx-1] - xcoord[0]|; the ring needs nx >= 2.  The coordinate of a node column c outside
+ *     [0, nx) is xcoord[c mod nx] + period or xcoord[c mod nx] - period: one float64 addition or subtraction
+ *     (only one lap either way can occur).
+ *   The plane gains one cell column, index nx-1: its left corners are node column nx-1, its right corners node
+ *     column 0; cL = nx-1, xL = xcoord[nx-1], xR = xcoord[0] + period.  Everything else is the rule above,
+ *     unchanged: case table, frac, np.interp end points between (nx-1, xL) and (nx, xR), saddles, dropped
+ *     degenerate segments, a NaN corner emits nothing, a total of 0 becomes NaN.  The window constant of the
+ *     fixed-point sums takes the seam cell's width into its largest cell diagonal.
+ *   By construction the result is, bit for bit, what xc_contour_lengths returns for the plane with column 0
+ *     appended as column nx and xcoord[0] + period appended to the coordinates.
+ * The host form checks the period conditions (XC_EBADARG); the device form checks what it can without reading
+ * xcoord (finite, non-zero, nx >= 2).  xc_last_clen_geometry counts the tiles over nx cell columns.          */
+int xc_contour_lengths_periodic_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                    const double* ycoord, const double* xcoord, double period, double radius,
+                                    const double* contours, int ncont, int contours_per_slab,
+                                    double* out_len, uint64_t* out_nseg);
+int xc_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                const double* ycoord, const double* xcoord, double period, double radius,
+                                const double* contours, int ncont, int contours_per_slab,
+                                double* out_len, uint64_t* out_nseg);
+
 /* ------------------------------------------------------------------ K11 local (sliding-window) contour lengths
  * Replaces the loop of the reference's tests/test_localLength.py (rolling(center=True).construct(stride=), one
  * find_contours call per window): per window, the length of ONE contour traced on the window alone.
  *   windows: centres are the nodes (j, i), j = 0, sy, 2 sy, ... < ny and i = 0, sx, ... < nx, so
  *     nwy = ceil(ny / sy), nwx = ceil(nx / sx); window (j, i) owns node rows [j - wy/2, j - wy/2 + wy - 1]
- *     (integer division) and likewise columns, clipped to the plane; no wrap across the X seam.  wy, wx >= 2;
+ *     (integer division) and likewise columns, clipped to the plane; no wrap across the X seam unless the
+ *     _periodic entry points below are used.  wy, wx >= 2;
  *   level: levels[slab][wj][wi] when `levels` is given; else (levels == NULL) the window's NaN-skipping mean in
  *     float64, in a fixed order: per window row the valid nodes left to right from 0.0 (a NaN node adds nothing
  *     and does not count), the row sums top to bottom, one IEEE division by the valid count; fewer than
@@ -375,6 +400,22 @@ int xc_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t ns
                              const double* ycoord, const double* xcoord, double radius,
                              int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
                              const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
+
+/* K11 with a periodic X direction: `period` as for xc_contour_lengths_periodic.  Windows are no longer clipped in X:
+ *   window i owns the node columns [i - wx/2, i - wx/2 + wx - 1] taken modulo nx, in that (unwrapped) order, with the
+ *   unwrapped coordinates xcoord[c mod nx] +/- period.  It needs wx <= nx, else XC_EBADARG.  Y clipping, the window
+ *   centres and nwx = ceil(nx / sx) are unchanged.  The mean level keeps its order: per row left to right in window
+ *   order.  Length, NaN rules and the window constant are those of periodic K10.  The result is, bit for bit, what
+ *   xc_local_contour_lengths returns at the matching centres of the plane with h columns of the ring copied to either
+ *   side (h a multiple of sx, h >= wx).                                                                           */
+int xc_local_contour_lengths_periodic_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                          const double* ycoord, const double* xcoord, double period, double radius,
+                                          int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                          const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
+int xc_local_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                      const double* ycoord, const double* xcoord, double period, double radius,
+                                      int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                      const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
 
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
@@ -479,7 +520,7 @@ typedef struct xc_hist_variant {
     int32_t G, cps, rpc;                                         /* K3S: workgroups, chunks per strip, rows per chunk */
 } xc_hist_variant;
 int xc_last_hist_variant(xc_ctx* ctx, xc_hist_variant* out);
-/* how the last xc_contour_lengths / xc_contour_lengths_dev call launched K10, as the launcher chose it on the host.  All zero
+/* how the last xc_contour_lengths / xc_contour_lengths_dev call (or its _periodic form) launched K10, as the launcher chose it on the host.  All zero
  * when the last such call failed; bps = 0 (and bps_rule 0) when the plane has no cells.                                      */
 #define XC_CLEN_BPS_SHARE    1   /* bps = 2048 / nslab: the launch's share of ~2048 blocks */
 #define XC_CLEN_BPS_FLOOR    2   /* bps = 8: the floor under that share */

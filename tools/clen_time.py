@@ -4,6 +4,7 @@ PV-like, 1: pure noise), N levels from the field's range, lat / lon in radians. 
 `rocprofv3 --kernel-trace --stats -- python tools/clen_time.py ...` for the per-kernel times.
 
     python tools/clen_time.py --slabs 64 --variant 0 --ncont 121 --reps 5
+    python tools/clen_time.py --slabs 64 --periodic        # the longitude ring closed (xc_contour_lengths_periodic_dev)
 """
 import argparse
 import os
@@ -23,6 +24,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ny', type=int, default=1801)
     ap.add_argument('--nx', type=int, default=3600)
+    ap.add_argument('--periodic', action='store_true', help='periodic X: the period is 360 degrees (float32 radians)')
     a = ap.parse_args()
     from xcontour_amd import _native as nat
     ctx = nat.Context(0)
@@ -39,9 +41,15 @@ def main():
     dy, dx, dc = ctx.to_device(y), ctx.to_device(x), ctx.to_device(lv)
     out, cnt = ctx.alloc(S * a.ncont * 8), ctx.alloc(S * a.ncont * 8)
 
+    period = float(np.float64(np.deg2rad(np.float32(360.0))))
+
     def call():
-        ctx._check(ctx.lib.xc_contour_lengths_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, 6371200.0,
-                                                  dc.ptr, a.ncont, 0, out.ptr, cnt.ptr))
+        if a.periodic:
+            ctx._check(ctx.lib.xc_contour_lengths_periodic_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, period, 6371200.0,
+                                                               dc.ptr, a.ncont, 0, out.ptr, cnt.ptr))
+        else:
+            ctx._check(ctx.lib.xc_contour_lengths_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, 6371200.0,
+                                                      dc.ptr, a.ncont, 0, out.ptr, cnt.ptr))
     call()
     ctx.sync()
     e0, e1 = ctx.event(), ctx.event()
@@ -52,9 +60,9 @@ def main():
     ctx.sync()
     ms = ctx.elapsed_ms(e0, e1) / a.reps
     n = cnt.download((S, a.ncont), np.uint64)
-    cells = S * (ny - 1) * (nx - 1)
-    print('slabs %d variant %d ncont %d: %.1f us per call, %.2f us per slab, %.2f segments per cell, %.0f GB/s of tracer'
-          % (S, a.variant, a.ncont, ms * 1e3, ms * 1e3 / S, float(n.sum()) / cells, S * ny * nx * 8 / (ms * 1e-3) / 1e9))
+    cells = S * (ny - 1) * (nx if a.periodic else nx - 1)
+    print('slabs %d variant %d ncont %d%s: %.1f us per call, %.2f us per slab, %.2f segments per cell, %.0f GB/s of tracer'
+          % (S, a.variant, a.ncont, ' periodic' if a.periodic else '', ms * 1e3, ms * 1e3 / S, float(n.sum()) / cells, S * ny * nx * 8 / (ms * 1e-3) / 1e9))
     ctx.close()
 
 

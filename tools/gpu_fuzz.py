@@ -174,10 +174,16 @@ def case_clen():
     cs = np.sort(rng.uniform(-2.5, 2.5, (S, N) if per_slab else N), axis=-1)
     if rng.random() < 0.3:
         cs = np.sort(np.linspace(-2, 2, N) + 0 * cs, axis=-1)          # equally spaced: the arithmetic level search
-    lens, cnts = ctx.contour_lengths(q, cs, y, x, radius=CR.RADIUS if latlon else 0.0)
+    period = None
+    if nx >= 2 and rng.random() < 0.4:                                # periodic X: the plane with column 0 appended one period on
+        period = float(x[-1] - x[0] + rng.uniform(0.2, 3.0) * (0.005 if latlon else 1e3))
+    lens, cnts = ctx.contour_lengths(q, cs, y, x, radius=CR.RADIUS if latlon else 0.0, period=period)
     for s in range(S):
-        rt, rn = CR.contour_lengths(q[s].astype(np.float64), cs[s] if per_slab else cs, y, x, latlon)
-        assert np.array_equal(cnts[s].astype(np.int64), rn), 'clen counts %r' % ((S, ny, nx, N, latlon, per_slab),)
+        qs, xs = q[s].astype(np.float64), x
+        if period is not None:
+            qs, xs = np.concatenate([qs, qs[:, :1]], axis=1), np.concatenate([x, [x[0] + period]])
+        rt, rn = CR.contour_lengths(qs, cs[s] if per_slab else cs, y, xs, latlon)
+        assert np.array_equal(cnts[s].astype(np.int64), rn), 'clen counts %r' % ((S, ny, nx, N, latlon, per_slab, period),)
         assert relerr(lens[s], rt) < 1e-12, 'clen lengths'
         tick('clen')
 

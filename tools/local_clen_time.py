@@ -5,6 +5,7 @@ Prints the event time per call; run it under `rocprofv3 --kernel-trace --stats -
 per-kernel times.
 
     python tools/local_clen_time.py --slabs 1 --variant 0 --window 101 --stride 10 --reps 5
+    python tools/local_clen_time.py --periodic             # windows run on round the longitude ring (xc_local_contour_lengths_periodic_dev)
 """
 import argparse
 import os
@@ -25,6 +26,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ny', type=int, default=1801)
     ap.add_argument('--nx', type=int, default=3600)
+    ap.add_argument('--periodic', action='store_true', help='periodic X: the period is 360 degrees (float32 radians)')
     ap.add_argument('--given', action='store_true', help='give the levels (the means of a first call): phase two alone')
     a = ap.parse_args()
     from xcontour_amd import _native as nat
@@ -42,9 +44,15 @@ def main():
     out, lvl, cnt = ctx.alloc(S * nwin * 8), ctx.alloc(S * nwin * 8), ctx.alloc(S * nwin * 8)
     given = ctx.alloc(S * nwin * 8)
 
+    period = float(np.float64(np.deg2rad(np.float32(360.0))))
+
     def call(levels=None, lvl_out=lvl):
-        ctx._check(ctx.lib.xc_local_contour_lengths_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, 6371200.0,
-                                                        w, w, st, st, 1, levels, out.ptr, lvl_out.ptr, cnt.ptr))
+        if a.periodic:
+            ctx._check(ctx.lib.xc_local_contour_lengths_periodic_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, period,
+                                                                     6371200.0, w, w, st, st, 1, levels, out.ptr, lvl_out.ptr, cnt.ptr))
+        else:
+            ctx._check(ctx.lib.xc_local_contour_lengths_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, 6371200.0,
+                                                            w, w, st, st, 1, levels, out.ptr, lvl_out.ptr, cnt.ptr))
     call(lvl_out=given)
     ctx.sync()
     levels = given.ptr if a.given else None
@@ -60,9 +68,9 @@ def main():
     n = cnt.download((S, nwin), np.uint64)
     ln = out.download((S, nwin), np.float64)
     nodes = S * nwin * min(w, ny) * min(w, nx)
-    print('slabs %d variant %d window %d stride %d%s: %d windows, %.1f us per call, %.2f us per slab, %.1f segments per window, '
+    print('slabs %d variant %d window %d stride %d%s%s: %d windows, %.1f us per call, %.2f us per slab, %.1f segments per window, '
           '%.1f %% of the windows with a contour, %.0f G window nodes per s'
-          % (S, a.variant, w, st, ' (levels given)' if a.given else '', S * nwin, ms * 1e3, ms * 1e3 / S, float(n.sum()) / (S * nwin),
+          % (S, a.variant, w, st, ' periodic' if a.periodic else '', ' (levels given)' if a.given else '', S * nwin, ms * 1e3, ms * 1e3 / S, float(n.sum()) / (S * nwin),
              100.0 * float(np.mean(~np.isnan(ln))), nodes / (ms * 1e-3) / 1e9))
     ctx.close()
 

@@ -145,6 +145,11 @@ PROTOTYPES = {
     'xc_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
     'xc_local_contour_lengths_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'xc_local_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    # the periodic forms: the same lists with `double period` after xcoord
+    'xc_contour_lengths_periodic_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_contour_lengths_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_local_contour_lengths_periodic_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'xc_local_contour_lengths_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -265,6 +270,17 @@ def _stack_now(q, s0, s1):
     if _is_lazy(q):
         return np.ascontiguousarray(q[s0:s1])
     return q if s1 - s0 == q.shape[0] else q[s0:s1]
+
+
+def _check_period(period, xcoord, what):
+    """the period of a periodic X direction (K10, K11) as a float, checked against the host coordinates: finite, non-zero, of the
+    sign of xcoord[-1] - xcoord[0] and longer than that span; the ring needs two columns"""
+    period = float(period)
+    span = float(xcoord[-1] - xcoord[0]) if xcoord.size >= 2 else 0.0
+    if (xcoord.size < 2 or not np.isfinite(period) or period == 0.0 or period * span < 0.0 or not abs(period) > abs(span)):
+        raise XContourHipError(XC_EBADARG, '%s: period must be finite, non-zero, of the sign of xcoord[nx-1] - xcoord[0] and longer '
+                               'than that span, and nx >= 2' % what)
+    return period
 
 
 def _part(a, slab_ndim, s0, s1):
@@ -859,12 +875,14 @@ class Context(object):
             return lens, cnts
         return self._batched(nslab, ny * nx * (q.dtype.itemsize + (area.dtype.itemsize if area.ndim == 3 else 0)), one)
 
-    def contour_lengths(self, q, contours, ycoord, xcoord, radius=0.0):
+    def contour_lengths(self, q, contours, ycoord, xcoord, radius=0.0, period=None):
         """Marching-squares contour lengths (xc_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours (N,) or
         (nslab, N) ASCENDING f64; ycoord (ny,) / xcoord (nx,) the coordinates of rows / columns (radians when radius > 0).
         radius > 0: great-circle lengths times radius; 0: Cartesian.  Returns (lengths f64 (nslab, N), NaN where the total is 0;
         segment counts uint64 (nslab, N)).  A tracer with a device mirror (keep_resident) is read in place through the _dev
-        entry point."""
+        entry point.  period: None -- the plane has two free edges in X --, or the period of the X coordinate (in its units:
+        radians when radius > 0; of the sign of xcoord[-1] - xcoord[0] and longer than that span): the cell between the last and
+        the first column is traced too (xc_contour_lengths_periodic), as on the plane with column 0 appended one period on."""
         q = _stack_in(q)
         if len(q.shape) != 3:
             raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
@@ -879,6 +897,14 @@ class Context(object):
                                    % (ycoord.size, xcoord.size, ny, nx))
         radius = float(radius)
         N = contours.shape[-1]
+        if period is not None:
+            if not np.isfinite(xcoord).all():
+                raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
+            period = _check_period(period, xcoord, 'xc_contour_lengths_periodic')
+        # what follows xcoord in the argument lists, and the entry points that take it
+        mid = (radius,) if period is None else (period, radius)
+        f_host = self.lib.xc_contour_lengths if period is None else self.lib.xc_contour_lengths_periodic
+        f_dev = self.lib.xc_contour_lengths_dev if period is None else self.lib.xc_contour_lengths_periodic_dev
 
         def one(s0, s1):
             n = s1 - s0
@@ -890,24 +916,25 @@ class Context(object):
                 if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
                     raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
                 with self._temporaries([ycoord, xcoord, cb], [n * N * 8, n * N * 8]) as (dy, dx, dc, dl, dn):
-                    self._check(self.lib.xc_contour_lengths_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr,
-                                                                dx.ptr, radius, dc.ptr, N, 1 if per_slab else 0, dl.ptr, dn.ptr))
+                    self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *mid, dc.ptr, N,
+                                      1 if per_slab else 0, dl.ptr, dn.ptr))
                     return dl.download((n, N), np.float64), dn.download((n, N), np.uint64)
             lens = np.empty((n, N), dtype=np.float64)
             cnts = np.empty((n, N), dtype=np.uint64)
-            self._check(self.lib.xc_contour_lengths(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord),
-                                                    _ptr(xcoord), radius, _ptr(cb), N, 1 if per_slab else 0,
-                                                    _ptr(lens), _ptr(cnts)))
+            self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord), *mid, _ptr(cb), N,
+                               1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
             return lens, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
-    def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0):
+    def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):
         """Sliding-window contour lengths (xc_local_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); ycoord (ny,) /
         xcoord (nx,) as for contour_lengths; window (wy, wx) nodes, both >= 2; stride (sy, sx), both >= 1: the windows are centred
         on the nodes (0, sy, 2 sy, ...) x (0, sx, ...) and clipped to the plane.  levels: None -- every window is traced at its
         NaN-skipping mean (NaN with fewer than `min_periods` valid nodes) --, a scalar, or an array over (nslab, nwy, nwx) /
         (nwy, nwx).  Returns (lengths f64 (nslab, nwy, nwx), NaN where the total is 0; the levels used f64; segment counts
-        uint64).  A tracer with a device mirror (keep_resident) is read in place through the _dev entry point."""
+        uint64).  A tracer with a device mirror (keep_resident) is read in place through the _dev entry point.  period: None, or
+        the period of the X coordinate as for contour_lengths: windows are then not clipped in X but run on round the ring
+        (xc_local_contour_lengths_periodic; the window must not be wider than the ring, wx <= nx)."""
         q = _stack_in(q)
         if len(q.shape) != 3:
             raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
@@ -923,6 +950,11 @@ class Context(object):
                                    % (ycoord.size, xcoord.size, ny, nx))
         if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
             raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: coordinates must be finite')
+        if period is not None:
+            period = _check_period(period, xcoord, 'xc_local_contour_lengths_periodic')
+            if wx > nx:
+                raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths_periodic: the window must not be wider than the ring '
+                                       '(wx <= nx)')
         nwy, nwx = -(-ny // sy), -(-nx // sx)
         if levels is not None:
             levels = np.asarray(levels, dtype=np.float64)
@@ -931,6 +963,10 @@ class Context(object):
             levels = np.ascontiguousarray(np.broadcast_to(levels, (nslab, nwy, nwx)))
         shape = (ny, nx)
         rest = (float(radius), wy, wx, sy, sx, int(min_periods))
+        if period is not None:
+            rest = (period,) + rest
+        f_host = self.lib.xc_local_contour_lengths if period is None else self.lib.xc_local_contour_lengths_periodic
+        f_dev = self.lib.xc_local_contour_lengths_dev if period is None else self.lib.xc_local_contour_lengths_periodic_dev
         ob = nwy * nwx * 8
 
         def one(s0, s1):
@@ -942,15 +978,14 @@ class Context(object):
                 with self._temporaries([ycoord, xcoord] + ([lb] if lb is not None else []), [n * ob] * 3) as bufs:
                     dy, dx = bufs[:2]
                     dl, de, dn = bufs[-3:]
-                    self._check(self.lib.xc_local_contour_lengths_dev(self.handle, qp, dtype_code(q.dtype), n, *shape, dy.ptr, dx.ptr,
-                                                                      *rest, bufs[2].ptr if lb is not None else None,
-                                                                      dl.ptr, de.ptr, dn.ptr))
+                    self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, *shape, dy.ptr, dx.ptr, *rest,
+                                      bufs[2].ptr if lb is not None else None, dl.ptr, de.ptr, dn.ptr))
                     return (dl.download((n, nwy, nwx), np.float64), de.download((n, nwy, nwx), np.float64),
                             dn.download((n, nwy, nwx), np.uint64))
             lens, lvls = np.empty((n, nwy, nwx), dtype=np.float64), np.empty((n, nwy, nwx), dtype=np.float64)
             cnts = np.empty((n, nwy, nwx), dtype=np.uint64)
-            self._check(self.lib.xc_local_contour_lengths(self.handle, _ptr(qb), dtype_code(q.dtype), n, *shape, _ptr(ycoord),
-                                                          _ptr(xcoord), *rest, _ptr(lb), _ptr(lens), _ptr(lvls), _ptr(cnts)))
+            self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, *shape, _ptr(ycoord), _ptr(xcoord), *rest, _ptr(lb),
+                               _ptr(lens), _ptr(lvls), _ptr(cnts)))
             return lens, lvls, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize + 4 * ob, one)
 

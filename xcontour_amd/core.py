@@ -681,7 +681,37 @@ class Contour2D(object):
         return np.take_along_axis(b, order, axis=1), order, ccoord
 
     # ------------------------------------------------------------------ contour lengths
-    def cal_contour_lengths(self, contours, tracer=None, latlon=False):
+    @staticmethod
+    def _x_period(periodic, xdeg, latlon, who):
+        """the `periodic` argument of cal_contour_lengths / cal_local_contour_lengths -> None (X has two free edges) or the period
+        handed to the library, a float64 in the units of the X coordinates it gets: float64(P), with latlon=True
+        float64(deg2rad(float32(P))) -- the cast chain of the coordinates themselves.  `xdeg`: the X coordinate as given, after
+        its cast to float32.  True: 360 degrees, along the direction the coordinate runs in."""
+        if periodic is None or periodic is False or (isinstance(periodic, np.bool_) and not periodic):
+            return None
+        span = float(xdeg[-1]) - float(xdeg[0]) if xdeg.size >= 2 else 0.0
+        if periodic is True or isinstance(periodic, np.bool_):
+            if not latlon:
+                raise Exception('%s: periodic=True needs latlon=True (there is no default period for a Cartesian plane: '
+                                'give periodic=<the period>)' % who)
+            P = -360.0 if span < 0 else 360.0
+        else:
+            try:
+                P = float(periodic)
+            except (TypeError, ValueError):
+                raise Exception('%s: periodic should be False, True or the period as a number' % who)
+        if xdeg.size < 2:
+            raise Exception('%s: periodic needs at least two columns along the periodic dim' % who)
+        if not np.isfinite(P) or P == 0.0:
+            raise Exception('%s: periodic should be a finite, non-zero period, not %r' % (who, periodic))
+        if P * span < 0.0:
+            raise Exception('%s: periodic=%r runs against the X coordinate (%r ... %r): give it the sign of last - first'
+                            % (who, periodic, float(xdeg[0]), float(xdeg[-1])))
+        if not abs(P) > abs(span):
+            raise Exception('%s: periodic=%r is too short: the X coordinate already spans %r' % (who, periodic, abs(span)))
+        return float(np.float64(np.deg2rad(np.float32(P)))) if latlon else float(np.float64(P))
+
+    def cal_contour_lengths(self, contours, tracer=None, latlon=False, periodic=False):
         """
         Perimeter of every contour (reference core.py:969-1014, _contour_lengths 1437-1487 and
         utils.contour_length 565-608): the total length of what skimage's find_contours(plane, c)
@@ -692,7 +722,11 @@ class Contour2D(object):
         coordinates are cast to float32 as the reference does (core.py:1003-1004) and, with
         latlon=True, converted to radians in float32; segments are then great-circle arcs times
         Rearth, else Cartesian distances.  A cell with a NaN corner contributes nothing, and
-        contours do not wrap across the X seam (skimage does neither).  A contour of total length 0
+        contours do not wrap across the X seam (skimage does neither) unless `periodic`: True --
+        360 degrees, with latlon=True only -- or the period in the X coordinate's units (degrees
+        with latlon=True; of the sign of last - first and longer than that span).  The cell
+        between the last and the first column is then traced too, so a contour that circles the
+        pole is closed.  A contour of total length 0
         -- a level outside the field's range, at its minimum or maximum, or NaN -- gives NaN
         (utils.py:603-604).  With latlon=True the latitude is the plane's real latitude whatever the
         tracer's dim order (the reference would read longitude as latitude on an (X, Y) tracer).
@@ -709,15 +743,16 @@ class Contour2D(object):
         for d in (self.dimEqV, self._xdim):
             v = np.asarray(dcoords[d]).astype(np.float32)                      # core.py:1003-1004
             fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
+        period = self._x_period(periodic, v, latlon, 'cal_contour_lengths')
         q, lead, lshape, coords = self._plane(data)
         q = self._float(q)
         nslab = q.shape[0]
         bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
-        lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0)
+        lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
         return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
 
     def cal_local_contour_lengths(self, window, stride=1, levels=None, min_periods=None, tracer=None, latlon=False,
-                                  return_levels=False):
+                                  return_levels=False, periodic=False):
         """
         Contour length in a sliding window (the loop of the reference's tests/test_localLength.py: rolling(center=True)
         .construct(stride=) and one find_contours call per window), all windows of all slabs in one GPU pass (K11,
@@ -725,7 +760,9 @@ class Contour2D(object):
 
         `window` and `stride`: an int, or a {dim: int} dict over the two plane dims (window >= 2 nodes, stride >= 1).  Windows
         are centred on the nodes 0, stride, 2 stride, ... of each plane dim, own the nodes [centre - window // 2,
-        centre - window // 2 + window - 1] and are clipped at the plane's edges (no wrap across the X seam).  Every window is
+        centre - window // 2 + window - 1] and are clipped at the plane's edges (no wrap across the X seam unless `periodic`:
+        True or a period, as for cal_contour_lengths -- windows then run on round the ring along the non-equivalent plane dim
+        instead of being clipped there, and must not be wider than the ring).  Every window is
         traced on its own, as a small plane, at ONE level: `levels` -- a scalar, or an array over (..., windows along the
         equivalent dim, windows along the other plane dim) -- or, by default, the window's NaN-skipping mean, NaN when the
         window holds fewer than `min_periods` valid nodes (None: the full window, as xarray's rolling does).  The length
@@ -757,6 +794,9 @@ class Contour2D(object):
         for d in pdims:
             v = np.asarray(dcoords[d]).astype(np.float32)                      # as cal_contour_lengths
             fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
+        period = self._x_period(periodic, v, latlon, 'cal_local_contour_lengths')
+        if period is not None and win[1] > v.size:
+            raise Exception('window should not be wider than the periodic dim %s: %d > %d nodes' % (self._xdim, win[1], v.size))
         q, lead, lshape, coords = self._plane(data)
         q = self._float(q)
         nslab, ny, nx = q.shape
@@ -774,7 +814,7 @@ class Contour2D(object):
                 levels = levels.reshape((nslab,) + nw)
         mp = win[0] * win[1] if min_periods is None else int(min_periods)
         lens, lvls, _ = self.ctx.local_contour_lengths(q, fdef[0], fdef[1], win, st, mp, levels=levels,
-                                                       radius=Rearth if latlon else 0.0)
+                                                       radius=Rearth if latlon else 0.0, period=period)
         c = {d: np.asarray(coords[d]) for d in lead if d in coords}
         for d, t in zip(pdims, st):
             c[d] = np.asarray(dcoords[d])[::t]

@@ -26,7 +26,18 @@
 // Capacity: a limb word takes at most one chunk (< 2^48) per segment; a block gives each of its `ncopy` LDS copies at most
 // 32767 cells (launcher), i.e. at most 65534 chunks (< 2^64), and carries before it writes.  Levels that do not fit the LDS
 // budget are split over gridDim.z (each group a full pass: any N is accepted).
+//
+// Periodic X (WRAP, xc_contour_lengths_periodic): the plane gains one cell column, index nx-1, whose left corners are node column
+// nx-1 and whose right corners are node column 0: cL = nx-1, xL = fx[nx-1], xR = fx[0] + period (one float64 addition); everything
+// else is the rule above, and the window constant takes that cell's width into its largest cell diagonal.  The result is, bit for
+// bit, what the plain kernel returns for the plane with column 0 appended as column nx and fx[0] + period appended to the
+// coordinates.  period: finite, non-zero, of the sign of fx[nx-1] - fx[0], |period| > |fx[nx-1] - fx[0]|; nx >= 2.  Y never wraps.
+// Kernels k_ring_len / k_ring_window; k_clen and k_clen_window are the same code with the wrap compiled out.
+// Mapping: tiles cover nx cell columns, and the lane whose column is nx -- the right neighbour of the seam cell's lane, a cell lane
+// or the wave's halo lane 63 -- loads node column 0 and carries fx[0] + period, so the seam cell takes its right corner by the
+// same DPP shift as every other cell.
 #include "xc_internal.h"
+#include <cmath>
 
 namespace xc {
 namespace {
@@ -40,15 +51,17 @@ constexpr int CLEN_TPB = 256;               // threads per block
 constexpr int CLEN_W = 252;                 // cell columns per tile: 4 waves x 63 cells
 constexpr size_t CLEN_LDS = 48 * 1024;      // LDS per block (several blocks per CU)
 
-// The window constant of every slab from a bound on one segment: pi on the unit sphere, else the largest cell diagonal.
-__global__ __launch_bounds__(256)
-void k_clen_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon,
-                   int64_t nslab, int* __restrict__ c0)
+// The window constant of every slab from a bound on one segment: pi on the unit sphere, else the largest cell diagonal (WRAP: the
+// seam cell, fx[nx-1] to fx[0] + period, among them).
+template <bool WRAP>
+__device__ __forceinline__ void clen_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon,
+                                            int64_t nslab, int* __restrict__ c0, double period)
 {
     const int tid = threadIdx.x;
     double my = 0.0, mx = 0.0;
     for (int64_t i = tid; i + 1 < ny; i += 256) my = fmax(my, fabs(fy[i + 1] - fy[i]));
     for (int64_t i = tid; i + 1 < nx; i += 256) mx = fmax(mx, fabs(fx[i + 1] - fx[i]));
+    if constexpr (WRAP) { if (tid == 0) mx = fmax(mx, fabs(__dadd_rn(fx[0], period) - fx[nx - 1])); }
     for (int o = 32; o > 0; o >>= 1) { my = fmax(my, __shfl_xor(my, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
     __shared__ double s_m[2][4];
     if ((tid & 63) == 0) { s_m[0][tid >> 6] = my; s_m[1][tid >> 6] = mx; }
@@ -60,13 +73,29 @@ void k_clen_window(const double* __restrict__ fy, int64_t ny, const double* __re
     for (int64_t s = tid; s < nslab; s += 256) c0[s] = w;
 }
 
-// grid (bps, nslab, level groups of G).  LDS: levels [G + 2] (-inf, the group's levels, +inf), then per (level, copy)
-// CLEN_WORDS limb words and one count word.
-template <typename TQ, bool LATLON>
-__global__ __launch_bounds__(CLEN_TPB)
-void k_clen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx,
+__global__ __launch_bounds__(256)
+void k_clen_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon,
+                   int64_t nslab, int* __restrict__ c0)
+{
+    clen_window<false>(fy, ny, fx, nx, latlon, nslab, c0, 0.0);
+}
+
+__global__ __launch_bounds__(256)
+void k_ring_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon,
+                   int64_t nslab, int* __restrict__ c0, double period)
+{
+    clen_window<true>(fy, ny, fx, nx, latlon, nslab, c0, period);
+}
+
+// The pass of k_clen (WRAP = false: the plane as it is) and k_ring_len (WRAP = true: periodic X); WRAP is a compile-time variant: the
+// plain kernel pays nothing for it.  grid (bps, nslab, level groups of G).  LDS: levels [G + 2] (-inf, the group's levels, +inf), then per
+// (level, copy) CLEN_WORDS limb words and one count word.
+template <typename TQ, bool LATLON, bool WRAP>
+__device__ __forceinline__
+void clen_pass(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx,
             const double* __restrict__ contours, int N, int contours_per_slab, int G, const int* __restrict__ c0s,
-            int64_t ntj, int64_t nti, int bps, int ncopy, unsigned long long* __restrict__ part_l, unsigned* __restrict__ part_c)
+            int64_t ntj, int64_t nti, int bps, int ncopy, unsigned long long* __restrict__ part_l, unsigned* __restrict__ part_c,
+            double period)
 {
     extern __shared__ double sm[];
     const int tid = threadIdx.x;
@@ -105,7 +134,7 @@ void k_clen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
     }
     const int cshift = __builtin_ctz((unsigned)ncopy), copy = tid & (ncopy - 1);
     const TQ* qs = q + (size_t)slab * ny * nx;
-    const int64_t ncx = nx - 1, ncy = ny - 1;
+    const int64_t ncx = WRAP ? nx : nx - 1, ncy = ny - 1;
     const int lane = tid & 63, wave = tid >> 6;
 
     for (int64_t tile = blockIdx.x; tile < ntj * nti; tile += bps) {
@@ -113,8 +142,15 @@ void k_clen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
         const int64_t i = ti * CLEN_W + wave * 63 + lane;                                // this lane's cell column
         const int64_t j0 = tj * CLEN_RB, j1 = (j0 + CLEN_RB < ncy) ? j0 + CLEN_RB : ncy;
         const bool cell = lane < 63 && i < ncx;                                          // lanes without a cell still load and shift
-        const int64_t c = i < nx - 1 ? i : nx - 1;                                       // corner column loaded by this lane
-        const double xL = fx[c], xR = lane_shift_keep<DPP_WAVE_SHL1>(xL, xL);
+        int64_t c = i < nx - 1 ? i : nx - 1;                                             // corner column loaded by this lane
+        double xL;
+        if constexpr (WRAP) {                                                            // column nx is column 0, one period on
+            if (i == nx) c = 0;
+            xL = i == nx ? __dadd_rn(fx[0], period) : fx[c];
+        } else {
+            xL = fx[c];
+        }
+        const double xR = lane_shift_keep<DPP_WAVE_SHL1>(xL, xL);
         const double cL = (double)c;
         double ul = (double)qs[(size_t)j0 * nx + c];
         double ur = lane_shift_keep<DPP_WAVE_SHL1>(ul, ul);
@@ -180,6 +216,28 @@ void k_clen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
     }
 }
 
+#define XC_CLEN_PARAMS const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx, \
+                        const double* __restrict__ contours, int N, int contours_per_slab, int G, const int* __restrict__ c0s,            \
+                        int64_t ntj, int64_t nti, int bps, int ncopy, unsigned long long* __restrict__ part_l, unsigned* __restrict__ part_c
+#define XC_CLEN_ARGS q, ny, nx, fy, fx, contours, N, contours_per_slab, G, c0s, ntj, nti, bps, ncopy, part_l, part_c
+
+template <typename TQ, bool LATLON>
+__global__ __launch_bounds__(CLEN_TPB)
+void k_clen(XC_CLEN_PARAMS)
+{
+    clen_pass<TQ, LATLON, false>(XC_CLEN_ARGS, 0.0);
+}
+
+// periodic X: the ring of nx cell columns
+template <typename TQ, bool LATLON>
+__global__ __launch_bounds__(CLEN_TPB)
+void k_ring_len(XC_CLEN_PARAMS, double period)
+{
+    clen_pass<TQ, LATLON, true>(XC_CLEN_ARGS, period);
+}
+#undef XC_CLEN_ARGS
+#undef XC_CLEN_PARAMS
+
 // total == 0 -> NaN (utils.py:603-604); else times the radius once (utils.py:606-607)
 __global__ __launch_bounds__(256)
 void k_clen_finish(double* __restrict__ out, int64_t n, double radius)
@@ -192,15 +250,19 @@ void k_clen_finish(double* __restrict__ out, int64_t n, double radius)
 
 }  // namespace
 
-int launch_clen_window(xc_ctx* ctx, const double* ycoord, int64_t ny, const double* xcoord, int64_t nx, int latlon, int64_t nslab, int* c0)
+int launch_clen_window(xc_ctx* ctx, const double* ycoord, int64_t ny, const double* xcoord, int64_t nx, double period, int latlon,
+                       int64_t nslab, int* c0)
 {
-    hipLaunchKernelGGL(k_clen_window, dim3(1), dim3(256), 0, ctx->stream, ycoord, ny, xcoord, nx, latlon, nslab, c0);
+    if (period != 0.0)
+        hipLaunchKernelGGL(k_ring_window, dim3(1), dim3(256), 0, ctx->stream, ycoord, ny, xcoord, nx, latlon, nslab, c0, period);
+    else
+        hipLaunchKernelGGL(k_clen_window, dim3(1), dim3(256), 0, ctx->stream, ycoord, ny, xcoord, nx, latlon, nslab, c0);
     XC_HIP(ctx, hipGetLastError());
     return XC_OK;
 }
 
 int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
-                           const double* ycoord, const double* xcoord, double radius,
+                           const double* ycoord, const double* xcoord, double period, double radius,
                            const double* contours, int N, int contours_per_slab, double* out_len, uint64_t* out_nseg)
 {
     if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || N < 1)
@@ -208,6 +270,10 @@ int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
     if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_lengths: q_dtype must be XC_F32 or XC_F64");
     if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: radius must be >= 0");
     if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_contour_lengths: nslab too large");
+    // period != 0: periodic X (the entry points have checked the period); the ring has nx cell columns
+    const bool wrap = period != 0.0;
+    if (wrap && (!std::isfinite(period) || nx < 2))
+        return fail(ctx, XC_EBADARG, "xc_contour_lengths_periodic: period must be finite and non-zero, and nx >= 2");
     // LDS: level values 8 B + per copy CLEN_WORDS x 8 + 4 B.  As many copies (up to 8) as the budget takes for all levels;
     // one copy and groups of G levels past it
     auto lds_of = [](int g, int nc) { return (size_t)(g + 2) * 8 + (size_t)g * nc * (CLEN_WORDS * 8 + 4) + 16; };
@@ -217,7 +283,7 @@ int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
     if (lds_of(N, ncopy) > CLEN_LDS) G = (int)((CLEN_LDS - 32) / (8 + CLEN_WORDS * 8 + 4));
     const int ngroup = (N + G - 1) / G;
     const size_t lds = lds_of(G, ncopy);
-    const int64_t ncx = nx - 1, ncy = ny - 1;
+    const int64_t ncx = wrap ? nx : nx - 1, ncy = ny - 1;
     const int64_t ntj = ncy > 0 ? (ncy + CLEN_RB - 1) / CLEN_RB : 0, nti = ncx > 0 ? (ncx + CLEN_W - 1) / CLEN_W : 0;
     const int64_t ntile = ntj * nti;
     // blocks per slab: ~2048 blocks per launch, and at most CLEN_COPY_CELLS cells per copy: a tile gives a copy
@@ -253,16 +319,20 @@ int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
     unsigned long long* nseg = out_nseg ? (unsigned long long*)out_nseg : (unsigned long long*)(sc + pl + pc + pw);
     const int latlon = radius > 0.0;
     {
-        const int rc = launch_clen_window(ctx, ycoord, ny, xcoord, nx, latlon, nslab, c0);
+        const int rc = launch_clen_window(ctx, ycoord, ny, xcoord, nx, period, latlon, nslab, c0);
         if (rc != XC_OK) return rc;
     }
     if (bps > 0) {
         const dim3 grid((unsigned)bps, (unsigned)nslab, (unsigned)ngroup);
-#define XC_CLEN(TQ_, LL_) hipLaunchKernelGGL((k_clen<TQ_, LL_>), grid, dim3(CLEN_TPB), lds, ctx->stream, (const TQ_*)q, ny, nx, \
-                                             ycoord, xcoord, contours, N, contours_per_slab, G, c0, ntj, nti, (int)bps, ncopy, part_l, part_c)
+#define XC_CLEN_ARGS(TQ_) (const TQ_*)q, ny, nx, ycoord, xcoord, contours, N, contours_per_slab, G, c0, ntj, nti, (int)bps, ncopy, part_l, part_c
+#define XC_CLEN(TQ_, LL_) do {                                                                                                        \
+            if (wrap) hipLaunchKernelGGL((k_ring_len<TQ_, LL_>), grid, dim3(CLEN_TPB), lds, ctx->stream, XC_CLEN_ARGS(TQ_), period);      \
+            else hipLaunchKernelGGL((k_clen<TQ_, LL_>), grid, dim3(CLEN_TPB), lds, ctx->stream, XC_CLEN_ARGS(TQ_));                       \
+        } while (0)
         if (q_dtype == XC_F64) { if (latlon) XC_CLEN(double, true); else XC_CLEN(double, false); }
         else { if (latlon) XC_CLEN(float, true); else XC_CLEN(float, false); }
 #undef XC_CLEN
+#undef XC_CLEN_ARGS
         XC_HIP(ctx, hipGetLastError());
     }
     const int rc = launch_det3_reduce(ctx, nslab, (int)bps, 1, N, reinterpret_cast<const double*>(part_l), part_c, c0, out_len, nseg);

@@ -24,8 +24,55 @@ static int clen_recorded(xc_ctx* ctx, int rc)
     return rc;
 }
 
+// the period of a periodic X direction (K10, K11) against the host coordinates: finite, non-zero, of the sign of
+// xcoord[nx-1] - xcoord[0] and longer than that span; the ring needs nx >= 2
+static bool check_period(const double* xcoord, int64_t nx, double period)
+{
+    if (nx < 2 || !std::isfinite(period) || period == 0.0) return false;
+    const double span = xcoord[nx - 1] - xcoord[0];
+    if ((span > 0.0 && period < 0.0) || (span < 0.0 && period > 0.0)) return false;
+    return std::fabs(period) > std::fabs(span);
+}
+
+// `periodic` == 0: `period` is not read and X does not wrap
+static int local_contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                      const double* ycoord, const double* xcoord, int periodic, double period, double radius,
+                                      int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                      const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
+{
+    if (!q || !ycoord || !xcoord || !out_len || nslab < 1 || ny < 1 || nx < 1)
+        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad dtype");
+    if (wy < 2 || wx < 2) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: the window must be at least 2 x 2 nodes");
+    if (sy < 1 || sx < 1) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: strides must be >= 1");
+    for (int64_t i = 0; i < ny; ++i)
+        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
+    for (int64_t i = 0; i < nx; ++i)
+        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
+    if (periodic && !check_period(xcoord, nx, period))
+        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: period must be finite, non-zero, of the sign of "
+                                     "xcoord[nx-1] - xcoord[0] and longer than that span, and nx >= 2");
+    if (periodic && wx > nx)
+        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: the window must not be wider than the ring (wx <= nx)");
+    const size_t nwin = (size_t)((ny + sy - 1) / sy) * (size_t)((nx + sx - 1) / sx);
+    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, ob = (size_t)nslab * nwin * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + 4 * al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb);
+    double* dv = levels ? (double*)st.take(ob) : nullptr;
+    double* dl = st.out(out_len, ob); double* de = st.out(out_level, ob); uint64_t* dn = st.out(out_nseg, ob);
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb));
+    if (levels) XC_TRY(h2d(ctx, dv, levels, ob));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_local_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, periodic ? period : 0.0, radius, wy, wx, sy, sx, min_periods,
+                                        dv, dl, de, dn));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
 static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
-                                const double* ycoord, const double* xcoord, double radius,
+                                const double* ycoord, const double* xcoord, int periodic, double period, double radius,
                                 const double* contours, int ncont, int contours_per_slab,
                                 double* out_len, uint64_t* out_nseg)
 {
@@ -37,6 +84,9 @@ static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t
         if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
     for (int64_t i = 0; i < nx; ++i)
         if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
+    if (periodic && !check_period(xcoord, nx, period))
+        return fail(ctx, XC_EBADARG, "xc_contour_lengths_periodic: period must be finite, non-zero, of the sign of xcoord[nx-1] - xcoord[0] "
+                                     "and longer than that span, and nx >= 2");
     const int64_t nc = contours_per_slab ? nslab : 1;
     if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_lengths: contours must be ascending without NaN");
     const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
@@ -48,7 +98,7 @@ static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t
     const void* pq;                                          // (a tracer with a device mirror is read where it is)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
     XC_TRY(flush_in(ctx));
-    XC_TRY(launch_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, radius, dc, ncont, contours_per_slab, dl, dn));
+    XC_TRY(launch_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, periodic ? period : 0.0, radius, dc, ncont, contours_per_slab, dl, dn));
     XC_TRY(st.deliver());
     return xc_sync(ctx);
 }
@@ -158,7 +208,7 @@ int xc_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
 {
     XC_CTX(ctx);
     ctx->last_clen = xc_clen_geometry{};
-    return clen_recorded(ctx, launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont,
+    return clen_recorded(ctx, launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 0.0, radius, contours, ncont,
                                                      contours_per_slab, out_len, out_nseg));
 }
 
@@ -169,7 +219,32 @@ int xc_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, i
 {
     XC_CTX(ctx);
     ctx->last_clen = xc_clen_geometry{};
-    return clen_recorded(ctx, contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, contours, ncont,
+    return clen_recorded(ctx, contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 0, 0.0, radius, contours, ncont,
+                                                   contours_per_slab, out_len, out_nseg));
+}
+
+// (the device form cannot read the coordinates: its caller vouches for the period's sign and length)
+int xc_contour_lengths_periodic_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                    const double* ycoord, const double* xcoord, double period, double radius,
+                                    const double* contours, int ncont, int contours_per_slab,
+                                    double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    if (!std::isfinite(period) || period == 0.0 || nx < 2)
+        return fail(ctx, XC_EBADARG, "xc_contour_lengths_periodic: period must be finite and non-zero, and nx >= 2");
+    return clen_recorded(ctx, launch_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, period, radius, contours, ncont,
+                                                     contours_per_slab, out_len, out_nseg));
+}
+
+int xc_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                const double* ycoord, const double* xcoord, double period, double radius,
+                                const double* contours, int ncont, int contours_per_slab,
+                                double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 1, period, radius, contours, ncont,
                                                    contours_per_slab, out_len, out_nseg));
 }
 
@@ -187,7 +262,7 @@ int xc_local_contour_lengths_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_
                                  const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
 {
     XC_CTX(ctx);
-    return launch_local_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, radius, wy, wx, sy, sx, min_periods,
+    return launch_local_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 0.0, radius, wy, wx, sy, sx, min_periods,
                                         levels, out_len, out_level, out_nseg);
 }
 
@@ -197,29 +272,31 @@ int xc_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t ns
                              const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
 {
     XC_CTX(ctx);
-    if (!q || !ycoord || !xcoord || !out_len || nslab < 1 || ny < 1 || nx < 1)
-        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad dtype");
-    if (wy < 2 || wx < 2) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: the window must be at least 2 x 2 nodes");
-    if (sy < 1 || sx < 1) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: strides must be >= 1");
-    for (int64_t i = 0; i < ny; ++i)
-        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
-    for (int64_t i = 0; i < nx; ++i)
-        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
-    const size_t nwin = (size_t)((ny + sy - 1) / sy) * (size_t)((nx + sx - 1) / sx);
-    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, ob = (size_t)nslab * nwin * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + 4 * al(ob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb);
-    double* dv = levels ? (double*)st.take(ob) : nullptr;
-    double* dl = st.out(out_len, ob); double* de = st.out(out_level, ob); uint64_t* dn = st.out(out_nseg, ob);
-    const void* pq;                                          // (a tracer with a device mirror is read where it is)
-    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb));
-    if (levels) XC_TRY(h2d(ctx, dv, levels, ob));
-    XC_TRY(flush_in(ctx));
-    XC_TRY(launch_local_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, radius, wy, wx, sy, sx, min_periods, dv, dl, de, dn));
-    XC_TRY(st.deliver());
-    return xc_sync(ctx);
+    return local_contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 0, 0.0, radius, wy, wx, sy, sx, min_periods,
+                                      levels, out_len, out_level, out_nseg);
+}
+
+// (the device form cannot read the coordinates: its caller vouches for the period's sign and length)
+int xc_local_contour_lengths_periodic_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                          const double* ycoord, const double* xcoord, double period, double radius,
+                                          int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                          const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    if (!std::isfinite(period) || period == 0.0 || nx < 2)
+        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: period must be finite and non-zero, and nx >= 2");
+    return launch_local_contour_lengths(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, period, radius, wy, wx, sy, sx, min_periods,
+                                        levels, out_len, out_level, out_nseg);
+}
+
+int xc_local_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                      const double* ycoord, const double* xcoord, double period, double radius,
+                                      int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
+                                      const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    return local_contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 1, period, radius, wy, wx, sy, sx, min_periods,
+                                      levels, out_len, out_level, out_nseg);
 }
 
 // ------------------------------------------------------------------------------------ K7

@@ -312,13 +312,15 @@ int launch_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int6
                     int pad_x, int pad_mode, const double* contours, int N, int contours_per_slab,
                     const void* area, int area_dtype, int area_per_slab, int stride, int full_width,
                     double* out_len, uint64_t* out_cnt);
+// K10 / K11: `period` != 0 makes X periodic (0: the plane has two free edges)
 int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
-                           const double* ycoord, const double* xcoord, double radius,
+                           const double* ycoord, const double* xcoord, double period, double radius,
                            const double* contours, int N, int contours_per_slab, double* out_len, uint64_t* out_nseg);
 // K10's window constant (one segment's bound from the plane's coordinates) for `nslab` slabs, into c0[nslab]
-int launch_clen_window(xc_ctx* ctx, const double* ycoord, int64_t ny, const double* xcoord, int64_t nx, int latlon, int64_t nslab, int* c0);
+int launch_clen_window(xc_ctx* ctx, const double* ycoord, int64_t ny, const double* xcoord, int64_t nx, double period, int latlon,
+                       int64_t nslab, int* c0);
 int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
-                                 const double* ycoord, const double* xcoord, double radius,
+                                 const double* ycoord, const double* xcoord, double period, double radius,
                                  int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
                                  const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,

@@ -20,7 +20,15 @@
 // Sums are K10's fixed-point sums on K10's window constant (k_clen_window over the whole plane's coordinates): a window's bits
 // do not depend on the threads per block, the stride, the slabs per call or who else shares the launch.  Capacity: a wave's
 // copy takes at most 31 strips = 31744 cells (<= 32767) before thread 0 carries the copies into its registers; it converts once.
+//
+// Periodic X (WRAP, xc_local_contour_lengths_periodic): windows are not clipped in X.  Window i owns the node columns
+// [i - wx/2, i - wx/2 + wx - 1] taken modulo nx, in that (unwrapped) order; the coordinate of a column c outside [0, nx) is
+// fx[c mod nx] + period or fx[c mod nx] - period (one float64 addition or subtraction; wx <= nx, so only one lap either way can
+// occur).  The mean keeps its order, per row left to right in window order; length, NaN rules and the window constant are those
+// of periodic K10 (xc_clen.hip).  The result is, bit for bit, the plain kernel's on the plane with h >= wx columns of the ring
+// copied to either side, at the matching centres.  Y is clipped as before; nwx = ceil(nx / sx).  Column indices wrap per lane.
 #include "xc_internal.h"
+#include <cmath>
 
 namespace xc {
 namespace {
@@ -36,13 +44,14 @@ constexpr int LCLEN_STRIPS = CLEN_COPY_CELLS / (64 * LCLEN_RB);   // strips of a
 
 static_assert(LCLEN_STRIPS >= 1 && LCLEN_STRIPS * 64 * LCLEN_RB <= CLEN_COPY_CELLS, "a copy takes at most CLEN_COPY_CELLS cells before a carry");
 
-// grid (windows per slab, nslab); blockDim.x 64 or LCLEN_TPB
-template <typename TQ, bool LATLON>
-__global__ __launch_bounds__(LCLEN_TPB)
-void k_lclen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx,
+// The body of k_lclen (WRAP = false: windows clipped in X) and k_ring_lclen (WRAP = true: periodic X); WRAP is a compile-time variant:
+// the plain kernel pays nothing for it.  grid (windows per slab, nslab); blockDim.x 64 or LCLEN_TPB
+template <typename TQ, bool LATLON, bool WRAP>
+__device__ __forceinline__
+void lclen_window(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx,
              int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t nwx, int64_t nwin, int64_t min_periods,
              const double* __restrict__ levels, const int* __restrict__ c0s, double radius,
-             double* __restrict__ out_len, double* __restrict__ out_level, unsigned long long* __restrict__ out_nseg)
+             double* __restrict__ out_len, double* __restrict__ out_level, unsigned long long* __restrict__ out_nseg, double period)
 {
     __shared__ double s_row[LCLEN_TPB];
     __shared__ unsigned long long s_acc[LCLEN_WAVES][CLEN_WORDS];
@@ -53,9 +62,9 @@ void k_lclen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __r
     const int64_t win = blockIdx.x, slab = blockIdx.y;
     const int64_t wj = win / nwx, wi = win - wj * nwx;
     const int64_t jr = wj * sy - wy / 2, ic = wi * sx - wx / 2;
-    // the window's nodes: rows [r0, r1], columns [c0, c1]
+    // the window's nodes: rows [r0, r1], columns [c0, c1] (WRAP: unwrapped columns, c0 in (-nx, nx) and c1 < 2 nx, not clipped)
     const int64_t r0 = jr > 0 ? jr : 0, r1 = jr + wy - 1 < ny - 1 ? jr + wy - 1 : ny - 1;
-    const int64_t c0 = ic > 0 ? ic : 0, c1 = ic + wx - 1 < nx - 1 ? ic + wx - 1 : nx - 1;
+    const int64_t c0 = WRAP ? ic : (ic > 0 ? ic : 0), c1 = WRAP ? ic + wx - 1 : (ic + wx - 1 < nx - 1 ? ic + wx - 1 : nx - 1);
     const int64_t wh = r1 - r0 + 1, ww = c1 - c0 + 1;
     const TQ* qs = q + (size_t)slab * ny * nx;
     const size_t o = (size_t)slab * nwin + win;
@@ -72,12 +81,19 @@ void k_lclen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __r
         for (int64_t b = 0; b < wh; b += ntd) {
             __syncthreads();                                                              // s_row is free (and s_valid cleared)
             if (b + tid < wh) {
-                const TQ* p = qs + (size_t)(r0 + b + tid) * nx + c0;
+                const TQ* p = qs + (size_t)(r0 + b + tid) * nx + (WRAP ? 0 : c0);
                 double s = 0.0;
                 unsigned long long n = 0ull;
 #pragma unroll 8
                 for (int64_t k = 0; k < ww; ++k) {
-                    const double v = (double)p[k];
+                    double v;
+                    if constexpr (WRAP) {                                                 // the node column on the ring
+                        int64_t kc = c0 + k;
+                        kc += kc < 0 ? nx : 0; kc -= kc >= nx ? nx : 0;
+                        v = (double)p[kc];
+                    } else {
+                        v = (double)p[k];
+                    }
                     const bool ok = v == v;
                     s = __dadd_rn(s, ok ? v : 0.0);                                       // (s is never -0.0: adding 0.0 adds nothing)
                     n += ok;
@@ -114,9 +130,21 @@ void k_lclen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __r
                 const bool cell = i < cw;                                                 // lanes without a cell load the last one's corners
                 const int64_t ci = cell ? i : cw - 1;
                 const int64_t j0 = bj * LCLEN_RB, j1 = j0 + LCLEN_RB < ch ? j0 + LCLEN_RB : ch;
-                const double xL = fx[c0 + ci], xR = fx[c0 + ci + 1], cL = (double)ci;
-                const TQ* p = qs + (size_t)(r0 + j0) * nx + (c0 + ci);
-                double ul = (double)p[0], ur = (double)p[1];
+                const double cL = (double)ci;
+                double xL, xR;
+                int64_t nL = c0 + ci, dR = 1;                                             // the left corner's column, the right one's offset
+                if constexpr (WRAP) {
+                    const int64_t uL = c0 + ci, uR = uL + 1;                              // unwrapped, in (-nx, 2 nx)
+                    nL = uL < 0 ? uL + nx : (uL >= nx ? uL - nx : uL);
+                    const int64_t nR = uR < 0 ? uR + nx : (uR >= nx ? uR - nx : uR);
+                    xL = uL < 0 ? __dsub_rn(fx[nL], period) : (uL >= nx ? __dadd_rn(fx[nL], period) : fx[nL]);
+                    xR = uR < 0 ? __dsub_rn(fx[nR], period) : (uR >= nx ? __dadd_rn(fx[nR], period) : fx[nR]);
+                    dR = nR - nL;                                                         // 1, or 1 - nx across the seam
+                } else {
+                    xL = fx[nL]; xR = fx[nL + 1];
+                }
+                const TQ* p = qs + (size_t)(r0 + j0) * nx + nL;
+                double ul = (double)p[0], ur = (double)p[dR];
                 constexpr int B = 4;
                 for (int64_t jb = j0; jb < j1; jb += B) {
                     TQ v[B][2];
@@ -124,7 +152,7 @@ void k_lclen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __r
                     for (int b = 0; b < B; ++b) {                                         // all loads of the batch in flight together
                         const int64_t jj = (jb + b < j1) ? jb + b : j1 - 1;
                         const TQ* pr = p + (size_t)(jj + 1 - j0) * nx;
-                        v[b][0] = pr[0]; v[b][1] = pr[1];
+                        v[b][0] = pr[0]; v[b][1] = pr[dR];
                     }
 #pragma unroll
                     for (int b = 0; b < B; ++b) {
@@ -177,10 +205,33 @@ void k_lclen(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __r
     }
 }
 
+#define XC_LCLEN_PARAMS const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ fy, const double* __restrict__ fx,       \
+                        int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t nwx, int64_t nwin, int64_t min_periods,                       \
+                        const double* __restrict__ levels, const int* __restrict__ c0s, double radius, double* __restrict__ out_len,           \
+                        double* __restrict__ out_level, unsigned long long* __restrict__ out_nseg
+#define XC_LCLEN_ARGS q, ny, nx, fy, fx, wy, wx, sy, sx, nwx, nwin, min_periods, levels, c0s, radius, out_len, out_level, out_nseg
+
+template <typename TQ, bool LATLON>
+__global__ __launch_bounds__(LCLEN_TPB)
+void k_lclen(XC_LCLEN_PARAMS)
+{
+    lclen_window<TQ, LATLON, false>(XC_LCLEN_ARGS, 0.0);
+}
+
+// periodic X: windows run on round the ring
+template <typename TQ, bool LATLON>
+__global__ __launch_bounds__(LCLEN_TPB)
+void k_ring_lclen(XC_LCLEN_PARAMS, double period)
+{
+    lclen_window<TQ, LATLON, true>(XC_LCLEN_ARGS, period);
+}
+#undef XC_LCLEN_ARGS
+#undef XC_LCLEN_PARAMS
+
 }  // namespace
 
 int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
-                                 const double* ycoord, const double* xcoord, double radius,
+                                 const double* ycoord, const double* xcoord, double period, double radius,
                                  int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
                                  const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
 {
@@ -192,6 +243,11 @@ int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_
     if (sy < 1 || sx < 1) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: strides must be >= 1");
     if (min_periods < 0) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: min_periods must be >= 0");
     if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: nslab too large");
+    // period != 0: periodic X (the entry points have checked the period)
+    const bool wrap = period != 0.0;
+    if (wrap && (!std::isfinite(period) || nx < 2))
+        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: period must be finite and non-zero, and nx >= 2");
+    if (wrap && wx > nx) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: the window must not be wider than the ring (wx <= nx)");
     const int64_t nwy = (ny + sy - 1) / sy, nwx = (nx + sx - 1) / sx;
     if (nwy > 0x7fffffff / nwx) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: too many windows per slab");
     const int64_t nwin = nwy * nwx;
@@ -202,19 +258,23 @@ int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_
     int* c0 = (int*)ctx->scratch;
     const int latlon = radius > 0.0;
     {
-        const int rc = launch_clen_window(ctx, ycoord, ny, xcoord, nx, latlon, 1, c0);
+        const int rc = launch_clen_window(ctx, ycoord, ny, xcoord, nx, period, latlon, 1, c0);
         if (rc != XC_OK) return rc;
     }
     // the cells of an unclipped window decide the threads per block (the sums do not depend on it)
-    const int64_t hy = (wy < ny ? wy : ny) - 1, hx = (wx < nx ? wx : nx) - 1;
+    const int64_t hy = (wy < ny ? wy : ny) - 1, hx = (wx < nx ? wx : nx) - 1;                        // (periodic: wx <= nx, wx - 1 cells)
     const int tpb = hy * hx <= LCLEN_SMALL ? 64 : LCLEN_TPB;
     const dim3 grid((unsigned)nwin, (unsigned)nslab);
-#define XC_LCLEN(TQ_, LL_) hipLaunchKernelGGL((k_lclen<TQ_, LL_>), grid, dim3(tpb), 0, ctx->stream, (const TQ_*)q, ny, nx, ycoord, xcoord, \
-                                              wy, wx, sy, sx, nwx, nwin, min_periods, levels, c0, latlon ? radius : 0.0, out_len, out_level, \
-                                              (unsigned long long*)out_nseg)
+#define XC_LCLEN_ARGS(TQ_) (const TQ_*)q, ny, nx, ycoord, xcoord, wy, wx, sy, sx, nwx, nwin, min_periods, levels, c0, latlon ? radius : 0.0, \
+                      out_len, out_level, (unsigned long long*)out_nseg
+#define XC_LCLEN(TQ_, LL_) do {                                                                                              \
+        if (wrap) hipLaunchKernelGGL((k_ring_lclen<TQ_, LL_>), grid, dim3(tpb), 0, ctx->stream, XC_LCLEN_ARGS(TQ_), period);     \
+        else hipLaunchKernelGGL((k_lclen<TQ_, LL_>), grid, dim3(tpb), 0, ctx->stream, XC_LCLEN_ARGS(TQ_));                       \
+    } while (0)
     if (q_dtype == XC_F64) { if (latlon) XC_LCLEN(double, true); else XC_LCLEN(double, false); }
     else { if (latlon) XC_LCLEN(float, true); else XC_LCLEN(float, false); }
 #undef XC_LCLEN
+#undef XC_LCLEN_ARGS
     XC_HIP(ctx, hipGetLastError());
     return XC_OK;
 }
