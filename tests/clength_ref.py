@@ -189,3 +189,11 @@ def hashed_coords(n, salt=0, start=0.0, scale=1.0, descending=False):
     d = scale * (1.0 + 0.25 * (h.astype(np.float64) / 2.0 ** 31 - 1.0))
     c = start + np.concatenate([[0.0], np.cumsum(d)])
     return c[::-1].copy() if descending else c
+
+
+def few_bits(n, salt, scale, bits_=20):
+    """spacings scale (1 + 0.25 f(i)) cut to `bits_` significant bits; coordinates their exact running sum"""
+    d = np.diff(hashed_coords(n, salt))
+    e = np.floor(np.log2(d))
+    d = np.floor(d * 2.0 ** (bits_ - 1 - e)) / 2.0 ** (bits_ - 1 - e) * scale
+    return np.concatenate([[0.0], np.cumsum(d)])

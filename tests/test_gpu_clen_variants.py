@@ -299,12 +299,7 @@ def test_checkerboard_saturates_every_copy(ctx):
 
 
 # ------------------------------------------------------------------------------------------------------------------- (d) fixed point
-def few_bits(n, salt, scale, bits_=20):
-    """spacings scale (1 + 0.25 f(i)) cut to `bits_` significant bits; coordinates their exact running sum"""
-    d = np.diff(CR.hashed_coords(n, salt))
-    e = np.floor(np.log2(d))
-    d = np.floor(d * 2.0 ** (bits_ - 1 - e)) / 2.0 ** (bits_ - 1 - e) * scale
-    return np.concatenate([[0.0], np.cumsum(d)])
+few_bits = CR.few_bits              # (shared with the K11 geometry tests)
 
 
 FP_ROWS = ['x-only', 'y-only', 'wide-column', 'wide-row', 'tall-cells']

@@ -132,6 +132,7 @@ def test_whole_plane_window_is_k10(ctx, latlon):
         assert np.array_equal(cnts[:, 0, 0], n10[:, 0])
         r = np.abs(lens[:, 0, 0] - k10[:, 0]) / k10[:, 0]
         assert r.max() <= 1e-12
+        assert bits_equal(lens[:, 0, 0], k10[:, 0])              # K10's fixed-point sums on K10's window constant: the same integers
         for s in range(2):
             rt, rn = CR.contour_lengths(q[s], [lv], y, x, latlon)
             check(lens[s, 0], cnts[s, 0], rt, rn, 'whole plane')
