@@ -417,6 +417,39 @@ int xc_local_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, i
                                       int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
                                       const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
 
+/* ------------------------------------------------------------------ K12 marching-squares contour segments
+ * No call site inside the reference's package: its scripts trace the contours themselves with skimage's find_contours
+ * (tests/test_clength.py:615-630, tests/test_breaking.py, tests/test_localLength.py).  The segments K10 sums, written
+ * out, for ALL contours of all slabs.  The rule is K10's (case table, frac, saddles as fully_connected='low', a cell
+ * with a NaN corner emits nothing; no wrap across the X seam) with two differences: segments are DIRECTED, start ->
+ * end, in the order of skimage's _get_contour_segments
+ *     1 T->L   2 R->T   3 R->L   4 L->B   5 T->B   6 R->T, L->B   7 R->B
+ *     8 B->R   9 T->L, B->R   10 B->T   11 B->L   12 L->R   13 T->R   14 L->T        (T top, B bottom, L left, R right)
+ * and a segment whose two end points coincide is KEPT (the join needs it).
+ *   record (structure of arrays):  e_from[i], e_to[i]  the ids of the grid edges the start / end point lie on:
+ *       the horizontal edge between nodes (r, c) and (r, c+1) is 2 (r nx + c), the vertical edge between (r, c) and
+ *       (r+1, c) is 2 (r nx + c) + 1; cell (r0, c0) has T = H(r0, c0), B = H(r0+1, c0), L = V(r0, c0), R = V(r0, c0+1).
+ *       Within one (slab, contour) every edge is the start of at most one segment and the end of at most one.
+ *     pts[4 i .. 4 i + 3] = (r1, c1, r2, c2) in index space (row, column), float64, one correctly rounded
+ *       subtraction, division and addition each: reproducible bit for bit.
+ *   layout: segments packed by (slab, contour) in the caller's contour order; the range of (s, k) is
+ *     [off[s ncont + k], off[s ncont + k + 1]) with off the exclusive scan of out_count.  The order INSIDE a range is
+ *     unspecified.
+ *   out_count[nslab][ncont] is always written (segments per contour, coincident-end ones included).
+ *   capacity >= sum(out_count): the records are written, XC_OK.  Otherwise nothing is written to the record arrays
+ *     and 1 is returned (capacity 0 with NULL record arrays = count only).
+ *   q f32 / f64; contours double[ncont] or double[nslab][ncont] (contours_per_slab), ASCENDING, no NaN, as for K10
+ *     (the host entry point checks).  Any ncont is accepted: contours beyond XC_CSEG_GROUP_LEVELS are processed in
+ *     groups of that many.  ny < 2 or nx < 2: no cells, all counts 0, XC_OK.
+ * Both forms wait for the stream once (the total decides on the host whether the records fit).               */
+#define XC_CSEG_GROUP_LEVELS 2048
+int xc_contour_segments_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                            const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                            uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts);
+int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                        const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                        uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)
@@ -621,6 +654,19 @@ int xc_host_gradient_wrt_area(const void* var, int var_dtype, const void* var_co
  * XC_EBADARG 'need at least two contour levels' / 'not every time or level is increasing/decreasing'. */
 int xc_host_edges_from_levels(const void* levels, int levels_dtype, int64_t nslab, int64_t N, int right_edge,
                               double* out_edges, int* out_increasing);
+
+/* The directed segments of K12 joined into polylines (host only; compiles without HIP).  nrange ranges (one per (slab,
+ * contour)), range r = segments [off[r], off[r+1]) of e_from / e_to, off[0] = 0.  Per range: next(i) is the segment whose
+ * e_from == e_to[i], prev(i) the one whose e_to == e_from[i] (sort + binary search on the edge ids); a segment without prev heads
+ * an OPEN polyline; every remaining segment lies on a RING, which starts at its segment of smallest e_from; the polylines of a
+ * range are ordered by the smallest e_from they contain.
+ *   order[total]               global segment indices, polyline by polyline, in walk order (total = off[nrange])
+ *   poly_off[total + 1]        polyline p = order[poly_off[p] .. poly_off[p+1])   (capacity total + 1; npoly + 1 entries written)
+ *   poly_closed[total]         1 for a ring, 0 for an open polyline                (capacity total; npoly entries written)
+ *   range_poly_off[nrange + 1] the polylines of range r are [range_poly_off[r], range_poly_off[r+1]); npoly = the last entry
+ * XC_EBADARG: a duplicate e_from or a duplicate e_to within a range (such input is never walked), descending off, NULL arrays. */
+int xc_join_segments(int64_t nrange, const int64_t* off, const int64_t* e_from, const int64_t* e_to,
+                     int64_t* order, int64_t* poly_off, uint8_t* poly_closed, int64_t* range_poly_off);
 
 /* ------------------------------------------------------------------ synthetic slabs (bench / tests)
  * PV-like tracer q = sin(phi) + 0.25 sum_k a_k cos(k lambda + theta_k) cos^2(phi) + 0.02 eps

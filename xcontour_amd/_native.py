@@ -24,6 +24,7 @@ XC_SINGLE_AUTO, XC_SINGLE_NEVER, XC_SINGLE_FORCE = 0, 1, 2
 XC_MAX_INTEGRANDS = 2
 MAX_SLABS_PER_LAUNCH = 65535
 XC_PAD_EDGE, XC_PAD_WRAP, XC_PAD_NAN, XC_PAD_REFLECT, XC_PAD_SYMMETRIC = 0, 1, 2, 3, 4
+XC_CSEG_GROUP_LEVELS = 2048      # contours one level group of K12 holds (include/xcontour_hip.h)
 PAD_MODES = {'edge': XC_PAD_EDGE, 'wrap': XC_PAD_WRAP, 'constant': XC_PAD_NAN, 'reflect': XC_PAD_REFLECT,
              'symmetric': XC_PAD_SYMMETRIC}
 
@@ -150,6 +151,9 @@ PROTOTYPES = {
     'xc_contour_lengths_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
     'xc_local_contour_lengths_periodic_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'xc_local_contour_lengths_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'xc_contour_segments_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
+    'xc_contour_segments': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
+    'xc_join_segments': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -325,6 +329,26 @@ def _check_ascending(contours, who):
     """the host entry points validate the contours; the device ones trust their caller"""
     if np.isnan(contours).any() or (np.diff(contours, axis=-1) < 0).any():
         raise XContourHipError(XC_EEDGES, '%s: contours must be ascending without NaN' % who)
+
+
+def join_segments(off, e_from, e_to):
+    """xc_join_segments (host only, no device): the directed segments of `Context.contour_segments` joined into polylines.  off
+    (nrange + 1,) int64, the exclusive scan of the counts; e_from / e_to (total,) int64.  Returns (order (total,) int64: segment
+    indices polyline by polyline in walk order; poly_off (npoly + 1,) int64 into `order`; closed (npoly,) bool; range_poly_off
+    (nrange + 1,) int64: the polylines of range r are [range_poly_off[r], range_poly_off[r+1])).  A duplicate e_from or e_to
+    within a range raises."""
+    off, e_from, e_to = _contig(off, np.int64), _contig(e_from, np.int64), _contig(e_to, np.int64)
+    if off.ndim != 1 or off.size < 1 or e_from.ndim != 1 or e_from.shape != e_to.shape or int(off[-1]) != e_from.size:
+        raise XContourHipError(XC_EBADARG, 'xc_join_segments: off must be (nrange + 1,) and end at the number of segments')
+    total = e_from.size
+    order, poly_off = np.empty(total, dtype=np.int64), np.empty(total + 1, dtype=np.int64)
+    closed, rpo = np.empty(total, dtype=np.uint8), np.empty(off.size, dtype=np.int64)
+    rc = load().xc_join_segments(off.size - 1, _ptr(off), _ptr(e_from), _ptr(e_to), _ptr(order), _ptr(poly_off), _ptr(closed), _ptr(rpo))
+    if rc != XC_OK:
+        raise XContourHipError(rc, 'xc_join_segments: off must start at 0 and ascend, and no edge id may repeat among the e_from or '
+                               'among the e_to of a range')
+    npoly = int(rpo[-1])
+    return order, poly_off[:npoly + 1].copy(), closed[:npoly].astype(bool), rpo
 
 
 class DeviceBuffer(object):
@@ -924,6 +948,48 @@ class Context(object):
             self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord), *mid, _ptr(cb), N,
                                1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
             return lens, cnts
+        return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+
+    def contour_segments(self, q, contours):
+        """Marching-squares contour segments (K12, xc_contour_segments_dev).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours
+        (N,) or (nslab, N) ASCENDING f64 without NaN.  Returns (count uint64 (nslab, N); e_from, e_to int64 (total,): the ids of the
+        grid edges the start / end of each directed segment lie on -- horizontal (r, c)-(r, c+1): 2 (r nx + c), vertical
+        (r, c)-(r+1, c): 2 (r nx + c) + 1 --; pts float64 (total, 4): (r1, c1, r2, c2) in index space).  Segments are packed by
+        (slab, contour): range (s, k) starts at the exclusive scan of `count`; segments whose end points coincide are kept.
+        Inside a range the segments are sorted by e_from (unique there), so the result is the same on every call.  Every batch
+        is staged once: a count-only call sizes the buffers of the second."""
+        q = _stack_in(q)
+        if len(q.shape) != 3:
+            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
+        nslab, ny, nx = q.shape
+        contours = _contig(contours, np.float64)
+        per_slab = contours.ndim == 2
+        if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
+            raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
+        N = contours.shape[-1]
+        _check_ascending(contours, 'xc_contour_segments')
+        f = self.lib.xc_contour_segments_dev
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
+            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+            with self._temporaries(([] if qp else [qb]) + [cb], [n * N * 8]) as bufs:
+                dc, dn = bufs[-2:]
+                head = (self.handle, qp or bufs[0].ptr, dtype_code(q.dtype), n, ny, nx, dc.ptr, N, 1 if per_slab else 0)
+                rc = f(*head, 0, dn.ptr, None, None, None)
+                if rc not in (XC_OK, 1):
+                    self._check(rc)
+                cnt = dn.download((n, N), np.uint64)
+                total = int(cnt.sum())
+                if total == 0:
+                    return cnt, np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty((0, 4), dtype=np.float64)
+                with self._temporaries([], [total * 8, total * 8, total * 32]) as (df, dt, dp):
+                    self._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr))
+                    ef, et = df.download((total,), np.int64), dt.download((total,), np.int64)
+                    pts = dp.download((total, 4), np.float64)
+            o = np.lexsort((ef, np.repeat(np.arange(n * N), cnt.ravel().astype(np.int64))))
+            return cnt, ef[o], et[o], pts[o]
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):

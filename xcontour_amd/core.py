@@ -824,6 +824,66 @@ class Contour2D(object):
             return out, lb.wrap(lvls.reshape(tuple(lshape) + nw), dims, c, 'level', data)
         return out
 
+    # ------------------------------------------------------------------ contour polylines
+    def find_contours(self, contours, tracer=None, index=False, return_closed=False):
+        """
+        The contours themselves: every level traced into polylines on the GPU (K12, xc_contour_segments, and the host join
+        xc_join_segments).  The reference's scripts do this with skimage's find_contours through a `find_contour` helper that
+        is not part of the reference snapshot this package was built against, so what follows is build-defined.
+
+        `contours` as for cal_contour_lengths: an int or list goes through cal_contours; a labelled array over (..., contour)
+        may differ per slab; levels in any order, a NaN level has no polylines.  The segments are those cal_contour_lengths
+        sums (same case table, saddles, NaN cells; no wrap across the X seam), directed, and joined by matching the grid edges
+        their end points lie on -- no float comparison.  A polyline's vertices are the start of its first segment and the end
+        of every segment; consecutive equal vertices are merged, polylines left with fewer than two vertices are dropped, and a
+        closed polyline (a ring) repeats its first vertex at the end.  An open polyline starts and ends on the plane's edge or
+        beside a NaN cell.  The polylines of a level are ordered by the smallest grid-edge id they touch.
+
+        Each polyline is an (n, 2) float64 array [row, column] = [equivalent dim, other plane dim]: with index=True in index
+        space, else mapped onto the plane's coordinates AS GIVEN with np.interp(., arange(n), coord) in float64 (no float32
+        cast, unlike cal_contour_lengths).  Returns out[k] -- a list of arrays per level -- when the tracer has no leading dims,
+        else out[slab][k] with the leading dims flattened in the tracer's order; with return_closed=True also the same nesting
+        of bools (True: a ring).
+        """
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        data = self.tracer if tracer is None else tracer
+        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
+        cds = []
+        if not index:
+            for d in (self.dimEqV, self._xdim):
+                if d not in dcoords:
+                    raise Exception('find_contours needs coordinate values for the plane dim %s (or index=True)' % d)
+                cds.append(np.asarray(dcoords[d], dtype=np.float64))
+        q, lead, lshape, coords = self._plane(data)
+        q = self._float(q)
+        nslab = q.shape[0]
+        bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
+        N = bs.shape[1]
+        cnt, ef, et, pts = self.ctx.contour_segments(q, bs)
+        off = np.concatenate([[0], np.cumsum(cnt.ravel().astype(np.int64))])
+        walk, poff, closed, rpo = nat.join_segments(off, ef, et)
+        if not index and pts.size:
+            pts = np.stack([np.interp(pts[:, 0], np.arange(cds[0].size), cds[0]), np.interp(pts[:, 1], np.arange(cds[1].size), cds[1]),
+                            np.interp(pts[:, 2], np.arange(cds[0].size), cds[0]), np.interp(pts[:, 3], np.arange(cds[1].size), cds[1])], axis=1)
+        out = [[None] * N for _ in range(nslab)]
+        flags = [[None] * N for _ in range(nslab)]
+        for s in range(nslab):
+            for j in range(N):                                   # j: the sorted level; order[s, j]: where the caller put it
+                polys, cl = [], []
+                for p in range(int(rpo[s * N + j]), int(rpo[s * N + j + 1])):
+                    segs = walk[poff[p]:poff[p + 1]]
+                    v = np.concatenate([pts[segs[:1], :2], pts[segs, 2:]])
+                    keep = np.concatenate([[True], (v[1:] != v[:-1]).any(axis=1)])
+                    if int(keep.sum()) < 2:
+                        continue
+                    polys.append(np.ascontiguousarray(v[keep]))
+                    cl.append(bool(closed[p]))
+                out[s][int(order[s, j])], flags[s][int(order[s, j])] = polys, cl
+        if not lead:
+            out, flags = out[0], flags[0]
+        return (out, flags) if return_closed else out
+
     # ------------------------------------------------------------------ local wave activity
     def cal_local_wave_activity(self, q, Q, mask_idx=None, part='all', metric=None, exact=None):
         """
@@ -1194,6 +1254,24 @@ def _edges_from_levels(b, right_edge):
         edges[:, -1] += 1e-8                                           # in the levels' own dtype, like `edge + 1e-8` on the array
         last_closed = False
     return edges.astype(np.float64), binc, last_closed
+
+
+def find_contour(data, dims, level, period=[None, None]):
+    """
+    The polylines of ONE level of a 2-D labelled field, in the call shape of the reference's scripts
+    (tests/test_clength.py:615: find_contour(tr1[0], ['YC', 'XC'], 1.15076609, period=[None, None])): `dims` = [ydim, xdim].
+    Returns a list of (n, 2) float64 arrays [y, x] in the field's coordinates -- Contour2D.find_contours([level])[0], which
+    states the rule.  Periodic tracing is not supported yet: an entry of `period` that is not None raises.
+    """
+    if period is not None and any(p is not None for p in period):
+        raise NotImplementedError('find_contour: period=%r is not supported yet (only [None, None]: no wrap across the plane\'s '
+                                  'edges)' % (period,))
+    ydim, xdim = dims
+    ddims = lb.unwrap(data, lazy=True)[1]
+    if len(ddims) != 2 or set(ddims) != {ydim, xdim}:
+        raise Exception('find_contour expects a 2-D field on the dims %s' % [ydim, xdim])
+    cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
+    return cm.find_contours(np.array([float(level)]))[0]
 
 
 def _level_order(vals, order):

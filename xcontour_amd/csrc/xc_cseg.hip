@@ -1,0 +1,272 @@
+// K12 -- marching-squares contour SEGMENTS (gfx950): what K10 (xc_clen.hip) sums, written out.
+//
+// No reference call site inside the snapshot's package (its find_contour helper is not in it); the reference's scripts trace contours
+// with skimage's find_contours and go on from the polylines (tests/test_clength.py:615-630, tests/test_breaking.py,
+// tests/test_localLength.py).  Build-defined.  The rule is K10's, stated in the header of xc_clen.hip (case table, frac, saddles as
+// fully_connected='low', a NaN corner emits nothing), with the two differences of xc_cseg_cell.h: segments are DIRECTED (start -> end
+// as in skimage's _get_contour_segments) and a segment whose two end points coincide is kept.  X is not periodic here.
+//
+// Record, one per segment, as a structure of arrays: e_from / e_to (int64) the ids of the grid edges its start / end point lie on --
+// horizontal edge (r, c)-(r, c+1): 2 (r nx + c); vertical edge (r, c)-(r+1, c): 2 (r nx + c) + 1 -- and pts[4] (float64) = (r1, c1, r2,
+// c2) in index space, each coordinate one correctly rounded sub / div / add.  Within one (slab, level) every grid edge is the start of
+// at most one segment and the end of at most one: e_from identifies the segment, and joining (xc_join.cpp) is integer matching.
+//
+// Layout: segments packed by (slab, level): range (s, k) = [off[s N + k], off[s N + k + 1]), off the exclusive scan of the counts.  The
+// order INSIDE a range is unspecified (it depends on the order in which a block's lanes take their slots).
+//
+// Two passes over K10's launch geometry (tiles of 32 x 252 cells, lanes along X, the right neighbour by DPP, count_below(_uniform),
+// level groups of XC_CSEG_GROUP_LEVELS over gridDim.z; grid (bps, nslab, groups), a block walks the tiles blockIdx.x, + bps, ...):
+//   count  every block counts its segments per level in LDS (ds_add_u32) and writes them: part[slab][block][level];
+//   k_cseg_sum   per (slab, level): the blocks' counts -> each block's offset inside the range, and the range's count;
+//   k_cseg_scan  the exclusive scan of the range counts -> off[nslab N + 1];
+//   emit   the same walk; every block keeps one LDS cursor per level (ds_add_rtn_u32) and writes the record at
+//          off[range] + the block's offset + slot with plain stores.
+// No global atomics, no float atomics; counts and records are the same on every run, up to the order inside a range.
+// Capacity: a block's count of one level is a 32-bit word: the launcher gives a block at most 2^17 tiles (< 2^32 segments).
+#include "xc_internal.h"
+#include <cmath>
+
+namespace xc {
+namespace {
+
+#include "xc_binning.h"
+#include "xc_levels.h"
+#include "xc_clen_cell.h"
+#include "xc_cseg_cell.h"
+
+constexpr int CSEG_RB = 32;                 // cell rows per tile            (K10's tile)
+constexpr int CSEG_TPB = 256;               // threads per block
+constexpr int CSEG_W = 252;                 // cell columns per tile: 4 waves x 63 cells
+constexpr int64_t CSEG_MAX_TILES = 1 << 17; // tiles per block at most: 2^17 x 32 x 252 cells x 2 segments < 2^32
+
+// LDS of a block (dynamic, 16-byte aligned carve): s_dev[4] | s_cx[G + 2] (-inf, the group's levels, +inf) | s_base[G] | s_cur[G]
+constexpr size_t cseg_lds(int G) { return (size_t)(4 + G + 2) * 8 + (size_t)G * 8 + (size_t)G * 4 + 16; }
+static_assert(cseg_lds(XC_CSEG_GROUP_LEVELS) <= 48 * 1024, "a level group must fit 48 KB of LDS");
+
+// EMIT = false: part[slab][block][level] = the block's segment count.  EMIT = true: the records, at off[slab N + level] +
+// part_off[slab][block][level] + slot; nothing is written at or past `capacity`.
+template <typename TQ, bool EMIT>
+__global__ __launch_bounds__(CSEG_TPB)
+void k_cseg(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ contours, int N, int contours_per_slab, int G,
+            int64_t ntj, int64_t nti, int bps, unsigned* __restrict__ part, const unsigned long long* __restrict__ part_off,
+            const long long* __restrict__ off, long long capacity, long long* __restrict__ e_from, long long* __restrict__ e_to,
+            double* __restrict__ pts)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    const int tid = threadIdx.x;
+    const int64_t slab = blockIdx.y;
+    const int g0 = blockIdx.z * G, ng = (N - g0 < G) ? N - g0 : G;
+    double* s_dev = sm;                                                                   // [4]
+    double* s_cx = sm + 4;                                                                // [ng + 2]
+    unsigned long long* s_base = (unsigned long long*)(s_cx + ng + 2);                    // [ng]
+    unsigned* s_cur = (unsigned*)(s_base + ng);                                           // [ng]
+    const double* cs = contours + (contours_per_slab ? (size_t)slab * N : 0) + g0;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    const size_t pb = ((size_t)slab * bps + blockIdx.x) * N + g0;                         // this block's row of part / part_off
+    for (int k = tid; k < ng; k += CSEG_TPB) {
+        s_cx[k + 1] = cs[k];
+        s_cur[k] = 0u;
+        if constexpr (EMIT) s_base[k] = (unsigned long long)off[(size_t)slab * N + g0 + k] + part_off[pb + k];
+    }
+    if (tid == 0) { s_cx[0] = -inf; s_cx[ng + 1] = inf; }
+    __syncthreads();
+    const double c_first = s_cx[1];
+    double inv_step = (ng > 1) ? (double)(ng - 1) / (s_cx[ng] - c_first) : 0.0;
+    if (!(inv_step > 0.0 && inv_step < inf)) inv_step = 0.0;
+    double zlo = 0.5;
+    {   // equally spaced levels?  (block-uniform answer, as in K10) -- and how far the levels sit from their ideal positions
+        int ok = inv_step > 0.0;
+        double dev = 0.0;
+        for (int k = tid; k < ng && ok; k += CSEG_TPB) {
+            const double d = fabs((s_cx[k + 1] - c_first) * inv_step - (double)k);
+            ok = d < 0.01; dev = fmax(dev, d);
+        }
+        if (!__syncthreads_and(ok)) inv_step = 0.0;
+        for (int o = 32; o > 0; o >>= 1) dev = fmax(dev, __shfl_xor(dev, o));
+        if ((tid & 63) == 0) s_dev[tid >> 6] = dev;
+        __syncthreads();
+        dev = fmax(fmax(s_dev[0], s_dev[1]), fmax(s_dev[2], s_dev[3]));
+        zlo = 2.0 * dev + 1e-9;
+    }
+    const TQ* qs = q + (size_t)slab * ny * nx;
+    const int64_t ncx = nx - 1, ncy = ny - 1, nx2 = 2 * nx;
+    const int lane = tid & 63, wave = tid >> 6;
+
+    for (int64_t tile = blockIdx.x; tile < ntj * nti; tile += bps) {
+        const int64_t tj = tile / nti, ti = tile - tj * nti;
+        const int64_t i = ti * CSEG_W + wave * 63 + lane;                                // this lane's cell column
+        const int64_t j0 = tj * CSEG_RB, j1 = (j0 + CSEG_RB < ncy) ? j0 + CSEG_RB : ncy;
+        const bool cell = lane < 63 && i < ncx;                                          // lanes without a cell still load and shift
+        const int64_t c = i < nx - 1 ? i : nx - 1;                                       // corner column loaded by this lane
+        const double cL = (double)c;
+        double ul = (double)qs[(size_t)j0 * nx + c];
+        double ur = lane_shift_keep<DPP_WAVE_SHL1>(ul, ul);
+        constexpr int B = 4;
+        for (int64_t jb = j0; jb < j1; jb += B) {
+            TQ v[B];
+#pragma unroll
+            for (int b = 0; b < B; ++b) {                                                // all loads of the batch in flight together
+                const int64_t jj = (jb + b < j1) ? jb + b : j1 - 1;
+                v[b] = qs[(size_t)(jj + 1) * nx + c];
+            }
+#pragma unroll
+            for (int b = 0; b < B; ++b) {
+                const int64_t r = jb + b;
+                if (r >= j1) break;                                                      // wave-uniform
+                const double ll = (double)v[b], lr = lane_shift_keep<DPP_WAVE_SHL1>(ll, ll);
+                const bool hasnan = (ul != ul) | (ur != ur) | (ll != ll) | (lr != lr);
+                if (cell && !hasnan) {
+                    const double mn = fmin(fmin(ul, ur), fmin(ll, lr)), mx = fmax(fmax(ul, ur), fmax(ll, lr));
+                    int klo, khi;
+                    if (inv_step > 0.0) {
+                        klo = count_below_uniform(s_cx, ng, mn, c_first, inv_step, zlo);
+                        khi = count_below_uniform(s_cx, ng, mx, c_first, inv_step, zlo);
+                    } else {
+                        klo = count_below(s_cx, ng, mn);
+                        khi = count_below(s_cx, ng, mx);
+                    }
+                    const int64_t hT = 2 * (r * nx + c);
+                    for (int k = klo; k < khi; ++k) {
+                        const double lv = s_cx[k + 1];
+                        if constexpr (EMIT) {
+                            const unsigned long long base = s_base[k];
+                            cseg_cell(ul, ur, ll, lr, lv, (double)r, cL, hT, nx2,
+                                      [&](int64_t ef, int64_t et, double r1, double c1, double r2, double c2) {
+                                          const unsigned slot = __hip_atomic_fetch_add(s_cur + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                          const long long at = (long long)(base + slot);
+                                          if (at < capacity) {
+                                              e_from[at] = ef; e_to[at] = et;
+                                              double* p = pts + 4 * (size_t)at;
+                                              p[0] = r1; p[1] = c1; p[2] = r2; p[3] = c2;
+                                          }
+                                      });
+                        } else {
+                            lds_add(s_cur + k, (unsigned)cseg_count(cseg_case(ul, ur, ll, lr, lv)));
+                        }
+                    }
+                }
+                ul = ll; ur = lr;
+            }
+        }
+    }
+    if constexpr (!EMIT) {
+        __syncthreads();
+        for (int k = tid; k < ng; k += CSEG_TPB) part[pb + k] = s_cur[k];
+    }
+}
+
+// per (slab, level): part[slab][b][level], b = 0 .. bps-1, -> part_off[slab][b][level] = the sum over the blocks before b, and
+// count[slab][level] = the sum over all.  bps = 0 (no cells): counts of 0.
+__global__ __launch_bounds__(256)
+void k_cseg_sum(const unsigned* __restrict__ part, int64_t nslab, int bps, int N, unsigned long long* __restrict__ part_off,
+                unsigned long long* __restrict__ count)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nslab * N) return;
+    const int64_t s = i / N, k = i - s * N;
+    unsigned long long t = 0ull;
+    for (int b = 0; b < bps; ++b) {
+        const size_t at = ((size_t)s * bps + b) * N + k;
+        part_off[at] = t;
+        t += part[at];
+    }
+    count[i] = t;
+}
+
+// off[0 .. M] = the exclusive scan of count[0 .. M-1] (off[M] the total).  One block: every thread sums a contiguous chunk, the
+// chunk sums are scanned in LDS, every thread writes its chunk.
+__global__ __launch_bounds__(1024)
+void k_cseg_scan(const unsigned long long* __restrict__ count, int64_t M, long long* __restrict__ off)
+{
+    __shared__ unsigned long long s_sum[1024];
+    const int tid = threadIdx.x;
+    const int64_t per = (M + 1023) / 1024, i0 = tid * per, i1 = (i0 + per < M) ? i0 + per : M;
+    unsigned long long t = 0ull;
+    for (int64_t i = i0; i < i1; ++i) t += count[i];
+    s_sum[tid] = t;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                                                  // inclusive scan of the chunk sums
+        const unsigned long long a = tid >= o ? s_sum[tid - o] : 0ull;
+        __syncthreads();
+        s_sum[tid] += a;
+        __syncthreads();
+    }
+    unsigned long long run = s_sum[tid] - t;
+    for (int64_t i = i0; i < i1; ++i) { off[i] = (long long)run; run += count[i]; }
+    if (tid == 1023) off[M] = (long long)s_sum[1023];
+}
+
+}  // namespace
+
+// One xc_contour_segments_dev call (device pointers).  Waits for the stream once, between the passes: the total decides on the host
+// whether the records fit.  -> XC_OK, 1 (capacity < total: only out_count was written) or an error.
+int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                            const double* contours, int N, int contours_per_slab, int64_t capacity,
+                            uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts, int64_t* out_total)
+{
+    if (out_total) *out_total = 0;
+    if (!q || !contours || !out_count || nslab < 1 || ny < 1 || nx < 1 || N < 1 || capacity < 0)
+        return fail(ctx, XC_EBADARG, "xc_contour_segments: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_segments: q_dtype must be XC_F32 or XC_F64");
+    if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_contour_segments: nslab too large");
+    if (capacity > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_segments: capacity > 0 needs the record arrays");
+    if (ny > (int64_t)1 << 30 || nx > (int64_t)1 << 30) return fail(ctx, XC_EBADARG, "xc_contour_segments: plane too large for the edge ids");
+    const int G = N < XC_CSEG_GROUP_LEVELS ? N : XC_CSEG_GROUP_LEVELS;
+    const int ngroup = (N + G - 1) / G;
+    if (ngroup > 65535) return fail(ctx, XC_EBADARG, "xc_contour_segments: too many contours");
+    const size_t lds = cseg_lds(G);
+    const int64_t ncx = nx - 1, ncy = ny - 1;
+    const int64_t ntj = ncy > 0 ? (ncy + CSEG_RB - 1) / CSEG_RB : 0, nti = ncx > 0 ? (ncx + CSEG_W - 1) / CSEG_W : 0;
+    const int64_t ntile = ntj * nti;
+    // blocks per slab: the launch's share of ~2048 blocks, at least 8, no more than tiles, and at most CSEG_MAX_TILES tiles each
+    int64_t bps = 0;
+    if (ntile > 0) {
+        bps = 2048 / nslab;
+        if (bps < 8) bps = 8;
+        const int64_t need = (ntile + CSEG_MAX_TILES - 1) / CSEG_MAX_TILES;
+        if (bps < need) bps = need;
+        if (bps > ntile) bps = ntile;
+        if (bps > 0x7fffffff) return fail(ctx, XC_EBADARG, "xc_contour_segments: plane too large");
+    }
+    const int64_t M = nslab * (int64_t)N;
+    const size_t a256 = 256;
+    auto up = [&](size_t b) { return (b + a256 - 1) & ~(a256 - 1); };
+    const size_t pc = up((size_t)nslab * bps * N * 4), po = up((size_t)nslab * bps * N * 8), pf = up((size_t)(M + 1) * 8);
+    {
+        const int rc = ensure_scratch(ctx, pc + po + pf + a256);
+        if (rc != XC_OK) return rc;
+    }
+    char* sc = (char*)ctx->scratch;
+    unsigned* part = (unsigned*)sc;
+    unsigned long long* part_off = (unsigned long long*)(sc + pc);
+    long long* off = (long long*)(sc + pc + po);
+    const dim3 grid((unsigned)bps, (unsigned)nslab, (unsigned)ngroup);
+#define XC_CSEG(TQ_, EMIT_) hipLaunchKernelGGL((k_cseg<TQ_, EMIT_>), grid, dim3(CSEG_TPB), lds, ctx->stream, (const TQ_*)q, ny, nx, contours, N,  \
+                                               contours_per_slab, G, ntj, nti, (int)bps, part, part_off, off, (long long)capacity,                \
+                                               (long long*)e_from, (long long*)e_to, pts)
+    if (bps > 0) {
+        if (q_dtype == XC_F64) XC_CSEG(double, false); else XC_CSEG(float, false);
+        XC_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_cseg_sum, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, part, nslab, (int)bps, N, part_off,
+                       (unsigned long long*)out_count);
+    XC_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_cseg_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long*)out_count, M, off);
+    XC_HIP(ctx, hipGetLastError());
+    // the one round trip: the total
+    if (!ctx->pinned_flag) XC_HIP(ctx, hipHostMalloc((void**)&ctx->pinned_flag, 64, hipHostMallocDefault));
+    long long* h_total = (long long*)ctx->pinned_flag;
+    XC_HIP(ctx, hipMemcpyAsync(h_total, off + M, 8, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t total = (int64_t)*h_total;
+    if (out_total) *out_total = total;
+    if (total > capacity) return 1;
+    if (total > 0) {
+        if (q_dtype == XC_F64) XC_CSEG(double, true); else XC_CSEG(float, true);
+        XC_HIP(ctx, hipGetLastError());
+    }
+#undef XC_CSEG
+    return XC_OK;
+}
+
+}  // namespace xc

@@ -1,5 +1,5 @@
 // C ABI, part 4: the host forms of the kernels outside the Keff chain -- row sums (K2), the squared gradient (K4), the local wave
-// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip; K11, xc_lclen.hip),
+// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip; K11, xc_lclen.hip), contour segments (K12, xc_cseg.hip),
 // synthetic slabs -- and the records of what they launched.
 #include "xc_capi.h"
 #include <cmath>
@@ -297,6 +297,60 @@ int xc_local_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, i
     XC_CTX(ctx);
     return local_contour_lengths_host(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, 1, period, radius, wy, wx, sy, sx, min_periods,
                                       levels, out_len, out_level, out_nseg);
+}
+
+// ------------------------------------------------------------------------------------ K12
+int xc_contour_segments_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                            const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                            uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
+{
+    XC_CTX(ctx);
+    return launch_contour_segments(ctx, q, q_dtype, nslab, ny, nx, contours, ncont, contours_per_slab, capacity, out_count, e_from, e_to, pts,
+                                   nullptr);
+}
+
+// The records are as many as the field has segments, known only after the count pass: they land in a device block of their own,
+// taken and released inside the call, and are copied out from there.
+int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                        const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                        uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
+{
+    XC_CTX(ctx);
+    if (!q || !contours || !out_count || nslab < 1 || ny < 1 || nx < 1 || ncont < 1 || capacity < 0)
+        return fail(ctx, XC_EBADARG, "xc_contour_segments: bad arguments");
+    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_segments: bad dtype");
+    if (capacity > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_segments: capacity > 0 needs the record arrays");
+    const int64_t nc = contours_per_slab ? nslab : 1;
+    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_segments: contours must be ascending without NaN");
+    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(cb) + al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); double* dc = (double*)st.take(cb); uint64_t* dn = st.out(out_count, ob);
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dc, contours, cb));
+    XC_TRY(flush_in(ctx));
+    int64_t total = 0;
+    int rc = launch_contour_segments(ctx, pq, q_dtype, nslab, ny, nx, dc, ncont, contours_per_slab, 0, dn, nullptr, nullptr, nullptr, &total);
+    if (rc < 0) return rc;
+    XC_TRY(st.deliver());
+    XC_TRY(xc_sync(ctx));
+    if (total > capacity) return 1;
+    if (total == 0) return XC_OK;
+    char* rec = nullptr;                                      // e_from | e_to | pts
+    const size_t n8 = (size_t)total * 8;
+    if (hipMalloc((void**)&rec, 6 * n8) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, XC_ENOMEM, "xc_contour_segments: no device memory for the records"); }
+    rc = launch_contour_segments(ctx, pq, q_dtype, nslab, ny, nx, dc, ncont, contours_per_slab, total, dn, (int64_t*)rec, (int64_t*)(rec + n8),
+                                 (double*)(rec + 2 * n8), nullptr);
+    hipError_t e = hipSuccess;
+    if (rc == XC_OK) {
+        e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(e_from, rec, n8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(e_to, rec + n8, n8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(pts, rec + 2 * n8, 4 * n8, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(rec);
+    if (e != hipSuccess) return hipfail(ctx, e, "xc_contour_segments: copying the records");
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------ K7

@@ -33,6 +33,23 @@ def _unwrap(x):
     return np.asarray(x), (lambda v: v)
 
 
+def polyline_length(poly, latlon=False, Rearth=Rearth):
+    """Length of one polyline of Contour2D.find_contours: `poly` an (n, 2) array of [y, x] vertices.  latlon=True: y / x are
+    latitude / longitude in degrees and every piece is a great-circle arc, the reference's haversine (utils.__geodist, in its
+    operation order) times Rearth; else the pieces are Cartesian distances (hypot)."""
+    p = np.asarray(poly, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise Exception('polyline_length expects an (n, 2) array of [y, x] vertices')
+    if p.shape[0] < 2:
+        return 0.0
+    if not latlon:
+        return float(np.sum(np.hypot(p[:-1, 1] - p[1:, 1], p[:-1, 0] - p[1:, 0])))
+    y, x = np.deg2rad(p[:, 0]), np.deg2rad(p[:, 1])
+    dlon, dlat = x[1:] - x[:-1], y[1:] - y[:-1]
+    a = np.sin(dlat / 2.0) ** 2.0 + np.cos(y[:-1]) * np.cos(y[1:]) * np.sin(dlon / 2) ** 2.0
+    return float(np.sum(2.0 * np.arcsin(np.sqrt(a))) * Rearth)
+
+
 def cell_area(lat, lon, Rearth=Rearth, to_poles=True):
     """2-D float64 cell areas R^2 |sin(phi_n) - sin(phi_s)| dlambda with mid-point cell
     edges (the `rA` formula of reference utils.py:179-208; the reference builds its
