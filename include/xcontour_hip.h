@@ -421,7 +421,7 @@ int xc_local_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, i
  * No call site inside the reference's package: its scripts trace the contours themselves with skimage's find_contours
  * (tests/test_clength.py:615-630, tests/test_breaking.py, tests/test_localLength.py).  The segments K10 sums, written
  * out, for ALL contours of all slabs.  The rule is K10's (case table, frac, saddles as fully_connected='low', a cell
- * with a NaN corner emits nothing; no wrap across the X seam) with two differences: segments are DIRECTED, start ->
+ * with a NaN corner emits nothing; no wrap across the X seam unless the _periodic entry points below are used) with two differences: segments are DIRECTED, start ->
  * end, in the order of skimage's _get_contour_segments
  *     1 T->L   2 R->T   3 R->L   4 L->B   5 T->B   6 R->T, L->B   7 R->B
  *     8 B->R   9 T->L, B->R   10 B->T   11 B->L   12 L->R   13 T->R   14 L->T        (T top, B bottom, L left, R right)
@@ -449,6 +449,25 @@ int xc_contour_segments_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
 int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                         const double* contours, int ncont, int contours_per_slab, int64_t capacity,
                         uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts);
+
+/* K12 with a periodic X direction (no period value: K12 works in index space).  The plane is a ring of nx cell columns:
+ *   the seam cell, cell column nx-1, has its left corners on node column nx-1 and its right corners on node column 0; its
+ *   columns run from nx-1 to nx exactly (a point on its right edge has column (double)nx).  Its top and bottom edges are
+ *   H(r, nx-1) and H(r+1, nx-1) -- ids the plain call never uses -- and its right edge is column 0's, V(r, 0) = 2 r nx + 1;
+ *   every other id and every other cell is as above, and within one (slab, contour) every edge is still the start of at
+ *   most one segment and the end of at most one.  Y never wraps.
+ *   By construction: for the plane with column 0 appended as column nx, the periodic call returns the records of the plain
+ *   call on that (ny, nx + 1) plane, up to the order inside a range: pts are bit for bit the same, and every edge id is
+ *   folded from the extended plane's numbering to the ring's: (kind, r, c) over nx + 1 columns, id 2 (r (nx+1) + c) + kind,
+ *   becomes 2 (r nx + (c mod nx)) + kind.
+ *   Arguments, layout, the capacity protocol and the return values are those of the plain pair.  It needs nx >= 2, else
+ *   XC_EBADARG; ny < 2: no cells, all counts 0, XC_OK.                                                              */
+int xc_contour_segments_periodic_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                     const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                                     uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts);
+int xc_contour_segments_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                 const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                                 uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts);
 
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident

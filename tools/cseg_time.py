@@ -5,9 +5,11 @@ PV-like, 1: pure noise), N levels from the field's range.  Reports, per call,
   full    the call into exactly sized buffers: the above + the emit pass (emit = full - count);
   join    xc_join_segments on the host, records already downloaded (skipped above --join-max segments);
   facade  Contour2D.find_contours(levels, index=True) on the same slab, host arrays in, polylines out (skipped likewise).
-Wall-clock times around calls that end in a stream synchronisation.
+Wall-clock times around calls that end in a stream synchronisation.  --periodic: the periodic forms
+(xc_contour_segments_periodic_dev, find_contours(periodic=True)): the ring of nx cell columns.
 
     python tools/cseg_time.py --variant 0 --ncont 121 --reps 5
+    python tools/cseg_time.py --variant 0 --ncont 121 --reps 5 --periodic
 """
 import argparse
 import os
@@ -28,6 +30,7 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--ny', type=int, default=1801)
     ap.add_argument('--nx', type=int, default=3600)
+    ap.add_argument('--periodic', action='store_true', help='periodic X: the seam cell column is traced too')
     ap.add_argument('--join-max', type=int, default=30000000, help='most segments the host join and the facade call are timed on')
     a = ap.parse_args()
     import xcontour_amd as xa
@@ -43,6 +46,7 @@ def main():
     lv = np.linspace(mm[0], mm[1], N)
     dc, dn = ctx.to_device(lv), ctx.alloc(S * N * 8)
     head = (ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dc.ptr, N, 0)
+    f = ctx.lib.xc_contour_segments_periodic_dev if a.periodic else ctx.lib.xc_contour_segments_dev
 
     def timed(fn):
         fn()
@@ -54,17 +58,18 @@ def main():
         return (time.perf_counter() - t0) / a.reps
 
     def count():
-        rc = ctx.lib.xc_contour_segments_dev(*head, 0, dn.ptr, None, None, None)
+        rc = f(*head, 0, dn.ptr, None, None, None)
         if rc not in (0, 1):
             ctx._check(rc)
     t_count = timed(count)
     cnt = dn.download((S, N), np.uint64)
     total = int(cnt.sum())
-    cells = S * (ny - 1) * (nx - 1)
-    print('slabs %d variant %d ncont %d: %d segments (%.2f per cell, %.1f MB of records)' % (S, a.variant, N, total, total / cells, total * 48 / 1e6))
+    cells = S * (ny - 1) * (nx if a.periodic else nx - 1)
+    print('slabs %d variant %d ncont %d%s: %d segments (%.2f per cell, %.1f MB of records)'
+          % (S, a.variant, N, ' periodic' if a.periodic else '', total, total / cells, total * 48 / 1e6))
     print('count pass  %10.1f us per call' % (t_count * 1e6))
     df, dt, dp = ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 32)
-    t_full = timed(lambda: ctx._check(ctx.lib.xc_contour_segments_dev(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr)))
+    t_full = timed(lambda: ctx._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr)))
     print('count+emit  %10.1f us per call  (emit pass %.1f us, %.0f GB/s of records)'
           % (t_full * 1e6, (t_full - t_count) * 1e6, total * 48 / max(t_full - t_count, 1e-9) / 1e9))
     if total <= a.join_max:
@@ -76,9 +81,9 @@ def main():
         qh = q.download((ny, nx), np.float64)
         tr = xa.DataArray(qh, ('latitude', 'longitude'), {'latitude': lat, 'longitude': lon}, 'q')
         cm = xa.Contour2D(tr, np.ones(ny), {'X': 'longitude', 'Y': 'latitude'}, {'Y': 'latitude'}, dtype=np.float64)
-        cm.find_contours(lv[:2], index=True)
+        cm.find_contours(lv[:2], index=True, periodic=a.periodic)
         t0 = time.perf_counter()
-        out = cm.find_contours(lv, index=True)
+        out = cm.find_contours(lv, index=True, periodic=a.periodic)
         print('facade      %10.1f us  (find_contours of slab 0, %d polylines kept)' % ((time.perf_counter() - t0) * 1e6, sum(len(p) for p in out)))
     else:
         print('host join   not measured (more than --join-max segments)')

@@ -153,6 +153,8 @@ PROTOTYPES = {
     'xc_local_contour_lengths_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'xc_contour_segments_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
     'xc_contour_segments': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
+    'xc_contour_segments_periodic_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
+    'xc_contour_segments_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
     'xc_join_segments': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -950,14 +952,16 @@ class Context(object):
             return lens, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
-    def contour_segments(self, q, contours):
-        """Marching-squares contour segments (K12, xc_contour_segments_dev).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours
+    def contour_segments(self, q, contours, periodic=False):
+        """Marching-squares contour segments (K12, xc_contour_segments_dev; periodic=True: xc_contour_segments_periodic_dev).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours
         (N,) or (nslab, N) ASCENDING f64 without NaN.  Returns (count uint64 (nslab, N); e_from, e_to int64 (total,): the ids of the
         grid edges the start / end of each directed segment lie on -- horizontal (r, c)-(r, c+1): 2 (r nx + c), vertical
         (r, c)-(r+1, c): 2 (r nx + c) + 1 --; pts float64 (total, 4): (r1, c1, r2, c2) in index space).  Segments are packed by
         (slab, contour): range (s, k) starts at the exclusive scan of `count`; segments whose end points coincide are kept.
         Inside a range the segments are sorted by e_from (unique there), so the result is the same on every call.  Every batch
-        is staged once: a count-only call sizes the buffers of the second."""
+        is staged once: a count-only call sizes the buffers of the second.  periodic=True: X is a ring of nx cell columns (nx >= 2):
+        the seam cell between the last column and the first is traced too, its columns run from nx-1 to nx, and its right edge has
+        column 0's id, 2 r nx + 1 -- the records of the plane with column 0 appended as column nx, ids folded onto the ring."""
         q = _stack_in(q)
         if len(q.shape) != 3:
             raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
@@ -968,7 +972,9 @@ class Context(object):
             raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
         N = contours.shape[-1]
         _check_ascending(contours, 'xc_contour_segments')
-        f = self.lib.xc_contour_segments_dev
+        if periodic and nx < 2:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
+        f = self.lib.xc_contour_segments_periodic_dev if periodic else self.lib.xc_contour_segments_dev
 
         def one(s0, s1):
             n = s1 - s0

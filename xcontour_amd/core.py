@@ -682,16 +682,18 @@ class Contour2D(object):
 
     # ------------------------------------------------------------------ contour lengths
     @staticmethod
-    def _x_period(periodic, xdeg, latlon, who):
+    def _x_period(periodic, xdeg, latlon, who, plain=False):
         """the `periodic` argument of cal_contour_lengths / cal_local_contour_lengths -> None (X has two free edges) or the period
         handed to the library, a float64 in the units of the X coordinates it gets: float64(P), with latlon=True
         float64(deg2rad(float32(P))) -- the cast chain of the coordinates themselves.  `xdeg`: the X coordinate as given, after
-        its cast to float32.  True: 360 degrees, along the direction the coordinate runs in."""
+        its cast to float32.  True: 360 degrees, along the direction the coordinate runs in.
+        plain=True (find_contours, which never casts): `xdeg` is the coordinate as given in float64, True is 360 whatever
+        `latlon`, and the period comes back as float64(P), in the coordinate's own units."""
         if periodic is None or periodic is False or (isinstance(periodic, np.bool_) and not periodic):
             return None
         span = float(xdeg[-1]) - float(xdeg[0]) if xdeg.size >= 2 else 0.0
         if periodic is True or isinstance(periodic, np.bool_):
-            if not latlon:
+            if not latlon and not plain:
                 raise Exception('%s: periodic=True needs latlon=True (there is no default period for a Cartesian plane: '
                                 'give periodic=<the period>)' % who)
             P = -360.0 if span < 0 else 360.0
@@ -709,7 +711,7 @@ class Contour2D(object):
                             % (who, periodic, float(xdeg[0]), float(xdeg[-1])))
         if not abs(P) > abs(span):
             raise Exception('%s: periodic=%r is too short: the X coordinate already spans %r' % (who, periodic, abs(span)))
-        return float(np.float64(np.deg2rad(np.float32(P)))) if latlon else float(np.float64(P))
+        return float(np.float64(np.deg2rad(np.float32(P)))) if latlon and not plain else float(np.float64(P))
 
     def cal_contour_lengths(self, contours, tracer=None, latlon=False, periodic=False):
         """
@@ -825,7 +827,7 @@ class Contour2D(object):
         return out
 
     # ------------------------------------------------------------------ contour polylines
-    def find_contours(self, contours, tracer=None, index=False, return_closed=False):
+    def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):
         """
         The contours themselves: every level traced into polylines on the GPU (K12, xc_contour_segments, and the host join
         xc_join_segments).  The reference's scripts do this with skimage's find_contours through a `find_contour` helper that
@@ -833,17 +835,32 @@ class Contour2D(object):
 
         `contours` as for cal_contour_lengths: an int or list goes through cal_contours; a labelled array over (..., contour)
         may differ per slab; levels in any order, a NaN level has no polylines.  The segments are those cal_contour_lengths
-        sums (same case table, saddles, NaN cells; no wrap across the X seam), directed, and joined by matching the grid edges
-        their end points lie on -- no float comparison.  A polyline's vertices are the start of its first segment and the end
-        of every segment; consecutive equal vertices are merged, polylines left with fewer than two vertices are dropped, and a
-        closed polyline (a ring) repeats its first vertex at the end.  An open polyline starts and ends on the plane's edge or
-        beside a NaN cell.  The polylines of a level are ordered by the smallest grid-edge id they touch.
+        sums (same case table, saddles, NaN cells; no wrap across the X seam unless `periodic`), directed, and joined by
+        matching the grid edges their end points lie on -- no float comparison.  A polyline's vertices are the start of its
+        first segment and the end of every segment; consecutive equal vertices are merged, polylines left with fewer than two
+        vertices are dropped, and a closed polyline (a ring) repeats its first vertex at the end.  An open polyline starts and
+        ends on the plane's edge or beside a NaN cell.  The polylines of a level are ordered by the smallest grid-edge id they
+        touch.
 
         Each polyline is an (n, 2) float64 array [row, column] = [equivalent dim, other plane dim]: with index=True in index
         space, else mapped onto the plane's coordinates AS GIVEN with np.interp(., arange(n), coord) in float64 (no float32
         cast, unlike cal_contour_lengths).  Returns out[k] -- a list of arrays per level -- when the tracer has no leading dims,
         else out[slab][k] with the leading dims flattened in the tracer's order; with return_closed=True also the same nesting
-        of bools (True: a ring).
+        of bools (True: a ring), with return_winding=True also the same nesting of ints (below): out[, closed][, winding].
+
+        `periodic`: False, True or the period, the values cal_contour_lengths takes (K12's periodic form,
+        xc_contour_segments_periodic).  The cell between the last and the first column is then traced too, so a contour that
+        circles the pole is one ring.  The period is in the X coordinate's units as given, in float64 (no float32 cast, no
+        radians); True is 360 along the direction the coordinate runs in; it has the sign of last - first, is longer than that
+        span, and the ring has at least two columns.  With index=True only its truth value matters and no coordinates are
+        needed.  A polyline runs on continuously past the seam instead of jumping back: in walk order every segment has an
+        integer lap m, 0 for the first, one more each time the walk leaves the seam cell through its right edge into column 0
+        and one less the other way.  With index=True a vertex column is c + nx m, c in [0, nx] as the kernel wrote it (one
+        float64 addition: it rounds once where m != 0); else x = np.interp(c, arange(nx + 1), [x..., x[0] + P]) + m P.  Rows
+        map as ever.  The winding number W of a ring is the number of times it goes round the ring of columns, signed by its
+        direction of travel in X: 0 for an ordinary ring, +1 or -1 for one that circles the globe; 0 for an open polyline.  A
+        ring still repeats its first vertex, but with W != 0 its last vertex is the first displaced by W nx columns (W P in
+        coordinates).  Without `periodic` every winding number is 0.
         """
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
@@ -855,34 +872,33 @@ class Contour2D(object):
                 if d not in dcoords:
                     raise Exception('find_contours needs coordinate values for the plane dim %s (or index=True)' % d)
                 cds.append(np.asarray(dcoords[d], dtype=np.float64))
+            period = self._x_period(periodic, cds[1], False, 'find_contours', plain=True)
+            ring = period is not None
+        else:
+            period, ring = None, bool(periodic)
         q, lead, lshape, coords = self._plane(data)
         q = self._float(q)
-        nslab = q.shape[0]
+        nslab, nx = q.shape[0], q.shape[2]
+        if ring and nx < 2:
+            raise Exception('find_contours: periodic needs at least two columns along the periodic dim')
         bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
         N = bs.shape[1]
-        cnt, ef, et, pts = self.ctx.contour_segments(q, bs)
+        cnt, ef, et, pts = self.ctx.contour_segments(q, bs, periodic=ring)
         off = np.concatenate([[0], np.cumsum(cnt.ravel().astype(np.int64))])
         walk, poff, closed, rpo = nat.join_segments(off, ef, et)
-        if not index and pts.size:
-            pts = np.stack([np.interp(pts[:, 0], np.arange(cds[0].size), cds[0]), np.interp(pts[:, 1], np.arange(cds[1].size), cds[1]),
-                            np.interp(pts[:, 2], np.arange(cds[0].size), cds[0]), np.interp(pts[:, 3], np.arange(cds[1].size), cds[1])], axis=1)
+        polys, cl, wd = contour_polylines(walk, poff, closed, rpo, pts, nx=nx if ring else None,
+                                          ycoord=None if index else cds[0], xcoord=None if index else cds[1], period=period)
         out = [[None] * N for _ in range(nslab)]
         flags = [[None] * N for _ in range(nslab)]
+        winds = [[None] * N for _ in range(nslab)]
         for s in range(nslab):
             for j in range(N):                                   # j: the sorted level; order[s, j]: where the caller put it
-                polys, cl = [], []
-                for p in range(int(rpo[s * N + j]), int(rpo[s * N + j + 1])):
-                    segs = walk[poff[p]:poff[p + 1]]
-                    v = np.concatenate([pts[segs[:1], :2], pts[segs, 2:]])
-                    keep = np.concatenate([[True], (v[1:] != v[:-1]).any(axis=1)])
-                    if int(keep.sum()) < 2:
-                        continue
-                    polys.append(np.ascontiguousarray(v[keep]))
-                    cl.append(bool(closed[p]))
-                out[s][int(order[s, j])], flags[s][int(order[s, j])] = polys, cl
+                k, r = int(order[s, j]), s * N + j
+                out[s][k], flags[s][k], winds[s][k] = polys[r], cl[r], wd[r]
         if not lead:
-            out, flags = out[0], flags[0]
-        return (out, flags) if return_closed else out
+            out, flags, winds = out[0], flags[0], winds[0]
+        res = (out,) + ((flags,) if return_closed else ()) + ((winds,) if return_winding else ())
+        return res if len(res) > 1 else out
 
     # ------------------------------------------------------------------ local wave activity
     def cal_local_wave_activity(self, q, Q, mask_idx=None, part='all', metric=None, exact=None):
@@ -1256,14 +1272,84 @@ def _edges_from_levels(b, right_edge):
     return edges.astype(np.float64), binc, last_closed
 
 
-def find_contour(data, dims, level, period=[None, None]):
+def contour_polylines(walk, poff, closed, rpo, pts, nx=None, ycoord=None, xcoord=None, period=None):
+    """
+    The vertex rule of Contour2D.find_contours on the host (no device): the joined segments -> polylines, laps and winding
+    numbers.  walk (total,) int64: segment indices polyline by polyline in walk order; poff (npoly + 1,) into `walk`; closed
+    (npoly,) bool; rpo (nrange + 1,): the polylines of range r are [rpo[r], rpo[r+1]) -- what _native.join_segments returns --;
+    pts (total, 4) float64 (r1, c1, r2, c2) in index space, as Context.contour_segments returns them.  nx: None, or the number
+    of columns of a plane traced with a periodic X direction (columns in [0, nx], the seam cell's right edge at nx).  ycoord /
+    xcoord: None (index space) or the plane's coordinates in float64; period: the X period, with xcoord and nx.
+
+    Vertices: the start of the first segment and the end of every segment, consecutive equal vertices merged, polylines left
+    with fewer than two vertices dropped.  With nx, a segment's lap m counts the passes through the seam before it in walk
+    order: between one segment's end column and the next one's start column the jump is 0, +nx (m + 1: from the seam cell's
+    right edge, column nx, into column 0) or -nx (m - 1); its columns are c + nx m in index space and
+    np.interp(c, arange(nx + 1), [xcoord..., xcoord[0] + period]) + m period in coordinates.  The winding number of a ring is
+    m_last + (c_end[last] - c_start[first]) / nx, an integer; of an open polyline, 0.
+    Returns (polys, closed, winding): per range a list of (n, 2) float64 arrays [row, column], of bools and of ints.
+    """
+    walk, poff, rpo = np.asarray(walk, dtype=np.int64), np.asarray(poff, dtype=np.int64), np.asarray(rpo, dtype=np.int64)
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 4)
+    r1, c1, r2, c2 = (pts[walk, i] for i in range(4))                      # in walk order
+    ring = nx is not None
+    npoly = poff.size - 1
+    wind = np.zeros(npoly, dtype=np.int64)
+    if ring:
+        nx = int(nx)
+        heads = poff[:-1]
+        jump = np.zeros(walk.size, dtype=np.float64)
+        jump[1:] = c2[:-1] - c1[1:]
+        jump[heads] = 0.0
+        step = (jump == float(nx)).astype(np.int64) - (jump == -float(nx)).astype(np.int64)
+        if ((jump != 0.0) & (step == 0)).any():
+            raise Exception('contour_polylines: consecutive segments that are neither adjacent nor one ring apart')
+        run = np.cumsum(step)
+        m = run - np.repeat(run[heads], np.diff(poff))                      # segmented cumulative sum: 0 at every head
+        if npoly:
+            last = poff[1:] - 1
+            w = m[last] + ((c2[last] - c1[heads]) / float(nx)).astype(np.int64)
+            wind = np.where(np.asarray(closed, dtype=bool), w, 0)
+    if ycoord is not None:
+        ycoord, xcoord = np.asarray(ycoord, dtype=np.float64), np.asarray(xcoord, dtype=np.float64)
+        yi = np.arange(ycoord.size)
+        xi, xe = (np.arange(nx + 1), np.concatenate([xcoord, [xcoord[0] + period]])) if ring else (np.arange(xcoord.size), xcoord)
+        if walk.size:
+            r1, r2 = np.interp(r1, yi, ycoord), np.interp(r2, yi, ycoord)
+            c1, c2 = np.interp(c1, xi, xe), np.interp(c2, xi, xe)
+        if ring:
+            c1, c2 = c1 + m * float(period), c2 + m * float(period)
+    elif ring:
+        c1, c2 = c1 + (nx * m).astype(np.float64), c2 + (nx * m).astype(np.float64)
+    S, E = np.stack([r1, c1], axis=1), np.stack([r2, c2], axis=1)
+    polys, cl, wd = [], [], []
+    for r in range(rpo.size - 1):
+        ps, cs, ws = [], [], []
+        for p in range(int(rpo[r]), int(rpo[r + 1])):
+            a, b = int(poff[p]), int(poff[p + 1])
+            v = np.concatenate([S[a:a + 1], E[a:b]])
+            keep = np.concatenate([[True], (v[1:] != v[:-1]).any(axis=1)])
+            if int(keep.sum()) < 2:
+                continue
+            ps.append(np.ascontiguousarray(v[keep]))
+            cs.append(bool(closed[p]))
+            ws.append(int(wind[p]))
+        polys.append(ps); cl.append(cs); wd.append(ws)
+    return polys, cl, wd
+
+
+def find_contour(data, dims, level, period=[None, None], periodic=False):
     """
     The polylines of ONE level of a 2-D labelled field, in the call shape of the reference's scripts
     (tests/test_clength.py:615: find_contour(tr1[0], ['YC', 'XC'], 1.15076609, period=[None, None])): `dims` = [ydim, xdim].
     Returns a list of (n, 2) float64 arrays [y, x] in the field's coordinates -- Contour2D.find_contours([level])[0], which
     states the rule.  Periodic tracing is not supported yet: an entry of `period` that is not None raises.
+    A periodic X direction goes through the keyword `periodic` instead -- False, True (360) or the period in xdim's units --,
+    handed to Contour2D.find_contours(periodic=...), which states what it means: the seam cell is traced, polylines run on
+    past the seam, and a contour that circles the globe is one ring.
     """
     if period is not None and any(p is not None for p in period):
+        # (a periodic X direction: the keyword `periodic` of this function, not `period`)
         raise NotImplementedError('find_contour: period=%r is not supported yet (only [None, None]: no wrap across the plane\'s '
                                   'edges)' % (period,))
     ydim, xdim = dims
@@ -1271,7 +1357,7 @@ def find_contour(data, dims, level, period=[None, None]):
     if len(ddims) != 2 or set(ddims) != {ydim, xdim}:
         raise Exception('find_contour expects a 2-D field on the dims %s' % [ydim, xdim])
     cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
-    return cm.find_contours(np.array([float(level)]))[0]
+    return cm.find_contours(np.array([float(level)]), periodic=periodic)[0]
 
 
 def _level_order(vals, order):

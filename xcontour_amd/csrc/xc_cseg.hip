@@ -4,7 +4,7 @@
 // with skimage's find_contours and go on from the polylines (tests/test_clength.py:615-630, tests/test_breaking.py,
 // tests/test_localLength.py).  Build-defined.  The rule is K10's, stated in the header of xc_clen.hip (case table, frac, saddles as
 // fully_connected='low', a NaN corner emits nothing), with the two differences of xc_cseg_cell.h: segments are DIRECTED (start -> end
-// as in skimage's _get_contour_segments) and a segment whose two end points coincide is kept.  X is not periodic here.
+// as in skimage's _get_contour_segments) and a segment whose two end points coincide is kept.
 //
 // Record, one per segment, as a structure of arrays: e_from / e_to (int64) the ids of the grid edges its start / end point lie on --
 // horizontal edge (r, c)-(r, c+1): 2 (r nx + c); vertical edge (r, c)-(r+1, c): 2 (r nx + c) + 1 -- and pts[4] (float64) = (r1, c1, r2,
@@ -23,6 +23,17 @@
 //          off[range] + the block's offset + slot with plain stores.
 // No global atomics, no float atomics; counts and records are the same on every run, up to the order inside a range.
 // Capacity: a block's count of one level is a 32-bit word: the launcher gives a block at most 2^17 tiles (< 2^32 segments).
+//
+// Periodic X (WRAP, xc_contour_segments_periodic): as in K10 the plane gains one cell column, index nx-1 -- the seam cell --, whose
+// left corners are node column nx-1 and whose right corners are node column 0: cL = nx-1, cR = nx exactly (a point on its right edge
+// has column (double)nx).  Edge ids: the seam cell's top and bottom edges are H(r, nx-1) and H(r+1, nx-1), ids the plain kernel never
+// uses, and its right edge is column 0's, V(r, 0) = 2 r nx + 1 (the plain hT + 3 would be V(r+1, 0)); every other id is unchanged, so
+// per (slab, level) every edge still starts at most one segment and ends at most one.  The result is what the plain kernel returns
+// for the plane with column 0 appended as column nx -- pts bit for bit -- with every edge id folded from that plane's numbering to
+// the ring's: (kind, r, c) over nx + 1 columns -> 2 (r nx + (c mod nx)) + kind.  nx >= 2; Y never wraps.
+// Kernels k_ring_seg<TQ, EMIT>; k_cseg is the same code with the wrap compiled out.
+// Mapping: tiles cover nx cell columns, and the lane whose column is nx -- the right neighbour of the seam cell's lane, a cell lane
+// or the wave's halo lane 63 -- loads node column 0, so the seam cell takes its right corners by the same DPP shift as every other.
 #include "xc_internal.h"
 #include <cmath>
 
@@ -43,14 +54,19 @@ constexpr int64_t CSEG_MAX_TILES = 1 << 17; // tiles per block at most: 2^17 x 3
 constexpr size_t cseg_lds(int G) { return (size_t)(4 + G + 2) * 8 + (size_t)G * 8 + (size_t)G * 4 + 16; }
 static_assert(cseg_lds(XC_CSEG_GROUP_LEVELS) <= 48 * 1024, "a level group must fit 48 KB of LDS");
 
+#define XC_CSEG_PARAMS const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ contours, int N, int contours_per_slab, \
+                        int G, int64_t ntj, int64_t nti, int bps, unsigned* __restrict__ part,                                            \
+                        const unsigned long long* __restrict__ part_off, const long long* __restrict__ off, long long capacity,           \
+                        long long* __restrict__ e_from, long long* __restrict__ e_to, double* __restrict__ pts
+#define XC_CSEG_ARGS q, ny, nx, contours, N, contours_per_slab, G, ntj, nti, bps, part, part_off, off, capacity, e_from, e_to, pts
+
+// The pass of k_cseg (WRAP = false: the plane as it is) and k_ring_seg (WRAP = true: periodic X); WRAP is a compile-time variant: the
+// plain kernel pays nothing for it.
 // EMIT = false: part[slab][block][level] = the block's segment count.  EMIT = true: the records, at off[slab N + level] +
 // part_off[slab][block][level] + slot; nothing is written at or past `capacity`.
-template <typename TQ, bool EMIT>
-__global__ __launch_bounds__(CSEG_TPB)
-void k_cseg(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ contours, int N, int contours_per_slab, int G,
-            int64_t ntj, int64_t nti, int bps, unsigned* __restrict__ part, const unsigned long long* __restrict__ part_off,
-            const long long* __restrict__ off, long long capacity, long long* __restrict__ e_from, long long* __restrict__ e_to,
-            double* __restrict__ pts)
+template <typename TQ, bool EMIT, bool WRAP>
+__device__ __forceinline__
+void cseg_pass(XC_CSEG_PARAMS)
 {
     extern __shared__ __attribute__((aligned(16))) double sm[];
     const int tid = threadIdx.x;
@@ -89,7 +105,7 @@ void k_cseg(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
         zlo = 2.0 * dev + 1e-9;
     }
     const TQ* qs = q + (size_t)slab * ny * nx;
-    const int64_t ncx = nx - 1, ncy = ny - 1, nx2 = 2 * nx;
+    const int64_t ncx = WRAP ? nx : nx - 1, ncy = ny - 1, nx2 = 2 * nx;
     const int lane = tid & 63, wave = tid >> 6;
 
     for (int64_t tile = blockIdx.x; tile < ntj * nti; tile += bps) {
@@ -97,8 +113,10 @@ void k_cseg(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
         const int64_t i = ti * CSEG_W + wave * 63 + lane;                                // this lane's cell column
         const int64_t j0 = tj * CSEG_RB, j1 = (j0 + CSEG_RB < ncy) ? j0 + CSEG_RB : ncy;
         const bool cell = lane < 63 && i < ncx;                                          // lanes without a cell still load and shift
-        const int64_t c = i < nx - 1 ? i : nx - 1;                                       // corner column loaded by this lane
+        int64_t c = i < nx - 1 ? i : nx - 1;                                             // corner column loaded by this lane
+        if constexpr (WRAP) { if (i == nx) c = 0; }                                      // column nx is column 0
         const double cL = (double)c;
+        const int64_t rwrap = (WRAP && i == nx - 1) ? nx2 : 0;                           // the seam cell's right edge: V(r, 0)
         double ul = (double)qs[(size_t)j0 * nx + c];
         double ur = lane_shift_keep<DPP_WAVE_SHL1>(ul, ul);
         constexpr int B = 4;
@@ -130,7 +148,7 @@ void k_cseg(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
                         const double lv = s_cx[k + 1];
                         if constexpr (EMIT) {
                             const unsigned long long base = s_base[k];
-                            cseg_cell(ul, ur, ll, lr, lv, (double)r, cL, hT, nx2,
+                            cseg_cell(ul, ur, ll, lr, lv, (double)r, cL, hT, nx2, rwrap,
                                       [&](int64_t ef, int64_t et, double r1, double c1, double r2, double c2) {
                                           const unsigned slot = __hip_atomic_fetch_add(s_cur + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                                           const long long at = (long long)(base + slot);
@@ -154,6 +172,23 @@ void k_cseg(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __re
         for (int k = tid; k < ng; k += CSEG_TPB) part[pb + k] = s_cur[k];
     }
 }
+
+template <typename TQ, bool EMIT>
+__global__ __launch_bounds__(CSEG_TPB)
+void k_cseg(XC_CSEG_PARAMS)
+{
+    cseg_pass<TQ, EMIT, false>(XC_CSEG_ARGS);
+}
+
+// periodic X: the ring of nx cell columns
+template <typename TQ, bool EMIT>
+__global__ __launch_bounds__(CSEG_TPB)
+void k_ring_seg(XC_CSEG_PARAMS)
+{
+    cseg_pass<TQ, EMIT, true>(XC_CSEG_ARGS);
+}
+#undef XC_CSEG_ARGS
+#undef XC_CSEG_PARAMS
 
 // per (slab, level): part[slab][b][level], b = 0 .. bps-1, -> part_off[slab][b][level] = the sum over the blocks before b, and
 // count[slab][level] = the sum over all.  bps = 0 (no cells): counts of 0.
@@ -198,9 +233,10 @@ void k_cseg_scan(const unsigned long long* __restrict__ count, int64_t M, long l
 
 }  // namespace
 
-// One xc_contour_segments_dev call (device pointers).  Waits for the stream once, between the passes: the total decides on the host
-// whether the records fit.  -> XC_OK, 1 (capacity < total: only out_count was written) or an error.
-int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+// One xc_contour_segments_dev call (device pointers; wrap != 0: xc_contour_segments_periodic_dev, the ring of nx cell columns).  Waits
+// for the stream once, between the passes: the total decides on the host whether the records fit.  -> XC_OK, 1 (capacity < total:
+// only out_count was written) or an error.
+int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int wrap,
                             const double* contours, int N, int contours_per_slab, int64_t capacity,
                             uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts, int64_t* out_total)
 {
@@ -208,6 +244,7 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
     if (!q || !contours || !out_count || nslab < 1 || ny < 1 || nx < 1 || N < 1 || capacity < 0)
         return fail(ctx, XC_EBADARG, "xc_contour_segments: bad arguments");
     if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_segments: q_dtype must be XC_F32 or XC_F64");
+    if (wrap && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_segments_periodic: nx >= 2");
     if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_contour_segments: nslab too large");
     if (capacity > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_segments: capacity > 0 needs the record arrays");
     if (ny > (int64_t)1 << 30 || nx > (int64_t)1 << 30) return fail(ctx, XC_EBADARG, "xc_contour_segments: plane too large for the edge ids");
@@ -215,7 +252,7 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
     const int ngroup = (N + G - 1) / G;
     if (ngroup > 65535) return fail(ctx, XC_EBADARG, "xc_contour_segments: too many contours");
     const size_t lds = cseg_lds(G);
-    const int64_t ncx = nx - 1, ncy = ny - 1;
+    const int64_t ncx = wrap ? nx : nx - 1, ncy = ny - 1;
     const int64_t ntj = ncy > 0 ? (ncy + CSEG_RB - 1) / CSEG_RB : 0, nti = ncx > 0 ? (ncx + CSEG_W - 1) / CSEG_W : 0;
     const int64_t ntile = ntj * nti;
     // blocks per slab: the launch's share of ~2048 blocks, at least 8, no more than tiles, and at most CSEG_MAX_TILES tiles each
@@ -241,9 +278,12 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
     unsigned long long* part_off = (unsigned long long*)(sc + pc);
     long long* off = (long long*)(sc + pc + po);
     const dim3 grid((unsigned)bps, (unsigned)nslab, (unsigned)ngroup);
-#define XC_CSEG(TQ_, EMIT_) hipLaunchKernelGGL((k_cseg<TQ_, EMIT_>), grid, dim3(CSEG_TPB), lds, ctx->stream, (const TQ_*)q, ny, nx, contours, N,  \
-                                               contours_per_slab, G, ntj, nti, (int)bps, part, part_off, off, (long long)capacity,                \
-                                               (long long*)e_from, (long long*)e_to, pts)
+#define XC_CSEG_ARGS(TQ_) (const TQ_*)q, ny, nx, contours, N, contours_per_slab, G, ntj, nti, (int)bps, part, part_off, off, (long long)capacity, \
+                          (long long*)e_from, (long long*)e_to, pts
+#define XC_CSEG(TQ_, EMIT_) do {                                                                                                      \
+        if (wrap) hipLaunchKernelGGL((k_ring_seg<TQ_, EMIT_>), grid, dim3(CSEG_TPB), lds, ctx->stream, XC_CSEG_ARGS(TQ_));                \
+        else hipLaunchKernelGGL((k_cseg<TQ_, EMIT_>), grid, dim3(CSEG_TPB), lds, ctx->stream, XC_CSEG_ARGS(TQ_));                         \
+    } while (0)
     if (bps > 0) {
         if (q_dtype == XC_F64) XC_CSEG(double, false); else XC_CSEG(float, false);
         XC_HIP(ctx, hipGetLastError());
@@ -266,6 +306,7 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
         XC_HIP(ctx, hipGetLastError());
     }
 #undef XC_CSEG
+#undef XC_CSEG_ARGS
     return XC_OK;
 }
 

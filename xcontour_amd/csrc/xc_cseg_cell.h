@@ -32,11 +32,13 @@ __device__ __forceinline__ int cseg_case(double ul, double ur, double ll, double
 __device__ __forceinline__ int cseg_count(int cs) { return (cs == 6 || cs == 9) ? 2 : 1; }
 
 // One NaN-free cell (r0, c0) and one crossed level: `emit(e_from, e_to, r1, c1, r2, c2)` once per segment, in the rule's order.
-// rT / cL: the cell's first row / column as doubles; hT: the id of its top edge, 2 (r0 nx + c0); nx2 = 2 nx.
+// rT / cL: the cell's first row / column as doubles; hT: the id of its top edge, 2 (r0 nx + c0); nx2 = 2 nx; rwrap: what the id of
+// its right edge is short of hT + 3 -- 0, except for the seam cell of a periodic plane (c0 = nx - 1), whose right edge is column
+// 0's, 2 r0 nx + 1: nx2.
 // Edge ids: horizontal (r, c)-(r, c+1): 2 (r nx + c); vertical (r, c)-(r+1, c): 2 (r nx + c) + 1.
 template <typename Emit>
 __device__ __forceinline__ void cseg_cell(double ul, double ur, double ll, double lr, double c, double rT, double cL,
-                                          int64_t hT, int64_t nx2, Emit&& emit)
+                                          int64_t hT, int64_t nx2, int64_t rwrap, Emit&& emit)
 {
     const int cs = cseg_case(ul, ur, ll, lr, c);
     const double rB = rT + 1.0, cR = cL + 1.0;
@@ -44,7 +46,7 @@ __device__ __forceinline__ void cseg_cell(double ul, double ur, double ll, doubl
     const double lrow = __dadd_rn(rT, frac_of(ul, ll, c)), rrow = __dadd_rn(rT, frac_of(ur, lr, c));
     auto row = [&](int i) { return i == CSEG_T ? rT : i == CSEG_B ? rB : i == CSEG_L ? lrow : rrow; };
     auto col = [&](int i) { return i == CSEG_T ? tc : i == CSEG_B ? bc : i == CSEG_L ? cL : cR; };
-    auto eid = [&](int i) { return i == CSEG_T ? hT : i == CSEG_B ? hT + nx2 : i == CSEG_L ? hT + 1 : hT + 3; };
+    auto eid = [&](int i) { return i == CSEG_T ? hT : i == CSEG_B ? hT + nx2 : i == CSEG_L ? hT + 1 : hT + 3 - rwrap; };
     const int nseg = cseg_count(cs);
 #pragma unroll 1
     for (int t = 0; t < nseg; ++t) {

@@ -305,19 +305,28 @@ int xc_contour_segments_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
                             uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
 {
     XC_CTX(ctx);
-    return launch_contour_segments(ctx, q, q_dtype, nslab, ny, nx, contours, ncont, contours_per_slab, capacity, out_count, e_from, e_to, pts,
-                                   nullptr);
+    return launch_contour_segments(ctx, q, q_dtype, nslab, ny, nx, 0, contours, ncont, contours_per_slab, capacity, out_count, e_from, e_to,
+                                   pts, nullptr);
+}
+
+int xc_contour_segments_periodic_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                     const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                                     uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
+{
+    XC_CTX(ctx);
+    return launch_contour_segments(ctx, q, q_dtype, nslab, ny, nx, 1, contours, ncont, contours_per_slab, capacity, out_count, e_from, e_to,
+                                   pts, nullptr);
 }
 
 // The records are as many as the field has segments, known only after the count pass: they land in a device block of their own,
-// taken and released inside the call, and are copied out from there.
-int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
-                        const double* contours, int ncont, int contours_per_slab, int64_t capacity,
-                        uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
+// taken and released inside the call, and are copied out from there.  wrap: the _periodic form.
+static int contour_segments_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int wrap,
+                                 const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                                 uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
 {
-    XC_CTX(ctx);
     if (!q || !contours || !out_count || nslab < 1 || ny < 1 || nx < 1 || ncont < 1 || capacity < 0)
         return fail(ctx, XC_EBADARG, "xc_contour_segments: bad arguments");
+    if (wrap && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_segments_periodic: nx >= 2");
     if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_segments: bad dtype");
     if (capacity > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_segments: capacity > 0 needs the record arrays");
     const int64_t nc = contours_per_slab ? nslab : 1;
@@ -330,7 +339,8 @@ int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, 
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dc, contours, cb));
     XC_TRY(flush_in(ctx));
     int64_t total = 0;
-    int rc = launch_contour_segments(ctx, pq, q_dtype, nslab, ny, nx, dc, ncont, contours_per_slab, 0, dn, nullptr, nullptr, nullptr, &total);
+    int rc = launch_contour_segments(ctx, pq, q_dtype, nslab, ny, nx, wrap, dc, ncont, contours_per_slab, 0, dn, nullptr, nullptr, nullptr,
+                                     &total);
     if (rc < 0) return rc;
     XC_TRY(st.deliver());
     XC_TRY(xc_sync(ctx));
@@ -339,8 +349,8 @@ int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, 
     char* rec = nullptr;                                      // e_from | e_to | pts
     const size_t n8 = (size_t)total * 8;
     if (hipMalloc((void**)&rec, 6 * n8) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, XC_ENOMEM, "xc_contour_segments: no device memory for the records"); }
-    rc = launch_contour_segments(ctx, pq, q_dtype, nslab, ny, nx, dc, ncont, contours_per_slab, total, dn, (int64_t*)rec, (int64_t*)(rec + n8),
-                                 (double*)(rec + 2 * n8), nullptr);
+    rc = launch_contour_segments(ctx, pq, q_dtype, nslab, ny, nx, wrap, dc, ncont, contours_per_slab, total, dn, (int64_t*)rec,
+                                 (int64_t*)(rec + n8), (double*)(rec + 2 * n8), nullptr);
     hipError_t e = hipSuccess;
     if (rc == XC_OK) {
         e = hipStreamSynchronize(ctx->stream);
@@ -351,6 +361,22 @@ int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, 
     (void)hipFree(rec);
     if (e != hipSuccess) return hipfail(ctx, e, "xc_contour_segments: copying the records");
     return rc;
+}
+
+int xc_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                        const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                        uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
+{
+    XC_CTX(ctx);
+    return contour_segments_host(ctx, q, q_dtype, nslab, ny, nx, 0, contours, ncont, contours_per_slab, capacity, out_count, e_from, e_to, pts);
+}
+
+int xc_contour_segments_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                 const double* contours, int ncont, int contours_per_slab, int64_t capacity,
+                                 uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts)
+{
+    XC_CTX(ctx);
+    return contour_segments_host(ctx, q, q_dtype, nslab, ny, nx, 1, contours, ncont, contours_per_slab, capacity, out_count, e_from, e_to, pts);
 }
 
 // ------------------------------------------------------------------------------------ K7

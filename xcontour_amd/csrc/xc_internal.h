@@ -323,8 +323,9 @@ int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_
                                  const double* ycoord, const double* xcoord, double period, double radius,
                                  int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
                                  const double* levels, double* out_len, double* out_level, uint64_t* out_nseg);
-// K12: counts, then (when they fit `capacity`) the records; waits for the stream once.  *out_total (may be null): the segment total
-int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+// K12: counts, then (when they fit `capacity`) the records; waits for the stream once.  *out_total (may be null): the segment total.
+// wrap != 0: periodic X (nx >= 2)
+int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int wrap,
                             const double* contours, int N, int contours_per_slab, int64_t capacity,
                             uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts, int64_t* out_total);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
