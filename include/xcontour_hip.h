@@ -469,6 +469,49 @@ int xc_contour_segments_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_
                                  const double* contours, int ncont, int contours_per_slab, int64_t capacity,
                                  uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts);
 
+/* ------------------------------------------------------------------ K13 contour pieces and their statistics
+ * The reference's scripts work piece by piece (tests/test_breaking.py: the largest contour round the pole; tests/test_clength.py:
+ * contour_length(seg) per piece; utils.contour_area).  Input: K12's records ON THE DEVICE, as the K12 _dev entry points wrote them --
+ * count[nrange] (a range = one (slab, contour), K12's out_count), e_from, e_to, pts -- with ny, nx and `periodic` of that call.
+ * A PIECE is a connected chain of segments under "next(i) is the segment of the same range whose e_from == e_to[i]": a ring, or an
+ * open polyline headed by a segment without a predecessor (the polylines of the host join above).  2 ny nx < 2^31 and every range has
+ * fewer than 2^31 segments, else XC_EBADARG.
+ *   ycoord[ny], xcoord[nx], period, radius: the plane's coordinates with exactly the meaning they have for the K10 entry points
+ *     (radians when radius > 0; period is read only when periodic != 0: column nx is xcoord[0] + period).
+ *   record (structure of arrays, one per piece):
+ *     first_edge int64  the smallest e_from of the piece: unique within a range, the key the host join orders polylines by
+ *     nseg       int64  its segments, coincident-end ones included
+ *     closed     int32  1 for a ring, 0 for an open polyline
+ *     winding    int32  rings of a periodic plane: the number of links that jump from column nx to column 0 minus those that jump
+ *                       back (the ring's closing link included) -- what the facade's contour_polylines computes; else 0
+ *     length     f64    the sum of K10's segment lengths (np.interp end points, haversine x radius or hypot; a segment whose end
+ *                       points coincide adds nothing; a piece of such segments only has length 0, not NaN)
+ *     area       f64    S = 1/2 sum over the directed segments a -> b of (Ya' + Yb') (Xa - Xb); Y' = Y on a Cartesian plane; Y' = sin(Y)
+ *                       when radius > 0, and S is then multiplied by radius^2 (the shoelace formula on the equal-area (lambda, sin phi)
+ *                       plane).  Signed; NaN for an open piece.  Ring with winding 0: |S| is the enclosed area, S > 0 when the ring
+ *                       encloses values ABOVE the level for (ycoord, xcoord) both ascending (each descending coordinate flips the
+ *                       sign).  Ring with winding != 0: S is the signed area between the ring and the line Y' = 0; on the sphere
+ *                       the polar cap it bounds measures 2 pi radius^2 -/+ S.
+ *     row_min, row_max f64  the smallest / largest index-space row over the end points of the piece's segments
+ *   length and area are exact sums of their float64 terms rounded once (fixed-point accumulators), and every other field is an
+ *   integer reduction: the records do not depend on the order of the segments or of arrival.
+ *   layout: pieces packed by range: the pieces of range r are [poff[r], poff[r+1]), poff the exclusive scan of piece_count.  The order
+ *     INSIDE a range is unspecified (sort by first_edge for the order of the host join).
+ *   piece_count[nrange] is always written.  capacity >= sum(piece_count): the records are written, XC_OK.  Otherwise nothing is
+ *     written to the record arrays and 1 is returned (capacity 0 with NULL record arrays = count only).  The number of segments is an
+ *     upper bound of the number of pieces.
+ * The call waits for the stream twice (K12's counts size the work; the piece counts decide whether the records fit).  Edge tables of
+ * 2 ny nx int32 per range are built for groups of ranges; xc_set_cpiece_workspace caps a group's tables in bytes (default 1 GiB; one
+ * range is always allowed; the result does not depend on it).  With xc_set_kernel_timing on, xc_last_cpiece_profile returns the last
+ * call's device times in ms -- ms[0] edge tables (clear, scatter, link), ms[1] the doubling rounds, ms[2] roots and slots, ms[3] the
+ * reductions -- the number of rounds summed over the groups, and the number of groups.                                          */
+int xc_contour_pieces_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                          int64_t ny, int64_t nx, int periodic, const double* ycoord, const double* xcoord, double period, double radius,
+                          int64_t capacity, uint64_t* piece_count, int64_t* first_edge, int64_t* nseg, int32_t* closed, int32_t* winding,
+                          double* length, double* area, double* row_min, double* row_max);
+int xc_set_cpiece_workspace(xc_ctx* ctx, uint64_t bytes);
+int xc_last_cpiece_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

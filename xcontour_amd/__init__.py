@@ -10,7 +10,7 @@ There is no CPU fallback.
 """
 from .core import Contour2D, Table, find_contour, contour_polylines
 from .utils import equivalent_latitudes, latitude_lengths_at, cell_area, grad_metrics, \
-    cartesian_metrics, Rearth, polyline_length
+    cartesian_metrics, Rearth, polyline_length, contour_area
 from .labeled import DataArray, Dataset
 from .ncio import open_dataset
 from .pipeline import KeffPlan, shard_slabs

@@ -156,6 +156,10 @@ PROTOTYPES = {
     'xc_contour_segments_periodic_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
     'xc_contour_segments_periodic': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp]),
     'xc_join_segments': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_contour_pieces_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _f64, _f64, _i64,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
+    'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
                                       _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'xc_sort_profile': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -996,6 +1000,89 @@ class Context(object):
                     pts = dp.download((total, 4), np.float64)
             o = np.lexsort((ef, np.repeat(np.arange(n * N), cnt.ravel().astype(np.int64))))
             return cnt, ef[o], et[o], pts[o]
+        return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+
+    # the per-piece table of `contour_pieces`: one record per connected piece of a contour
+    PIECE_DTYPE = np.dtype([('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),
+                            ('length', np.float64), ('area', np.float64), ('row_min', np.float64), ('row_max', np.float64)])
+
+    def set_cpiece_workspace(self, nbytes):
+        """cap, in bytes, on the edge tables K13 builds for one group of ranges (xc_set_cpiece_workspace; default 1 GiB; one range
+        is always allowed; the result does not depend on it)"""
+        self._check(self.lib.xc_set_cpiece_workspace(self.handle, int(nbytes)))
+
+    def last_cpiece_profile(self):
+        """device times of the last `contour_pieces` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
+        reduce_ms, rounds, groups)"""
+        ms = (C.c_double * 4)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cpiece_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], reduce_ms=ms[3], rounds=r.value, groups=g.value)
+
+    def contour_pieces(self, q, contours, ycoord, xcoord, radius=0.0, period=None):
+        """The connected pieces of every contour and their statistics (K13, xc_contour_pieces_dev, on the device records of K12,
+        xc_contour_segments[_periodic]_dev: the segment records are never downloaded).  q, contours, ycoord, xcoord, radius and
+        period as for `contour_lengths` (period not None: X is a ring).  Returns (piece_count uint64 (nslab, N), table): `table`
+        a structured array (PIECE_DTYPE) of all pieces packed by (slab, contour) -- range (s, k) starts at the exclusive scan of
+        piece_count --, each range sorted by first_edge (unique there): the order of the polylines of `join_segments`.
+          first_edge  the smallest e_from of the piece;  nseg  its segments;  closed  a ring;  winding  of a ring on a periodic plane;
+          length  the sum of K10's segment lengths (times radius), 0.0 for a piece of coincident-end segments only;
+          area  S = 1/2 sum (Ya' + Yb') (Xa - Xb), Y' = sin(Y) and S radius^2 when radius > 0; NaN for an open piece;
+          row_min, row_max  the extent in index-space rows."""
+        q = _stack_in(q)
+        if len(q.shape) != 3:
+            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
+        nslab, ny, nx = q.shape
+        contours = _contig(contours, np.float64)
+        per_slab = contours.ndim == 2
+        if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
+            raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
+        N = contours.shape[-1]
+        _check_ascending(contours, 'xc_contour_pieces')
+        ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
+        if ycoord.shape != (ny,) or xcoord.shape != (nx,):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_pieces: coordinates of length (%d, %d) for a (%d, %d) plane'
+                                   % (ycoord.size, xcoord.size, ny, nx))
+        if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_pieces: coordinates must be finite')
+        radius = float(radius)
+        periodic = period is not None
+        if periodic:
+            period = _check_period(period, xcoord, 'xc_contour_pieces')
+        fseg = self.lib.xc_contour_segments_periodic_dev if periodic else self.lib.xc_contour_segments_dev
+        dt = self.PIECE_DTYPE
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
+            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+            with self._temporaries(([] if qp else [qb]) + [cb, ycoord, xcoord], [n * N * 8, n * N * 8]) as bufs:
+                dc, dy, dx, dn, dpc = bufs[-5:]
+                head = (self.handle, qp or bufs[0].ptr, dtype_code(q.dtype), n, ny, nx, dc.ptr, N, 1 if per_slab else 0)
+                rc = fseg(*head, 0, dn.ptr, None, None, None)
+                if rc not in (XC_OK, 1):
+                    self._check(rc)
+                total = int(dn.download((n, N), np.uint64).sum())
+                if total == 0:
+                    return np.zeros((n, N), dtype=np.uint64), np.empty(0, dtype=dt)
+                # the segment records, and one piece record per segment at most: six 8-byte columns, then two 4-byte ones
+                with self._temporaries([], [total * 8, total * 8, total * 32, total * 56]) as (df, dto, dp, drec):
+                    self._check(fseg(*head, total, dn.ptr, df.ptr, dto.ptr, dp.ptr))
+                    col = [drec.ptr + k * total * 8 for k in range(6)]          # first_edge, nseg, length, area, row_min, row_max
+                    i32 = [drec.ptr + 48 * total, drec.ptr + 52 * total]          # closed, winding
+                    rc = self.lib.xc_contour_pieces_dev(self.handle, n * N, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0,
+                                                        dy.ptr, dx.ptr, period if periodic else 0.0, radius, total, dpc.ptr,
+                                                        col[0], col[1], i32[0], i32[1], col[2], col[3], col[4], col[5])
+                    self._check(rc)
+                    pc = dpc.download((n, N), np.uint64)
+                    npiece = int(pc.sum())
+                    out = np.empty(npiece, dtype=dt)
+                    for name, at, t in (('first_edge', col[0], np.int64), ('nseg', col[1], np.int64), ('length', col[2], np.float64),
+                                        ('area', col[3], np.float64), ('row_min', col[4], np.float64), ('row_max', col[5], np.float64),
+                                        ('closed', i32[0], np.int32), ('winding', i32[1], np.int32)):
+                        out[name] = drec.download((npiece,), t, offset_bytes=at - drec.ptr)
+            o = np.lexsort((out['first_edge'], np.repeat(np.arange(n * N), pc.ravel().astype(np.int64))))
+            return pc, out[o]
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):

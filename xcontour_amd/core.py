@@ -826,6 +826,72 @@ class Contour2D(object):
             return out, lb.wrap(lvls.reshape(tuple(lshape) + nw), dims, c, 'level', data)
         return out
 
+    # ------------------------------------------------------------------ contour pieces
+    PIECE_FIELDS = [('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),
+                    ('length', np.float64), ('area', np.float64), ('y_min', np.float64), ('y_max', np.float64)]
+
+    def cal_contour_pieces(self, contours, tracer=None, latlon=False, periodic=False):
+        """
+        The connected pieces of every contour, one record each, computed on the GPU (K12's segments joined and reduced on
+        the device, K13, xc_contour_pieces_dev): what the reference's scripts get by tracing a level with skimage and looping
+        over the polylines (tests/test_clength.py: contour_length(seg) per piece; tests/test_breaking.py: the largest contour
+        round the pole; utils.contour_area).  Only the per-piece table crosses to the host.
+
+        `contours`, the coordinates (float32 cast; float32 radians with latlon=True), `periodic` and the order of the levels
+        are handled exactly as in cal_contour_lengths, so the lengths of a level's pieces add up to that method's value.  A
+        piece is a ring, or an open polyline that starts and ends on the plane's edge or beside a NaN cell.
+
+        Returns, per level, a numpy structured array with one row per piece, in the order of
+        find_contours(..., return_closed=True) (by the smallest grid-edge id the piece touches):
+          first_edge  that id;  nseg  the piece's segments;  closed  True for a ring;
+          winding  of a ring on a periodic plane: +1 / -1 when it goes round the ring of columns, else 0;
+          length   Cartesian, or great-circle arcs times Rearth with latlon=True;
+          area     S = 1/2 sum over the directed segments a -> b of (Ya' + Yb') (Xa - Xb), with Y' = Y, or Y' = sin(Y) and
+                   S Rearth^2 with latlon=True (the shoelace formula on the equal-area plane); NaN for an open piece.  For a
+                   ring with winding 0, |S| is the enclosed area (utils.contour_area of its vertices), and S > 0 where the
+                   ring encloses values above the level when both coordinates ascend (each descending coordinate flips the
+                   sign).  For a ring with winding != 0, S is the signed area between the ring and the line Y' = 0: on the
+                   sphere the polar cap it bounds measures 2 pi Rearth^2 -/+ S;
+          y_min, y_max  the piece's extent along the equivalent dim: its smallest / largest index-space row mapped with
+                   np.interp onto that coordinate as given (swapped where the coordinate descends).
+        Unlike find_contours, a piece whose segments all have coincident end points (fewer than two distinct vertices) is
+        NOT dropped: it stays, with length 0.  The result is out[k] when the tracer has no leading dims, else out[slab][k]
+        with the leading dims flattened in the tracer's order.  A NaN level, or a level without segments, gives an empty array.
+        Every field is bit-reproducible.
+        """
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        data = self.tracer if tracer is None else tracer
+        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
+        for d in (self.dimEqV, self._xdim):
+            if d not in dcoords:
+                raise Exception('cal_contour_pieces needs coordinate values for the plane dim %s' % d)
+        fdef = []
+        for d in (self.dimEqV, self._xdim):
+            v = np.asarray(dcoords[d]).astype(np.float32)                      # as cal_contour_lengths (core.py:1003-1004)
+            fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
+        period = self._x_period(periodic, v, latlon, 'cal_contour_pieces')
+        q, lead, lshape, coords = self._plane(data)
+        q = self._float(q)
+        nslab = q.shape[0]
+        bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
+        N = bs.shape[1]
+        pc, tab = self.ctx.contour_pieces(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
+        yg = np.asarray(dcoords[self.dimEqV], dtype=np.float64)
+        rec = np.empty(tab.size, dtype=self.PIECE_FIELDS)
+        for f in ('first_edge', 'nseg', 'closed', 'winding', 'length', 'area'):
+            rec[f] = tab[f]
+        if tab.size:
+            ya, yb = np.interp(tab['row_min'], np.arange(yg.size), yg), np.interp(tab['row_max'], np.arange(yg.size), yg)
+            rec['y_min'], rec['y_max'] = np.minimum(ya, yb), np.maximum(ya, yb)
+        poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
+        out = [[None] * N for _ in range(nslab)]
+        for s in range(nslab):
+            for j in range(N):                                   # j: the sorted level; order[s, j]: where the caller put it
+                r = s * N + j
+                out[s][int(order[s, j])] = rec[poff[r]:poff[r + 1]].copy()
+        return out if lead else out[0]
+
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):
         """

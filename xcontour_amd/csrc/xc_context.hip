@@ -212,6 +212,8 @@ int xc_destroy(xc_ctx* ctx)
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->big) (void)hipFree(ctx->big);
+    if (ctx->cpiece_ws) (void)hipFree(ctx->cpiece_ws);
+    if (ctx->cpiece_acc) (void)hipFree(ctx->cpiece_acc);
     if (ctx->ones) (void)hipFree(ctx->ones);
     for (int i = 0; i < 2; ++i) if (ctx->mmnext[i]) (void)hipFree(ctx->mmnext[i]);
     if (ctx->ev_hist0) (void)hipEventDestroy(ctx->ev_hist0);

@@ -1,0 +1,549 @@
+// K13 -- the connected PIECES of the contours and their statistics (gfx950), from K12's segment records on the device.
+//
+// The reference's scripts work on pieces: tests/test_breaking.py keeps "the largest contour that encircles the pole", tests/test_clength.py
+// sums contour_length(seg) piece by piece, utils.contour_area (utils.py:537-561) measures one.  Build-defined: a piece is a connected chain
+// of segments under "next(i) is the segment of the same range whose e_from == e_to[i]" (xc_join.cpp): a ring, or an open polyline headed
+// by a segment without a predecessor.  Only the per-piece table leaves the device.
+//
+// Input: count[nrange], e_from, e_to, pts as xc_contour_segments[_periodic]_dev wrote them (a range = one (slab, contour)); E = 2 ny nx
+// bounds every edge id.  Labels, links and slots are 32-bit: E < 2^31 and every range has fewer than 2^31 segments (XC_EBADARG else).
+//
+// Phase A, per GROUP of consecutive ranges (as many as keep g E 4 bytes of table under the context's workspace cap, at least one; fewer
+// than 2^31 segments per group; indices are group-local):
+//   k_cp_scatter  tab[range][e_from[i]] = i (the table is -1 everywhere else), label0 = e_from, prev0 = -1, the segment's range
+//   k_cp_link     next0[i] = tab[range][e_to[i]], and prev0[next0[i]] = i: prev is the inverse of next, no second table
+//   k_cp_round    R = ceil(log2(largest count of the group)) + 1 rounds of synchronous pointer doubling on double buffers:
+//                 label' = min(label, label[next], label[prev]), next' = next[next], prev' = prev[prev].  After k rounds a label is the
+//                 smallest e_from within 2^k - 1 links either way: R rounds cover every piece, so a piece's label is the smallest e_from
+//                 it contains -- the key xc_join_segments orders polylines by.  R is fixed on the host from the counts.  After R rounds
+//                 prev is -1 on every member of an open piece (2^R links back fall off its head) and >= 0 on every member of a ring.
+//   k_cp_root     root(i) = tab[range][label]; a segment that is its own root takes the next slot of its range (one atomic per wave on
+//                 piece_count[range] where the wave lies in one range) and notes whether its piece is open
+//   k_cp_bcast    every segment copies slot and open bit from its root into the one array that outlives the group (pslot[total])
+//   k_cp_unscatter  tab[range][e_from[i]] = -1: the table is cleared once per call and handed on clean
+// The host reads piece_count (the one round trip, as in K12), scans it, and stops with 1 when the pieces exceed `capacity`.
+// Phase B, over all segments at once: k_cp_init, k_cp_reduce, k_cp_finish.  Every reduction is order-free:
+//   nseg, winding   integer atomic adds;   first_edge, row_min, row_max   integer atomic min / max (rows are non-negative doubles: their
+//                   bit patterns order like the values);   closed   the open bit, stored as 0 by any member of an open piece
+//   winding  the sum over the links i -> next(i) of +1 where c2[i] == nx and c1[next] == 0, -1 for the opposite jump.  On a ring every
+//            segment has a successor and a predecessor, an end point on the seam cell's right edge (column nx) is always followed by a
+//            start point at column 0, and a start point at column nx always follows an end point at column 0: the sum is the number of
+//            segments with c2 == nx minus the number with c1 == nx, which needs no link.  Open pieces and non-periodic planes get 0.
+//   length   K10's segment length (interp_at on the node floor(r) / floor(c), column nx of a periodic plane at xcoord[0] + period,
+//            seg_len<LATLON>; a segment whose end points coincide adds nothing), times radius once at the end
+//   area     S = 1/2 sum (Ya' + Yb') (Xa - Xb), Y' = sin(Y) on the sphere (then S radius^2), NaN for an open piece
+//   Sums: every term is added WHOLE (all 53 bits) to a fixed-point accumulator of CP_L 32-bit limbs kept in 64-bit words: a term is cut at
+//   the limb boundaries into three chunks below 2^32, each added (negated for a negative term) with one 64-bit integer atomic; a word
+//   takes 2^31 chunks before it could wrap.  The window's top sits 12 bits above a bound on one term fixed before the pass (K10's window
+//   constant for the lengths; max |Y'| times the largest cell width for the areas); bits more than 32 CP_L below the top are dropped (a
+//   function of the term alone).  k_cp_finish carries the words and rounds once, half to even: the result is the exact sum of the
+//   terms, rounded once, whatever the order of arrival.
+#include "xc_capi.h"
+#include <cmath>
+#include <vector>
+
+namespace xc {
+namespace {
+
+#include "xc_binning.h"
+#include "xc_clen_cell.h"
+
+constexpr int CP_TPB = 256;
+constexpr int CP_L = 5;                       // 32-bit limbs per accumulator: a 160-bit window, 148 bits of it below the bound
+constexpr int CP_OPEN = (int)0x80000000u;     // pslot: the piece is open
+constexpr int CP_ERR_EDGE = 1, CP_ERR_LINK = 2;
+
+// largest r in [lo, hi) with off[r] <= i (off ascending, off[lo] <= i < off[hi])
+__device__ __forceinline__ int64_t cp_range_of(const long long* __restrict__ off, int64_t lo, int64_t hi, long long i)
+{
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_scatter(int64_t n, long long s0, const long long* __restrict__ off, int64_t r0, int64_t r1, long long E,
+                  const long long* __restrict__ e_from, int* __restrict__ tab, int* __restrict__ rid, int* __restrict__ lab,
+                  int* __restrict__ prv, int* __restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int rl = (int)(cp_range_of(off, r0, r1, s0 + i) - r0);
+    const long long e = e_from[s0 + i];
+    rid[i] = rl;
+    prv[i] = -1;
+    if (e < 0 || e >= E) { lab[i] = 0x7fffffff; *err = CP_ERR_EDGE; return; }
+    lab[i] = (int)e;
+    tab[(size_t)rl * E + e] = (int)i;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_link(int64_t n, long long s0, long long E, const long long* __restrict__ e_to, const int* __restrict__ tab,
+               const int* __restrict__ rid, int* __restrict__ nxt, int* __restrict__ prv, int* __restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const long long e = e_to[s0 + i];
+    int j = -1;
+    if (e < 0 || e >= E) *err = CP_ERR_EDGE;
+    else j = tab[(size_t)rid[i] * E + e];
+    if (j >= n) j = -1;
+    nxt[i] = j;
+    if (j >= 0) prv[j] = (int)i;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_round(int64_t n, const int* __restrict__ lab, const int* __restrict__ nxt, const int* __restrict__ prv,
+                int* __restrict__ lab2, int* __restrict__ nxt2, int* __restrict__ prv2)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int a = nxt[i], b = prv[i];
+    int l = lab[i], a2 = -1, b2 = -1;
+    if (a >= 0) { const int la = lab[a]; l = la < l ? la : l; a2 = nxt[a]; }
+    if (b >= 0) { const int lb = lab[b]; l = lb < l ? lb : l; b2 = prv[b]; }
+    lab2[i] = l; nxt2[i] = a2; prv2[i] = b2;
+}
+
+// roots take their slots: root[i] (group-local) for every segment, slot[i] (with the open bit) for roots only
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_root(int64_t n, long long E, const int* __restrict__ tab, const int* __restrict__ rid, const int* __restrict__ lab,
+               const int* __restrict__ prv, int64_t r0, unsigned long long* __restrict__ piece_count, int* __restrict__ root,
+               int* __restrict__ slot)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    const bool valid = i < n;
+    int r = -1;
+    bool isroot = false;
+    if (valid) {
+        r = rid[i];
+        const int l = lab[i];
+        int t = (l >= 0 && l < E) ? tab[(size_t)r * E + l] : (int)i;
+        if (t < 0 || t >= n) t = (int)i;
+        root[i] = t;
+        isroot = t == (int)i;
+    }
+    const int rf = __builtin_amdgcn_readfirstlane(r);
+    const int lane = threadIdx.x & 63;
+    int s = 0;
+    if (__all(!valid || r == rf)) {                                   // the wave lies in one range: one atomic for all its roots
+        const unsigned long long m = __ballot(isroot);
+        if (m != 0ull) {
+            int base = 0;
+            if (lane == 0) base = (int)atomicAdd(piece_count + r0 + rf, (unsigned long long)__popcll(m));
+            base = __shfl(base, 0);
+            s = base + __popcll(m & ((1ull << lane) - 1ull));
+        }
+    } else if (isroot) {
+        s = (int)atomicAdd(piece_count + r0 + r, 1ull);
+    }
+    if (isroot) slot[i] = s | (prv[i] < 0 ? CP_OPEN : 0);
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_bcast(int64_t n, long long s0, const int* __restrict__ root, const int* __restrict__ slot, int* __restrict__ pslot)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    pslot[s0 + i] = slot[root[i]];
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_unscatter(int64_t n, long long s0, long long E, const long long* __restrict__ e_from, const int* __restrict__ rid,
+                    int* __restrict__ tab)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const long long e = e_from[s0 + i];
+    if (e >= 0 && e < E) tab[(size_t)rid[i] * E + e] = -1;
+}
+
+// the window constant of the area terms: |1/2 (Ya' + Yb') (Xa - Xb)| <= max |Y'| x the largest cell width
+__global__ __launch_bounds__(256)
+void k_cp_area_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon, int wrap,
+                      double period, int* __restrict__ c0)
+{
+    const int tid = threadIdx.x;
+    double my = 0.0, mx = 0.0;
+    for (int64_t i = tid; i < ny; i += 256) my = fmax(my, fabs(fy[i]));
+    for (int64_t i = tid; i + 1 < nx; i += 256) mx = fmax(mx, fabs(fx[i + 1] - fx[i]));
+    if (wrap && tid == 0) mx = fmax(mx, fabs(__dadd_rn(fx[0], period) - fx[nx - 1]));
+    for (int o = 32; o > 0; o >>= 1) { my = fmax(my, __shfl_xor(my, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
+    __shared__ double s_m[2][4];
+    if ((tid & 63) == 0) { s_m[0][tid >> 6] = my; s_m[1][tid >> 6] = mx; }
+    __syncthreads();
+    if (tid != 0) return;
+    my = fmax(fmax(s_m[0][0], s_m[0][1]), fmax(s_m[0][2], s_m[0][3]));
+    mx = fmax(fmax(s_m[1][0], s_m[1][1]), fmax(s_m[1][2], s_m[1][3]));
+    if (latlon) my = 1.0;
+    c0[0] = det_c0_from_bound(1.0000001 * my * mx);
+}
+
+// the top exponent of the window from a window constant of det_c0_from_bound
+__device__ __forceinline__ int cp_top(int c0) { return c0 - (1023 + 52 - (53 - kDetPrecBits)); }
+
+// one term, whole, into the CP_L words of its accumulator (limb j counts units of 2^(top - 32 (j + 1)))
+__device__ __forceinline__ void cp_add(unsigned long long* __restrict__ acc, int* __restrict__ flag, int bit, double v, int top)
+{
+    const unsigned bh = (unsigned)__double2hiint(v), bl = (unsigned)__double2loint(v);
+    const int Eb = (int)((bh >> 20) & 0x7ffu);
+    if (Eb == 2047) { atomicOr(flag, bit); return; }
+    if (Eb == 0) return;                                                   // zeros and denormals lie under every window
+    unsigned long long m = ((unsigned long long)((bh & 0xfffffu) | 0x100000u) << 32) | bl;
+    const bool neg = (bh >> 31) != 0u;
+    int sh = (Eb - 1075) - (top - 32 * CP_L);                              // bits between m's last bit and the window's bottom
+    if (sh < 0) {
+        if (sh <= -53) return;
+        m >>= -sh; sh = 0;
+    }
+    const int k = sh >> 5, s = sh & 31;
+    const unsigned long long lo = m << s, hi = s ? m >> (64 - s) : 0ull;
+    const unsigned long long c[3] = {lo & 0xffffffffull, lo >> 32, hi};
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        if (c[t] == 0ull) continue;
+        const int j = CP_L - 1 - k - t;
+        if (j < 0) { atomicOr(flag, bit); continue; }                      // above the window: the term broke its bound
+        atomicAdd(acc + j, neg ? (unsigned long long)(-(long long)c[t]) : c[t]);
+    }
+}
+
+// the words of an accumulator (signed sums of chunks), carried and converted ONCE: round half to even
+__device__ __forceinline__ double cp_to_double(const unsigned long long* __restrict__ acc, int top)
+{
+    long long w[CP_L];
+#pragma unroll
+    for (int j = 0; j < CP_L; ++j) w[j] = (long long)acc[j];
+#pragma unroll
+    for (int j = CP_L - 1; j > 0; --j) { const long long c = w[j] >> 32; w[j] -= c << 32; w[j - 1] += c; }
+    const bool neg = w[0] < 0;
+    if (neg) {
+        long long borrow = 0;
+#pragma unroll
+        for (int j = CP_L - 1; j >= 0; --j) {
+            long long t = -w[j] - borrow; borrow = 0;
+            if (j > 0 && t < 0) { t += 1ll << 32; borrow = 1; }
+            w[j] = t;
+        }
+    }
+    constexpr int ND = CP_L + 1;                                           // 32-bit digits: the top word gives two
+    unsigned long long d[ND];
+    d[0] = (unsigned long long)w[0] >> 32; d[1] = (unsigned long long)w[0] & 0xffffffffull;
+#pragma unroll
+    for (int j = 1; j < CP_L; ++j) d[j + 1] = (unsigned long long)w[j];
+    int first = -1;
+#pragma unroll
+    for (int i = 0; i < ND; ++i) if (first < 0 && d[i] != 0ull) first = i;
+    if (first < 0) return 0.0;
+    unsigned long long T = 0ull; int nb = 0, below = 0; bool sticky = false;
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+        const unsigned long long D = d[i];
+        if (i == first) { T = D; nb = 64 - __clzll((long long)D); below = 32 * (ND - 1 - i); }
+        else if (i > first) {
+            if (nb + 32 <= 64) { T = (T << 32) | D; nb += 32; below -= 32; }
+            else if (nb < 64) {
+                const int take = 64 - nb, rest = 32 - take;
+                T = (T << take) | (D >> rest);
+                sticky = sticky || (D & ((1ull << rest) - 1ull)) != 0ull;
+                nb = 64; below -= take;
+            } else sticky = sticky || D != 0ull;
+        }
+    }
+    int e = (top - 32 * CP_L) + below;
+    if (nb > 53) {
+        const int drop = nb - 53;
+        const unsigned long long rem = T & ((1ull << drop) - 1ull), half = 1ull << (drop - 1);
+        T >>= drop;
+        if (rem > half || (rem == half && (sticky || (T & 1ull)))) ++T;
+        e += drop;
+    }
+    const double out = ldexp((double)T, e);
+    return neg ? -out : out;
+}
+
+#define XC_CP_RECORDS long long* __restrict__ first_edge, long long* __restrict__ nseg, int* __restrict__ closed, int* __restrict__ winding, \
+                      double* __restrict__ length, double* __restrict__ area, double* __restrict__ row_min, double* __restrict__ row_max
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_init(int64_t np, XC_CP_RECORDS, unsigned long long* __restrict__ acc, int* __restrict__ flags)
+{
+    const int64_t p = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (p >= np) return;
+    first_edge[p] = 0x7fffffffffffffffll; nseg[p] = 0; closed[p] = 1; winding[p] = 0;
+    length[p] = 0.0; area[p] = 0.0;
+    row_min[p] = __longlong_as_double(0x7ff0000000000000ll); row_max[p] = 0.0;
+    flags[p] = 0;
+#pragma unroll
+    for (int j = 0; j < 2 * CP_L; ++j) acc[(size_t)p * 2 * CP_L + j] = 0ull;
+}
+
+template <bool LATLON>
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_reduce(int64_t total, const long long* __restrict__ off, int64_t nrange, const long long* __restrict__ poff,
+                 const unsigned long long* __restrict__ piece_count, const int* __restrict__ pslot,
+                 const long long* __restrict__ e_from, const double* __restrict__ pts, int64_t ny, int64_t nx, int wrap,
+                 const double* __restrict__ fy, const double* __restrict__ fx, double period, const int* __restrict__ c0,
+                 XC_CP_RECORDS, unsigned long long* __restrict__ acc, int* __restrict__ flags, int* __restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= total) return;
+    const int64_t r = cp_range_of(off, 0, nrange, i);
+    const int ps = pslot[i];
+    const unsigned long long sl = (unsigned)(ps & 0x7fffffff);
+    if (sl >= piece_count[r]) { *err = CP_ERR_LINK; return; }             // records that are no K12 output: never past the table
+    const int64_t p = poff[r] + (int64_t)sl;
+    const bool open = ps < 0;
+    const double2 a = *reinterpret_cast<const double2*>(pts + 4 * (size_t)i), b = *reinterpret_cast<const double2*>(pts + 4 * (size_t)i + 2);
+    const double r1 = a.x, c1 = a.y, r2 = b.x, c2 = b.y;
+    atomicAdd((unsigned long long*)nseg + p, 1ull);
+    atomicMin((unsigned long long*)first_edge + p, (unsigned long long)e_from[i]);
+    if (open) closed[p] = 0;
+    atomicMin((unsigned long long*)row_min + p, (unsigned long long)__double_as_longlong(fmin(r1, r2)));
+    atomicMax((unsigned long long*)row_max + p, (unsigned long long)__double_as_longlong(fmax(r1, r2)));
+    if (wrap) {
+        const double xn = (double)nx;
+        const int w = (int)(c2 == xn) - (int)(c1 == xn);
+        if (w != 0) atomicAdd(winding + p, w);
+    }
+    // index space -> coordinates: np.interp on the node floor(.)
+    auto ycd = [&](double rr) {
+        int64_t i0 = (int64_t)floor(rr);
+        i0 = i0 < 0 ? 0 : (i0 > ny - 1 ? ny - 1 : i0);
+        const int64_t i1 = i0 + 1 < ny ? i0 + 1 : ny - 1;
+        return interp_at(rr, (double)i0, fy[i0], fy[i1]);
+    };
+    const int64_t cmax = wrap ? nx : nx - 1;                               // the last node column; column nx is column 0 one period on
+    auto xat = [&](int64_t j) { return j < nx ? fx[j] : __dadd_rn(fx[0], period); };
+    auto xcd = [&](double cc) {
+        int64_t j0 = (int64_t)floor(cc);
+        j0 = j0 < 0 ? 0 : (j0 > cmax ? cmax : j0);
+        const int64_t j1 = j0 + 1 < cmax ? j0 + 1 : cmax;
+        return interp_at(cc, (double)j0, xat(j0), xat(j1));
+    };
+    const double y1 = ycd(r1), y2 = ycd(r2), x1 = xcd(c1), x2 = xcd(c2);
+    unsigned long long* pa = acc + (size_t)p * 2 * CP_L;
+    if (!(r1 == r2 && c1 == c2)) cp_add(pa, flags + p, 1, seg_len<LATLON>(x1, y1, x2, y2), cp_top(c0[0]));
+    if (!open) {
+        const double ya = LATLON ? sin(y1) : y1, yb = LATLON ? sin(y2) : y2;
+        cp_add(pa + CP_L, flags + p, 2, __dmul_rn(0.5, __dmul_rn(__dadd_rn(ya, yb), __dsub_rn(x1, x2))), cp_top(c0[1]));
+    }
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_finish(int64_t np, XC_CP_RECORDS, const unsigned long long* __restrict__ acc, const int* __restrict__ flags,
+                 const int* __restrict__ c0, double radius)
+{
+    const int64_t p = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (p >= np) return;
+    const int fl = flags[p], cl = closed[p];
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    double len = cp_to_double(acc + (size_t)p * 2 * CP_L, cp_top(c0[0]));
+    if (radius > 0.0) len = __dmul_rn(len, radius);
+    length[p] = (fl & 1) ? qnan : len;
+    double s = qnan;
+    if (cl && !(fl & 2)) {
+        s = cp_to_double(acc + (size_t)p * 2 * CP_L + CP_L, cp_top(c0[1]));
+        if (radius > 0.0) s = __dmul_rn(s, __dmul_rn(radius, radius));
+    }
+    area[p] = s;
+    if (!cl) winding[p] = 0;
+}
+#undef XC_CP_RECORDS
+
+inline unsigned cp_blocks(int64_t n) { return (unsigned)((n + CP_TPB - 1) / CP_TPB); }
+
+}  // namespace
+
+// One xc_contour_pieces_dev call.  Waits for the stream twice: for K12's counts (they size the groups and fix the rounds) and for the
+// piece counts (they decide on the host whether the records fit).
+int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                          int64_t ny, int64_t nx, int periodic, const double* ycoord, const double* xcoord, double period, double radius,
+                          int64_t capacity, uint64_t* piece_count, int64_t* first_edge, int64_t* nseg, int32_t* closed, int32_t* winding,
+                          double* length, double* area, double* row_min, double* row_max)
+{
+    if (!count || !piece_count || !ycoord || !xcoord || nrange < 1 || ny < 1 || nx < 1 || capacity < 0)
+        return fail(ctx, XC_EBADARG, "xc_contour_pieces: bad arguments");
+    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_pieces: radius must be >= 0");
+    if (periodic && (!std::isfinite(period) || period == 0.0 || nx < 2))
+        return fail(ctx, XC_EBADARG, "xc_contour_pieces: a periodic plane needs a finite, non-zero period and nx >= 2");
+    if (capacity > 0 && (!first_edge || !nseg || !closed || !winding || !length || !area || !row_min || !row_max))
+        return fail(ctx, XC_EBADARG, "xc_contour_pieces: capacity > 0 needs the record arrays");
+    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_pieces: plane too large for 32-bit labels (2 ny nx < 2^31)");
+    const long long E = 2 * ny * nx;
+    const int wrap = periodic ? 1 : 0, latlon = radius > 0.0;
+    for (int k = 0; k < 4; ++k) ctx->cpiece_ms[k] = 0.f;
+    ctx->cpiece_rounds = 0; ctx->cpiece_groups = 0;
+
+    std::vector<uint64_t> hc((size_t)nrange);
+    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(piece_count, 0, (size_t)nrange * 8, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<long long> off((size_t)nrange + 1);
+    off[0] = 0;
+    for (int64_t r = 0; r < nrange; ++r) {
+        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_pieces: a range of 2^31 or more segments");
+        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
+    }
+    const long long total = off[(size_t)nrange];
+    if (total == 0) return XC_OK;
+    if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, "xc_contour_pieces: segments without their records");
+
+    // groups of consecutive ranges [r0, r1): the table rows fit the cap (one range always does), fewer than 2^31 segments
+    struct Group { int64_t r0, r1; };
+    std::vector<Group> groups;
+    int64_t gmax = 1; long long nmax = 0;
+    {
+        int64_t rows_cap = (int64_t)(ctx->cpiece_cap / ((size_t)E * 4));
+        if (rows_cap < 1) rows_cap = 1;
+        int64_t r = 0;
+        while (r < nrange) {
+            while (r < nrange && hc[(size_t)r] == 0) ++r;                  // empty ranges in front of a group cost no table row
+            if (r >= nrange) break;
+            int64_t r1 = r + 1;
+            while (r1 < nrange && r1 - r < rows_cap && off[(size_t)r1 + 1] - off[(size_t)r] < (1ll << 31) - 1) ++r1;
+            while (r1 - 1 > r && hc[(size_t)r1 - 1] == 0) --r1;            // ... nor behind it
+            groups.push_back({r, r1});
+            if (r1 - r > gmax) gmax = r1 - r;
+            if (off[(size_t)r1] - off[(size_t)r] > nmax) nmax = off[(size_t)r1] - off[(size_t)r];
+            r = r1;
+        }
+    }
+    // workspace: off | poff | c0[2], err | pslot[total] | tab[gmax][E] | rid[nmax] | label, next, prev x 2 [nmax]
+    const size_t b_off = al((size_t)(nrange + 1) * 8), b_small = 256, b_slot = al((size_t)total * 4);
+    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + b_slot + b_tab + 7 * b_n));
+    char* ws = (char*)ctx->cpiece_ws;
+    long long* d_off = (long long*)ws;
+    long long* d_poff = (long long*)(ws + b_off);
+    int* d_c0 = (int*)(ws + 2 * b_off);
+    int* d_err = d_c0 + 2;
+    int* pslot = (int*)(ws + 2 * b_off + b_small);
+    int* tab = (int*)((char*)pslot + b_slot);
+    int* rid = (int*)((char*)tab + b_tab);
+    int* buf[6];
+    for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+
+    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
+    std::vector<std::pair<hipEvent_t, int>> marks;
+    auto mark = [&](int kind) {
+        if (!ctx->timing) return;
+        hipEvent_t ev;
+        if (hipEventCreate(&ev) != hipSuccess) return;
+        (void)hipEventRecord(ev, ctx->stream);
+        marks.push_back({ev, kind});
+    };
+    auto settle = [&]() {
+        for (size_t k = 1; k < marks.size(); ++k) {
+            float ms = 0.f;
+            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->cpiece_ms[marks[k].second] += ms;
+        }
+        for (auto& m : marks) (void)hipEventDestroy(m.first);
+        marks.clear();
+    };
+
+    mark(-1);
+    XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(d_c0, 0, b_small, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
+    mark(0);
+    int rounds_total = 0;
+    for (const Group& g : groups) {
+        const long long s0 = off[(size_t)g.r0];
+        const int64_t n = off[(size_t)g.r1] - s0;
+        uint64_t cmaxg = 1;
+        for (int64_t r = g.r0; r < g.r1; ++r) if (hc[(size_t)r] > cmaxg) cmaxg = hc[(size_t)r];
+        int R = 1;                                                         // ceil(log2(largest count)) + 1
+        while ((1ull << (R - 1)) < cmaxg) ++R;
+        const dim3 grid(cp_blocks(n)), blk(CP_TPB);
+        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
+        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
+        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
+        XC_HIP(ctx, hipGetLastError());
+        mark(0);
+        for (int k = 0; k < R; ++k) {
+            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
+            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
+        }
+        XC_HIP(ctx, hipGetLastError());
+        rounds_total += R;
+        mark(1);
+        hipLaunchKernelGGL(k_cp_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, prv, g.r0, (unsigned long long*)piece_count, nxt2, lab2);
+        hipLaunchKernelGGL(k_cp_bcast, grid, blk, 0, ctx->stream, n, s0, nxt2, lab2, pslot);
+        XC_HIP(ctx, hipGetLastError());
+        mark(2);
+        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
+        XC_HIP(ctx, hipGetLastError());
+        mark(0);
+    }
+    ctx->cpiece_rounds = rounds_total; ctx->cpiece_groups = (int)groups.size();
+    // the second round trip: the piece counts (and whether the records were K12's)
+    std::vector<uint64_t> hp((size_t)nrange);
+    int herr[2] = {0, 0};
+    XC_HIP(ctx, hipMemcpyAsync(hp.data(), piece_count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (herr[0]) { settle(); return fail(ctx, XC_EBADARG, "xc_contour_pieces: an edge id outside [0, 2 ny nx)"); }
+    std::vector<long long> poff((size_t)nrange + 1);
+    poff[0] = 0;
+    for (int64_t r = 0; r < nrange; ++r) poff[(size_t)r + 1] = poff[(size_t)r] + (long long)hp[(size_t)r];
+    const long long np = poff[(size_t)nrange];
+    if (np > capacity) { settle(); return 1; }
+    XC_TRY(grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, al((size_t)np * 2 * CP_L * 8) + al((size_t)np * 4)));
+    unsigned long long* acc = (unsigned long long*)ctx->cpiece_acc;
+    int* flags = (int*)((char*)ctx->cpiece_acc + al((size_t)np * 2 * CP_L * 8));
+    mark(-1);
+    XC_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    XC_TRY(launch_clen_window(ctx, ycoord, ny, xcoord, nx, wrap ? period : 0.0, latlon, 1, d_c0));
+    hipLaunchKernelGGL(k_cp_area_window, dim3(1), dim3(256), 0, ctx->stream, ycoord, ny, xcoord, nx, latlon, wrap, period, d_c0 + 1);
+#define XC_CP_RECORDS (long long*)first_edge, (long long*)nseg, (int*)closed, (int*)winding, length, area, row_min, row_max
+    hipLaunchKernelGGL(k_cp_init, dim3(cp_blocks(np)), dim3(CP_TPB), 0, ctx->stream, (int64_t)np, XC_CP_RECORDS, acc, flags);
+    XC_HIP(ctx, hipGetLastError());
+#define XC_CP_REDUCE(LL_) hipLaunchKernelGGL((k_cp_reduce<LL_>), dim3(cp_blocks(total)), dim3(CP_TPB), 0, ctx->stream, (int64_t)total, d_off, nrange, \
+                          d_poff, (const unsigned long long*)piece_count, pslot, (const long long*)e_from, pts, ny, nx, wrap, ycoord, xcoord, \
+                          period, d_c0, XC_CP_RECORDS, acc, flags, d_err)
+    if (latlon) XC_CP_REDUCE(true); else XC_CP_REDUCE(false);
+#undef XC_CP_REDUCE
+    XC_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_cp_finish, dim3(cp_blocks(np)), dim3(CP_TPB), 0, ctx->stream, (int64_t)np, XC_CP_RECORDS, acc, flags, d_c0, radius);
+#undef XC_CP_RECORDS
+    XC_HIP(ctx, hipGetLastError());
+    mark(3);
+    XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    settle();
+    if (herr[0]) return fail(ctx, XC_EBADARG, "xc_contour_pieces: the records are not those of one xc_contour_segments call (a repeated edge id)");
+    return XC_OK;
+}
+
+}  // namespace xc
+
+// ------------------------------------------------------------------------------------ C ABI
+int xc_contour_pieces_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                          int64_t ny, int64_t nx, int periodic, const double* ycoord, const double* xcoord, double period, double radius,
+                          int64_t capacity, uint64_t* piece_count, int64_t* first_edge, int64_t* nseg, int32_t* closed, int32_t* winding,
+                          double* length, double* area, double* row_min, double* row_max)
+{
+    XC_CTX(ctx);
+    return xc::launch_contour_pieces(ctx, nrange, count, e_from, e_to, pts, ny, nx, periodic, ycoord, xcoord, period, radius, capacity,
+                                     piece_count, first_edge, nseg, closed, winding, length, area, row_min, row_max);
+}
+
+int xc_set_cpiece_workspace(xc_ctx* ctx, uint64_t bytes)
+{
+    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
+    if (bytes < 1) return xc::fail(ctx, XC_EBADARG, "xc_set_cpiece_workspace: at least one byte (one range is always allowed)");
+    ctx->cpiece_cap = (size_t)bytes;
+    return XC_OK;
+}
+
+int xc_last_cpiece_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
+{
+    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = (double)ctx->cpiece_ms[k];
+    if (rounds) *rounds = ctx->cpiece_rounds;
+    if (groups) *groups = ctx->cpiece_groups;
+    return XC_OK;
+}

@@ -94,6 +94,11 @@ struct xc_ctx {
     int last_keff_path = 0;     // last xc_keff_dev call: 0 min/max pass + histogram pass (two reads of the tracer), 1 the single-read kernel
     xc_hist_variant last_hist = {};   // last xc_hist(_dev) / xc_keff_dev call: the histogram instantiation and geometry launched (launch_three, launch_s4)
     xc_clen_geometry last_clen = {};  // last xc_contour_lengths(_dev) call: K10's launch geometry (launch_contour_lengths)
+    // K13 (xc_cpiece.hip): the cap on the edge tables of one group of ranges, the grow-only workspaces and the last call's stage times
+    size_t cpiece_cap = (size_t)1 << 30;
+    void*  cpiece_ws = nullptr;   size_t cpiece_ws_bytes = 0;    // offsets, slots, the edge tables, labels and links
+    void*  cpiece_acc = nullptr;  size_t cpiece_acc_bytes = 0;   // per-piece fixed-point accumulators
+    float  cpiece_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpiece_rounds = 0, cpiece_groups = 0;   // table, rounds, roots, reductions (xc_set_kernel_timing)
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -328,6 +333,11 @@ int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_
 int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int wrap,
                             const double* contours, int N, int contours_per_slab, int64_t capacity,
                             uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts, int64_t* out_total);
+// K13: the pieces of K12's records (device pointers) and their statistics; waits for the stream twice
+int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                          int64_t ny, int64_t nx, int periodic, const double* ycoord, const double* xcoord, double period, double radius,
+                          int64_t capacity, uint64_t* piece_count, int64_t* first_edge, int64_t* nseg, int32_t* closed, int32_t* winding,
+                          double* length, double* area, double* row_min, double* row_max);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 

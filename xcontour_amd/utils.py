@@ -50,6 +50,20 @@ def polyline_length(poly, latlon=False, Rearth=Rearth):
     return float(np.sum(2.0 * np.arcsin(np.sqrt(a))) * Rearth)
 
 
+def contour_area(verts):
+    """Area enclosed by a polygon (the reference's utils.contour_area, utils.py:537-561): `verts` an (n, 2) array of vertices
+    [j, i] (scikit-image's row, column order; a closing vertex equal to the first may be given or left out).  The shoelace sum
+    1/2 |sum_k (i_(k-1) + i_k) (j_(k-1) - j_k)|, the polygon closed from its last vertex to its first; the absolute value makes
+    it independent of the orientation."""
+    v = np.asarray(verts)
+    if v.ndim != 2 or v.shape[1] != 2:
+        raise Exception('contour_area expects an (n, 2) array of vertices')
+    if v.shape[0] == 0:
+        return 0.0
+    j0, i0 = np.roll(v[:, 0], 1), np.roll(v[:, 1], 1)
+    return abs(((i0 + v[:, 1]) * (j0 - v[:, 0])).sum()) / 2.0
+
+
 def cell_area(lat, lon, Rearth=Rearth, to_poles=True):
     """2-D float64 cell areas R^2 |sin(phi_n) - sin(phi_s)| dlambda with mid-point cell
     edges (the `rA` formula of reference utils.py:179-208; the reference builds its
