@@ -150,3 +150,49 @@ def test_two_calls_give_the_same_records(ctx):
     lv = np.linspace(-1.5, 1.5, 11)
     a, b = ctx.contour_segments(q, lv), ctx.contour_segments(q, lv)
     same_records(a, b)
+
+
+# K12 runs K10's tile walk and level search (xc_cell_walk.h, xc_levels.h): the edges K10 is pinned at (test_gpu_clen_variants.py)
+EDGE_X = [1, 62, 63, 64, 251, 252, 253, 504, 505]
+EDGE_Y = [1, 4, 5, 32, 33]
+
+
+@pytest.mark.parametrize('ncy', EDGE_Y)
+def test_tile_and_wave_edges(ctx, ncy):
+    """nx - 1 across the wave (63 cells) and tile (252) boundaries, ny - 1 across the row batches (4) and tiles (32); two slabs,
+    17 uneven levels, float32 and float64"""
+    for ncx in EDGE_X:
+        rng = np.random.default_rng(100 * ncy + ncx)
+        lv = np.sort(rng.uniform(-2.0, 2.0, 17))
+        for dt in (np.float32, np.float64):
+            q = field('random', (2, ncy + 1, ncx + 1), seed=ncx * ncy + 1).astype(dt)
+            got = check(ctx, q, lv, 'cells %dx%d %s' % (ncy, ncx, np.dtype(dt).name))
+            assert got[0].sum() > 0
+
+
+def on_and_next_to(q, lv, rng, dt):
+    """corners exactly on a level and one ulp (of the tracer dtype) to either side"""
+    S, ny, nx = q.shape
+    for s in range(S):
+        j, i = rng.integers(0, ny, 300), rng.integers(0, nx, 300)
+        v = dt(lv[rng.integers(0, lv.size, 300)])
+        q[s, j, i] = np.where(np.arange(300) % 3 == 0, v, np.where(np.arange(300) % 3 == 1, np.nextafter(v, dt(np.inf)),
+                                                                     np.nextafter(v, dt(-np.inf))))
+    return q
+
+
+@pytest.mark.parametrize('dt', [np.float32, np.float64])
+@pytest.mark.parametrize('kind', ['f32-linspace-300', 'f32-linspace-1e-4'])
+def test_equally_spaced_search_edges(ctx, kind, dt):
+    """equally spaced levels rounded through float32 (the arithmetic search and its verifying read), corners on levels and one ulp off"""
+    rng = np.random.default_rng(len(kind))
+    shape = (2, 53, 97)
+    if kind == 'f32-linspace-300':
+        lv = np.linspace(299.0, 301.0, 41).astype(np.float32).astype(np.float64)
+        base = 300.0 + 0.8 * field('random', shape, seed=1)
+    else:
+        lv = np.linspace(-1e-4, 1e-4, 33).astype(np.float32).astype(np.float64)
+        base = 0.7e-4 * field('random', shape, seed=3)
+    q = on_and_next_to(base.astype(dt), lv, rng, dt)
+    got = check(ctx, q, lv, kind)
+    assert (got[0] > 0).all()

@@ -1,7 +1,10 @@
 // The per-cell rule of the contour-length kernels, shared by K10 (xc_clen.hip: all levels of a plane) and K11 (xc_lclen.hip: one
 // level per sliding window): the segments one NaN-free cell emits for one crossed level and their lengths, added to a fixed-point
-// accumulator in LDS.  The rule itself is stated in the header of xc_clen.hip.  Included inside namespace xc { namespace { ... } }
-// after xc_binning.h.
+// accumulator in LDS.  The rule itself is stated in the header of xc_clen.hip.  Also here, because more than one kernel needs them:
+// the case index and the four edge points of a cell (cell_case, cell_edges: K10, K11 and K12's xc_cseg_cell.h), the fold of an LDS
+// accumulator into carried limbs (clen_carry, clen_carry_top: K10, K11) and the block-wide coordinate maxima behind the window
+// constants (window_maxima: k_clen_window, K13's k_cp_area_window).  Included inside namespace xc { namespace { ... } } after
+// xc_binning.h.
 #pragma once
 
 constexpr int CLEN_COPY_CELLS = 32767;      // cells one LDS copy of a block may receive (2 segments x 2^48 per cell < 2^64 per word)
@@ -39,6 +42,21 @@ __device__ __forceinline__ void add_len(unsigned long long* acc, unsigned* cnt, 
     lds_add(cnt, E == 2047 ? CLEN_FLAG | 1u : 1u);
 }
 
+// case = (ul > c) + 2 (ur > c) + 4 (ll > c) + 8 (lr > c)
+__device__ __forceinline__ int cell_case(double ul, double ur, double ll, double lr, double c)
+{
+    return (int)(ul > c) | ((int)(ur > c) << 1) | ((int)(ll > c) << 2) | ((int)(lr > c) << 3);
+}
+
+// The four edge points of a cell in index space, each one correctly rounded sub / div / add: the columns of the top and bottom
+// points, the rows of the left and right points.  (rT, cL): the cell's first row / column as doubles.
+__device__ __forceinline__ void cell_edges(double ul, double ur, double ll, double lr, double c, double rT, double cL,
+                                           double& tc, double& bc, double& lrow, double& rrow)
+{
+    tc = __dadd_rn(cL, frac_of(ul, ur, c)); bc = __dadd_rn(cL, frac_of(ll, lr, c));
+    lrow = __dadd_rn(rT, frac_of(ul, ll, c)); rrow = __dadd_rn(rT, frac_of(ur, lr, c));
+}
+
 // One NaN-free cell and one crossed level: its (up to two) segments.  (rT, rB): the cell's rows as doubles, (cL, cR) its
 // columns; (yT, yB) / (xL, xR) the coordinates of those nodes.
 template <bool LATLON>
@@ -47,11 +65,11 @@ __device__ __forceinline__ void cell_level(double ul, double ur, double ll, doub
                                            unsigned long long* acc, unsigned* cnt, int c0w)
 {
     const bool a = ul > c, b = ur > c, d = ll > c, e = lr > c;
-    const int cs = (int)a | ((int)b << 1) | ((int)d << 2) | ((int)e << 3);
+    const int cs = cell_case(ul, ur, ll, lr, c);
     const double rB = rT + 1.0, cR = cL + 1.0;
     // the four edge points in index space, then in coordinates
-    const double tc = __dadd_rn(cL, frac_of(ul, ur, c)), bc = __dadd_rn(cL, frac_of(ll, lr, c));
-    const double lr_ = __dadd_rn(rT, frac_of(ul, ll, c)), rr = __dadd_rn(rT, frac_of(ur, lr, c));
+    double tc, bc, lr_, rr;
+    cell_edges(ul, ur, ll, lr, c, rT, cL, tc, bc, lr_, rr);
     const double tx = interp_at(tc, cL, xL, xR), bx = interp_at(bc, cL, xL, xR);
     const double ly = interp_at(lr_, rT, yT, yB), ry = interp_at(rr, rT, yT, yB);
     // point ids: 0 top, 1 bottom, 2 left, 3 right
@@ -70,4 +88,46 @@ __device__ __forceinline__ void cell_level(double ul, double ur, double ll, doub
         const int u = t == 0 ? p : 1, v = t == 0 ? q : (cs == 6 ? 2 : 3);
         if (!(row(u) == row(v) && col(u) == col(v))) add_len(acc, cnt, seg_len<LATLON>(xcd(u), ycd(u), xcd(v), ycd(v)), c0w);
     }
+}
+
+// One LDS accumulator (the CLEN_WORDS words add_len adds to, and its count word) folded into carried limbs: words 1..3 give their
+// low 48 bits to their limb and the rest to the limb above, word 0 stays whole, the trash word is dropped; the count word gives its
+// count to n and its CLEN_FLAG to flag.
+__device__ __forceinline__ void clen_carry(unsigned long long (&acc)[kDetLimbsX], unsigned long long& n, unsigned& flag,
+                                           const unsigned long long* words, unsigned cntword)
+{
+#pragma unroll
+    for (int l = 0; l < kDetLimbsX; ++l) {
+        const unsigned long long x = words[l];
+        acc[l] += x & 0xffffffffffffull;
+        if (l > 0) acc[l - 1] += x >> kDetLimbBits; else acc[0] += x & ~0xffffffffffffull;
+    }
+    n += cntword & 0x0fffffffu; flag |= cntword & CLEN_FLAG;
+}
+
+// ... and after the last fold the carries once more, from the last limb up: limbs 1..3 < 2^48
+__device__ __forceinline__ void clen_carry_top(unsigned long long (&acc)[kDetLimbsX])
+{
+#pragma unroll
+    for (int l = kDetLimbsX - 1; l > 0; --l) { acc[l - 1] += acc[l] >> kDetLimbBits; acc[l] &= 0xffffffffffffull; }
+}
+
+// What the window constants are bounded by, over one block of 256 threads (every thread calls it and gets both): my = the largest
+// |fy[i + 1] - fy[i]| (YDIFF) or the largest |fy[i]|, mx = the largest |fx[i + 1] - fx[i]|, the seam cell fx[nx - 1] to
+// fx[0] + period among them when wrap.
+template <bool YDIFF>
+__device__ __forceinline__ void window_maxima(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx,
+                                              bool wrap, double period, double& my, double& mx)
+{
+    const int tid = threadIdx.x;
+    my = 0.0; mx = 0.0;
+    for (int64_t i = tid; i + (YDIFF ? 1 : 0) < ny; i += 256) my = fmax(my, fabs(YDIFF ? fy[i + 1] - fy[i] : fy[i]));
+    for (int64_t i = tid; i + 1 < nx; i += 256) mx = fmax(mx, fabs(fx[i + 1] - fx[i]));
+    if (wrap && tid == 0) mx = fmax(mx, fabs(__dadd_rn(fx[0], period) - fx[nx - 1]));
+    for (int o = 32; o > 0; o >>= 1) { my = fmax(my, __shfl_xor(my, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
+    __shared__ double s_m[2][4];
+    if ((tid & 63) == 0) { s_m[0][tid >> 6] = my; s_m[1][tid >> 6] = mx; }
+    __syncthreads();
+    my = fmax(fmax(s_m[0][0], s_m[0][1]), fmax(s_m[0][2], s_m[0][3]));
+    mx = fmax(fmax(s_m[1][0], s_m[1][1]), fmax(s_m[1][2], s_m[1][3]));
 }

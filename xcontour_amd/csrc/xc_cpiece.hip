@@ -165,20 +165,10 @@ __global__ __launch_bounds__(256)
 void k_cp_area_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon, int wrap,
                       double period, int* __restrict__ c0)
 {
-    const int tid = threadIdx.x;
-    double my = 0.0, mx = 0.0;
-    for (int64_t i = tid; i < ny; i += 256) my = fmax(my, fabs(fy[i]));
-    for (int64_t i = tid; i + 1 < nx; i += 256) mx = fmax(mx, fabs(fx[i + 1] - fx[i]));
-    if (wrap && tid == 0) mx = fmax(mx, fabs(__dadd_rn(fx[0], period) - fx[nx - 1]));
-    for (int o = 32; o > 0; o >>= 1) { my = fmax(my, __shfl_xor(my, o)); mx = fmax(mx, __shfl_xor(mx, o)); }
-    __shared__ double s_m[2][4];
-    if ((tid & 63) == 0) { s_m[0][tid >> 6] = my; s_m[1][tid >> 6] = mx; }
-    __syncthreads();
-    if (tid != 0) return;
-    my = fmax(fmax(s_m[0][0], s_m[0][1]), fmax(s_m[0][2], s_m[0][3]));
-    mx = fmax(fmax(s_m[1][0], s_m[1][1]), fmax(s_m[1][2], s_m[1][3]));
+    double my, mx;
+    window_maxima<false>(fy, ny, fx, nx, wrap != 0, period, my, mx);
     if (latlon) my = 1.0;
-    c0[0] = det_c0_from_bound(1.0000001 * my * mx);
+    if (threadIdx.x == 0) c0[0] = det_c0_from_bound(1.0000001 * my * mx);
 }
 
 // the top exponent of the window from a window constant of det_c0_from_bound

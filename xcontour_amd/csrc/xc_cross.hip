@@ -24,6 +24,9 @@
 namespace xc {
 namespace {
 
+#include "xc_binning.h"
+#include "xc_levels.h"
+
 constexpr int CROSS_RB = 32;     // box rows per tile
 constexpr int CROSS_TPB = 256;   // threads = box columns per tile
 #ifndef XC_CROSS_GROUP
@@ -46,7 +49,7 @@ __device__ __forceinline__ int64_t pad_source(int64_t c, int64_t nx, int mode)
 template <typename T>
 __device__ __forceinline__ double load_padded(const T* __restrict__ row, int64_t c, int64_t nx, int mode)
 {
-    if (c >= nx) { c = pad_source(c, nx, mode); if (c < 0) return __longlong_as_double(0x7ff8000000000000LL); }
+    if (c >= nx) { c = pad_source(c, nx, mode); if (c < 0) return dnan(); }
     return (double)row[c];
 }
 
@@ -60,17 +63,6 @@ __device__ __forceinline__ void row_segment(const T* __restrict__ row, int64_t c
         mn = fmin(mn, v); mx = fmax(mx, v);          // fmin / fmax return the non-NaN operand
     }
 }
-
-// lane i <- lane i+1 (DPP wave_shl:1); lane 63 keeps its own value
-__device__ __forceinline__ double from_right_lane(double v)
-{
-    const unsigned long long u = __double_as_longlong(v);
-    const unsigned lo = __builtin_amdgcn_update_dpp((int)(u & 0xffffffffu), (int)(u & 0xffffffffu), 0x130, 0xf, 0xf, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp((int)(u >> 32), (int)(u >> 32), 0x130, 0xf, 0xf, false);
-    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-
-#include "xc_levels.h"
 
 template <typename TA> __device__ __forceinline__ double sqrt_like_numpy(TA a);
 // f32 area: np.sqrt rounds in f32; an f64 root rounded once more to f32 IS the correctly rounded f32 root (53 >= 2*24+2)
@@ -98,10 +90,10 @@ __device__ __forceinline__ void box_done(const double* __restrict__ cx, int N, d
         const int khi = count_below_uniform(cx, N, mx, c_first, inv_step, zlo);
         if (khi <= klo) return;                            // no level in [mn, mx): the common case on a smooth field ends here
         double w = __dmul_rn(sqrt_like_numpy<TA>(araw), fs);    // core.py:1560 (product in f64: numba types f32 * int64 as f64)
-        if (nanfill) w = __longlong_as_double(0x7ff8000000000000LL);
+        if (nanfill) w = dnan();
 #ifndef XC_CROSS_NOATOM
         if (w == w) {                                      // np.nansum skips NaN (negative or NaN area)
-            if (w < __longlong_as_double(0x7ff0000000000000LL)) { atomicAdd(&my_len[(klo) << cshift], w); atomicAdd(&my_len[(khi) << cshift], -w); }
+            if (w < dinf()) { atomicAdd(&my_len[(klo) << cshift], w); atomicAdd(&my_len[(khi) << cshift], -w); }
             else for (int t = klo; t < khi; ++t) atomicAdd(&s_dir[t], w);        // an infinite area: +inf / -inf differences would turn into NaN
         }
         if (CNT) { atomicAdd(&my_cnt[(klo) << cshift], 1u); atomicAdd(&my_cnt[(khi) << cshift], 0xffffffffu); }
@@ -116,7 +108,7 @@ __device__ __forceinline__ void box_done(const double* __restrict__ cx, int N, d
     double ck = cx[k + 1];
     if (!(ck < mx)) return;
     double w = __dmul_rn(sqrt_like_numpy<TA>(araw), fs);
-    if (nanfill) w = __longlong_as_double(0x7ff8000000000000LL);
+    if (nanfill) w = dnan();
     const bool add = (w == w);
     do {                                               // the +inf sentinel ends the scan
 #ifndef XC_CROSS_NOATOM
@@ -153,14 +145,14 @@ __device__ __forceinline__ void boxes_group(const double* __restrict__ cx, int N
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         w[i] = __dmul_rn(sqrt_like_numpy<TA>(araw[i]), fs);                             // core.py:1560
-        if (nanfill) w[i] = __longlong_as_double(0x7ff8000000000000LL);
+        if (nanfill) w[i] = dnan();
     }
 #ifndef XC_CROSS_NOATOM
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         if (cross[i]) {
             if (w[i] == w[i]) {                            // np.nansum skips NaN (negative or NaN area)
-                if (w[i] < __longlong_as_double(0x7ff0000000000000LL)) { atomicAdd(&my_len[klo[i] << cshift], w[i]); atomicAdd(&my_len[khi[i] << cshift], -w[i]); }
+                if (w[i] < dinf()) { atomicAdd(&my_len[klo[i] << cshift], w[i]); atomicAdd(&my_len[khi[i] << cshift], -w[i]); }
                 else for (int t = klo[i]; t < khi[i]; ++t) atomicAdd(&s_dir[t], w[i]);
             }
             if (CNT) { atomicAdd(&my_cnt[klo[i] << cshift], 1u); atomicAdd(&my_cnt[khi[i] << cshift], 0xffffffffu); }
@@ -189,12 +181,11 @@ void k_crossing(const TQ* __restrict__ q, int64_t ny, int64_t nx, int pad_mode,
     const int tid = threadIdx.x;
     const int64_t slab = blockIdx.y;
     const double* cs = contours + (contours_per_slab ? (size_t)slab * N : 0);
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
-    for (int k = tid; k < N; k += CROSS_TPB) s_cx[k + 1] = cs[k];
-    if (tid == 0) { s_cx[0] = -inf; s_cx[N + 1] = inf; }
+    const double inf = dinf();
     for (int k = tid; k < ncopy * np; k += CROSS_TPB) { s_len[k] = 0.0; if (CNT) s_cnt[k] = 0u; }
     for (int k = tid; k < N; k += CROSS_TPB) s_dir[k] = 0.0;
-    __syncthreads();
+    const LevelSearch ls = load_levels<CROSS_TPB>(cs, N, s_cx);                      // (its barrier covers the sums cleared above)
+    const double c_first = ls.c_first, inv_step = ls.inv_step, zlo = ls.zlo;
     // cell k of copy c sits at [k * ncopy + c] (level-major, round 4): the lanes of a wave hold `ncopy` different copies and
     // levels a few positions apart, i.e. addresses spread over ncopy * (a few) consecutive words -- distinct banks.  Rounds 1-3
     // kept the copies apart by an odd pitch (copies 0 / 3 / 6, 1 / 4 / 7 and 2 / 5 came out two banks apart) and the round-3
@@ -210,27 +201,7 @@ void k_crossing(const TQ* __restrict__ q, int64_t ny, int64_t nx, int pad_mode,
     const TQ* qs = q + (size_t)slab * ny * nx;
     const TA* as = area + (area_per_slab ? (size_t)slab * ny * nx : 0);
     const double fs = (double)s;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
-    const double c_first = s_cx[1];
-    double inv_step = (N > 1) ? (double)(N - 1) / (s_cx[N] - c_first) : 0.0;
-    if (!(inv_step > 0.0 && inv_step < inf)) inv_step = 0.0;
-    double zlo = 0.5;
-    {   // equally spaced?  (block-uniform answer) -- and how exactly: the largest distance of a level from its ideal position
-        int ok = inv_step > 0.0;
-        double dev = 0.0;
-        for (int k = tid; k < N && ok; k += CROSS_TPB) {
-            const double d = fabs((s_cx[k + 1] - c_first) * inv_step - (double)k);
-            ok = d < 0.01; dev = fmax(dev, d);
-        }
-        if (!__syncthreads_and(ok)) inv_step = 0.0;
-        for (int o = 32; o > 0; o >>= 1) dev = fmax(dev, __shfl_xor(dev, o));
-        __shared__ double s_dev[CROSS_TPB / 64];
-        if ((tid & 63) == 0) s_dev[tid >> 6] = dev;
-        __syncthreads();
-        dev = s_dev[0];
-        for (int w = 1; w < CROSS_TPB / 64; ++w) dev = fmax(dev, s_dev[w]);
-        zlo = 2.0 * dev + 1e-9;                                  // + the rounding of t itself (|t| <= ~N: 1e-13 at most)
-    }
+    const double qnan = dnan();
     int g = 0;
 
     for (int64_t tile = blockIdx.x; tile < ntj * nti; tile += bps) {
@@ -313,7 +284,7 @@ void k_crossing(const TQ* __restrict__ q, int64_t ny, int64_t nx, int pad_mode,
             if (ac >= nx) { ac = pad_source(ac, nx, pad_mode); nanfill = ac < 0; if (nanfill) ac = 0; }
             double cmn, cmx;
             {
-                const double x = pn ? qnan : (double)qs[(size_t)j0 * nx + c], xr = from_right_lane(x);
+                const double x = pn ? qnan : (double)qs[(size_t)j0 * nx + c], xr = lane_shift_keep<DPP_WAVE_SHL1>(x, x);
                 cmn = fmin(fmin(inf, x), xr); cmx = fmax(fmax(-inf, x), xr);
             }
             for (int64_t jb = j0; jb < j1; jb += B) {
@@ -332,7 +303,7 @@ void k_crossing(const TQ* __restrict__ q, int64_t ny, int64_t nx, int pad_mode,
 #pragma unroll
                         for (int i = 0; i < G; ++i) {
                             const int b = b0 + i;
-                            const double x = pn ? qnan : (double)v[b], xr = from_right_lane(x);
+                            const double x = pn ? qnan : (double)v[b], xr = lane_shift_keep<DPP_WAVE_SHL1>(x, x);
                             const double rmn = fmin(fmin(inf, x), xr), rmx = fmax(fmax(-inf, x), xr);
                             mnb[i] = fmin(cmn, rmn); mxb[i] = fmax(cmx, rmx);
                             cmn = rmn; cmx = rmx;
@@ -345,7 +316,7 @@ void k_crossing(const TQ* __restrict__ q, int64_t ny, int64_t nx, int pad_mode,
 #pragma unroll
                 for (int b = 0; b < B; ++b) {
                     if (jb + b >= j1) break;                          // wave-uniform
-                    const double x = pn ? qnan : (double)v[b], xr = from_right_lane(x);
+                    const double x = pn ? qnan : (double)v[b], xr = lane_shift_keep<DPP_WAVE_SHL1>(x, x);
                     const double rmn = fmin(fmin(inf, x), xr), rmx = fmax(fmax(-inf, x), xr);
                     const double mn = fmin(cmn, rmn), mx = fmax(cmx, rmx);
                     cmn = rmn; cmx = rmx;

@@ -14,8 +14,7 @@
 // Layout: segments packed by (slab, level): range (s, k) = [off[s N + k], off[s N + k + 1]), off the exclusive scan of the counts.  The
 // order INSIDE a range is unspecified (it depends on the order in which a block's lanes take their slots).
 //
-// Two passes over K10's launch geometry (tiles of 32 x 252 cells, lanes along X, the right neighbour by DPP, count_below(_uniform),
-// level groups of XC_CSEG_GROUP_LEVELS over gridDim.z; grid (bps, nslab, groups), a block walks the tiles blockIdx.x, + bps, ...):
+// Two passes over K10's tile walk and launch geometry (xc_cell_walk.h; level groups of XC_CSEG_GROUP_LEVELS over gridDim.z):
 //   count  every block counts its segments per level in LDS (ds_add_u32) and writes them: part[slab][block][level];
 //   k_cseg_sum   per (slab, level): the blocks' counts -> each block's offset inside the range, and the range's count;
 //   k_cseg_scan  the exclusive scan of the range counts -> off[nslab N + 1];
@@ -31,10 +30,9 @@
 // per (slab, level) every edge still starts at most one segment and ends at most one.  The result is what the plain kernel returns
 // for the plane with column 0 appended as column nx -- pts bit for bit -- with every edge id folded from that plane's numbering to
 // the ring's: (kind, r, c) over nx + 1 columns -> 2 (r nx + (c mod nx)) + kind.  nx >= 2; Y never wraps.
-// Kernels k_ring_seg<TQ, EMIT>; k_cseg is the same code with the wrap compiled out.
-// Mapping: tiles cover nx cell columns, and the lane whose column is nx -- the right neighbour of the seam cell's lane, a cell lane
-// or the wave's halo lane 63 -- loads node column 0, so the seam cell takes its right corners by the same DPP shift as every other.
-#include "xc_internal.h"
+// Kernels k_ring_seg<TQ, EMIT>; k_cseg is the same code with the wrap compiled out.  Mapping: the seam rule of xc_cell_walk.h; what
+// K12 adds is above: the seam cell's edge ids (rwrap) and cR = nx, which is cL + 1 as for every other cell.
+#include "xc_capi.h"
 #include <cmath>
 
 namespace xc {
@@ -42,17 +40,16 @@ namespace {
 
 #include "xc_binning.h"
 #include "xc_levels.h"
+#include "xc_cell_walk.h"
 #include "xc_clen_cell.h"
 #include "xc_cseg_cell.h"
 
-constexpr int CSEG_RB = 32;                 // cell rows per tile            (K10's tile)
-constexpr int CSEG_TPB = 256;               // threads per block
-constexpr int CSEG_W = 252;                 // cell columns per tile: 4 waves x 63 cells
 constexpr int64_t CSEG_MAX_TILES = 1 << 17; // tiles per block at most: 2^17 x 32 x 252 cells x 2 segments < 2^32
 
-// LDS of a block (dynamic, 16-byte aligned carve): s_dev[4] | s_cx[G + 2] (-inf, the group's levels, +inf) | s_base[G] | s_cur[G]
-constexpr size_t cseg_lds(int G) { return (size_t)(4 + G + 2) * 8 + (size_t)G * 8 + (size_t)G * 4 + 16; }
-static_assert(cseg_lds(XC_CSEG_GROUP_LEVELS) <= 48 * 1024, "a level group must fit 48 KB of LDS");
+// LDS of a block (dynamic, 16-byte aligned carve): s_cx[G + 2] (-inf, the group's levels, +inf) | s_base[G] | s_cur[G]; load_levels
+// adds 32 static bytes
+constexpr size_t cseg_lds(int G) { return (size_t)(G + 2) * 8 + (size_t)G * 8 + (size_t)G * 4 + 16; }
+static_assert(cseg_lds(XC_CSEG_GROUP_LEVELS) + 32 <= 48 * 1024, "a level group must fit 48 KB of LDS");
 
 #define XC_CSEG_PARAMS const TQ* __restrict__ q, int64_t ny, int64_t nx, const double* __restrict__ contours, int N, int contours_per_slab, \
                         int G, int64_t ntj, int64_t nti, int bps, unsigned* __restrict__ part,                                            \
@@ -72,109 +69,46 @@ void cseg_pass(XC_CSEG_PARAMS)
     const int tid = threadIdx.x;
     const int64_t slab = blockIdx.y;
     const int g0 = blockIdx.z * G, ng = (N - g0 < G) ? N - g0 : G;
-    double* s_dev = sm;                                                                   // [4]
-    double* s_cx = sm + 4;                                                                // [ng + 2]
+    double* s_cx = sm;                                                                    // [ng + 2]
     unsigned long long* s_base = (unsigned long long*)(s_cx + ng + 2);                    // [ng]
     unsigned* s_cur = (unsigned*)(s_base + ng);                                           // [ng]
     const double* cs = contours + (contours_per_slab ? (size_t)slab * N : 0) + g0;
-    const double inf = __longlong_as_double(0x7ff0000000000000LL);
     const size_t pb = ((size_t)slab * bps + blockIdx.x) * N + g0;                         // this block's row of part / part_off
-    for (int k = tid; k < ng; k += CSEG_TPB) {
-        s_cx[k + 1] = cs[k];
+    for (int k = tid; k < ng; k += WALK_TPB) {
         s_cur[k] = 0u;
         if constexpr (EMIT) s_base[k] = (unsigned long long)off[(size_t)slab * N + g0 + k] + part_off[pb + k];
     }
-    if (tid == 0) { s_cx[0] = -inf; s_cx[ng + 1] = inf; }
-    __syncthreads();
-    const double c_first = s_cx[1];
-    double inv_step = (ng > 1) ? (double)(ng - 1) / (s_cx[ng] - c_first) : 0.0;
-    if (!(inv_step > 0.0 && inv_step < inf)) inv_step = 0.0;
-    double zlo = 0.5;
-    {   // equally spaced levels?  (block-uniform answer, as in K10) -- and how far the levels sit from their ideal positions
-        int ok = inv_step > 0.0;
-        double dev = 0.0;
-        for (int k = tid; k < ng && ok; k += CSEG_TPB) {
-            const double d = fabs((s_cx[k + 1] - c_first) * inv_step - (double)k);
-            ok = d < 0.01; dev = fmax(dev, d);
-        }
-        if (!__syncthreads_and(ok)) inv_step = 0.0;
-        for (int o = 32; o > 0; o >>= 1) dev = fmax(dev, __shfl_xor(dev, o));
-        if ((tid & 63) == 0) s_dev[tid >> 6] = dev;
-        __syncthreads();
-        dev = fmax(fmax(s_dev[0], s_dev[1]), fmax(s_dev[2], s_dev[3]));
-        zlo = 2.0 * dev + 1e-9;
-    }
-    const TQ* qs = q + (size_t)slab * ny * nx;
-    const int64_t ncx = WRAP ? nx : nx - 1, ncy = ny - 1, nx2 = 2 * nx;
-    const int lane = tid & 63, wave = tid >> 6;
-
-    for (int64_t tile = blockIdx.x; tile < ntj * nti; tile += bps) {
-        const int64_t tj = tile / nti, ti = tile - tj * nti;
-        const int64_t i = ti * CSEG_W + wave * 63 + lane;                                // this lane's cell column
-        const int64_t j0 = tj * CSEG_RB, j1 = (j0 + CSEG_RB < ncy) ? j0 + CSEG_RB : ncy;
-        const bool cell = lane < 63 && i < ncx;                                          // lanes without a cell still load and shift
-        int64_t c = i < nx - 1 ? i : nx - 1;                                             // corner column loaded by this lane
-        if constexpr (WRAP) { if (i == nx) c = 0; }                                      // column nx is column 0
-        const double cL = (double)c;
-        const int64_t rwrap = (WRAP && i == nx - 1) ? nx2 : 0;                           // the seam cell's right edge: V(r, 0)
-        double ul = (double)qs[(size_t)j0 * nx + c];
-        double ur = lane_shift_keep<DPP_WAVE_SHL1>(ul, ul);
-        constexpr int B = 4;
-        for (int64_t jb = j0; jb < j1; jb += B) {
-            TQ v[B];
-#pragma unroll
-            for (int b = 0; b < B; ++b) {                                                // all loads of the batch in flight together
-                const int64_t jj = (jb + b < j1) ? jb + b : j1 - 1;
-                v[b] = qs[(size_t)(jj + 1) * nx + c];
+    const LevelSearch ls = load_levels<WALK_TPB>(cs, ng, s_cx);                            // (its barrier covers the cursors set above)
+    const int64_t nx2 = 2 * nx;
+    int64_t rwrap;                                                                        // the seam cell's right edge: V(r, 0)
+    cell_walk<TQ, WRAP>(q + (size_t)slab * ny * nx, ny, nx, ntj, nti, bps, s_cx, ng, ls,
+        [&](int64_t i, int64_t) { rwrap = (WRAP && i == nx - 1) ? nx2 : 0; },
+        [&](int k, int64_t r, int64_t c, double ul, double ur, double ll, double lr) {
+            const double lv = s_cx[k + 1];
+            if constexpr (EMIT) {
+                const unsigned long long base = s_base[k];
+                cseg_cell(ul, ur, ll, lr, lv, (double)r, (double)c, 2 * (r * nx + c), nx2, rwrap,
+                          [&](int64_t ef, int64_t et, double r1, double c1, double r2, double c2) {
+                              const unsigned slot = __hip_atomic_fetch_add(s_cur + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                              const long long at = (long long)(base + slot);
+                              if (at < capacity) {
+                                  e_from[at] = ef; e_to[at] = et;
+                                  double* p = pts + 4 * (size_t)at;
+                                  p[0] = r1; p[1] = c1; p[2] = r2; p[3] = c2;
+                              }
+                          });
+            } else {
+                lds_add(s_cur + k, (unsigned)cseg_count(cell_case(ul, ur, ll, lr, lv)));
             }
-#pragma unroll
-            for (int b = 0; b < B; ++b) {
-                const int64_t r = jb + b;
-                if (r >= j1) break;                                                      // wave-uniform
-                const double ll = (double)v[b], lr = lane_shift_keep<DPP_WAVE_SHL1>(ll, ll);
-                const bool hasnan = (ul != ul) | (ur != ur) | (ll != ll) | (lr != lr);
-                if (cell && !hasnan) {
-                    const double mn = fmin(fmin(ul, ur), fmin(ll, lr)), mx = fmax(fmax(ul, ur), fmax(ll, lr));
-                    int klo, khi;
-                    if (inv_step > 0.0) {
-                        klo = count_below_uniform(s_cx, ng, mn, c_first, inv_step, zlo);
-                        khi = count_below_uniform(s_cx, ng, mx, c_first, inv_step, zlo);
-                    } else {
-                        klo = count_below(s_cx, ng, mn);
-                        khi = count_below(s_cx, ng, mx);
-                    }
-                    const int64_t hT = 2 * (r * nx + c);
-                    for (int k = klo; k < khi; ++k) {
-                        const double lv = s_cx[k + 1];
-                        if constexpr (EMIT) {
-                            const unsigned long long base = s_base[k];
-                            cseg_cell(ul, ur, ll, lr, lv, (double)r, cL, hT, nx2, rwrap,
-                                      [&](int64_t ef, int64_t et, double r1, double c1, double r2, double c2) {
-                                          const unsigned slot = __hip_atomic_fetch_add(s_cur + k, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                                          const long long at = (long long)(base + slot);
-                                          if (at < capacity) {
-                                              e_from[at] = ef; e_to[at] = et;
-                                              double* p = pts + 4 * (size_t)at;
-                                              p[0] = r1; p[1] = c1; p[2] = r2; p[3] = c2;
-                                          }
-                                      });
-                        } else {
-                            lds_add(s_cur + k, (unsigned)cseg_count(cseg_case(ul, ur, ll, lr, lv)));
-                        }
-                    }
-                }
-                ul = ll; ur = lr;
-            }
-        }
-    }
+        });
     if constexpr (!EMIT) {
         __syncthreads();
-        for (int k = tid; k < ng; k += CSEG_TPB) part[pb + k] = s_cur[k];
+        for (int k = tid; k < ng; k += WALK_TPB) part[pb + k] = s_cur[k];
     }
 }
 
 template <typename TQ, bool EMIT>
-__global__ __launch_bounds__(CSEG_TPB)
+__global__ __launch_bounds__(WALK_TPB)
 void k_cseg(XC_CSEG_PARAMS)
 {
     cseg_pass<TQ, EMIT, false>(XC_CSEG_ARGS);
@@ -182,7 +116,7 @@ void k_cseg(XC_CSEG_PARAMS)
 
 // periodic X: the ring of nx cell columns
 template <typename TQ, bool EMIT>
-__global__ __launch_bounds__(CSEG_TPB)
+__global__ __launch_bounds__(WALK_TPB)
 void k_ring_seg(XC_CSEG_PARAMS)
 {
     cseg_pass<TQ, EMIT, true>(XC_CSEG_ARGS);
@@ -252,25 +186,14 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
     const int ngroup = (N + G - 1) / G;
     if (ngroup > 65535) return fail(ctx, XC_EBADARG, "xc_contour_segments: too many contours");
     const size_t lds = cseg_lds(G);
-    const int64_t ncx = wrap ? nx : nx - 1, ncy = ny - 1;
-    const int64_t ntj = ncy > 0 ? (ncy + CSEG_RB - 1) / CSEG_RB : 0, nti = ncx > 0 ? (ncx + CSEG_W - 1) / CSEG_W : 0;
-    const int64_t ntile = ntj * nti;
-    // blocks per slab: the launch's share of ~2048 blocks, at least 8, no more than tiles, and at most CSEG_MAX_TILES tiles each
-    int64_t bps = 0;
-    if (ntile > 0) {
-        bps = 2048 / nslab;
-        if (bps < 8) bps = 8;
-        const int64_t need = (ntile + CSEG_MAX_TILES - 1) / CSEG_MAX_TILES;
-        if (bps < need) bps = need;
-        if (bps > ntile) bps = ntile;
-        if (bps > 0x7fffffff) return fail(ctx, XC_EBADARG, "xc_contour_segments: plane too large");
-    }
+    // blocks per slab: at most CSEG_MAX_TILES tiles each
+    const WalkGeometry wg = walk_geometry(ny, nx, wrap != 0, nslab, CSEG_MAX_TILES);
+    const int64_t ntj = wg.ntj, nti = wg.nti, bps = wg.bps;
+    if (bps > 0x7fffffff) return fail(ctx, XC_EBADARG, "xc_contour_segments: plane too large");
     const int64_t M = nslab * (int64_t)N;
-    const size_t a256 = 256;
-    auto up = [&](size_t b) { return (b + a256 - 1) & ~(a256 - 1); };
-    const size_t pc = up((size_t)nslab * bps * N * 4), po = up((size_t)nslab * bps * N * 8), pf = up((size_t)(M + 1) * 8);
+    const size_t pc = al((size_t)nslab * bps * N * 4), po = al((size_t)nslab * bps * N * 8), pf = al((size_t)(M + 1) * 8);
     {
-        const int rc = ensure_scratch(ctx, pc + po + pf + a256);
+        const int rc = ensure_scratch(ctx, pc + po + pf + 256);
         if (rc != XC_OK) return rc;
     }
     char* sc = (char*)ctx->scratch;
@@ -281,8 +204,8 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
 #define XC_CSEG_ARGS(TQ_) (const TQ_*)q, ny, nx, contours, N, contours_per_slab, G, ntj, nti, (int)bps, part, part_off, off, (long long)capacity, \
                           (long long*)e_from, (long long*)e_to, pts
 #define XC_CSEG(TQ_, EMIT_) do {                                                                                                      \
-        if (wrap) hipLaunchKernelGGL((k_ring_seg<TQ_, EMIT_>), grid, dim3(CSEG_TPB), lds, ctx->stream, XC_CSEG_ARGS(TQ_));                \
-        else hipLaunchKernelGGL((k_cseg<TQ_, EMIT_>), grid, dim3(CSEG_TPB), lds, ctx->stream, XC_CSEG_ARGS(TQ_));                         \
+        if (wrap) hipLaunchKernelGGL((k_ring_seg<TQ_, EMIT_>), grid, dim3(WALK_TPB), lds, ctx->stream, XC_CSEG_ARGS(TQ_));                \
+        else hipLaunchKernelGGL((k_cseg<TQ_, EMIT_>), grid, dim3(WALK_TPB), lds, ctx->stream, XC_CSEG_ARGS(TQ_));                         \
     } while (0)
     if (bps > 0) {
         if (q_dtype == XC_F64) XC_CSEG(double, false); else XC_CSEG(float, false);

@@ -1,5 +1,5 @@
 // The per-cell rule of the contour-segment kernel K12 (xc_cseg.hip): the DIRECTED segments one NaN-free cell emits for one crossed
-// level.  The rule is K10's (header of xc_clen.hip; frac_of comes from xc_clen_cell.h) with two differences: every segment has a
+// level.  The rule is K10's (header of xc_clen.hip; cell_case and cell_edges come from xc_clen_cell.h) with two differences: every segment has a
 // start and an end, in the order of skimage's _get_contour_segments (fully_connected='low'), and a segment whose two end points
 // coincide is kept (the join needs it; the facade drops the repeated vertex).  Included inside namespace xc { namespace { ... } }
 // after xc_clen_cell.h.
@@ -23,11 +23,6 @@ constexpr int CSEG_END_TBL[16] = {0, CSEG_L, CSEG_T, CSEG_L, CSEG_B, CSEG_B, CSE
                                   CSEG_R, CSEG_L, CSEG_T, CSEG_L, CSEG_R, CSEG_R, CSEG_T, 0};
 constexpr unsigned CSEG_START = cseg_pack(CSEG_START_TBL), CSEG_END = cseg_pack(CSEG_END_TBL);
 
-__device__ __forceinline__ int cseg_case(double ul, double ur, double ll, double lr, double c)
-{
-    return (int)(ul > c) | ((int)(ur > c) << 1) | ((int)(ll > c) << 2) | ((int)(lr > c) << 3);
-}
-
 // segments of a crossed cell (case 1 .. 14): two at a saddle, else one
 __device__ __forceinline__ int cseg_count(int cs) { return (cs == 6 || cs == 9) ? 2 : 1; }
 
@@ -40,10 +35,10 @@ template <typename Emit>
 __device__ __forceinline__ void cseg_cell(double ul, double ur, double ll, double lr, double c, double rT, double cL,
                                           int64_t hT, int64_t nx2, int64_t rwrap, Emit&& emit)
 {
-    const int cs = cseg_case(ul, ur, ll, lr, c);
+    const int cs = cell_case(ul, ur, ll, lr, c);
     const double rB = rT + 1.0, cR = cL + 1.0;
-    const double tc = __dadd_rn(cL, frac_of(ul, ur, c)), bc = __dadd_rn(cL, frac_of(ll, lr, c));
-    const double lrow = __dadd_rn(rT, frac_of(ul, ll, c)), rrow = __dadd_rn(rT, frac_of(ur, lr, c));
+    double tc, bc, lrow, rrow;
+    cell_edges(ul, ur, ll, lr, c, rT, cL, tc, bc, lrow, rrow);
     auto row = [&](int i) { return i == CSEG_T ? rT : i == CSEG_B ? rB : i == CSEG_L ? lrow : rrow; };
     auto col = [&](int i) { return i == CSEG_T ? tc : i == CSEG_B ? bc : i == CSEG_L ? cL : cR; };
     auto eid = [&](int i) { return i == CSEG_T ? hT : i == CSEG_B ? hT + nx2 : i == CSEG_L ? hT + 1 : hT + 3 - rwrap; };

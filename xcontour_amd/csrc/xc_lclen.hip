@@ -171,24 +171,15 @@ void lclen_window(const TQ* __restrict__ q, int64_t ny, int64_t nx, const double
                 }
             }
             __syncthreads();
-            // the waves' copies carried into thread 0's limbs (words 1..3 < 2^48 plus carries, word 0 the rest; the trash word is
-            // dropped) and cleared for the next strips
+            // the waves' copies carried into thread 0's limbs (clen_carry of xc_clen_cell.h) and cleared for the next strips
             if (tid == 0) {
                 for (int w = 0; w < nwave; ++w) {
-#pragma unroll
-                    for (int l = 0; l < kDetLimbsX; ++l) {
-                        const unsigned long long x = s_acc[w][l];
-                        m[l] += x & 0xffffffffffffull;
-                        if (l > 0) m[l - 1] += x >> kDetLimbBits; else m[0] += x & ~0xffffffffffffull;
-                    }
+                    clen_carry(m, nseg, flag, s_acc[w], s_cnt[w]);
 #pragma unroll
                     for (int l = 0; l < CLEN_WORDS; ++l) s_acc[w][l] = 0ull;
-                    const unsigned u = s_cnt[w];
-                    nseg += u & 0x0fffffffu; flag |= u & CLEN_FLAG;
                     s_cnt[w] = 0u;
                 }
-#pragma unroll
-                for (int l = kDetLimbsX - 1; l > 0; --l) { m[l - 1] += m[l] >> kDetLimbBits; m[l] &= 0xffffffffffffull; }
+                clen_carry_top(m);
             }
             __syncthreads();
         }
