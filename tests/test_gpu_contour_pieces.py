@@ -265,3 +265,67 @@ def test_c_entry_rows_and_capacity_one_short(noise):
             o = np.lexsort((fe, np.repeat(np.arange(N), pc.ravel().astype(np.int64))))
             assert np.array_equal(fe[o], tab['first_edge'])
             assert np.array_equal(rec[4].download((npiece,), np.float64)[o].view(np.int64), tab['length'].view(np.int64))
+
+
+# ------------------------------------------------------------------ one call, batches of 2 + 1 slabs, a resident tracer
+def batching_case(dt):
+    """as in test_gpu_contour_segments.py: (3, 9, 12), five levels per slab with the last above the field, the last slab all NaN"""
+    q = np.random.default_rng(31).standard_normal((3, 9, 12)).astype(dt)
+    q[2] = np.nan
+    lv = np.array([-0.8, -0.3, 0.1, 0.6, 50.0])[None, :] + 0.07 * np.arange(3)[:, None]
+    return q, lv
+
+
+def in_batches_of_two(ctx, q, call):
+    cap = ctx.max_batch_bytes
+    try:
+        ctx.max_batch_bytes = 2 * q[0].nbytes + 8
+        assert ctx._batches(3, q[0].nbytes) == [(0, 2), (2, 3)]
+        return call()
+    finally:
+        ctx.max_batch_bytes = cap
+
+
+@pytest.mark.parametrize('period', [None, 24.0])
+@pytest.mark.parametrize('dt', [np.float32, np.float64])
+def test_batches_and_a_resident_tracer_give_the_same_table(dt, period):
+    ctx = nat.default_context(0)
+    q, lv = batching_case(dt)
+    y, x = np.arange(9) * 1.5, np.arange(12) * 2.0
+    call = lambda: ctx.contour_pieces(q, lv, y, x, period=period)
+    a = call()
+    b = in_batches_of_two(ctx, q, call)
+    try:
+        ctx.keep_resident(q)
+        assert ctx.resident_ptr(q)
+        c = call()
+    finally:
+        ctx.release_resident(q)
+    pc = a[0].astype(np.int64)
+    assert (pc[:2, :4] > 0).all() and (pc[:2, 4] == 0).all() and (pc[2] == 0).all() and a[1].size == pc.sum()
+    for r, what in ((b, 'batches of 2 + 1'), (c, 'resident')):
+        assert type(r) is tuple and r[0].dtype == np.uint64 and np.array_equal(r[0], a[0]), what
+        same_table(r[1], a[1], what)
+
+
+@pytest.mark.parametrize('periodic', [False, True])
+@pytest.mark.parametrize('dt', [np.float32, np.float64])
+def test_facade_in_batches_with_descending_levels(dt, periodic):
+    """find_contours and cal_contour_pieces on a (time, lat, lon) tracer, levels descending: one call against batches of 2 + 1"""
+    q, _ = batching_case(dt)
+    lat, lon = -60.0 + 15.0 * np.arange(9), 30.0 * np.arange(12)
+    cm = facade(q, lat, lon, lead=(3,))
+    lv = np.array([50.0, 0.6, 0.1, -0.3, -0.8])
+    fc = lambda: cm.find_contours(lv, return_closed=True, return_winding=True, periodic=periodic)
+    pcs = lambda: cm.cal_contour_pieces(lv, latlon=periodic, periodic=periodic)
+    (pa, ca, wa), ta = fc(), pcs()
+    (pb, cb, wb), tb = in_batches_of_two(cm.ctx, q, fc), in_batches_of_two(cm.ctx, q, pcs)
+    assert ca == cb and wa == wb
+    for s in range(3):
+        assert len(pa[s]) == len(pb[s]) == len(ta[s]) == len(tb[s]) == 5
+        for k in range(5):
+            assert len(pa[s][k]) == len(pb[s][k])
+            for u, v in zip(pa[s][k], pb[s][k]):
+                assert u.shape == v.shape and np.array_equal(np.ascontiguousarray(u).view(np.int64), np.ascontiguousarray(v).view(np.int64))
+            same_table(ta[s][k], tb[s][k], 'slab %d level %d' % (s, k))
+            assert (ta[s][k].size > 0) == (s < 2 and k > 0) and (len(pa[s][k]) > 0) == (s < 2 and k > 0)

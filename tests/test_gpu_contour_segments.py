@@ -196,3 +196,45 @@ def test_equally_spaced_search_edges(ctx, kind, dt):
     q = on_and_next_to(base.astype(dt), lv, rng, dt)
     got = check(ctx, q, lv, kind)
     assert (got[0] > 0).all()
+
+
+# ------------------------------------------------------------------ one call, batches of 2 + 1 slabs, a resident tracer
+def batching_case(dt):
+    """the smallest stack with more than one batch and an unequal last one, a seam column, and an empty range beside a full one:
+    (3, 9, 12), five levels per slab of which the last lies above the field, the last slab -- a batch of its own -- all NaN"""
+    q = field('random', (3, 9, 12), seed=31).astype(dt)
+    q[2] = np.nan
+    lv = np.array([-0.8, -0.3, 0.1, 0.6, 50.0])[None, :] + 0.07 * np.arange(3)[:, None]
+    return q, lv
+
+
+def three_ways(ctx, q, call):
+    """call() (a) as it is, (b) in batches of 2 + 1 slabs, (c) on the device mirror of `q`"""
+    a = call()
+    cap = ctx.max_batch_bytes
+    try:
+        ctx.max_batch_bytes = 2 * q[0].nbytes + 8
+        assert ctx._batches(3, q[0].nbytes) == [(0, 2), (2, 3)]
+        b = call()
+    finally:
+        ctx.max_batch_bytes = cap
+    try:
+        ctx.keep_resident(q)
+        assert ctx.resident_ptr(q)
+        c = call()
+    finally:
+        ctx.release_resident(q)
+    return a, b, c
+
+
+@pytest.mark.parametrize('periodic', [False, True])
+@pytest.mark.parametrize('dt', [np.float32, np.float64])
+def test_batches_and_a_resident_tracer_give_the_same_records(ctx, dt, periodic):
+    q, lv = batching_case(dt)
+    a, b, c = three_ways(ctx, q, lambda: ctx.contour_segments(q, lv, periodic=periodic))
+    cnt = a[0].astype(np.int64)
+    assert (cnt[:2, :4] > 0).all() and (cnt[:2, 4] == 0).all() and (cnt[2] == 0).all()
+    same_records(b, a, 'batches of 2 + 1')
+    same_records(c, a, 'resident')
+    for r in (b, c):
+        assert [v.dtype for v in r] == [v.dtype for v in a] and type(r) is tuple

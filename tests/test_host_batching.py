@@ -13,32 +13,64 @@ from xcontour_amd import labeled as lb
 S, NY, NX, N = 5, 6, 8, 4
 SLAB = NY * NX * 8                      # bytes of one float64 slab
 
-# position of `nslab` in the argument list of the entry points that take it by value (include/xcontour_hip.h)
+# position of `nslab` in the argument list of the entry points that take it by value (include/xcontour_hip.h); for
+# xc_contour_pieces_dev, which sees no slabs, the position of `nrange`
 _NSLAB_ARG = {'xc_minmax': 3, 'xc_levels': 3, 'xc_contours': 3, 'xc_grad2': 3, 'xc_crossing': 3, 'xc_crossing_dev': 3,
-              'xc_contour_lengths': 3, 'xc_contour_lengths_dev': 3, 'xc_lwa': 10, 'xc_sort_profile_batch': 8}
+              'xc_contour_lengths': 3, 'xc_contour_lengths_dev': 3, 'xc_lwa': 10, 'xc_sort_profile_batch': 8,
+              'xc_contour_lengths_periodic': 3, 'xc_contour_lengths_periodic_dev': 3,
+              'xc_local_contour_lengths': 3, 'xc_local_contour_lengths_dev': 3,
+              'xc_local_contour_lengths_periodic': 3, 'xc_local_contour_lengths_periodic_dev': 3,
+              'xc_contour_segments_dev': 3, 'xc_contour_segments_periodic_dev': 3, 'xc_contour_pieces_dev': 1}
+_K12 = ('xc_contour_segments_dev', 'xc_contour_segments_periodic_dev')
+RES = 1 << 44                           # where the stand-in's device mirror of a resident array starts
 
 
 class _Lib(object):
-    """every xc_* entry point returns XC_OK and leaves its outputs alone; compute entry points are recorded"""
+    """every xc_* entry point returns XC_OK and leaves its outputs alone; compute entry points are recorded: (name, nslab) in
+    `calls`, (name, every positional argument) in `args`; the bytes of every xc_malloc in `mallocs`.  `d2h_u64`: None -- a
+    download reads zeros --, or a callable (this library) -> the value every uint64 of the next download holds (a count download
+    of twos takes K12 / K13 into their second pass; K12's count-only call then returns 1, as the library's does).
+    `resident_base`: None -- xc_resident_lookup finds nothing --, or the host address of the one registered array, whose mirror
+    starts at RES."""
 
     def __init__(self):
-        self.calls = []
-        self._next = 1 << 40
+        self.calls, self.args, self.mallocs = [], [], []
+        self.d2h_u64 = self.resident_base = None
+        self._next = self._base = 1 << 40                            # the next allocation; the first one _take has not seen
 
     def __getattr__(self, name):
         if name == 'xc_malloc':
             return self._malloc
         if name == 'xc_memcpy_d2h':
-            return lambda h, dst, src, n: (C.memset(dst, 0, n), 0)[1]
+            return self._d2h
+        if name == 'xc_resident_lookup':
+            return self._lookup
         if name == 'xc_hist':
             return lambda h, dref: (self.calls.append((name, int(dref._obj.nslab))), 0)[1]
         if name in _NSLAB_ARG:
-            return lambda *a: (self.calls.append((name, int(a[_NSLAB_ARG[name]]))), 0)[1]
+            return lambda *a: self._record(name, a)
         return lambda *a: 0
 
+    def _record(self, name, a):
+        self.calls.append((name, int(a[_NSLAB_ARG[name]])))
+        self.args.append((name, tuple(a)))
+        return 1 if name in _K12 and a[9] == 0 and self.d2h_u64 is not None and self.d2h_u64(self) else 0
+
     def _malloc(self, h, n, pref):
+        self.mallocs.append(int(n))
         pref._obj.value = self._next
         self._next += (int(n) + 4095) & ~4095
+        return 0
+
+    def _d2h(self, h, dst, src, n):
+        C.memset(dst, 0, n)
+        v = self.d2h_u64(self) if self.d2h_u64 is not None else 0
+        if v:
+            (C.c_uint64 * (n // 8)).from_address(dst)[:] = [v] * (n // 8)
+        return 0
+
+    def _lookup(self, h, p, n, pref):
+        pref._obj.value = None if self.resident_base is None else RES + (p - self.resident_base)
         return 0
 
 
@@ -166,7 +198,7 @@ def _lazy(q):
 
 
 @pytest.mark.parametrize('method', ['minmax', 'contours', 'hist', 'grad2', 'crossing', 'crossing_strides', 'contour_lengths', 'lwa',
-                                    'sort_profile'])
+                                    'contour_segments', 'contour_pieces', 'local_contour_lengths', 'sort_profile'])
 def test_a_lazy_stack_is_read_batch_by_batch_every_slab_once_in_order(ctx, q, method):
     src, st = _lazy(q)
     levels = np.linspace(-1, 1, N)
@@ -188,6 +220,13 @@ def test_a_lazy_stack_is_read_batch_by_batch_every_slab_once_in_order(ctx, q, me
         out, want = ctx.crossing(st, levels, np.ones((NY, NX)), stride=[1, 2])[1][0], pairs
     elif method == 'contour_lengths':
         out, want = ctx.contour_lengths(st, levels, np.arange(NY, dtype=float), np.arange(NX, dtype=float))[0], pairs
+    elif method == 'contour_segments':
+        out, want = ctx.contour_segments(st, levels)[0], pairs
+    elif method == 'contour_pieces':
+        out, want = ctx.contour_pieces(st, levels, np.arange(NY, dtype=float), np.arange(NX, dtype=float))[0], pairs
+    elif method == 'local_contour_lengths':
+        ctx.max_batch_bytes = 2 * (SLAB + 4 * NWY * NWX * 8) + 8
+        out, want = ctx.local_contour_lengths(st, np.arange(NY, dtype=float), np.arange(NX, dtype=float), WIN, STR, 4)[0], pairs
     elif method == 'lwa':
         out, want = ctx.lwa(st, np.sort(q[:, :, 0], axis=1), np.arange(NY, dtype=float), np.ones(NY), 1.0)[0], one_by_one
     else:
@@ -200,3 +239,271 @@ def test_a_lazy_stack_is_read_batch_by_batch_every_slab_once_in_order(ctx, q, me
     ctx.max_batch_bytes = 8 << 30
     ctx.minmax(st)
     assert src.reads == [tuple(range(S))]
+
+
+# ------------------------------------------------------------------ the contour family (K10 periodic, K11, K12, K13)
+Y, X = np.arange(NY, dtype=float), np.arange(NX, dtype=float)
+PERIOD, RADIUS = float(NX), 2.5
+WIN, STR = (3, 4), (2, 3)                                           # K11: windows of 3 x 4 nodes every 2 rows / 3 columns
+NWY, NWX = 3, 3                                                     # ceil(6 / 2), ceil(8 / 3)
+OB = NWY * NWX * 8                                                  # bytes of one slab's windows in one K11 output
+BATCHES = [(0, 2), (2, 2), (4, 1)]                                  # (first slab, slabs) of the batches of S = 5
+F64 = nat.XC_F64
+
+
+def _per_slab_levels():
+    return np.linspace(-1, 1, N)[None, :] + 0.01 * np.arange(S)[:, None]
+
+
+def _make_resident(ctx, q):
+    """what keep_resident(q) leaves behind: batch [s0, s1) of `q` has its mirror at RES + s0 * SLAB"""
+    ctx._resident[q.ctypes.data] = q
+    ctx.lib.resident_base = q.ctypes.data
+
+
+def _take(ctx):
+    """(calls, args, mallocs, the address of every allocation) since the last _take"""
+    lib = ctx.lib
+    out = lib.calls, [a for _, a in lib.args], lib.mallocs
+    addr, at = [], lib._base
+    for n in lib.mallocs:
+        addr.append(at)
+        at += (n + 4095) & ~4095
+    lib._base = at
+    lib.calls, lib.args, lib.mallocs = [], [], []
+    return out + (addr,)
+
+
+def _where_q(q, resident, s0):
+    return (RES if resident else q.ctypes.data) + s0 * SLAB
+
+
+@pytest.mark.parametrize('period', [None, PERIOD])
+def test_contour_lengths_host_path_plain_and_periodic(ctx, q, period):
+    res = ctx.contour_lengths(q, np.linspace(-1, 1, N), Y, X, radius=RADIUS, period=period)
+    calls, args, mallocs, _ = _take(ctx)
+    name = 'xc_contour_lengths' if period is None else 'xc_contour_lengths_periodic'
+    assert calls == _seq(name, 2, 2, 1) and mallocs == []
+    mid = (RADIUS,) if period is None else (PERIOD, RADIUS)         # the period goes between xcoord and the radius
+    for a, (s0, n) in zip(args, BATCHES):
+        assert a[:8] + a[8:8 + len(mid)] == (None, q.ctypes.data + s0 * SLAB, F64, n, NY, NX, Y.ctypes.data, X.ctypes.data) + mid
+        assert a[9 + len(mid):11 + len(mid)] == (N, 0) and len(a) == 13 + len(mid)
+        assert all(type(v) is float for v in a[8:8 + len(mid)])
+    assert type(res) is tuple and len(res) == 2
+    assert res[0].shape == res[1].shape == (S, N) and res[0].dtype == np.float64 and res[1].dtype == np.uint64
+    assert ctx._buffers == []
+
+
+@pytest.mark.parametrize('period', [None, PERIOD])
+def test_contour_lengths_resident_path_plain_and_periodic(ctx, q, period):
+    _make_resident(ctx, q)
+    res = ctx.contour_lengths(q, _per_slab_levels(), Y, X, radius=RADIUS, period=period)
+    calls, args, mallocs, at = _take(ctx)
+    name = 'xc_contour_lengths_dev' if period is None else 'xc_contour_lengths_periodic_dev'
+    assert calls == _seq(name, 2, 2, 1)
+    assert mallocs == [b for _, n in BATCHES for b in (NY * 8, NX * 8, n * N * 8, n * N * 8, n * N * 8)]
+    mid = (RADIUS,) if period is None else (PERIOD, RADIUS)
+    for k, (a, (s0, n)) in enumerate(zip(args, BATCHES)):
+        dy, dx, dc, dl, dn = at[5 * k:5 * k + 5]
+        assert a == (None, RES + s0 * SLAB, F64, n, NY, NX, dy, dx) + mid + (dc, N, 1, dl, dn)
+    assert type(res) is tuple and len(res) == 2
+    assert res[0].shape == res[1].shape == (S, N) and res[0].dtype == np.float64 and res[1].dtype == np.uint64
+    assert ctx._buffers == []
+
+
+def _twos_but_in_the_second_batch(lib):
+    """for _Lib.d2h_u64: every count is 2, but 0 in the second batch -- the batches are told apart by K12's count-only calls"""
+    return 0 if sum(1 for name, a in lib.args if name in _K12 and a[9] == 0) == 2 else 2
+
+
+@pytest.mark.parametrize('resident', [False, True])
+@pytest.mark.parametrize('periodic', [False, True])
+def test_contour_segments_two_passes_per_batch(ctx, q, periodic, resident):
+    if resident:
+        _make_resident(ctx, q)
+    ctx.lib.d2h_u64 = _twos_but_in_the_second_batch
+    res = ctx.contour_segments(q, _per_slab_levels(), periodic=periodic)
+    calls, args, mallocs, at = _take(ctx)
+    name = _K12[1] if periodic else _K12[0]
+    assert calls == _seq(name, 2, 2, 2, 1, 1)                       # count and records; count alone (total 0); count and records
+    want_m, want_a, k = [], [], 0
+    for b, (s0, n) in enumerate(BATCHES):
+        total = 0 if b == 1 else 2 * n * N
+        stage = ([] if resident else [n * SLAB]) + [n * N * 8, n * N * 8]            # [tracer,] contours, counts
+        recs = [total * 8, total * 8, total * 32] if total else []
+        want_m += stage + recs
+        dc, dn = at[k + len(stage) - 2], at[k + len(stage) - 1]
+        head = (None, RES + s0 * SLAB if resident else at[k], F64, n, NY, NX, dc, N, 1)
+        want_a.append(head + (0, dn, None, None, None))
+        if total:
+            want_a.append(head + (total, dn) + tuple(at[k + len(stage):k + len(stage) + 3]))
+        k += len(stage) + len(recs)
+    assert mallocs == want_m and args == want_a
+    cnt, ef, et, pts = res
+    assert type(res) is tuple and len(res) == 4
+    assert cnt.shape == (S, N) and cnt.dtype == np.uint64 and cnt[:, 0].tolist() == [2, 2, 0, 0, 2]
+    assert ef.shape == et.shape == (24,) and ef.dtype == et.dtype == np.int64
+    assert pts.shape == (24, 4) and pts.dtype == np.float64
+    assert ctx._buffers == []
+    # levels every slab shares: uploaded whole with every batch, the per-slab flag 0; everything zero: one pass, empty records
+    ctx.lib.d2h_u64 = None
+    res = ctx.contour_segments(q, np.linspace(-1, 1, N), periodic=periodic)
+    calls, args, mallocs, at = _take(ctx)
+    assert calls == _seq(name, 2, 2, 1) and all(a[7:10] == (N, 0, 0) for a in args)
+    assert mallocs == [b for _, n in BATCHES for b in ([] if resident else [n * SLAB]) + [N * 8, n * N * 8]]
+    assert res[0].shape == (S, N) and not res[0].any() and res[0].dtype == np.uint64
+    assert res[1].shape == res[2].shape == (0,) and res[1].dtype == res[2].dtype == np.int64
+    assert res[3].shape == (0, 4) and res[3].dtype == np.float64
+    assert ctx._buffers == []
+
+
+@pytest.mark.parametrize('resident', [False, True])
+@pytest.mark.parametrize('period', [None, PERIOD])
+def test_contour_pieces_runs_k13_on_the_records_of_each_batch(ctx, q, period, resident):
+    if resident:
+        _make_resident(ctx, q)
+    ctx.lib.d2h_u64 = _twos_but_in_the_second_batch
+    res = ctx.contour_pieces(q, _per_slab_levels(), Y, X, radius=RADIUS, period=period)
+    calls, args, mallocs, at = _take(ctx)
+    seg = _K12[0] if period is None else _K12[1]
+    K13 = 'xc_contour_pieces_dev'
+    assert calls == [(seg, 2), (seg, 2), (K13, 2 * N), (seg, 2), (seg, 1), (seg, 1), (K13, N)]
+    want_m, want_a, k = [], [], 0
+    for b, (s0, n) in enumerate(BATCHES):
+        total = 0 if b == 1 else 2 * n * N
+        stage = ([] if resident else [n * SLAB]) + [n * N * 8, NY * 8, NX * 8, n * N * 8, n * N * 8]
+        recs = [total * 8, total * 8, total * 32, total * 56] if total else []
+        want_m += stage + recs
+        dc, dy, dx, dn, dpc = at[k + len(stage) - 5:k + len(stage)]
+        head = (None, RES + s0 * SLAB if resident else at[k], F64, n, NY, NX, dc, N, 1)
+        want_a.append(head + (0, dn, None, None, None))
+        if total:
+            df, dto, dp, drec = at[k + len(stage):k + len(stage) + 4]
+            want_a.append(head + (total, dn, df, dto, dp))
+            col = [drec + c * total * 8 for c in range(6)]
+            want_a.append((None, n * N, dn, df, dto, dp, NY, NX) + ((0, dy, dx, 0.0) if period is None else (1, dy, dx, PERIOD))
+                          + (RADIUS, total, dpc, col[0], col[1], drec + 48 * total, drec + 52 * total, col[2], col[3], col[4], col[5]))
+        k += len(stage) + len(recs)
+    assert mallocs == want_m and args == want_a
+    pc, tab = res
+    assert type(res) is tuple and len(res) == 2
+    assert pc.shape == (S, N) and pc.dtype == np.uint64 and pc[:, 0].tolist() == [2, 2, 0, 0, 2]
+    assert type(tab) is np.ndarray and tab.shape == (24,) and tab.dtype == nat.Context.PIECE_DTYPE
+    assert ctx._buffers == []
+    ctx.lib.d2h_u64 = None                                          # everything zero: K13 is never run
+    pc, tab = ctx.contour_pieces(q, np.linspace(-1, 1, N), Y, X, period=period)
+    calls, args, mallocs, at = _take(ctx)
+    assert calls == _seq(seg, 2, 2, 1) and all(a[7:10] == (N, 0, 0) for a in args)
+    assert mallocs == [b for _, n in BATCHES for b in ([] if resident else [n * SLAB]) + [N * 8, NY * 8, NX * 8, n * N * 8, n * N * 8]]
+    assert pc.shape == (S, N) and pc.dtype == np.uint64 and not pc.any()
+    assert tab.shape == (0,) and tab.dtype == nat.Context.PIECE_DTYPE
+    assert ctx._buffers == []
+
+
+@pytest.mark.parametrize('with_levels', [False, True])
+@pytest.mark.parametrize('resident', [False, True])
+@pytest.mark.parametrize('period', [None, PERIOD])
+def test_local_contour_lengths_batches(ctx, q, period, resident, with_levels):
+    """a slab of K11 stages the tracer and four window arrays: the cap that gives batches of 2, 2, 1 is its own"""
+    ctx.max_batch_bytes = 2 * (SLAB + 4 * OB) + 8
+    if resident:
+        _make_resident(ctx, q)
+    levels = np.linspace(-1, 1, S * NWY * NWX).reshape(S, NWY, NWX) if with_levels else None
+    res = ctx.local_contour_lengths(q, Y, X, WIN, STR, 5, levels=levels, radius=RADIUS, period=period)
+    calls, args, mallocs, at = _take(ctx)
+    name = 'xc_local_contour_lengths' + ('' if period is None else '_periodic') + ('_dev' if resident else '')
+    assert calls == _seq(name, 2, 2, 1)
+    rest = (() if period is None else (PERIOD,)) + (RADIUS, 3, 4, 2, 3, 5)           # the period goes between xcoord and the radius
+    if resident:
+        assert mallocs == [b for _, n in BATCHES for b in [NY * 8, NX * 8] + ([n * OB] if with_levels else []) + [n * OB] * 3]
+        per = 6 if with_levels else 5
+        for k, (a, (s0, n)) in enumerate(zip(args, BATCHES)):
+            b = at[per * k:per * k + per]
+            assert a == (None, RES + s0 * SLAB, F64, n, NY, NX, b[0], b[1]) + rest + (b[2] if with_levels else None,) + tuple(b[-3:])
+    else:
+        assert mallocs == []
+        for a, (s0, n) in zip(args, BATCHES):
+            assert a[:8 + len(rest)] == (None, q.ctypes.data + s0 * SLAB, F64, n, NY, NX, Y.ctypes.data, X.ctypes.data) + rest
+            assert a[8 + len(rest)] == (levels.ctypes.data + s0 * OB if with_levels else None) and len(a) == 12 + len(rest)
+    assert type(res) is tuple and len(res) == 3
+    assert res[0].shape == res[1].shape == res[2].shape == (S, NWY, NWX)
+    assert res[0].dtype == res[1].dtype == np.float64 and res[2].dtype == np.uint64
+    assert ctx._buffers == []
+
+
+# ------------------------------------------------------------------ what the four methods refuse, and in which words
+def _call(ctx, method, q, contours=None, y=Y, x=X, period=None, window=WIN, stride=STR, levels=None):
+    if contours is None:
+        contours = np.linspace(-1, 1, N)
+    if method == 'contour_lengths':
+        return ctx.contour_lengths(q, contours, y, x, period=period)
+    if method == 'contour_segments':
+        return ctx.contour_segments(q, contours, periodic=period is not None)
+    if method == 'contour_pieces':
+        return ctx.contour_pieces(q, contours, y, x, period=period)
+    return ctx.local_contour_lengths(q, y, x, window, stride, 4, levels=levels, period=period)
+
+
+K10, K11, K12, K13 = 'contour_lengths', 'local_contour_lengths', 'contour_segments', 'contour_pieces'
+_BAD, _EDGES = nat.XC_EBADARG, nat.XC_EEDGES
+_Q_TEXT = 'q must be (nslab, ny, nx)'
+_C_TEXT = 'contours must be (N,) or (nslab, N)'
+_ASC = '%s: contours must be ascending without NaN'
+_LEN = '%%s: coordinates of length (%%d, %%d) for a (%d, %d) plane' % (NY, NX)
+_FIN = '%s: coordinates must be finite'
+_PER = ('%s: period must be finite, non-zero, of the sign of xcoord[nx-1] - xcoord[0] and longer than that span, and nx >= 2')
+_XNAN = np.where(np.arange(NX) == 3, np.nan, X)
+_YINF = np.where(np.arange(NY) == 2, np.inf, Y)
+# (method, what is wrong, keyword arguments of _call, error code, text); 'resident': the tracer has a device mirror
+_REFUSED = [(m, 'q not 3-D', dict(q=np.zeros((NY, NX))), _BAD, _Q_TEXT) for m in (K10, K11, K12, K13)]
+for m, who in ((K10, 'xc_contour_lengths'), (K12, 'xc_contour_segments'), (K13, 'xc_contour_pieces')):
+    res = dict(resident=True) if m == K10 else {}                   # K10's host path leaves these two to the C library, same texts
+    _REFUSED += [(m, 'contours 3-D', dict(contours=np.zeros((S, 1, N))), _BAD, _C_TEXT),
+                 (m, 'wrong leading contour dim', dict(contours=np.zeros((S + 1, N))), _BAD, _C_TEXT),
+                 (m, 'zero contours', dict(contours=np.zeros(0)), _BAD, _C_TEXT),
+                 (m, 'a NaN contour', dict(contours=np.array([0.0, np.nan, 1.0]), **res), _EDGES, _ASC % who),
+                 (m, 'a descending contour', dict(contours=np.array([0.0, 1.0, 0.5]), **res), _EDGES, _ASC % who),
+                 (m, 'a descending contour of one slab', dict(contours=np.where(np.arange(S)[:, None] == 0, -1.0, 1.0)
+                                                               * np.arange(3.0), **res), _EDGES, _ASC % who)]
+for m, who, pwho in ((K10, 'xc_contour_lengths', 'xc_contour_lengths_periodic'), (K13, 'xc_contour_pieces', 'xc_contour_pieces'),
+                     (K11, 'xc_local_contour_lengths', 'xc_local_contour_lengths_periodic')):
+    res = dict(resident=True) if m == K10 else {}                   # without a period K10's host path leaves finiteness to C too
+    _REFUSED += [(m, 'wrong ycoord length', dict(y=np.arange(NY + 1.0)), _BAD, _LEN % (who, NY + 1, NX)),
+                 (m, 'wrong xcoord length', dict(x=np.arange(NX - 1.0)), _BAD, _LEN % (who, NY, NX - 1)),
+                 (m, 'xcoord 2-D', dict(x=np.zeros((1, NX))), _BAD, _LEN % (who, NY, NX)),
+                 (m, 'a NaN xcoord', dict(x=_XNAN, **res), _BAD, _FIN % who),
+                 (m, 'an infinite ycoord', dict(y=_YINF, **res), _BAD, _FIN % who),
+                 (m, 'a NaN xcoord, periodic', dict(x=_XNAN, period=PERIOD), _BAD, _FIN % who),
+                 (m, 'nx == 1 with a period', dict(q=np.zeros((S, NY, 1)), x=np.zeros(1), period=1.0), _BAD, _PER % pwho)]
+    # tests/test_gpu_periodic_contour_lengths.py::test_bad_periods_rejected, for a span of NX - 1
+    _REFUSED += [(m, 'period %r' % bad, dict(period=bad), _BAD, _PER % pwho) for bad in (0.0, np.nan, np.inf, -float(NX), NX - 1.0, NX - 2.0)]
+_REFUSED += [(K12, 'nx == 1 with a period', dict(q=np.zeros((S, NY, 1)), period=1.0), _BAD, 'xc_contour_segments_periodic: nx >= 2'),
+             (K11, 'a window of one row', dict(window=(1, 4)), _BAD, 'xc_local_contour_lengths: the window must be at least 2 x 2 nodes'),
+             (K11, 'a window of one column', dict(window=(3, 1)), _BAD, 'xc_local_contour_lengths: the window must be at least 2 x 2 nodes'),
+             (K11, 'a row stride of 0', dict(stride=(0, 1)), _BAD, 'xc_local_contour_lengths: strides must be >= 1'),
+             (K11, 'a column stride of 0', dict(stride=(1, 0)), _BAD, 'xc_local_contour_lengths: strides must be >= 1'),
+             (K11, 'wx > nx on a ring', dict(window=(3, NX + 1), period=PERIOD), _BAD,
+              'xc_local_contour_lengths_periodic: the window must not be wider than the ring (wx <= nx)'),
+             (K11, 'levels of a wrong shape', dict(levels=np.zeros((NWY, NWX + 1))), _BAD,
+              'levels must be a scalar, (nwy, nwx) or (nslab, nwy, nwx)'),
+             (K11, 'levels for other slabs', dict(levels=np.zeros((S + 1, NWY, NWX))), _BAD,
+              'levels must be a scalar, (nwy, nwx) or (nslab, nwy, nwx)')]
+
+
+@pytest.mark.parametrize('method,what,kw,code,text', _REFUSED, ids=['%s-%s' % r[:2] for r in _REFUSED])
+def test_one_defect_one_error(ctx, q, method, what, kw, code, text):
+    kw = dict(kw)
+    q = kw.pop('q', q)
+    if kw.pop('resident', False):
+        _make_resident(ctx, q)
+    with pytest.raises(nat.XContourHipError) as e:
+        _call(ctx, method, q, **kw)
+    assert e.value.code == code and str(e.value) == text
+    assert ctx.lib.calls == [] and ctx._buffers == []               # refused before anything reached the library
+
+
+def test_the_defect_free_calls_of_the_table_pass(ctx, q):
+    for m in (K10, K11, K12, K13):
+        for period in (None, PERIOD):
+            _call(ctx, m, q, period=period)
+    assert ctx._buffers == []

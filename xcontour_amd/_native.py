@@ -337,6 +337,42 @@ def _check_ascending(contours, who):
         raise XContourHipError(XC_EEDGES, '%s: contours must be ascending without NaN' % who)
 
 
+def _stack3(q):
+    """a stack as the contour calls take it (an array, or a lazy stack) -> (the stack, (nslab, ny, nx))"""
+    q = _stack_in(q)
+    if len(q.shape) != 3:
+        raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
+    return q, tuple(q.shape)
+
+
+def _levels_of(contours, nslab):
+    """the contours of K10 / K12 / K13 -> (contiguous float64, per-slab flag, N): (N,) or (nslab, N), N >= 1"""
+    contours = _contig(contours, np.float64)
+    per_slab = contours.ndim == 2
+    if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
+        raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
+    return contours, per_slab, contours.shape[-1]
+
+
+def _plane_coords(ycoord, xcoord, ny, nx, who):
+    """the coordinates of rows / columns -> contiguous float64 (ny,) / (nx,)"""
+    ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
+    if ycoord.shape != (ny,) or xcoord.shape != (nx,):
+        raise XContourHipError(XC_EBADARG, '%s: coordinates of length (%d, %d) for a (%d, %d) plane'
+                               % (who, ycoord.size, xcoord.size, ny, nx))
+    return ycoord, xcoord
+
+
+def _check_finite(who, *coords):
+    if not all(np.isfinite(c).all() for c in coords):
+        raise XContourHipError(XC_EBADARG, '%s: coordinates must be finite' % who)
+
+
+def _range_order(counts, key):
+    """the order that sorts records packed range by range (`counts` of them in each) by `key` inside every range"""
+    return np.lexsort((key, np.repeat(np.arange(counts.size), counts.ravel().astype(np.int64))))
+
+
 def join_segments(off, e_from, e_to):
     """xc_join_segments (host only, no device): the directed segments of `Context.contour_segments` joined into polylines.  off
     (nrange + 1,) int64, the exclusive scan of the counts; e_from / e_to (total,) int64.  Returns (order (total,) int64: segment
@@ -532,50 +568,47 @@ class Context(object):
         self._check(self.lib.xc_event_elapsed_ms(self.handle, e0, e1, C.byref(ms)))
         return ms.value
 
+    def _last_int(self, fn):
+        p = C.c_int()
+        self._check(fn(self.handle, C.byref(p)))
+        return p.value
+
     def last_sort_path(self):
         """K8, last call: 0 key passes only, 1 the three range-key passes sufficed, 2 they failed the check (re-sorted)"""
-        p = C.c_int()
-        self._check(self.lib.xc_last_sort_path(self.handle, C.byref(p)))
-        return p.value
+        return self._last_int(self.lib.xc_last_sort_path)
 
     def last_keff_path(self):
         """last xc_keff_dev call: 0 the min/max + histogram + finalize chain, 1 the single-read kernel (calls of one or two slabs)"""
-        p = C.c_int()
-        self._check(self.lib.xc_last_keff_path(self.handle, C.byref(p)))
-        return p.value
+        return self._last_int(self.lib.xc_last_keff_path)
+
+    def last_lwa_path(self):
+        """K7, last call: 0 band walk (bit-exact), 1 the O(ny log ny) interval kernel, 2 its premises failed the check"""
+        return self._last_int(self.lib.xc_last_lwa_path)
+
+    def _last_record(self, fn, rec, named, names, live):
+        """a launch record as a dict of its fields: `named` through `names`, 'q_dtype' a numpy dtype -- None when `live` is unset"""
+        self._check(fn(self.handle, C.byref(rec)))
+        out = {f[0]: getattr(rec, f[0]) for f in rec._fields_}
+        out[named] = names[out[named]]
+        out['q_dtype'] = np.dtype(np.float32 if out['q_dtype'] == XC_F32 else np.float64) if out[live] else None
+        return out
 
     def last_hist_variant(self):
         """the histogram kernel of the last hist / keff call and how it was launched (xc_last_hist_variant): a dict of the record's
         fields, 'kernel' named ('K3', 'K3-det', 'K3S'; None after a failed call) and 'q_dtype' a numpy dtype"""
-        v = HistVariant()
-        self._check(self.lib.xc_last_hist_variant(self.handle, C.byref(v)))
-        out = {f[0]: getattr(v, f[0]) for f in HistVariant._fields_}
-        out['kernel'] = HIST_KERNELS[out['kernel']]
-        out['q_dtype'] = np.dtype(np.float32 if out['q_dtype'] == XC_F32 else np.float64) if out['kernel'] else None
-        return out
+        return self._last_record(self.lib.xc_last_hist_variant, HistVariant(), 'kernel', HIST_KERNELS, 'kernel')
 
     def last_clen_geometry(self):
         """how the last contour_lengths call (its last batch) launched K10 (xc_last_clen_geometry): a dict of the record's fields,
         'bps_rule' named ('share', 'floor', 'capacity', 'ntile'; None when the plane has no cells) and 'q_dtype' a numpy dtype (None
         after a failed call: then every field is 0)"""
-        g = ClenGeometry()
-        self._check(self.lib.xc_last_clen_geometry(self.handle, C.byref(g)))
-        out = {f[0]: getattr(g, f[0]) for f in ClenGeometry._fields_}
-        out['bps_rule'] = CLEN_BPS_RULES[out['bps_rule']]
-        out['q_dtype'] = np.dtype(np.float32 if out['q_dtype'] == XC_F32 else np.float64) if out['N'] else None
-        return out
+        return self._last_record(self.lib.xc_last_clen_geometry, ClenGeometry(), 'bps_rule', CLEN_BPS_RULES, 'N')
 
     def single_stamps(self, enable=True):
         """diagnostics: (device pointer, slots) of the single-read kernel's phase stamps; enable=False frees them"""
         ptr, n = _vp(), C.c_int()
         self._check(self.lib.xc_dbg_single_stamps(self.handle, 1 if enable else 0, C.byref(ptr), C.byref(n)))
         return ptr.value, n.value
-
-    def last_lwa_path(self):
-        """K7, last call: 0 band walk (bit-exact), 1 the O(ny log ny) interval kernel, 2 its premises failed the check"""
-        p = C.c_int()
-        self._check(self.lib.xc_last_lwa_path(self.handle, C.byref(p)))
-        return p.value
 
     def set_kernel_timing(self, on):
         self._check(self.lib.xc_set_kernel_timing(self.handle, 1 if on else 0))
@@ -905,6 +938,17 @@ class Context(object):
             return lens, cnts
         return self._batched(nslab, ny * nx * (q.dtype.itemsize + (area.dtype.itemsize if area.ndim == 3 else 0)), one)
 
+    def _mirror(self, qb):
+        """device address of the mirror of a batch of the tracer (keep_resident), or None"""
+        return self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+
+    def _ring_forms(self, name, period):
+        """K10 / K11, plain or periodic: (the host entry point, the _dev one, what their argument lists hold between xcoord and the
+        radius: the period, in the periodic forms)"""
+        if period is not None:
+            name, period = name + '_periodic', (period,)
+        return getattr(self.lib, name), getattr(self.lib, name + '_dev'), period or ()
+
     def contour_lengths(self, q, contours, ycoord, xcoord, radius=0.0, period=None):
         """Marching-squares contour lengths (xc_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours (N,) or
         (nslab, N) ASCENDING f64; ycoord (ny,) / xcoord (nx,) the coordinates of rows / columns (radians when radius > 0).
@@ -913,38 +957,24 @@ class Context(object):
         entry point.  period: None -- the plane has two free edges in X --, or the period of the X coordinate (in its units:
         radians when radius > 0; of the sign of xcoord[-1] - xcoord[0] and longer than that span): the cell between the last and
         the first column is traced too (xc_contour_lengths_periodic), as on the plane with column 0 appended one period on."""
-        q = _stack_in(q)
-        if len(q.shape) != 3:
-            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
-        nslab, ny, nx = q.shape
-        contours = _contig(contours, np.float64)
-        per_slab = contours.ndim == 2
-        if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
-            raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
-        ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
-        if ycoord.shape != (ny,) or xcoord.shape != (nx,):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates of length (%d, %d) for a (%d, %d) plane'
-                                   % (ycoord.size, xcoord.size, ny, nx))
-        radius = float(radius)
-        N = contours.shape[-1]
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, per_slab, N = _levels_of(contours, nslab)
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_lengths')
         if period is not None:
-            if not np.isfinite(xcoord).all():
-                raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
+            _check_finite('xc_contour_lengths', xcoord)
             period = _check_period(period, xcoord, 'xc_contour_lengths_periodic')
-        # what follows xcoord in the argument lists, and the entry points that take it
-        mid = (radius,) if period is None else (period, radius)
-        f_host = self.lib.xc_contour_lengths if period is None else self.lib.xc_contour_lengths_periodic
-        f_dev = self.lib.xc_contour_lengths_dev if period is None else self.lib.xc_contour_lengths_periodic_dev
+        f_host, f_dev, ring = self._ring_forms('xc_contour_lengths', period)
+        mid = ring + (float(radius),)
 
         def one(s0, s1):
             n = s1 - s0
             qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
-            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+            qp = self._mirror(qb)
             if qp:
-                # the tracer is on the device already: only the small arrays cross (the device entry point trusts its caller)
+                # the tracer is on the device already: only the small arrays cross.  The device entry point trusts its caller, so
+                # what the host form checks itself (xc_forms.hip, the same texts) is checked here
                 _check_ascending(cb, 'xc_contour_lengths')
-                if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
-                    raise XContourHipError(XC_EBADARG, 'xc_contour_lengths: coordinates must be finite')
+                _check_finite('xc_contour_lengths', ycoord, xcoord)
                 with self._temporaries([ycoord, xcoord, cb], [n * N * 8, n * N * 8]) as (dy, dx, dc, dl, dn):
                     self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *mid, dc.ptr, N,
                                       1 if per_slab else 0, dl.ptr, dn.ptr))
@@ -956,6 +986,36 @@ class Context(object):
             return lens, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
+    def _with_segment_records(self, periodic, qb, cb, use, inputs=(), out_nbytes=(), per_segment=()):
+        """K12's two passes over one batch, everything staged once.  Uploaded: the tracer `qb` (unless it has a device mirror), the
+        contours `cb` ((N,) or one row per slab) and the caller's further `inputs`; allocated: the counts and one buffer per entry
+        of `out_nbytes`.  A count-only call gives the total, which sizes the three record buffers, and one of b bytes per segment
+        for every b of `per_segment`, of the second call (none without segments).  Returns
+        use(counts (n, N) uint64, total, count buffer, buffers of `inputs`, buffers of `out_nbytes`,
+        [e_from, e_to, pts, *per-segment buffers] or []); every device buffer is freed on the way out."""
+        f = self.lib.xc_contour_segments_periodic_dev if periodic else self.lib.xc_contour_segments_dev
+        n, ny, nx = qb.shape
+        N, nin = cb.shape[-1], len(inputs)
+        qp = self._mirror(qb)
+        dq = None if qp else self.to_device(qb)
+        bufs = [self.to_device(a) for a in (cb,) + tuple(inputs)] + [self.alloc(b) for b in (n * N * 8,) + tuple(out_nbytes)]
+        recs = []
+        try:
+            dn = bufs[1 + nin]
+            head = (self.handle, qp or dq.ptr, dtype_code(qb.dtype), n, ny, nx, bufs[0].ptr, N, 1 if cb.ndim == 2 else 0)
+            rc = f(*head, 0, dn.ptr, None, None, None)
+            if rc not in (XC_OK, 1):                             # (1: there are segments, and no room was given)
+                self._check(rc)
+            cnt = dn.download((n, N), np.uint64)
+            total = int(cnt.sum())
+            if total:
+                recs = [self.alloc(total * b) for b in (8, 8, 32) + tuple(per_segment)]
+                self._check(f(*head, total, dn.ptr, recs[0].ptr, recs[1].ptr, recs[2].ptr))
+            return use(cnt, total, dn, bufs[1:1 + nin], bufs[2 + nin:], recs)
+        finally:
+            for b in recs + ([] if dq is None else [dq]) + bufs:
+                b.free()
+
     def contour_segments(self, q, contours, periodic=False):
         """Marching-squares contour segments (K12, xc_contour_segments_dev; periodic=True: xc_contour_segments_periodic_dev).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours
         (N,) or (nslab, N) ASCENDING f64 without NaN.  Returns (count uint64 (nslab, N); e_from, e_to int64 (total,): the ids of the
@@ -966,40 +1026,22 @@ class Context(object):
         is staged once: a count-only call sizes the buffers of the second.  periodic=True: X is a ring of nx cell columns (nx >= 2):
         the seam cell between the last column and the first is traced too, its columns run from nx-1 to nx, and its right edge has
         column 0's id, 2 r nx + 1 -- the records of the plane with column 0 appended as column nx, ids folded onto the ring."""
-        q = _stack_in(q)
-        if len(q.shape) != 3:
-            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
-        nslab, ny, nx = q.shape
-        contours = _contig(contours, np.float64)
-        per_slab = contours.ndim == 2
-        if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
-            raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
-        N = contours.shape[-1]
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, _, _ = _levels_of(contours, nslab)
         _check_ascending(contours, 'xc_contour_segments')
         if periodic and nx < 2:
             raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
-        f = self.lib.xc_contour_segments_periodic_dev if periodic else self.lib.xc_contour_segments_dev
+
+        def download(cnt, total, dn, ins, outs, recs):
+            if total == 0:
+                return cnt, np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty((0, 4), dtype=np.float64)
+            df, dt, dp = recs
+            ef, et, pts = df.download((total,), np.int64), dt.download((total,), np.int64), dp.download((total, 4), np.float64)
+            o = _range_order(cnt, ef)
+            return cnt, ef[o], et[o], pts[o]
 
         def one(s0, s1):
-            n = s1 - s0
-            qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
-            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
-            with self._temporaries(([] if qp else [qb]) + [cb], [n * N * 8]) as bufs:
-                dc, dn = bufs[-2:]
-                head = (self.handle, qp or bufs[0].ptr, dtype_code(q.dtype), n, ny, nx, dc.ptr, N, 1 if per_slab else 0)
-                rc = f(*head, 0, dn.ptr, None, None, None)
-                if rc not in (XC_OK, 1):
-                    self._check(rc)
-                cnt = dn.download((n, N), np.uint64)
-                total = int(cnt.sum())
-                if total == 0:
-                    return cnt, np.empty(0, dtype=np.int64), np.empty(0, dtype=np.int64), np.empty((0, 4), dtype=np.float64)
-                with self._temporaries([], [total * 8, total * 8, total * 32]) as (df, dt, dp):
-                    self._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr))
-                    ef, et = df.download((total,), np.int64), dt.download((total,), np.int64)
-                    pts = dp.download((total, 4), np.float64)
-            o = np.lexsort((ef, np.repeat(np.arange(n * N), cnt.ravel().astype(np.int64))))
-            return cnt, ef[o], et[o], pts[o]
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), download)
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
     # the per-piece table of `contour_pieces`: one record per connected piece of a contour
@@ -1029,60 +1071,41 @@ class Context(object):
           length  the sum of K10's segment lengths (times radius), 0.0 for a piece of coincident-end segments only;
           area  S = 1/2 sum (Ya' + Yb') (Xa - Xb), Y' = sin(Y) and S radius^2 when radius > 0; NaN for an open piece;
           row_min, row_max  the extent in index-space rows."""
-        q = _stack_in(q)
-        if len(q.shape) != 3:
-            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
-        nslab, ny, nx = q.shape
-        contours = _contig(contours, np.float64)
-        per_slab = contours.ndim == 2
-        if contours.ndim not in (1, 2) or (per_slab and contours.shape[0] != nslab) or contours.shape[-1] < 1:
-            raise XContourHipError(XC_EBADARG, 'contours must be (N,) or (nslab, N)')
-        N = contours.shape[-1]
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, _, N = _levels_of(contours, nslab)
         _check_ascending(contours, 'xc_contour_pieces')
-        ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
-        if ycoord.shape != (ny,) or xcoord.shape != (nx,):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_pieces: coordinates of length (%d, %d) for a (%d, %d) plane'
-                                   % (ycoord.size, xcoord.size, ny, nx))
-        if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_pieces: coordinates must be finite')
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_pieces')
+        _check_finite('xc_contour_pieces', ycoord, xcoord)
         radius = float(radius)
         periodic = period is not None
         if periodic:
             period = _check_period(period, xcoord, 'xc_contour_pieces')
-        fseg = self.lib.xc_contour_segments_periodic_dev if periodic else self.lib.xc_contour_segments_dev
         dt = self.PIECE_DTYPE
 
+        def pieces(cnt, total, dn, ins, outs, recs):
+            if total == 0:
+                return np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt)
+            (dy, dx), (dpc,), (df, dto, dp, drec) = ins, outs, recs
+            col = [drec.ptr + k * total * 8 for k in range(6)]              # first_edge, nseg, length, area, row_min, row_max
+            i32 = [drec.ptr + 48 * total, drec.ptr + 52 * total]              # closed, winding
+            rc = self.lib.xc_contour_pieces_dev(self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0,
+                                                dy.ptr, dx.ptr, period if periodic else 0.0, radius, total, dpc.ptr,
+                                                col[0], col[1], i32[0], i32[1], col[2], col[3], col[4], col[5])
+            self._check(rc)
+            pc = dpc.download(cnt.shape, np.uint64)
+            npiece = int(pc.sum())
+            out = np.empty(npiece, dtype=dt)
+            for name, at, t in (('first_edge', col[0], np.int64), ('nseg', col[1], np.int64), ('length', col[2], np.float64),
+                                ('area', col[3], np.float64), ('row_min', col[4], np.float64), ('row_max', col[5], np.float64),
+                                ('closed', i32[0], np.int32), ('winding', i32[1], np.int32)):
+                out[name] = drec.download((npiece,), t, offset_bytes=at - drec.ptr)
+            return pc, out[_range_order(pc, out['first_edge'])]
+
         def one(s0, s1):
-            n = s1 - s0
-            qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
-            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
-            with self._temporaries(([] if qp else [qb]) + [cb, ycoord, xcoord], [n * N * 8, n * N * 8]) as bufs:
-                dc, dy, dx, dn, dpc = bufs[-5:]
-                head = (self.handle, qp or bufs[0].ptr, dtype_code(q.dtype), n, ny, nx, dc.ptr, N, 1 if per_slab else 0)
-                rc = fseg(*head, 0, dn.ptr, None, None, None)
-                if rc not in (XC_OK, 1):
-                    self._check(rc)
-                total = int(dn.download((n, N), np.uint64).sum())
-                if total == 0:
-                    return np.zeros((n, N), dtype=np.uint64), np.empty(0, dtype=dt)
-                # the segment records, and one piece record per segment at most: six 8-byte columns, then two 4-byte ones
-                with self._temporaries([], [total * 8, total * 8, total * 32, total * 56]) as (df, dto, dp, drec):
-                    self._check(fseg(*head, total, dn.ptr, df.ptr, dto.ptr, dp.ptr))
-                    col = [drec.ptr + k * total * 8 for k in range(6)]          # first_edge, nseg, length, area, row_min, row_max
-                    i32 = [drec.ptr + 48 * total, drec.ptr + 52 * total]          # closed, winding
-                    rc = self.lib.xc_contour_pieces_dev(self.handle, n * N, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0,
-                                                        dy.ptr, dx.ptr, period if periodic else 0.0, radius, total, dpc.ptr,
-                                                        col[0], col[1], i32[0], i32[1], col[2], col[3], col[4], col[5])
-                    self._check(rc)
-                    pc = dpc.download((n, N), np.uint64)
-                    npiece = int(pc.sum())
-                    out = np.empty(npiece, dtype=dt)
-                    for name, at, t in (('first_edge', col[0], np.int64), ('nseg', col[1], np.int64), ('length', col[2], np.float64),
-                                        ('area', col[3], np.float64), ('row_min', col[4], np.float64), ('row_max', col[5], np.float64),
-                                        ('closed', i32[0], np.int32), ('winding', i32[1], np.int32)):
-                        out[name] = drec.download((npiece,), t, offset_bytes=at - drec.ptr)
-            o = np.lexsort((out['first_edge'], np.repeat(np.arange(n * N), pc.ravel().astype(np.int64))))
-            return pc, out[o]
+            # beside K12's records: the coordinates, the piece counts, and one piece record per segment at most -- six 8-byte
+            # columns, then two 4-byte ones
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), pieces,
+                                              inputs=(ycoord, xcoord), out_nbytes=((s1 - s0) * N * 8,), per_segment=(56,))
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):
@@ -1094,21 +1117,14 @@ class Context(object):
         uint64).  A tracer with a device mirror (keep_resident) is read in place through the _dev entry point.  period: None, or
         the period of the X coordinate as for contour_lengths: windows are then not clipped in X but run on round the ring
         (xc_local_contour_lengths_periodic; the window must not be wider than the ring, wx <= nx)."""
-        q = _stack_in(q)
-        if len(q.shape) != 3:
-            raise XContourHipError(XC_EBADARG, 'q must be (nslab, ny, nx)')
-        nslab, ny, nx = q.shape
+        q, (nslab, ny, nx) = _stack3(q)
         (wy, wx), (sy, sx) = (int(v) for v in window), (int(v) for v in stride)
         if wy < 2 or wx < 2:
             raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: the window must be at least 2 x 2 nodes')
         if sy < 1 or sx < 1:
             raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: strides must be >= 1')
-        ycoord, xcoord = _contig(ycoord, np.float64), _contig(xcoord, np.float64)
-        if ycoord.shape != (ny,) or xcoord.shape != (nx,):
-            raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: coordinates of length (%d, %d) for a (%d, %d) plane'
-                                   % (ycoord.size, xcoord.size, ny, nx))
-        if not (np.isfinite(ycoord).all() and np.isfinite(xcoord).all()):
-            raise XContourHipError(XC_EBADARG, 'xc_local_contour_lengths: coordinates must be finite')
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_local_contour_lengths')
+        _check_finite('xc_local_contour_lengths', ycoord, xcoord)
         if period is not None:
             period = _check_period(period, xcoord, 'xc_local_contour_lengths_periodic')
             if wx > nx:
@@ -1120,30 +1136,26 @@ class Context(object):
             if levels.shape not in ((), (nwy, nwx), (nslab, nwy, nwx)):
                 raise XContourHipError(XC_EBADARG, 'levels must be a scalar, (nwy, nwx) or (nslab, nwy, nwx)')
             levels = np.ascontiguousarray(np.broadcast_to(levels, (nslab, nwy, nwx)))
-        shape = (ny, nx)
-        rest = (float(radius), wy, wx, sy, sx, int(min_periods))
-        if period is not None:
-            rest = (period,) + rest
-        f_host = self.lib.xc_local_contour_lengths if period is None else self.lib.xc_local_contour_lengths_periodic
-        f_dev = self.lib.xc_local_contour_lengths_dev if period is None else self.lib.xc_local_contour_lengths_periodic_dev
+        f_host, f_dev, ring = self._ring_forms('xc_local_contour_lengths', period)
+        rest = ring + (float(radius), wy, wx, sy, sx, int(min_periods))
         ob = nwy * nwx * 8
 
         def one(s0, s1):
             n = s1 - s0
             qb, lb = _stack_now(q, s0, s1), _part(levels, 3, s0, s1)
-            qp = self.resident_ptr(qb) if isinstance(qb, np.ndarray) and qb.flags.c_contiguous else None
+            qp = self._mirror(qb)
             if qp:
                 # the tracer is on the device already: only the small arrays cross
                 with self._temporaries([ycoord, xcoord] + ([lb] if lb is not None else []), [n * ob] * 3) as bufs:
                     dy, dx = bufs[:2]
                     dl, de, dn = bufs[-3:]
-                    self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, *shape, dy.ptr, dx.ptr, *rest,
+                    self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *rest,
                                       bufs[2].ptr if lb is not None else None, dl.ptr, de.ptr, dn.ptr))
                     return (dl.download((n, nwy, nwx), np.float64), de.download((n, nwy, nwx), np.float64),
                             dn.download((n, nwy, nwx), np.uint64))
             lens, lvls = np.empty((n, nwy, nwx), dtype=np.float64), np.empty((n, nwy, nwx), dtype=np.float64)
             cnts = np.empty((n, nwy, nwx), dtype=np.uint64)
-            self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, *shape, _ptr(ycoord), _ptr(xcoord), *rest, _ptr(lb),
+            self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord), *rest, _ptr(lb),
                                _ptr(lens), _ptr(lvls), _ptr(cnts)))
             return lens, lvls, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize + 4 * ob, one)

@@ -713,6 +713,44 @@ class Contour2D(object):
             raise Exception('%s: periodic=%r is too short: the X coordinate already spans %r' % (who, periodic, abs(span)))
         return float(np.float64(np.deg2rad(np.float32(P)))) if latlon and not plain else float(np.float64(P))
 
+    def _plane_dcoords(self, who, tracer, hint=''):
+        """-> (the data a contour method works on, its coordinates: both plane dims must have values)"""
+        data = self.tracer if tracer is None else tracer
+        dcoords = lb.unwrap(data, lazy=True)[2]
+        for d in (self.dimEqV, self._xdim):
+            if d not in dcoords:
+                raise Exception('%s needs coordinate values for the plane dim %s%s' % (who, d, hint))
+        return data, dcoords
+
+    def _contour_coords(self, who, tracer, latlon, periodic):
+        """what cal_contour_lengths, cal_local_contour_lengths and cal_contour_pieces open with -> (the data, its coordinates,
+        [ycoord, xcoord] as handed to the library -- cast to float32 as the reference does (core.py:1003-1004), to radians in
+        float32 under `latlon`, then to float64 --, the period from `_x_period`)"""
+        data, dcoords = self._plane_dcoords(who, tracer)
+        f32 = [np.asarray(dcoords[d]).astype(np.float32) for d in (self.dimEqV, self._xdim)]
+        fdef = [(np.deg2rad(v) if latlon else v).astype(np.float64) for v in f32]
+        return data, dcoords, fdef, self._x_period(periodic, f32[1], latlon, who)
+
+    def _float_plane(self, data):
+        """`_plane` with the values through `_float`: what the contour kernels read"""
+        q, lead, lshape, coords = self._plane(data)
+        return self._float(q), lead, lshape, coords
+
+    @staticmethod
+    def _in_caller_order(order, lead, *per_range):
+        """per-range lists in sorted-level order (range s * N + j: slab s, sorted level j; `order` from `_sorted_levels`) ->
+        for each of them the nesting out[slab][k] with every level where the caller put it, out[k] without leading dims"""
+        nslab, N = order.shape
+        where = order.tolist()
+        outs = []
+        for vals in per_range:
+            out = [[None] * N for _ in range(nslab)]
+            for s, row in enumerate(where):
+                for j, k in enumerate(row):                      # j: the sorted level; k: where the caller put it
+                    out[s][k] = vals[s * N + j]
+            outs.append(out if lead else out[0])
+        return outs
+
     def cal_contour_lengths(self, contours, tracer=None, latlon=False, periodic=False):
         """
         Perimeter of every contour (reference core.py:969-1014, _contour_lengths 1437-1487 and
@@ -736,20 +774,9 @@ class Contour2D(object):
         """
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
-        data = self.tracer if tracer is None else tracer
-        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
-        for d in (self.dimEqV, self._xdim):
-            if d not in dcoords:
-                raise Exception('cal_contour_lengths needs coordinate values for the plane dim %s' % d)
-        fdef = []
-        for d in (self.dimEqV, self._xdim):
-            v = np.asarray(dcoords[d]).astype(np.float32)                      # core.py:1003-1004
-            fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
-        period = self._x_period(periodic, v, latlon, 'cal_contour_lengths')
-        q, lead, lshape, coords = self._plane(data)
-        q = self._float(q)
-        nslab = q.shape[0]
-        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
+        data, _, fdef, period = self._contour_coords('cal_contour_lengths', tracer, latlon, periodic)
+        q, lead, lshape, coords = self._float_plane(data)
+        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
         lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
         return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
 
@@ -787,20 +814,10 @@ class Contour2D(object):
                 raise Exception('%s should be at least %d' % (what, least))
             return v
         win, st = pair(window, 'window', 2), pair(stride, 'stride', 1)
-        data = self.tracer if tracer is None else tracer
-        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
-        for d in pdims:
-            if d not in dcoords:
-                raise Exception('cal_local_contour_lengths needs coordinate values for the plane dim %s' % d)
-        fdef = []
-        for d in pdims:
-            v = np.asarray(dcoords[d]).astype(np.float32)                      # as cal_contour_lengths
-            fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
-        period = self._x_period(periodic, v, latlon, 'cal_local_contour_lengths')
-        if period is not None and win[1] > v.size:
-            raise Exception('window should not be wider than the periodic dim %s: %d > %d nodes' % (self._xdim, win[1], v.size))
-        q, lead, lshape, coords = self._plane(data)
-        q = self._float(q)
+        data, dcoords, fdef, period = self._contour_coords('cal_local_contour_lengths', tracer, latlon, periodic)
+        if period is not None and win[1] > fdef[1].size:
+            raise Exception('window should not be wider than the periodic dim %s: %d > %d nodes' % (self._xdim, win[1], fdef[1].size))
+        q, lead, lshape, coords = self._float_plane(data)
         nslab, ny, nx = q.shape
         nw = (-(-ny // st[0]), -(-nx // st[1]))
         if levels is not None:
@@ -827,8 +844,8 @@ class Contour2D(object):
         return out
 
     # ------------------------------------------------------------------ contour pieces
-    PIECE_FIELDS = [('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),
-                    ('length', np.float64), ('area', np.float64), ('y_min', np.float64), ('y_max', np.float64)]
+    # a piece as the facade returns it: the library's record (Context.PIECE_DTYPE) with the row extent on the equivalent dim's coordinate
+    PIECE_FIELDS = [({'row_min': 'y_min', 'row_max': 'y_max'}.get(f, f), nat.Context.PIECE_DTYPE[f]) for f in nat.Context.PIECE_DTYPE.names]
 
     def cal_contour_pieces(self, contours, tracer=None, latlon=False, periodic=False):
         """
@@ -861,36 +878,20 @@ class Contour2D(object):
         """
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
-        data = self.tracer if tracer is None else tracer
-        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
-        for d in (self.dimEqV, self._xdim):
-            if d not in dcoords:
-                raise Exception('cal_contour_pieces needs coordinate values for the plane dim %s' % d)
-        fdef = []
-        for d in (self.dimEqV, self._xdim):
-            v = np.asarray(dcoords[d]).astype(np.float32)                      # as cal_contour_lengths (core.py:1003-1004)
-            fdef.append((np.deg2rad(v) if latlon else v).astype(np.float64))
-        period = self._x_period(periodic, v, latlon, 'cal_contour_pieces')
-        q, lead, lshape, coords = self._plane(data)
-        q = self._float(q)
-        nslab = q.shape[0]
-        bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
-        N = bs.shape[1]
+        data, dcoords, fdef, period = self._contour_coords('cal_contour_pieces', tracer, latlon, periodic)
+        q, lead, lshape, _ = self._float_plane(data)
+        bs, order, _ = self._sorted_levels(contours, q.shape[0], lead, lshape)
         pc, tab = self.ctx.contour_pieces(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
         yg = np.asarray(dcoords[self.dimEqV], dtype=np.float64)
         rec = np.empty(tab.size, dtype=self.PIECE_FIELDS)
-        for f in ('first_edge', 'nseg', 'closed', 'winding', 'length', 'area'):
-            rec[f] = tab[f]
+        for f in tab.dtype.names:
+            if f in rec.dtype.names:
+                rec[f] = tab[f]
         if tab.size:
             ya, yb = np.interp(tab['row_min'], np.arange(yg.size), yg), np.interp(tab['row_max'], np.arange(yg.size), yg)
             rec['y_min'], rec['y_max'] = np.minimum(ya, yb), np.maximum(ya, yb)
         poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
-        out = [[None] * N for _ in range(nslab)]
-        for s in range(nslab):
-            for j in range(N):                                   # j: the sorted level; order[s, j]: where the caller put it
-                r = s * N + j
-                out[s][int(order[s, j])] = rec[poff[r]:poff[r + 1]].copy()
-        return out if lead else out[0]
+        return self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
 
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):
@@ -930,39 +931,24 @@ class Contour2D(object):
         """
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
-        data = self.tracer if tracer is None else tracer
-        _, _, dcoords, _ = lb.unwrap(data, lazy=True)
-        cds = []
-        if not index:
-            for d in (self.dimEqV, self._xdim):
-                if d not in dcoords:
-                    raise Exception('find_contours needs coordinate values for the plane dim %s (or index=True)' % d)
-                cds.append(np.asarray(dcoords[d], dtype=np.float64))
+        if index:                                                # no coordinates needed, and only the truth value of `periodic`
+            data, cds, period, ring = self.tracer if tracer is None else tracer, [None, None], None, bool(periodic)
+        else:                                                    # the coordinates as given, in float64, and the period in their units
+            data, dcoords = self._plane_dcoords('find_contours', tracer, ' (or index=True)')
+            cds = [np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim)]
             period = self._x_period(periodic, cds[1], False, 'find_contours', plain=True)
             ring = period is not None
-        else:
-            period, ring = None, bool(periodic)
-        q, lead, lshape, coords = self._plane(data)
-        q = self._float(q)
+        q, lead, lshape, _ = self._float_plane(data)
         nslab, nx = q.shape[0], q.shape[2]
         if ring and nx < 2:
             raise Exception('find_contours: periodic needs at least two columns along the periodic dim')
         bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
-        N = bs.shape[1]
         cnt, ef, et, pts = self.ctx.contour_segments(q, bs, periodic=ring)
         off = np.concatenate([[0], np.cumsum(cnt.ravel().astype(np.int64))])
         walk, poff, closed, rpo = nat.join_segments(off, ef, et)
         polys, cl, wd = contour_polylines(walk, poff, closed, rpo, pts, nx=nx if ring else None,
-                                          ycoord=None if index else cds[0], xcoord=None if index else cds[1], period=period)
-        out = [[None] * N for _ in range(nslab)]
-        flags = [[None] * N for _ in range(nslab)]
-        winds = [[None] * N for _ in range(nslab)]
-        for s in range(nslab):
-            for j in range(N):                                   # j: the sorted level; order[s, j]: where the caller put it
-                k, r = int(order[s, j]), s * N + j
-                out[s][k], flags[s][k], winds[s][k] = polys[r], cl[r], wd[r]
-        if not lead:
-            out, flags, winds = out[0], flags[0], winds[0]
+                                          ycoord=cds[0], xcoord=cds[1], period=period)
+        out, flags, winds = self._in_caller_order(order, lead, polys, cl, wd)
         res = (out,) + ((flags,) if return_closed else ()) + ((winds,) if return_winding else ())
         return res if len(res) > 1 else out
 
