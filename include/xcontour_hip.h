@@ -494,7 +494,12 @@ int xc_contour_segments_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_
  *                       the polar cap it bounds measures 2 pi radius^2 -/+ S.
  *     row_min, row_max f64  the smallest / largest index-space row over the end points of the piece's segments
  *   length and area are exact sums of their float64 terms rounded once (fixed-point accumulators), and every other field is an
- *   integer reduction: the records do not depend on the order of the segments or of arrival.
+ *   integer reduction: the records do not depend on the order of the segments or of arrival.  Each sum has a window of 160 bits
+ *   under 2^top, top = 12 + the frexp exponent of a bound on one term fixed from the coordinates alone (length: 1.0000001 x the
+ *   largest cell diagonal, 3.2 on the sphere; area: 1.0000001 x max |Y'| x the largest cell width; the seam cell counts on a periodic
+ *   plane).  Every term of K12's records lies inside.  Of other records: the bits of a term under 2^(top - 160) are cut off (toward
+ *   zero; the sum is then exact in the cut terms), and a term of 2^top or more, or a non-finite one, makes THAT sum of THAT piece
+ *   NaN -- length and area each by their own window; every other piece of the call is untouched.
  *   layout: pieces packed by range: the pieces of range r are [poff[r], poff[r+1]), poff the exclusive scan of piece_count.  The order
  *     INSIDE a range is unspecified (sort by first_edge for the order of the host join).
  *   piece_count[nrange] is always written.  capacity >= sum(piece_count): the records are written, XC_OK.  Otherwise nothing is

@@ -1,6 +1,8 @@
 """Contour2D.cal_contour_pieces / Context.contour_pieces / xc_contour_pieces_dev (K13) on the GPU against the restatement
-contour_pieces_ref: the integer fields and the row extents equal, `length` within 1e-12 * length (K10's own bar), `area` within
-1e-12 * fsum(|terms|) (the sum is signed and cancels); every facade call is made twice and compared bit for bit."""
+contour_pieces_ref: the integer fields and the row extents equal, `length` within 1e-12 * length (K10's own bar), `area` on a
+Cartesian plane BIT FOR BIT the restatement's math.fsum (its terms are the kernel's: test_cpiece_records_host.py shows that the
+restatement's np.interp coordinates are the separately rounded ones), on the sphere within 1e-12 * fsum(|terms|) (the sum is signed
+and cancels; the device sin is not the host's); every facade call is made twice and compared bit for bit."""
 import math
 
 import numpy as np
@@ -51,7 +53,7 @@ def ref_period(periodic, latlon):
     return float(np.float64(np.deg2rad(np.float32(P)))) if latlon else P
 
 
-def check_level(got, ref, y, what=''):
+def check_level(got, ref, y, what='', latlon=False):
     """one level: the facade's table against the restatement's"""
     assert got.dtype.names == FIELDS, what
     assert got.size == ref.size, '%s: %d pieces, restatement %d' % (what, got.size, ref.size)
@@ -67,6 +69,10 @@ def check_level(got, ref, y, what=''):
     cl = ref['closed']
     assert np.isnan(got['area'][~cl]).all() and not np.isnan(got['area'][cl]).any(), what + ': area is NaN exactly for open pieces'
     da = np.abs(got['area'][cl] - ref['area'][cl])
+    if not latlon:                                                           # every term is the restatement's: the exact sum, rounded once
+        bad = np.flatnonzero(got['area'][cl].view(np.int64) != ref['area'][cl].view(np.int64))
+        assert bad.size == 0, '%s: area of %d rings is not fsum of its terms, first %r != %r' % (
+            what, bad.size, float(got['area'][cl][bad[0]]), float(ref['area'][cl][bad[0]]))
     assert (da <= 1e-12 * ref['area_abs'][cl]).all(), '%s: area off by %g of fsum(|terms|)' % (what, float(np.max(da / np.maximum(ref['area_abs'][cl], 1e-300))))
 
 
@@ -75,7 +81,7 @@ def check_plane(got, q2d, lv, y, x, latlon=False, periodic=False, what=''):
     ref = PR.pieces(np.asarray(q2d, dtype=np.float64), lv, fy, fx, latlon, ref_period(periodic, latlon))
     assert len(got) == len(ref)
     for k in range(len(ref)):
-        check_level(got[k], ref[k], y, '%s level %d' % (what, k))
+        check_level(got[k], ref[k], y, '%s level %d' % (what, k), latlon)
     return ref
 
 
