@@ -517,6 +517,32 @@ int xc_contour_pieces_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
 int xc_set_cpiece_workspace(xc_ctx* ctx, uint64_t bytes);
 int xc_last_cpiece_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K14 contour polylines: the join on the device
+ * The content of xc_join_segments (below) computed on the device from K12's records where the K12 _dev entry points left them, with
+ * the records already gathered into walk order: nothing is sorted or walked on the host.  Input as for K13: count[nrange], e_from,
+ * e_to, pts, with ny, nx of that call (plain or periodic: the ids alone decide the links).  2 ny nx < 2^31 and every range has fewer
+ * than 2^31 segments, else XC_EBADARG.
+ *   per polyline, packed by range, and inside a range in ascending first_edge order -- the order of xc_join_segments, no host sort:
+ *     poly_nseg int64  its segments;  poly_closed int32  1 for a ring;  poly_first_edge int64  the smallest e_from it contains
+ *   per segment, at its WALK POSITION: polylines laid out range by range in the order above (range r fills [off[r], off[r+1]), off the
+ *     exclusive scan of count: the polyline offsets are the running sum of poly_nseg), inside a polyline in walk order; an open
+ *     polyline starts at its segment without predecessor, a ring at its segment of smallest e_from:
+ *     pts_walk[total][4], e_from_walk[total]  the records of the segment that stands there, bit for bit;
+ *     order[total]  its index among the input records (xc_join_segments' `order`).  Each of the three may be NULL.
+ *   poly_count[nrange] is always written.  capacity >= sum(poly_count): everything is written, XC_OK.  Otherwise nothing but poly_count
+ *     is written and 1 is returned (capacity 0 with NULL arrays = count only).  The number of segments bounds the number of polylines.
+ *   Records that are no join's input are XC_EBADARG, as for xc_join_segments: an edge id outside [0, 2 ny nx), or an id that repeats
+ *     among the e_from or among the e_to of one range.  No input makes the call write outside the caller's arrays or loop unboundedly.
+ * The call waits for the stream twice (K12's counts; the polyline counts).  It works in K13's groups of ranges under K13's cap
+ * (xc_set_cpiece_workspace; the result does not depend on it).  With xc_set_kernel_timing on, xc_last_cjoin_profile returns the last
+ * call's device times in ms -- ms[0] edge tables (clear, scatter, link, check), ms[1] the label rounds, ms[2] roots and the ranking
+ * rounds, ms[3] placement (the scan along the tables), ms[4] the gather into walk order -- the number of rounds summed over the
+ * groups (labels and ranks), and the number of groups.                                                                          */
+int xc_contour_polylines_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                             int64_t ny, int64_t nx, int64_t capacity, uint64_t* poly_count, int64_t* poly_nseg, int32_t* poly_closed,
+                             int64_t* poly_first_edge, double* pts_walk, int64_t* e_from_walk, int64_t* order);
+int xc_last_cjoin_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -158,6 +158,8 @@ PROTOTYPES = {
     'xc_join_segments': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_contour_pieces_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _f64, _f64, _i64,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_contour_polylines_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_last_cjoin_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1107,6 +1109,53 @@ class Context(object):
             return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), pieces,
                                               inputs=(ycoord, xcoord), out_nbytes=((s1 - s0) * N * 8,), per_segment=(56,))
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+
+    def last_cjoin_profile(self):
+        """device times of the last `contour_polylines` batch under set_kernel_timing(True): dict(table_ms, label_ms, rank_ms,
+        place_ms, gather_ms, rounds, groups)"""
+        ms = (C.c_double * 5)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cjoin_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], label_ms=ms[1], rank_ms=ms[2], place_ms=ms[3], gather_ms=ms[4], rounds=r.value, groups=g.value)
+
+    def contour_polylines(self, q, contours, periodic=False):
+        """The contours joined into polylines on the device (K14, xc_contour_polylines_dev, on the device records of K12): what
+        `contour_segments` and `join_segments` give together, with the records already in walk order -- only those and the
+        per-polyline table are downloaded, nothing is sorted on the host.  q, contours and periodic as for `contour_segments`.
+        Returns (count uint64 (nslab, N); e_from_walk int64 (total,) and pts_walk float64 (total, 4): e_from[walk] and pts[walk] of
+        `contour_segments` / `join_segments`, bit for bit; poly_off (npoly + 1,) int64 into them; closed (npoly,) bool; rpo
+        (nrange + 1,) int64: the polylines of range r are [rpo[r], rpo[r+1])) -- with walk = arange(total), the arguments of
+        core.contour_polylines."""
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, _, N = _levels_of(contours, nslab)
+        _check_ascending(contours, 'xc_contour_polylines')
+        if periodic and nx < 2:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
+        if 2 * ny * nx >= 1 << 31:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_polylines: plane too large for 32-bit labels (2 ny nx < 2^31)')
+
+        def polylines(cnt, total, dn, ins, outs, recs):
+            if total == 0:
+                return (cnt, np.empty(0, dtype=np.int64), np.empty((0, 4), dtype=np.float64), np.empty(0, dtype=np.int64),
+                        np.empty(0, dtype=bool), np.zeros(cnt.shape, dtype=np.uint64))
+            (dpc,), (df, dto, dp, dfw, dpw, drec) = outs, recs
+            nseg, first, closed = drec.ptr, drec.ptr + 8 * total, drec.ptr + 16 * total       # one polyline per segment at most
+            self._check(self.lib.xc_contour_polylines_dev(self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, total,
+                                                          dpc.ptr, nseg, closed, first, dpw.ptr, dfw.ptr, None))
+            pc = dpc.download(cnt.shape, np.uint64)
+            npoly = int(pc.sum())
+            return (cnt, dfw.download((total,), np.int64), dpw.download((total, 4), np.float64), drec.download((npoly,), np.int64),
+                    drec.download((npoly,), np.int32, offset_bytes=16 * total).astype(bool), pc)
+
+        def one(s0, s1):
+            # beside K12's records: the polyline counts, the walk-ordered e_from and pts, and one polyline record per segment at
+            # most -- two 8-byte columns, then a 4-byte one
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), polylines,
+                                              out_nbytes=((s1 - s0) * N * 8,), per_segment=(8, 32, 20))
+        cnt, efw, ptw, nseg, closed, pc = self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+        poly_off = np.concatenate([[0], np.cumsum(nseg, dtype=np.int64)])
+        rpo = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
+        return cnt, efw, ptw, poly_off, closed, rpo
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):
         """Sliding-window contour lengths (xc_local_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); ycoord (ny,) /

@@ -928,7 +928,33 @@ class Contour2D(object):
         direction of travel in X: 0 for an ordinary ring, +1 or -1 for one that circles the globe; 0 for an open polyline.  A
         ring still repeats its first vertex, but with W != 0 its last vertex is the first displaced by W nx columns (W P in
         coordinates).  Without `periodic` every winding number is 0.
+
+        The same tracing with the join on the GPU, and all polylines as one vertex array: `trace_contours` (join='device',
+        packed=True); this method is trace_contours with join='host' and packed=False.
         """
+        return self.trace_contours(contours, tracer=tracer, index=index, return_closed=return_closed, periodic=periodic,
+                                   return_winding=return_winding)
+
+    def trace_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False,
+                       join='host', packed=False):
+        """
+        find_contours -- every argument before `join` and the nested return are find_contours', which states the rule -- with a
+        choice of where the segments are joined and of the form of the result.
+
+        `join`: 'host' -- the segment records are downloaded, sorted and joined on one host thread (xc_join_segments) -- or
+        'device': the join runs on the GPU (K14, xc_contour_polylines_dev) and only the walk-ordered records and the polyline
+        table are downloaded; the result is the same bit for bit.  The device join numbers edges in 32 bits: a plane with
+        2 ny nx >= 2^31 raises and names join='host'.  Any other value raises.
+
+        `packed`: True -- instead of one small array per polyline, ONE (M, 2) float64 vertex array for the whole call, built
+        with array operations only (no Python loop over polylines): returns (verts, vert_off, closed, winding, span).  Polyline
+        p has the vertices verts[vert_off[p]:vert_off[p + 1]] -- the same vertices, by the same rule, as the array the nested
+        return holds for it --, closed[p] (bool) and winding[p] (int64); span (N, 2), or (nslab, N, 2) with leading dims, int64:
+        the polylines of level k (where the caller put it) of slab s are [span[s, k, 0], span[s, k, 1]), in the nested order.
+        return_closed / return_winding do not apply.
+        """
+        if join not in ('host', 'device'):
+            raise Exception('trace_contours: join must be \'host\' or \'device\', got %r' % (join,))
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         if index:                                                # no coordinates needed, and only the truth value of `periodic`
@@ -943,9 +969,21 @@ class Contour2D(object):
         if ring and nx < 2:
             raise Exception('find_contours: periodic needs at least two columns along the periodic dim')
         bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
-        cnt, ef, et, pts = self.ctx.contour_segments(q, bs, periodic=ring)
-        off = np.concatenate([[0], np.cumsum(cnt.ravel().astype(np.int64))])
-        walk, poff, closed, rpo = nat.join_segments(off, ef, et)
+        if join == 'device':
+            _check_device_join(q.shape[1], nx)
+            cnt, _, pts, poff, closed, rpo = self.ctx.contour_polylines(q, bs, periodic=ring)
+            walk = np.arange(pts.shape[0], dtype=np.int64)
+        else:
+            cnt, ef, et, pts = self.ctx.contour_segments(q, bs, periodic=ring)
+            off = np.concatenate([[0], np.cumsum(cnt.ravel().astype(np.int64))])
+            walk, poff, closed, rpo = nat.join_segments(off, ef, et)
+        if packed:
+            verts, voff, cl, wd, rk = contour_polylines(walk, poff, closed, rpo, pts, nx=nx if ring else None,
+                                                        ycoord=cds[0], xcoord=cds[1], period=period, packed=True)
+            N = order.shape[1]
+            span = np.empty((nslab, N, 2), dtype=np.int64)                   # per sorted level -> where the caller put it
+            np.put_along_axis(span, order[:, :, None], np.stack([rk[:-1], rk[1:]], axis=1).reshape(nslab, N, 2), axis=1)
+            return verts, voff, cl, wd, (span if lead else span[0])
         polys, cl, wd = contour_polylines(walk, poff, closed, rpo, pts, nx=nx if ring else None,
                                           ycoord=cds[0], xcoord=cds[1], period=period)
         out, flags, winds = self._in_caller_order(order, lead, polys, cl, wd)
@@ -1324,7 +1362,7 @@ def _edges_from_levels(b, right_edge):
     return edges.astype(np.float64), binc, last_closed
 
 
-def contour_polylines(walk, poff, closed, rpo, pts, nx=None, ycoord=None, xcoord=None, period=None):
+def contour_polylines(walk, poff, closed, rpo, pts, nx=None, ycoord=None, xcoord=None, period=None, packed=False):
     """
     The vertex rule of Contour2D.find_contours on the host (no device): the joined segments -> polylines, laps and winding
     numbers.  walk (total,) int64: segment indices polyline by polyline in walk order; poff (npoly + 1,) into `walk`; closed
@@ -1340,6 +1378,10 @@ def contour_polylines(walk, poff, closed, rpo, pts, nx=None, ycoord=None, xcoord
     np.interp(c, arange(nx + 1), [xcoord..., xcoord[0] + period]) + m period in coordinates.  The winding number of a ring is
     m_last + (c_end[last] - c_start[first]) / nx, an integer; of an open polyline, 0.
     Returns (polys, closed, winding): per range a list of (n, 2) float64 arrays [row, column], of bools and of ints.
+    packed=True: the same polylines in ONE array, built with array operations only (no Python loop over polylines): returns
+    (verts (M, 2) float64, vert_off (nkept + 1,) int64, closed (nkept,) bool, winding (nkept,) int64, range_off (nrange + 1,)
+    int64): kept polyline p has the vertices verts[vert_off[p]:vert_off[p+1]], and those of range r are
+    [range_off[r], range_off[r+1]) -- polys[r][k] is polyline range_off[r] + k.
     """
     walk, poff, rpo = np.asarray(walk, dtype=np.int64), np.asarray(poff, dtype=np.int64), np.asarray(rpo, dtype=np.int64)
     pts = np.asarray(pts, dtype=np.float64).reshape(-1, 4)
@@ -1374,6 +1416,8 @@ def contour_polylines(walk, poff, closed, rpo, pts, nx=None, ycoord=None, xcoord
     elif ring:
         c1, c2 = c1 + (nx * m).astype(np.float64), c2 + (nx * m).astype(np.float64)
     S, E = np.stack([r1, c1], axis=1), np.stack([r2, c2], axis=1)
+    if packed:
+        return _packed_polylines(S, E, poff, np.asarray(closed, dtype=bool), wind, rpo)
     polys, cl, wd = [], [], []
     for r in range(rpo.size - 1):
         ps, cs, ws = [], [], []
@@ -1390,6 +1434,38 @@ def contour_polylines(walk, poff, closed, rpo, pts, nx=None, ycoord=None, xcoord
     return polys, cl, wd
 
 
+def _check_device_join(ny, nx):
+    """trace_contours(join='device'): K14 numbers the grid edges of a plane in 32 bits"""
+    if 2 * int(ny) * int(nx) >= 1 << 31:
+        raise Exception('trace_contours: join=\'device\' numbers the grid edges in 32 bits and a (%d, %d) plane has 2 ny nx '
+                        '>= 2^31 of them: use join=\'host\'' % (ny, nx))
+
+
+def _packed_polylines(S, E, poff, closed, wind, rpo):
+    """the vertex rule of contour_polylines for all polylines at once.  S, E (total, 2): start and end of every segment in walk
+    order.  Polyline p (segments [a, b)) has the candidate vertices S[a], E[a], ..., E[b-1]: they stand at [a + p, b + p + 1) of
+    one candidate array; a candidate stays when it heads its polyline or differs from the candidate before it; a polyline
+    stays when two or more of its candidates do."""
+    total, npoly = S.shape[0], poff.size - 1
+    if npoly == 0:
+        return (np.empty((0, 2), dtype=np.float64), np.zeros(1, dtype=np.int64), np.empty(0, dtype=bool),
+                np.empty(0, dtype=np.int64), np.zeros(rpo.size, dtype=np.int64))
+    nseg = np.diff(poff)
+    heads = poff[:-1] + np.arange(npoly, dtype=np.int64)                    # where each polyline's first candidate stands
+    V = np.empty((total + npoly, 2), dtype=np.float64)
+    V[heads] = S[poff[:-1]]
+    V[np.arange(total, dtype=np.int64) + np.repeat(np.arange(1, npoly + 1, dtype=np.int64), nseg)] = E
+    keep = np.ones(total + npoly, dtype=bool)
+    keep[1:] = (V[1:] != V[:-1]).any(axis=1)
+    keep[heads] = True
+    nvert = np.add.reduceat(keep.astype(np.int64), heads)
+    stays = nvert >= 2
+    keep &= np.repeat(stays, nseg + 1)
+    vert_off = np.concatenate([[0], np.cumsum(nvert[stays])]).astype(np.int64)
+    range_off = np.concatenate([[0], np.cumsum(stays)]).astype(np.int64)[rpo]
+    return np.ascontiguousarray(V[keep]), vert_off, closed[stays], np.asarray(wind, dtype=np.int64)[stays], range_off
+
+
 def find_contour(data, dims, level, period=[None, None], periodic=False):
     """
     The polylines of ONE level of a 2-D labelled field, in the call shape of the reference's scripts
@@ -1399,7 +1475,14 @@ def find_contour(data, dims, level, period=[None, None], periodic=False):
     A periodic X direction goes through the keyword `periodic` instead -- False, True (360) or the period in xdim's units --,
     handed to Contour2D.find_contours(periodic=...), which states what it means: the seam cell is traced, polylines run on
     past the seam, and a contour that circles the globe is one ring.
+    `trace_contour` is this function with the join on the GPU on request.
     """
+    return trace_contour(data, dims, level, period=period, periodic=periodic)
+
+
+def trace_contour(data, dims, level, period=[None, None], periodic=False, join='host'):
+    """find_contour with `join` passed through to Contour2D.trace_contours: 'host' (find_contour itself) or 'device' (the join on
+    the GPU, K14); the same polylines bit for bit."""
     if period is not None and any(p is not None for p in period):
         # (a periodic X direction: the keyword `periodic` of this function, not `period`)
         raise NotImplementedError('find_contour: period=%r is not supported yet (only [None, None]: no wrap across the plane\'s '
@@ -1409,7 +1492,7 @@ def find_contour(data, dims, level, period=[None, None], periodic=False):
     if len(ddims) != 2 or set(ddims) != {ydim, xdim}:
         raise Exception('find_contour expects a 2-D field on the dims %s' % [ydim, xdim])
     cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
-    return cm.find_contours(np.array([float(level)]), periodic=periodic)[0]
+    return cm.trace_contours(np.array([float(level)]), periodic=periodic, join=join)[0]
 
 
 def _level_order(vals, order):

@@ -8,7 +8,8 @@
 // Input: count[nrange], e_from, e_to, pts as xc_contour_segments[_periodic]_dev wrote them (a range = one (slab, contour)); E = 2 ny nx
 // bounds every edge id.  Labels, links and slots are 32-bit: E < 2^31 and every range has fewer than 2^31 segments (XC_EBADARG else).
 //
-// Phase A, per GROUP of consecutive ranges (as many as keep g E 4 bytes of table under the context's workspace cap, at least one; fewer
+// Phase A (scatter, link, round, unscatter and the groups live in xc_cpiece_link.h: K14, xc_cjoin.hip, shares them), per GROUP of
+// consecutive ranges (as many as keep g E 4 bytes of table under the context's workspace cap, at least one; fewer
 // than 2^31 segments per group; indices are group-local):
 //   k_cp_scatter  tab[range][e_from[i]] = i (the table is -1 everywhere else), label0 = e_from, prev0 = -1, the segment's range
 //   k_cp_link     next0[i] = tab[range][e_to[i]], and prev0[next0[i]] = i: prev is the inverse of next, no second table
@@ -48,64 +49,10 @@ namespace {
 #include "xc_binning.h"
 #include "xc_clen_cell.h"
 
-constexpr int CP_TPB = 256;
+#include "xc_cpiece_link.h"
+
 constexpr int CP_L = 5;                       // 32-bit limbs per accumulator: a 160-bit window, 148 bits of it below the bound
 constexpr int CP_OPEN = (int)0x80000000u;     // pslot: the piece is open
-constexpr int CP_ERR_EDGE = 1, CP_ERR_LINK = 2;
-
-// largest r in [lo, hi) with off[r] <= i (off ascending, off[lo] <= i < off[hi])
-__device__ __forceinline__ int64_t cp_range_of(const long long* __restrict__ off, int64_t lo, int64_t hi, long long i)
-{
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_cp_scatter(int64_t n, long long s0, const long long* __restrict__ off, int64_t r0, int64_t r1, long long E,
-                  const long long* __restrict__ e_from, int* __restrict__ tab, int* __restrict__ rid, int* __restrict__ lab,
-                  int* __restrict__ prv, int* __restrict__ err)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const int rl = (int)(cp_range_of(off, r0, r1, s0 + i) - r0);
-    const long long e = e_from[s0 + i];
-    rid[i] = rl;
-    prv[i] = -1;
-    if (e < 0 || e >= E) { lab[i] = 0x7fffffff; *err = CP_ERR_EDGE; return; }
-    lab[i] = (int)e;
-    tab[(size_t)rl * E + e] = (int)i;
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_cp_link(int64_t n, long long s0, long long E, const long long* __restrict__ e_to, const int* __restrict__ tab,
-               const int* __restrict__ rid, int* __restrict__ nxt, int* __restrict__ prv, int* __restrict__ err)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const long long e = e_to[s0 + i];
-    int j = -1;
-    if (e < 0 || e >= E) *err = CP_ERR_EDGE;
-    else j = tab[(size_t)rid[i] * E + e];
-    if (j >= n) j = -1;
-    nxt[i] = j;
-    if (j >= 0) prv[j] = (int)i;
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_cp_round(int64_t n, const int* __restrict__ lab, const int* __restrict__ nxt, const int* __restrict__ prv,
-                int* __restrict__ lab2, int* __restrict__ nxt2, int* __restrict__ prv2)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const int a = nxt[i], b = prv[i];
-    int l = lab[i], a2 = -1, b2 = -1;
-    if (a >= 0) { const int la = lab[a]; l = la < l ? la : l; a2 = nxt[a]; }
-    if (b >= 0) { const int lb = lab[b]; l = lb < l ? lb : l; b2 = prv[b]; }
-    lab2[i] = l; nxt2[i] = a2; prv2[i] = b2;
-}
 
 // roots take their slots: root[i] (group-local) for every segment, slot[i] (with the open bit) for roots only
 __global__ __launch_bounds__(CP_TPB)
@@ -148,16 +95,6 @@ void k_cp_bcast(int64_t n, long long s0, const int* __restrict__ root, const int
     const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
     if (i >= n) return;
     pslot[s0 + i] = slot[root[i]];
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_cp_unscatter(int64_t n, long long s0, long long E, const long long* __restrict__ e_from, const int* __restrict__ rid,
-                    int* __restrict__ tab)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const long long e = e_from[s0 + i];
-    if (e >= 0 && e < E) tab[(size_t)rid[i] * E + e] = -1;
 }
 
 // the window constant of the area terms: |1/2 (Ya' + Yb') (Xa - Xb)| <= max |Y'| x the largest cell width
@@ -343,8 +280,6 @@ void k_cp_finish(int64_t np, XC_CP_RECORDS, const unsigned long long* __restrict
 }
 #undef XC_CP_RECORDS
 
-inline unsigned cp_blocks(int64_t n) { return (unsigned)((n + CP_TPB - 1) / CP_TPB); }
-
 }  // namespace
 
 // One xc_contour_pieces_dev call.  Waits for the stream twice: for K12's counts (they size the groups and fix the rounds) and for the
@@ -381,26 +316,9 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     if (total == 0) return XC_OK;
     if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, "xc_contour_pieces: segments without their records");
 
-    // groups of consecutive ranges [r0, r1): the table rows fit the cap (one range always does), fewer than 2^31 segments
-    struct Group { int64_t r0, r1; };
-    std::vector<Group> groups;
+    // groups of consecutive ranges [r0, r1) (xc_cpiece_link.h)
     int64_t gmax = 1; long long nmax = 0;
-    {
-        int64_t rows_cap = (int64_t)(ctx->cpiece_cap / ((size_t)E * 4));
-        if (rows_cap < 1) rows_cap = 1;
-        int64_t r = 0;
-        while (r < nrange) {
-            while (r < nrange && hc[(size_t)r] == 0) ++r;                  // empty ranges in front of a group cost no table row
-            if (r >= nrange) break;
-            int64_t r1 = r + 1;
-            while (r1 < nrange && r1 - r < rows_cap && off[(size_t)r1 + 1] - off[(size_t)r] < (1ll << 31) - 1) ++r1;
-            while (r1 - 1 > r && hc[(size_t)r1 - 1] == 0) --r1;            // ... nor behind it
-            groups.push_back({r, r1});
-            if (r1 - r > gmax) gmax = r1 - r;
-            if (off[(size_t)r1] - off[(size_t)r] > nmax) nmax = off[(size_t)r1] - off[(size_t)r];
-            r = r1;
-        }
-    }
+    const std::vector<CpGroup> groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
     // workspace: off | poff | c0[2], err | pslot[total] | tab[gmax][E] | rid[nmax] | label, next, prev x 2 [nmax]
     const size_t b_off = al((size_t)(nrange + 1) * 8), b_small = 256, b_slot = al((size_t)total * 4);
     const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
@@ -440,13 +358,10 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
     mark(0);
     int rounds_total = 0;
-    for (const Group& g : groups) {
+    for (const CpGroup& g : groups) {
         const long long s0 = off[(size_t)g.r0];
         const int64_t n = off[(size_t)g.r1] - s0;
-        uint64_t cmaxg = 1;
-        for (int64_t r = g.r0; r < g.r1; ++r) if (hc[(size_t)r] > cmaxg) cmaxg = hc[(size_t)r];
-        int R = 1;                                                         // ceil(log2(largest count)) + 1
-        while ((1ull << (R - 1)) < cmaxg) ++R;
+        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
         const dim3 grid(cp_blocks(n)), blk(CP_TPB);
         int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
         hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);

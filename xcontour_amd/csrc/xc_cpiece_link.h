@@ -1,0 +1,109 @@
+// Phase A of the device joins, shared by K13 (xc_cpiece.hip) and K14 (xc_cjoin.hip): the dense edge tables of a GROUP of consecutive
+// ranges, the next / prev links, the pointer-doubling rounds, and the plan that cuts the ranges into groups.  xc_cpiece.hip's header
+// states the rule.  Included inside namespace xc { namespace { ... } }, like xc_binning.h.
+#pragma once
+
+constexpr int CP_TPB = 256;
+constexpr int CP_ERR_EDGE = 1, CP_ERR_LINK = 2;
+
+// largest r in [lo, hi) with off[r] <= i (off ascending, off[lo] <= i < off[hi])
+__device__ __forceinline__ int64_t cp_range_of(const long long* __restrict__ off, int64_t lo, int64_t hi, long long i)
+{
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_scatter(int64_t n, long long s0, const long long* __restrict__ off, int64_t r0, int64_t r1, long long E,
+                  const long long* __restrict__ e_from, int* __restrict__ tab, int* __restrict__ rid, int* __restrict__ lab,
+                  int* __restrict__ prv, int* __restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int rl = (int)(cp_range_of(off, r0, r1, s0 + i) - r0);
+    const long long e = e_from[s0 + i];
+    rid[i] = rl;
+    prv[i] = -1;
+    if (e < 0 || e >= E) { lab[i] = 0x7fffffff; *err = CP_ERR_EDGE; return; }
+    lab[i] = (int)e;
+    tab[(size_t)rl * E + e] = (int)i;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_link(int64_t n, long long s0, long long E, const long long* __restrict__ e_to, const int* __restrict__ tab,
+               const int* __restrict__ rid, int* __restrict__ nxt, int* __restrict__ prv, int* __restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const long long e = e_to[s0 + i];
+    int j = -1;
+    if (e < 0 || e >= E) *err = CP_ERR_EDGE;
+    else j = tab[(size_t)rid[i] * E + e];
+    if (j >= n) j = -1;
+    nxt[i] = j;
+    if (j >= 0) prv[j] = (int)i;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_round(int64_t n, const int* __restrict__ lab, const int* __restrict__ nxt, const int* __restrict__ prv,
+                int* __restrict__ lab2, int* __restrict__ nxt2, int* __restrict__ prv2)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int a = nxt[i], b = prv[i];
+    int l = lab[i], a2 = -1, b2 = -1;
+    if (a >= 0) { const int la = lab[a]; l = la < l ? la : l; a2 = nxt[a]; }
+    if (b >= 0) { const int lb = lab[b]; l = lb < l ? lb : l; b2 = prv[b]; }
+    lab2[i] = l; nxt2[i] = a2; prv2[i] = b2;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_cp_unscatter(int64_t n, long long s0, long long E, const long long* __restrict__ e_from, const int* __restrict__ rid,
+                    int* __restrict__ tab)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const long long e = e_from[s0 + i];
+    if (e >= 0 && e < E) tab[(size_t)rid[i] * E + e] = -1;
+}
+
+inline unsigned cp_blocks(int64_t n) { return (unsigned)((n + CP_TPB - 1) / CP_TPB); }
+
+// groups of consecutive ranges [r0, r1): the table rows fit the cap (one range always does), fewer than 2^31 segments; empty ranges in
+// front of a group or behind it cost no table row.  hc: the counts, off: their exclusive scan.  gmax / nmax: the most rows / segments
+// of one group.
+struct CpGroup { int64_t r0, r1; };
+inline std::vector<CpGroup> cp_plan_groups(size_t cap, long long E, int64_t nrange, const std::vector<uint64_t>& hc,
+                                           const std::vector<long long>& off, int64_t* gmax, long long* nmax)
+{
+    std::vector<CpGroup> groups;
+    *gmax = 1; *nmax = 0;
+    int64_t rows_cap = (int64_t)(cap / ((size_t)E * 4));
+    if (rows_cap < 1) rows_cap = 1;
+    int64_t r = 0;
+    while (r < nrange) {
+        while (r < nrange && hc[(size_t)r] == 0) ++r;
+        if (r >= nrange) break;
+        int64_t r1 = r + 1;
+        while (r1 < nrange && r1 - r < rows_cap && off[(size_t)r1 + 1] - off[(size_t)r] < (1ll << 31) - 1) ++r1;
+        while (r1 - 1 > r && hc[(size_t)r1 - 1] == 0) --r1;
+        groups.push_back({r, r1});
+        if (r1 - r > *gmax) *gmax = r1 - r;
+        if (off[(size_t)r1] - off[(size_t)r] > *nmax) *nmax = off[(size_t)r1] - off[(size_t)r];
+        r = r1;
+    }
+    return groups;
+}
+
+// the doubling rounds of a group: ceil(log2(its largest count)) + 1, from the host's counts
+inline int cp_rounds(const std::vector<uint64_t>& hc, const CpGroup& g)
+{
+    uint64_t cmaxg = 1;
+    for (int64_t r = g.r0; r < g.r1; ++r) if (hc[(size_t)r] > cmaxg) cmaxg = hc[(size_t)r];
+    int R = 1;
+    while ((1ull << (R - 1)) < cmaxg) ++R;
+    return R;
+}

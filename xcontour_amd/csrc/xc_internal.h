@@ -99,6 +99,7 @@ struct xc_ctx {
     void*  cpiece_ws = nullptr;   size_t cpiece_ws_bytes = 0;    // offsets, slots, the edge tables, labels and links
     void*  cpiece_acc = nullptr;  size_t cpiece_acc_bytes = 0;   // per-piece fixed-point accumulators
     float  cpiece_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpiece_rounds = 0, cpiece_groups = 0;   // table, rounds, roots, reductions (xc_set_kernel_timing)
+    float  cjoin_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cjoin_rounds = 0, cjoin_groups = 0;   // K14 (xc_cjoin.hip, on K13's workspace): table, label rounds, rank rounds, placement, emit
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -334,6 +335,9 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
                             const double* contours, int N, int contours_per_slab, int64_t capacity,
                             uint64_t* out_count, int64_t* e_from, int64_t* e_to, double* pts, int64_t* out_total);
 // K13: the pieces of K12's records (device pointers) and their statistics; waits for the stream twice
+int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                             int64_t ny, int64_t nx, int64_t capacity, uint64_t* poly_count, int64_t* poly_nseg, int32_t* poly_closed,
+                             int64_t* poly_first_edge, double* pts_walk, int64_t* e_from_walk, int64_t* order);
 int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
                           int64_t ny, int64_t nx, int periodic, const double* ycoord, const double* xcoord, double period, double radius,
                           int64_t capacity, uint64_t* piece_count, int64_t* first_edge, int64_t* nseg, int32_t* closed, int32_t* winding,
