@@ -373,6 +373,33 @@ int xc_contour_lengths_periodic(xc_ctx* ctx, const void* q, int q_dtype, int64_t
                                 const double* contours, int ncont, int contours_per_slab,
                                 double* out_len, uint64_t* out_nseg);
 
+/* ------------------------------------------------------------------ K15 integrals of a field along contours
+ * The line integral of `f` (the tracer's shape, float32 or float64) along every contour K10 traces, evaluated on the traced
+ * segments themselves (the reference's cal_contour_mean is an area-derivative estimate; nothing there walks the contour).
+ *   segments: exactly K10's -- cells, crossed levels, cases, saddles, end points, lengths `len`; with period != 0 the seam
+ *     cell of xc_contour_lengths_periodic among them (period == 0.0: two free edges);
+ *   F(u) at an end point u on the grid edge between two nodes: f mapped as the coordinates are -- the node's value on a
+ *     node (the other node does not enter), else (F1 - F0) * (x - i0) + F0 in float64, every operation rounded once; the
+ *     seam cell's right nodes are column 0;
+ *   term = (0.5 * (F(u) + F(v))) * len; a segment with a NaN F(u) or F(v) is skipped in EVERY output;
+ *   out_integral[slab][k] = sum of the terms, out_length[slab][k] = sum of len over the same segments, each times the radius
+ *     once when radius > 0; out_nseg[slab][k] = their number (may be NULL).  Both sums are NaN where the length sum is 0
+ *     (K10's rule); a level that met an infinite term has a NaN integral and keeps its length.
+ * With a NaN-free f, out_length and out_nseg are xc_contour_lengths' bit for bit.  Sums are bit-reproducible (signed
+ * fixed-point sums, independent of launch geometry and slabs per call).  contours, coordinates and the period: as for
+ * xc_contour_lengths / xc_contour_lengths_periodic (the host form checks them; the device form checks what it can without
+ * reading xcoord).  xc_last_clen_geometry reports this launch too.                                              */
+int xc_contour_line_integrals_dev(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype,
+                                  int64_t nslab, int64_t ny, int64_t nx,
+                                  const double* ycoord, const double* xcoord, double period, double radius,
+                                  const double* contours, int ncont, int contours_per_slab,
+                                  double* out_integral, double* out_length, uint64_t* out_nseg);
+int xc_contour_line_integrals(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype,
+                              int64_t nslab, int64_t ny, int64_t nx,
+                              const double* ycoord, const double* xcoord, double period, double radius,
+                              const double* contours, int ncont, int contours_per_slab,
+                              double* out_integral, double* out_length, uint64_t* out_nseg);
+
 /* ------------------------------------------------------------------ K11 local (sliding-window) contour lengths
  * Replaces the loop of the reference's tests/test_localLength.py (rolling(center=True).construct(stride=), one
  * find_contours call per window): per window, the length of ONE contour traced on the window alone.
@@ -646,7 +673,7 @@ typedef struct xc_hist_variant {
     int32_t G, cps, rpc;                                         /* K3S: workgroups, chunks per strip, rows per chunk */
 } xc_hist_variant;
 int xc_last_hist_variant(xc_ctx* ctx, xc_hist_variant* out);
-/* how the last xc_contour_lengths / xc_contour_lengths_dev call (or its _periodic form) launched K10, as the launcher chose it on the host.  All zero
+/* how the last xc_contour_lengths / xc_contour_lengths_dev call (or its _periodic form; or xc_contour_line_integrals(_dev): K15, whose copies take 16383 cells) launched K10, as the launcher chose it on the host.  All zero
  * when the last such call failed; bps = 0 (and bps_rule 0) when the plane has no cells.                                      */
 #define XC_CLEN_BPS_SHARE    1   /* bps = 2048 / nslab: the launch's share of ~2048 blocks */
 #define XC_CLEN_BPS_FLOOR    2   /* bps = 8: the floor under that share */

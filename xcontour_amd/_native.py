@@ -144,6 +144,8 @@ PROTOTYPES = {
                               _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'xc_contour_lengths_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
     'xc_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_contour_line_integrals_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    'xc_contour_line_integrals': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     'xc_local_contour_lengths_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     'xc_local_contour_lengths': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     # the periodic forms: the same lists with `double period` after xcoord
@@ -601,7 +603,7 @@ class Context(object):
         return self._last_record(self.lib.xc_last_hist_variant, HistVariant(), 'kernel', HIST_KERNELS, 'kernel')
 
     def last_clen_geometry(self):
-        """how the last contour_lengths call (its last batch) launched K10 (xc_last_clen_geometry): a dict of the record's fields,
+        """how the last contour_lengths / contour_line_integrals call (its last batch) launched K10 / K15 (xc_last_clen_geometry): a dict of the record's fields,
         'bps_rule' named ('share', 'floor', 'capacity', 'ntile'; None when the plane has no cells) and 'q_dtype' a numpy dtype (None
         after a failed call: then every field is 0)"""
         return self._last_record(self.lib.xc_last_clen_geometry, ClenGeometry(), 'bps_rule', CLEN_BPS_RULES, 'N')
@@ -987,6 +989,46 @@ class Context(object):
                                1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
             return lens, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+
+    def contour_line_integrals(self, q, f, contours, ycoord, xcoord, radius=0.0, period=None):
+        """Integrals of a field along contours (K15, xc_contour_line_integrals).  q and contours, ycoord, xcoord, radius, period as for
+        `contour_lengths`; f: the integrand, f32/f64, of q's shape (an array).  On K10's segments, each with the integrand mapped onto
+        its end points u, v like the coordinates: integral = sum of 0.5 (F(u) + F(v)) len, length = sum of len, both over the segments
+        whose F(u) and F(v) are not NaN, nseg their number.  Returns (integral f64 (nslab, N), length f64 (nslab, N), nseg uint64
+        (nslab, N)); integral and length are NaN where the length is 0, and a level that met an infinite term has a NaN integral.
+        A tracer with a device mirror (keep_resident) is read in place through the _dev entry point."""
+        q, (nslab, ny, nx) = _stack3(q)
+        f = _f48(_contig(f))
+        if tuple(f.shape) != (nslab, ny, nx):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_line_integrals: the integrand must have the shape of q, %r' % ((nslab, ny, nx),))
+        contours, per_slab, N = _levels_of(contours, nslab)
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_line_integrals')
+        if period is not None:
+            _check_finite('xc_contour_line_integrals', xcoord)
+            period = _check_period(period, xcoord, 'xc_contour_line_integrals')
+        mid = (0.0 if period is None else period, float(radius))
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, fb, cb = _stack_now(q, s0, s1), _part(f, 3, s0, s1), _part(contours, 2, s0, s1)
+            qp = self._mirror(qb)
+            if qp:
+                # the tracer is on the device already.  The device entry point trusts its caller, so what the host form checks itself
+                # (xc_forms.hip, the same texts) is checked here
+                _check_ascending(cb, 'xc_contour_line_integrals')
+                _check_finite('xc_contour_line_integrals', ycoord, xcoord)
+                with self._temporaries([fb, ycoord, xcoord, cb], [n * N * 8] * 3) as (df, dy, dx, dc, di, dl, dn):
+                    self._check(self.lib.xc_contour_line_integrals_dev(self.handle, qp, dtype_code(q.dtype), df.ptr, dtype_code(f.dtype),
+                                                                       n, ny, nx, dy.ptr, dx.ptr, *mid, dc.ptr, N, 1 if per_slab else 0,
+                                                                       di.ptr, dl.ptr, dn.ptr))
+                    return di.download((n, N), np.float64), dl.download((n, N), np.float64), dn.download((n, N), np.uint64)
+            integ, lens = np.empty((n, N), dtype=np.float64), np.empty((n, N), dtype=np.float64)
+            cnts = np.empty((n, N), dtype=np.uint64)
+            self._check(self.lib.xc_contour_line_integrals(self.handle, _ptr(qb), dtype_code(q.dtype), _ptr(fb), dtype_code(f.dtype),
+                                                           n, ny, nx, _ptr(ycoord), _ptr(xcoord), *mid, _ptr(cb), N, 1 if per_slab else 0,
+                                                           _ptr(integ), _ptr(lens), _ptr(cnts)))
+            return integ, lens, cnts
+        return self._batched(nslab, ny * nx * (q.dtype.itemsize + f.dtype.itemsize), one)
 
     def _with_segment_records(self, periodic, qb, cb, use, inputs=(), out_nbytes=(), per_segment=()):
         """K12's two passes over one batch, everything staged once.  Uploaded: the tracer `qb` (unless it has a device mirror), the

@@ -780,6 +780,68 @@ class Contour2D(object):
         lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
         return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
 
+    def _aligned_plane(self, who, integrand, data, shape):
+        """a labelled integrand over the dims of `data` (the tracer a contour method works on) in any order -> its values as
+        (S, ny, nx), the slabs in the tracer's order; `shape`: the tracer's own (S, ny, nx)"""
+        if not lb.is_labeled(integrand):
+            raise Exception('%s: the integrand should be a labelled array over the tracer\'s dims' % who)
+        v, dims, _, _ = lb.unwrap(integrand)
+        ddims = lb.unwrap(data, lazy=True)[1]
+        if len(dims) != len(ddims) or set(dims) != set(ddims):
+            raise Exception('%s: the integrand has the dims %r, the tracer %r' % (who, tuple(dims), tuple(ddims)))
+        lead = [d for d in ddims if d not in (self.dimEqV, self._xdim)]
+        order = [dims.index(d) for d in lead] + [dims.index(self.dimEqV), dims.index(self._xdim)]
+        g = np.transpose(np.asarray(v), order)
+        g = g.reshape((-1,) + g.shape[-2:])
+        if g.shape != tuple(shape):
+            raise Exception('%s: the integrand has the shape %r on the tracer\'s dims, the tracer %r' % (who, g.shape, tuple(shape)))
+        return np.ascontiguousarray(self._float(g))
+
+    def _line_integrals(self, who, contours, integrand, tracer, latlon, periodic):
+        """one K15 call behind cal_contour_line_integral / cal_contour_line_mean, opened like cal_contour_lengths -> (integral, length,
+        both (nslab, N) float64 per SORTED level, wrap: such an array -> the labelled result in the caller's level order)"""
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        data, _, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
+        q, lead, lshape, coords = self._float_plane(data)
+        g = self._aligned_plane(who, integrand, data, q.shape)
+        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
+        integ, lens, _ = self.ctx.contour_line_integrals(q, g, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
+
+        def wrap(v):
+            return self._wrap_contour(_level_order(v, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
+        return integ, lens, wrap
+
+    def cal_contour_line_integral(self, contours, integrand, tracer=None, latlon=False, periodic=False, return_length=False):
+        """
+        The integral of `integrand` along every contour, evaluated on the traced contour itself (K15,
+        xc_contour_line_integrals): wind speed along a PV contour, |grad q| along a tracer contour, LWA along the
+        reference state's contour.  (cal_contour_mean is the area-derivative estimate, which needs a second field and is
+        smeared over the bin width.)  Build-defined: the reference has no counterpart.
+
+        `contours`, `tracer`, `latlon`, `periodic`, the float32 cast of the coordinates and the order of the levels are
+        handled exactly as in cal_contour_lengths, and the segments are the ones that method sums.  `integrand`: a
+        labelled array over the tracer's dims in any order, of the tracer's shape.  It is mapped onto a segment's two end
+        points like the coordinates are (linear along the grid edge the point lies on, the node's value on a node), and
+        the segment adds 0.5 (F(u) + F(v)) times its length.  A segment with a NaN end-point value is left out of the
+        integral AND of the length returned here; a contour of total length 0 gives NaN; a contour that meets an
+        infinite value gives a NaN integral.  With latlon=True lengths are great-circle arcs times Rearth.  Sums are
+        bit-reproducible.  Returns (..., contour) in `self.dtype`; with return_length=True (integral, length), the length
+        over the same segments (cal_contour_lengths' own value when the integrand has no NaN).
+        """
+        integ, lens, wrap = self._line_integrals('cal_contour_line_integral', contours, integrand, tracer, latlon, periodic)
+        return (wrap(integ), wrap(lens)) if return_length else wrap(integ)
+
+    def cal_contour_line_mean(self, contours, integrand, tracer=None, latlon=False, periodic=False):
+        """
+        The mean of `integrand` along every contour: cal_contour_line_integral divided by the length of the same segments
+        (one float64 division; the radius of latlon=True cancels).  NaN where the length is NaN.  Arguments as for
+        cal_contour_line_integral.  Returns (..., contour) in `self.dtype`.
+        """
+        integ, lens, wrap = self._line_integrals('cal_contour_line_mean', contours, integrand, tracer, latlon, periodic)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return wrap(integ / lens)
+
     def cal_local_contour_lengths(self, window, stride=1, levels=None, min_periods=None, tracer=None, latlon=False,
                                   return_levels=False, periodic=False):
         """

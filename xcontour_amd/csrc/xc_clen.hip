@@ -52,10 +52,7 @@ __global__ __launch_bounds__(256)
 void k_clen_window(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx, int latlon,
                    int64_t nslab, int* __restrict__ c0, double period)
 {
-    double my, mx;
-    window_maxima<true>(fy, ny, fx, nx, period != 0.0, period, my, mx);
-    const double bound = latlon ? 3.2 : 1.0000001 * hypot(mx, my);
-    const int w = det_c0_from_bound(bound);
+    const int w = det_c0_from_bound(clen_segment_bound(fy, ny, fx, nx, latlon, period));
     for (int64_t s = threadIdx.x; s < nslab; s += 256) c0[s] = w;
 }
 

@@ -1,9 +1,9 @@
-// The per-cell rule of the contour-length kernels, shared by K10 (xc_clen.hip: all levels of a plane) and K11 (xc_lclen.hip: one
-// level per sliding window): the segments one NaN-free cell emits for one crossed level and their lengths, added to a fixed-point
-// accumulator in LDS.  The rule itself is stated in the header of xc_clen.hip.  Also here, because more than one kernel needs them:
+// The per-cell rule of the contour-length kernels, shared by K10 (xc_clen.hip: all levels of a plane), K11 (xc_lclen.hip: one
+// level per sliding window) and K15 (xc_cline.hip: line integrals): the segments one NaN-free cell emits for one crossed level and
+// their lengths (cell_segments), added to a fixed-point accumulator in LDS (cell_level).  The rule itself is stated in the header of xc_clen.hip.  Also here, because more than one kernel needs them:
 // the case index and the four edge points of a cell (cell_case, cell_edges: K10, K11 and K12's xc_cseg_cell.h), the fold of an LDS
 // accumulator into carried limbs (clen_carry, clen_carry_top: K10, K11) and the block-wide coordinate maxima behind the window
-// constants (window_maxima: k_clen_window, K13's k_cp_area_window).  Included inside namespace xc { namespace { ... } } after
+// constants (window_maxima: K13's k_cp_area_window; clen_segment_bound: k_clen_window, K15's k_cline_window).  Included inside namespace xc { namespace { ... } } after
 // xc_binning.h.
 #pragma once
 
@@ -58,11 +58,13 @@ __device__ __forceinline__ void cell_edges(double ul, double ur, double ll, doub
 }
 
 // One NaN-free cell and one crossed level: its (up to two) segments.  (rT, rB): the cell's rows as doubles, (cL, cR) its
-// columns; (yT, yB) / (xL, xR) the coordinates of those nodes.
-template <bool LATLON>
-__device__ __forceinline__ void cell_level(double ul, double ur, double ll, double lr, double c, double rT, double cL,
-                                           double yT, double yB, double xL, double xR,
-                                           unsigned long long* acc, unsigned* cnt, int c0w)
+// columns; (yT, yB) / (xL, xR) the coordinates of those nodes.  Every kept segment (coincident end points: dropped) goes to
+// emit(u, v, pu, pv, len) -- u, v: its end points' ids (0 top, 1 bottom, 2 left, 3 right); pu, pv: where they lie on their edge in index
+// space (the column of a top / bottom point, the row of a left / right one); len: seg_len of their coordinates.  The ONE definition of the
+// segments, their end points and their lengths: K10 and K11 sum `len` (cell_level), K15 a function of all five (xc_cline_cell.h).
+template <bool LATLON, typename Emit>
+__device__ __forceinline__ void cell_segments(double ul, double ur, double ll, double lr, double c, double rT, double cL,
+                                              double yT, double yB, double xL, double xR, Emit&& emit)
 {
     const bool a = ul > c, b = ur > c, d = ll > c, e = lr > c;
     const int cs = cell_case(ul, ur, ll, lr, c);
@@ -80,14 +82,25 @@ __device__ __forceinline__ void cell_level(double ul, double ur, double ll, doub
     auto col = [&](int i) { return i == 0 ? tc : i == 1 ? bc : i == 2 ? cL : cR; };
     auto ycd = [&](int i) { return i == 0 ? yT : i == 1 ? yB : i == 2 ? ly : ry; };
     auto xcd = [&](int i) { return i == 0 ? tx : i == 1 ? bx : i == 2 ? xL : xR; };
+    auto pos = [&](int i) { return i == 0 ? tc : i == 1 ? bc : i == 2 ? lr_ : rr; };
     // the first segment joins p and q; the saddles 6 / 9 add (bottom, left) / (bottom, right).  One loop body: the length
     // arithmetic (sin / cos / asin on the sphere) is emitted once
     const int nseg = (cs == 6 || cs == 9) ? 2 : 1;
 #pragma unroll 1
     for (int t = 0; t < nseg; ++t) {
         const int u = t == 0 ? p : 1, v = t == 0 ? q : (cs == 6 ? 2 : 3);
-        if (!(row(u) == row(v) && col(u) == col(v))) add_len(acc, cnt, seg_len<LATLON>(xcd(u), ycd(u), xcd(v), ycd(v)), c0w);
+        if (!(row(u) == row(v) && col(u) == col(v))) emit(u, v, pos(u), pos(v), seg_len<LATLON>(xcd(u), ycd(u), xcd(v), ycd(v)));
     }
+}
+
+// ... and their lengths added to one fixed-point accumulator (K10, K11)
+template <bool LATLON>
+__device__ __forceinline__ void cell_level(double ul, double ur, double ll, double lr, double c, double rT, double cL,
+                                           double yT, double yB, double xL, double xR,
+                                           unsigned long long* acc, unsigned* cnt, int c0w)
+{
+    cell_segments<LATLON>(ul, ur, ll, lr, c, rT, cL, yT, yB, xL, xR,
+                          [&](int, int, double, double, double len) { add_len(acc, cnt, len, c0w); });
 }
 
 // One LDS accumulator (the CLEN_WORDS words add_len adds to, and its count word) folded into carried limbs: words 1..3 give their
@@ -130,4 +143,14 @@ __device__ __forceinline__ void window_maxima(const double* __restrict__ fy, int
     __syncthreads();
     my = fmax(fmax(s_m[0][0], s_m[0][1]), fmax(s_m[0][2], s_m[0][3]));
     mx = fmax(fmax(s_m[1][0], s_m[1][1]), fmax(s_m[1][2], s_m[1][3]));
+}
+
+// K10's bound on one segment, from the plane's coordinates (every thread of a block of 256 calls it): pi on the unit sphere, else the
+// largest cell diagonal (period != 0: the seam cell, fx[nx-1] to fx[0] + period, among them)
+__device__ __forceinline__ double clen_segment_bound(const double* __restrict__ fy, int64_t ny, const double* __restrict__ fx, int64_t nx,
+                                                     int latlon, double period)
+{
+    double my, mx;
+    window_maxima<true>(fy, ny, fx, nx, period != 0.0, period, my, mx);
+    return latlon ? 3.2 : 1.0000001 * hypot(mx, my);
 }

@@ -1,5 +1,5 @@
 // C ABI, part 4: the host forms of the kernels outside the Keff chain -- row sums (K2), the squared gradient (K4), the local wave
-// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip; K11, xc_lclen.hip), contour segments (K12, xc_cseg.hip),
+// activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip; K11, xc_lclen.hip), line integrals along contours (K15, xc_cline.hip), contour segments (K12, xc_cseg.hip),
 // synthetic slabs -- and the records of what they launched.
 #include "xc_capi.h"
 #include <cmath>
@@ -99,6 +99,43 @@ static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
     XC_TRY(flush_in(ctx));
     XC_TRY(launch_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, periodic ? period : 0.0, radius, dc, ncont, contours_per_slab, dl, dn));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// period == 0.0: X has two free edges
+static int contour_line_integrals_host(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype, int64_t nslab, int64_t ny,
+                                       int64_t nx, const double* ycoord, const double* xcoord, double period, double radius,
+                                       const double* contours, int ncont, int contours_per_slab,
+                                       double* out_integral, double* out_length, uint64_t* out_nseg)
+{
+    if (!q || !f || !ycoord || !xcoord || !contours || !out_integral || !out_length || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
+        return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad arguments");
+    if ((q_dtype != XC_F32 && q_dtype != XC_F64) || (f_dtype != XC_F32 && f_dtype != XC_F64))
+        return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad dtype");
+    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: radius must be >= 0");
+    for (int64_t i = 0; i < ny; ++i)
+        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: coordinates must be finite");
+    for (int64_t i = 0; i < nx; ++i)
+        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: coordinates must be finite");
+    if (period != 0.0 && !check_period(xcoord, nx, period))
+        return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: period must be 0, or finite, of the sign of xcoord[nx-1] - xcoord[0] "
+                                     "and longer than that span, and nx >= 2");
+    const int64_t nc = contours_per_slab ? nslab : 1;
+    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_line_integrals: contours must be ascending without NaN");
+    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype), fb = cells * esize(f_dtype);
+    const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
+    XC_TRY(ensure_arena(ctx, al(qb) + al(fb) + al(yb) + al(xb) + al(cb) + 3 * al(ob)));
+    Stage st(ctx);
+    void* dq = st.take(qb); void* df = st.take(fb);
+    double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb); double* dc = (double*)st.take(cb);
+    double* di = st.out(out_integral, ob); double* dl = st.out(out_length, ob); uint64_t* dn = st.out(out_nseg, ob);
+    const void* pq; const void* pf;                          // (a tracer / integrand with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(stage_in(ctx, df, f, fb, &pf));
+    XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_contour_line_integrals(ctx, pq, q_dtype, pf, f_dtype, nslab, ny, nx, dy, dx, period, radius, dc, ncont, contours_per_slab,
+                                         di, dl, dn));
     XC_TRY(st.deliver());
     return xc_sync(ctx);
 }
@@ -253,6 +290,30 @@ int xc_last_clen_geometry(xc_ctx* ctx, xc_clen_geometry* out)
     if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_clen_geometry: bad arguments");
     *out = ctx->last_clen;
     return XC_OK;
+}
+
+// ------------------------------------------------------------------------------------ K15
+// (the device form cannot read the coordinates: its caller vouches for a period's sign and length)
+int xc_contour_line_integrals_dev(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                  const double* ycoord, const double* xcoord, double period, double radius,
+                                  const double* contours, int ncont, int contours_per_slab,
+                                  double* out_integral, double* out_length, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, launch_contour_line_integrals(ctx, q, q_dtype, f, f_dtype, nslab, ny, nx, ycoord, xcoord, period, radius,
+                                                            contours, ncont, contours_per_slab, out_integral, out_length, out_nseg));
+}
+
+int xc_contour_line_integrals(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                              const double* ycoord, const double* xcoord, double period, double radius,
+                              const double* contours, int ncont, int contours_per_slab,
+                              double* out_integral, double* out_length, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, contour_line_integrals_host(ctx, q, q_dtype, f, f_dtype, nslab, ny, nx, ycoord, xcoord, period, radius,
+                                                          contours, ncont, contours_per_slab, out_integral, out_length, out_nseg));
 }
 
 // ------------------------------------------------------------------------------------ K11

@@ -93,7 +93,7 @@ struct xc_ctx {
     void* single_ws = nullptr;  unsigned single_launches = 0;  int single_dirty_bins[2] = {0, 0};
     int last_keff_path = 0;     // last xc_keff_dev call: 0 min/max pass + histogram pass (two reads of the tracer), 1 the single-read kernel
     xc_hist_variant last_hist = {};   // last xc_hist(_dev) / xc_keff_dev call: the histogram instantiation and geometry launched (launch_three, launch_s4)
-    xc_clen_geometry last_clen = {};  // last xc_contour_lengths(_dev) call: K10's launch geometry (launch_contour_lengths)
+    xc_clen_geometry last_clen = {};  // last xc_contour_lengths(_dev) / xc_contour_line_integrals(_dev) call: K10's / K15's launch geometry
     // K13 (xc_cpiece.hip): the cap on the edge tables of one group of ranges, the grow-only workspaces and the last call's stage times
     size_t cpiece_cap = (size_t)1 << 30;
     void*  cpiece_ws = nullptr;   size_t cpiece_ws_bytes = 0;    // offsets, slots, the edge tables, labels and links
@@ -325,6 +325,11 @@ int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
 // K10's window constant (one segment's bound from the plane's coordinates) for `nslab` slabs, into c0[nslab]
 int launch_clen_window(xc_ctx* ctx, const double* ycoord, int64_t ny, const double* xcoord, int64_t nx, double period, int latlon,
                        int64_t nslab, int* c0);
+// K15: the line integral of `f` (the tracer's shape) along every contour, its length and its segment count; period as for K10
+int launch_contour_line_integrals(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype, int64_t nslab, int64_t ny,
+                                  int64_t nx, const double* ycoord, const double* xcoord, double period, double radius,
+                                  const double* contours, int N, int contours_per_slab, double* out_integral, double* out_length,
+                                  uint64_t* out_nseg);
 int launch_local_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                                  const double* ycoord, const double* xcoord, double period, double radius,
                                  int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
