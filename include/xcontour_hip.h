@@ -570,6 +570,42 @@ int xc_contour_polylines_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
                              int64_t* poly_first_edge, double* pts_walk, int64_t* e_from_walk, int64_t* order);
 int xc_last_cjoin_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K16 contour overturning: meridian crossings of selected pieces
+ * The reference's tests/test_breaking.py traces a PV contour and keeps "the largest contour fully encircling the pole" (its
+ * Subroutines 4-5).  The next step of a wave-breaking analysis is to find where that contour is OVERTURNED -- where one meridian meets
+ * it three times or more -- and how far in latitude the fold reaches.  Build-defined; it works in index space, needs no coordinates,
+ * and every output is an integer or a copy of a K12 value.
+ * Input as for K13: count[nrange], e_from, e_to, pts where the K12 _dev entry points left them, with ny, nx, periodic of that call.
+ * Pieces, closed, winding, nseg and first_edge are K13's.  2 ny nx < 2^31 and every range has fewer than 2^31 segments, else
+ * XC_EBADARG; so is an edge id outside [0, 2 ny nx).
+ *   select: 0 'all'         every piece
+ *           1 'circumpolar' every ring with winding != 0
+ *           2 'main'        of those, per range, the one ring with the most segments, ties broken by the smallest first_edge
+ *     select != 0 with periodic == 0 is XC_EBADARG (nothing is written): no piece goes round a plain plane.
+ *   A MERIDIAN CROSSING of a selected piece is the start point of any of its segments whose e_from is odd (it lies on a vertical
+ *     edge V(r, c)), or the end point of a segment without successor (the tail of an open piece) whose e_to is odd.  Its column is
+ *     (id >> 1) % nx, its row the stored r1 (a start point) or r2 (an end point) of that record, bit for bit.  On a ring every vertex
+ *     is counted once.  On the periodic plane V(r, 0) is cell 0's left edge and the seam cell's right edge, and is column 0.  Which
+ *     edge a point on a node belongs to is whatever K12 wrote: the ids are read, the field is not looked at again.
+ *   per (range, column), dense [nrange][nx]:
+ *     ncross int32  the crossings;  row_lo, row_hi f64  the smallest / largest crossing row, NaN where ncross == 0
+ *   per range, [nrange]:
+ *     nsel int32  the selected pieces;  main_first_edge int64 (-1: none), main_nseg int64 (0), main_winding int32 (0): the ring
+ *     'main' would pick, filled under every select on a periodic plane.  main_first_edge is the key under which K13 and K14 list
+ *     that ring.
+ *   A column of the main ring with ncross >= 3 is overturned; row_hi - row_lo there is the depth of the fold.  Every output is an
+ *   integer reduction (rows by their bit patterns: they are non-negative): nothing depends on the order of the segments or of arrival.
+ *   On XC_OK all seven arrays are fully written, whatever the records hold; there is no capacity protocol.
+ * The call waits for the stream twice (K12's counts; the word that says whether the ids were in range).  It works in K13's groups of
+ * ranges under K13's cap and in K13's workspace (xc_set_cpiece_workspace; the result does not depend on it).  With xc_set_kernel_timing
+ * on, xc_last_coverturn_profile returns the last call's device times in ms -- ms[0] edge tables (clear, scatter, link), ms[1] the
+ * doubling rounds, ms[2] per-piece sums and the selection, ms[3] the count (with the init and finish passes over the outputs) -- the
+ * number of rounds summed over the groups, and the number of groups.                                                             */
+int xc_contour_overturning_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                               int64_t ny, int64_t nx, int periodic, int select, int32_t* ncross, double* row_lo, double* row_hi, int32_t* nsel,
+                               int64_t* main_first_edge, int64_t* main_nseg, int32_t* main_winding);
+int xc_last_coverturn_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -162,6 +162,8 @@ PROTOTYPES = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_contour_polylines_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_last_cjoin_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_overturning_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_last_coverturn_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1198,6 +1200,59 @@ class Context(object):
         poly_off = np.concatenate([[0], np.cumsum(nseg, dtype=np.int64)])
         rpo = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
         return cnt, efw, ptw, poly_off, closed, rpo
+
+    # how `contour_overturning` selects pieces: the names and the library's codes
+    OVERTURN_SELECT = {'all': 0, 'circumpolar': 1, 'main': 2}
+
+    def last_coverturn_profile(self):
+        """device times of the last `contour_overturning` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, select_ms,
+        count_ms, rounds, groups)"""
+        ms = (C.c_double * 4)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_coverturn_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], select_ms=ms[2], count_ms=ms[3], rounds=r.value, groups=g.value)
+
+    def contour_overturning(self, q, contours, periodic=False, select='main'):
+        """Where the contours are overturned (K16, xc_contour_overturning_dev, on the device records of K12: the segment records
+        are never downloaded): the crossings of every meridian with the selected pieces of every contour.  q, contours and
+        periodic as for `contour_segments`; select: 'all' / 0 every piece, 'circumpolar' / 1 every ring of winding != 0, 'main' / 2
+        per contour the one such ring with the most segments (ties: the smallest first_edge) -- the last two on a periodic plane
+        only.  A crossing is a segment's start point on a vertical grid edge (e_from odd), or the end point on one of an open
+        piece's last segment; its column is (id >> 1) % nx, its row the record's.  Returns (ncross int32, row_lo, row_hi float64
+        (nslab, N, nx): the crossings of a column, their smallest / largest row, NaN without one; nsel int32, main_first_edge
+        int64, main_nseg int64, main_winding int32 (nslab, N): the selected pieces, and the ring 'main' picks (-1, 0, 0 without
+        one) under the key `contour_pieces` lists it by).  A column with ncross >= 3 is overturned."""
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, _, N = _levels_of(contours, nslab)
+        _check_ascending(contours, 'xc_contour_overturning')
+        sel = self.OVERTURN_SELECT.get(select, select) if isinstance(select, str) else select
+        if isinstance(sel, bool) or sel not in (0, 1, 2):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_overturning: select is \'all\', \'circumpolar\' or \'main\' (0, 1, 2), not %r' % (select,))
+        if sel != 0 and not periodic:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_overturning: select=%r needs periodic=True (no piece goes round a plain plane)' % (select,))
+        if periodic and nx < 2:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
+        if 2 * ny * nx >= 1 << 31:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_overturning: plane too large for 32-bit labels (2 ny nx < 2^31)')
+        types = (np.int32, np.float64, np.float64, np.int32, np.int64, np.int64, np.int32)
+
+        def overturning(cnt, total, dn, ins, outs, recs):
+            n = cnt.shape[0]
+            shapes = [(n, N, nx)] * 3 + [(n, N)] * 4
+            if total == 0:
+                fill = (0, np.nan, np.nan, 0, -1, 0, 0)
+                return tuple(np.full(sh, v, dtype=t) for sh, v, t in zip(shapes, fill, types))
+            df, dto, dp = recs
+            self._check(self.lib.xc_contour_overturning_dev(self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx,
+                                                            1 if periodic else 0, int(sel), *[b.ptr for b in outs]))
+            return tuple(b.download(sh, t) for b, sh, t in zip(outs, shapes, types))
+
+        def one(s0, s1):
+            # beside K12's records: the seven dense outputs -- 20 bytes per (contour, column), 24 per contour
+            n = s1 - s0
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), overturning,
+                                              out_nbytes=tuple(n * N * b for b in (nx * 4, nx * 8, nx * 8, 4, 8, 8, 4)))
+        return self._batched(nslab, ny * nx * q.dtype.itemsize + N * nx * 20, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):
         """Sliding-window contour lengths (xc_local_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); ycoord (ny,) /

@@ -955,6 +955,56 @@ class Contour2D(object):
         poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
         return self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
 
+    # ------------------------------------------------------------------ contour overturning
+    def cal_contour_overturning(self, contours, tracer=None, periodic=False, select='main'):
+        """
+        Where every contour is overturned, computed on the GPU (K12's segments, K13's pieces, K16, xc_contour_overturning_dev):
+        how often each meridian -- each column of the plane -- meets the selected pieces of a contour, and between which
+        latitudes.  The reference's tests/test_breaking.py keeps "the largest contour fully encircling the pole" and stops
+        there; this is the step after it.  Build-defined: the reference has no counterpart.
+
+        `contours`, `tracer` and the order of the levels as for cal_contour_pieces; `periodic` as for find_contours (False, True
+        or the period in the X coordinate's own units).  `select`: 'all' -- every piece --, 'circumpolar' -- every ring that goes
+        round the ring of columns (winding != 0) --, or 'main': per contour the one such ring with the most segments (ties: the
+        smallest first_edge).  The last two need `periodic`.
+
+        A crossing is a vertex of a selected piece that lies on a grid line along the equivalent dim (between the nodes (r, c)
+        and (r + 1, c)); every vertex counts once.  Returns a Dataset.  Over (..., contour, X): `ncross`, the crossings of that
+        column (int32), and `y_lo` / `y_hi`, the lowest / highest of them along the equivalent dim: the index-space rows mapped
+        with np.interp onto that coordinate as given (swapped where the coordinate descends, like cal_contour_pieces' y_min /
+        y_max), NaN where ncross is 0.  Over (..., contour): `nsel`, the selected pieces, and `main_first_edge` (-1: none),
+        `main_nseg`, `main_winding` (0: none): the ring 'main' picks, under the `first_edge` by which cal_contour_pieces lists it
+        (filled under every `select` on a periodic plane).  A column of the main ring with ncross >= 3 is overturned, and
+        y_hi - y_lo there is the depth of the fold.  Every value is bit-reproducible.
+        """
+        who = 'cal_contour_overturning'
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        if select not in nat.Context.OVERTURN_SELECT:
+            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
+        data, dcoords = self._plane_dcoords(who, tracer)
+        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
+        ring = self._x_period(periodic, xg, False, who, plain=True) is not None
+        if select != 'all' and not ring:
+            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
+                            'periodic=True or the period, or select=\'all\'' % (who, select))
+        q, lead, lshape, coords = self._float_plane(data)
+        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
+        res = self.ctx.contour_overturning(q, bs, periodic=ring, select=select)
+        res = [_level_order(v, order if v.ndim == 2 else order[:, :, None]) for v in res]   # where the caller put each level
+        ncross, row_lo, row_hi, nsel, mfe, mns, mw = res
+        ya, yb = np.interp(row_lo, np.arange(yg.size), yg), np.interp(row_hi, np.arange(yg.size), yg)
+        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
+        c['contour'] = np.asarray(ccoord)
+        c[self._xdim] = np.asarray(dcoords[self._xdim])
+        dims = tuple(lead) + ('contour',)
+        shape = tuple(lshape) + ncross.shape[1:2]
+        out = [lb.wrap(v.reshape(shape + v.shape[2:]), dims + (self._xdim,), c, name, data)
+               for name, v in (('ncross', ncross), ('y_lo', np.minimum(ya, yb)), ('y_hi', np.maximum(ya, yb)))]
+        out += [lb.wrap(v.reshape(shape), dims, c, name, data)
+                for name, v in (('nsel', nsel), ('main_first_edge', mfe), ('main_nseg', mns), ('main_winding', mw))]
+        return lb.merge(out, data)
+
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):
         """

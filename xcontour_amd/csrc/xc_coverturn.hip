@@ -1,0 +1,311 @@
+// K16 -- where a contour is OVERTURNED (gfx950): the crossings of every meridian with the selected pieces of K12's segment records,
+// on the device.
+//
+// The reference's tests/test_breaking.py traces a PV contour and keeps "the largest contour fully encircling the pole" (Subroutines
+// 4-5), and stops there.  The next step of a wave-breaking analysis asks where that contour folds over: where one meridian meets it
+// three times or more, and how far in latitude the fold reaches.  Build-defined, in index space, integers and copies of K12's values only.
+//
+// Input: count[nrange], e_from, e_to, pts as xc_contour_segments[_periodic]_dev wrote them (xc_cpiece.hip states the record and the
+// pieces); E = 2 ny nx bounds every edge id, labels and links are 32-bit (E < 2^31, fewer than 2^31 segments per range).
+//
+// Per GROUP of consecutive ranges (xc_cpiece_link.h: K13's groups under K13's cap, indices group-local):
+//   phase A (K13's kernels)  k_cp_scatter, k_cp_link, R x k_cp_round: label = the piece's smallest e_from (its first_edge), prev >= 0 on
+//                   every member of a ring and -1 on every member of an open piece
+//   k_co_root       root(i) = tab[range][label], the segment that carries its piece's sums; the sums start at 0
+//   k_co_piece      onto the root, integer atomic adds: nseg, and on a periodic plane the winding by K13's seam count (+1 where
+//                   c2 == nx, -1 where c1 == nx: on a ring every jump across the seam is one of each kind)
+//   k_co_pick       roots only: a root counts into nsel[range] when its piece is selected ('all': every piece; 'circumpolar': a ring
+//                   of winding != 0; one atomic per wave where the wave lies in one range), and a ring of winding != 0 bids for the
+//                   range's main ring with ONE 64-bit atomic max on (nseg << 31) | (2^31 - 1 - first_edge): most segments first, then
+//                   the smallest first_edge.  first_edge is unique within a range, so the winning key names one piece.
+//   k_co_count      one thread per segment of a selected piece ('main': the piece whose key won): a start point on a vertical edge
+//                   (e_from odd) is a crossing of column (e_from >> 1) % nx at row r1; the end point of a segment WITHOUT successor
+//                   (tab[range][e_to] holds no segment: the tail of an open piece) with e_to odd is one at row r2.  Integer atomic add
+//                   into ncross, atomic min / max on the row's bit pattern (rows are non-negative doubles: their bits order like
+//                   the values).  The root of the main ring leaves its winding.
+//   k_cp_unscatter  the table is handed on clean
+// Around the groups: k_co_init (counts 0, row_lo +inf, row_hi 0, no main ring) and k_co_finish (NaN rows where nothing crossed; the
+// winning key taken apart into main_first_edge and main_nseg; nsel of 'main').  The outputs are dense and fully written whatever the
+// records hold; every index taken from a table is checked before it addresses anything; every launch has a fixed amount of work.
+#include "xc_capi.h"
+#include <vector>
+
+namespace xc {
+namespace {
+
+#include "xc_cpiece_link.h"
+
+constexpr unsigned long long CO_FE = 0x7fffffffull;          // the low 31 bits of a key: 2^31 - 1 - first_edge
+
+__global__ __launch_bounds__(CP_TPB)
+void k_co_init(int64_t ncol, int64_t nrange, int* __restrict__ ncross, double* __restrict__ row_lo, double* __restrict__ row_hi,
+               int* __restrict__ nsel, long long* __restrict__ mfe, long long* __restrict__ mns, int* __restrict__ mw,
+               unsigned long long* __restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i < ncol) { ncross[i] = 0; row_lo[i] = __longlong_as_double(0x7ff0000000000000ll); row_hi[i] = 0.0; }
+    if (i < nrange) { nsel[i] = 0; mfe[i] = -1; mns[i] = 0; mw[i] = 0; key[i] = 0ull; }
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_co_root(int64_t n, long long E, const int* __restrict__ tab, const int* __restrict__ rid, const int* __restrict__ lab,
+               int* __restrict__ root, unsigned* __restrict__ pn, int* __restrict__ pw)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int l = lab[i];
+    int t = (l >= 0 && l < E) ? tab[(size_t)rid[i] * E + l] : (int)i;
+    if (t < 0 || t >= n) t = (int)i;
+    root[i] = t;
+    pn[i] = 0u; pw[i] = 0;
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_co_piece(int64_t n, long long s0, int wrap, int64_t nx, const double* __restrict__ pts, const int* __restrict__ root,
+                unsigned* __restrict__ pn, int* __restrict__ pw)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int t = root[i];
+    atomicAdd(pn + t, 1u);
+    if (wrap) {
+        const double xn = (double)nx;
+        const double c1 = pts[4 * (size_t)(s0 + i) + 1], c2 = pts[4 * (size_t)(s0 + i) + 3];
+        const int w = (int)(c2 == xn) - (int)(c1 == xn);
+        if (w != 0) atomicAdd(pw + t, w);
+    }
+}
+
+// the key a ring of winding != 0 bids with
+__device__ __forceinline__ unsigned long long co_key(unsigned nseg, int first_edge)
+{
+    return ((unsigned long long)nseg << 31) | (CO_FE - ((unsigned long long)(unsigned)first_edge & CO_FE));
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_co_pick(int64_t n, int64_t r0, int select, const int* __restrict__ rid, const int* __restrict__ root, const int* __restrict__ prv,
+               const int* __restrict__ lab, const unsigned* __restrict__ pn, const int* __restrict__ pw, int* __restrict__ nsel,
+               unsigned long long* __restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    const bool valid = i < n;
+    int r = -1;
+    bool sel = false;
+    if (valid) {
+        r = rid[i];
+        if (root[i] == (int)i) {
+            const bool circ = prv[i] >= 0 && pw[i] != 0;
+            sel = select == 0 || (select == 1 && circ);
+            if (circ) atomicMax(key + r0 + r, co_key(pn[i], lab[i]));
+        }
+    }
+    const int rf = __builtin_amdgcn_readfirstlane(r);
+    if (__all(!valid || r == rf)) {                                   // the wave lies in one range: one atomic for all its roots
+        const unsigned long long m = __ballot(sel);
+        if (m != 0ull && (threadIdx.x & 63) == 0) atomicAdd(nsel + r0 + rf, (int)__popcll(m));
+    } else if (sel) {
+        atomicAdd(nsel + r0 + r, 1);
+    }
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_co_count(int64_t n, long long s0, int64_t r0, long long E, int64_t nx, int select, const long long* __restrict__ e_from,
+                const long long* __restrict__ e_to, const double* __restrict__ pts, const int* __restrict__ tab,
+                const int* __restrict__ rid, const int* __restrict__ root, const int* __restrict__ prv, const int* __restrict__ lab,
+                const unsigned* __restrict__ pn, const int* __restrict__ pw, const unsigned long long* __restrict__ key,
+                int* __restrict__ ncross, double* __restrict__ row_lo, double* __restrict__ row_hi, int* __restrict__ mw)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int t = root[i], r = rid[i];                                // (k_co_root left 0 <= t < n)
+    const bool ring = prv[i] >= 0;
+    const int w = ring ? pw[t] : 0;
+    const bool circ = w != 0;
+    const bool ismain = circ && co_key(pn[t], lab[i]) == key[r0 + r];
+    if (ismain && t == (int)i) mw[r0 + r] = w;
+    if (!(select == 0 || (select == 1 ? circ : ismain))) return;
+    const size_t out0 = (size_t)(r0 + r) * (size_t)nx;
+    auto cross = [&](long long e, double row) {
+        const size_t at = out0 + (size_t)((e >> 1) % nx);
+        const unsigned long long b = (unsigned long long)__double_as_longlong(row);
+        atomicAdd(ncross + at, 1);
+        atomicMin((unsigned long long*)row_lo + at, b);
+        atomicMax((unsigned long long*)row_hi + at, b);
+    };
+    const long long ef = e_from[s0 + i];
+    if ((ef & 1) && ef >= 0 && ef < E) cross(ef, pts[4 * (size_t)(s0 + i)]);
+    if (!ring) {
+        const long long et = e_to[s0 + i];
+        if ((et & 1) && et >= 0 && et < E) {
+            const int j = tab[(size_t)r * E + et];
+            if (j < 0 || j >= n) cross(et, pts[4 * (size_t)(s0 + i) + 2]);      // no successor: the tail of its piece
+        }
+    }
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_co_finish(int64_t ncol, int64_t nrange, int select, const int* __restrict__ ncross, double* __restrict__ row_lo,
+                 double* __restrict__ row_hi, const unsigned long long* __restrict__ key, int* __restrict__ nsel,
+                 long long* __restrict__ mfe, long long* __restrict__ mns)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i < ncol && ncross[i] == 0) {
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        row_lo[i] = qnan; row_hi[i] = qnan;
+    }
+    if (i < nrange) {
+        const unsigned long long k = key[i];
+        if (k != 0ull) { mfe[i] = (long long)(CO_FE - (k & CO_FE)); mns[i] = (long long)(k >> 31); }
+        if (select == 2) nsel[i] = k != 0ull ? 1 : 0;
+    }
+}
+
+}  // namespace
+
+// One xc_contour_overturning_dev call.  Waits for the stream twice: for K12's counts (they size the groups and fix the rounds) and
+// for the word that says whether the records were K12's.
+int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                               int64_t ny, int64_t nx, int periodic, int select, int32_t* ncross, double* row_lo, double* row_hi, int32_t* nsel,
+                               int64_t* main_first_edge, int64_t* main_nseg, int32_t* main_winding)
+{
+    if (!count || !ncross || !row_lo || !row_hi || !nsel || !main_first_edge || !main_nseg || !main_winding || nrange < 1 || ny < 1 || nx < 1)
+        return fail(ctx, XC_EBADARG, "xc_contour_overturning: bad arguments");
+    if (select < 0 || select > 2) return fail(ctx, XC_EBADARG, "xc_contour_overturning: select is 0 (all), 1 (circumpolar) or 2 (main)");
+    if (select != 0 && !periodic)
+        return fail(ctx, XC_EBADARG, "xc_contour_overturning: select != 0 needs periodic != 0 (no piece goes round a plain plane)");
+    if (periodic && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_overturning: a periodic plane needs nx >= 2");
+    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_overturning: plane too large for 32-bit labels (2 ny nx < 2^31)");
+    if (nrange > ((int64_t)1 << 38) / nx) return fail(ctx, XC_EBADARG, "xc_contour_overturning: nrange nx must stay below 2^38");
+    const long long E = 2 * ny * nx;
+    const int wrap = periodic ? 1 : 0;
+    for (int k = 0; k < 4; ++k) ctx->coverturn_ms[k] = 0.f;
+    ctx->coverturn_rounds = 0; ctx->coverturn_groups = 0;
+
+    std::vector<uint64_t> hc((size_t)nrange);
+    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<long long> off((size_t)nrange + 1);
+    off[0] = 0;
+    for (int64_t r = 0; r < nrange; ++r) {
+        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_overturning: a range of 2^31 or more segments");
+        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
+    }
+    const long long total = off[(size_t)nrange];
+    if (total > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_overturning: segments without their records");
+
+    // groups of consecutive ranges [r0, r1) (xc_cpiece_link.h); none without segments
+    int64_t gmax = 0; long long nmax = 0;
+    std::vector<CpGroup> groups;
+    if (total > 0) groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
+    // workspace: off | key | err | tab[gmax][E] | rid[nmax] | label, next, prev x 2 [nmax]
+    const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_small = 256;
+    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_key + b_small + b_tab + 7 * b_n));
+    char* ws = (char*)ctx->cpiece_ws;
+    long long* d_off = (long long*)ws;
+    unsigned long long* key = (unsigned long long*)(ws + b_off);
+    int* d_err = (int*)(ws + b_off + b_key);
+    int* tab = (int*)((char*)d_err + b_small);
+    int* rid = (int*)((char*)tab + b_tab);
+    int* buf[6];
+    for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+
+    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
+    std::vector<std::pair<hipEvent_t, int>> marks;
+    auto mark = [&](int kind) {
+        if (!ctx->timing) return;
+        hipEvent_t ev;
+        if (hipEventCreate(&ev) != hipSuccess) return;
+        (void)hipEventRecord(ev, ctx->stream);
+        marks.push_back({ev, kind});
+    };
+    auto settle = [&]() {
+        for (size_t k = 1; k < marks.size(); ++k) {
+            float ms = 0.f;
+            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->coverturn_ms[marks[k].second] += ms;
+        }
+        for (auto& m : marks) (void)hipEventDestroy(m.first);
+        marks.clear();
+    };
+
+    const int64_t ncol = nrange * nx;
+    const dim3 ogrid(cp_blocks(ncol)), blk(CP_TPB);
+    mark(-1);
+    hipLaunchKernelGGL(k_co_init, ogrid, blk, 0, ctx->stream, ncol, nrange, (int*)ncross, row_lo, row_hi, (int*)nsel, (long long*)main_first_edge,
+                       (long long*)main_nseg, (int*)main_winding, key);
+    XC_HIP(ctx, hipGetLastError());
+    mark(3);
+    XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
+    if (total > 0) {
+        XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
+    }
+    mark(0);
+    int rounds_total = 0;
+    for (const CpGroup& g : groups) {
+        const long long s0 = off[(size_t)g.r0];
+        const int64_t n = off[(size_t)g.r1] - s0;
+        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
+        const dim3 grid(cp_blocks(n));
+        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
+        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
+        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
+        XC_HIP(ctx, hipGetLastError());
+        mark(0);
+        for (int k = 0; k < R; ++k) {
+            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
+            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
+        }
+        XC_HIP(ctx, hipGetLastError());
+        rounds_total += R;
+        mark(1);
+        // lab, prv: the labels and the ring marks; nxt, lab2, nxt2 are free from here on
+        int* root = nxt;
+        unsigned* pn = (unsigned*)lab2;
+        int* pw = nxt2;
+        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, root, pn, pw);
+        hipLaunchKernelGGL(k_co_piece, grid, blk, 0, ctx->stream, n, s0, wrap, nx, pts, root, pn, pw);
+        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, prv, lab, pn, pw, (int*)nsel, key);
+        XC_HIP(ctx, hipGetLastError());
+        mark(2);
+        hipLaunchKernelGGL(k_co_count, grid, blk, 0, ctx->stream, n, s0, g.r0, E, nx, select, (const long long*)e_from, (const long long*)e_to, pts,
+                           tab, rid, root, prv, lab, pn, pw, key, (int*)ncross, row_lo, row_hi, (int*)main_winding);
+        XC_HIP(ctx, hipGetLastError());
+        mark(3);
+        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
+        XC_HIP(ctx, hipGetLastError());
+        mark(0);
+    }
+    ctx->coverturn_rounds = rounds_total; ctx->coverturn_groups = (int)groups.size();
+    hipLaunchKernelGGL(k_co_finish, ogrid, blk, 0, ctx->stream, ncol, nrange, select, (const int*)ncross, row_lo, row_hi, key, (int*)nsel,
+                       (long long*)main_first_edge, (long long*)main_nseg);
+    XC_HIP(ctx, hipGetLastError());
+    mark(3);
+    int herr = 0;
+    XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    settle();
+    if (herr) return fail(ctx, XC_EBADARG, "xc_contour_overturning: an edge id outside [0, 2 ny nx)");
+    return XC_OK;
+}
+
+}  // namespace xc
+
+// ------------------------------------------------------------------------------------ C ABI
+int xc_contour_overturning_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                               int64_t ny, int64_t nx, int periodic, int select, int32_t* ncross, double* row_lo, double* row_hi, int32_t* nsel,
+                               int64_t* main_first_edge, int64_t* main_nseg, int32_t* main_winding)
+{
+    XC_CTX(ctx);
+    return xc::launch_contour_overturning(ctx, nrange, count, e_from, e_to, pts, ny, nx, periodic, select, ncross, row_lo, row_hi, nsel,
+                                          main_first_edge, main_nseg, main_winding);
+}
+
+int xc_last_coverturn_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
+{
+    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = (double)ctx->coverturn_ms[k];
+    if (rounds) *rounds = ctx->coverturn_rounds;
+    if (groups) *groups = ctx->coverturn_groups;
+    return XC_OK;
+}
