@@ -180,6 +180,36 @@ def det_totals(q2d, levels, ycoord, xcoord, latlon=False):
         return np.where(t == 0, np.nan, t * RADIUS if latlon else t)
 
 
+def launch_geometry(N, ny, nx, nslab, words=5, copy_cells=32767, wrap=False):
+    """the launch choices of the tile-walk contour kernels, restated: K10 (launch_contour_lengths: words = 5 LDS words per (level,
+    copy), copy_cells = 32767 cells per copy) and K15 (launch_contour_line_integrals: 10 words, 16383 cells).  LDS: the level values
+    (+ 2 sentinels) 8 B each, per (level, copy) `words` x 8 B + a 4 B count, 16 B of slack, 48 KiB in all: as many copies (8, 4, 2, 1)
+    as take every level, else one copy and level groups of G.  Tiles of 32 x 252 cells (wrap: the ring has nx cell columns); a block
+    gives a copy 32 x 256 / ncopy cell slots per tile, so it may walk copy_cells x ncopy // 8192 tiles.  Blocks per slab: 2048 // nslab
+    ('share'), at least 8 ('floor'), at least ntile / max_tiles ('capacity'), at most ntile ('ntile')"""
+    lds_of = lambda g, nc: (g + 2) * 8 + g * nc * (words * 8 + 4) + 16
+    ncopy = 8
+    while ncopy > 1 and lds_of(N, ncopy) > 48 * 1024:
+        ncopy //= 2
+    G = N if lds_of(N, ncopy) <= 48 * 1024 else (48 * 1024 - 32) // (8 + words * 8 + 4)
+    ncx = nx if wrap else nx - 1
+    ntj = -(-(ny - 1) // 32) if ny > 1 else 0
+    nti = -(-ncx // 252) if ncx > 0 else 0
+    ntile = ntj * nti
+    max_tiles = copy_cells * ncopy // (32 * 256)
+    bps, rule = 0, None
+    if ntile > 0:
+        bps, rule = 2048 // nslab, 'share'
+        if bps < 8:
+            bps, rule = 8, 'floor'
+        need = -(-ntile // max_tiles)
+        if bps < need:
+            bps, rule = need, 'capacity'
+        if bps > ntile:
+            bps, rule = ntile, 'ntile'
+    return dict(N=N, ncopy=ncopy, G=G, ngroup=-(-N // G), ntile=ntile, bps=bps, bps_rule=rule, nslab=nslab)
+
+
 def hashed_coords(n, salt=0, start=0.0, scale=1.0, descending=False):
     """n coordinates whose spacings scale (1 + 0.25 f(i)) differ in every cell (f hashed into [-1, 1), as in
     test_gpu_hist_variants.hashed); descending=True runs them from the top down"""

@@ -27,27 +27,9 @@ TOL = 1e-12
 
 # ------------------------------------------------------------------------------------------------------------------- launch model
 def expected_geometry(N, ny, nx, nslab):
-    """the choices of launch_contour_lengths (xc_clen.hip), restated: LDS copies, level groups, tiles, blocks per slab and their rule"""
-    lds_of = lambda g, nc: (g + 2) * 8 + g * nc * (5 * 8 + 4) + 16
-    ncopy = 8
-    while ncopy > 1 and lds_of(N, ncopy) > 48 * 1024:
-        ncopy //= 2
-    G = N if lds_of(N, ncopy) <= 48 * 1024 else (48 * 1024 - 32) // (8 + 5 * 8 + 4)
-    ntj = -(-(ny - 1) // 32) if ny > 1 else 0
-    nti = -(-(nx - 1) // 252) if nx > 1 else 0
-    ntile = ntj * nti
-    max_tiles = 32767 * ncopy // (32 * 256)
-    bps, rule = 0, None
-    if ntile > 0:
-        bps, rule = 2048 // nslab, 'share'
-        if bps < 8:
-            bps, rule = 8, 'floor'
-        need = -(-ntile // max_tiles)
-        if bps < need:
-            bps, rule = need, 'capacity'
-        if bps > ntile:
-            bps, rule = ntile, 'ntile'
-    return dict(N=N, ncopy=ncopy, G=G, ngroup=-(-N // G), ntile=ntile, bps=bps, bps_rule=rule, nslab=nslab)
+    """the choices of launch_contour_lengths (xc_clen.hip), restated: LDS copies, level groups, tiles, blocks per slab and their rule
+    (clength_ref.launch_geometry with K10's 5 words and 32767 cells per LDS copy)"""
+    return CR.launch_geometry(N, ny, nx, nslab, words=5, copy_cells=32767)
 
 
 def run(ctx, q, lv, y, x, latlon, want=None):
