@@ -606,6 +606,47 @@ int xc_contour_overturning_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
                                int64_t* main_first_edge, int64_t* main_nseg, int32_t* main_winding);
 int xc_last_coverturn_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K17 contour interior: what the selected pieces bound
+ * The threshold rule of the reference's cal_integral_within_contours sums over every node with q > c: cut-off blobs and filaments
+ * land in the same bucket as the vortex they left.  This call measures the region bounded by the SELECTED pieces alone -- with
+ * select 2, by the one ring K16 calls main -- and can return it as a mask.  Build-defined; index space; the field is not read again.
+ * Input as for K13 and K16: count[nrange], e_from, e_to, pts where the K12 _dev entry points left them, with ny, nx, periodic of that
+ * call.  Pieces, rings, winding, select (0 all, 1 circumpolar, 2 main) and the tie rule of the main ring are K16's.  2 ny nx < 2^31,
+ * every range has fewer than 2^31 segments, every edge id lies in [0, 2 ny nx), else XC_EBADARG; select != 0 with periodic == 0 is
+ * XC_EBADARG (nothing is written).  range = s ncont + k: nrange is a multiple of ncont, and nrange / ncont (at most 65535) is the
+ * number of slabs of w (with w_per_slab) and of f.
+ *   CROSSING FLAG  X[r][c], 0 <= r < ny - 1, 0 <= c < nx, is 1 iff the vertical edge V(r, c) carries a meridian crossing of a selected
+ *     piece under K16's definition: the start point of a segment with odd e_from, or the end point of a segment without successor
+ *     with odd e_to.  Column (id >> 1) % nx, row (id >> 1) / nx.  Setting the flag is idempotent; an edge is the start of at most one
+ *     segment per range in K12's records, so sum_r X[r][c] is K16's ncross[c] under the same select.
+ *   NODE PARITY    P[r][c] = XOR over r' < r of X[r'][c]; P[0][c] = 0: whether the node lies on the other side of the selected pieces
+ *     from row 0 of its own column.
+ *   INSIDE         inside = P ^ flip, flip 0 or 1.
+ *   per range, [nrange]:
+ *     n_in   int64  the inside nodes
+ *     sum_w  f64    the sum over the inside nodes of w[r][c]; w is double[ny][nx], or double[nslab][ny][nx] with w_per_slab != 0;
+ *                   w == NULL is weight 1 (sum_w == n_in)
+ *     sum_wf f64    the sum of w[r][c] f[s][r][c], each product rounded once; f is f32 (f_dtype XC_F32) or f64 [nslab][ny][nx], or
+ *                   NULL, and sum_wf is NULL exactly when f is
+ *     mask   uint8 [nrange][ny][nx], 1 inside; may be NULL
+ *   The sums are K13's: exact sums of their float64 terms rounded once, independent of order and launch geometry.  Each has a window
+ *   of 160 bits under 2^top, top = 12 + the frexp exponent of max |w| (max |w f|) over the finite values of the range's slab (all of
+ *   the plane, inside or not), never below -800; the bits of a term under 2^(top - 160) are cut off toward zero.  A NaN term is
+ *   skipped (as np.nansum does); a +-inf term makes THAT sum of THAT range NaN, and no other.
+ *   With select 0 on the records of a NaN-free field, P[r][c] == (q[r][c] > level) ^ (q[0][c] > level).  Beside NaN cells, and for
+ *   a vertex on a node, the ids are whatever K12 wrote: a crossing that no NaN-free cell saw is no crossing.
+ *   On XC_OK every output is fully written, whatever the records hold; there is no capacity protocol.
+ * The call waits for the stream twice (K12's counts; the word that says whether the ids were in range).  It works in K13's groups of
+ * ranges under K13's cap and in K13's workspace (xc_set_cpiece_workspace; the result does not depend on it), with ny ceil(nx / 32)
+ * 32-bit words of crossing flags per range of a group.  With xc_set_kernel_timing on, xc_last_cinterior_profile returns the last call's
+ * device times in ms -- ms[0] edge tables (clear, scatter, link), ms[1] the doubling rounds, ms[2] per-piece sums and the selection,
+ * ms[3] the marks and the scan (with the bounds of the windows and the finish pass) -- the number of rounds summed over the groups,
+ * and the number of groups.                                                                                                     */
+int xc_contour_interior_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                            int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
+                            const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask);
+int xc_last_cinterior_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -164,6 +164,9 @@ PROTOTYPES = {
     'xc_last_cjoin_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_contour_overturning_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_last_coverturn_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_interior_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                          _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    'xc_last_cinterior_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1253,6 +1256,72 @@ class Context(object):
             return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), overturning,
                                               out_nbytes=tuple(n * N * b for b in (nx * 4, nx * 8, nx * 8, 4, 8, 8, 4)))
         return self._batched(nslab, ny * nx * q.dtype.itemsize + N * nx * 20, one)
+
+    def last_cinterior_profile(self):
+        """device times of the last `contour_interior` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, select_ms,
+        scan_ms, rounds, groups)"""
+        ms = (C.c_double * 4)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cinterior_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], select_ms=ms[2], scan_ms=ms[3], rounds=r.value, groups=g.value)
+
+    def contour_interior(self, q, contours, w=None, f=None, periodic=False, select='main', flip=False, return_mask=False):
+        """What the selected pieces of every contour bound (K17, xc_contour_interior_dev, on the device records of K12: the segment
+        records are never downloaded).  q, contours, periodic and select as for `contour_overturning`.  A node (r, c) is INSIDE
+        when the selected pieces cross the grid line of column c between row 0 and row r an odd number of times (K16's meridian
+        crossings, one flag per vertical edge), the other nodes when `flip`.  w: None (weight 1), (ny, nx) or (nslab, ny, nx)
+        float64; f: None or (nslab, ny, nx) f32/f64.  Returns (n_in int64, sum_w float64, sum_wf float64 or None (nslab, N): the
+        inside nodes, the sum of w and of w f over them -- exact sums rounded once, NaN terms skipped, an infinite term gives NaN
+        --[, mask bool (nslab, N, ny, nx)]).  Only these cross to the host."""
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, _, N = _levels_of(contours, nslab)
+        _check_ascending(contours, 'xc_contour_interior')
+        sel = self.OVERTURN_SELECT.get(select, select) if isinstance(select, str) else select
+        if isinstance(sel, bool) or sel not in (0, 1, 2):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_interior: select is \'all\', \'circumpolar\' or \'main\' (0, 1, 2), not %r' % (select,))
+        if sel != 0 and not periodic:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_interior: select=%r needs periodic=True (no piece goes round a plain plane)' % (select,))
+        if periodic and nx < 2:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
+        if 2 * ny * nx >= 1 << 31:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_interior: plane too large for 32-bit labels (2 ny nx < 2^31)')
+        if w is not None:
+            w = _contig(w, np.float64)
+            if w.shape not in ((ny, nx), (nslab, ny, nx)):
+                raise XContourHipError(XC_EBADARG, 'xc_contour_interior: w must be (ny, nx) or (nslab, ny, nx)')
+        if f is not None:
+            f = _contig(_f48(np.asarray(f)))
+            if f.shape != (nslab, ny, nx):
+                raise XContourHipError(XC_EBADARG, 'xc_contour_interior: f must be (nslab, ny, nx)')
+        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
+        has_f, want_mask = f is not None, bool(return_mask)
+
+        def interior(cnt, total, dn, ins, outs, recs):
+            n = cnt.shape[0]
+            ins = list(ins)
+            dw = ins.pop(0) if w is not None else None
+            df_ = ins.pop(0) if has_f else None
+            outs = list(outs)
+            dni, dsw = outs[0], outs[1]
+            dsf = outs[2] if has_f else None
+            dm = outs[-1] if want_mask else None
+            rec = [b.ptr for b in recs] if total else [None, None, None]
+            self._check(self.lib.xc_contour_interior_dev(self.handle, cnt.size, dn.ptr, rec[0], rec[1], rec[2], ny, nx, 1 if periodic else 0,
+                                                         int(sel), 1 if flip else 0, N, dw.ptr if dw is not None else None, w_per_slab,
+                                                         df_.ptr if df_ is not None else None, dtype_code(f.dtype) if has_f else 0,
+                                                         dni.ptr, dsw.ptr, dsf.ptr if dsf is not None else None, dm.ptr if dm is not None else None))
+            res = (dni.download((n, N), np.int64), dsw.download((n, N), np.float64), dsf.download((n, N), np.float64) if has_f else None)
+            return res + ((dm.download((n, N, ny, nx), np.uint8).view(np.bool_),) if want_mask else ())
+
+        def one(s0, s1):
+            # beside K12's records: the weights and the integrand, three 8-byte results per contour, and the mask when asked for
+            n = s1 - s0
+            ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
+            nb = [n * N * 8, n * N * 8] + ([n * N * 8] if has_f else []) + ([n * N * ny * nx] if want_mask else [])
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), interior,
+                                              inputs=tuple(ins), out_nbytes=tuple(nb))
+        per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (N if want_mask else 0))
+        return self._batched(nslab, per, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):
         """Sliding-window contour lengths (xc_local_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); ycoord (ny,) /

@@ -1005,6 +1005,75 @@ class Contour2D(object):
                 for name, v in (('nsel', nsel), ('main_first_edge', mfe), ('main_nseg', mns), ('main_winding', mw))]
         return lb.merge(out, data)
 
+    def cal_integral_inside_contours(self, contours, tracer=None, integrand=None, periodic=False, select='main', side='upper',
+                                     return_mask=False):
+        """
+        Area, node count and integral of what the SELECTED pieces of every contour bound, computed on the GPU (K12's segments,
+        K13's pieces, K16's selection, K17, xc_contour_interior_dev).  Build-defined: the reference has no counterpart.
+
+        cal_integral_within_contours is the reference's threshold rule: it sums dA over every node with q > c (or q < c), so a
+        blob or a filament that broke away from the vortex stays in the vortex's bucket.  This method follows the contour
+        itself: with select='main' the region is bounded by the one ring cal_contour_overturning calls main -- "the largest
+        contour fully encircling the pole" of the reference's tests/test_breaking.py --, whatever the tracer does elsewhere,
+        and the difference from the threshold integral is what has been shed.
+
+        `contours`, `tracer`, `periodic`, `select` and the order of the levels as for cal_contour_overturning.  A vertex of a
+        selected piece on a grid line along the equivalent dim, between the nodes (r, c) and (r + 1, c), is a crossing of
+        column c (every such grid edge counts once).  Walking a column from its first row, a node is on the far side when the
+        crossings passed so far are odd in number.  `side`: 'upper' takes the side of the row with the larger equivalent-dim
+        coordinate -- the far side when that coordinate ascends, else the near one --, 'lower' the other.  With select='all'
+        on a NaN-free tracer the far side of level c is exactly (q > c) != (q[first row] > c), column by column; beside NaN
+        cells the crossings are those the segments of find_contours have, and a crossing no NaN-free cell sees is none.
+
+        The weight is this object's dA; `integrand`: a labelled array like the tracer, or None.  Returns a Dataset over
+        (..., contour): `area`, the sum of dA over the nodes of the region, `nodes`, their number (int64), and with an
+        integrand `integral`, the sum of dA * integrand, each product rounded once.  The sums are exact sums of their float64
+        terms rounded once: bit-reproducible, whatever the order; a NaN term is skipped, an infinite one gives NaN.  With
+        return_mask=True also `mask`, bool over (..., contour, Y, X).  A NaN level, or one no contour follows, has the whole
+        plane on one side.
+        """
+        who = 'cal_integral_inside_contours'
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        if select not in nat.Context.OVERTURN_SELECT:
+            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
+        if side not in ('upper', 'lower'):
+            raise Exception('%s: side should be \'upper\' or \'lower\', not %r' % (who, side))
+        data, dcoords = self._plane_dcoords(who, tracer)
+        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
+        ring = self._x_period(periodic, xg, False, who, plain=True) is not None
+        if select != 'all' and not ring:
+            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
+                            'periodic=True or the period, or select=\'all\'' % (who, select))
+        q, lead, lshape, coords = self._float_plane(data)
+        nslab, ny, nx = q.shape
+        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
+        dA = self._dA_array(ny, nx, nslab)[0]
+        if dA.ndim == 1:
+            dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
+        g = None
+        if integrand is not None:
+            g = self._integrand_plane(integrand)
+            if g.shape != q.shape:
+                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
+        ascends = yg.size < 2 or yg[-1] >= yg[0]
+        flip = (side == 'upper') != bool(ascends)
+        res = self.ctx.contour_interior(q, bs, w=dA, f=g, periodic=ring, select=select, flip=flip, return_mask=return_mask)
+        nodes, area, integral = (None if v is None else _level_order(v, order) for v in res[:3])
+        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
+        c['contour'] = np.asarray(ccoord)
+        dims = tuple(lead) + ('contour',)
+        shape = tuple(lshape) + nodes.shape[1:2]
+        out = [lb.wrap(area.reshape(shape), dims, c, 'area', data), lb.wrap(nodes.reshape(shape), dims, c, 'nodes', data)]
+        if integral is not None:
+            out.append(lb.wrap(integral.reshape(shape), dims, c, 'integral', data))
+        if return_mask:
+            m = _level_order(res[3], order[:, :, None, None])
+            cm = dict(c)
+            cm[self.dimEqV], cm[self._xdim] = np.asarray(dcoords[self.dimEqV]), np.asarray(dcoords[self._xdim])
+            out.append(lb.wrap(m.reshape(shape + (ny, nx)), dims + (self.dimEqV, self._xdim), cm, 'mask', data))
+        return lb.merge(out, data)
+
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):
         """

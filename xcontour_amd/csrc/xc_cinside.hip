@@ -1,0 +1,433 @@
+// K17 -- what lies INSIDE the selected pieces of a contour (gfx950): node counts, weighted sums and a mask of the region they bound, from
+// K12's segment records on the device.
+//
+// The package's other "integral within a contour" is the reference's threshold rule (every node with q > c), which puts cut-off blobs and
+// filaments into the same bucket as the vortex they broke away from.  K16 selects "the largest contour fully encircling the pole"; this
+// measures the region that one ring bounds.  Build-defined, in index space; the field is never read again.
+//
+// Input: count[nrange], e_from, e_to, pts as xc_contour_segments[_periodic]_dev wrote them; pieces, rings, winding, `select` and the main
+// ring's tie rule are K16's (xc_cpiece_select.h).  E = 2 ny nx < 2^31 bounds every edge id.
+//   X[r][c] = 1 iff the vertical edge V(r, c) carries a meridian crossing of a selected piece under K16's definition (the start point of a
+//             segment with odd e_from, or the end point of a successor-less segment with odd e_to): column (id >> 1) % nx, row
+//             (id >> 1) / nx.  Setting the flag is idempotent.
+//   P[r][c] = XOR over r' < r of X[r'][c]: whether node (r, c) lies on the other side of the selected pieces from row 0 of its column.
+//   inside  = P ^ flip.
+//   per range: n_in = the inside nodes, sum_w = sum of w over them, sum_wf = sum of w f (one correctly rounded product per node), and the
+//             mask itself.  The sums are K13's (xc_cpiece_sum.h): every term whole into CP_L limbs, rounded once.  The window's top sits
+//             12 bits above max |w| (max |w f|) over the finite values of the range's slab, found by one pass before the scan.  A NaN
+//             term is skipped; a +-inf term makes that sum of that range NaN.
+//
+// Per GROUP of consecutive ranges (xc_cpiece_link.h: K13's groups under K13's cap, indices group-local):
+//   the group's bit planes are cleared: ny rows of wpr = ceil(nx / 32) 32-bit words per range, bit c & 31 of word c >> 5 of row r is
+//                   X[r][c] -- the 64 lanes of a wave of the scan (consecutive columns) read two consecutive words per row
+//   phase A (K13's kernels), k_co_root, k_co_piece, k_co_pick (K16's selection)
+//   k_ci_mark       one thread per segment of a selected piece: an atomic OR of its crossing bit(s); every id is checked first
+//   k_cp_unscatter  the table is handed on clean
+//   k_ci_chunk      (only where the rows are cut into more than one chunk) the XOR of every bit-plane word over the rows of each chunk
+//   k_ci_scan       over the ranges from the end of the previous group to the end of this one (ranges without segments in front of the
+//                   group have no crossing: their P is 0 everywhere): a block is 256 consecutive columns x one chunk of rows x one
+//                   range.  A lane takes the XOR of the chunks above its own, then walks its rows with the parity in a register;
+//                   w and f are read along x; n_in and the limbs of both sums stay in the lane's registers.  One wave reduction and
+//                   one set of 64-bit integer atomics per wave close the pass.  The mask is written from the same walk.  Integer sums:
+//                   the result depends neither on the chunks nor on the launch geometry.
+// Around the groups: k_ci_bound (the maxima behind the windows), a last k_ci_scan for the ranges behind the last group, and k_ci_finish
+// (the limbs rounded to double).  All outputs are dense and fully written whatever the records hold; every index taken from a record or a
+// table is checked before it addresses anything; every launch has a fixed amount of work.
+#include "xc_capi.h"
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
+namespace xc {
+namespace {
+
+#include "xc_binning.h"
+
+#include "xc_cpiece_link.h"
+#include "xc_cpiece_select.h"
+#include "xc_cpiece_sum.h"
+
+constexpr int CI_TPB = 256;                   // the columns of one block of the scan
+constexpr int CI_MIN_ROWS = 4;                // a chunk of rows is never shorter (but for the last one) ...
+constexpr int CI_MAX_CHUNKS = 64;             // ... and a column is never cut into more chunks
+constexpr int64_t CI_BLOCKS = 4096;           // the rows are cut until the scan has about this many blocks
+constexpr unsigned long long CI_INF = 0x7ff0000000000000ull;
+
+template <typename T>
+__device__ __forceinline__ T ci_wave_sum(T v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long ci_wave_max(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_xor(v, d); v = o > v ? o : v; }
+    return v;
+}
+
+// the bit patterns of max |w| and max |w f| over the finite values of every slab: mx[2 s], mx[2 s + 1] (0 at the start).  FT: the type of f
+// (void: none)
+template <typename FT>
+__global__ __launch_bounds__(CI_TPB)
+void k_ci_bound(int64_t npl, const double* __restrict__ w, int w_per_slab, const FT* __restrict__ f, unsigned long long* __restrict__ mx)
+{
+    constexpr bool HASF = !std::is_void<FT>::value;
+    const int64_t s = blockIdx.y;
+    const double* wp = w ? w + (w_per_slab ? (size_t)s * (size_t)npl : 0) : nullptr;
+    unsigned long long mw = 0ull, mf = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * CI_TPB + threadIdx.x; i < npl; i += (int64_t)gridDim.x * CI_TPB) {
+        const double a = wp ? wp[i] : 1.0;
+        const unsigned long long ba = (unsigned long long)__double_as_longlong(fabs(a));
+        if (ba < CI_INF && ba > mw) mw = ba;
+        if constexpr (HASF) {
+            const double t = __dmul_rn(a, (double)f[(size_t)s * (size_t)npl + i]);
+            const unsigned long long bt = (unsigned long long)__double_as_longlong(fabs(t));
+            if (bt < CI_INF && bt > mf) mf = bt;
+        }
+    }
+    mw = ci_wave_max(mw);
+    if constexpr (HASF) mf = ci_wave_max(mf);
+    if ((threadIdx.x & 63) == 0) {
+        if (mw) atomicMax(mx + 2 * s, mw);
+        if constexpr (HASF) if (mf) atomicMax(mx + 2 * s + 1, mf);
+    }
+}
+
+// the top of a window from the bit pattern of the bound on one term
+__device__ __forceinline__ int ci_top(unsigned long long bound_bits) { return cp_top(det_c0_from_bound(__longlong_as_double((long long)bound_bits))); }
+
+__global__ __launch_bounds__(CP_TPB)
+void k_ci_mark(int64_t n, long long s0, int64_t r0, long long E, int64_t nx, int64_t wpr, size_t plane, int select,
+               const long long* __restrict__ e_from, const long long* __restrict__ e_to, const int* __restrict__ tab,
+               const int* __restrict__ rid, const int* __restrict__ root, const int* __restrict__ prv, const int* __restrict__ lab,
+               const unsigned* __restrict__ pn, const int* __restrict__ pw, const unsigned long long* __restrict__ key,
+               unsigned* __restrict__ bits)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= n) return;
+    const int t = root[i], r = rid[i];                                // (k_co_root left 0 <= t < n)
+    const bool ring = prv[i] >= 0;
+    int w; bool ismain;
+    if (!co_selected(select, ring, t, lab[i], pn, pw, key[r0 + r], w, ismain)) return;
+    auto cross = [&](long long e) {                                   // 0 <= e < E: the node e >> 1 lies on the plane
+        const long long node = e >> 1, row = node / nx, col = node - row * nx;
+        atomicOr(bits + (size_t)r * plane + (size_t)row * (size_t)wpr + (size_t)(col >> 5), 1u << (col & 31));
+    };
+    const long long ef = e_from[s0 + i];
+    if ((ef & 1) && ef >= 0 && ef < E) cross(ef);
+    if (!ring) {
+        const long long et = e_to[s0 + i];
+        if ((et & 1) && et >= 0 && et < E) {
+            const int j = tab[(size_t)r * E + et];
+            if (j < 0 || j >= n) cross(et);                           // no successor: the tail of its piece
+        }
+    }
+}
+
+// cpar[g][chunk][word] = the XOR of the bit plane's words over the rows of the chunk
+__global__ __launch_bounds__(CP_TPB)
+void k_ci_chunk(int64_t nwords, int64_t ny, int64_t wpr, int64_t rc, int64_t nchunk, const unsigned* __restrict__ bits,
+                unsigned* __restrict__ cpar)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= nwords) return;
+    const int64_t word = i % wpr, ch = (i / wpr) % nchunk, g = i / (wpr * nchunk);
+    const int64_t ra = ch * rc, rb = ra + rc < ny ? ra + rc : ny;
+    const unsigned* bp = bits + (size_t)g * (size_t)ny * (size_t)wpr + (size_t)word;
+    unsigned x = 0u;
+    for (int64_t r = ra; r < rb; ++r) x ^= bp[(size_t)r * (size_t)wpr];
+    cpar[i] = x;
+}
+
+// Ranges [ra, ra + nr): block b is (column block, chunk, range).  Ranges of [g0, g1) have the bit plane bits[range - g0]; the others none.
+template <typename FT, bool MASK>
+__global__ __launch_bounds__(CI_TPB)
+void k_ci_scan(int64_t ra, int64_t g0, int64_t g1, int64_t ny, int64_t nx, int64_t wpr, int64_t ncb, int64_t rc, int64_t nchunk, int ncont,
+               unsigned flip, const unsigned* __restrict__ bits, const unsigned* __restrict__ cpar, const double* __restrict__ w,
+               int w_per_slab, const FT* __restrict__ f, const unsigned long long* __restrict__ mx, unsigned long long* __restrict__ acc,
+               unsigned long long* __restrict__ cnt, int* __restrict__ flg, unsigned char* __restrict__ mask)
+{
+    constexpr bool HASF = !std::is_void<FT>::value;
+    const int64_t b = blockIdx.x;
+    const int64_t cb = b % ncb, ch = (b / ncb) % nchunk, r = ra + b / (ncb * nchunk);
+    const int64_t c = cb * CI_TPB + threadIdx.x;
+    const bool active = c < nx;
+    const int64_t s = r / ncont;
+    const bool has = r >= g0 && r < g1;
+    const size_t npl = (size_t)ny * (size_t)nx;
+    const int64_t cw = c >> 5;
+    const int cs = (int)(c & 31);
+    const unsigned* bp = bits + (has ? (size_t)(r - g0) * (size_t)ny * (size_t)wpr : 0) + (size_t)cw;
+    const double* wp = w ? w + (w_per_slab ? (size_t)s * npl : 0) + (size_t)c : nullptr;
+    const int top_w = ci_top(mx[2 * s]);
+    int top_f = 0;
+    if constexpr (HASF) top_f = ci_top(mx[2 * s + 1]);
+
+    unsigned p = flip;
+    if (has && active)
+        for (int64_t k = 0; k < ch; ++k) p ^= (cpar[(size_t)((r - g0) * nchunk + k) * (size_t)wpr + (size_t)cw] >> cs) & 1u;
+    unsigned long long nin = 0ull, aw[CP_L], af[CP_L];
+#pragma unroll
+    for (int l = 0; l < CP_L; ++l) { aw[l] = 0ull; af[l] = 0ull; }
+    int bad = 0;
+    const int64_t row0 = ch * rc, row1 = row0 + rc < ny ? row0 + rc : ny;
+    if (active) {
+        for (int64_t row = row0; row < row1; ++row) {
+            const size_t at = (size_t)row * (size_t)nx;
+            if (p) {
+                ++nin;
+                const double a = wp ? wp[at] : 1.0;
+                if (a == a && !cp_add_private(aw, a, top_w)) bad |= 1;
+                if constexpr (HASF) {
+                    const double t = __dmul_rn(a, (double)f[(size_t)s * npl + at + (size_t)c]);
+                    if (t == t && !cp_add_private(af, t, top_f)) bad |= 2;
+                }
+            }
+            if constexpr (MASK) mask[(size_t)r * npl + at + (size_t)c] = (unsigned char)p;
+            if (has) p ^= (bp[(size_t)row * (size_t)wpr] >> cs) & 1u;
+        }
+    }
+    // one wave, one set of atomics
+    nin = ci_wave_sum(nin);
+#pragma unroll
+    for (int l = 0; l < CP_L; ++l) aw[l] = ci_wave_sum(aw[l]);
+    if constexpr (HASF) {
+#pragma unroll
+        for (int l = 0; l < CP_L; ++l) af[l] = ci_wave_sum(af[l]);
+    }
+    const unsigned long long anybad1 = __ballot(bad & 1), anybad2 = __ballot(bad & 2);
+    if ((threadIdx.x & 63) == 0) {
+        if (nin) atomicAdd(cnt + r, nin);
+        unsigned long long* pa = acc + (size_t)r * 2 * CP_L;
+#pragma unroll
+        for (int l = 0; l < CP_L; ++l) if (aw[l]) atomicAdd(pa + l, aw[l]);
+        if constexpr (HASF) {
+#pragma unroll
+            for (int l = 0; l < CP_L; ++l) if (af[l]) atomicAdd(pa + CP_L + l, af[l]);
+        }
+        const int fl = (anybad1 ? 1 : 0) | (anybad2 ? 2 : 0);
+        if (fl) atomicOr(flg + r, fl);
+    }
+}
+
+__global__ __launch_bounds__(CP_TPB)
+void k_ci_finish(int64_t nrange, int ncont, const unsigned long long* __restrict__ acc, const unsigned long long* __restrict__ cnt,
+                 const int* __restrict__ flg, const unsigned long long* __restrict__ mx, long long* __restrict__ n_in,
+                 double* __restrict__ sum_w, double* __restrict__ sum_wf)
+{
+    const int64_t r = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (r >= nrange) return;
+    const int64_t s = r / ncont;
+    const int fl = flg[r];
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    n_in[r] = (long long)cnt[r];
+    sum_w[r] = (fl & 1) ? qnan : cp_to_double(acc + (size_t)r * 2 * CP_L, ci_top(mx[2 * s]));
+    if (sum_wf) sum_wf[r] = (fl & 2) ? qnan : cp_to_double(acc + (size_t)r * 2 * CP_L + CP_L, ci_top(mx[2 * s + 1]));
+}
+
+}  // namespace
+
+// One xc_contour_interior_dev call.  Waits for the stream twice: for K12's counts (they size the groups and fix the rounds) and for the
+// word that says whether the records were K12's.
+int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                            int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
+                            const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask)
+{
+    if (!count || !n_in || !sum_w || nrange < 1 || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_contour_interior: bad arguments");
+    if (select < 0 || select > 2) return fail(ctx, XC_EBADARG, "xc_contour_interior: select is 0 (all), 1 (circumpolar) or 2 (main)");
+    if (select != 0 && !periodic)
+        return fail(ctx, XC_EBADARG, "xc_contour_interior: select != 0 needs periodic != 0 (no piece goes round a plain plane)");
+    if (flip != 0 && flip != 1) return fail(ctx, XC_EBADARG, "xc_contour_interior: flip is 0 or 1");
+    if (ncont < 1 || nrange % ncont != 0) return fail(ctx, XC_EBADARG, "xc_contour_interior: nrange must be a multiple of ncont >= 1");
+    if ((f == nullptr) != (sum_wf == nullptr)) return fail(ctx, XC_EBADARG, "xc_contour_interior: f and sum_wf go together");
+    if (f && f_dtype != XC_F32 && f_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_interior: f_dtype is XC_F32 or XC_F64");
+    if (periodic && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_interior: a periodic plane needs nx >= 2");
+    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_interior: plane too large for 32-bit labels (2 ny nx < 2^31)");
+    const long long E = 2 * ny * nx;
+    const int wrap = periodic ? 1 : 0;
+    const int64_t nslab = nrange / ncont;
+    if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_contour_interior: more than 65535 slabs");
+    for (int k = 0; k < 4; ++k) ctx->cinterior_ms[k] = 0.f;
+    ctx->cinterior_rounds = 0; ctx->cinterior_groups = 0;
+
+    std::vector<uint64_t> hc((size_t)nrange);
+    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<long long> off((size_t)nrange + 1);
+    off[0] = 0;
+    for (int64_t r = 0; r < nrange; ++r) {
+        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_interior: a range of 2^31 or more segments");
+        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
+    }
+    const long long total = off[(size_t)nrange];
+    if (total > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_interior: segments without their records");
+
+    // groups of consecutive ranges [r0, r1) (xc_cpiece_link.h); none without segments
+    int64_t gmax = 0; long long nmax = 0;
+    std::vector<CpGroup> groups;
+    if (total > 0) groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
+    // the scan's geometry: 256 columns x rc rows x one range per block
+    const int64_t wpr = (nx + 31) / 32, ncb = (nx + CI_TPB - 1) / CI_TPB;
+    int64_t nchunk = (CI_BLOCKS + ncb * nrange - 1) / (ncb * nrange);
+    nchunk = std::min<int64_t>(std::min<int64_t>(nchunk, CI_MAX_CHUNKS), std::max<int64_t>(1, ny / CI_MIN_ROWS));
+    const int64_t rc = (ny + nchunk - 1) / nchunk;
+    nchunk = (ny + rc - 1) / rc;
+    const size_t plane = (size_t)ny * (size_t)wpr;
+    // workspace: off | key, nsel, mx, acc, cnt, flg (cleared together) | err | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | tab[gmax][E]
+    //            | rid[nmax] | label, next, prev x 2 [nmax]
+    const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_nsel = al((size_t)nrange * 4);
+    const size_t b_mx = al((size_t)nslab * 16), b_acc = al((size_t)nrange * 2 * CP_L * 8), b_cnt = al((size_t)nrange * 8), b_flg = al((size_t)nrange * 4);
+    const size_t b_zero = b_key + b_nsel + b_mx + b_acc + b_cnt + b_flg, b_small = 256;
+    const size_t b_bits = al((size_t)gmax * plane * 4), b_cpar = al((size_t)gmax * (size_t)nchunk * (size_t)wpr * 4);
+    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_zero + b_small + b_bits + b_cpar + b_tab + 7 * b_n));
+    char* ws = (char*)ctx->cpiece_ws;
+    long long* d_off = (long long*)ws;
+    unsigned long long* key = (unsigned long long*)(ws + b_off);
+    int* nsel = (int*)((char*)key + b_key);
+    unsigned long long* mx = (unsigned long long*)((char*)nsel + b_nsel);
+    unsigned long long* acc = (unsigned long long*)((char*)mx + b_mx);
+    unsigned long long* cnt = (unsigned long long*)((char*)acc + b_acc);
+    int* flg = (int*)((char*)cnt + b_cnt);
+    int* d_err = (int*)((char*)flg + b_flg);
+    unsigned* bits = (unsigned*)((char*)d_err + b_small);
+    unsigned* cpar = (unsigned*)((char*)bits + b_bits);
+    int* tab = (int*)((char*)cpar + b_cpar);
+    int* rid = (int*)((char*)tab + b_tab);
+    int* buf[6];
+    for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+
+    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
+    std::vector<std::pair<hipEvent_t, int>> marks;
+    auto mark = [&](int kind) {
+        if (!ctx->timing) return;
+        hipEvent_t ev;
+        if (hipEventCreate(&ev) != hipSuccess) return;
+        (void)hipEventRecord(ev, ctx->stream);
+        marks.push_back({ev, kind});
+    };
+    auto settle = [&]() {
+        for (size_t k = 1; k < marks.size(); ++k) {
+            float ms = 0.f;
+            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->cinterior_ms[marks[k].second] += ms;
+        }
+        for (auto& m : marks) (void)hipEventDestroy(m.first);
+        marks.clear();
+    };
+
+    const dim3 blk(CP_TPB);
+    const int64_t npl = ny * nx;
+    // the scan of the ranges [a, b), those of [g0, g1) with their bit planes; as many launches as keep a grid below 2^31 blocks
+    auto scan = [&](int64_t a, int64_t b, int64_t g0, int64_t g1) -> int {
+        const int64_t per = ncb * nchunk, step = std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / per);
+        for (int64_t ra = a; ra < b; ra += step) {
+            const int64_t nr = std::min<int64_t>(step, b - ra);
+            const dim3 grid((unsigned)(nr * per));
+#define XC_CI_SCAN(FT_, M_) hipLaunchKernelGGL((k_ci_scan<FT_, M_>), grid, dim3(CI_TPB), 0, ctx->stream, ra, g0, g1, ny, nx, wpr, ncb, rc, nchunk, ncont, \
+                                               (unsigned)flip, bits, cpar, w, w_per_slab, (const FT_*)f, mx, acc, cnt, flg, (unsigned char*)mask)
+            if (!f) { if (mask) XC_CI_SCAN(void, true); else XC_CI_SCAN(void, false); }
+            else if (f_dtype == XC_F32) { if (mask) XC_CI_SCAN(float, true); else XC_CI_SCAN(float, false); }
+            else { if (mask) XC_CI_SCAN(double, true); else XC_CI_SCAN(double, false); }
+#undef XC_CI_SCAN
+            XC_HIP(ctx, hipGetLastError());
+        }
+        return XC_OK;
+    };
+
+    mark(-1);
+    XC_HIP(ctx, hipMemsetAsync(key, 0, b_zero + b_small, ctx->stream));
+    {
+        const dim3 bgrid((unsigned)std::min<int64_t>((npl + CI_TPB - 1) / CI_TPB, 1024), (unsigned)nslab);
+        if (!f) hipLaunchKernelGGL((k_ci_bound<void>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const void*)nullptr, mx);
+        else if (f_dtype == XC_F32) hipLaunchKernelGGL((k_ci_bound<float>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const float*)f, mx);
+        else hipLaunchKernelGGL((k_ci_bound<double>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const double*)f, mx);
+        XC_HIP(ctx, hipGetLastError());
+    }
+    mark(3);
+    if (total > 0) {
+        XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
+    }
+    mark(0);
+    int rounds_total = 0;
+    int64_t done = 0;                                                       // the ranges scanned so far
+    for (const CpGroup& g : groups) {
+        const long long s0 = off[(size_t)g.r0];
+        const int64_t n = off[(size_t)g.r1] - s0, ng = g.r1 - g.r0;
+        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
+        const dim3 grid(cp_blocks(n));
+        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
+        XC_HIP(ctx, hipMemsetAsync(bits, 0, (size_t)ng * plane * 4, ctx->stream));
+        mark(3);
+        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
+        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
+        XC_HIP(ctx, hipGetLastError());
+        mark(0);
+        for (int k = 0; k < R; ++k) {
+            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
+            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
+        }
+        XC_HIP(ctx, hipGetLastError());
+        rounds_total += R;
+        mark(1);
+        // lab, prv: the labels and the ring marks; nxt, lab2, nxt2 are free from here on
+        int* root = nxt;
+        unsigned* pn = (unsigned*)lab2;
+        int* pw = nxt2;
+        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, root, pn, pw);
+        hipLaunchKernelGGL(k_co_piece, grid, blk, 0, ctx->stream, n, s0, wrap, nx, pts, root, pn, pw);
+        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, prv, lab, pn, pw, nsel, key);
+        XC_HIP(ctx, hipGetLastError());
+        mark(2);
+        hipLaunchKernelGGL(k_ci_mark, grid, blk, 0, ctx->stream, n, s0, g.r0, E, nx, wpr, plane, select, (const long long*)e_from,
+                           (const long long*)e_to, tab, rid, root, prv, lab, pn, pw, key, bits);
+        XC_HIP(ctx, hipGetLastError());
+        mark(3);
+        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
+        XC_HIP(ctx, hipGetLastError());
+        mark(0);
+        if (nchunk > 1) {
+            const int64_t nwords = ng * nchunk * wpr;
+            hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, bits, cpar);
+            XC_HIP(ctx, hipGetLastError());
+        }
+        XC_TRY(scan(done, g.r1, g.r0, g.r1));
+        done = g.r1;
+        mark(3);
+    }
+    if (done < nrange) XC_TRY(scan(done, nrange, 0, 0));
+    ctx->cinterior_rounds = rounds_total; ctx->cinterior_groups = (int)groups.size();
+    hipLaunchKernelGGL(k_ci_finish, dim3(cp_blocks(nrange)), blk, 0, ctx->stream, nrange, ncont, acc, cnt, flg, mx, (long long*)n_in, sum_w, sum_wf);
+    XC_HIP(ctx, hipGetLastError());
+    mark(3);
+    int herr = 0;
+    XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    settle();
+    if (herr) return fail(ctx, XC_EBADARG, "xc_contour_interior: an edge id outside [0, 2 ny nx)");
+    return XC_OK;
+}
+
+}  // namespace xc
+
+// ------------------------------------------------------------------------------------ C ABI
+int xc_contour_interior_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                            int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
+                            const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask)
+{
+    XC_CTX(ctx);
+    return xc::launch_contour_interior(ctx, nrange, count, e_from, e_to, pts, ny, nx, periodic, select, flip, ncont, w, w_per_slab, f, f_dtype,
+                                       n_in, sum_w, sum_wf, mask);
+}
+
+int xc_last_cinterior_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
+{
+    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = (double)ctx->cinterior_ms[k];
+    if (rounds) *rounds = ctx->cinterior_rounds;
+    if (groups) *groups = ctx->cinterior_groups;
+    return XC_OK;
+}

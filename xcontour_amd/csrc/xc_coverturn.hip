@@ -11,13 +11,8 @@
 // Per GROUP of consecutive ranges (xc_cpiece_link.h: K13's groups under K13's cap, indices group-local):
 //   phase A (K13's kernels)  k_cp_scatter, k_cp_link, R x k_cp_round: label = the piece's smallest e_from (its first_edge), prev >= 0 on
 //                   every member of a ring and -1 on every member of an open piece
-//   k_co_root       root(i) = tab[range][label], the segment that carries its piece's sums; the sums start at 0
-//   k_co_piece      onto the root, integer atomic adds: nseg, and on a periodic plane the winding by K13's seam count (+1 where
-//                   c2 == nx, -1 where c1 == nx: on a ring every jump across the seam is one of each kind)
-//   k_co_pick       roots only: a root counts into nsel[range] when its piece is selected ('all': every piece; 'circumpolar': a ring
-//                   of winding != 0; one atomic per wave where the wave lies in one range), and a ring of winding != 0 bids for the
-//                   range's main ring with ONE 64-bit atomic max on (nseg << 31) | (2^31 - 1 - first_edge): most segments first, then
-//                   the smallest first_edge.  first_edge is unique within a range, so the winning key names one piece.
+//   k_co_root, k_co_piece, k_co_pick  (xc_cpiece_select.h, shared with K17) the root of every piece, its nseg and winding, nsel, and
+//                   the bid for the range's main ring under co_key
 //   k_co_count      one thread per segment of a selected piece ('main': the piece whose key won): a start point on a vertical edge
 //                   (e_from odd) is a crossing of column (e_from >> 1) % nx at row r1; the end point of a segment WITHOUT successor
 //                   (tab[range][e_to] holds no segment: the tail of an open piece) with e_to odd is one at row r2.  Integer atomic add
@@ -34,8 +29,7 @@ namespace xc {
 namespace {
 
 #include "xc_cpiece_link.h"
-
-constexpr unsigned long long CO_FE = 0x7fffffffull;          // the low 31 bits of a key: 2^31 - 1 - first_edge
+#include "xc_cpiece_select.h"
 
 __global__ __launch_bounds__(CP_TPB)
 void k_co_init(int64_t ncol, int64_t nrange, int* __restrict__ ncross, double* __restrict__ row_lo, double* __restrict__ row_hi,
@@ -45,67 +39,6 @@ void k_co_init(int64_t ncol, int64_t nrange, int* __restrict__ ncross, double* _
     const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
     if (i < ncol) { ncross[i] = 0; row_lo[i] = __longlong_as_double(0x7ff0000000000000ll); row_hi[i] = 0.0; }
     if (i < nrange) { nsel[i] = 0; mfe[i] = -1; mns[i] = 0; mw[i] = 0; key[i] = 0ull; }
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_co_root(int64_t n, long long E, const int* __restrict__ tab, const int* __restrict__ rid, const int* __restrict__ lab,
-               int* __restrict__ root, unsigned* __restrict__ pn, int* __restrict__ pw)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const int l = lab[i];
-    int t = (l >= 0 && l < E) ? tab[(size_t)rid[i] * E + l] : (int)i;
-    if (t < 0 || t >= n) t = (int)i;
-    root[i] = t;
-    pn[i] = 0u; pw[i] = 0;
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_co_piece(int64_t n, long long s0, int wrap, int64_t nx, const double* __restrict__ pts, const int* __restrict__ root,
-                unsigned* __restrict__ pn, int* __restrict__ pw)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const int t = root[i];
-    atomicAdd(pn + t, 1u);
-    if (wrap) {
-        const double xn = (double)nx;
-        const double c1 = pts[4 * (size_t)(s0 + i) + 1], c2 = pts[4 * (size_t)(s0 + i) + 3];
-        const int w = (int)(c2 == xn) - (int)(c1 == xn);
-        if (w != 0) atomicAdd(pw + t, w);
-    }
-}
-
-// the key a ring of winding != 0 bids with
-__device__ __forceinline__ unsigned long long co_key(unsigned nseg, int first_edge)
-{
-    return ((unsigned long long)nseg << 31) | (CO_FE - ((unsigned long long)(unsigned)first_edge & CO_FE));
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_co_pick(int64_t n, int64_t r0, int select, const int* __restrict__ rid, const int* __restrict__ root, const int* __restrict__ prv,
-               const int* __restrict__ lab, const unsigned* __restrict__ pn, const int* __restrict__ pw, int* __restrict__ nsel,
-               unsigned long long* __restrict__ key)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    const bool valid = i < n;
-    int r = -1;
-    bool sel = false;
-    if (valid) {
-        r = rid[i];
-        if (root[i] == (int)i) {
-            const bool circ = prv[i] >= 0 && pw[i] != 0;
-            sel = select == 0 || (select == 1 && circ);
-            if (circ) atomicMax(key + r0 + r, co_key(pn[i], lab[i]));
-        }
-    }
-    const int rf = __builtin_amdgcn_readfirstlane(r);
-    if (__all(!valid || r == rf)) {                                   // the wave lies in one range: one atomic for all its roots
-        const unsigned long long m = __ballot(sel);
-        if (m != 0ull && (threadIdx.x & 63) == 0) atomicAdd(nsel + r0 + rf, (int)__popcll(m));
-    } else if (sel) {
-        atomicAdd(nsel + r0 + r, 1);
-    }
 }
 
 __global__ __launch_bounds__(CP_TPB)
@@ -119,11 +52,10 @@ void k_co_count(int64_t n, long long s0, int64_t r0, long long E, int64_t nx, in
     if (i >= n) return;
     const int t = root[i], r = rid[i];                                // (k_co_root left 0 <= t < n)
     const bool ring = prv[i] >= 0;
-    const int w = ring ? pw[t] : 0;
-    const bool circ = w != 0;
-    const bool ismain = circ && co_key(pn[t], lab[i]) == key[r0 + r];
+    int w; bool ismain;
+    const bool sel = co_selected(select, ring, t, lab[i], pn, pw, key[r0 + r], w, ismain);
     if (ismain && t == (int)i) mw[r0 + r] = w;
-    if (!(select == 0 || (select == 1 ? circ : ismain))) return;
+    if (!sel) return;
     const size_t out0 = (size_t)(r0 + r) * (size_t)nx;
     auto cross = [&](long long e, double row) {
         const size_t at = out0 + (size_t)((e >> 1) % nx);

@@ -101,6 +101,7 @@ struct xc_ctx {
     float  cpiece_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpiece_rounds = 0, cpiece_groups = 0;   // table, rounds, roots, reductions (xc_set_kernel_timing)
     float  cjoin_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cjoin_rounds = 0, cjoin_groups = 0;   // K14 (xc_cjoin.hip, on K13's workspace): table, label rounds, rank rounds, placement, emit
     float  coverturn_ms[4] = {0.f, 0.f, 0.f, 0.f};  int coverturn_rounds = 0, coverturn_groups = 0;   // K16 (xc_coverturn.hip, on K13's workspace): table, rounds, pieces / select, count
+    float  cinterior_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cinterior_rounds = 0, cinterior_groups = 0;   // K17 (xc_cinside.hip, on K13's workspace): table, rounds, select, mark + scan
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -352,6 +353,10 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
 int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
                                int64_t ny, int64_t nx, int periodic, int select, int32_t* ncross, double* row_lo, double* row_hi, int32_t* nsel,
                                int64_t* main_first_edge, int64_t* main_nseg, int32_t* main_winding);
+// K17: node counts, weighted sums and the mask of what the selected pieces of K12's records (device pointers) bound; waits for the stream twice
+int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                            int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
+                            const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 
