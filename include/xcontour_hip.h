@@ -647,6 +647,51 @@ int xc_contour_interior_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
                             const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask);
 int xc_last_cinterior_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K18 contour piece interiors: what EVERY piece bounds
+ * K17 measures one selection per range and leaves out what the vortex has shed.  A cut-off low, a shed filament, a blob of
+ * stratospheric air is a closed piece with winding 0, and the questions asked of it are per piece: how many nodes, how much w, how much
+ * w f does it enclose.  This call answers for every piece of every range at once; only a per-piece table is written.  Build-defined;
+ * index space; the field is not read again.
+ * Input as for K13, K16 and K17: count[nrange], e_from, e_to, pts where the K12 _dev entry points left them, with ny, nx, periodic of
+ * that call; w with w_per_slab and f with f_dtype exactly as K17 reads them (range = s ncont + k, nrange a multiple of ncont, at most
+ * 65535 slabs).  Pieces, closed, winding, nseg and first_edge are K13's.  2 ny nx < 2^31, every range has fewer than 2^31 segments,
+ * every edge id lies in [0, 2 ny nx) and repeats neither among the e_from nor among the e_to of a range, else XC_EBADARG (the edge
+ * tables are handed on clean first).  periodic with nx < 3 is XC_EBADARG: with two columns a cell's two vertical edges are one edge.
+ * For ONE piece p of a range, K17's definitions with the selection being p alone:
+ *   CROSSING FLAG  X_p[r][c] = 1 iff V(r, c), r < ny - 1, carries a meridian crossing (K16's definition) of a segment of p.
+ *   NODE PARITY    P_p[r][c] = XOR over r' < r of X_p[r'][c].
+ *   INSIDE         a ring with winding 0: inside = P_p (row 0 is always outside such a ring);
+ *                  a ring with winding != 0: inside = P_p ^ flip, flip 0 or 1 (K17's);
+ *                  an open piece bounds nothing: n_in = -1 and both sums are NaN.
+ *   The interior is that of the ring ALONE: the nodes of a ring nested inside it are counted, not subtracted -- the caller subtracts
+ *   nested pieces.
+ * per piece, packed by range like K13's records (the pieces of range r are [poff[r], poff[r+1]), poff the exclusive scan of
+ * piece_count; the order INSIDE a range is unspecified: sort by first_edge):
+ *     first_edge int64  the smallest e_from of the piece: the key that joins the row to xc_contour_pieces_dev
+ *     nseg int64, closed int32, winding int32   K13's
+ *     n_in   int64  the inside nodes
+ *     sum_w  f64    the sum of w over them; w == NULL is weight 1
+ *     sum_wf f64    the sum of w f, each product rounded once; NULL exactly when f is NULL
+ *   The sums are K17's: exact sums of their float64 terms rounded once, a window of 160 bits under 2^top, top = 12 + the frexp exponent
+ *   of max |w| (max |w f|) over the finite values of the range's slab; a NaN term is skipped; a +-inf term makes THAT sum of THAT piece
+ *   NaN, and no other.  Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
+ *   piece_count[nrange] is always written.  capacity >= sum(piece_count): the records are written, XC_OK.  Otherwise nothing is
+ *     written to the record arrays and 1 is returned (capacity 0 with NULL record arrays = count only).  The number of segments is an
+ *     upper bound of the number of pieces.
+ * What the call relies on: a ring of K12's records is a simple closed curve, so down one column its crossings alternate between
+ * entering and leaving, and the ids say which is which (xc_cpinside.hip states how).  On such records the result IS the rule above.  On
+ * records that are no K12 output n_in and the sums are unspecified, but every access stays in bounds and every walk ends within ny steps.
+ * The call waits for the stream once for K12's counts, once per group for its piece counts, once at the end.  It works in K13's groups
+ * of ranges under K13's cap and in K13's workspaces (xc_set_cpiece_workspace; the result does not depend on it).  With
+ * xc_set_kernel_timing on, xc_last_cpinside_profile returns the last call's device times in ms -- ms[0] edge tables (clear, scatter,
+ * link), ms[1] the doubling rounds, ms[2] roots, slots and the per-piece signs (with the wait for the piece counts), ms[3] the walks
+ * (with the bounds of the windows and the finish pass) -- the number of rounds summed over the groups, and the number of groups.    */
+int xc_contour_piece_interiors_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                                   const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                                   int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                                   int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf);
+int xc_last_cpinside_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

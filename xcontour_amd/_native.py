@@ -167,6 +167,9 @@ PROTOTYPES = {
     'xc_contour_interior_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                           _vp, C.c_int, _vp, _vp, _vp, _vp]),
     'xc_last_cinterior_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_piece_interiors_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                                 _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_last_cpinside_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1321,6 +1324,81 @@ class Context(object):
             return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), interior,
                                               inputs=tuple(ins), out_nbytes=tuple(nb))
         per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (N if want_mask else 0))
+        return self._batched(nslab, per, one)
+
+    # the per-piece table of `contour_piece_interiors`: K13's key fields and what the piece encloses
+    PIECE_INTERIOR_DTYPE = np.dtype([('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),
+                                     ('n_in', np.int64), ('sum_w', np.float64), ('sum_wf', np.float64)])
+
+    def last_cpinside_profile(self):
+        """device times of the last `contour_piece_interiors` batch under set_kernel_timing(True): dict(table_ms, rounds_ms,
+        roots_ms, walk_ms, rounds, groups)"""
+        ms = (C.c_double * 4)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cpinside_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], rounds=r.value, groups=g.value)
+
+    def contour_piece_interiors(self, q, contours, w=None, f=None, periodic=False, flip=False):
+        """What EVERY piece of every contour bounds (K18, xc_contour_piece_interiors_dev, on the device records of K12: the segment
+        records are never downloaded).  q, contours, periodic, w, f and flip as for `contour_interior`; periodic needs nx >= 3.  For
+        one ring the rule is `contour_interior`'s with that ring alone selected: a node (r, c) is inside a ring of winding 0 when the
+        ring crosses the grid line of column c between row 0 and row r an odd number of times; for a ring of winding != 0 the other
+        nodes when `flip`.  The nodes of a ring nested inside another count for the outer one too: subtract nested pieces yourself.
+        Returns (piece_count uint64 (nslab, N), table): `table` a structured array (PIECE_INTERIOR_DTYPE) of all pieces packed by
+        (slab, contour) -- range (s, k) starts at the exclusive scan of piece_count --, each range sorted by first_edge: its rows line
+        up with those of `contour_pieces`.  first_edge, nseg, closed, winding are that method's; n_in the inside nodes, sum_w the sum
+        of w over them (None: weight 1), sum_wf that of w f (NaN without f) -- exact sums rounded once, NaN terms skipped, an infinite
+        term makes that sum of that piece NaN.  An open piece bounds nothing: n_in -1, NaN sums."""
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, _, N = _levels_of(contours, nslab)
+        _check_ascending(contours, 'xc_contour_piece_interiors')
+        if periodic and nx < 3:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: a periodic plane needs nx >= 3')
+        if 2 * ny * nx >= 1 << 31:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: plane too large for 32-bit labels (2 ny nx < 2^31)')
+        if w is not None:
+            w = _contig(w, np.float64)
+            if w.shape not in ((ny, nx), (nslab, ny, nx)):
+                raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: w must be (ny, nx) or (nslab, ny, nx)')
+        if f is not None:
+            f = _contig(_f48(np.asarray(f)))
+            if f.shape != (nslab, ny, nx):
+                raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: f must be (nslab, ny, nx)')
+        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
+        has_f = f is not None
+        dt = self.PIECE_INTERIOR_DTYPE
+
+        def interiors(cnt, total, dn, ins, outs, recs):
+            if total == 0:
+                return np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt)
+            ins = list(ins)
+            dw = ins.pop(0) if w is not None else None
+            df_ = ins.pop(0) if has_f else None
+            (dpc,), (df, dto, dp, drec) = outs, recs
+            col = [drec.ptr + k * total * 8 for k in range(5)]              # first_edge, nseg, n_in, sum_w, sum_wf
+            i32 = [drec.ptr + 40 * total, drec.ptr + 44 * total]              # closed, winding
+            self._check(self.lib.xc_contour_piece_interiors_dev(
+                self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
+                dw.ptr if dw is not None else None, w_per_slab, df_.ptr if df_ is not None else None,
+                dtype_code(f.dtype) if has_f else 0, total, dpc.ptr, col[0], col[1], i32[0], i32[1], col[2], col[3],
+                col[4] if has_f else None))
+            pc = dpc.download(cnt.shape, np.uint64)
+            npiece = int(pc.sum())
+            out = np.empty(npiece, dtype=dt)
+            out['sum_wf'] = np.nan
+            for name, at, t in (('first_edge', col[0], np.int64), ('nseg', col[1], np.int64), ('n_in', col[2], np.int64),
+                                ('sum_w', col[3], np.float64), ('closed', i32[0], np.int32), ('winding', i32[1], np.int32)) + \
+                    ((('sum_wf', col[4], np.float64),) if has_f else ()):
+                out[name] = drec.download((npiece,), t, offset_bytes=at - drec.ptr)
+            return pc, out[_range_order(pc, out['first_edge'])]
+
+        def one(s0, s1):
+            # beside K12's records: the weights and the integrand, the piece counts, and one piece record per segment at most -- five
+            # 8-byte columns, then two 4-byte ones
+            ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), interiors,
+                                              inputs=tuple(ins), out_nbytes=((s1 - s0) * N * 8,), per_segment=(48,))
+        per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0))
         return self._batched(nslab, per, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):

@@ -1074,6 +1074,64 @@ class Contour2D(object):
             out.append(lb.wrap(m.reshape(shape + (ny, nx)), dims + (self.dimEqV, self._xdim), cm, 'mask', data))
         return lb.merge(out, data)
 
+    def cal_integral_inside_pieces(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
+        """
+        Area, node count and integral of what EVERY piece of every contour bounds, computed on the GPU in one call (K12's
+        segments, K13's pieces, K18, xc_contour_piece_interiors_dev).  Build-defined: the reference has no counterpart.
+
+        cal_integral_inside_contours measures one selection per contour -- with select='main' the vortex itself -- and leaves
+        out what the vortex has shed.  A cut-off low, a shed filament or a blob of stratospheric air is a closed piece that
+        does not go round the pole (winding 0); this method says, for each of them, how many nodes it encloses, how much dA
+        (the sum of this object's dA over those nodes, not the planar shoelace `area` of cal_contour_pieces) and how much of
+        an integrand.
+
+        `contours`, `tracer` and the order of the levels as for cal_contour_pieces; `periodic` (False, True or the period; it
+        needs at least three columns), the weight and `integrand` as for cal_integral_inside_contours.  For one ring the rule is that
+        method's with the ring alone selected: walking a column from its first row, a node is inside a ring of winding 0 when
+        the ring has been crossed an odd number of times.  For a ring that goes round the pole, `side` picks the region as
+        in cal_integral_inside_contours ('upper': the side of the larger equivalent-dim coordinate).  The interior is that of
+        the ring ALONE: the nodes of a ring nested inside it are counted, not subtracted -- subtract nested pieces yourself.
+
+        Returns, per level (out[k], or out[slab][k] with leading dims), a numpy structured array with one row per piece in
+        first_edge order: its rows line up with those of cal_contour_pieces.  first_edge, nseg, closed, winding are that
+        method's; `nodes` the inside nodes (int64), `area` the sum of dA over them, and with an integrand `integral`, the sum
+        of dA * integrand, each product rounded once.  The sums are exact sums of their float64 terms rounded once; a NaN
+        term is skipped, an infinite one gives NaN.  An open piece bounds nothing: nodes -1, area and integral NaN.  A NaN
+        level, or a level without segments, gives an empty array.
+        """
+        who = 'cal_integral_inside_pieces'
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        if side not in ('upper', 'lower'):
+            raise Exception('%s: side should be \'upper\' or \'lower\', not %r' % (who, side))
+        data, dcoords = self._plane_dcoords(who, tracer)
+        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
+        ring = self._x_period(periodic, xg, False, who, plain=True) is not None
+        q, lead, lshape, _ = self._float_plane(data)
+        nslab, ny, nx = q.shape
+        if ring and nx < 3:
+            raise Exception('%s: periodic needs at least three columns along the periodic dim' % who)
+        bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
+        dA = self._dA_array(ny, nx, nslab)[0]
+        if dA.ndim == 1:
+            dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
+        g = None
+        if integrand is not None:
+            g = self._integrand_plane(integrand)
+            if g.shape != q.shape:
+                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
+        ascends = yg.size < 2 or yg[-1] >= yg[0]
+        flip = (side == 'upper') != bool(ascends)
+        pc, tab = self.ctx.contour_piece_interiors(q, bs, w=dA, f=g, periodic=ring, flip=flip)
+        names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral'}
+        fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f != 'sum_wf' or g is not None]
+        rec = np.empty(tab.size, dtype=fields)
+        for f in tab.dtype.names:
+            if names.get(f, f) in rec.dtype.names:
+                rec[names.get(f, f)] = tab[f]
+        poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
+        return self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
+
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):
         """
