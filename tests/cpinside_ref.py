@@ -5,8 +5,9 @@ and flip, ncont, w, f.
 piece_interiors(): brute force, no orientation trick.  Pieces, per range: cpiece_records_ref.walk.  For ONE piece p: X_p[r][c] = 1 iff
 V(r, c), r < ny - 1, carries the start point of a segment of p with odd e_from (or, on an open piece, the end point of its last segment
 in walk order with odd e_to); P_p = cinside_ref.parity(X_p).  Ring of winding 0: inside = P_p; ring of winding != 0: inside = P_p ^ flip;
-open piece: n_in = -1 and NaN sums.  Sums: cinside_ref.nan_skipping_sum (NaN terms dropped, any infinite term gives NaN, else math.fsum).
-Returns per range a structured array (DTYPE) sorted by first_edge (and the masks when asked for).
+open piece: n_in = -1 and NaN sums.  Sums: cinside_ref.window_sum on the windows of cinside_ref.window_tops (NaN terms dropped, any
+infinite term gives NaN, else math.fsum of the terms cut toward zero at the bottom of the slab's window).
+Returns per range a structured array (DTYPE) sorted by first_edge (and the masks and the windows' tops when asked for).
 
 mapping(): what the kernel does instead of scanning the plane once per piece, written out -- each crossing of a ring gets s = +1 when
 its segment lies in the cell to the right of its vertical edge (e_to is that cell's top, bottom or right edge), else -1; per ring
@@ -48,24 +49,25 @@ def _pieces(ef, et, pts, s0, c, ny, nx, periodic):
     return out
 
 
-def _sums(inside, r, ncont, ny, nx, w, f):
+def _sums(inside, r, ncont, ny, nx, w, f, tops):
+    """-> (sum_w, sum_wf, (top_w, top_f)) of one piece of range r"""
     s = r // ncont
-    wa = np.ones((ny, nx)) if w is None else np.asarray(w, dtype=np.float64)
-    ws = wa[s] if wa.ndim == 3 else wa
-    sw = IR.nan_skipping_sum(ws[inside])
-    swf = np.nan
-    if f is not None:
-        with np.errstate(all='ignore'):
-            swf = IR.nan_skipping_sum(ws[inside] * np.asarray(f[s], dtype=np.float64)[inside])
-    return sw, swf
+    ws, wf = IR.slab_planes(w, f, s, ny, nx)
+    sw = IR.window_sum(ws[inside], tops[s][0])
+    swf = np.nan if wf is None else IR.window_sum(wf[inside], tops[s][1])
+    return sw, swf, tops[s]
 
 
-def piece_interiors(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, w=None, f=None, return_masks=False):
+def piece_interiors(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, w=None, f=None, return_masks=False,
+                    return_tops=False, tops=None):
     """-> per range a DTYPE array sorted by first_edge[, per range the list of bool masks (ny, nx) in the same order; None for an open
-    piece]"""
+    piece][, per slab the windows' tops (top_w, top_f)].  `tops`: the windows to use instead of cinside_ref.window_tops' (the host tests
+    hand in those of broken bound rules)."""
     count, ef, et, pts = _ranges(count, e_from, e_to, pts)
     ncont = count.size if ncont is None else int(ncont)
     assert count.size % ncont == 0
+    if tops is None:
+        tops = IR.window_tops(w, f, count.size // ncont, ny, nx)
     tables, masks, s0 = [], [], 0
     for r, c in enumerate(count):
         rows = []
@@ -79,13 +81,14 @@ def piece_interiors(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=No
                 if row < ny - 1:
                     X[0, row, col] = 1
             inside = (IR.parity(X, ny)[0] ^ np.uint8(1 if (flip and wind != 0) else 0)).astype(bool)
-            sw, swf = _sums(inside, r, ncont, ny, nx, w, f)
+            sw, swf, _ = _sums(inside, r, ncont, ny, nx, w, f, tops)
             rows.append(((first, g.size, True, wind, int(inside.sum()), sw, swf), inside))
         rows.sort(key=lambda t: t[0][0])
         tables.append(np.array([t[0] for t in rows], dtype=DTYPE))
         masks.append([t[1] for t in rows])
         s0 += int(c)
-    return (tables, masks) if return_masks else tables
+    out = (tables,) + ((masks,) if return_masks else ()) + ((tops,) if return_tops else ())
+    return out if len(out) > 1 else tables
 
 
 def mapping(count, e_from, e_to, pts, ny, nx, periodic, flip=0, wrong=None):

@@ -110,76 +110,7 @@ def running_sum(terms):
     return s
 
 
-def round_exact(fr, ties_away=False):
-    """a Fraction -> the nearest float64, half to even (ties_away True: half away from zero; None: half toward zero)"""
-    if fr == 0:
-        return 0.0
-    neg, fr = fr < 0, abs(fr)
-    e = fr.numerator.bit_length() - fr.denominator.bit_length()
-    while Fraction(2) ** e > fr:
-        e -= 1
-    while Fraction(2) ** (e + 1) <= fr:
-        e += 1
-    scaled = fr / Fraction(2) ** (e - 52)                                   # in [2^52, 2^53)
-    n, rem = divmod(scaled.numerator, scaled.denominator)
-    twice = 2 * rem
-    if twice > scaled.denominator or (twice == scaled.denominator and ties_away is not None and (ties_away or n & 1)):
-        n += 1
-    out = math.ldexp(float(n), e - 52)
-    return -out if neg else out
-
-
-def limb_sum(terms, top, defect=None):
-    """The mechanism the header names, in Python integers: a window of five 32-bit limbs under 2^top kept in 64-bit words; a term
-    cut at the limb boundaries into three chunks below 2^32, negated for a negative term; the words carried; a negative total
-    complemented with borrows; the top 64 bits rounded half to even with a sticky bit for the rest.  `defect` breaks one step."""
-    M32, W = (1 << 32) - 1, 1 << 64
-    acc = [0] * 5
-    for v in terms:
-        v = float(v)
-        if v == 0.0:
-            continue
-        m, e = math.frexp(abs(v))
-        M, sh = int(math.ldexp(m, 53)), (e - 53) - (top - 160)
-        if sh < 0:
-            M, sh = (M >> -sh if -sh < 53 else 0), 0
-        k, s = divmod(sh, 32)
-        big = M << s
-        for t, c in enumerate((big & M32, (big >> 32) & M32, big >> 64)):
-            j = 4 - k - t
-            if defect == 'a chunk one limb off at shift 17' and s == 17 and t == 1:
-                j += 1
-            if c:
-                assert 0 <= j < 5
-                acc[j] = (acc[j] + (-c if v < 0 else c)) % W
-    w = [a - W if a >= W // 2 else a for a in acc]
-    for j in range(4, 0, -1):
-        c = w[j] >> 32
-        w[j] -= c << 32
-        if not (defect == 'a carry lost between limbs' and j == 2):
-            w[j - 1] += c
-    neg = w[0] < 0
-    if neg:
-        borrow = 0
-        for j in range(4, -1, -1):
-            t = -w[j] - borrow
-            borrow = 0
-            if j > 0 and t < 0:
-                t += 1 << 32
-                borrow = 0 if defect == 'no borrow on a negative sum' else 1
-            w[j] = t
-    total = sum(w[j] << (32 * (4 - j)) for j in range(5))
-    if total == 0:
-        return 0.0
-    nb, e = total.bit_length(), top - 160
-    if nb > 64 and defect == 'no sticky bit':
-        total, e = total >> (nb - 64), e + nb - 64
-    out = round_exact(Fraction(total) * Fraction(2) ** e, ties_away={'ties away from zero': True, 'ties toward zero': None}.get(defect, False))
-    return -out if neg else out
-
-
-DEFECTS = ('ties away from zero', 'ties toward zero', 'no sticky bit', 'a carry lost between limbs', 'no borrow on a negative sum',
-           'a chunk one limb off at shift 17')
+round_exact, limb_sum, DEFECTS = RR.round_exact, RR.limb_sum, RR.DEFECTS      # the limb model lives beside the cases it is run on
 TOP = 13                                # the windows of every exact case (asserted below)
 
 

@@ -174,3 +174,45 @@ def test_nested_nodes_that_are_subtracted_are_caught():
     q = np.zeros((5, 6))
     q[2, 3] = 1.0
     assert not caught(records(q, False, (0.5,)), 'nested nodes subtracted')   # a single blob cannot tell
+
+
+# ------------------------------------------------------------------ the windows of the sums (K17's rule, cinside_ref.window_tops)
+import cinside_sums_cases as SC
+import cpiece_records_ref as RR
+from test_gpu_cpinside_records import noise, scaled
+
+
+@pytest.mark.parametrize('periodic', [False, True], ids=['plain', 'ring'])
+def test_on_the_scaled_inputs_of_the_records_suite_the_window_changes_nothing(periodic):
+    """exponents in [-20, 20]: every term lies wholly inside its window, so the sums of the header's rule ARE plain math.fsum, bit for
+    bit -- what test_gpu_cpinside_records.py asserted before the reference stated the window, it asserts still"""
+    ny, nx = 33, 40
+    q = noise(ny, nx, 2, 90 + ny + nx)
+    lv = np.sort(np.array([-0.7, q[1, 3, 3], 0.8]))
+    rec = (JP if periodic else JR).stack_records(q, lv) + (ny, nx, int(periodic))
+    rng = np.random.default_rng(92 + nx)
+    w2, w3 = scaled(rng, (ny, nx)), scaled(rng, (2, ny, nx))
+    f32, f64 = scaled(rng, (2, ny, nx), np.float32), scaled(rng, (2, ny, nx))
+    w2[5, 5], f64[1, 7, 7] = np.nan, np.nan
+    for w, f in ((w2, f64), (w3, f32), (None, None), (None, f64)):
+        tables, masks, tops = PR.piece_interiors(*rec, flip=1, ncont=3, w=w, f=f, return_masks=True, return_tops=True)
+        assert len(tops) == 2 and all(-8 <= tw <= 33 and (tf is None or -28 <= tf <= 53) for tw, tf in tops)
+        nclosed = 0
+        for r, (t, ms) in enumerate(zip(tables, masks)):
+            ws, wf = PR.IR.slab_planes(w, f, r // 3, ny, nx)
+            for row, m in zip(t, ms):
+                if m is None:
+                    continue
+                nclosed += 1
+                assert SC.same(row['sum_w'], PR.IR.nan_skipping_sum(ws[m]))
+                assert np.isnan(row['sum_wf']) if f is None else SC.same(row['sum_wf'], PR.IR.nan_skipping_sum(wf[m]))
+        assert nclosed > 20
+
+
+@pytest.mark.parametrize('kind', [k for k in SC.KINDS if k.startswith('k18')])
+def test_the_limb_model_on_k18s_windows_every_defect_caught_by_the_list_written_for_it(kind):
+    """block ring (walks down), comb ring without flip (down) and with flip (up): the same term lists, the same windows"""
+    caught, seen = SC.limb_model_report(kind)
+    assert seen > 1000
+    for d in RR.DEFECTS:
+        assert SC.CATCHES[d] <= caught[d], (d, sorted(SC.CATCHES[d] - caught[d]))

@@ -1,9 +1,11 @@
 """xc_contour_interior_dev (K17), the C entry on device records, against cinside_ref: n_in and the mask equal, sum_w and sum_wf equal
-to math.fsum BIT FOR BIT.  The records are K12's own (Context.contour_segments of a small field) or built by the test.  Weights and
-integrands have exponents in [-20, 20], so every term of either sum lies within 2^+-40 and wholly inside its 160-bit window.
-test_cinside_host.py shows on the CPU what the restatement computes.  Every call hands the entry output arrays filled with a
-pattern and followed by guard elements: on XC_OK every element is written and every guard intact, on a refusal before the first
-launch nothing is touched."""
+to the header's rule BIT FOR BIT.  The records are K12's own (Context.contour_segments of a small field) or built by the test.  Weights
+and integrands have exponents in [-20, 20], so every term of either sum lies within 2^+-40 and wholly inside its 160-bit window: here
+the rule is plain math.fsum (test_cinside_host.py shows it).  Everything else about the sums -- ties, the window's bottom and floor,
+bounds far from the terms, non-finite values, windows per slab -- is in test_gpu_cinside_sums.py; the cuts of the scan's launch geometry
+are in test_gpu_cinside_geometry.py.  test_cinside_host.py shows on the CPU what the restatement computes.  Every call hands the entry
+output arrays filled with a pattern and followed by guard elements: on XC_OK every element is written and every guard intact, on a
+refusal before the first launch nothing is touched."""
 import numpy as np
 import pytest
 
@@ -19,8 +21,10 @@ PAT_I64, PAT_F64, PAT_U8 = 0x5a5a5a5a5a5a5a5a, -1.2345e300, 0xa5
 SELECTS = ((0, 0), (1, 0), (1, 1), (1, 2))                                   # (periodic, select)
 
 
-def call(ctx, count, e_from, e_to, pts, ny, nx, periodic, select, flip, ncont, w=None, f=None, want_mask=True, w_per_slab=None):
-    """one xc_contour_interior_dev call on host records -> (rc, dict(n_in, sum_w, sum_wf, mask), untouched); the guards are checked"""
+def call(ctx, count, e_from, e_to, pts, ny, nx, periodic, select, flip, ncont, w=None, f=None, want_mask=True, w_per_slab=None,
+         null_records=False):
+    """one xc_contour_interior_dev call on host records -> (rc, dict(n_in, sum_w, sum_wf, mask), untouched); the guards are checked.
+    null_records: e_from, e_to and pts are handed over as NULL (a call without any segment)"""
     count = np.ascontiguousarray(count, dtype=np.uint64).ravel()
     total, nr = int(count.sum()), count.size
     ins = [count, np.ascontiguousarray(e_from, dtype=np.int64), np.ascontiguousarray(e_to, dtype=np.int64),
@@ -37,7 +41,8 @@ def call(ctx, count, e_from, e_to, pts, ny, nx, periodic, select, flip, ncont, w
         dw = bufs[4] if w is not None else None
         dfi = bufs[4 + (w is not None)] if f is not None else None
         dni, dsw, dsf, dm = bufs[-4:]
-        rc = ctx.lib.xc_contour_interior_dev(ctx.handle, nr, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, int(periodic), int(select), int(flip),
+        recs = [None] * 3 if null_records else [df.ptr, dt.ptr, dp.ptr]
+        rc = ctx.lib.xc_contour_interior_dev(ctx.handle, nr, dn.ptr, *recs, ny, nx, int(periodic), int(select), int(flip),
                                              int(ncont), dw.ptr if dw is not None else None, int(w_per_slab),
                                              dfi.ptr if dfi is not None else None, nat.dtype_code(f.dtype) if f is not None else 0,
                                              dni.ptr, dsw.ptr, dsf.ptr if f is not None else None, dm.ptr if want_mask else None)

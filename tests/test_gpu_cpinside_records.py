@@ -1,8 +1,10 @@
 """xc_contour_piece_interiors_dev (K18), the C entry on host records, against cpinside_ref.piece_interiors: the integer fields equal,
-sum_w and sum_wf equal to math.fsum BIT FOR BIT.  The records are hand-built: the restatements of K12 (contour_join_ref,
+sum_w and sum_wf equal to the header's rule BIT FOR BIT.  The records are hand-built: the restatements of K12 (contour_join_ref,
 contour_join_periodic_ref) trace planes the test draws -- rings of a chosen number of segments, noise with hundreds of pieces, rings that
 go round either way -- and the test then stores every range in an order of its choosing.  Weights and integrands have exponents in
-[-20, 20], so every term lies wholly inside its 160-bit window.  test_cpinside_host.py shows on the CPU what the restatement computes.
+[-20, 20], so every term lies wholly inside its 160-bit window: here the rule is plain math.fsum (test_cpinside_host.py shows it).
+Everything else about the sums -- ties, the window's bottom and floor, bounds far from the terms, non-finite values, windows per slab --
+is in test_gpu_cinside_sums.py, for K17 and K18 alike.  test_cpinside_host.py shows on the CPU what the restatement computes.
 Every call hands the entry output arrays filled with a pattern and followed by guard elements: on XC_OK the records are written and every
 guard intact, on 1 or a refusal nothing but piece_count is touched."""
 import functools
@@ -26,8 +28,9 @@ PATS = ((np.int64, 0x5a5a5a5a5a5a5a5a), (np.int64, 0x5a5a5a5a5a5a5a5a), (np.int3
 NAMES = ('first_edge', 'nseg', 'closed', 'winding', 'n_in', 'sum_w', 'sum_wf')
 
 
-def call(ctx, count, e_from, e_to, pts, ny, nx, periodic, flip, ncont, w=None, f=None, capacity=None, null_records=False):
-    """one call -> (rc, piece_count, the seven columns as written (None where nothing may be), untouched); the guards are checked"""
+def call(ctx, count, e_from, e_to, pts, ny, nx, periodic, flip, ncont, w=None, f=None, capacity=None, null_records=False, null_inputs=False):
+    """one call -> (rc, piece_count, the seven columns as written (None where nothing may be), untouched); the guards are checked.
+    null_inputs: e_from, e_to and pts are handed over as NULL (a call without any segment)"""
     count = np.ascontiguousarray(count, dtype=np.uint64).ravel()
     total, nr = int(count.sum()), count.size
     capacity = total if capacity is None else int(capacity)
@@ -46,7 +49,8 @@ def call(ctx, count, e_from, e_to, pts, ny, nx, periodic, flip, ncont, w=None, f
         ptrs = [None] * 7 if null_records else [b.ptr for b in rec]
         if f is None:
             ptrs[6] = None
-        rc = ctx.lib.xc_contour_piece_interiors_dev(ctx.handle, nr, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, int(periodic), int(flip), int(ncont),
+        recs = [None] * 3 if null_inputs else [df.ptr, dt.ptr, dp.ptr]
+        rc = ctx.lib.xc_contour_piece_interiors_dev(ctx.handle, nr, dn.ptr, *recs, ny, nx, int(periodic), int(flip), int(ncont),
                                                     dw.ptr if dw is not None else None, w_per_slab, dfi.ptr if dfi is not None else None,
                                                     nat.dtype_code(f.dtype) if f is not None else 0, capacity, dpc.ptr, *ptrs)
         pcb = dpc.download((nr + GUARD,), np.uint64)
