@@ -663,8 +663,8 @@ int xc_last_cinterior_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
  *   INSIDE         a ring with winding 0: inside = P_p (row 0 is always outside such a ring);
  *                  a ring with winding != 0: inside = P_p ^ flip, flip 0 or 1 (K17's);
  *                  an open piece bounds nothing: n_in = -1 and both sums are NaN.
- *   The interior is that of the ring ALONE: the nodes of a ring nested inside it are counted, not subtracted -- the caller subtracts
- *   nested pieces.
+ *   The interior is that of the ring ALONE: the nodes of a ring nested inside it are counted, not subtracted -- K19
+ *   (xc_contour_piece_tree_dev) says which piece is nested in which and gives the net records.
  * per piece, packed by range like K13's records (the pieces of range r are [poff[r], poff[r+1]), poff the exclusive scan of
  * piece_count; the order INSIDE a range is unspecified: sort by first_edge):
  *     first_edge int64  the smallest e_from of the piece: the key that joins the row to xc_contour_pieces_dev
@@ -691,6 +691,46 @@ int xc_contour_piece_interiors_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* 
                                    int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
                                    int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf);
 int xc_last_cpinside_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
+/* ------------------------------------------------------------------ K19 contour piece tree: which piece is NESTED in which
+ * K18 gives every ring what it bounds, nested rings' nodes included, and a flat list.  A cut-off low with a warm core, a vortex with a
+ * hole, an eddy with a ring round it are rings INSIDE rings: this call adds the hierarchy -- per piece its parent, its depth, the number
+ * of its children -- and what the ring bounds NET of its children.  Build-defined; index space; the field is not read again.
+ * Input exactly as K18 takes it: count[nrange], e_from, e_to, pts where the K12 _dev entry points left them, with ny, nx, periodic of
+ * that call, flip, ncont, w with w_per_slab and f with f_dtype; the same limits and the same XC_EBADARG cases.  Pieces, closed, winding,
+ * nseg, first_edge, n_in, sum_w and sum_wf are K18's, bit for bit.
+ * For a ring p let I_p be K18's inside set: P_p for winding 0, P_p ^ flip for winding != 0.
+ *   ENCLOSES   for two different rings a, b of the same range, a encloses b iff every node of I_b lies in I_a.  Rings of one level do
+ *              not meet: two rings are nested one way, nested the other way, or disjoint, and never have the same inside set.
+ *   PARENT     parent[b] is the ring that encloses b and has the fewest inside nodes -- the innermost enclosing ring --, -1 when no
+ *              ring encloses b.  Pieces of different ranges (levels, slabs) are never related.
+ *   OPEN PIECES bound nothing and are transparent: they are nobody's parent; their own parent is -1, depth 0, nchild 0, n_net -1 and
+ *              both net sums NaN.
+ *   DEPTH      0 where parent is -1, else depth[parent] + 1.
+ *   NCHILD     the number of rings whose parent is p.
+ *   NET        over the nodes of I_p that lie in no child's inside set: n_net their number, net_w and net_wf the sums of w and of w f
+ *              over them under K17/K18's rule (each product rounded once; the exact sum of the float64 terms rounded once, in K18's
+ *              window; a NaN term is skipped).  A net sum is NaN exactly when the ring's own gross sum (sum_w / sum_wf) is NaN.  The
+ *              children's inside sets are disjoint subsets of I_p: n_net = n_in - the sum of n_in over the children, and so for the
+ *              exact sums.
+ * per piece, packed like K18's records, beside them:
+ *     parent int64  an index into this call's piece table, poff[r] + position as the rows are packed; -1 for none
+ *     depth  int32, nchild int32
+ *     n_net  int64, net_w f64, net_wf f64 (NULL exactly when f is NULL)
+ *   Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
+ *   piece_count and the capacity / count-only protocol are K18's: short of capacity nothing is written to any record array, 1 is returned.
+ * What the call relies on is what K18 relies on (xc_cptree.hip states how the parent is found: one column walk per ring from the node
+ * across its outermost crossing).  On records that are no K12 output the tree fields are unspecified, but every access stays in bounds and
+ * every loop ends: walks within ny steps, chases of parents within the range's piece count (one that does not end there is XC_EBADARG).
+ * Stream waits, groups and workspaces are K18's.  With xc_set_kernel_timing on, xc_last_cptree_profile returns the last call's device
+ * times in ms -- ms[0] to ms[3] as xc_last_cpinside_profile, ms[4] the tree stages (top crossings, parent walks, depths, net words and
+ * their finish pass) -- the number of rounds summed over the groups, and the number of groups.                                      */
+int xc_contour_piece_tree_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                              const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                              int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                              int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
+                              int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf);
+int xc_last_cptree_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident

@@ -170,6 +170,9 @@ PROTOTYPES = {
     'xc_contour_piece_interiors_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                                  _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_last_cpinside_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_piece_tree_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                            _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_last_cptree_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1343,61 +1346,104 @@ class Context(object):
         records are never downloaded).  q, contours, periodic, w, f and flip as for `contour_interior`; periodic needs nx >= 3.  For
         one ring the rule is `contour_interior`'s with that ring alone selected: a node (r, c) is inside a ring of winding 0 when the
         ring crosses the grid line of column c between row 0 and row r an odd number of times; for a ring of winding != 0 the other
-        nodes when `flip`.  The nodes of a ring nested inside another count for the outer one too: subtract nested pieces yourself.
+        nodes when `flip`.  The nodes of a ring nested inside another count for the outer one too: `contour_piece_tree` gives the nesting.
         Returns (piece_count uint64 (nslab, N), table): `table` a structured array (PIECE_INTERIOR_DTYPE) of all pieces packed by
         (slab, contour) -- range (s, k) starts at the exclusive scan of piece_count --, each range sorted by first_edge: its rows line
         up with those of `contour_pieces`.  first_edge, nseg, closed, winding are that method's; n_in the inside nodes, sum_w the sum
         of w over them (None: weight 1), sum_wf that of w f (NaN without f) -- exact sums rounded once, NaN terms skipped, an infinite
         term makes that sum of that piece NaN.  An open piece bounds nothing: n_in -1, NaN sums."""
+        return self._piece_records('xc_contour_piece_interiors', False, q, contours, w, f, periodic, flip)
+
+    # the per-piece table of `contour_piece_tree`: that of `contour_piece_interiors` and where the piece hangs in the tree of its range
+    PIECE_TREE_DTYPE = np.dtype(PIECE_INTERIOR_DTYPE.descr + [('parent', np.int64), ('depth', np.int32), ('nchild', np.int32),
+                                                              ('n_net', np.int64), ('net_w', np.float64), ('net_wf', np.float64)])
+
+    def last_cptree_profile(self):
+        """device times of the last `contour_piece_tree` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
+        walk_ms, tree_ms, rounds, groups)"""
+        ms = (C.c_double * 5)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cptree_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], tree_ms=ms[4], rounds=r.value, groups=g.value)
+
+    def contour_piece_tree(self, q, contours, w=None, f=None, periodic=False, flip=False):
+        """Which piece of every contour is nested in which (K19, xc_contour_piece_tree_dev, on the device records of K12).  Arguments,
+        packing and row order as for `contour_piece_interiors`, whose fields come first, bit for bit.  A ring encloses another ring of
+        its (slab, contour) range when it holds all of the other's inside nodes.  Further fields: `parent` the ROW, counted from the
+        start of the piece's own range (rows in first_edge order), of the innermost ring that encloses the piece, -1 for none; `depth`
+        0 without parent, else the parent's + 1; `nchild` the rings whose parent the piece is; `n_net`, `net_w`, `net_wf` what
+        n_in, sum_w, sum_wf become when the inside nodes of the children are taken out (exact sums rounded once; NaN exactly where
+        the gross sum is).  An open piece is transparent: parent -1, depth 0, nchild 0, n_net -1, NaN net sums."""
+        return self._piece_records('xc_contour_piece_tree', True, q, contours, w, f, periodic, flip)
+
+    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip):
+        """`contour_piece_interiors` (K18) and, with `tree`, `contour_piece_tree` (K19): the same staging, one entry point each"""
         q, (nslab, ny, nx) = _stack3(q)
         contours, _, N = _levels_of(contours, nslab)
-        _check_ascending(contours, 'xc_contour_piece_interiors')
+        _check_ascending(contours, who)
         if periodic and nx < 3:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: a periodic plane needs nx >= 3')
+            raise XContourHipError(XC_EBADARG, '%s: a periodic plane needs nx >= 3' % who)
         if 2 * ny * nx >= 1 << 31:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: plane too large for 32-bit labels (2 ny nx < 2^31)')
+            raise XContourHipError(XC_EBADARG, '%s: plane too large for 32-bit labels (2 ny nx < 2^31)' % who)
         if w is not None:
             w = _contig(w, np.float64)
             if w.shape not in ((ny, nx), (nslab, ny, nx)):
-                raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: w must be (ny, nx) or (nslab, ny, nx)')
+                raise XContourHipError(XC_EBADARG, '%s: w must be (ny, nx) or (nslab, ny, nx)' % who)
         if f is not None:
             f = _contig(_f48(np.asarray(f)))
             if f.shape != (nslab, ny, nx):
-                raise XContourHipError(XC_EBADARG, 'xc_contour_piece_interiors: f must be (nslab, ny, nx)')
+                raise XContourHipError(XC_EBADARG, '%s: f must be (nslab, ny, nx)' % who)
         w_per_slab = 1 if w is not None and w.ndim == 3 else 0
         has_f = f is not None
-        dt = self.PIECE_INTERIOR_DTYPE
+        dt = self.PIECE_TREE_DTYPE if tree else self.PIECE_INTERIOR_DTYPE
+        # one piece record per segment at most: the 8-byte columns, then the 4-byte ones
+        c8 = ('first_edge', 'nseg', 'n_in', 'sum_w', 'sum_wf') + (('parent', 'n_net', 'net_w', 'net_wf') if tree else ())
+        c4 = ('closed', 'winding') + (('depth', 'nchild') if tree else ())
+        types = {'first_edge': np.int64, 'nseg': np.int64, 'n_in': np.int64, 'parent': np.int64, 'n_net': np.int64}
 
-        def interiors(cnt, total, dn, ins, outs, recs):
+        def records(cnt, total, dn, ins, outs, recs):
             if total == 0:
                 return np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt)
             ins = list(ins)
             dw = ins.pop(0) if w is not None else None
             df_ = ins.pop(0) if has_f else None
             (dpc,), (df, dto, dp, drec) = outs, recs
-            col = [drec.ptr + k * total * 8 for k in range(5)]              # first_edge, nseg, n_in, sum_w, sum_wf
-            i32 = [drec.ptr + 40 * total, drec.ptr + 44 * total]              # closed, winding
-            self._check(self.lib.xc_contour_piece_interiors_dev(
-                self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
-                dw.ptr if dw is not None else None, w_per_slab, df_.ptr if df_ is not None else None,
-                dtype_code(f.dtype) if has_f else 0, total, dpc.ptr, col[0], col[1], i32[0], i32[1], col[2], col[3],
-                col[4] if has_f else None))
+            at = {k: drec.ptr + j * total * 8 for j, k in enumerate(c8)}
+            at.update({k: drec.ptr + (8 * len(c8) + 4 * j) * total for j, k in enumerate(c4)})
+            head = (self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
+                    dw.ptr if dw is not None else None, w_per_slab, df_.ptr if df_ is not None else None,
+                    dtype_code(f.dtype) if has_f else 0, total, dpc.ptr, at['first_edge'], at['nseg'], at['closed'], at['winding'],
+                    at['n_in'], at['sum_w'], at['sum_wf'] if has_f else None)
+            if tree:
+                self._check(self.lib.xc_contour_piece_tree_dev(*head, at['parent'], at['depth'], at['nchild'], at['n_net'], at['net_w'],
+                                                               at['net_wf'] if has_f else None))
+            else:
+                self._check(self.lib.xc_contour_piece_interiors_dev(*head))
             pc = dpc.download(cnt.shape, np.uint64)
             npiece = int(pc.sum())
             out = np.empty(npiece, dtype=dt)
-            out['sum_wf'] = np.nan
-            for name, at, t in (('first_edge', col[0], np.int64), ('nseg', col[1], np.int64), ('n_in', col[2], np.int64),
-                                ('sum_w', col[3], np.float64), ('closed', i32[0], np.int32), ('winding', i32[1], np.int32)) + \
-                    ((('sum_wf', col[4], np.float64),) if has_f else ()):
-                out[name] = drec.download((npiece,), t, offset_bytes=at - drec.ptr)
-            return pc, out[_range_order(pc, out['first_edge'])]
+            for name in c8 + c4:
+                if name in ('sum_wf', 'net_wf') and not has_f:
+                    out[name] = np.nan
+                    continue
+                t = np.int32 if name in c4 else types.get(name, np.float64)
+                out[name] = drec.download((npiece,), t, offset_bytes=at[name] - drec.ptr)
+            order = _range_order(pc, out['first_edge'])
+            if tree:
+                # the entry's parent is an index into the rows as it packed them: -> the row inside the piece's own range, sorted
+                where = np.empty(npiece, dtype=np.int64)
+                where[order] = np.arange(npiece)
+                start = np.repeat(np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64), pc.ravel().astype(np.int64))
+                has = out['parent'] >= 0
+                out['parent'][has] = where[out['parent'][has]] - start[where[has.nonzero()[0]]]
+            return pc, out[order]
 
         def one(s0, s1):
-            # beside K12's records: the weights and the integrand, the piece counts, and one piece record per segment at most -- five
-            # 8-byte columns, then two 4-byte ones
+            # beside K12's records: the weights and the integrand, the piece counts, and the piece records
             ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), interiors,
-                                              inputs=tuple(ins), out_nbytes=((s1 - s0) * N * 8,), per_segment=(48,))
+            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), records,
+                                              inputs=tuple(ins), out_nbytes=((s1 - s0) * N * 8,),
+                                              per_segment=(8 * len(c8) + 4 * len(c4),))
         per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0))
         return self._batched(nslab, per, one)
 

@@ -1090,7 +1090,8 @@ class Contour2D(object):
         method's with the ring alone selected: walking a column from its first row, a node is inside a ring of winding 0 when
         the ring has been crossed an odd number of times.  For a ring that goes round the pole, `side` picks the region as
         in cal_integral_inside_contours ('upper': the side of the larger equivalent-dim coordinate).  The interior is that of
-        the ring ALONE: the nodes of a ring nested inside it are counted, not subtracted -- subtract nested pieces yourself.
+        the ring ALONE: the nodes of a ring nested inside it are counted, not subtracted -- cal_contour_piece_tree says which
+        piece is nested in which and gives the same figures net of the nested pieces.
 
         Returns, per level (out[k], or out[slab][k] with leading dims), a numpy structured array with one row per piece in
         first_edge order: its rows line up with those of cal_contour_pieces.  first_edge, nseg, closed, winding are that
@@ -1099,7 +1100,32 @@ class Contour2D(object):
         term is skipped, an infinite one gives NaN.  An open piece bounds nothing: nodes -1, area and integral NaN.  A NaN
         level, or a level without segments, gives an empty array.
         """
-        who = 'cal_integral_inside_pieces'
+        return self._piece_tables('cal_integral_inside_pieces', False, contours, tracer, integrand, periodic, side)
+
+    def cal_contour_piece_tree(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
+        """
+        Which piece of every contour is NESTED in which, and what every ring bounds net of the rings inside it, computed on
+        the GPU in one call (K12's segments, K13's pieces, K18's interiors, K19, xc_contour_piece_tree_dev).  Build-defined: the
+        reference has no counterpart.
+
+        cal_integral_inside_pieces returns a flat list of rings, each with all it encloses.  A cut-off low with a warm core, a
+        vortex with a hole, an eddy with a ring round it are rings inside rings; this method returns the hierarchy that
+        polygon libraries give with their rings (holes, RETR_TREE): a ring encloses another ring of the same level when it holds
+        all of the other's inside nodes, and a ring's parent is the innermost ring that encloses it.
+
+        Arguments, validation, the nesting of the return and the row order (first_edge) are those of
+        cal_integral_inside_pieces, and so are its fields, bit for bit.  Each level's structured array has beside them
+        `parent` (int64: the ROW of the parent in this same array, -1 for none), `depth` (int32: 0 without parent, else the
+        parent's + 1), `nchild` (int32: the rings whose parent this is), and over the inside nodes that lie inside no child
+        `nodes_net` (int64), `area_net` and, with an integrand, `integral_net` (float64): exact sums rounded once like `area`
+        and `integral`, NaN exactly where those are.  For a ring that goes round the pole `side` picks the inside, so the
+        nesting of such rings reverses with it.  An open piece bounds nothing and is transparent: parent -1, depth 0, nchild
+        0, nodes_net -1, NaN net sums, and it is nobody's parent.
+        """
+        return self._piece_tables('cal_contour_piece_tree', True, contours, tracer, integrand, periodic, side)
+
+    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side):
+        """cal_integral_inside_pieces and, with `tree`, cal_contour_piece_tree: one validation, one staging, one entry each"""
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         if side not in ('upper', 'lower'):
@@ -1122,9 +1148,10 @@ class Contour2D(object):
                 g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
         ascends = yg.size < 2 or yg[-1] >= yg[0]
         flip = (side == 'upper') != bool(ascends)
-        pc, tab = self.ctx.contour_piece_interiors(q, bs, w=dA, f=g, periodic=ring, flip=flip)
-        names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral'}
-        fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f != 'sum_wf' or g is not None]
+        call = self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
+        pc, tab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
+        names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net', 'net_wf': 'integral_net'}
+        fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f not in ('sum_wf', 'net_wf') or g is not None]
         rec = np.empty(tab.size, dtype=fields)
         for f in tab.dtype.names:
             if names.get(f, f) in rec.dtype.names:

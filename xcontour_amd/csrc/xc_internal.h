@@ -103,6 +103,7 @@ struct xc_ctx {
     float  coverturn_ms[4] = {0.f, 0.f, 0.f, 0.f};  int coverturn_rounds = 0, coverturn_groups = 0;   // K16 (xc_coverturn.hip, on K13's workspace): table, rounds, pieces / select, count
     float  cinterior_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cinterior_rounds = 0, cinterior_groups = 0;   // K17 (xc_cinside.hip, on K13's workspace): table, rounds, select, mark + scan
     float  cpinside_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpinside_rounds = 0, cpinside_groups = 0;   // K18 (xc_cpinside.hip, on K13's workspaces): table, rounds, roots / slots / signs, walks
+    float  cptree_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cptree_rounds = 0, cptree_groups = 0;   // K19 (xc_cptree.hip, on K13's workspaces): K18's four, then the tree stages
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -363,6 +364,12 @@ int launch_contour_piece_interiors(xc_ctx* ctx, int64_t nrange, const uint64_t* 
                                    const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
                                    int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
                                    int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf);
+// K19: K18's records and, per piece, its parent ring, depth, children and what it bounds net of them; waits for the stream as K18 does
+int launch_contour_piece_tree(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                              const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                              int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                              int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
+                              int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 
