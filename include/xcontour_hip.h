@@ -732,6 +732,41 @@ int xc_contour_piece_tree_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count
                               int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf);
 int xc_last_cptree_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K20 contour piece labels: which ring HOLDS each node
+ * K18 and K19 say, per ring, how many nodes, how much w and how much w f it bounds, gross and net of its children -- not WHICH nodes.
+ * This call returns K19's records unchanged and, per range, a dense map [ny][nx] that names the innermost ring round every node: what
+ * a centroid, an extremum, a composite of further fields over one ring, or the overlap of two days' blobs need (the label image that
+ * image libraries ship beside their ring tree).  Build-defined; index space; the field is not read again.
+ * Input exactly as K19 takes it, with the same limits and the same XC_EBADARG cases; the thirteen record columns are K19's, bit for bit.
+ * For a ring p let I_p be K18's inside set: P_p for winding 0, P_p ^ flip for winding != 0.
+ *   LABEL      label[range][r][c] is the ring p of that range with (r, c) in I_p and the fewest inside nodes, -1 where no ring holds the
+ *              node.  Rings of one range are nested or disjoint and never share an inside set, so that ring is unique: the DEEPEST ring
+ *              that holds the node.
+ *   OPEN PIECES are transparent, as in K19: they never appear in the map.
+ *   VALUE      the ring's position inside its own range as the rows are packed, p - poff[range] (int32: a range has fewer than 2^31
+ *              segments, hence pieces); sort the range's rows by first_edge and map the values likewise to line them up with K13.
+ *   On K12's records:
+ *     the number of nodes with label == p is n_net[p];
+ *     the nodes with label == p or label a descendant of p are I_p;
+ *     depth[label] is the number of rings that hold the node, minus 1.
+ *   label int32 [nrange][ny][nx].  On XC_OK the map is fully written, whatever the records hold; a range without segments is all -1.
+ *   piece_count and the capacity / count-only protocol are K19's: short of capacity nothing is written to any record array, 1 is
+ *   returned, and the contents of the map are then unspecified.  label == NULL with capacity > 0 is XC_EBADARG.
+ *   Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
+ * What the call relies on is what K19 relies on (xc_cplabel.hip states the scan: one pass per column from the row that lies outside
+ * every ring, a crossing enters its ring or leaves it for the ring's parent).  On records that are no K12 output the labels are
+ * unspecified (-1, or a position inside the range's piece count), but every access stays in bounds and every loop ends within ny steps.
+ * Stream waits, groups and workspaces are K18's.  With xc_set_kernel_timing on, xc_last_cplabel_profile returns the last call's device
+ * times in ms -- ms[0] to ms[4] as xc_last_cptree_profile, ms[5] the label scan (carries, scan and the -1 fill of ranges without
+ * segments) -- the number of rounds summed over the groups, and the number of groups.                                                */
+int xc_contour_piece_labels_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                                const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                                int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                                int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
+                                int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
+                                int32_t* label);
+int xc_last_cplabel_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

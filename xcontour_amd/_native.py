@@ -173,6 +173,10 @@ PROTOTYPES = {
     'xc_contour_piece_tree_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                             _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_last_cptree_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_piece_labels_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                              _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp]),
+    'xc_last_cplabel_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1376,8 +1380,27 @@ class Context(object):
         the gross sum is).  An open piece is transparent: parent -1, depth 0, nchild 0, n_net -1, NaN net sums."""
         return self._piece_records('xc_contour_piece_tree', True, q, contours, w, f, periodic, flip)
 
-    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip):
-        """`contour_piece_interiors` (K18) and, with `tree`, `contour_piece_tree` (K19): the same staging, one entry point each"""
+    def last_cplabel_profile(self):
+        """device times of the last `contour_piece_labels` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
+        walk_ms, tree_ms, label_ms, rounds, groups)"""
+        ms = (C.c_double * 6)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cplabel_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], tree_ms=ms[4], label_ms=ms[5], rounds=r.value,
+                    groups=g.value)
+
+    def contour_piece_labels(self, q, contours, w=None, f=None, periodic=False, flip=False):
+        """Which ring HOLDS every node (K20, xc_contour_piece_labels_dev, on the device records of K12).  Arguments as for
+        `contour_piece_tree`.  Returns (piece_count, table, labels): the first two are `contour_piece_tree`'s, bit for bit; `labels`
+        int32 (nslab, N, ny, nx) names per (slab, contour) the innermost ring round each node -- the one of its inside set (that of
+        `contour_piece_interiors`) with the fewest nodes -- as the ROW of that range's rows of `table` (first_edge order, counted from
+        the start of the range, like `parent`), -1 where no ring holds the node.  Open pieces never appear.  The nodes with label p
+        are those `n_net`, `net_w`, `net_wf` of row p sum over; depth[label] + 1 rings hold a node."""
+        return self._piece_records('xc_contour_piece_labels', True, q, contours, w, f, periodic, flip, labels=True)
+
+    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip, labels=False):
+        """`contour_piece_interiors` (K18), with `tree` `contour_piece_tree` (K19), and with `labels` too `contour_piece_labels`
+        (K20): the same staging, one entry point each"""
         q, (nslab, ny, nx) = _stack3(q)
         contours, _, N = _levels_of(contours, nslab)
         _check_ascending(contours, who)
@@ -1402,12 +1425,14 @@ class Context(object):
         types = {'first_edge': np.int64, 'nseg': np.int64, 'n_in': np.int64, 'parent': np.int64, 'n_net': np.int64}
 
         def records(cnt, total, dn, ins, outs, recs):
+            lshape = cnt.shape + (ny, nx)
             if total == 0:
-                return np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt)
+                none = (np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt))
+                return none + ((np.full(lshape, -1, dtype=np.int32),) if labels else ())
             ins = list(ins)
             dw = ins.pop(0) if w is not None else None
             df_ = ins.pop(0) if has_f else None
-            (dpc,), (df, dto, dp, drec) = outs, recs
+            dpc, (df, dto, dp, drec) = outs[0], recs
             at = {k: drec.ptr + j * total * 8 for j, k in enumerate(c8)}
             at.update({k: drec.ptr + (8 * len(c8) + 4 * j) * total for j, k in enumerate(c4)})
             head = (self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
@@ -1415,8 +1440,11 @@ class Context(object):
                     dtype_code(f.dtype) if has_f else 0, total, dpc.ptr, at['first_edge'], at['nseg'], at['closed'], at['winding'],
                     at['n_in'], at['sum_w'], at['sum_wf'] if has_f else None)
             if tree:
-                self._check(self.lib.xc_contour_piece_tree_dev(*head, at['parent'], at['depth'], at['nchild'], at['n_net'], at['net_w'],
-                                                               at['net_wf'] if has_f else None))
+                more = (at['parent'], at['depth'], at['nchild'], at['n_net'], at['net_w'], at['net_wf'] if has_f else None)
+            if labels:
+                self._check(self.lib.xc_contour_piece_labels_dev(*head, *more, outs[1].ptr))
+            elif tree:
+                self._check(self.lib.xc_contour_piece_tree_dev(*head, *more))
             else:
                 self._check(self.lib.xc_contour_piece_interiors_dev(*head))
             pc = dpc.download(cnt.shape, np.uint64)
@@ -1436,15 +1464,22 @@ class Context(object):
                 start = np.repeat(np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64), pc.ravel().astype(np.int64))
                 has = out['parent'] >= 0
                 out['parent'][has] = where[out['parent'][has]] - start[where[has.nonzero()[0]]]
-            return pc, out[order]
+            if not labels:
+                return pc, out[order]
+            # the entry's label is a position inside the range as it packed the rows: -> the row of the range's sorted table
+            lab = outs[1].download(lshape, np.int32)
+            first = (np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64)).reshape(cnt.shape + (1, 1))
+            has = lab >= 0
+            lab[has] = (where[(lab + first)[has]] - np.broadcast_to(first, lshape)[has]).astype(np.int32)
+            return pc, out[order], lab
 
         def one(s0, s1):
             # beside K12's records: the weights and the integrand, the piece counts, and the piece records
             ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
+            nb = ((s1 - s0) * N * 8,) + (((s1 - s0) * N * ny * nx * 4,) if labels else ())
             return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), records,
-                                              inputs=tuple(ins), out_nbytes=((s1 - s0) * N * 8,),
-                                              per_segment=(8 * len(c8) + 4 * len(c4),))
-        per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0))
+                                              inputs=tuple(ins), out_nbytes=nb, per_segment=(8 * len(c8) + 4 * len(c4),))
+        per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (4 * N if labels else 0))
         return self._batched(nslab, per, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):

@@ -1124,8 +1124,29 @@ class Contour2D(object):
         """
         return self._piece_tables('cal_contour_piece_tree', True, contours, tracer, integrand, periodic, side)
 
-    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side):
-        """cal_integral_inside_pieces and, with `tree`, cal_contour_piece_tree: one validation, one staging, one entry each"""
+    def cal_contour_piece_labels(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
+        """
+        Which ring of every contour HOLDS each node, computed on the GPU in one call (K12's segments, K13's pieces, K18's
+        interiors, K19's tree, K20, xc_contour_piece_labels_dev).  Build-defined: the reference has no counterpart.
+
+        cal_contour_piece_tree says how many nodes, how much dA and how much of one integrand every ring bounds, gross and net
+        of the rings inside it.  This method adds WHICH nodes those are -- the label image that image libraries return beside
+        their ring tree --, which is what the centroid of a cut-off low, the extremum of the tracer inside a ring, a composite of
+        further fields over one ring, or the overlap of today's blobs with yesterday's need.
+
+        Arguments and validation are those of cal_contour_piece_tree.  Returns (tree, labels): `tree` is exactly what
+        cal_contour_piece_tree returns for the same arguments; `labels` is a labelled int32 array over (..., contour, Y, X), laid
+        out and coordinated like the `mask` of cal_integral_inside_contours, levels where the caller put them.  labels[..., k, r,
+        c] is the ROW in that level's array of `tree` of the innermost ring round node (r, c) -- of the rings whose inside set
+        (cal_integral_inside_pieces') holds the node, the one with the fewest nodes --, -1 where no ring holds it.  Open pieces
+        bound nothing and never appear.  The nodes labelled p are the nodes `nodes_net`, `area_net` and `integral_net` of row p
+        sum over, and depth[label] + 1 rings hold a node.  A NaN level, or a level without segments, is -1 everywhere.
+        """
+        return self._piece_tables('cal_contour_piece_labels', True, contours, tracer, integrand, periodic, side, labels=True)
+
+    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False):
+        """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, and with `labels` too cal_contour_piece_labels: one
+        validation, one staging, one entry each"""
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         if side not in ('upper', 'lower'):
@@ -1133,11 +1154,11 @@ class Contour2D(object):
         data, dcoords = self._plane_dcoords(who, tracer)
         yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
         ring = self._x_period(periodic, xg, False, who, plain=True) is not None
-        q, lead, lshape, _ = self._float_plane(data)
+        q, lead, lshape, coords = self._float_plane(data)
         nslab, ny, nx = q.shape
         if ring and nx < 3:
             raise Exception('%s: periodic needs at least three columns along the periodic dim' % who)
-        bs, order, _ = self._sorted_levels(contours, nslab, lead, lshape)
+        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
         dA = self._dA_array(ny, nx, nslab)[0]
         if dA.ndim == 1:
             dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
@@ -1148,8 +1169,8 @@ class Contour2D(object):
                 g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
         ascends = yg.size < 2 or yg[-1] >= yg[0]
         flip = (side == 'upper') != bool(ascends)
-        call = self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
-        pc, tab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
+        call = self.ctx.contour_piece_labels if labels else self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
+        pc, tab, *lab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
         names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net', 'net_wf': 'integral_net'}
         fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f not in ('sum_wf', 'net_wf') or g is not None]
         rec = np.empty(tab.size, dtype=fields)
@@ -1157,7 +1178,15 @@ class Contour2D(object):
             if names.get(f, f) in rec.dtype.names:
                 rec[names.get(f, f)] = tab[f]
         poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
-        return self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
+        tables = self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
+        if not labels:
+            return tables
+        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
+        c['contour'] = np.asarray(ccoord)
+        c[self.dimEqV], c[self._xdim] = np.asarray(dcoords[self.dimEqV]), np.asarray(dcoords[self._xdim])
+        m = _level_order(lab[0], order[:, :, None, None])
+        dims = tuple(lead) + ('contour', self.dimEqV, self._xdim)
+        return tables, lb.wrap(m.reshape(tuple(lshape) + m.shape[1:]), dims, c, 'labels', data)
 
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):

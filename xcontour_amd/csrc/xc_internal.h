@@ -104,6 +104,7 @@ struct xc_ctx {
     float  cinterior_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cinterior_rounds = 0, cinterior_groups = 0;   // K17 (xc_cinside.hip, on K13's workspace): table, rounds, select, mark + scan
     float  cpinside_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpinside_rounds = 0, cpinside_groups = 0;   // K18 (xc_cpinside.hip, on K13's workspaces): table, rounds, roots / slots / signs, walks
     float  cptree_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cptree_rounds = 0, cptree_groups = 0;   // K19 (xc_cptree.hip, on K13's workspaces): K18's four, then the tree stages
+    float  cplabel_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cplabel_rounds = 0, cplabel_groups = 0;   // K20 (xc_cplabel.hip, on K13's workspaces): K19's five, then the label scan
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -370,6 +371,13 @@ int launch_contour_piece_tree(xc_ctx* ctx, int64_t nrange, const uint64_t* count
                               int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
                               int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
                               int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf);
+// K20: K19's records and the dense map node -> innermost ring of every range; waits for the stream as K18 does
+int launch_contour_piece_labels(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                                const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                                int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                                int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
+                                int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
+                                int32_t* label);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 
