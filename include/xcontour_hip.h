@@ -767,6 +767,51 @@ int xc_contour_piece_labels_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* cou
                                 int32_t* label);
 int xc_last_cplabel_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K21 contour piece props: what every ring HOLDS of further fields
+ * K20's map names the ring round every node; what its consumers then compute per ring -- the centroid of a cut-off low (three moments),
+ * the extremum of the tracer inside a ring, a composite of further fields over one ring -- are reductions over that map.  This call
+ * returns K19's records unchanged and those reductions, per ring and in one pass over the columns: the map [nrange][ny][nx] is never
+ * allocated and only per-piece tables are written.  Build-defined; index space.
+ * Input exactly as K19 takes it, with the same limits and the same XC_EBADARG cases; the thirteen record columns are K19's, bit for bit.
+ * Further input:
+ *   nf           the number of fields, 0 <= nf <= XC_PROPS_MAXF
+ *   g[nf]        HOST array of device pointers, one plane or stack per field
+ *   g_dtype[nf]  HOST array: XC_F32 or XC_F64
+ *   g_per_slab[nf] HOST array: 0 one plane [ny][nx] shared by all slabs, non-zero [nslab][ny][nx]
+ *   x, x_dtype   the extremum field [nslab][ny][nx], XC_F32 or XC_F64, or NULL
+ * For a ring p let I_p be K18's inside set and N_p its NET set: the nodes K20 would label p (I_p minus the inside sets of p's children).
+ * Open pieces are transparent, as in K19 and K20.
+ * per piece, packed like K19's records; column m of a per-field array starts at m * capacity:
+ *     net_g f64 [nf][capacity]  the sum over N_p of w g_m, each product rounded once (float32 fields widened first; w == NULL is weight 1)
+ *     sum_g f64 [nf][capacity]  the same over I_p
+ *       Both are K17's sums: the exact sum of the float64 terms rounded once, a window of 160 bits under 2^top, top = 12 + the frexp
+ *       exponent of max |w g_m| over the finite values of the range's slab.  A NaN term is skipped.  A +-inf term makes THAT field's sums
+ *       NaN for the ring that holds the node (net and gross) and for every ring that encloses it (gross), and for no other ring and no
+ *       other field.  For an open piece the sums are NaN.  Both pointers are NULL exactly when nf == 0.
+ *     x_min, x_max f64, at_min, at_max int64   the extremum of x over the nodes of N_p whose x is not NaN, and the flat node r * nx + c
+ *       it sits on.  Order: by value, -0.0 below +0.0 (the order of the usual monotone 64-bit key of a double); ties go to the smallest
+ *       flat node.  With no such node, or for an open piece: NaN and -1.  The four pointers are NULL exactly when x is NULL.  Only the
+ *       NET extremum is computed: the gross one is a min / max over the subtree of parent[], exact on the host.
+ *   On K12's records sum_g[m][p] is the exact sum of the terms of net_g[m] over p and all its descendants.
+ *   piece_count and the capacity / count-only protocol are K19's: short of capacity nothing is written to any record array, 1 is returned.
+ *   Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
+ * What the call relies on is what K20 relies on (xc_cpprops.hip states the scan).  On records that are no K12 output the new fields are
+ * unspecified, but every access stays in bounds and every loop ends: scans within ny steps, chases of parents within the range's piece
+ * count (one that does not end there is XC_EBADARG, as in K19).
+ * Stream waits, groups and workspaces are K18's; the staged words take 2 x 40 bytes per field and piece of min(capacity, segments).  With
+ * xc_set_kernel_timing on, xc_last_cpprops_profile returns the last call's device times in ms -- ms[0] to ms[4] as
+ * xc_last_cptree_profile, ms[5] the carries and the props scans (with the bounds of the fields' windows), ms[6] the fold up the tree and
+ * the finish pass -- the number of rounds summed over the groups, and the number of groups.                                          */
+#define XC_PROPS_MAXF 8
+int xc_contour_piece_props_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                               const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                               int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                               int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
+                               int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
+                               int nf, const void* const* g, const int* g_dtype, const int* g_per_slab, const void* x, int x_dtype,
+                               double* net_g, double* sum_g, double* x_min, double* x_max, int64_t* at_min, int64_t* at_max);
+int xc_last_cpprops_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

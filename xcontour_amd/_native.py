@@ -177,6 +177,9 @@ PROTOTYPES = {
                                               _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               _vp]),
     'xc_last_cplabel_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_piece_props_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                             _vp, C.c_int, _i64] + [_vp] * 14 + [C.c_int, _vp, _vp, _vp, _vp, C.c_int] + [_vp] * 6),
+    'xc_last_cpprops_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1398,9 +1401,33 @@ class Context(object):
         are those `n_net`, `net_w`, `net_wf` of row p sum over; depth[label] + 1 rings hold a node."""
         return self._piece_records('xc_contour_piece_labels', True, q, contours, w, f, periodic, flip, labels=True)
 
-    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip, labels=False):
-        """`contour_piece_interiors` (K18), with `tree` `contour_piece_tree` (K19), and with `labels` too `contour_piece_labels`
-        (K20): the same staging, one entry point each"""
+    XC_PROPS_MAXF = 8
+
+    def last_cpprops_profile(self):
+        """device times of the last `contour_piece_props` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
+        walk_ms, tree_ms, scan_ms, fold_ms, rounds, groups)"""
+        ms = (C.c_double * 7)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cpprops_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], tree_ms=ms[4], scan_ms=ms[5], fold_ms=ms[6],
+                    rounds=r.value, groups=g.value)
+
+    def contour_piece_props(self, q, contours, w=None, fields=(), x=None, periodic=False, flip=False):
+        """What every ring HOLDS of further fields (K21, xc_contour_piece_props_dev, on the device records of K12): the reductions
+        over `contour_piece_labels`' map without the map.  q, contours, w, periodic and flip as for `contour_piece_tree` (no
+        integrand).  fields: a sequence of at most XC_PROPS_MAXF f32 / f64 arrays, each (ny, nx) -- one plane for all slabs, uploaded
+        once per batch -- or (nslab, ny, nx); x: the extremum field (nslab, ny, nx) f32 / f64, or None.  Returns (piece_count,
+        table, props): the first two are `contour_piece_tree`'s, bit for bit; `props` a dict over the rows of `table`: 'net' and
+        'gross' f64 (npiece, nf), the sums of w g_m over the nodes labelled with the ring and over its whole inside set (exact sums
+        rounded once; NaN terms skipped; an infinite term makes that field's sum NaN for the ring that holds it and, gross, for every
+        ring round it); with x 'x_min', 'x_max' f64 and 'at_min', 'at_max' int64 (else None): the extremum of x over the ring's
+        net nodes that are not NaN and the flat node r nx + c it sits on (-0.0 below +0.0, ties to the smallest node; NaN and -1
+        without such a node).  Open pieces: NaN and -1."""
+        return self._piece_records('xc_contour_piece_props', True, q, contours, w, None, periodic, flip, props=(tuple(fields), x))
+
+    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip, labels=False, props=None):
+        """`contour_piece_interiors` (K18), with `tree` `contour_piece_tree` (K19), with `labels` too `contour_piece_labels`
+        (K20), and with `props` = (fields, x) `contour_piece_props` (K21): the same staging, one entry point each"""
         q, (nslab, ny, nx) = _stack3(q)
         contours, _, N = _levels_of(contours, nslab)
         _check_ascending(contours, who)
@@ -1416,6 +1443,17 @@ class Context(object):
             f = _contig(_f48(np.asarray(f)))
             if f.shape != (nslab, ny, nx):
                 raise XContourHipError(XC_EBADARG, '%s: f must be (nslab, ny, nx)' % who)
+        flds, x = props if props is not None else ((), None)
+        if len(flds) > self.XC_PROPS_MAXF:
+            raise XContourHipError(XC_EBADARG, '%s: %d fields, at most %d (XC_PROPS_MAXF)' % (who, len(flds), self.XC_PROPS_MAXF))
+        flds = [_contig(_f48(np.asarray(a))) for a in flds]
+        if any(a.shape not in ((ny, nx), (nslab, ny, nx)) for a in flds):
+            raise XContourHipError(XC_EBADARG, '%s: a field must be (ny, nx) or (nslab, ny, nx)' % who)
+        if x is not None:
+            x = _contig(_f48(np.asarray(x)))
+            if x.shape != (nslab, ny, nx):
+                raise XContourHipError(XC_EBADARG, '%s: x must be (nslab, ny, nx)' % who)
+        nfld, has_x = len(flds), x is not None
         w_per_slab = 1 if w is not None and w.ndim == 3 else 0
         has_f = f is not None
         dt = self.PIECE_TREE_DTYPE if tree else self.PIECE_INTERIOR_DTYPE
@@ -1428,10 +1466,14 @@ class Context(object):
             lshape = cnt.shape + (ny, nx)
             if total == 0:
                 none = (np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt))
+                if props is not None:
+                    return none + (_props_of(0, 0, None, None),)
                 return none + ((np.full(lshape, -1, dtype=np.int32),) if labels else ())
             ins = list(ins)
             dw = ins.pop(0) if w is not None else None
             df_ = ins.pop(0) if has_f else None
+            dflds = [ins.pop(0) for _ in flds]
+            dx = ins.pop(0) if has_x else None
             dpc, (df, dto, dp, drec) = outs[0], recs
             at = {k: drec.ptr + j * total * 8 for j, k in enumerate(c8)}
             at.update({k: drec.ptr + (8 * len(c8) + 4 * j) * total for j, k in enumerate(c4)})
@@ -1441,7 +1483,18 @@ class Context(object):
                     at['n_in'], at['sum_w'], at['sum_wf'] if has_f else None)
             if tree:
                 more = (at['parent'], at['depth'], at['nchild'], at['n_net'], at['net_w'], at['net_wf'] if has_f else None)
-            if labels:
+            if props is not None:
+                # behind the thirteen columns of a segment's record bytes: net_g, sum_g [nf][total], then x_min, x_max, at_min, at_max
+                pbase = drec.ptr + (8 * len(c8) + 4 * len(c4)) * total
+                pat = [pbase + j * total * 8 for j in (0, nfld, 2 * nfld, 2 * nfld + 1, 2 * nfld + 2, 2 * nfld + 3)]
+                gp = (_vp * max(nfld, 1))(*[b.ptr for b in dflds])
+                gd = (C.c_int * max(nfld, 1))(*[dtype_code(a.dtype) for a in flds])
+                gs = (C.c_int * max(nfld, 1))(*[1 if a.ndim == 3 else 0 for a in flds])
+                self._check(self.lib.xc_contour_piece_props_dev(
+                    *head, *more, nfld, C.cast(gp, _vp), C.cast(gd, _vp), C.cast(gs, _vp), dx.ptr if has_x else None,
+                    dtype_code(x.dtype) if has_x else 0, pat[0] if nfld else None, pat[1] if nfld else None,
+                    *[a if has_x else None for a in pat[2:]]))
+            elif labels:
                 self._check(self.lib.xc_contour_piece_labels_dev(*head, *more, outs[1].ptr))
             elif tree:
                 self._check(self.lib.xc_contour_piece_tree_dev(*head, *more))
@@ -1464,6 +1517,8 @@ class Context(object):
                 start = np.repeat(np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64), pc.ravel().astype(np.int64))
                 has = out['parent'] >= 0
                 out['parent'][has] = where[out['parent'][has]] - start[where[has.nonzero()[0]]]
+            if props is not None:
+                return pc, out[order], _props_of(npiece, total, lambda j, shape, t: drec.download(shape, t, offset_bytes=pat[j] - drec.ptr), order)
             if not labels:
                 return pc, out[order]
             # the entry's label is a position inside the range as it packed the rows: -> the row of the range's sorted table
@@ -1473,13 +1528,29 @@ class Context(object):
             lab[has] = (where[(lab + first)[has]] - np.broadcast_to(first, lshape)[has]).astype(np.int32)
             return pc, out[order], lab
 
+        def _props_of(npiece, total, get, order):
+            """K21's per-piece columns, downloaded by get(column block, shape, dtype), as rows in the table's sorted order"""
+            cols = {}
+            for j, name in ((0, 'net'), (1, 'gross')):
+                # column m of a per-field array starts at m * capacity, the capacity being `total`
+                if nfld and npiece:
+                    cols[name] = np.ascontiguousarray(get(j, (nfld, total), np.float64)[:, :npiece].T[order])
+                else:
+                    cols[name] = np.empty((npiece, nfld))
+            for j, name, t in ((2, 'x_min', np.float64), (3, 'x_max', np.float64), (4, 'at_min', np.int64), (5, 'at_max', np.int64)):
+                cols[name] = None if not has_x else get(j, (npiece,), t)[order] if npiece else np.empty(0, dtype=t)
+            return cols
+
         def one(s0, s1):
-            # beside K12's records: the weights and the integrand, the piece counts, and the piece records
+            # beside K12's records: the weights, the integrand, the fields and the extremum field, the piece counts, and the piece records
             ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
+            ins += [_part(a, 3, s0, s1) for a in flds] + ([x[s0:s1]] if has_x else [])
             nb = ((s1 - s0) * N * 8,) + (((s1 - s0) * N * ny * nx * 4,) if labels else ())
+            pbytes = 8 * (2 * nfld + 4) if props is not None else 0
             return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), records,
-                                              inputs=tuple(ins), out_nbytes=nb, per_segment=(8 * len(c8) + 4 * len(c4),))
+                                              inputs=tuple(ins), out_nbytes=nb, per_segment=(8 * len(c8) + 4 * len(c4) + pbytes,))
         per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (4 * N if labels else 0))
+        per += ny * nx * (sum(a.dtype.itemsize for a in flds if a.ndim == 3) + (x.dtype.itemsize if has_x else 0))
         return self._batched(nslab, per, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):

@@ -1144,9 +1144,120 @@ class Contour2D(object):
         """
         return self._piece_tables('cal_contour_piece_labels', True, contours, tracer, integrand, periodic, side, labels=True)
 
-    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False):
-        """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, and with `labels` too cal_contour_piece_labels: one
-        validation, one staging, one entry each"""
+    def cal_contour_piece_props(self, contours, fields=None, extremum=None, tracer=None, latlon=False, periodic=False, side='upper',
+                                centroid=True):
+        """
+        What every ring of every contour HOLDS of further fields -- sums of up to eight fields, the extremum of one field and
+        where it sits, the ring's centroid --, computed on the GPU in one call (K12's segments, K13's pieces, K18's interiors,
+        K19's tree, K21, xc_contour_piece_props_dev).  Build-defined: the reference has no counterpart.
+
+        These are the reductions one would take over the map of cal_contour_piece_labels (np.bincount(labels, weights=...),
+        a minimum per label): here every node is read once on the device, no map is allocated or downloaded, and only the
+        per-ring table crosses to the host.
+
+        `contours`, `tracer`, `periodic`, `side`, the order of the levels and the nesting of the return (out[k], or
+        out[slab][k] with leading dims) are those of cal_contour_piece_tree.  `fields`: a dict name -> labelled array over the
+        tracer's dims (or over the plane's two dims alone, or a 2-D numpy plane: one plane for every slab).  `extremum`: a
+        labelled array like the tracer; None: the tracer as the kernels see it; False: no extremum.
+
+        Each level's structured array has cal_contour_piece_tree's fields without an integrand (first_edge ... nodes, area,
+        parent, depth, nchild, nodes_net, area_net), bit for bit, and beside them
+          per field    `<name>`: the sum of dA * field over the ring's inside nodes (gross), `<name>_net`: over the inside nodes
+                       that lie inside no child (the nodes labelled with the ring) -- exact sums rounded once, each product
+                       rounded once; a NaN term is skipped; an infinite term makes that field NaN for the ring that holds the
+                       node and, gross, for every ring round it;
+          extremum     `vmin_net`, `vmax_net`: the smallest and largest value that is not NaN over the net nodes (-0.0 below
+                       +0.0), `vmin`, `vmax` the same over all inside nodes (folded over the ring's subtree on the host); their
+                       places on the coordinates as given `vmin_y`, `vmin_x`, `vmax_y`, `vmax_x` and `vmin_net_y`, `vmin_net_x`,
+                       `vmax_net_y`, `vmax_net_x`: of equal values the node of smallest r * nx + c.  NaN where there is none.
+          centroid=True  the moments `mom0`, `mom1`[, `mom2`] (gross) and `mom0_net` ...: the sums of dA * plane for the planes
+                       below, float64, built from the coordinates as given, and `centroid_y`, `centroid_x` from the GROSS moments
+                       (m0, m1, m2 = mom0, mom1, mom2):
+            latlon=True             planes cos(lat) cos(lon), cos(lat) sin(lon), sin(lat) (degrees -> radians in float64)
+                                    centroid_y = degrees(arctan2(m2, hypot(m0, m1)))
+                                    centroid_x = degrees(arctan2(m1, m0)) % 360
+            Cartesian, not periodic planes y, x (no mom2)
+                                    centroid_y = m0 / area
+                                    centroid_x = m1 / area
+            Cartesian, period P     planes y, cos(2 pi (x - x[0]) / P), sin(2 pi (x - x[0]) / P)
+                                    centroid_y = m0 / area
+                                    centroid_x = (arctan2(m2, m1) % (2 pi)) * P / (2 pi) + x[0]
+                       NaN where the moments are NaN and where the vector (m0, m1, m2), (m1, m2) or `area` is zero.
+        An open piece holds nothing: NaN everywhere.  More than 8 fields (the caller's plus the moments) raise.
+        """
+        return self._piece_tables('cal_contour_piece_props', True, contours, tracer, None, periodic, side,
+                                  props=dict(fields=fields, extremum=extremum, latlon=latlon, centroid=centroid))
+
+    @staticmethod
+    def _moment_planes(yg, xg, latlon, period):
+        """the planes whose dA-weighted sums give a ring's centroid (cal_contour_piece_props states them): float64 (ny, nx) each"""
+        yg, xg = np.asarray(yg, dtype=np.float64), np.asarray(xg, dtype=np.float64)
+        shape = (yg.size, xg.size)
+        if latlon:
+            lat, lon = np.deg2rad(yg)[:, None], np.deg2rad(xg)[None, :]
+            planes = [np.cos(lat) * np.cos(lon), np.cos(lat) * np.sin(lon), np.sin(lat) * np.ones_like(lon)]
+        elif period is None:
+            planes = [yg[:, None] * np.ones(shape), xg[None, :] * np.ones(shape)]
+        else:
+            a = 2 * np.pi * (xg - xg[0]) / period
+            planes = [yg[:, None] * np.ones(shape), np.cos(a)[None, :] * np.ones(shape), np.sin(a)[None, :] * np.ones(shape)]
+        return [np.ascontiguousarray(p, dtype=np.float64) for p in planes]
+
+    @staticmethod
+    def _centroid_of(m, area, latlon, period, x0):
+        """(centroid_y, centroid_x) from the gross moments m[0], m[1][, m[2]] and the gross area: the formulas of
+        cal_contour_piece_props, verbatim"""
+        with np.errstate(all='ignore'):
+            if latlon:
+                m0, m1, m2 = m
+                cy = np.degrees(np.arctan2(m2, np.hypot(m0, m1)))
+                cx = np.degrees(np.arctan2(m1, m0)) % 360
+                zero = (m0 == 0) & (m1 == 0) & (m2 == 0)
+            elif period is None:
+                m0, m1 = m
+                cy = m0 / area
+                cx = m1 / area
+                zero = area == 0
+            else:
+                m0, m1, m2 = m
+                cy = m0 / area
+                cx = (np.arctan2(m2, m1) % (2 * np.pi)) * period / (2 * np.pi) + x0
+                zero = (area == 0) | ((m1 == 0) & (m2 == 0))
+        bad = zero | np.isnan(cy) | np.isnan(cx)
+        return np.where(bad, np.nan, cy), np.where(bad, np.nan, cx)
+
+    @staticmethod
+    def _order_key(v):
+        """the monotone uint64 key of float64 values: unsigned order of the keys = order of the values, -0.0 below +0.0"""
+        b = np.ascontiguousarray(v, dtype=np.float64).view(np.uint64)
+        sign = np.uint64(1) << np.uint64(63)
+        return np.where(b & sign != 0, ~b, b | sign)
+
+    @staticmethod
+    def _gross_extrema(parent, depth, v_net, at_net, largest):
+        """the extremum over a ring's whole subtree from the net extrema of its rings: `parent` GLOBAL rows (-1: none), `v_net` NaN
+        and `at_net` -1 where a ring has none -> (v, at).  Deepest rings first, one vectorised step per depth level; among rings
+        the smaller value wins (`largest`: the larger), then the smaller flat node."""
+        v, at = np.array(v_net, dtype=np.float64), np.array(at_net, dtype=np.int64)
+        key = Contour2D._order_key(v)
+        if largest:
+            key = ~key
+        has = at >= 0
+        for d in range(int(depth.max()) if depth.size else 0, 0, -1):
+            kids = np.flatnonzero((depth == d) & has & (parent >= 0))
+            if not kids.size:
+                continue
+            o = kids[np.lexsort((at[kids], key[kids], parent[kids]))]          # by parent, then value, then node
+            best = o[np.concatenate([[True], parent[o][1:] != parent[o][:-1]])]   # the best child of every parent
+            par = parent[best]
+            take = ~has[par] | (key[best] < key[par]) | ((key[best] == key[par]) & (at[best] < at[par]))
+            best, par = best[take], par[take]
+            v[par], at[par], key[par], has[par] = v[best], at[best], key[best], True
+        return v, at
+
+    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False, props=None):
+        """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, with `labels` too cal_contour_piece_labels, and with
+        `props` cal_contour_piece_props: one validation, one staging, one entry each"""
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         if side not in ('upper', 'lower'):
@@ -1169,8 +1280,36 @@ class Contour2D(object):
                 g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
         ascends = yg.size < 2 or yg[-1] >= yg[0]
         flip = (side == 'upper') != bool(ascends)
-        call = self.ctx.contour_piece_labels if labels else self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
-        pc, tab, *lab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
+        if props is not None:
+            period = self._x_period(periodic, xg, False, who, plain=True)
+            user = dict(props['fields'] or {})
+            moments = self._moment_planes(yg, xg, props['latlon'], period) if props['centroid'] else []
+            names_g = list(user) + ['mom%d' % k for k in range(len(moments))]
+            if len(names_g) > self.ctx.XC_PROPS_MAXF:
+                raise Exception('%s: %d fields and %d moment planes are %d, more than the %d one call takes'
+                                % (who, len(user), len(moments), len(names_g), self.ctx.XC_PROPS_MAXF))
+            planes = []
+            for v in user.values():
+                v = self._float(self._plane_of(v)[0]) if lb.is_labeled(v) else nat._f48(np.asarray(v))
+                if v.ndim == 3 and v.shape[0] == 1 and v.shape != q.shape:
+                    v = v[0]
+                if v.shape not in ((ny, nx), tuple(q.shape)):
+                    raise Exception('%s: a field should lie over the tracer\'s dims or over the plane\'s two dims' % who)
+                planes.append(v)
+            ext = props['extremum']
+            if ext is None:
+                xq = q[0:nslab] if getattr(q, '_xc_lazy_stack', False) else q
+            elif ext is False:
+                xq = None
+            else:
+                xq = self._float(self._plane_of(ext)[0])
+                if xq.shape != q.shape:
+                    xq = np.ascontiguousarray(np.broadcast_to(np.asarray(xq), q.shape))
+            pc, tab, pr = self.ctx.contour_piece_props(q, bs, w=dA, fields=planes + moments, x=xq, periodic=ring, flip=flip)
+            lab = []
+        else:
+            call = self.ctx.contour_piece_labels if labels else self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
+            pc, tab, *lab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
         names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net', 'net_wf': 'integral_net'}
         fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f not in ('sum_wf', 'net_wf') or g is not None]
         rec = np.empty(tab.size, dtype=fields)
@@ -1178,6 +1317,8 @@ class Contour2D(object):
             if names.get(f, f) in rec.dtype.names:
                 rec[names.get(f, f)] = tab[f]
         poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
+        if props is not None:
+            rec = self._with_props(who, rec, poff, pr, names_g, len(user), xq is not None, yg, xg, props['latlon'], period)
         tables = self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
         if not labels:
             return tables
@@ -1187,6 +1328,41 @@ class Contour2D(object):
         m = _level_order(lab[0], order[:, :, None, None])
         dims = tuple(lead) + ('contour', self.dimEqV, self._xdim)
         return tables, lb.wrap(m.reshape(tuple(lshape) + m.shape[1:]), dims, c, 'labels', data)
+
+    def _with_props(self, who, rec, poff, pr, names_g, nuser, has_x, yg, xg, latlon, period):
+        """the packed table of cal_contour_piece_tree with K21's columns beside it (cal_contour_piece_props names them)"""
+        nx = xg.size
+        cols = []
+        for m, name in enumerate(names_g):
+            cols += [(name, pr['gross'][:, m]), (name + '_net', pr['net'][:, m])]
+        if has_x:
+            # parent is a row of the piece's own range: -> a row of the packed table
+            start = np.repeat(poff[:-1], np.diff(poff))
+            gpar = np.where(rec['parent'] >= 0, rec['parent'] + start, -1)
+            ext = {'vmin_net': (pr['x_min'], pr['at_min']), 'vmax_net': (pr['x_max'], pr['at_max']),
+                   'vmin': self._gross_extrema(gpar, rec['depth'], pr['x_min'], pr['at_min'], False),
+                   'vmax': self._gross_extrema(gpar, rec['depth'], pr['x_max'], pr['at_max'], True)}
+            cols += [(k, ext[k][0]) for k in ('vmin_net', 'vmax_net', 'vmin', 'vmax')]
+            for k in ('vmin', 'vmax', 'vmin_net', 'vmax_net'):
+                at = ext[k][1]
+                there = at >= 0
+                cols += [(k + '_y', np.where(there, yg[np.maximum(at, 0) // nx], np.nan)),
+                         (k + '_x', np.where(there, xg[np.maximum(at, 0) % nx], np.nan))]
+        if len(names_g) > nuser:
+            cy, cx = self._centroid_of([pr['gross'][:, m] for m in range(nuser, len(names_g))], rec['area'], latlon, period,
+                                       float(xg[0]))
+            cols += [('centroid_y', cy), ('centroid_x', cx)]
+        taken = set(rec.dtype.names)
+        for name, _ in cols:
+            if name in taken:
+                raise Exception('%s: the field name %r is taken' % (who, name))
+            taken.add(name)
+        out = np.empty(rec.size, dtype=rec.dtype.descr + [(name, np.float64) for name, _ in cols])
+        for name in rec.dtype.names:
+            out[name] = rec[name]
+        for name, v in cols:
+            out[name] = v
+        return out
 
     # ------------------------------------------------------------------ contour polylines
     def find_contours(self, contours, tracer=None, index=False, return_closed=False, periodic=False, return_winding=False):

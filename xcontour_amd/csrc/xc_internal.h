@@ -105,6 +105,7 @@ struct xc_ctx {
     float  cpinside_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpinside_rounds = 0, cpinside_groups = 0;   // K18 (xc_cpinside.hip, on K13's workspaces): table, rounds, roots / slots / signs, walks
     float  cptree_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cptree_rounds = 0, cptree_groups = 0;   // K19 (xc_cptree.hip, on K13's workspaces): K18's four, then the tree stages
     float  cplabel_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cplabel_rounds = 0, cplabel_groups = 0;   // K20 (xc_cplabel.hip, on K13's workspaces): K19's five, then the label scan
+    float  cpprops_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cpprops_rounds = 0, cpprops_groups = 0;   // K21 (xc_cpprops.hip, on K13's workspaces): K19's five, then the props scan, then the fold and the finish
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -378,6 +379,13 @@ int launch_contour_piece_labels(xc_ctx* ctx, int64_t nrange, const uint64_t* cou
                                 int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
                                 int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
                                 int32_t* label);
+int launch_contour_piece_props(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                               const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
+                               int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
+                               int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
+                               int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
+                               int nf, const void* const* g, const int* g_dtype, const int* g_per_slab, const void* x, int x_dtype,
+                               double* net_g, double* sum_g, double* x_min, double* x_max, int64_t* at_min, int64_t* at_max);
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 
