@@ -812,6 +812,46 @@ int xc_contour_piece_props_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
                                double* net_g, double* sum_g, double* x_min, double* x_max, int64_t* at_min, int64_t* at_max);
 int xc_last_cpprops_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K22 label overlap: which rings of two fields share nodes
+ * K20's map names the ring round every node of one field.  Following a cut-off low or a shed filament from one day to the next -- the
+ * reason to label rings at all -- is a contingency table between the maps of two fields: for every pair of rings (a of field A, b of
+ * field B) that share a node, how many nodes, how much w and how much w f they share.  This call builds that sparse table from two maps
+ * on the device; only the table is written.  Build-defined; index space.  The maps need not be K20's: any two int32 maps are taken.
+ * Input (all pointers device pointers):
+ *   lab_a, lab_b int32 [nrange][ny][nx]   the two maps; range r belongs to slab r / ncont (this matters for w when w_per_slab is
+ *                                         set, and for f); nrange a multiple of ncont >= 1
+ *   w f64 [ny][nx], or [nslab][ny][nx] with w_per_slab, or NULL: weight 1;  f [nslab][ny][nx] XC_F32 or XC_F64, or NULL
+ *   LABELS     any negative label means "no ring" and is reported as -1.  Every non-negative int32 is a valid label: no bound on the
+ *              label values is needed and none is checked.
+ *   ROWS       for every range one row per distinct pair (a, b) that occurs on at least one node.  The pair (-1, -1) is omitted;
+ *              pairs with exactly one -1 ARE rows (a node in a ring of A but in no ring of B).  Hence for every a >= 0 the sum of n
+ *              over that a's rows is the number of nodes labelled a, and the same holds for b.
+ *   a, b int32, n int64      the pair and the number of its nodes
+ *   sum_w, sum_wf f64        K17's sums over the pair's nodes, with its rules: the exact sum of the float64 terms rounded once, a window
+ *              of 160 bits under 2^top, top = 12 + the frexp exponent of max |w| resp. max |w f| over the finite values of the range's
+ *              slab; w == NULL is weight 1; a float32 f is widened first and the product is rounded once; a NaN term is skipped; a
+ *              +-inf term makes THAT sum of THAT pair NaN, and no other.  sum_wf is NULL exactly when f is NULL.
+ *   PACKING    rows are packed by range: range r starts at the exclusive scan of pair_count.  The order inside a range is the call's
+ *              own; callers sort by (a, b).
+ *   CAPACITY   K19's count-only / capacity protocol: pair_count uint64 [nrange] is always written; short of capacity nothing is
+ *              written to any row array and 1 is returned; with capacity == 0 the row pointers may be NULL.  A NULL row pointer (other
+ *              than sum_wf) with capacity > 0 is XC_EBADARG, and so are ny, nx, nrange or ncont < 1, nrange % ncont != 0, a plane of
+ *              2^31 nodes or more, and more than 65535 slabs.
+ *   Nothing depends on the order of arrival, on the cap of a group, or on the launch geometry: two calls give the same rows, bit for
+ *   bit, after sorting.
+ * xc_cpoverlap.hip states the mapping: runs of constant pair down column chunks, handed over to a per-range open-addressing table in
+ * K13's workspaces (64 bytes a slot, 104 with f; twice the range's runs rounded up to a power of two; groups of ranges under the
+ * xc_set_cpiece_workspace cap, one range always allowed; the result does not depend on it).  Allocation failure is XC_ENOMEM.  The call
+ * waits for the stream as K18 does.  With xc_set_kernel_timing on, xc_last_cpoverlap_profile returns the last call's device times in ms
+ * -- ms[0] the run count, ms[1] the accumulate pass (with the bounds of the windows and the clearing of the tables), ms[2] the finish --
+ * and the number of groups; `rounds` is 0 and is kept for symmetry with the other profile calls.                                      */
+int xc_label_overlap_dev(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, int ncont,
+                         const int32_t* lab_a, const int32_t* lab_b,      /* device, [nrange][ny][nx] each */
+                         const double* w, int w_per_slab, const void* f, int f_dtype,
+                         int64_t capacity, uint64_t* pair_count,          /* [nrange] */
+                         int32_t* a, int32_t* b, int64_t* n, double* sum_w, double* sum_wf);
+int xc_last_cpoverlap_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -16,4 +16,10 @@ from .ncio import open_dataset
 from .pipeline import KeffPlan, shard_slabs
 from ._native import Context, default_context, XContourHipError
 
+
+def label_overlap(lab_a, lab_b, w=None, f=None):
+    """The overlap of two label maps (K22, `Context.label_overlap` on the default context): numpy in, numpy out.  For callers
+    that already hold two maps of `Contour2D.cal_contour_piece_labels`."""
+    return default_context().label_overlap(lab_a, lab_b, w=w, f=f)
+
 __version__ = "0.1.0"

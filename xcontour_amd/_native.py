@@ -180,6 +180,9 @@ PROTOTYPES = {
     'xc_contour_piece_props_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                              _vp, C.c_int, _i64] + [_vp] * 14 + [C.c_int, _vp, _vp, _vp, _vp, C.c_int] + [_vp] * 6),
     'xc_last_cpprops_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_label_overlap_dev': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
+    'xc_last_cpoverlap_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -1425,9 +1428,12 @@ class Context(object):
         without such a node).  Open pieces: NaN and -1."""
         return self._piece_records('xc_contour_piece_props', True, q, contours, w, None, periodic, flip, props=(tuple(fields), x))
 
-    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip, labels=False, props=None):
+    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip, labels=False, props=None, keep=None):
         """`contour_piece_interiors` (K18), with `tree` `contour_piece_tree` (K19), with `labels` too `contour_piece_labels`
-        (K20), and with `props` = (fields, x) `contour_piece_props` (K21): the same staging, one entry point each"""
+        (K20), and with `props` = (fields, x) `contour_piece_props` (K21): the same staging, one entry point each.  keep (with
+        `labels`): a DeviceBuffer of the caller's that takes the map and keeps it on the device -- all slabs are then ONE batch
+        (the caller batches) and the return is (piece_count, table, rows) with `rows` int32 (npiece,): the row of the range's
+        sorted table for every position of the packed order the device labels count in"""
         q, (nslab, ny, nx) = _stack3(q)
         contours, _, N = _levels_of(contours, nslab)
         _check_ascending(contours, who)
@@ -1468,6 +1474,9 @@ class Context(object):
                 none = (np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt))
                 if props is not None:
                     return none + (_props_of(0, 0, None, None),)
+                if keep is not None:
+                    keep.upload(np.full(lshape, -1, dtype=np.int32))
+                    return none + (np.empty(0, dtype=np.int32),)
                 return none + ((np.full(lshape, -1, dtype=np.int32),) if labels else ())
             ins = list(ins)
             dw = ins.pop(0) if w is not None else None
@@ -1495,7 +1504,7 @@ class Context(object):
                     dtype_code(x.dtype) if has_x else 0, pat[0] if nfld else None, pat[1] if nfld else None,
                     *[a if has_x else None for a in pat[2:]]))
             elif labels:
-                self._check(self.lib.xc_contour_piece_labels_dev(*head, *more, outs[1].ptr))
+                self._check(self.lib.xc_contour_piece_labels_dev(*head, *more, keep.ptr if keep is not None else outs[1].ptr))
             elif tree:
                 self._check(self.lib.xc_contour_piece_tree_dev(*head, *more))
             else:
@@ -1521,6 +1530,8 @@ class Context(object):
                 return pc, out[order], _props_of(npiece, total, lambda j, shape, t: drec.download(shape, t, offset_bytes=pat[j] - drec.ptr), order)
             if not labels:
                 return pc, out[order]
+            if keep is not None:
+                return pc, out[order], (where - start).astype(np.int32)
             # the entry's label is a position inside the range as it packed the rows: -> the row of the range's sorted table
             lab = outs[1].download(lshape, np.int32)
             first = (np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64)).reshape(cnt.shape + (1, 1))
@@ -1545,12 +1556,151 @@ class Context(object):
             # beside K12's records: the weights, the integrand, the fields and the extremum field, the piece counts, and the piece records
             ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
             ins += [_part(a, 3, s0, s1) for a in flds] + ([x[s0:s1]] if has_x else [])
-            nb = ((s1 - s0) * N * 8,) + (((s1 - s0) * N * ny * nx * 4,) if labels else ())
+            nb = ((s1 - s0) * N * 8,) + (((s1 - s0) * N * ny * nx * 4,) if labels and keep is None else ())
             pbytes = 8 * (2 * nfld + 4) if props is not None else 0
             return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), records,
                                               inputs=tuple(ins), out_nbytes=nb, per_segment=(8 * len(c8) + 4 * len(c4) + pbytes,))
         per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (4 * N if labels else 0))
         per += ny * nx * (sum(a.dtype.itemsize for a in flds if a.ndim == 3) + (x.dtype.itemsize if has_x else 0))
+        if keep is not None:
+            return one(0, nslab)
+        return self._batched(nslab, per, one)
+
+    # the rows of `label_overlap` and `contour_piece_overlap`: one per pair of labels that share a node
+    OVERLAP_DTYPE = np.dtype([('a', np.int32), ('b', np.int32), ('n', np.int64), ('sum_w', np.float64), ('sum_wf', np.float64)])
+
+    def last_cpoverlap_profile(self):
+        """device times of the last xc_label_overlap_dev call (the last batch of `label_overlap` / `contour_piece_overlap`) under
+        set_kernel_timing(True): dict(runs_ms, accumulate_ms, finish_ms, rounds (0), groups)"""
+        ms = (C.c_double * 3)()
+        r, g = C.c_int(0), C.c_int(0)
+        self._check(self.lib.xc_last_cpoverlap_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
+        return dict(runs_ms=ms[0], accumulate_ms=ms[1], finish_ms=ms[2], rounds=r.value, groups=g.value)
+
+    def _overlap_rows(self, nrange, ny, nx, ncont, pa, pb, pw, w_per_slab, pf, f_code):
+        """K22 on two maps that lie on the device (pa, pb, pw, pf: device addresses, pw / pf or None): a count-only call, then a
+        sized one -> (pair_count uint64 (nrange,), the rows (OVERLAP_DTYPE) packed by range, in the call's own order)"""
+        head = (self.handle, nrange, ny, nx, ncont, pa, pb, pw, w_per_slab, pf, f_code)
+        dpc, drow = self.alloc(nrange * 8), None
+        try:
+            rc = self.lib.xc_label_overlap_dev(*head, 0, dpc.ptr, None, None, None, None, None)
+            if rc not in (XC_OK, 1):                             # (1: there are rows, and no room was given)
+                self._check(rc)
+            pc = dpc.download((nrange,), np.uint64)
+            total = int(pc.sum())
+            rows = np.empty(total, dtype=self.OVERLAP_DTYPE)
+            rows['sum_wf'] = np.nan
+            if total:
+                # the 4-byte columns, then the 8-byte ones
+                drow = self.alloc(total * 32)
+                at = {k: drow.ptr + j * total for k, j in (('a', 0), ('b', 4), ('n', 8), ('sum_w', 16), ('sum_wf', 24))}
+                self._check(self.lib.xc_label_overlap_dev(*head, total, dpc.ptr, at['a'], at['b'], at['n'], at['sum_w'],
+                                                          at['sum_wf'] if pf else None))
+                for k in rows.dtype.names:
+                    if k != 'sum_wf' or pf:
+                        rows[k] = drow.download((total,), rows.dtype[k], offset_bytes=at[k] - drow.ptr)
+            return pc, rows
+        finally:
+            for b in (dpc, drow):
+                if b is not None:
+                    b.free()
+
+    @staticmethod
+    def _sorted_overlap(pc, rows):
+        """rows packed by range -> each range sorted by (a, b)"""
+        return rows[np.lexsort((rows['b'], rows['a'], np.repeat(np.arange(pc.size), pc.ravel().astype(np.int64))))]
+
+    def _overlap_weights(self, who, w, f, nslab, ny, nx):
+        if w is not None:
+            w = _contig(w, np.float64)
+            if w.shape not in ((ny, nx), (nslab, ny, nx)):
+                raise XContourHipError(XC_EBADARG, '%s: w must be (ny, nx) or (nslab, ny, nx)' % who)
+        if f is not None:
+            f = _contig(_f48(np.asarray(f)))
+            if f.shape != (nslab, ny, nx):
+                raise XContourHipError(XC_EBADARG, '%s: f must be (nslab, ny, nx)' % who)
+        return w, f
+
+    def label_overlap(self, lab_a, lab_b, w=None, f=None):
+        """Which labels of two maps share nodes (K22, xc_label_overlap_dev): the contingency table of two label maps, built on the
+        device.  lab_a, lab_b int32 of one shape, (nrange, ny, nx) -- every range its own slab -- or (nslab, N, ny, nx): the maps
+        of `contour_piece_labels` of two fields.  w None (weight 1), (ny, nx) or (nslab, ny, nx) f64; f None or (nslab, ny, nx)
+        f32 / f64.  Any negative label is "no ring" and comes back as -1.  Returns (pair_count uint64 (nrange,) or (nslab, N),
+        rows): `rows` a structured array (OVERLAP_DTYPE) packed by range -- range r starts at the exclusive scan of pair_count --,
+        each range sorted by (a, b): one row per pair of labels that occurs on a node, the pair (-1, -1) left out, with n the
+        nodes of the pair, sum_w the sum of w and sum_wf that of w f over them (NaN without f): exact sums rounded once, NaN terms
+        skipped, an infinite term makes that sum of that pair NaN."""
+        who = 'xc_label_overlap'
+        lab_a, lab_b = _contig(lab_a, np.int32), _contig(lab_b, np.int32)
+        if lab_a.ndim not in (3, 4) or lab_a.shape != lab_b.shape or lab_a.size == 0:
+            raise XContourHipError(XC_EBADARG, '%s: two maps of one shape, (nrange, ny, nx) or (nslab, N, ny, nx)' % who)
+        lead, (ny, nx) = lab_a.shape[:-2], lab_a.shape[-2:]
+        nslab, N = lead[0], (lead[1] if len(lead) == 2 else 1)
+        lab_a, lab_b = lab_a.reshape(nslab, N, ny, nx), lab_b.reshape(nslab, N, ny, nx)
+        w, f = self._overlap_weights(who, w, f, nslab, ny, nx)
+        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
+
+        def one(s0, s1):
+            ins = [lab_a[s0:s1], lab_b[s0:s1]] + ([] if w is None else [_part(w, 3, s0, s1)]) + ([] if f is None else [f[s0:s1]])
+            with self._temporaries(ins, []) as bufs:
+                pw = bufs[2].ptr if w is not None else None
+                pf = bufs[-1].ptr if f is not None else None
+                pc, rows = self._overlap_rows((s1 - s0) * N, ny, nx, N, bufs[0].ptr, bufs[1].ptr, pw, w_per_slab, pf,
+                                              dtype_code(f.dtype) if f is not None else 0)
+            return pc.reshape(s1 - s0, N), self._sorted_overlap(pc, rows)
+        per = ny * nx * (2 * 4 * N + (8 if w_per_slab else 0) + (f.dtype.itemsize if f is not None else 0))
+        pc, rows = self._batched(nslab, per, one)
+        return pc.reshape(lead), rows
+
+    def contour_piece_overlap(self, qa, qb, contours, contours_b=None, w=None, f=None, periodic=False, flip=False):
+        """Which rings of two fields share nodes (K20 on each field, then K22, xc_label_overlap_dev): both label maps stay on the
+        device, only the two piece tables and the overlap rows are downloaded.  qa, qb (nslab, ny, nx) of one shape; contours
+        (levels of qa) and contours_b (levels of qb; None: `contours`) (N,) or (nslab, N), ascending; w, f, periodic and flip as
+        for `contour_piece_tree`, the same for both fields.  Returns (pc_a, table_a, pc_b, table_b, pair_count, rows): the first
+        four are `contour_piece_tree`'s of the two fields, bit for bit; pair_count uint64 (nslab, N) and `rows` (OVERLAP_DTYPE)
+        as for `label_overlap`, with a and b the ROWS of the range's rows of table_a / table_b (counted from the start of the
+        range, like `parent`), -1 for "in no ring"; range (s, k) pairs level k of qa with level k of qb."""
+        who = 'xc_contour_piece_overlap'
+        qa, (nslab, ny, nx) = _stack3(qa)
+        qb, shape_b = _stack3(qb)
+        if tuple(shape_b) != (nslab, ny, nx):
+            raise XContourHipError(XC_EBADARG, '%s: the two fields must have one shape' % who)
+        ca, _, N = _levels_of(contours, nslab)
+        cb, _, Nb = _levels_of(contours if contours_b is None else contours_b, nslab)
+        if Nb != N:
+            raise XContourHipError(XC_EBADARG, '%s: as many levels for the one field as for the other' % who)
+        w, f = self._overlap_weights(who, w, f, nslab, ny, nx)
+        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
+
+        def rows_of(a, first, rowmap):
+            has = a >= 0
+            a[has] = rowmap[first[has] + a[has]]
+
+        def one(s0, s1):
+            n = s1 - s0
+            wp, fp = _part(w, 3, s0, s1), (None if f is None else f[s0:s1])
+            maps = [self.alloc(n * N * ny * nx * 4) for _ in range(2)]
+            try:
+                ta = self._piece_records(who, True, _stack_now(qa, s0, s1), _part(ca, 2, s0, s1), wp, fp, periodic, flip, labels=True,
+                                         keep=maps[0])
+                tb = self._piece_records(who, True, _stack_now(qb, s0, s1), _part(cb, 2, s0, s1), wp, fp, periodic, flip, labels=True,
+                                         keep=maps[1])
+                with self._temporaries([a for a in (wp, fp) if a is not None], []) as bufs:
+                    pw = bufs[0].ptr if wp is not None else None
+                    pf = bufs[-1].ptr if fp is not None else None
+                    pc, rows = self._overlap_rows(n * N, ny, nx, N, maps[0].ptr, maps[1].ptr, pw, w_per_slab, pf,
+                                                  dtype_code(f.dtype) if f is not None else 0)
+            finally:
+                for b in maps:
+                    b.free()
+            # the device labels are positions in each call's packed order: -> rows of the first_edge-sorted tables
+            rng = np.repeat(np.arange(pc.size), pc.astype(np.int64))
+            for key, t in (('a', ta), ('b', tb)):
+                cnt = t[0].ravel().astype(np.int64)
+                rows_of(rows[key], (np.cumsum(cnt) - cnt)[rng], t[2])
+            return ta[0], ta[1], tb[0], tb[1], pc.reshape(n, N), self._sorted_overlap(pc, rows)
+        per = ny * nx * (qa.dtype.itemsize + qb.dtype.itemsize + 2 * 4 * N + (8 if w_per_slab else 0)
+                         + (f.dtype.itemsize if f is not None else 0))
         return self._batched(nslab, per, one)
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):

@@ -1188,6 +1188,38 @@ class Contour2D(object):
         return self._piece_tables('cal_contour_piece_props', True, contours, tracer, None, periodic, side,
                                   props=dict(fields=fields, extremum=extremum, latlon=latlon, centroid=centroid))
 
+    def cal_contour_piece_overlap(self, contours, other, other_contours=None, tracer=None, integrand=None, periodic=False,
+                                  side='upper'):
+        """
+        Which rings of the tracer's contours share nodes with which rings of ANOTHER field's -- the other day, the other
+        member --, computed on the GPU (K20, xc_contour_piece_labels_dev, on either field, then K22, xc_label_overlap_dev).
+        Build-defined: the reference has no counterpart.
+
+        This is the step that follows a cut-off low or a shed filament from one day to the next: the contingency table of
+        the two label maps of cal_contour_piece_labels (np.unique over the pairs of labels, np.bincount for every sum).  Both
+        maps stay on the device; only the two ring tables and the sparse table of pairs cross to the host.  For a ring `a` of
+        the tracer the best match is the `b` of its rows with the most `nodes` or `area`; a ring that is born or dies shows as
+        a row with -1 on the other side.
+
+        `contours`, `tracer`, `integrand`, `periodic`, `side`, the order of the levels and the nesting of the return are
+        those of cal_contour_piece_tree.  `other`: a labelled array with the dims and the shape of the tracer, validated and
+        staged like it.  `other_contours`: the levels of `other` (None: `contours`), as many as `contours`: level k of the one
+        field is paired with level k of the other, so they must ascend where `contours` ascend (a NaN level sorts last).
+
+        Returns (tree_a, tree_b, overlap).  The trees are exactly what cal_contour_piece_tree returns for the two fields (the
+        same `integrand` for both).  overlap[k] (overlap[slab][k] with leading dims) is a structured array, sorted by (a, b),
+        with one row per pair of rings that share at least one node: `a`, `b` (int32) the ROWS of tree_a[k] and tree_b[k] of
+        the innermost ring round the node in either field, -1 for "in no ring" (nodes in no ring of both fields have no row);
+        `nodes` (int64) the shared nodes, `area` the sum of dA over them and `integral` that of dA * integrand (NaN without
+        an integrand): exact sums rounded once, a NaN term skipped, an infinite one gives NaN.  The rows of one `a` partition
+        the nodes labelled `a`: their `nodes` add up to nodes_net of that row of tree_a, and likewise for `b`.  These are NET
+        overlaps, of the nodes labelled with the rings; the gross overlap of two rings with all that is nested in them is the
+        sum over both subtrees (`parent`) and is left to the caller.  A level that is NaN or without segments in both fields
+        gives an empty array.
+        """
+        return self._piece_tables('cal_contour_piece_overlap', True, contours, tracer, integrand, periodic, side,
+                                  overlap=(other, other_contours))
+
     @staticmethod
     def _moment_planes(yg, xg, latlon, period):
         """the planes whose dA-weighted sums give a ring's centroid (cal_contour_piece_props states them): float64 (ny, nx) each"""
@@ -1255,9 +1287,10 @@ class Contour2D(object):
             v[par], at[par], key[par], has[par] = v[best], at[best], key[best], True
         return v, at
 
-    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False, props=None):
-        """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, with `labels` too cal_contour_piece_labels, and with
-        `props` cal_contour_piece_props: one validation, one staging, one entry each"""
+    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False, props=None, overlap=None):
+        """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, with `labels` too cal_contour_piece_labels, with
+        `props` cal_contour_piece_props, and with `overlap` = (other, other_contours) cal_contour_piece_overlap: one validation,
+        one staging, one entry each"""
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         if side not in ('upper', 'lower'):
@@ -1307,19 +1340,51 @@ class Contour2D(object):
                     xq = np.ascontiguousarray(np.broadcast_to(np.asarray(xq), q.shape))
             pc, tab, pr = self.ctx.contour_piece_props(q, bs, w=dA, fields=planes + moments, x=xq, periodic=ring, flip=flip)
             lab = []
+        elif overlap is not None:
+            other, ocontours = overlap
+            if not lb.is_labeled(other):
+                raise Exception('%s: other should be a labelled array over the dims of the tracer' % who)
+            qb, lead_b, lshape_b, _ = self._float_plane(self._plane_dcoords(who, other)[0])
+            if tuple(qb.shape) != tuple(q.shape) or list(lead_b) != list(lead) or list(lshape_b) != list(lshape):
+                raise Exception('%s: other should have the dims and the shape of the tracer' % who)
+            if ocontours is None:
+                ocontours = contours
+            elif type(ocontours) in [int, list]:
+                ocontours = self.cal_contours(ocontours)
+            bs_b, order_b, _ = self._sorted_levels(ocontours, nslab, lead, lshape)
+            if not np.array_equal(order, order_b):
+                # range (slab, j) pairs the j-th SORTED level of either field: they must be the same level of the caller's
+                raise Exception('%s: other_contours should ascend where contours ascend (the levels of the two fields are paired '
+                                'in the order given, and both are traced in ascending order)' % who)
+            pc, tab, pc_b, tab_b, pairs, rows = self.ctx.contour_piece_overlap(q, qb, bs, contours_b=bs_b, w=dA, f=g, periodic=ring,
+                                                                               flip=flip)
         else:
             call = self.ctx.contour_piece_labels if labels else self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
             pc, tab, *lab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
         names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net', 'net_wf': 'integral_net'}
-        fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f not in ('sum_wf', 'net_wf') or g is not None]
-        rec = np.empty(tab.size, dtype=fields)
-        for f in tab.dtype.names:
-            if names.get(f, f) in rec.dtype.names:
-                rec[names.get(f, f)] = tab[f]
+
+        def named(tab):
+            fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f not in ('sum_wf', 'net_wf') or g is not None]
+            rec = np.empty(tab.size, dtype=fields)
+            for f in tab.dtype.names:
+                if names.get(f, f) in rec.dtype.names:
+                    rec[names.get(f, f)] = tab[f]
+            return rec
+
+        def per_range(rec, counts):
+            poff = np.concatenate([[0], np.cumsum(counts.ravel().astype(np.int64))])
+            return [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])]
+        rec = named(tab)
         poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
         if props is not None:
             rec = self._with_props(who, rec, poff, pr, names_g, len(user), xq is not None, yg, xg, props['latlon'], period)
-        tables = self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
+        if overlap is not None:
+            ov = np.empty(rows.size, dtype=[('a', np.int32), ('b', np.int32), ('nodes', np.int64), ('area', np.float64),
+                                            ('integral', np.float64)])
+            for k, f in (('a', 'a'), ('b', 'b'), ('nodes', 'n'), ('area', 'sum_w'), ('integral', 'sum_wf')):
+                ov[k] = rows[f]
+            return tuple(self._in_caller_order(order, lead, per_range(rec, pc), per_range(named(tab_b), pc_b), per_range(ov, pairs)))
+        tables = self._in_caller_order(order, lead, per_range(rec, pc))[0]
         if not labels:
             return tables
         c = {d: np.asarray(coords[d]) for d in lead if d in coords}
