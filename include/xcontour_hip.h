@@ -679,7 +679,7 @@ int xc_last_cinterior_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
  *     written to the record arrays and 1 is returned (capacity 0 with NULL record arrays = count only).  The number of segments is an
  *     upper bound of the number of pieces.
  * What the call relies on: a ring of K12's records is a simple closed curve, so down one column its crossings alternate between
- * entering and leaving, and the ids say which is which (xc_cpinside.hip states how).  On such records the result IS the rule above.  On
+ * entering and leaving, and the ids say which is which (xc_cpiece_interior.h states how).  On such records the result IS the rule above.  On
  * records that are no K12 output n_in and the sums are unspecified, but every access stays in bounds and every walk ends within ny steps.
  * The call waits for the stream once for K12's counts, once per group for its piece counts, once at the end.  It works in K13's groups
  * of ranges under K13's cap and in K13's workspaces (xc_set_cpiece_workspace; the result does not depend on it).  With
@@ -719,7 +719,7 @@ int xc_last_cpinside_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
  *     n_net  int64, net_w f64, net_wf f64 (NULL exactly when f is NULL)
  *   Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
  *   piece_count and the capacity / count-only protocol are K18's: short of capacity nothing is written to any record array, 1 is returned.
- * What the call relies on is what K18 relies on (xc_cptree.hip states how the parent is found: one column walk per ring from the node
+ * What the call relies on is what K18 relies on (xc_cpiece_tree.h states how the parent is found: one column walk per ring from the node
  * across its outermost crossing).  On records that are no K12 output the tree fields are unspecified, but every access stays in bounds and
  * every loop ends: walks within ny steps, chases of parents within the range's piece count (one that does not end there is XC_EBADARG).
  * Stream waits, groups and workspaces are K18's.  With xc_set_kernel_timing on, xc_last_cptree_profile returns the last call's device
@@ -753,7 +753,7 @@ int xc_last_cptree_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
  *   piece_count and the capacity / count-only protocol are K19's: short of capacity nothing is written to any record array, 1 is
  *   returned, and the contents of the map are then unspecified.  label == NULL with capacity > 0 is XC_EBADARG.
  *   Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
- * What the call relies on is what K19 relies on (xc_cplabel.hip states the scan: one pass per column from the row that lies outside
+ * What the call relies on is what K19 relies on (xc_cpiece_label.h states the scan: one pass per column from the row that lies outside
  * every ring, a crossing enters its ring or leaves it for the ring's parent).  On records that are no K12 output the labels are
  * unspecified (-1, or a position inside the range's piece count), but every access stays in bounds and every loop ends within ny steps.
  * Stream waits, groups and workspaces are K18's.  With xc_set_kernel_timing on, xc_last_cplabel_profile returns the last call's device
@@ -795,7 +795,7 @@ int xc_last_cplabel_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
  *   On K12's records sum_g[m][p] is the exact sum of the terms of net_g[m] over p and all its descendants.
  *   piece_count and the capacity / count-only protocol are K19's: short of capacity nothing is written to any record array, 1 is returned.
  *   Nothing depends on the order of the segments or of arrival, on the cap of a group, or on the launch geometry.
- * What the call relies on is what K20 relies on (xc_cpprops.hip states the scan).  On records that are no K12 output the new fields are
+ * What the call relies on is what K20 relies on (xc_cpiece_props.h states the scan).  On records that are no K12 output the new fields are
  * unspecified, but every access stays in bounds and every loop ends: scans within ny steps, chases of parents within the range's piece
  * count (one that does not end there is XC_EBADARG, as in K19).
  * Stream waits, groups and workspaces are K18's; the staged words take 2 x 40 bytes per field and piece of min(capacity, segments).  With

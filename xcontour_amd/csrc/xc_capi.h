@@ -3,6 +3,8 @@
 #pragma once
 #include "xc_internal.h"
 #include <assert.h>
+#include <utility>
+#include <vector>
 
 namespace xc {
 
@@ -18,6 +20,32 @@ inline size_t dA_bytes(int rank, int64_t nslab, int64_t ny, int64_t nx)
 #define XC_CTX(ctx) do { if (!(ctx)) return xc::fail(nullptr, XC_EBADARG, "null context"); \
                          hipError_t _e = hipSetDevice((ctx)->device); \
                          if (_e != hipSuccess) return xc::hipfail((ctx), _e, "hipSetDevice"); } while (0)
+
+// Where the time of one launcher call goes (xc_set_kernel_timing): an event between its stages, and after the call the time between two
+// marks added to ms[kind of the later mark].  Nothing happens without ctx->timing; kind -1 opens an interval without booking it; an event
+// call that fails is ignored.
+struct StageTimer {
+    xc_ctx* ctx; float* ms;
+    std::vector<std::pair<hipEvent_t, int>> marks;
+    StageTimer(xc_ctx* c, float* m) : ctx(c), ms(m) {}
+    void mark(int kind)
+    {
+        if (!ctx->timing) return;
+        hipEvent_t ev;
+        if (hipEventCreate(&ev) != hipSuccess) return;
+        (void)hipEventRecord(ev, ctx->stream);
+        marks.push_back({ev, kind});
+    }
+    void settle()
+    {
+        for (size_t k = 1; k < marks.size(); ++k) {
+            float t = 0.f;
+            if (marks[k].second >= 0 && hipEventElapsedTime(&t, marks[k - 1].first, marks[k].first) == hipSuccess) ms[marks[k].second] += t;
+        }
+        for (auto& m : marks) (void)hipEventDestroy(m.first);
+        marks.clear();
+    }
+};
 
 // ---------------------------------------------------------------- xc_context.hip
 int grow(xc_ctx* ctx, void** p, size_t* have, size_t need);          // the grow-only rule of ensure_* for any device block of the context

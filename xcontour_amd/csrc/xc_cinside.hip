@@ -214,15 +214,9 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     for (int k = 0; k < 4; ++k) ctx->cinterior_ms[k] = 0.f;
     ctx->cinterior_rounds = 0; ctx->cinterior_groups = 0;
 
-    std::vector<uint64_t> hc((size_t)nrange);
-    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<long long> off((size_t)nrange + 1);
-    off[0] = 0;
-    for (int64_t r = 0; r < nrange; ++r) {
-        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_interior: a range of 2^31 or more segments");
-        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
-    }
+    std::vector<uint64_t> hc;
+    std::vector<long long> off;
+    XC_TRY(cp_read_counts(ctx, "xc_contour_interior", nrange, count, nullptr, hc, off));
     const long long total = off[(size_t)nrange];
     if (total > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_interior: segments without their records");
 
@@ -261,23 +255,7 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     int* buf[6];
     for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
 
-    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
-    std::vector<std::pair<hipEvent_t, int>> marks;
-    auto mark = [&](int kind) {
-        if (!ctx->timing) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, ctx->stream);
-        marks.push_back({ev, kind});
-    };
-    auto settle = [&]() {
-        for (size_t k = 1; k < marks.size(); ++k) {
-            float ms = 0.f;
-            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->cinterior_ms[marks[k].second] += ms;
-        }
-        for (auto& m : marks) (void)hipEventDestroy(m.first);
-        marks.clear();
-    };
+    StageTimer tm(ctx, ctx->cinterior_ms);                                      // where the time goes (xc_set_kernel_timing)
 
     const dim3 blk(CP_TPB);
     const int64_t npl = ny * nx;
@@ -298,21 +276,18 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         return XC_OK;
     };
 
-    mark(-1);
+    tm.mark(-1);
     XC_HIP(ctx, hipMemsetAsync(key, 0, b_zero + b_small, ctx->stream));
     {
-        const dim3 bgrid((unsigned)std::min<int64_t>((npl + CI_TPB - 1) / CI_TPB, 1024), (unsigned)nslab);
-        if (!f) hipLaunchKernelGGL((k_ci_bound<void>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const void*)nullptr, mx);
-        else if (f_dtype == XC_F32) hipLaunchKernelGGL((k_ci_bound<float>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const float*)f, mx);
-        else hipLaunchKernelGGL((k_ci_bound<double>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const double*)f, mx);
+        ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, mx);
         XC_HIP(ctx, hipGetLastError());
     }
-    mark(3);
+    tm.mark(3);
     if (total > 0) {
         XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
     }
-    mark(0);
+    tm.mark(0);
     int rounds_total = 0;
     int64_t done = 0;                                                       // the ranges scanned so far
     for (const CpGroup& g : groups) {
@@ -320,36 +295,31 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         const int64_t n = off[(size_t)g.r1] - s0, ng = g.r1 - g.r0;
         const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
         const dim3 grid(cp_blocks(n));
-        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
         XC_HIP(ctx, hipMemsetAsync(bits, 0, (size_t)ng * plane * 4, ctx->stream));
-        mark(3);
-        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
-        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
+        tm.mark(3);
+        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
-        for (int k = 0; k < R; ++k) {
-            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
-            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
-        }
+        tm.mark(0);
+        b = cp_launch_rounds(ctx->stream, n, R, b);
         XC_HIP(ctx, hipGetLastError());
         rounds_total += R;
-        mark(1);
+        tm.mark(1);
         // lab, prv: the labels and the ring marks; nxt, lab2, nxt2 are free from here on
-        int* root = nxt;
-        unsigned* pn = (unsigned*)lab2;
-        int* pw = nxt2;
-        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, root, pn, pw);
+        int* root = b.nxt;
+        unsigned* pn = (unsigned*)b.lab2;
+        int* pw = b.nxt2;
+        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, root, pn, pw);
         hipLaunchKernelGGL(k_co_piece, grid, blk, 0, ctx->stream, n, s0, wrap, nx, pts, root, pn, pw);
-        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, prv, lab, pn, pw, nsel, key);
+        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, b.prv, b.lab, pn, pw, nsel, key);
         XC_HIP(ctx, hipGetLastError());
-        mark(2);
+        tm.mark(2);
         hipLaunchKernelGGL(k_ci_mark, grid, blk, 0, ctx->stream, n, s0, g.r0, E, nx, wpr, plane, select, (const long long*)e_from,
-                           (const long long*)e_to, tab, rid, root, prv, lab, pn, pw, key, bits);
+                           (const long long*)e_to, tab, rid, root, b.prv, b.lab, pn, pw, key, bits);
         XC_HIP(ctx, hipGetLastError());
-        mark(3);
+        tm.mark(3);
         hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
+        tm.mark(0);
         if (nchunk > 1) {
             const int64_t nwords = ng * nchunk * wpr;
             hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, bits, cpar);
@@ -357,17 +327,17 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         }
         XC_TRY(scan(done, g.r1, g.r0, g.r1));
         done = g.r1;
-        mark(3);
+        tm.mark(3);
     }
     if (done < nrange) XC_TRY(scan(done, nrange, 0, 0));
     ctx->cinterior_rounds = rounds_total; ctx->cinterior_groups = (int)groups.size();
     hipLaunchKernelGGL(k_ci_finish, dim3(cp_blocks(nrange)), blk, 0, ctx->stream, nrange, ncont, acc, cnt, flg, mx, (long long*)n_in, sum_w, sum_wf);
     XC_HIP(ctx, hipGetLastError());
-    mark(3);
+    tm.mark(3);
     int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    settle();
+    tm.settle();
     if (herr) return fail(ctx, XC_EBADARG, "xc_contour_interior: an edge id outside [0, 2 ny nx)");
     return XC_OK;
 }

@@ -1,6 +1,6 @@
-// The bounds behind the windows of K17's sums, shared by K17 (xc_cinside.hip) and K18 (xc_cpinside.hip); xc_cinside.hip's header states
-// the rule: the window's top sits 12 bits above max |w| (max |w f|) over the finite values of the slab.  Included inside
-// namespace xc { namespace { ... } } after xc_binning.h and xc_cpiece_sum.h; the including file includes <type_traits>.
+// The bounds behind the windows of K17's sums, shared by K17 (xc_cinside.hip), K18-K21 (xc_cprecords.hip) and K22 (xc_cpoverlap.hip);
+// xc_cinside.hip's header states the rule: the window's top sits 12 bits above max |w| (max |w f|) over the finite values of the slab.
+// Included inside namespace xc { namespace { ... } } after xc_binning.h and xc_cpiece_sum.h; the including file includes <type_traits>.
 #pragma once
 
 constexpr int CI_TPB = 256;                   // the columns of one block of K17's scan; the block of k_ci_bound
@@ -39,6 +39,16 @@ void k_ci_bound(int64_t npl, const double* __restrict__ w, int w_per_slab, const
         if (mw) atomicMax(mx + 2 * s, mw);
         if constexpr (HASF) if (mf) atomicMax(mx + 2 * s + 1, mf);
     }
+}
+
+// k_ci_bound for an integrand of f_dtype (f null: none): at most 1024 blocks a slab
+inline void ci_launch_bound(hipStream_t stream, int64_t npl, int64_t nslab, const double* w, int w_per_slab, const void* f, int f_dtype,
+                            unsigned long long* mx)
+{
+    const dim3 bgrid((unsigned)std::min<int64_t>((npl + CI_TPB - 1) / CI_TPB, 1024), (unsigned)nslab);
+    if (!f) hipLaunchKernelGGL((k_ci_bound<void>), bgrid, dim3(CI_TPB), 0, stream, npl, w, w_per_slab, (const void*)nullptr, mx);
+    else if (f_dtype == XC_F32) hipLaunchKernelGGL((k_ci_bound<float>), bgrid, dim3(CI_TPB), 0, stream, npl, w, w_per_slab, (const float*)f, mx);
+    else hipLaunchKernelGGL((k_ci_bound<double>), bgrid, dim3(CI_TPB), 0, stream, npl, w, w_per_slab, (const double*)f, mx);
 }
 
 // the top of a window from the bit pattern of the bound on one term

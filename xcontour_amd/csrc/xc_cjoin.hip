@@ -288,16 +288,9 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
     for (int k = 0; k < CJ_STAGES; ++k) ctx->cjoin_ms[k] = 0.f;
     ctx->cjoin_rounds = 0; ctx->cjoin_groups = 0;
 
-    std::vector<uint64_t> hc((size_t)nrange);
-    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipMemsetAsync(poly_count, 0, (size_t)nrange * 8, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<long long> off((size_t)nrange + 1);
-    off[0] = 0;
-    for (int64_t r = 0; r < nrange; ++r) {
-        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_polylines: a range of 2^31 or more segments");
-        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
-    }
+    std::vector<uint64_t> hc;
+    std::vector<long long> off;
+    XC_TRY(cp_read_counts(ctx, "xc_contour_polylines", nrange, count, poly_count, hc, off));
     const long long total = off[(size_t)nrange];
     if (total == 0) return XC_OK;
     if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, "xc_contour_polylines: segments without their records");
@@ -325,74 +318,53 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
     int* buf[NBUF];
     for (int k = 0; k < NBUF; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
 
-    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
-    std::vector<std::pair<hipEvent_t, int>> marks;
-    auto mark = [&](int kind) {
-        if (!ctx->timing) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, ctx->stream);
-        marks.push_back({ev, kind});
-    };
-    auto settle = [&]() {
-        for (size_t k = 1; k < marks.size(); ++k) {
-            float ms = 0.f;
-            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->cjoin_ms[marks[k].second] += ms;
-        }
-        for (auto& m : marks) (void)hipEventDestroy(m.first);
-        marks.clear();
-    };
+    StageTimer tm(ctx, ctx->cjoin_ms);                                      // where the time goes (xc_set_kernel_timing)
 
-    mark(-1);
+    tm.mark(-1);
     XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(inv, 0xff, (size_t)total * 4, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
-    mark(0);
+    tm.mark(0);
     int rounds_total = 0;
     for (const CpGroup& g : groups) {
         const long long s0 = off[(size_t)g.r0];
         const int64_t n = off[(size_t)g.r1] - s0, rows = g.r1 - g.r0;
         const int R = cp_rounds(hc, g);
         const dim3 grid(cp_blocks(n)), blk(CP_TPB), sgrid((unsigned)(rows * nchunk));
-        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
         int *p = buf[6], *root = buf[7];
         unsigned* size = (unsigned*)buf[8];
         int* pidx = buf[9];
-        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
-        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
-        hipLaunchKernelGGL(k_cj_check, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, (const long long*)e_to, tab, rid, nxt, prv, p, d_err);
-        hipLaunchKernelGGL(k_cj_unmark, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt);
+        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
+        hipLaunchKernelGGL(k_cj_check, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, (const long long*)e_to, tab, rid, b.nxt, b.prv, p, d_err);
+        hipLaunchKernelGGL(k_cj_unmark, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, b.nxt);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
-        for (int k = 0; k < R; ++k) {
-            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
-            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
-        }
+        tm.mark(0);
+        b = cp_launch_rounds(ctx->stream, n, R, b);
         XC_HIP(ctx, hipGetLastError());
-        mark(1);
+        tm.mark(1);
         // lab, prv: the labels and the ring marks; nxt, lab2, nxt2, prv2 are free from here on
-        hipLaunchKernelGGL(k_cj_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, root, size);
-        unsigned *rank = (unsigned*)nxt, *rank2 = (unsigned*)nxt2;
-        int* p2 = lab2;
-        hipLaunchKernelGGL(k_cj_rank_init, grid, blk, 0, ctx->stream, n, root, prv, p, rank, size);
+        hipLaunchKernelGGL(k_cj_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, root, size);
+        unsigned *rank = (unsigned*)b.nxt, *rank2 = (unsigned*)b.nxt2;
+        int* p2 = b.lab2;
+        hipLaunchKernelGGL(k_cj_rank_init, grid, blk, 0, ctx->stream, n, root, b.prv, p, rank, size);
         for (int k = 0; k < R; ++k) {
             hipLaunchKernelGGL(k_cj_rank_round, grid, blk, 0, ctx->stream, n, p, rank, p2, rank2);
             std::swap(p, p2); std::swap(rank, rank2);
         }
         XC_HIP(ctx, hipGetLastError());
         rounds_total += 2 * R;
-        mark(2);
-        unsigned* start = (unsigned*)prv2;
+        tm.mark(2);
+        unsigned* start = (unsigned*)b.prv2;
         hipLaunchKernelGGL(k_cj_chunk_sums, sgrid, blk, 0, ctx->stream, E, nchunk, n, tab, root, size, sums);
         hipLaunchKernelGGL(k_cj_scan_sums, dim3((unsigned)rows), blk, 0, ctx->stream, nchunk, sums, g.r0, (unsigned long long*)poly_count);
         hipLaunchKernelGGL(k_cj_apply, sgrid, blk, 0, ctx->stream, E, nchunk, n, tab, root, size, sums, start, pidx);
-        hipLaunchKernelGGL(k_cj_place, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, rid, root, rank, start, pidx, size, prv, inv, gidx, gsz, d_err);
+        hipLaunchKernelGGL(k_cj_place, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, rid, root, rank, start, pidx, size, b.prv, inv, gidx, gsz, d_err);
         XC_HIP(ctx, hipGetLastError());
-        mark(3);
+        tm.mark(3);
         hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
+        tm.mark(0);
     }
     ctx->cjoin_rounds = rounds_total; ctx->cjoin_groups = (int)groups.size();
     // the second round trip: the polyline counts (and whether the records were a join's input)
@@ -401,22 +373,22 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
     XC_HIP(ctx, hipMemcpyAsync(hp.data(), poly_count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr & CP_ERR_EDGE) { settle(); return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id outside [0, 2 ny nx)"); }
-    if (herr) { settle(); return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id repeats among the e_from or the e_to of a range"); }
+    if (herr & CP_ERR_EDGE) { tm.settle(); return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id outside [0, 2 ny nx)"); }
+    if (herr) { tm.settle(); return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id repeats among the e_from or the e_to of a range"); }
     std::vector<long long> poff((size_t)nrange + 1);
     poff[0] = 0;
     for (int64_t r = 0; r < nrange; ++r) poff[(size_t)r + 1] = poff[(size_t)r] + (long long)hp[(size_t)r];
-    if (poff[(size_t)nrange] > capacity) { settle(); return 1; }
-    mark(-1);
+    if (poff[(size_t)nrange] > capacity) { tm.settle(); return 1; }
+    tm.mark(-1);
     XC_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_cj_emit, dim3(cp_blocks(total)), dim3(CP_TPB), 0, ctx->stream, (int64_t)total, d_off, nrange, d_poff,
                        (const unsigned long long*)poly_count, inv, gidx, gsz, (const long long*)e_from, pts, (long long*)poly_nseg,
                        (int*)poly_closed, (long long*)poly_first_edge, pts_walk, (long long*)e_from_walk, (long long*)order, d_err);
     XC_HIP(ctx, hipGetLastError());
-    mark(4);
+    tm.mark(4);
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    settle();
+    tm.settle();
     if (herr) return fail(ctx, XC_EBADARG, "xc_contour_polylines: the records are not those of one xc_contour_segments call");
     return XC_OK;
 }

@@ -113,15 +113,9 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
     for (int k = 0; k < 4; ++k) ctx->coverturn_ms[k] = 0.f;
     ctx->coverturn_rounds = 0; ctx->coverturn_groups = 0;
 
-    std::vector<uint64_t> hc((size_t)nrange);
-    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<long long> off((size_t)nrange + 1);
-    off[0] = 0;
-    for (int64_t r = 0; r < nrange; ++r) {
-        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_overturning: a range of 2^31 or more segments");
-        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
-    }
+    std::vector<uint64_t> hc;
+    std::vector<long long> off;
+    XC_TRY(cp_read_counts(ctx, "xc_contour_overturning", nrange, count, nullptr, hc, off));
     const long long total = off[(size_t)nrange];
     if (total > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_overturning: segments without their records");
 
@@ -142,81 +136,60 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
     int* buf[6];
     for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
 
-    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
-    std::vector<std::pair<hipEvent_t, int>> marks;
-    auto mark = [&](int kind) {
-        if (!ctx->timing) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, ctx->stream);
-        marks.push_back({ev, kind});
-    };
-    auto settle = [&]() {
-        for (size_t k = 1; k < marks.size(); ++k) {
-            float ms = 0.f;
-            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->coverturn_ms[marks[k].second] += ms;
-        }
-        for (auto& m : marks) (void)hipEventDestroy(m.first);
-        marks.clear();
-    };
+    StageTimer tm(ctx, ctx->coverturn_ms);                                      // where the time goes (xc_set_kernel_timing)
 
     const int64_t ncol = nrange * nx;
     const dim3 ogrid(cp_blocks(ncol)), blk(CP_TPB);
-    mark(-1);
+    tm.mark(-1);
     hipLaunchKernelGGL(k_co_init, ogrid, blk, 0, ctx->stream, ncol, nrange, (int*)ncross, row_lo, row_hi, (int*)nsel, (long long*)main_first_edge,
                        (long long*)main_nseg, (int*)main_winding, key);
     XC_HIP(ctx, hipGetLastError());
-    mark(3);
+    tm.mark(3);
     XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
     if (total > 0) {
         XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
         XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
     }
-    mark(0);
+    tm.mark(0);
     int rounds_total = 0;
     for (const CpGroup& g : groups) {
         const long long s0 = off[(size_t)g.r0];
         const int64_t n = off[(size_t)g.r1] - s0;
         const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
         const dim3 grid(cp_blocks(n));
-        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
-        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
-        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
+        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
-        for (int k = 0; k < R; ++k) {
-            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
-            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
-        }
+        tm.mark(0);
+        b = cp_launch_rounds(ctx->stream, n, R, b);
         XC_HIP(ctx, hipGetLastError());
         rounds_total += R;
-        mark(1);
+        tm.mark(1);
         // lab, prv: the labels and the ring marks; nxt, lab2, nxt2 are free from here on
-        int* root = nxt;
-        unsigned* pn = (unsigned*)lab2;
-        int* pw = nxt2;
-        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, root, pn, pw);
+        int* root = b.nxt;
+        unsigned* pn = (unsigned*)b.lab2;
+        int* pw = b.nxt2;
+        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, root, pn, pw);
         hipLaunchKernelGGL(k_co_piece, grid, blk, 0, ctx->stream, n, s0, wrap, nx, pts, root, pn, pw);
-        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, prv, lab, pn, pw, (int*)nsel, key);
+        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, b.prv, b.lab, pn, pw, (int*)nsel, key);
         XC_HIP(ctx, hipGetLastError());
-        mark(2);
+        tm.mark(2);
         hipLaunchKernelGGL(k_co_count, grid, blk, 0, ctx->stream, n, s0, g.r0, E, nx, select, (const long long*)e_from, (const long long*)e_to, pts,
-                           tab, rid, root, prv, lab, pn, pw, key, (int*)ncross, row_lo, row_hi, (int*)main_winding);
+                           tab, rid, root, b.prv, b.lab, pn, pw, key, (int*)ncross, row_lo, row_hi, (int*)main_winding);
         XC_HIP(ctx, hipGetLastError());
-        mark(3);
+        tm.mark(3);
         hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
+        tm.mark(0);
     }
     ctx->coverturn_rounds = rounds_total; ctx->coverturn_groups = (int)groups.size();
     hipLaunchKernelGGL(k_co_finish, ogrid, blk, 0, ctx->stream, ncol, nrange, select, (const int*)ncross, row_lo, row_hi, key, (int*)nsel,
                        (long long*)main_first_edge, (long long*)main_nseg);
     XC_HIP(ctx, hipGetLastError());
-    mark(3);
+    tm.mark(3);
     int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    settle();
+    tm.settle();
     if (herr) return fail(ctx, XC_EBADARG, "xc_contour_overturning: an edge id outside [0, 2 ny nx)");
     return XC_OK;
 }

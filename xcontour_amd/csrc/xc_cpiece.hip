@@ -183,16 +183,9 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     for (int k = 0; k < 4; ++k) ctx->cpiece_ms[k] = 0.f;
     ctx->cpiece_rounds = 0; ctx->cpiece_groups = 0;
 
-    std::vector<uint64_t> hc((size_t)nrange);
-    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipMemsetAsync(piece_count, 0, (size_t)nrange * 8, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<long long> off((size_t)nrange + 1);
-    off[0] = 0;
-    for (int64_t r = 0; r < nrange; ++r) {
-        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, "xc_contour_pieces: a range of 2^31 or more segments");
-        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
-    }
+    std::vector<uint64_t> hc;
+    std::vector<long long> off;
+    XC_TRY(cp_read_counts(ctx, "xc_contour_pieces", nrange, count, piece_count, hc, off));
     const long long total = off[(size_t)nrange];
     if (total == 0) return XC_OK;
     if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, "xc_contour_pieces: segments without their records");
@@ -215,54 +208,33 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     int* buf[6];
     for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
 
-    // where the time goes (xc_set_kernel_timing): events between the stages, summed per kind after the call
-    std::vector<std::pair<hipEvent_t, int>> marks;
-    auto mark = [&](int kind) {
-        if (!ctx->timing) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, ctx->stream);
-        marks.push_back({ev, kind});
-    };
-    auto settle = [&]() {
-        for (size_t k = 1; k < marks.size(); ++k) {
-            float ms = 0.f;
-            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->cpiece_ms[marks[k].second] += ms;
-        }
-        for (auto& m : marks) (void)hipEventDestroy(m.first);
-        marks.clear();
-    };
+    StageTimer tm(ctx, ctx->cpiece_ms);                                      // where the time goes (xc_set_kernel_timing)
 
-    mark(-1);
+    tm.mark(-1);
     XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(d_c0, 0, b_small, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
-    mark(0);
+    tm.mark(0);
     int rounds_total = 0;
     for (const CpGroup& g : groups) {
         const long long s0 = off[(size_t)g.r0];
         const int64_t n = off[(size_t)g.r1] - s0;
         const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
         const dim3 grid(cp_blocks(n)), blk(CP_TPB);
-        int *lab = buf[0], *nxt = buf[1], *prv = buf[2], *lab2 = buf[3], *nxt2 = buf[4], *prv2 = buf[5];
-        hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, lab, prv, d_err);
-        hipLaunchKernelGGL(k_cp_link, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, nxt, prv, d_err);
+        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
-        for (int k = 0; k < R; ++k) {
-            hipLaunchKernelGGL(k_cp_round, grid, blk, 0, ctx->stream, n, lab, nxt, prv, lab2, nxt2, prv2);
-            std::swap(lab, lab2); std::swap(nxt, nxt2); std::swap(prv, prv2);
-        }
+        tm.mark(0);
+        b = cp_launch_rounds(ctx->stream, n, R, b);
         XC_HIP(ctx, hipGetLastError());
         rounds_total += R;
-        mark(1);
-        hipLaunchKernelGGL(k_cp_root, grid, blk, 0, ctx->stream, n, E, tab, rid, lab, prv, g.r0, (unsigned long long*)piece_count, nxt2, lab2);
-        hipLaunchKernelGGL(k_cp_bcast, grid, blk, 0, ctx->stream, n, s0, nxt2, lab2, pslot);
+        tm.mark(1);
+        hipLaunchKernelGGL(k_cp_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, b.prv, g.r0, (unsigned long long*)piece_count, b.nxt2, b.lab2);
+        hipLaunchKernelGGL(k_cp_bcast, grid, blk, 0, ctx->stream, n, s0, b.nxt2, b.lab2, pslot);
         XC_HIP(ctx, hipGetLastError());
-        mark(2);
+        tm.mark(2);
         hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
         XC_HIP(ctx, hipGetLastError());
-        mark(0);
+        tm.mark(0);
     }
     ctx->cpiece_rounds = rounds_total; ctx->cpiece_groups = (int)groups.size();
     // the second round trip: the piece counts (and whether the records were K12's)
@@ -271,16 +243,16 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     XC_HIP(ctx, hipMemcpyAsync(hp.data(), piece_count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr[0]) { settle(); return fail(ctx, XC_EBADARG, "xc_contour_pieces: an edge id outside [0, 2 ny nx)"); }
+    if (herr[0]) { tm.settle(); return fail(ctx, XC_EBADARG, "xc_contour_pieces: an edge id outside [0, 2 ny nx)"); }
     std::vector<long long> poff((size_t)nrange + 1);
     poff[0] = 0;
     for (int64_t r = 0; r < nrange; ++r) poff[(size_t)r + 1] = poff[(size_t)r] + (long long)hp[(size_t)r];
     const long long np = poff[(size_t)nrange];
-    if (np > capacity) { settle(); return 1; }
+    if (np > capacity) { tm.settle(); return 1; }
     XC_TRY(grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, al((size_t)np * 2 * CP_L * 8) + al((size_t)np * 4)));
     unsigned long long* acc = (unsigned long long*)ctx->cpiece_acc;
     int* flags = (int*)((char*)ctx->cpiece_acc + al((size_t)np * 2 * CP_L * 8));
-    mark(-1);
+    tm.mark(-1);
     XC_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     XC_TRY(launch_clen_window(ctx, ycoord, ny, xcoord, nx, wrap ? period : 0.0, latlon, 1, d_c0));
     hipLaunchKernelGGL(k_cp_area_window, dim3(1), dim3(256), 0, ctx->stream, ycoord, ny, xcoord, nx, latlon, wrap, period, d_c0 + 1);
@@ -296,10 +268,10 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     hipLaunchKernelGGL(k_cp_finish, dim3(cp_blocks(np)), dim3(CP_TPB), 0, ctx->stream, (int64_t)np, XC_CP_RECORDS, acc, flags, d_c0, radius);
 #undef XC_CP_RECORDS
     XC_HIP(ctx, hipGetLastError());
-    mark(3);
+    tm.mark(3);
     XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    settle();
+    tm.settle();
     if (herr[0]) return fail(ctx, XC_EBADARG, "xc_contour_pieces: the records are not those of one xc_contour_segments call (a repeated edge id)");
     return XC_OK;
 }

@@ -1,6 +1,44 @@
-// K18's per-piece interiors, shared by K18 (xc_cpinside.hip) and K19 (xc_cptree.hip); xc_cpinside.hip's header states the rule: the staged
-// records of a call's pieces, the per-segment pass that gives every ring its sign, the column walks and the finish pass.  Included
-// inside namespace xc { namespace { ... } } after xc_cpiece_link.h, xc_cpiece_slot.h, xc_cpiece_sum.h and xc_cinside_bound.h.
+// K18 -- what lies INSIDE EVERY PIECE of a contour (gfx950): per ring the nodes it encloses and the sums of w and w f over them, from K12's
+// segment records on the device.  K17 (xc_cinside.hip) answers for one selection per range and scans the whole plane for it; this answers
+// for every piece of every range in one call, at a cost proportional to the nodes the rings enclose.
+//
+// The rule (include/xcontour_hip.h, K18 section) is K17's with the selection being one piece p:
+//   X_p[r][c] = 1 iff V(r, c) carries a meridian crossing of a segment of p;  P_p[r][c] = XOR over r' < r of X_p[r'][c];
+//   ring of winding 0: inside = P_p;  ring of winding != 0: inside = P_p ^ flip;  open piece: n_in = -1, both sums NaN.
+// Pieces, closed, winding, nseg, first_edge and the slots are K13's; the sums are K17's (xc_cpiece_sum.h, the tops of xc_cinside_bound.h).
+//
+// The mapping rests on two facts about a ring of K12's records: it is a simple closed curve, so down one column its crossings alternate
+// between entering and leaving; and the ids alone say which of the two a crossing is, up to one sign per ring:
+//   a segment with e_from = V(r, c) lies in cell (r, c) when its e_to is H(r, c), H(r+1, c) or V(r, (c+1) % nx), else in cell (r, c-1)
+//   (the seam cell for c = 0 of a periodic plane).  By K12's direction table (xc_cseg_cell.h) a segment that starts on a cell's left edge
+//   has the node BELOW the crossing above the level, one that starts on a cell's right edge the node ABOVE it: s = +1 / -1.
+//   The ring's sign S, from two integer sums over its crossings: winding 0 -- the crossings pair up into (entering at row a, leaving at
+//   row b > a) with opposite s, so B = sum of s x row is -(the nodes enclosed) when the entering ones have s = +1 and +(...) otherwise:
+//   S = +1 for B < 0, -1 for B > 0.  Winding != 0 -- every column has one crossing more with the parity-1 side below it than above it, so
+//   A = sum of s is +-nx: S = the sign of A.  A crossing with s == S has the side of parity 1 below it.
+// nx == 2 on a periodic plane makes V(r, c+1) and V(r, c-1) the same edge: nx < 3 with periodic is refused.
+//
+// Per GROUP of consecutive ranges (xc_cpiece_link.h: K13's groups under K13's cap, indices group-local):
+//   phase A (K13's kernels), k_cp_root (K13's roots and slots, xc_cpiece_slot.h)
+//   the host reads the group's piece counts (they place the group's pieces in the table; once the pieces no longer fit `capacity` the
+//   rest of the call only counts)
+//   k_pi_init       the staged records of the group's pieces are cleared
+//   k_pi_piece      one thread per segment, integer atomics onto its piece: nseg, the winding by K13's seam count, A and B; the root
+//                   writes first_edge and closed
+//   k_pi_walk       one thread per segment with odd e_from of a ring and s == S.  Winding 0, or winding != 0 without flip: it walks DOWN
+//                   its column from row r + 1, reading the group's edge table -- tab[V(r', c)] is the segment that starts there, root[] of
+//                   it its piece -- and stops behind the next crossing of its own piece, or at row ny - 1.  Winding != 0 with flip: it
+//                   walks UP from row r and stops before the previous crossing of its own piece, or at row 0.  n_in and the limbs of both
+//                   sums stay in registers; one set of 64-bit integer atomics onto the piece's slot closes the walk.  At most ny steps.
+//   k_cp_unscatter  the table is handed on clean
+// Around the groups: k_ci_bound (K17's maxima behind the windows) and k_pi_finish (the limbs rounded to double, the records written to
+// the caller's arrays -- only when all pieces fit).  The edge-table reads of a walk run along a column: one 4-byte read per step from a
+// line of its own (DESIGN.md says what that costs).  Every index taken from a record or a table is checked before it addresses
+// anything; no kernel waits for another block.
+//
+// This header holds the staged records of a call's pieces, the per-segment pass that gives every ring its sign, the column walks, the
+// finish pass and the host steps that launch them; xc_cprecords.hip is the launcher of K18-K21.  Included inside
+// namespace xc { namespace { ... } } after xc_cpiece_link.h, xc_cpiece_slot.h, xc_cpiece_sum.h and xc_cinside_bound.h.
 #pragma once
 
 // the staged per-piece records (ctx->cpiece_acc), `cap` of each
@@ -14,6 +52,32 @@ struct PiStage {
     int* wd;                      // winding (seam count)
     int* cl;                      // closed
     int* flg;                     // 1: sum_w is NaN, 2: sum_wf is NaN
+};
+
+// the staged records of `cap` pieces carved from `a` (null: nothing is carved); -> their bytes, b_acc + 5 b8 + 3 b4
+inline size_t pi_carve(char* a, int64_t cap, PiStage& st)
+{
+    const size_t b8 = al((size_t)cap * 8), b4 = al((size_t)cap * 4), b_acc = al((size_t)cap * 2 * CP_L * 8);
+    if (a) {
+        st.acc = (unsigned long long*)a; a += b_acc;
+        st.cnt = (unsigned long long*)a; a += b8;
+        st.sa = (unsigned long long*)a; a += b8;
+        st.sb = (unsigned long long*)a; a += b8;
+        st.ns = (unsigned long long*)a; a += b8;
+        st.fe = (long long*)a; a += b8;
+        st.wd = (int*)a; a += b4;
+        st.cl = (int*)a; a += b4;
+        st.flg = (int*)a;
+    }
+    return b_acc + 5 * b8 + 3 * b4;
+}
+
+// what the stages of a group need of it: n segments from s0 on, ranges from r0 on, the edge table, the roots and the slots (K20's and
+// K21's scans take it whole)
+struct PlGroup {
+    int64_t n; long long s0; int64_t r0; long long E; int64_t ny, nx; int flip; int64_t cap;
+    const long long* e_from; const long long* e_to; const int* tab; const int* root; const int* slot;
+    const unsigned long long* piece_count; const long long* poff;
 };
 
 __global__ __launch_bounds__(CP_TPB)
@@ -160,4 +224,25 @@ void k_pi_finish(int64_t np, int64_t nrange, int ncont, const long long* __restr
     n_in[p] = cl ? (long long)st.cnt[p] : -1ll;
     sum_w[p] = (!cl || (fl & 1)) ? qnan : cp_to_double(st.acc + (size_t)p * 2 * CP_L, ci_top(mx[2 * s]));
     if (sum_wf) sum_wf[p] = (!cl || (fl & 2)) ? qnan : cp_to_double(st.acc + (size_t)p * 2 * CP_L + CP_L, ci_top(mx[2 * s + 1]));
+}
+
+// ---------------------------------------------------------------- the host steps of K18, each launched from one place (xc_cprecords.hip)
+// the staged records of the group's pieces [p0, p1) cleared, then the per-segment pass
+inline void pi_launch_piece(hipStream_t stream, const PlGroup& g, int64_t p0, int64_t p1, int wrap, const double* pts, const int* rid,
+                            const PiStage& st, int* err)
+{
+    hipLaunchKernelGGL(k_pi_init, dim3(cp_blocks(p1 - p0)), dim3(CP_TPB), 0, stream, p0, p1, st);
+    hipLaunchKernelGGL(k_pi_piece, dim3(cp_blocks(g.n)), dim3(CP_TPB), 0, stream, g.n, g.s0, g.r0, g.E, g.ny, g.nx, wrap, g.cap, g.e_from, g.e_to,
+                       pts, rid, g.root, g.slot, g.piece_count, g.poff, st, err);
+}
+
+// the column walks for an integrand of f_dtype (f null: none)
+inline void pi_launch_walk(hipStream_t stream, const PlGroup& g, int ncont, const int* rid, const double* w, int w_per_slab, const void* f,
+                           int f_dtype, const unsigned long long* mx, const PiStage& st, int* err)
+{
+#define XC_PI_WALK(FT_) hipLaunchKernelGGL((k_pi_walk<FT_>), dim3(cp_blocks(g.n)), dim3(CP_TPB), 0, stream, g.n, g.s0, g.r0, g.E, g.ny, g.nx, g.flip, \
+                                           ncont, g.cap, g.e_from, g.e_to, g.tab, rid, g.root, g.slot, g.piece_count, g.poff, w, w_per_slab,       \
+                                           (const FT_*)f, mx, st, err)
+    if (!f) XC_PI_WALK(void); else if (f_dtype == XC_F32) XC_PI_WALK(float); else XC_PI_WALK(double);
+#undef XC_PI_WALK
 }

@@ -1,6 +1,7 @@
-// Phase A of the device joins, shared by K13 (xc_cpiece.hip) and K14 (xc_cjoin.hip): the dense edge tables of a GROUP of consecutive
-// ranges, the next / prev links, the pointer-doubling rounds, and the plan that cuts the ranges into groups.  xc_cpiece.hip's header
-// states the rule.  Included inside namespace xc { namespace { ... } }, like xc_binning.h.
+// Phase A of the device joins, shared by K13 (xc_cpiece.hip), K14 (xc_cjoin.hip), K16 (xc_coverturn.hip), K17 (xc_cinside.hip) and
+// K18-K21 (xc_cprecords.hip): the dense edge tables of a GROUP of consecutive ranges, the next / prev links, the pointer-doubling rounds,
+// the plan that cuts the ranges into groups and the host steps every one of these launchers takes.  xc_cpiece.hip's header states the
+// rule.  Included inside namespace xc { namespace { ... } } after xc_capi.h, like xc_binning.h.
 #pragma once
 
 constexpr int CP_TPB = 256;
@@ -106,4 +107,67 @@ inline int cp_rounds(const std::vector<uint64_t>& hc, const CpGroup& g)
     int R = 1;
     while ((1ull << (R - 1)) < cmaxg) ++R;
     return R;
+}
+
+// K12's counts on the host and their exclusive scan: one wait for the stream.  `clear` (the call's own per-range counts, or null) is
+// cleared between the copy and the wait.
+inline int cp_read_counts(xc_ctx* ctx, const char* who, int64_t nrange, const uint64_t* count, uint64_t* clear, std::vector<uint64_t>& hc,
+                          std::vector<long long>& off)
+{
+    hc.resize((size_t)nrange);
+    XC_HIP(ctx, hipMemcpyAsync(hc.data(), count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (clear) XC_HIP(ctx, hipMemsetAsync(clear, 0, (size_t)nrange * 8, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    off.assign((size_t)nrange + 1, 0);
+    for (int64_t r = 0; r < nrange; ++r) {
+        if (hc[(size_t)r] >= (1ull << 31)) return fail(ctx, XC_EBADARG, std::string(who) + ": a range of 2^31 or more segments");
+        off[(size_t)r + 1] = off[(size_t)r] + (long long)hc[(size_t)r];
+    }
+    return XC_OK;
+}
+
+// which of a group's six buffers [nmax] hold what: lab, nxt and prv stand, lab2, nxt2 and prv2 are free
+struct CpRoles { int *lab, *nxt, *prv, *lab2, *nxt2, *prv2; };
+
+// the edge table of group g (n segments from s0 on) and the links
+inline CpRoles cp_launch_table(hipStream_t stream, int64_t n, long long s0, const long long* d_off, const CpGroup& g, long long E,
+                               const int64_t* e_from, const int64_t* e_to, int* tab, int* rid, int* const* buf, int* d_err)
+{
+    const dim3 grid(cp_blocks(n)), blk(CP_TPB);
+    const CpRoles b = {buf[0], buf[1], buf[2], buf[3], buf[4], buf[5]};
+    hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, b.lab, b.prv, d_err);
+    hipLaunchKernelGGL(k_cp_link, grid, blk, 0, stream, n, s0, E, (const long long*)e_to, tab, rid, b.nxt, b.prv, d_err);
+    return b;
+}
+
+// R doubling rounds; -> the roles after them
+inline CpRoles cp_launch_rounds(hipStream_t stream, int64_t n, int R, CpRoles b)
+{
+    for (int k = 0; k < R; ++k) {
+        hipLaunchKernelGGL(k_cp_round, dim3(cp_blocks(n)), dim3(CP_TPB), 0, stream, n, b.lab, b.nxt, b.prv, b.lab2, b.nxt2, b.prv2);
+        std::swap(b.lab, b.lab2); std::swap(b.nxt, b.nxt2); std::swap(b.prv, b.prv2);
+    }
+    return b;
+}
+
+// The row chunks of a column scan (K20, K21: xc_cpiece_label.h; K22: xc_cpoverlap.hip).
+constexpr int PL_ROWS = 16;                   // a chunk of a column has at least this many rows ...
+constexpr int PL_CHUNKS = 32;                 // ... and a column at most this many chunks
+
+// the chunks of a column: `rows` rows each (the last one what is left), `nchunk` of them
+inline void pl_geometry(int64_t ny, int64_t* rows, int64_t* nchunk)
+{
+    int64_t R = (ny + PL_CHUNKS - 1) / PL_CHUNKS;
+    if (R < PL_ROWS) R = PL_ROWS;
+    *rows = R; *nchunk = (ny + R - 1) / R;
+}
+
+// thread -> (range of the group, chunk, column), columns fastest
+__device__ __forceinline__ bool pl_thread(int64_t ng, int64_t nchunk, int64_t nx, int64_t& rl, int64_t& k, int64_t& c)
+{
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= ng * nchunk * nx) return false;
+    const int64_t rk = i / nx;
+    c = i - rk * nx; rl = rk / nchunk; k = rk - rl * nchunk;
+    return true;
 }

@@ -1,4 +1,4 @@
-// K13's root and slot numbering, shared by K13 (xc_cpiece.hip) and K18 (xc_cpinside.hip); xc_cpiece.hip's header states the rule: after
+// K13's root and slot numbering, shared by K13 (xc_cpiece.hip) and K18-K21 (xc_cprecords.hip); xc_cpiece.hip's header states the rule: after
 // phase A (xc_cpiece_link.h) a segment that is its own root takes the next slot of its range and notes whether its piece is open.
 // Included inside namespace xc { namespace { ... } } after xc_cpiece_link.h.
 #pragma once

@@ -1,6 +1,39 @@
-// K19's tree of pieces, shared by K19 (xc_cptree.hip) and K20 (xc_cplabel.hip); xc_cptree.hip's header states the rule and the mapping:
-// the staged tree records of a call's pieces, the top crossings, the parent walks, the depths, the net words and the finish pass.
-// Included inside namespace xc { namespace { ... } } after xc_cpiece_interior.h.
+// K19 -- which piece of a contour is NESTED in which (gfx950): per ring its parent (the innermost ring that encloses it), its depth, the
+// number of its children and what it bounds NET of them, beside K18's records, from K12's segment records on the device.
+//
+// The rule (include/xcontour_hip.h, K19 section): with I_p K18's inside set of ring p, a encloses b iff I_b is a subset of I_a; parent[b] is
+// the enclosing ring with the fewest inside nodes; open pieces are transparent; the net records are those of I_p minus its children's sets.
+//
+// The mapping rests on K18's facts (xc_cpiece_interior.h) and two more.  Rings of one range do not meet, so two of them are nested or disjoint,
+// and a ring other than b holds ALL of I_b as soon as it holds the one node that lies across b's boundary from a node of I_b.  And down a
+// column a ring's crossings alternate, so a walker that enters a ring it started outside of is outside again behind that ring's next
+// crossing: whatever it meets in between is nested in that ring and cannot hold the start node.
+//   OUTSIDE NODE   without flip row 0 lies outside EVERY ring (P = 0 there): the node ABOVE a ring's topmost crossing (the smallest odd
+//                  e_from among its crossings) is outside it, and between that node and row 0 the column never meets the ring again.
+//                  With flip row 0 lies INSIDE every ring that goes round, and it is row ny - 1 that lies outside every ring (a ring of
+//                  winding 0 has an even number of crossings above it, one that goes round an odd number): the node BELOW a ring's
+//                  bottommost crossing is outside it.  A walk that ends on the row that is outside everything has missed no ring.
+//   PARENT WALK    from that node away from the ring, to row 0 (with flip: to row ny - 1).  A crossing of another ring x has x's inside BELOW it iff
+//                  (s == S_x) != (winding_x != 0 && flip) (K18's s and S).  Inside on the walker's side: the walker is inside x, and x is
+//                  the innermost such ring -- parent = x.  Inside on the far side: the walker enters x from outside and skips everything up
+//                  to x's next crossing in this column.  Crossings of open pieces are ignored.  One `skip` register; at most ny steps.
+//
+// Per group, between K18's walks and k_cp_unscatter (the edge table, root[] and slot[] still stand):
+//   k_pt_init    the staged tree records of the group's pieces are cleared
+//   k_pt_top     one thread per segment: one 64-bit integer atomicMin of its crossing's key onto its ring (e_from, or ~e_from with
+//                flip, when the walks go down, so that one minimum serves both)
+//   k_pt_parent  one thread per ring: the parent walk; one integer atomic counts the child at its parent
+//   k_pt_depth   one thread per ring chases its parents, at most the range's piece count of them; a chase that does not end there sets
+//                PT_ERR_TREE in the err word (XC_EBADARG after the call)
+//   k_pt_net     every ring with a parent adds its NEGATED n_in and limbs to the parent's net words, with 64-bit integer atomics.  K18's
+//                limbs are signed sums of 32-bit chunks in two's-complement 64-bit words, so negation is exact, and the words of
+//                (gross - children) are the words the net nodes alone would have given: cp_to_double rounds the exact net sum once.
+// k_pt_finish adds the gross and the net words and writes the records, after k_pi_finish has written K18's.  Every index taken from a
+// record or a table is checked before it addresses anything; no kernel waits for another block; no LDS, no scratch.
+//
+// This header holds the staged tree records of a call's pieces, the top crossings, the parent walks, the depths, the net words, the
+// finish pass and the host step that launches the stages of a group.  Included inside namespace xc { namespace { ... } } after
+// xc_cpiece_interior.h.
 #pragma once
 
 constexpr int PT_ERR_TREE = 4;                // beside CP_ERR_EDGE and CP_ERR_LINK: a chase of parents that does not end
@@ -15,6 +48,21 @@ struct PtStage {
     int* nch;                     // children
     int* dep;                     // depth
 };
+
+// the staged tree records of `cap` pieces carved from `a` (null: nothing is carved); -> their bytes, b_acc + 3 b8 + 2 b4
+inline size_t pt_carve(char* a, int64_t cap, PtStage& pt)
+{
+    const size_t b8 = al((size_t)cap * 8), b4 = al((size_t)cap * 4), b_acc = al((size_t)cap * 2 * CP_L * 8);
+    if (a) {
+        pt.net = (unsigned long long*)a; a += b_acc;
+        pt.key = (unsigned long long*)a; a += b8;
+        pt.nnet = (unsigned long long*)a; a += b8;
+        pt.par = (long long*)a; a += b8;
+        pt.nch = (int*)a; a += b4;
+        pt.dep = (int*)a;
+    }
+    return b_acc + 3 * b8 + 2 * b4;
+}
 
 __global__ __launch_bounds__(CP_TPB)
 void k_pt_init(int64_t p0, int64_t p1, PtStage pt)
@@ -142,4 +190,19 @@ void k_pt_finish(int64_t np, int64_t nrange, int ncont, const long long* __restr
     for (int l = 0; l < 2 * CP_L; ++l) a[l] = st.acc[(size_t)p * 2 * CP_L + l] + pt.net[(size_t)p * 2 * CP_L + l];
     net_w[p] = (!cl || (fl & 1)) ? qnan : cp_to_double(a, ci_top(mx[2 * s]));
     if (net_wf) net_wf[p] = (!cl || (fl & 2)) ? qnan : cp_to_double(a + CP_L, ci_top(mx[2 * s + 1]));
+}
+
+// ---------------------------------------------------------------- the host step of K19, launched from one place (xc_cprecords.hip)
+// the tree stages of a group (ranges [g.r0, r1), pieces [p0, p1)), behind K18's walks
+inline void pt_launch_group(hipStream_t stream, const PlGroup& g, int64_t r1, int64_t p0, int64_t p1, const int* rid, const PiStage& st,
+                            const PtStage& pt, int* err)
+{
+    const dim3 grid(cp_blocks(g.n)), pgrid(cp_blocks(p1 - p0)), blk(CP_TPB);
+    hipLaunchKernelGGL(k_pt_init, pgrid, blk, 0, stream, p0, p1, pt);
+    hipLaunchKernelGGL(k_pt_top, grid, blk, 0, stream, g.n, g.s0, g.r0, g.E, g.ny, g.nx, g.flip, g.cap, g.e_from, g.e_to, rid, g.root, g.slot,
+                       g.piece_count, g.poff, st, pt, err);
+    hipLaunchKernelGGL(k_pt_parent, pgrid, blk, 0, stream, p0, p1, g.n, g.s0, g.r0, r1, g.E, g.ny, g.nx, g.flip, g.cap, g.e_from, g.e_to, g.tab,
+                       g.root, g.slot, g.piece_count, g.poff, st, pt, err);
+    hipLaunchKernelGGL(k_pt_depth, pgrid, blk, 0, stream, p0, p1, g.r0, r1, g.poff, st, pt, err);
+    hipLaunchKernelGGL(k_pt_net, pgrid, blk, 0, stream, p0, p1, st, pt);
 }

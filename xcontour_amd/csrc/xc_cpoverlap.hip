@@ -1,6 +1,6 @@
 // K22 -- the OVERLAP of two label maps (gfx950): per range the contingency table of two dense int32 maps [ny][nx] -- for every pair of
 // labels (a, b) that share a node the number of shared nodes, the sum of w and the sum of w f over them -- built on the device; only the
-// sparse table crosses to the host.  The maps are K20's (xc_cplabel.hip) of two fields: today's rings against yesterday's.
+// sparse table crosses to the host.  The maps are K20's (xc_cpiece_label.h) of two fields: today's rings against yesterday's.
 //
 // The rule (include/xcontour_hip.h, K22 section).  The mapping is K20's layout without its carries (the maps are dense):
 //   THREADS    one thread per (range of the group, chunk of rows, column), columns fastest (pl_geometry, pl_thread): the two label loads
@@ -42,9 +42,6 @@ namespace {
 #include "xc_cpiece_slot.h"
 #include "xc_cpiece_sum.h"
 #include "xc_cinside_bound.h"
-#include "xc_cpiece_interior.h"
-#include "xc_cpiece_tree.h"
-#include "xc_cpiece_label.h"
 
 constexpr unsigned long long PO_EMPTY = ~0ull;   // no pair yet: the key of (-1, -1)
 constexpr int PO_ERR_FULL = 1;                   // an insertion found no slot within the table
@@ -323,28 +320,13 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     long long* d_poff = (long long*)((char*)d_soff + b_r);
     unsigned long long* d_cur = (unsigned long long*)((char*)d_poff + b_r);
 
-    std::vector<std::pair<hipEvent_t, int>> marks;
-    auto mark = [&](int kind) {
-        if (!ctx->timing) return;
-        hipEvent_t ev;
-        if (hipEventCreate(&ev) != hipSuccess) return;
-        (void)hipEventRecord(ev, ctx->stream);
-        marks.push_back({ev, kind});
-    };
-    auto settle = [&]() {
-        for (size_t k = 1; k < marks.size(); ++k) {
-            float ms = 0.f;
-            if (marks[k].second >= 0 && hipEventElapsedTime(&ms, marks[k - 1].first, marks[k].first) == hipSuccess) ctx->cpoverlap_ms[marks[k].second] += ms;
-        }
-        for (auto& m : marks) (void)hipEventDestroy(m.first);
-        marks.clear();
-    };
-    auto bail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); settle(); return rc; };
+    StageTimer tm(ctx, ctx->cpoverlap_ms);                                      // where the time goes (xc_set_kernel_timing)
+    auto bail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); tm.settle(); return rc; };
 
     const dim3 blk(CP_TPB);
     const int* la = (const int*)lab_a;
     const int* lb = (const int*)lab_b;
-    mark(-1);
+    tm.mark(-1);
     XC_HIP(ctx, hipMemsetAsync(mx, 0, b_mx + b_small, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(d_runs, 0, (size_t)nrange * 8, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(d_cur, 0, (size_t)nrange * 8, ctx->stream));
@@ -354,7 +336,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         hipLaunchKernelGGL(k_po_runs, dim3(cp_blocks(ng * nchunk * nx)), blk, 0, ctx->stream, ng, r0, rows, nchunk, ny, nx, la, lb, d_runs);
     }
     XC_HIP(ctx, hipGetLastError());
-    mark(0);
+    tm.mark(0);
     std::vector<uint64_t> runs((size_t)nrange);
     XC_HIP(ctx, hipMemcpyAsync(runs.data(), d_runs, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -369,7 +351,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         soff[(size_t)r + 1] = soff[(size_t)r] + s;
         total_runs += runs[(size_t)r];
     }
-    if (total_runs == 0) { settle(); return XC_OK; }                       // both maps hold no ring: no rows (pair_count is cleared)
+    if (total_runs == 0) { tm.settle(); return XC_OK; }                       // both maps hold no ring: no rows (pair_count is cleared)
     XC_HIP(ctx, hipMemcpyAsync(d_soff, soff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     // groups of consecutive ranges whose tables fit the cap (one range always does), no more than rmax ranges; ranges without runs in
     // front of a group cost nothing
@@ -388,13 +370,13 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         smax = std::max(smax, soff[(size_t)r1] - soff[(size_t)r]);
         r = r1;
     }
-    if (smax > ((1ull << 62) / ((unsigned long long)W * 8ull))) return settle(), fail(ctx, XC_ENOMEM, std::string(who) + ": the table of one group is too large");
+    if (smax > ((1ull << 62) / ((unsigned long long)W * 8ull))) return tm.settle(), fail(ctx, XC_ENOMEM, std::string(who) + ": the table of one group is too large");
     // the tables of one group, then the staged rows (a, b: 4 bytes; n, sum_w, sum_wf: 8 bytes) of min(capacity, all runs)
     const int64_t cap = (int64_t)std::min<uint64_t>((uint64_t)capacity, total_runs);
     const size_t b_tab = al((size_t)smax * (size_t)W * 8), b4 = al((size_t)cap * 4), b8 = al((size_t)cap * 8);
     {
         const int rc = grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, b_tab + 2 * b4 + 3 * b8);
-        if (rc != XC_OK) { settle(); return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the pair tables"); }
+        if (rc != XC_OK) { tm.settle(); return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the pair tables"); }
     }
     unsigned long long* tab = (unsigned long long*)ctx->cpiece_acc;
     int* sa = (int*)((char*)tab + b_tab);
@@ -403,12 +385,9 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     double* sw = (double*)((char*)sn + b8);
     double* swf = (double*)((char*)sw + b8);
 
-    const dim3 bgrid((unsigned)std::min<int64_t>((npl + CI_TPB - 1) / CI_TPB, 1024), (unsigned)nslab);
-    if (!f) hipLaunchKernelGGL((k_ci_bound<void>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const void*)nullptr, mx);
-    else if (f_dtype == XC_F32) hipLaunchKernelGGL((k_ci_bound<float>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const float*)f, mx);
-    else hipLaunchKernelGGL((k_ci_bound<double>), bgrid, dim3(CI_TPB), 0, ctx->stream, npl, w, w_per_slab, (const double*)f, mx);
+    ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, mx);
     XC_HIP(ctx, hipGetLastError());
-    mark(1);
+    tm.mark(1);
 
     std::vector<uint64_t> hp((size_t)nrange, 0);
     std::vector<long long> poff((size_t)nrange + 1, 0);
@@ -428,7 +407,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         if (!f) XC_PO_SCAN(void); else if (f_dtype == XC_F32) XC_PO_SCAN(float); else XC_PO_SCAN(double);
 #undef XC_PO_SCAN
         XC_HIP(ctx, hipGetLastError());
-        mark(1);
+        tm.mark(1);
         hipLaunchKernelGGL(k_po_count, sgrid, blk, 0, ctx->stream, gr.r0, gr.r1, d_soff, W, tab, (unsigned long long*)pair_count);
         XC_HIP(ctx, hipGetLastError());
         XC_HIP(ctx, hipMemcpyAsync(hp.data() + gr.r0, pair_count + gr.r0, (size_t)ng * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -441,7 +420,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
                                sw, swf, d_err);
             XC_HIP(ctx, hipGetLastError());
         }
-        mark(2);
+        tm.mark(2);
     }
     for (; done < nrange; ++done) poff[(size_t)done + 1] = poff[(size_t)done] + (long long)hp[(size_t)done];
     ctx->cpoverlap_groups = (int)groups.size();
@@ -449,8 +428,8 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr) { settle(); return fail(ctx, XC_EHIP, std::string(who) + (herr & PO_ERR_FULL ? ": a pair found no slot in its range's table" : ": a pair found no row in its range")); }
-    if (np > capacity) { settle(); return 1; }
+    if (herr) { tm.settle(); return fail(ctx, XC_EHIP, std::string(who) + (herr & PO_ERR_FULL ? ": a pair found no slot in its range's table" : ": a pair found no row in its range")); }
+    if (np > capacity) { tm.settle(); return 1; }
     if (np > 0) {
         XC_HIP(ctx, hipMemcpyAsync(a, sa, (size_t)np * 4, hipMemcpyDeviceToDevice, ctx->stream));
         XC_HIP(ctx, hipMemcpyAsync(b, sb, (size_t)np * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -458,7 +437,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         XC_HIP(ctx, hipMemcpyAsync(sum_w, sw, (size_t)np * 8, hipMemcpyDeviceToDevice, ctx->stream));
         if (hasf) XC_HIP(ctx, hipMemcpyAsync(sum_wf, swf, (size_t)np * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    mark(2);
+    tm.mark(2);
     return bail(XC_OK);
 }
 

@@ -102,10 +102,10 @@ struct xc_ctx {
     float  cjoin_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cjoin_rounds = 0, cjoin_groups = 0;   // K14 (xc_cjoin.hip, on K13's workspace): table, label rounds, rank rounds, placement, emit
     float  coverturn_ms[4] = {0.f, 0.f, 0.f, 0.f};  int coverturn_rounds = 0, coverturn_groups = 0;   // K16 (xc_coverturn.hip, on K13's workspace): table, rounds, pieces / select, count
     float  cinterior_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cinterior_rounds = 0, cinterior_groups = 0;   // K17 (xc_cinside.hip, on K13's workspace): table, rounds, select, mark + scan
-    float  cpinside_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpinside_rounds = 0, cpinside_groups = 0;   // K18 (xc_cpinside.hip, on K13's workspaces): table, rounds, roots / slots / signs, walks
-    float  cptree_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cptree_rounds = 0, cptree_groups = 0;   // K19 (xc_cptree.hip, on K13's workspaces): K18's four, then the tree stages
-    float  cplabel_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cplabel_rounds = 0, cplabel_groups = 0;   // K20 (xc_cplabel.hip, on K13's workspaces): K19's five, then the label scan
-    float  cpprops_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cpprops_rounds = 0, cpprops_groups = 0;   // K21 (xc_cpprops.hip, on K13's workspaces): K19's five, then the props scan, then the fold and the finish
+    float  cpinside_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpinside_rounds = 0, cpinside_groups = 0;   // K18 (xc_cprecords.hip, on K13's workspaces): table, rounds, roots / slots / signs, walks
+    float  cptree_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cptree_rounds = 0, cptree_groups = 0;   // K19 (xc_cprecords.hip, on K13's workspaces): K18's four, then the tree stages
+    float  cplabel_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cplabel_rounds = 0, cplabel_groups = 0;   // K20 (xc_cprecords.hip, on K13's workspaces): K19's five, then the label scan
+    float  cpprops_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cpprops_rounds = 0, cpprops_groups = 0;   // K21 (xc_cprecords.hip, on K13's workspaces): K19's five, then the props scan, then the fold and the finish
     float  cpoverlap_ms[3] = {0.f, 0.f, 0.f};  int cpoverlap_groups = 0;   // K22 (xc_cpoverlap.hip, on K13's workspaces): the run count, the accumulate pass, the finish
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
@@ -362,31 +362,7 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
 int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
                             int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
                             const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask);
-// K18: per piece of K12's records (device pointers) the nodes it encloses and the weighted sums over them; waits for the stream once per group
-int launch_contour_piece_interiors(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
-                                   const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
-                                   int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
-                                   int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf);
-// K19: K18's records and, per piece, its parent ring, depth, children and what it bounds net of them; waits for the stream as K18 does
-int launch_contour_piece_tree(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
-                              const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
-                              int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
-                              int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
-                              int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf);
-// K20: K19's records and the dense map node -> innermost ring of every range; waits for the stream as K18 does
-int launch_contour_piece_labels(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
-                                const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
-                                int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
-                                int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
-                                int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
-                                int32_t* label);
-int launch_contour_piece_props(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
-                               const double* pts, int64_t ny, int64_t nx, int periodic, int flip, int ncont, const double* w,
-                               int w_per_slab, const void* f, int f_dtype, int64_t capacity, uint64_t* piece_count, int64_t* first_edge,
-                               int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf,
-                               int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf,
-                               int nf, const void* const* g, const int* g_dtype, const int* g_per_slab, const void* x, int x_dtype,
-                               double* net_g, double* sum_g, double* x_min, double* x_max, int64_t* at_min, int64_t* at_max);
+// K18-K21 (xc_contour_piece_{interiors,tree,labels,props}_dev) have one launcher of their own file: xc_cprecords.hip
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
 
