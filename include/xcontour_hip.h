@@ -852,6 +852,50 @@ int xc_label_overlap_dev(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
                          int32_t* a, int32_t* b, int64_t* n, double* sum_w, double* sum_wf);
 int xc_last_cpoverlap_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K23 ring tracks: rings followed over many fields
+ * K22 pairs the rings of two fields.  Following every ring of a stack of fields from birth to death, with splits and mergers, is a graph
+ * problem: the rings of all steps are vertices, the accepted overlaps between the rings of consecutive steps are edges, and a TRACK is a
+ * connected component.  This call takes that graph as arrays and labels it on the device.  It is generic: it knows nothing of planes, and
+ * any ring / link arrays are taken.  Build-defined.
+ * Input (all pointers device pointers):
+ *   nring >= 1, nlink >= 0
+ *   ring_step int32 [nring]               the step of every ring (only its min and max per track are taken)
+ *   ring_size int64 [nring]               the size the threshold compares with; may be NULL iff min_overlap == 0
+ *   link_a, link_b int64 [nlink]          ring indices, a the earlier ring; any negative index means "no ring"
+ *   link_n int64 [nlink]                  the shared nodes
+ *   min_overlap                           in [0, 1]
+ *   ACCEPT     a link is accepted when a >= 0 && b >= 0 && n >= 1 and either min_overlap == 0 or
+ *              (double)n >= min_overlap * (double)min(size[a], size[b]), the product rounded once in float64.
+ *   REFUSALS   an index >= nring, a NaN min_overlap or one outside [0, 1], ring_size NULL with min_overlap != 0, nring < 1, nlink < 0,
+ *              more than 2^38 rings or links, a NULL output with capacity > 0: XC_EBADARG.  The indices are checked on the device through
+ *              an error word, as K22 checks its rows.  On an error nothing is written.
+ * Output per ring:
+ *   root int64      the smallest ring index of the ring's component over the accepted links
+ *   track int64     the rank of that root among all roots, ascending: tracks are numbered in the order of their first rings
+ *   nprev, nnext int32   the accepted links in which the ring is b, resp. a (duplicate links count as often as they are given)
+ * Output per link:  link_ok uint8, 1 where the link was accepted.
+ * Output per track, by K19's / K22's capacity protocol: ntrack uint64 [1] is always written; with ntrack > capacity nothing else is written
+ * -- no per-ring and no per-link array either -- and 1 is returned; with capacity == 0 every other output pointer may be NULL.  Row t:
+ *   first_ring int64          the root itself
+ *   first_step, last_step int32   min and max of ring_step over the track
+ *   nrings int64              its rings
+ *   nsplit, nmerge int64      its rings with nnext >= 2, resp. nprev >= 2
+ * All reductions are integer atomics (add, min, max), and the fixed point root = the component's minimum is unique: link order and launch
+ * geometry do not show in any word.  xc_cptrack.hip states the mapping: a parent array with parent[g] <= g, rounds of hook (atomicMin of
+ * the larger root under the smaller, per accepted link) and compress until the host reads an unchanged round; no thread waits for another;
+ * more than nring + 1 rounds is XC_EHIP.  The dense rank is a per-block count, the host's scan and a per-block ranking.  The call waits for
+ * the stream as K22 does.  xc_last_cptrack_profile returns the rounds of the last call (the last, unchanged one included; 0 without links)
+ * and, with xc_set_kernel_timing on, its device times in ms: ms[0] accept and degrees, ms[1] the rounds, ms[2] ranks, rows and copies. */
+int xc_ring_tracks_dev(xc_ctx* ctx, int64_t nring, int64_t nlink,
+                       const int32_t* ring_step, const int64_t* ring_size,            /* [nring] */
+                       const int64_t* link_a, const int64_t* link_b, const int64_t* link_n,   /* [nlink] */
+                       double min_overlap,
+                       int64_t* root, int64_t* track, int32_t* nprev, int32_t* nnext,   /* [nring] */
+                       uint8_t* link_ok,                                               /* [nlink] */
+                       int64_t capacity, uint64_t* ntrack,
+                       int64_t* first_ring, int32_t* first_step, int32_t* last_step, int64_t* nrings, int64_t* nsplit, int64_t* nmerge);
+int xc_last_cptrack_profile(xc_ctx* ctx, double* ms, int* rounds);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -183,6 +183,9 @@ PROTOTYPES = {
     'xc_label_overlap_dev': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _i64, _vp, _vp, _vp, _vp,
                                        _vp, _vp]),
     'xc_last_cpoverlap_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_ring_tracks_dev': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp]),
+    'xc_last_cptrack_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     'xc_set_cpiece_workspace': (C.c_int, [_vp, _u64]),
     'xc_last_cpiece_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_sort_profile_dev': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64, _i64, C.c_int, _vp, C.c_int,
@@ -461,6 +464,16 @@ class DeviceBuffer(object):
             self.ptr = None
             if self in self.ctx._buffers:
                 self.ctx._buffers.remove(self)
+
+
+class _DeviceView(object):
+    """`nbytes` bytes of a DeviceBuffer from `offset_bytes` on, for a call that takes a buffer (`ptr`, `upload`); the owner frees"""
+
+    def __init__(self, buf, offset_bytes, nbytes):
+        assert 0 <= offset_bytes and offset_bytes + nbytes <= buf.nbytes
+        self.ctx, self.ptr, self.nbytes = buf.ctx, buf.ptr + int(offset_bytes), int(nbytes)
+
+    upload = DeviceBuffer.upload
 
 
 class Context(object):
@@ -1702,6 +1715,169 @@ class Context(object):
         per = ny * nx * (qa.dtype.itemsize + qb.dtype.itemsize + 2 * 4 * N + (8 if w_per_slab else 0)
                          + (f.dtype.itemsize if f is not None else 0))
         return self._batched(nslab, per, one)
+
+    # the rows of `ring_tracks`: one per track
+    TRACK_DTYPE = np.dtype([('first_ring', np.int64), ('first_step', np.int32), ('last_step', np.int32), ('nrings', np.int64),
+                            ('nsplit', np.int64), ('nmerge', np.int64)])
+    # what `contour_piece_tracks` adds per ring, per link and per track
+    RING_TRACK_DTYPE = np.dtype([('track', np.int64), ('nprev', np.int32), ('nnext', np.int32)])
+    TRACK_LINK_DTYPE = np.dtype([('step', np.int32)] + OVERLAP_DTYPE.descr[:4] + [('linked', np.bool_)])
+    PIECE_TRACK_DTYPE = np.dtype([('first_step', np.int32), ('first_row', np.int64), ('last_step', np.int32), ('nrings', np.int64),
+                                  ('nsplit', np.int64), ('nmerge', np.int64)])
+
+    def last_cptrack_profile(self):
+        """the last xc_ring_tracks_dev call: dict(accept_ms, rounds_ms, finish_ms -- device times under set_kernel_timing(True) --,
+        rounds: the hook / compress rounds, the last, unchanged one included)"""
+        ms = (C.c_double * 3)()
+        r = C.c_int(0)
+        self._check(self.lib.xc_last_cptrack_profile(self.handle, C.cast(ms, _vp), C.byref(r)))
+        return dict(accept_ms=ms[0], rounds_ms=ms[1], finish_ms=ms[2], rounds=r.value)
+
+    def ring_tracks(self, ring_step, ring_size, link_a, link_b, link_n, min_overlap=0.0):
+        """The connected components of a ring graph (K23, xc_ring_tracks_dev): ring_step int32 (nring,), ring_size int64 (nring,) or
+        None (min_overlap 0 only), link_a / link_b / link_n int64 (nlink,), any negative index "no ring".  A link is accepted when
+        a >= 0, b >= 0, n >= 1 and n >= min_overlap * min(size[a], size[b]).  Everything is uploaded once; a count-only call, then
+        a sized one; only the outputs come back.  Returns dict(root int64, track int64, nprev int32, nnext int32 (nring,); link_ok
+        bool (nlink,); tracks (TRACK_DTYPE) in the order of their first rings)."""
+        ring_step = _contig(ring_step, np.int32)
+        la, lb, ln = (_contig(a, np.int64) for a in (link_a, link_b, link_n))
+        nring, nlink = ring_step.size, la.size
+        if ring_step.ndim != 1 or la.ndim != 1 or lb.shape != la.shape or ln.shape != la.shape:
+            raise XContourHipError(XC_EBADARG, 'xc_ring_tracks: ring_step (nring,), link_a, link_b and link_n (nlink,)')
+        if ring_size is not None:
+            ring_size = _contig(ring_size, np.int64)
+            if ring_size.shape != ring_step.shape:
+                raise XContourHipError(XC_EBADARG, 'xc_ring_tracks: ring_size must be (nring,)')
+        if nring == 0:
+            if nlink:
+                raise XContourHipError(XC_EBADARG, 'xc_ring_tracks: links without rings')
+            return dict(root=np.empty(0, np.int64), track=np.empty(0, np.int64), nprev=np.empty(0, np.int32), nnext=np.empty(0, np.int32),
+                        link_ok=np.empty(0, np.bool_), tracks=np.empty(0, dtype=self.TRACK_DTYPE))
+        ins = [ring_step] + ([ring_size] if ring_size is not None else []) + ([la, lb, ln] if nlink else [])
+        with self._temporaries(ins, [8]) as bufs:
+            dsize = bufs[1].ptr if ring_size is not None else None
+            dl = [b.ptr for b in bufs[-4:-1]] if nlink else [None] * 3
+            head = (self.handle, nring, nlink, bufs[0].ptr, dsize, *dl, float(min_overlap))
+            dnt = bufs[-1]
+            rc = self.lib.xc_ring_tracks_dev(*head, *[None] * 5, 0, dnt.ptr, *[None] * 6)
+            if rc not in (XC_OK, 1):                             # (1: there are tracks, and no room was given)
+                self._check(rc)
+            nt = int(dnt.download((1,), np.uint64)[0])
+            # per ring root, track (8 bytes), nprev, nnext (4 bytes); link_ok; per track four 8-byte and two 4-byte columns
+            with self._temporaries([], [nring * 24, max(nlink, 1), nt * 40]) as (dring, dok, drow):
+                rat = [dring.ptr + j * nring for j in (0, 8, 16, 20)]
+                tat = [drow.ptr + j * nt for j in (0, 32, 36, 8, 16, 24)]          # in the entry's order: first_ring, the steps, the counts
+                self._check(self.lib.xc_ring_tracks_dev(*head, *rat, dok.ptr, nt, dnt.ptr, *tat))
+                out = {k: dring.download((nring,), t, offset_bytes=p - dring.ptr)
+                       for k, t, p in zip(('root', 'track', 'nprev', 'nnext'), (np.int64, np.int64, np.int32, np.int32), rat)}
+                out['link_ok'] = dok.download((nlink,), np.uint8).astype(np.bool_)
+                rows = np.empty(nt, dtype=self.TRACK_DTYPE)
+                for k, p in zip(rows.dtype.names, tat):
+                    rows[k] = drow.download((nt,), rows.dtype[k], offset_bytes=p - drow.ptr)
+                out['tracks'] = rows
+        return out
+
+    def contour_piece_tracks(self, q, contours, w=None, f=None, periodic=False, flip=False, min_overlap=0.0):
+        """The rings of a stack of fields FOLLOWED through the stack (K20 on every step ONCE, K22 between consecutive steps, K23,
+        xc_ring_tracks_dev, over all of them).  q (nstep, ny, nx): the steps of one series, in order; contours, w, f, periodic and
+        flip as for `contour_piece_tree`; min_overlap in [0, 1]: a link counts when its shared nodes are at least that fraction of
+        the smaller ring's n_net (0: any shared node).
+        The steps are cut into batches from `max_batch_bytes`.  A batch of n steps writes its label maps into slots 1 .. n of one
+        device buffer of (n + 1) maps; slot 0 is the last map of the batch before, copied device to device, so ONE K22 call per
+        batch pairs slot j with slot j + 1 -- range (t, k) pairs step t - 1 with step t at level k -- and no map reaches the host.
+        K22 runs without f and with w as given (a per-step w: the earlier step's).
+        Returns (piece_count, table, ring, link_count, links, track_count, tracks): the first two are `contour_piece_tree`'s, bit
+        for bit; `ring` (RING_TRACK_DTYPE) lines up with `table`: track a row of the level's rows of `tracks`, nprev / nnext the
+        accepted links to the step before / after; link_count uint64 (nstep - 1, N) and `links` (TRACK_LINK_DTYPE) packed by
+        (step, level), each range sorted by (a, b): K22's rows of step `step` against step + 1 (a, b rows of the two ranges' sorted
+        tables, -1 "in no ring") with `linked`; track_count uint64 (N,) and `tracks` (PIECE_TRACK_DTYPE) packed by level, in the
+        order of their first rings' (step, row).  An open piece has no links and is a track of one."""
+        who = 'xc_contour_piece_tracks'
+        q, (nstep, ny, nx) = _stack3(q)
+        contours, _, N = _levels_of(contours, nstep)
+        mo = float(min_overlap)
+        if not 0.0 <= mo <= 1.0:
+            raise XContourHipError(XC_EBADARG, '%s: min_overlap must lie in [0, 1]' % who)
+        w, f = self._overlap_weights(who, w, f, nstep, ny, nx)
+        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
+        per = ny * nx * (q.dtype.itemsize + 4 * N + (8 if w_per_slab else 0) + (f.dtype.itemsize if f is not None else 0))
+        bt = self._batches(nstep, per)
+        slot = N * ny * nx * 4
+        maps = self.alloc((bt[0][1] - bt[0][0] + 1) * slot)
+        pcs, tabs, lcs, lks = [], [], [], []
+        last = None                                              # of the step before the batch: (its piece counts (1, N), its rows' permutation)
+        try:
+            for s0, s1 in bt:
+                n = s1 - s0
+                if last is not None:                             # the map of the step before: slot n of the batch before -> slot 0
+                    self.comm_wait_compute()
+                    self.comm_memcpy_d2d(maps.ptr, maps.ptr + (bt[0][1] - bt[0][0]) * slot, slot)
+                    self.compute_wait_comm()
+                pc, tab, perm = self._piece_records(who, True, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), _part(w, 3, s0, s1),
+                                                    None if f is None else f[s0:s1], periodic, flip, labels=True,
+                                                    keep=_DeviceView(maps, slot, n * slot))
+                pcs.append(pc)
+                tabs.append(tab)
+                cnt = pc.astype(np.int64).reshape(n, N)
+                first = 1 if last is None else 0                 # the slot of the earlier field of the batch's first pair
+                npair = n - first
+                if npair:
+                    wp = w if not w_per_slab else w[s0 + first - 1:s1 - 1]
+                    with self._temporaries([] if wp is None else [wp], []) as bufs:
+                        lc, rows = self._overlap_rows(npair * N, ny, nx, N, maps.ptr + first * slot, maps.ptr + (first + 1) * slot,
+                                                      bufs[0].ptr if bufs else None, w_per_slab, None, 0)
+                    # the device labels are positions in each step's packed order: -> rows of the first_edge-sorted tables
+                    scnt = cnt if last is None else np.concatenate([last[0], cnt])
+                    sperm = perm if last is None else np.concatenate([last[1], perm])
+                    start = (np.cumsum(scnt.ravel()) - scnt.ravel()).reshape(scnt.shape)
+                    rng = np.repeat(np.arange(lc.size), lc.astype(np.int64))
+                    for key, j in (('a', 0), ('b', 1)):
+                        has = rows[key] >= 0
+                        at = start[rng // N + j, rng % N]
+                        rows[key][has] = sperm[at[has] + rows[key][has]]
+                    rows = self._sorted_overlap(lc, rows)
+                    lk = np.empty(rows.size, dtype=self.TRACK_LINK_DTYPE)
+                    lk['step'] = s0 + first - 1 + np.repeat(np.arange(lc.size), lc.astype(np.int64)) // N
+                    for k in ('a', 'b', 'n', 'sum_w'):
+                        lk[k] = rows[k]
+                    lcs.append(lc.reshape(npair, N))
+                    lks.append(lk)
+                tail = int(cnt[:-1].sum())
+                last = (cnt[-1:], perm[tail:])
+        finally:
+            maps.free()
+        pc, tab = np.concatenate(pcs), np.concatenate(tabs)
+        lc = np.concatenate(lcs) if lcs else np.zeros((0, N), dtype=np.uint64)
+        links = np.concatenate(lks) if lks else np.empty(0, dtype=self.TRACK_LINK_DTYPE)
+        # ring indices, level-major: all steps of level 0, then level 1, ...: base[t, k] is the first ring of range (t, k)
+        cnt = pc.astype(np.int64).reshape(nstep, N)
+        base = (np.cumsum(cnt.T.ravel()) - cnt.T.ravel()).reshape(N, nstep).T
+        lvl0 = np.concatenate([base[0], [cnt.sum()]])            # where every level starts
+        npiece = tab.size
+        where = np.repeat(base.ravel(), cnt.ravel()) + np.arange(npiece) - np.repeat(np.cumsum(cnt.ravel()) - cnt.ravel(), cnt.ravel())
+        ring_step, ring_size = np.empty(npiece, dtype=np.int32), np.empty(npiece, dtype=np.int64)
+        ring_step[where] = np.repeat(np.repeat(np.arange(nstep), N), cnt.ravel())
+        ring_size[where] = tab['n_net']
+        lrange = np.repeat(np.arange(lc.size), lc.ravel().astype(np.int64))
+        lstep, llev = lrange // N, lrange % N
+        la = np.where(links['a'] >= 0, base[lstep, llev] + links['a'], -1) if links.size else np.empty(0, dtype=np.int64)
+        lb = np.where(links['b'] >= 0, base[np.minimum(lstep + 1, nstep - 1), llev] + links['b'], -1) if links.size else np.empty(0, dtype=np.int64)
+        got = self.ring_tracks(ring_step, ring_size, la, lb, links['n'], mo)
+        links['linked'] = got['link_ok']
+        # every level's rings are contiguous, so its tracks are a run of dense ids: the level's base is taken off
+        trows = got['tracks']
+        tlev = np.searchsorted(lvl0, trows['first_ring'], side='right') - 1
+        tcount = np.bincount(tlev, minlength=N)[:N].astype(np.uint64)
+        tbase = np.cumsum(tcount.astype(np.int64)) - tcount.astype(np.int64)
+        ring = np.empty(npiece, dtype=self.RING_TRACK_DTYPE)
+        rlev = np.repeat(np.tile(np.arange(N), nstep), cnt.ravel())
+        ring['track'] = got['track'][where] - tbase[rlev]
+        ring['nprev'], ring['nnext'] = got['nprev'][where], got['nnext'][where]
+        tracks = np.empty(trows.size, dtype=self.PIECE_TRACK_DTYPE)
+        for k in ('first_step', 'last_step', 'nrings', 'nsplit', 'nmerge'):
+            tracks[k] = trows[k]
+        tracks['first_row'] = trows['first_ring'] - base[trows['first_step'], tlev]
+        return pc, tab, ring, lc, links, tcount, tracks
 
     def local_contour_lengths(self, q, ycoord, xcoord, window, stride, min_periods, levels=None, radius=0.0, period=None):
         """Sliding-window contour lengths (xc_local_contour_lengths).  q (nslab, ny, nx) f32/f64 (or a lazy stack); ycoord (ny,) /

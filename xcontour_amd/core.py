@@ -1220,6 +1220,43 @@ class Contour2D(object):
         return self._piece_tables('cal_contour_piece_overlap', True, contours, tracer, integrand, periodic, side,
                                   overlap=(other, other_contours))
 
+    def cal_contour_piece_tracks(self, contours, along, tracer=None, integrand=None, periodic=False, side='upper', min_overlap=0.0):
+        """
+        The rings of every contour FOLLOWED along a leading dim of the tracer -- every cut-off low, shed filament and vortex
+        fragment from birth to death, with splits and mergers --, computed on the GPU (K20, xc_contour_piece_labels_dev, ONCE
+        per step; K22, xc_label_overlap_dev, between consecutive steps; K23, xc_ring_tracks_dev, over the whole stack).
+        Build-defined: the reference has no counterpart.
+
+        This replaces a loop of cal_contour_piece_overlap(tracer[t], tracer[t + 1]) calls and a union-find over their rows on
+        the host: there every step is traced and labelled twice, here once; the label maps stay on the device in a sliding
+        window; the connected components of the ring graph are found on the device.
+
+        `contours`, `tracer`, `integrand`, `periodic`, `side` and the order of the levels are those of cal_contour_piece_tree.
+        `along` names a LEADING dim of the tracer, for instance time; anything else raises.  The other leading dims are
+        independent series.  Level k of one step is followed into level k of the next, so the levels of a series must ascend
+        in the same order at every step.  `min_overlap` in [0, 1]: a link between two rings counts when their shared nodes are at
+        least that fraction of the smaller ring's nodes_net (exactly: float64(nodes) >= min_overlap * float64(min(nodes_net[a],
+        nodes_net[b])), the product rounded once); 0: any shared node.
+
+        Returns (tree, links, tracks).
+        tree     what cal_contour_piece_tree returns for the same arguments, bit for bit, nested the same way over all leading
+                 dims, with three more fields per ring: `track` (int64: a row of that series' tracks[k]; an open piece bounds
+                 nothing, has no links and is a track of one), `nprev`, `nnext` (int32: the accepted links to rings of the step
+                 before / after).
+        links    links[series][k] (links[k] when `along` is the only leading dim; the series are the other leading dims
+                 flattened in the tracer's order): a structured array sorted by (step, a, b): `step` (int32) the index along
+                 `along` of the EARLIER field; `a`, `b` (int32) rows of tree[step][k] and tree[step + 1][k], -1 for "in no
+                 ring" -- exactly cal_contour_piece_overlap's rows of the two steps, all kept; `nodes`, `area` as there;
+                 `linked` (bool) whether the link was accepted.  These are that method's NET overlaps, of the nodes labelled
+                 with the ring (the innermost ring round them), not of all a ring encloses.
+        tracks   tracks[series][k]: one row per track, in the order of its first ring's (step, row): `first_step`, `first_row`
+                 (the first ring is tree[first_step][k][first_row]), `last_step`, `nrings`, `nsplit` (its rings with nnext >= 2),
+                 `nmerge` (its rings with nprev >= 2).  A track is a connected component of the accepted links: after a merger the
+                 merged rings share one track.
+        """
+        return self._piece_tables('cal_contour_piece_tracks', True, contours, tracer, integrand, periodic, side,
+                                  tracks=(along, min_overlap))
+
     @staticmethod
     def _moment_planes(yg, xg, latlon, period):
         """the planes whose dA-weighted sums give a ring's centroid (cal_contour_piece_props states them): float64 (ny, nx) each"""
@@ -1287,10 +1324,10 @@ class Contour2D(object):
             v[par], at[par], key[par], has[par] = v[best], at[best], key[best], True
         return v, at
 
-    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False, props=None, overlap=None):
+    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False, props=None, overlap=None, tracks=None):
         """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, with `labels` too cal_contour_piece_labels, with
-        `props` cal_contour_piece_props, and with `overlap` = (other, other_contours) cal_contour_piece_overlap: one validation,
-        one staging, one entry each"""
+        `props` cal_contour_piece_props, with `overlap` = (other, other_contours) cal_contour_piece_overlap, and with `tracks` =
+        (along, min_overlap) cal_contour_piece_tracks: one validation, one staging, one entry each"""
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         if side not in ('upper', 'lower'):
@@ -1358,6 +1395,19 @@ class Contour2D(object):
                                 'in the order given, and both are traced in ascending order)' % who)
             pc, tab, pc_b, tab_b, pairs, rows = self.ctx.contour_piece_overlap(q, qb, bs, contours_b=bs_b, w=dA, f=g, periodic=ring,
                                                                                flip=flip)
+        elif tracks is not None:
+            along, min_overlap = tracks
+            if along not in lead:
+                raise Exception('%s: along should name a leading dim of the tracer (one of %r), not %r' % (who, tuple(lead), along))
+            ax = list(lead).index(along)
+            # the slabs of every series, in step order: the other leading dims, flattened in the tracer's order, are the series
+            series = np.moveaxis(np.arange(nslab).reshape(tuple(lshape)), ax, -1).reshape(-1, lshape[ax])
+            if (order[series] != order[series[:, :1]]).any():
+                raise Exception('%s: the levels of a series should ascend in the same order at every step (level k of one step is '
+                                'followed into level k of the next, and every step is traced in ascending order)' % who)
+            qs = q[0:nslab] if getattr(q, '_xc_lazy_stack', False) else q
+            runs = [self.ctx.contour_piece_tracks(qs[sl], bs[sl], w=dA[sl] if dA.ndim == 3 else dA, f=None if g is None else g[sl],
+                                                  periodic=ring, flip=flip, min_overlap=min_overlap) for sl in series]
         else:
             call = self.ctx.contour_piece_labels if labels else self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
             pc, tab, *lab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
@@ -1374,6 +1424,30 @@ class Contour2D(object):
         def per_range(rec, counts):
             poff = np.concatenate([[0], np.cumsum(counts.ravel().astype(np.int64))])
             return [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])]
+        if tracks is not None:
+            N = order.shape[1]
+            trees, links, rows = [None] * (nslab * N), [], []
+            for sl, (pc, tab, ring, lcount, lk, tcount, tr) in zip(series, runs):
+                rec = named(tab)
+                full = np.empty(rec.size, dtype=rec.dtype.descr + ring.dtype.descr)
+                for src in (rec, ring):
+                    for f in src.dtype.names:
+                        full[f] = src[f]
+                for t, s in enumerate(sl.tolist()):
+                    trees[s * N:(s + 1) * N] = per_range(full, pc)[t * N:(t + 1) * N]
+                ov = np.empty(lk.size, dtype=[('step', np.int32), ('a', np.int32), ('b', np.int32), ('nodes', np.int64), ('area', np.float64),
+                                              ('linked', np.bool_)])
+                for k, f in (('step', 'step'), ('a', 'a'), ('b', 'b'), ('nodes', 'n'), ('area', 'sum_w'), ('linked', 'linked')):
+                    ov[k] = lk[f]
+                by_range = per_range(ov, lcount)                 # packed by (step, level): a level's ranges, joined, are sorted by step
+                per_level = [np.concatenate(by_range[j::N]) if by_range else ov[:0].copy() for j in range(N)]
+                where = order[sl[0]].tolist()                    # j: the sorted level; where[j]: where the caller put it
+                for vals, out in ((per_level, links), (per_range(tr, tcount), rows)):
+                    out.append([None] * N)
+                    for j, k in enumerate(where):
+                        out[-1][k] = vals[j]
+            tree = self._in_caller_order(order, lead, trees)[0]
+            return (tree, links[0], rows[0]) if len(lead) == 1 else (tree, links, rows)
         rec = named(tab)
         poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
         if props is not None:

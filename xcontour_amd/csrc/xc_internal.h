@@ -107,6 +107,7 @@ struct xc_ctx {
     float  cplabel_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cplabel_rounds = 0, cplabel_groups = 0;   // K20 (xc_cprecords.hip, on K13's workspaces): K19's five, then the label scan
     float  cpprops_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cpprops_rounds = 0, cpprops_groups = 0;   // K21 (xc_cprecords.hip, on K13's workspaces): K19's five, then the props scan, then the fold and the finish
     float  cpoverlap_ms[3] = {0.f, 0.f, 0.f};  int cpoverlap_groups = 0;   // K22 (xc_cpoverlap.hip, on K13's workspaces): the run count, the accumulate pass, the finish
+    float  cptrack_ms[3] = {0.f, 0.f, 0.f};  int cptrack_rounds = 0;   // K23 (xc_cptrack.hip, on K13's workspaces): accept and degrees, the rounds, ranks and rows
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
