@@ -2,76 +2,16 @@
 """How `_native.Context` cuts a stack into batches, pinned without a GPU: a Context over a stand-in library that records
 (entry point, nslab) per call.  The batch boundaries, the order of the library calls, the container shape of every joined result
 and the reads of a lazy stack (every slab once, in order) are what a change to the batching must leave alone."""
-import ctypes as C
-
 import numpy as np
 import pytest
+
+from standin_lib import RES, _K12, _Lib
 
 from xcontour_amd import _native as nat
 from xcontour_amd import labeled as lb
 
 S, NY, NX, N = 5, 6, 8, 4
 SLAB = NY * NX * 8                      # bytes of one float64 slab
-
-# position of `nslab` in the argument list of the entry points that take it by value (include/xcontour_hip.h); for
-# xc_contour_pieces_dev, which sees no slabs, the position of `nrange`
-_NSLAB_ARG = {'xc_minmax': 3, 'xc_levels': 3, 'xc_contours': 3, 'xc_grad2': 3, 'xc_crossing': 3, 'xc_crossing_dev': 3,
-              'xc_contour_lengths': 3, 'xc_contour_lengths_dev': 3, 'xc_lwa': 10, 'xc_sort_profile_batch': 8,
-              'xc_contour_lengths_periodic': 3, 'xc_contour_lengths_periodic_dev': 3,
-              'xc_local_contour_lengths': 3, 'xc_local_contour_lengths_dev': 3,
-              'xc_local_contour_lengths_periodic': 3, 'xc_local_contour_lengths_periodic_dev': 3,
-              'xc_contour_segments_dev': 3, 'xc_contour_segments_periodic_dev': 3, 'xc_contour_pieces_dev': 1}
-_K12 = ('xc_contour_segments_dev', 'xc_contour_segments_periodic_dev')
-RES = 1 << 44                           # where the stand-in's device mirror of a resident array starts
-
-
-class _Lib(object):
-    """every xc_* entry point returns XC_OK and leaves its outputs alone; compute entry points are recorded: (name, nslab) in
-    `calls`, (name, every positional argument) in `args`; the bytes of every xc_malloc in `mallocs`.  `d2h_u64`: None -- a
-    download reads zeros --, or a callable (this library) -> the value every uint64 of the next download holds (a count download
-    of twos takes K12 / K13 into their second pass; K12's count-only call then returns 1, as the library's does).
-    `resident_base`: None -- xc_resident_lookup finds nothing --, or the host address of the one registered array, whose mirror
-    starts at RES."""
-
-    def __init__(self):
-        self.calls, self.args, self.mallocs = [], [], []
-        self.d2h_u64 = self.resident_base = None
-        self._next = self._base = 1 << 40                            # the next allocation; the first one _take has not seen
-
-    def __getattr__(self, name):
-        if name == 'xc_malloc':
-            return self._malloc
-        if name == 'xc_memcpy_d2h':
-            return self._d2h
-        if name == 'xc_resident_lookup':
-            return self._lookup
-        if name == 'xc_hist':
-            return lambda h, dref: (self.calls.append((name, int(dref._obj.nslab))), 0)[1]
-        if name in _NSLAB_ARG:
-            return lambda *a: self._record(name, a)
-        return lambda *a: 0
-
-    def _record(self, name, a):
-        self.calls.append((name, int(a[_NSLAB_ARG[name]])))
-        self.args.append((name, tuple(a)))
-        return 1 if name in _K12 and a[9] == 0 and self.d2h_u64 is not None and self.d2h_u64(self) else 0
-
-    def _malloc(self, h, n, pref):
-        self.mallocs.append(int(n))
-        pref._obj.value = self._next
-        self._next += (int(n) + 4095) & ~4095
-        return 0
-
-    def _d2h(self, h, dst, src, n):
-        C.memset(dst, 0, n)
-        v = self.d2h_u64(self) if self.d2h_u64 is not None else 0
-        if v:
-            (C.c_uint64 * (n // 8)).from_address(dst)[:] = [v] * (n // 8)
-        return 0
-
-    def _lookup(self, h, p, n, pref):
-        pref._obj.value = None if self.resident_base is None else RES + (p - self.resident_base)
-        return 0
 
 
 @pytest.fixture

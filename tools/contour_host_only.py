@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""The Python around the library calls of the contour family (K10 - K13), alone: the four `Context` methods and the four `Contour2D`
-methods on a small stack (4 x 24 x 48 float32, 8 levels) against a stand-in library whose entry points return at once.  No GPU
-needed; a sibling of tools/facade_host_only.py, which does the same for the Keff sequence.  Every count download reads 2, so K12's
-and K13's second pass is staged too -- but zeros under find_contours, whose host join wants real records (the join is the library's
-own xc_join_segments: build it first).  `--package DIR`: time the xcontour_amd package under DIR instead of this tree's (an A/B
-against another revision's Python; point XC_LIB_PATH at a built library if DIR has none).  Prints us per call, the best of `--rounds R`
-(default 5) rounds of 400 calls.  On a shared host the figures drift by tens of percent from one process to the next whatever R:
-alternate the two sides and compare medians and minima (profiles/contour_host_ab.md)."""
+"""The Python around the library calls of the contour family (K10 - K20), alone: `Context` methods and `Contour2D` methods of
+K10 - K13 and of the record kernels K14, K16, K17, K19 and K20 on a small stack (4 x 24 x 48 float32, 8 levels) against a stand-in
+library whose entry points return at once.  No GPU needed; a sibling of tools/facade_host_only.py, which does the same for the Keff
+sequence.  Every count download reads 2, so K12's and K13's second pass is staged too -- but zeros under find_contours, whose host
+join wants real records (the join is the library's own xc_join_segments: build it first), and under the label rows, where a label
+of 2 in a range of two pieces would point past the last range ("fill 0" in the row's name: the batch without segments, every label
+-1 and no map fetched).  `--package DIR`: time the xcontour_amd package under DIR instead of this tree's (an A/B against another
+revision's Python; point XC_LIB_PATH at a built library if DIR has none).  Prints us per call, the best of `--rounds R` (default 5)
+rounds of 400 calls.  On a shared host the figures drift by tens of percent from one process to the next whatever R: alternate the
+two sides and compare medians and minima (profiles/contour_host_ab.md, profiles/ring_host_ab.md)."""
 import ctypes as C
 import os
 import sys
@@ -62,6 +64,7 @@ cm = xa.Contour2D(tr, np.ones(NY), dims={'X': 'lon', 'Y': 'lat'}, dimEq={'Y': 'l
 lv = np.linspace(-1.5, 1.5, N)
 y, x = np.deg2rad(lat.astype(np.float64)), np.deg2rad(lon.astype(np.float64))
 P = 2.0 * np.pi
+wgt = np.ones((NY, NX))
 
 
 def zeros(fn):
@@ -83,6 +86,13 @@ calls = [
     ('cal_local_contour_lengths', lambda: cm.cal_local_contour_lengths(5, stride=4, latlon=True, periodic=True)),
     ('find_contours', zeros(lambda: cm.find_contours(lv, periodic=True, return_closed=True))),
     ('cal_contour_pieces', lambda: cm.cal_contour_pieces(lv, latlon=True, periodic=True)),
+    ('ctx.contour_polylines', lambda: ctx.contour_polylines(q, lv, periodic=True)),
+    ('ctx.contour_overturning', lambda: ctx.contour_overturning(q, lv, periodic=True, select='main')),
+    ('ctx.contour_interior', lambda: ctx.contour_interior(q, lv, w=wgt, f=q, periodic=True, select='main')),
+    ('ctx.contour_piece_tree', lambda: ctx.contour_piece_tree(q, lv, w=wgt, f=q, periodic=True)),
+    ('ctx.contour_piece_labels, fill 0', zeros(lambda: ctx.contour_piece_labels(q, lv, w=wgt, f=q, periodic=True))),
+    ('cal_contour_piece_tree', lambda: cm.cal_contour_piece_tree(lv, integrand=tr, periodic=True)),
+    ('cal_contour_piece_labels, fill 0', zeros(lambda: cm.cal_contour_piece_labels(lv, integrand=tr, periodic=True))),
 ]
 tot = 0.0
 with np.errstate(all='ignore'):                # (the stand-in leaves host-form outputs as np.empty made them)
@@ -96,5 +106,5 @@ with np.errstate(all='ignore'):                # (the stand-in leaves host-form 
                 fn()
             best = min(best, (time.perf_counter() - t) / 400 * 1e6)
         tot += best
-        print('%-26s %7.1f us' % (name, best))
-print('%-26s %7.1f us' % ('sum', tot))
+        print('%-34s %7.1f us' % (name, best))
+print('%-34s %7.1f us' % ('sum', tot))

@@ -8,6 +8,7 @@ library (works on a GPU-less build box so that symbol / ABI checks can run);
 `Context()` is what needs the device.
 """
 import contextlib
+import copy
 import ctypes as C
 import os
 
@@ -396,9 +397,166 @@ def _check_finite(who, *coords):
         raise XContourHipError(XC_EBADARG, '%s: coordinates must be finite' % who)
 
 
+def _scan(counts):
+    """counts of any shape and integer type -> (the counts, their exclusive scan -- where every range starts in the packed
+    order): both flat int64"""
+    c = counts.ravel().astype(np.int64)
+    return c, np.cumsum(c) - c
+
+
+def _range_of(counts):
+    """the range every record lies in, for records packed range by range (`counts` of them in each)"""
+    return np.repeat(np.arange(counts.size), counts.ravel().astype(np.int64))
+
+
 def _range_order(counts, key):
     """the order that sorts records packed range by range (`counts` of them in each) by `key` inside every range"""
-    return np.lexsort((key, np.repeat(np.arange(counts.size), counts.ravel().astype(np.int64))))
+    return np.lexsort((key, _range_of(counts)))
+
+
+def _row_map(pc, first_edge):
+    """The pieces of one batch as the device packed them, `pc` of them in each range -> (order, rows): `order` sorts every range
+    by first_edge (the order of the tables); rows[p] is the row, counted from the start of its range, that packed position p
+    has in its range's sorted table.  Whatever the device gives as an index into its packed order -- a parent, a label, the
+    rings of an overlap pair -- becomes a row of the tables through `rows` (`_to_rows`)."""
+    c, start = _scan(pc)
+    order = _range_order(pc, first_edge)
+    where = np.empty(order.size, dtype=np.int64)
+    where[order] = np.arange(order.size)
+    return order, where - np.repeat(start, c)
+
+
+def _to_rows(idx, start, rows):
+    """in place: every index >= 0 of `idx` counts inside its range's packed order, which begins at `start` (a scalar, or an array
+    that broadcasts against `idx`) of the positions `rows` (`_row_map`) covers -> the row in the range's sorted table"""
+    has = idx >= 0
+    idx[has] = rows[(idx + start)[has]]
+
+
+def _named(src, dtype, names=None):
+    """the structured array `src` as one of `dtype`: every field of `src` goes to the field of its name -- of names[its name]
+    where `names` renames it --, or nowhere when `dtype` has none; the fields of `dtype` beyond those are the caller's to fill"""
+    out = np.empty(src.shape, dtype=dtype)
+    for k in src.dtype.names:
+        to = names.get(k, k) if names else k
+        if to in out.dtype.names:
+            out[to] = src[k]
+    return out
+
+
+def _row_bytes(cols):
+    """bytes one entry takes in every column of `cols` together (`_Columns`)"""
+    return sum(np.dtype(c[1]).itemsize * (c[2] if len(c) > 2 else 1) for c in cols)
+
+
+class _Columns(object):
+    """A block of columns in one device buffer: `cols` = [(name, dtype[, width]), ...] lie one behind the other in that order,
+    each of `cap` entries (a column of `width` w: w sub-columns of `cap` entries).  From this one description come the
+    addresses an entry point is given and the download into a structured array."""
+
+    def __init__(self, buf, cap, cols):
+        self.buf, self.at, self.type = buf, {}, {}
+        off = 0
+        for c in cols:
+            self.at[c[0]], self.type[c[0]] = off, c[1]
+            off += cap * _row_bytes([c])
+        assert off <= buf.nbytes
+
+    def ptr(self, name, wanted=True):
+        """the device address of a column (None when the caller does not want it filled)"""
+        return self.buf.ptr + self.at[name] if wanted else None
+
+    def ptrs(self, names):
+        return [self.buf.ptr + self.at[k] for k in names]
+
+    def get(self, name, shape):
+        return self.buf.download(shape, self.type[name], offset_bytes=self.at[name])
+
+    def into(self, out, skip=()):
+        """the first out.size entries of every column that is a field of the structured array `out` (but those of `skip`)"""
+        for k in out.dtype.names:
+            if k not in skip:
+                out[k] = self.get(k, out.shape)
+        return out
+
+
+OVERTURN_SELECT = {'all': 0, 'circumpolar': 1, 'main': 2}       # how K16 / K17 select pieces: the names and the library's codes
+XC_PROPS_MAXF = 8                                               # fields one K21 call takes (include/xcontour_hip.h)
+_UNSET = object()
+
+
+class _RecordArgs(object):
+    """The one argument check of the calls that run on K12's records (K12, K14, K16 - K23), and what it made of the arguments.  The
+    caller names what applies to it.  The checks run in the order written here -- the stack and its levels (`plane`), then the
+    weights and fields --, which is the order a call with two defects reports them in; a caller that reports a bad w or f first
+    gives `shape` = (nslab, ny, nx) alone and calls `plane` itself afterwards.  q, contours: the stack and its levels ((N,) or
+    (nslab, N), ascending); select: K16's, by name or code; periodic with min_nx 2 or 3: the ring's fewest columns; labels32:
+    the plane must fit 32-bit edge labels; w, f: the weight and the integrand; fields, x: K21's.
+    Attributes: q, contours, N, nslab, ny, nx, sel, periodic, w, f, fields, x, as the batches take them (contiguous, f32 / f64)."""
+
+    def __init__(self, who, q=None, contours=None, shape=None, select=_UNSET, periodic=False, min_nx=0, labels32=False, w=None,
+                 f=None, fields=(), x=None):
+        self.who, self.periodic = who, periodic
+        self.q = self.contours = self.N = self.sel = None
+        if q is not None:
+            self.plane(q, contours, select, periodic, min_nx, labels32)
+        else:
+            self.nslab, self.ny, self.nx = shape
+        who, nslab, ny, nx = self.who, self.nslab, self.ny, self.nx
+        if w is not None:
+            w = _contig(w, np.float64)
+            if w.shape not in ((ny, nx), (nslab, ny, nx)):
+                raise XContourHipError(XC_EBADARG, '%s: w must be (ny, nx) or (nslab, ny, nx)' % who)
+        if f is not None:
+            f = _contig(_f48(np.asarray(f)))
+            if f.shape != (nslab, ny, nx):
+                raise XContourHipError(XC_EBADARG, '%s: f must be (nslab, ny, nx)' % who)
+        if len(fields) > XC_PROPS_MAXF:
+            raise XContourHipError(XC_EBADARG, '%s: %d fields, at most %d (XC_PROPS_MAXF)' % (who, len(fields), XC_PROPS_MAXF))
+        fields = [_contig(_f48(np.asarray(a))) for a in fields]
+        if any(a.shape not in ((ny, nx), (nslab, ny, nx)) for a in fields):
+            raise XContourHipError(XC_EBADARG, '%s: a field must be (ny, nx) or (nslab, ny, nx)' % who)
+        if x is not None:
+            x = _contig(_f48(np.asarray(x)))
+            if x.shape != (nslab, ny, nx):
+                raise XContourHipError(XC_EBADARG, '%s: x must be (nslab, ny, nx)' % who)
+        self.w, self.f, self.fields, self.x = w, f, fields, x
+
+    def plane(self, q, contours, select=_UNSET, periodic=False, min_nx=0, labels32=False):
+        """the stack, its levels and what the plane must satisfy"""
+        who = self.who
+        self.q, (self.nslab, ny, nx) = _stack3(q)
+        self.ny, self.nx, self.periodic = ny, nx, periodic
+        self.contours, _, self.N = _levels_of(contours, self.nslab)
+        _check_ascending(self.contours, who)
+        if _UNSET is not select:
+            self.sel = sel = OVERTURN_SELECT.get(select, select) if isinstance(select, str) else select
+            if isinstance(sel, bool) or sel not in (0, 1, 2):
+                raise XContourHipError(XC_EBADARG, '%s: select is \'all\', \'circumpolar\' or \'main\' (0, 1, 2), not %r' % (who, select))
+            if sel != 0 and not periodic:
+                raise XContourHipError(XC_EBADARG, '%s: select=%r needs periodic=True (no piece goes round a plain plane)' % (who, select))
+        if periodic and nx < min_nx:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2' if min_nx == 2 else
+                                   '%s: a periodic plane needs nx >= 3' % who)
+        if labels32 and 2 * ny * nx >= 1 << 31:
+            raise XContourHipError(XC_EBADARG, '%s: plane too large for 32-bit labels (2 ny nx < 2^31)' % who)
+
+    def on(self, q, contours):
+        """the same plane, weights and fields under another stack of the same shape and its (checked) levels"""
+        _check_ascending(contours, self.who)
+        other = copy.copy(self)
+        other.q, other.contours = q, contours
+        return other
+
+    def batch(self, s0, s1):
+        """what the batch of slabs [s0, s1) stages: (q -- a lazy stack is read now --, contours, w, f, fields, x)"""
+        return (_stack_now(self.q, s0, s1), _part(self.contours, 2, s0, s1), _part(self.w, 3, s0, s1), _part(self.f, 3, s0, s1),
+                [_part(a, 3, s0, s1) for a in self.fields], _part(self.x, 3, s0, s1))
+
+    def slab_bytes(self, more=0):
+        """the bytes one slab stages: per node the tracer, what of w, f, the fields and x rides on the slab axis, and `more`"""
+        per = sum(a.dtype.itemsize for a in [self.q, self.w, self.f, self.x] + self.fields if a is not None and len(a.shape) == 3)
+        return self.ny * self.nx * (per + more)
 
 
 def join_segments(off, e_from, e_to):
@@ -1064,6 +1222,22 @@ class Context(object):
             return integ, lens, cnts
         return self._batched(nslab, ny * nx * (q.dtype.itemsize + f.dtype.itemsize), one)
 
+    @contextlib.contextmanager
+    def _two_pass(self, call, dcount, shape, nbytes, always=False):
+        """A count-only call, then a sized one.  call(0, []) is the entry point with no room and no outputs: it leaves the counts
+        (`shape` uint64) in `dcount`; their sum, the total, sizes the outputs -- one allocation per entry of nbytes(total) --,
+        which call(total, outputs) fills.  Nothing counted: no second call and no outputs, unless `always`.  Yields (counts, total,
+        outputs); the outputs are freed on the way out."""
+        rc = call(0, [])
+        if rc not in (XC_OK, 1):                                 # (1: there is something, and no room was given)
+            self._check(rc)
+        cnt = dcount.download(shape, np.uint64)
+        total = int(cnt.sum())
+        with self._temporaries([], nbytes(total) if total or always else []) as outs:
+            if outs:
+                self._check(call(total, outs))
+            yield cnt, total, outs
+
     def _with_segment_records(self, periodic, qb, cb, use, inputs=(), out_nbytes=(), per_segment=()):
         """K12's two passes over one batch, everything staged once.  Uploaded: the tracer `qb` (unless it has a device mirror), the
         contours `cb` ((N,) or one row per slab) and the caller's further `inputs`; allocated: the counts and one buffer per entry
@@ -1075,24 +1249,15 @@ class Context(object):
         n, ny, nx = qb.shape
         N, nin = cb.shape[-1], len(inputs)
         qp = self._mirror(qb)
-        dq = None if qp else self.to_device(qb)
-        bufs = [self.to_device(a) for a in (cb,) + tuple(inputs)] + [self.alloc(b) for b in (n * N * 8,) + tuple(out_nbytes)]
-        recs = []
-        try:
-            dn = bufs[1 + nin]
-            head = (self.handle, qp or dq.ptr, dtype_code(qb.dtype), n, ny, nx, bufs[0].ptr, N, 1 if cb.ndim == 2 else 0)
-            rc = f(*head, 0, dn.ptr, None, None, None)
-            if rc not in (XC_OK, 1):                             # (1: there are segments, and no room was given)
-                self._check(rc)
-            cnt = dn.download((n, N), np.uint64)
-            total = int(cnt.sum())
-            if total:
-                recs = [self.alloc(total * b) for b in (8, 8, 32) + tuple(per_segment)]
-                self._check(f(*head, total, dn.ptr, recs[0].ptr, recs[1].ptr, recs[2].ptr))
-            return use(cnt, total, dn, bufs[1:1 + nin], bufs[2 + nin:], recs)
-        finally:
-            for b in recs + ([] if dq is None else [dq]) + bufs:
-                b.free()
+        with self._temporaries(([] if qp else [qb]) + [cb] + list(inputs), [n * N * 8] + list(out_nbytes)) as bufs:
+            rest = bufs[0 if qp else 1:]
+            dn = rest[1 + nin]
+            head = (self.handle, qp or bufs[0].ptr, dtype_code(qb.dtype), n, ny, nx, rest[0].ptr, N, 1 if cb.ndim == 2 else 0)
+
+            def k12(total, recs):
+                return f(*head, total, dn.ptr, *([b.ptr for b in recs[:3]] or [None] * 3))
+            with self._two_pass(k12, dn, (n, N), lambda total: [total * b for b in (8, 8, 32) + tuple(per_segment)]) as (cnt, total, recs):
+                return use(cnt, total, dn, rest[1:1 + nin], rest[2 + nin:], recs)
 
     def contour_segments(self, q, contours, periodic=False):
         """Marching-squares contour segments (K12, xc_contour_segments_dev; periodic=True: xc_contour_segments_periodic_dev).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours
@@ -1104,11 +1269,7 @@ class Context(object):
         is staged once: a count-only call sizes the buffers of the second.  periodic=True: X is a ring of nx cell columns (nx >= 2):
         the seam cell between the last column and the first is traced too, its columns run from nx-1 to nx, and its right edge has
         column 0's id, 2 r nx + 1 -- the records of the plane with column 0 appended as column nx, ids folded onto the ring."""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, _, _ = _levels_of(contours, nslab)
-        _check_ascending(contours, 'xc_contour_segments')
-        if periodic and nx < 2:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
+        a = _RecordArgs('xc_contour_segments', q, contours, periodic=periodic, min_nx=2)
 
         def download(cnt, total, dn, ins, outs, recs):
             if total == 0:
@@ -1119,8 +1280,8 @@ class Context(object):
             return cnt, ef[o], et[o], pts[o]
 
         def one(s0, s1):
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), download)
-        return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+            return self._with_segment_records(periodic, *a.batch(s0, s1)[:2], download)
+        return self._batched(a.nslab, a.slab_bytes(), one)
 
     # the per-piece table of `contour_pieces`: one record per connected piece of a contour
     PIECE_DTYPE = np.dtype([('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),
@@ -1131,13 +1292,19 @@ class Context(object):
         is always allowed; the result does not depend on it)"""
         self._check(self.lib.xc_set_cpiece_workspace(self.handle, int(nbytes)))
 
+    def _last_profile(self, name, stages, groups=True):
+        """xc_last_<name>_profile: the device times of the stages of the last batch as `<stage>_ms`, then `rounds`[, `groups`]"""
+        ms = (C.c_double * len(stages))()
+        counts = [C.c_int(0) for _ in range(2 if groups else 1)]
+        self._check(getattr(self.lib, 'xc_last_%s_profile' % name)(self.handle, C.cast(ms, _vp), *[C.byref(c) for c in counts]))
+        out = {s + '_ms': v for s, v in zip(stages, ms)}
+        out.update(zip(('rounds', 'groups'), (c.value for c in counts)))
+        return out
+
     def last_cpiece_profile(self):
         """device times of the last `contour_pieces` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
         reduce_ms, rounds, groups)"""
-        ms = (C.c_double * 4)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cpiece_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], reduce_ms=ms[3], rounds=r.value, groups=g.value)
+        return self._last_profile('cpiece', ('table', 'rounds', 'roots', 'reduce'))
 
     def contour_pieces(self, q, contours, ycoord, xcoord, radius=0.0, period=None):
         """The connected pieces of every contour and their statistics (K13, xc_contour_pieces_dev, on the device records of K12,
@@ -1149,9 +1316,8 @@ class Context(object):
           length  the sum of K10's segment lengths (times radius), 0.0 for a piece of coincident-end segments only;
           area  S = 1/2 sum (Ya' + Yb') (Xa - Xb), Y' = sin(Y) and S radius^2 when radius > 0; NaN for an open piece;
           row_min, row_max  the extent in index-space rows."""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, _, N = _levels_of(contours, nslab)
-        _check_ascending(contours, 'xc_contour_pieces')
+        a = _RecordArgs('xc_contour_pieces', q, contours)
+        ny, nx, N = a.ny, a.nx, a.N
         ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_pieces')
         _check_finite('xc_contour_pieces', ycoord, xcoord)
         radius = float(radius)
@@ -1159,40 +1325,32 @@ class Context(object):
         if periodic:
             period = _check_period(period, xcoord, 'xc_contour_pieces')
         dt = self.PIECE_DTYPE
+        # one piece record per segment at most: six 8-byte columns, then two 4-byte ones
+        cols = [(k, dt[k]) for k in ('first_edge', 'nseg', 'length', 'area', 'row_min', 'row_max')] + [('closed', np.int32), ('winding', np.int32)]
 
         def pieces(cnt, total, dn, ins, outs, recs):
             if total == 0:
                 return np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt)
             (dy, dx), (dpc,), (df, dto, dp, drec) = ins, outs, recs
-            col = [drec.ptr + k * total * 8 for k in range(6)]              # first_edge, nseg, length, area, row_min, row_max
-            i32 = [drec.ptr + 48 * total, drec.ptr + 52 * total]              # closed, winding
-            rc = self.lib.xc_contour_pieces_dev(self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0,
-                                                dy.ptr, dx.ptr, period if periodic else 0.0, radius, total, dpc.ptr,
-                                                col[0], col[1], i32[0], i32[1], col[2], col[3], col[4], col[5])
-            self._check(rc)
+            at = _Columns(drec, total, cols)
+            self._check(self.lib.xc_contour_pieces_dev(
+                self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, dy.ptr, dx.ptr,
+                period if periodic else 0.0, radius, total, dpc.ptr,
+                *at.ptrs(('first_edge', 'nseg', 'closed', 'winding', 'length', 'area', 'row_min', 'row_max'))))
             pc = dpc.download(cnt.shape, np.uint64)
-            npiece = int(pc.sum())
-            out = np.empty(npiece, dtype=dt)
-            for name, at, t in (('first_edge', col[0], np.int64), ('nseg', col[1], np.int64), ('length', col[2], np.float64),
-                                ('area', col[3], np.float64), ('row_min', col[4], np.float64), ('row_max', col[5], np.float64),
-                                ('closed', i32[0], np.int32), ('winding', i32[1], np.int32)):
-                out[name] = drec.download((npiece,), t, offset_bytes=at - drec.ptr)
+            out = at.into(np.empty(int(pc.sum()), dtype=dt))
             return pc, out[_range_order(pc, out['first_edge'])]
 
         def one(s0, s1):
-            # beside K12's records: the coordinates, the piece counts, and one piece record per segment at most -- six 8-byte
-            # columns, then two 4-byte ones
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), pieces,
-                                              inputs=(ycoord, xcoord), out_nbytes=((s1 - s0) * N * 8,), per_segment=(56,))
-        return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+            # beside K12's records: the coordinates, the piece counts, and the piece records
+            return self._with_segment_records(periodic, *a.batch(s0, s1)[:2], pieces, inputs=(ycoord, xcoord),
+                                              out_nbytes=((s1 - s0) * N * 8,), per_segment=(_row_bytes(cols),))
+        return self._batched(a.nslab, a.slab_bytes(), one)
 
     def last_cjoin_profile(self):
         """device times of the last `contour_polylines` batch under set_kernel_timing(True): dict(table_ms, label_ms, rank_ms,
         place_ms, gather_ms, rounds, groups)"""
-        ms = (C.c_double * 5)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cjoin_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], label_ms=ms[1], rank_ms=ms[2], place_ms=ms[3], gather_ms=ms[4], rounds=r.value, groups=g.value)
+        return self._last_profile('cjoin', ('table', 'label', 'rank', 'place', 'gather'))
 
     def contour_polylines(self, q, contours, periodic=False):
         """The contours joined into polylines on the device (K14, xc_contour_polylines_dev, on the device records of K12): what
@@ -1202,47 +1360,39 @@ class Context(object):
         `contour_segments` / `join_segments`, bit for bit; poly_off (npoly + 1,) int64 into them; closed (npoly,) bool; rpo
         (nrange + 1,) int64: the polylines of range r are [rpo[r], rpo[r+1])) -- with walk = arange(total), the arguments of
         core.contour_polylines."""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, _, N = _levels_of(contours, nslab)
-        _check_ascending(contours, 'xc_contour_polylines')
-        if periodic and nx < 2:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
-        if 2 * ny * nx >= 1 << 31:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_polylines: plane too large for 32-bit labels (2 ny nx < 2^31)')
+        a = _RecordArgs('xc_contour_polylines', q, contours, periodic=periodic, min_nx=2, labels32=True)
+        ny, nx, N = a.ny, a.nx, a.N
+        cols = [('nseg', np.int64), ('first', np.int64), ('closed', np.int32)]       # one polyline per segment at most
 
         def polylines(cnt, total, dn, ins, outs, recs):
             if total == 0:
                 return (cnt, np.empty(0, dtype=np.int64), np.empty((0, 4), dtype=np.float64), np.empty(0, dtype=np.int64),
                         np.empty(0, dtype=bool), np.zeros(cnt.shape, dtype=np.uint64))
             (dpc,), (df, dto, dp, dfw, dpw, drec) = outs, recs
-            nseg, first, closed = drec.ptr, drec.ptr + 8 * total, drec.ptr + 16 * total       # one polyline per segment at most
+            at = _Columns(drec, total, cols)
             self._check(self.lib.xc_contour_polylines_dev(self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, total,
-                                                          dpc.ptr, nseg, closed, first, dpw.ptr, dfw.ptr, None))
+                                                          dpc.ptr, *at.ptrs(('nseg', 'closed', 'first')), dpw.ptr, dfw.ptr, None))
             pc = dpc.download(cnt.shape, np.uint64)
             npoly = int(pc.sum())
-            return (cnt, dfw.download((total,), np.int64), dpw.download((total, 4), np.float64), drec.download((npoly,), np.int64),
-                    drec.download((npoly,), np.int32, offset_bytes=16 * total).astype(bool), pc)
+            return (cnt, dfw.download((total,), np.int64), dpw.download((total, 4), np.float64), at.get('nseg', (npoly,)),
+                    at.get('closed', (npoly,)).astype(bool), pc)
 
         def one(s0, s1):
-            # beside K12's records: the polyline counts, the walk-ordered e_from and pts, and one polyline record per segment at
-            # most -- two 8-byte columns, then a 4-byte one
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), polylines,
-                                              out_nbytes=((s1 - s0) * N * 8,), per_segment=(8, 32, 20))
-        cnt, efw, ptw, nseg, closed, pc = self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+            # beside K12's records: the polyline counts, the walk-ordered e_from and pts, and the polyline records
+            return self._with_segment_records(periodic, *a.batch(s0, s1)[:2], polylines,
+                                              out_nbytes=((s1 - s0) * N * 8,), per_segment=(8, 32, _row_bytes(cols)))
+        cnt, efw, ptw, nseg, closed, pc = self._batched(a.nslab, a.slab_bytes(), one)
         poly_off = np.concatenate([[0], np.cumsum(nseg, dtype=np.int64)])
         rpo = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
         return cnt, efw, ptw, poly_off, closed, rpo
 
     # how `contour_overturning` selects pieces: the names and the library's codes
-    OVERTURN_SELECT = {'all': 0, 'circumpolar': 1, 'main': 2}
+    OVERTURN_SELECT = OVERTURN_SELECT
 
     def last_coverturn_profile(self):
         """device times of the last `contour_overturning` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, select_ms,
         count_ms, rounds, groups)"""
-        ms = (C.c_double * 4)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_coverturn_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], select_ms=ms[2], count_ms=ms[3], rounds=r.value, groups=g.value)
+        return self._last_profile('coverturn', ('table', 'rounds', 'select', 'count'))
 
     def contour_overturning(self, q, contours, periodic=False, select='main'):
         """Where the contours are overturned (K16, xc_contour_overturning_dev, on the device records of K12: the segment records
@@ -1254,18 +1404,8 @@ class Context(object):
         (nslab, N, nx): the crossings of a column, their smallest / largest row, NaN without one; nsel int32, main_first_edge
         int64, main_nseg int64, main_winding int32 (nslab, N): the selected pieces, and the ring 'main' picks (-1, 0, 0 without
         one) under the key `contour_pieces` lists it by).  A column with ncross >= 3 is overturned."""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, _, N = _levels_of(contours, nslab)
-        _check_ascending(contours, 'xc_contour_overturning')
-        sel = self.OVERTURN_SELECT.get(select, select) if isinstance(select, str) else select
-        if isinstance(sel, bool) or sel not in (0, 1, 2):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_overturning: select is \'all\', \'circumpolar\' or \'main\' (0, 1, 2), not %r' % (select,))
-        if sel != 0 and not periodic:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_overturning: select=%r needs periodic=True (no piece goes round a plain plane)' % (select,))
-        if periodic and nx < 2:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
-        if 2 * ny * nx >= 1 << 31:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_overturning: plane too large for 32-bit labels (2 ny nx < 2^31)')
+        a = _RecordArgs('xc_contour_overturning', q, contours, select=select, periodic=periodic, min_nx=2, labels32=True)
+        ny, nx, N = a.ny, a.nx, a.N
         types = (np.int32, np.float64, np.float64, np.int32, np.int64, np.int64, np.int32)
 
         def overturning(cnt, total, dn, ins, outs, recs):
@@ -1276,23 +1416,20 @@ class Context(object):
                 return tuple(np.full(sh, v, dtype=t) for sh, v, t in zip(shapes, fill, types))
             df, dto, dp = recs
             self._check(self.lib.xc_contour_overturning_dev(self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx,
-                                                            1 if periodic else 0, int(sel), *[b.ptr for b in outs]))
+                                                            1 if periodic else 0, int(a.sel), *[b.ptr for b in outs]))
             return tuple(b.download(sh, t) for b, sh, t in zip(outs, shapes, types))
 
         def one(s0, s1):
             # beside K12's records: the seven dense outputs -- 20 bytes per (contour, column), 24 per contour
             n = s1 - s0
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), overturning,
+            return self._with_segment_records(periodic, *a.batch(s0, s1)[:2], overturning,
                                               out_nbytes=tuple(n * N * b for b in (nx * 4, nx * 8, nx * 8, 4, 8, 8, 4)))
-        return self._batched(nslab, ny * nx * q.dtype.itemsize + N * nx * 20, one)
+        return self._batched(a.nslab, a.slab_bytes() + N * nx * 20, one)
 
     def last_cinterior_profile(self):
         """device times of the last `contour_interior` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, select_ms,
         scan_ms, rounds, groups)"""
-        ms = (C.c_double * 4)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cinterior_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], select_ms=ms[2], scan_ms=ms[3], rounds=r.value, groups=g.value)
+        return self._last_profile('cinterior', ('table', 'rounds', 'select', 'scan'))
 
     def contour_interior(self, q, contours, w=None, f=None, periodic=False, select='main', flip=False, return_mask=False):
         """What the selected pieces of every contour bound (K17, xc_contour_interior_dev, on the device records of K12: the segment
@@ -1302,55 +1439,30 @@ class Context(object):
         float64; f: None or (nslab, ny, nx) f32/f64.  Returns (n_in int64, sum_w float64, sum_wf float64 or None (nslab, N): the
         inside nodes, the sum of w and of w f over them -- exact sums rounded once, NaN terms skipped, an infinite term gives NaN
         --[, mask bool (nslab, N, ny, nx)]).  Only these cross to the host."""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, _, N = _levels_of(contours, nslab)
-        _check_ascending(contours, 'xc_contour_interior')
-        sel = self.OVERTURN_SELECT.get(select, select) if isinstance(select, str) else select
-        if isinstance(sel, bool) or sel not in (0, 1, 2):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_interior: select is \'all\', \'circumpolar\' or \'main\' (0, 1, 2), not %r' % (select,))
-        if sel != 0 and not periodic:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_interior: select=%r needs periodic=True (no piece goes round a plain plane)' % (select,))
-        if periodic and nx < 2:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_segments_periodic: nx >= 2')
-        if 2 * ny * nx >= 1 << 31:
-            raise XContourHipError(XC_EBADARG, 'xc_contour_interior: plane too large for 32-bit labels (2 ny nx < 2^31)')
-        if w is not None:
-            w = _contig(w, np.float64)
-            if w.shape not in ((ny, nx), (nslab, ny, nx)):
-                raise XContourHipError(XC_EBADARG, 'xc_contour_interior: w must be (ny, nx) or (nslab, ny, nx)')
-        if f is not None:
-            f = _contig(_f48(np.asarray(f)))
-            if f.shape != (nslab, ny, nx):
-                raise XContourHipError(XC_EBADARG, 'xc_contour_interior: f must be (nslab, ny, nx)')
-        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
-        has_f, want_mask = f is not None, bool(return_mask)
+        a = _RecordArgs('xc_contour_interior', q, contours, select=select, periodic=periodic, min_nx=2, labels32=True, w=w, f=f)
+        ny, nx, N = a.ny, a.nx, a.N
+        has_w, has_f, want_mask = a.w is not None, a.f is not None, bool(return_mask)
 
         def interior(cnt, total, dn, ins, outs, recs):
             n = cnt.shape[0]
-            ins = list(ins)
-            dw = ins.pop(0) if w is not None else None
-            df_ = ins.pop(0) if has_f else None
-            outs = list(outs)
-            dni, dsw = outs[0], outs[1]
-            dsf = outs[2] if has_f else None
-            dm = outs[-1] if want_mask else None
+            dw, df_ = (ins[0] if has_w else None), (ins[-1] if has_f else None)
+            dni, dsw = outs[:2]
+            dsf, dm = (outs[2] if has_f else None), (outs[-1] if want_mask else None)
             rec = [b.ptr for b in recs] if total else [None, None, None]
-            self._check(self.lib.xc_contour_interior_dev(self.handle, cnt.size, dn.ptr, rec[0], rec[1], rec[2], ny, nx, 1 if periodic else 0,
-                                                         int(sel), 1 if flip else 0, N, dw.ptr if dw is not None else None, w_per_slab,
-                                                         df_.ptr if df_ is not None else None, dtype_code(f.dtype) if has_f else 0,
-                                                         dni.ptr, dsw.ptr, dsf.ptr if dsf is not None else None, dm.ptr if dm is not None else None))
+            self._check(self.lib.xc_contour_interior_dev(
+                self.handle, cnt.size, dn.ptr, rec[0], rec[1], rec[2], ny, nx, 1 if periodic else 0, int(a.sel), 1 if flip else 0, N,
+                dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, df_.ptr if has_f else None,
+                dtype_code(a.f.dtype) if has_f else 0, dni.ptr, dsw.ptr, dsf.ptr if has_f else None, dm.ptr if want_mask else None))
             res = (dni.download((n, N), np.int64), dsw.download((n, N), np.float64), dsf.download((n, N), np.float64) if has_f else None)
             return res + ((dm.download((n, N, ny, nx), np.uint8).view(np.bool_),) if want_mask else ())
 
         def one(s0, s1):
             # beside K12's records: the weights and the integrand, three 8-byte results per contour, and the mask when asked for
             n = s1 - s0
-            ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
+            qb, cb, wb, fb = a.batch(s0, s1)[:4]
             nb = [n * N * 8, n * N * 8] + ([n * N * 8] if has_f else []) + ([n * N * ny * nx] if want_mask else [])
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), interior,
-                                              inputs=tuple(ins), out_nbytes=tuple(nb))
-        per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (N if want_mask else 0))
-        return self._batched(nslab, per, one)
+            return self._with_segment_records(periodic, qb, cb, interior, inputs=[v for v in (wb, fb) if v is not None], out_nbytes=nb)
+        return self._batched(a.nslab, a.slab_bytes(N if want_mask else 0), one)
 
     # the per-piece table of `contour_piece_interiors`: K13's key fields and what the piece encloses
     PIECE_INTERIOR_DTYPE = np.dtype([('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),
@@ -1359,10 +1471,7 @@ class Context(object):
     def last_cpinside_profile(self):
         """device times of the last `contour_piece_interiors` batch under set_kernel_timing(True): dict(table_ms, rounds_ms,
         roots_ms, walk_ms, rounds, groups)"""
-        ms = (C.c_double * 4)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cpinside_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], rounds=r.value, groups=g.value)
+        return self._last_profile('cpinside', ('table', 'rounds', 'roots', 'walk'))
 
     def contour_piece_interiors(self, q, contours, w=None, f=None, periodic=False, flip=False):
         """What EVERY piece of every contour bounds (K18, xc_contour_piece_interiors_dev, on the device records of K12: the segment
@@ -1375,7 +1484,7 @@ class Context(object):
         up with those of `contour_pieces`.  first_edge, nseg, closed, winding are that method's; n_in the inside nodes, sum_w the sum
         of w over them (None: weight 1), sum_wf that of w f (NaN without f) -- exact sums rounded once, NaN terms skipped, an infinite
         term makes that sum of that piece NaN.  An open piece bounds nothing: n_in -1, NaN sums."""
-        return self._piece_records('xc_contour_piece_interiors', False, q, contours, w, f, periodic, flip)
+        return self._ring_tables('interiors', q, contours, w, f, periodic, flip)
 
     # the per-piece table of `contour_piece_tree`: that of `contour_piece_interiors` and where the piece hangs in the tree of its range
     PIECE_TREE_DTYPE = np.dtype(PIECE_INTERIOR_DTYPE.descr + [('parent', np.int64), ('depth', np.int32), ('nchild', np.int32),
@@ -1384,10 +1493,7 @@ class Context(object):
     def last_cptree_profile(self):
         """device times of the last `contour_piece_tree` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
         walk_ms, tree_ms, rounds, groups)"""
-        ms = (C.c_double * 5)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cptree_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], tree_ms=ms[4], rounds=r.value, groups=g.value)
+        return self._last_profile('cptree', ('table', 'rounds', 'roots', 'walk', 'tree'))
 
     def contour_piece_tree(self, q, contours, w=None, f=None, periodic=False, flip=False):
         """Which piece of every contour is nested in which (K19, xc_contour_piece_tree_dev, on the device records of K12).  Arguments,
@@ -1397,16 +1503,12 @@ class Context(object):
         0 without parent, else the parent's + 1; `nchild` the rings whose parent the piece is; `n_net`, `net_w`, `net_wf` what
         n_in, sum_w, sum_wf become when the inside nodes of the children are taken out (exact sums rounded once; NaN exactly where
         the gross sum is).  An open piece is transparent: parent -1, depth 0, nchild 0, n_net -1, NaN net sums."""
-        return self._piece_records('xc_contour_piece_tree', True, q, contours, w, f, periodic, flip)
+        return self._ring_tables('tree', q, contours, w, f, periodic, flip)
 
     def last_cplabel_profile(self):
         """device times of the last `contour_piece_labels` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
         walk_ms, tree_ms, label_ms, rounds, groups)"""
-        ms = (C.c_double * 6)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cplabel_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], tree_ms=ms[4], label_ms=ms[5], rounds=r.value,
-                    groups=g.value)
+        return self._last_profile('cplabel', ('table', 'rounds', 'roots', 'walk', 'tree', 'label'))
 
     def contour_piece_labels(self, q, contours, w=None, f=None, periodic=False, flip=False):
         """Which ring HOLDS every node (K20, xc_contour_piece_labels_dev, on the device records of K12).  Arguments as for
@@ -1415,18 +1517,26 @@ class Context(object):
         `contour_piece_interiors`) with the fewest nodes -- as the ROW of that range's rows of `table` (first_edge order, counted from
         the start of the range, like `parent`), -1 where no ring holds the node.  Open pieces never appear.  The nodes with label p
         are those `n_net`, `net_w`, `net_wf` of row p sum over; depth[label] + 1 rings hold a node."""
-        return self._piece_records('xc_contour_piece_labels', True, q, contours, w, f, periodic, flip, labels=True)
+        a = _RecordArgs('xc_contour_piece_labels', q, contours, periodic=periodic, min_nx=3, labels32=True, w=w, f=f)
 
-    XC_PROPS_MAXF = 8
+        def one(s0, s1):
+            lshape = (s1 - s0, a.N, a.ny, a.nx)
+            with self._temporaries([], [4 * lshape[0] * lshape[1] * lshape[2] * lshape[3]]) as (dmap,):
+                pc, tab, rows, _ = self._piece_records('labels', a, s0, s1, flip, dest=dmap)
+                if not rows.size:                                # no piece in the batch: no node is in a ring
+                    return pc, tab, np.full(lshape, -1, dtype=np.int32)
+                lab = dmap.download(lshape, np.int32)
+            # the entry's label is a position inside the range as it packed the rows: -> the row of the range's sorted table
+            _to_rows(lab, _scan(pc)[1].reshape(lshape[:2] + (1, 1)), rows)
+            return pc, tab, lab
+        return self._batched(a.nslab, a.slab_bytes(4 * a.N), one)
+
+    XC_PROPS_MAXF = XC_PROPS_MAXF
 
     def last_cpprops_profile(self):
         """device times of the last `contour_piece_props` batch under set_kernel_timing(True): dict(table_ms, rounds_ms, roots_ms,
         walk_ms, tree_ms, scan_ms, fold_ms, rounds, groups)"""
-        ms = (C.c_double * 7)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cpprops_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(table_ms=ms[0], rounds_ms=ms[1], roots_ms=ms[2], walk_ms=ms[3], tree_ms=ms[4], scan_ms=ms[5], fold_ms=ms[6],
-                    rounds=r.value, groups=g.value)
+        return self._last_profile('cpprops', ('table', 'rounds', 'roots', 'walk', 'tree', 'scan', 'fold'))
 
     def contour_piece_props(self, q, contours, w=None, fields=(), x=None, periodic=False, flip=False):
         """What every ring HOLDS of further fields (K21, xc_contour_piece_props_dev, on the device records of K12): the reductions
@@ -1439,145 +1549,95 @@ class Context(object):
         ring round it); with x 'x_min', 'x_max' f64 and 'at_min', 'at_max' int64 (else None): the extremum of x over the ring's
         net nodes that are not NaN and the flat node r nx + c it sits on (-0.0 below +0.0, ties to the smallest node; NaN and -1
         without such a node).  Open pieces: NaN and -1."""
-        return self._piece_records('xc_contour_piece_props', True, q, contours, w, None, periodic, flip, props=(tuple(fields), x))
-
-    def _piece_records(self, who, tree, q, contours, w, f, periodic, flip, labels=False, props=None, keep=None):
-        """`contour_piece_interiors` (K18), with `tree` `contour_piece_tree` (K19), with `labels` too `contour_piece_labels`
-        (K20), and with `props` = (fields, x) `contour_piece_props` (K21): the same staging, one entry point each.  keep (with
-        `labels`): a DeviceBuffer of the caller's that takes the map and keeps it on the device -- all slabs are then ONE batch
-        (the caller batches) and the return is (piece_count, table, rows) with `rows` int32 (npiece,): the row of the range's
-        sorted table for every position of the packed order the device labels count in"""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, _, N = _levels_of(contours, nslab)
-        _check_ascending(contours, who)
-        if periodic and nx < 3:
-            raise XContourHipError(XC_EBADARG, '%s: a periodic plane needs nx >= 3' % who)
-        if 2 * ny * nx >= 1 << 31:
-            raise XContourHipError(XC_EBADARG, '%s: plane too large for 32-bit labels (2 ny nx < 2^31)' % who)
-        if w is not None:
-            w = _contig(w, np.float64)
-            if w.shape not in ((ny, nx), (nslab, ny, nx)):
-                raise XContourHipError(XC_EBADARG, '%s: w must be (ny, nx) or (nslab, ny, nx)' % who)
-        if f is not None:
-            f = _contig(_f48(np.asarray(f)))
-            if f.shape != (nslab, ny, nx):
-                raise XContourHipError(XC_EBADARG, '%s: f must be (nslab, ny, nx)' % who)
-        flds, x = props if props is not None else ((), None)
-        if len(flds) > self.XC_PROPS_MAXF:
-            raise XContourHipError(XC_EBADARG, '%s: %d fields, at most %d (XC_PROPS_MAXF)' % (who, len(flds), self.XC_PROPS_MAXF))
-        flds = [_contig(_f48(np.asarray(a))) for a in flds]
-        if any(a.shape not in ((ny, nx), (nslab, ny, nx)) for a in flds):
-            raise XContourHipError(XC_EBADARG, '%s: a field must be (ny, nx) or (nslab, ny, nx)' % who)
-        if x is not None:
-            x = _contig(_f48(np.asarray(x)))
-            if x.shape != (nslab, ny, nx):
-                raise XContourHipError(XC_EBADARG, '%s: x must be (nslab, ny, nx)' % who)
-        nfld, has_x = len(flds), x is not None
-        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
-        has_f = f is not None
-        dt = self.PIECE_TREE_DTYPE if tree else self.PIECE_INTERIOR_DTYPE
-        # one piece record per segment at most: the 8-byte columns, then the 4-byte ones
-        c8 = ('first_edge', 'nseg', 'n_in', 'sum_w', 'sum_wf') + (('parent', 'n_net', 'net_w', 'net_wf') if tree else ())
-        c4 = ('closed', 'winding') + (('depth', 'nchild') if tree else ())
-        types = {'first_edge': np.int64, 'nseg': np.int64, 'n_in': np.int64, 'parent': np.int64, 'n_net': np.int64}
-
-        def records(cnt, total, dn, ins, outs, recs):
-            lshape = cnt.shape + (ny, nx)
-            if total == 0:
-                none = (np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt))
-                if props is not None:
-                    return none + (_props_of(0, 0, None, None),)
-                if keep is not None:
-                    keep.upload(np.full(lshape, -1, dtype=np.int32))
-                    return none + (np.empty(0, dtype=np.int32),)
-                return none + ((np.full(lshape, -1, dtype=np.int32),) if labels else ())
-            ins = list(ins)
-            dw = ins.pop(0) if w is not None else None
-            df_ = ins.pop(0) if has_f else None
-            dflds = [ins.pop(0) for _ in flds]
-            dx = ins.pop(0) if has_x else None
-            dpc, (df, dto, dp, drec) = outs[0], recs
-            at = {k: drec.ptr + j * total * 8 for j, k in enumerate(c8)}
-            at.update({k: drec.ptr + (8 * len(c8) + 4 * j) * total for j, k in enumerate(c4)})
-            head = (self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
-                    dw.ptr if dw is not None else None, w_per_slab, df_.ptr if df_ is not None else None,
-                    dtype_code(f.dtype) if has_f else 0, total, dpc.ptr, at['first_edge'], at['nseg'], at['closed'], at['winding'],
-                    at['n_in'], at['sum_w'], at['sum_wf'] if has_f else None)
-            if tree:
-                more = (at['parent'], at['depth'], at['nchild'], at['n_net'], at['net_w'], at['net_wf'] if has_f else None)
-            if props is not None:
-                # behind the thirteen columns of a segment's record bytes: net_g, sum_g [nf][total], then x_min, x_max, at_min, at_max
-                pbase = drec.ptr + (8 * len(c8) + 4 * len(c4)) * total
-                pat = [pbase + j * total * 8 for j in (0, nfld, 2 * nfld, 2 * nfld + 1, 2 * nfld + 2, 2 * nfld + 3)]
-                gp = (_vp * max(nfld, 1))(*[b.ptr for b in dflds])
-                gd = (C.c_int * max(nfld, 1))(*[dtype_code(a.dtype) for a in flds])
-                gs = (C.c_int * max(nfld, 1))(*[1 if a.ndim == 3 else 0 for a in flds])
-                self._check(self.lib.xc_contour_piece_props_dev(
-                    *head, *more, nfld, C.cast(gp, _vp), C.cast(gd, _vp), C.cast(gs, _vp), dx.ptr if has_x else None,
-                    dtype_code(x.dtype) if has_x else 0, pat[0] if nfld else None, pat[1] if nfld else None,
-                    *[a if has_x else None for a in pat[2:]]))
-            elif labels:
-                self._check(self.lib.xc_contour_piece_labels_dev(*head, *more, keep.ptr if keep is not None else outs[1].ptr))
-            elif tree:
-                self._check(self.lib.xc_contour_piece_tree_dev(*head, *more))
-            else:
-                self._check(self.lib.xc_contour_piece_interiors_dev(*head))
-            pc = dpc.download(cnt.shape, np.uint64)
-            npiece = int(pc.sum())
-            out = np.empty(npiece, dtype=dt)
-            for name in c8 + c4:
-                if name in ('sum_wf', 'net_wf') and not has_f:
-                    out[name] = np.nan
-                    continue
-                t = np.int32 if name in c4 else types.get(name, np.float64)
-                out[name] = drec.download((npiece,), t, offset_bytes=at[name] - drec.ptr)
-            order = _range_order(pc, out['first_edge'])
-            if tree:
-                # the entry's parent is an index into the rows as it packed them: -> the row inside the piece's own range, sorted
-                where = np.empty(npiece, dtype=np.int64)
-                where[order] = np.arange(npiece)
-                start = np.repeat(np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64), pc.ravel().astype(np.int64))
-                has = out['parent'] >= 0
-                out['parent'][has] = where[out['parent'][has]] - start[where[has.nonzero()[0]]]
-            if props is not None:
-                return pc, out[order], _props_of(npiece, total, lambda j, shape, t: drec.download(shape, t, offset_bytes=pat[j] - drec.ptr), order)
-            if not labels:
-                return pc, out[order]
-            if keep is not None:
-                return pc, out[order], (where - start).astype(np.int32)
-            # the entry's label is a position inside the range as it packed the rows: -> the row of the range's sorted table
-            lab = outs[1].download(lshape, np.int32)
-            first = (np.cumsum(pc.ravel().astype(np.int64)) - pc.ravel().astype(np.int64)).reshape(cnt.shape + (1, 1))
-            has = lab >= 0
-            lab[has] = (where[(lab + first)[has]] - np.broadcast_to(first, lshape)[has]).astype(np.int32)
-            return pc, out[order], lab
-
-        def _props_of(npiece, total, get, order):
-            """K21's per-piece columns, downloaded by get(column block, shape, dtype), as rows in the table's sorted order"""
-            cols = {}
-            for j, name in ((0, 'net'), (1, 'gross')):
-                # column m of a per-field array starts at m * capacity, the capacity being `total`
-                if nfld and npiece:
-                    cols[name] = np.ascontiguousarray(get(j, (nfld, total), np.float64)[:, :npiece].T[order])
-                else:
-                    cols[name] = np.empty((npiece, nfld))
-            for j, name, t in ((2, 'x_min', np.float64), (3, 'x_max', np.float64), (4, 'at_min', np.int64), (5, 'at_max', np.int64)):
-                cols[name] = None if not has_x else get(j, (npiece,), t)[order] if npiece else np.empty(0, dtype=t)
-            return cols
+        a = _RecordArgs('xc_contour_piece_props', q, contours, periodic=periodic, min_nx=3, labels32=True, w=w, fields=tuple(fields), x=x)
 
         def one(s0, s1):
-            # beside K12's records: the weights, the integrand, the fields and the extremum field, the piece counts, and the piece records
-            ins = ([] if w is None else [_part(w, 3, s0, s1)]) + ([f[s0:s1]] if has_f else [])
-            ins += [_part(a, 3, s0, s1) for a in flds] + ([x[s0:s1]] if has_x else [])
-            nb = ((s1 - s0) * N * 8,) + (((s1 - s0) * N * ny * nx * 4,) if labels and keep is None else ())
-            pbytes = 8 * (2 * nfld + 4) if props is not None else 0
-            return self._with_segment_records(periodic, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), records,
-                                              inputs=tuple(ins), out_nbytes=nb, per_segment=(8 * len(c8) + 4 * len(c4) + pbytes,))
-        per = ny * nx * (q.dtype.itemsize + (8 if w_per_slab else 0) + (f.dtype.itemsize if has_f else 0) + (4 * N if labels else 0))
-        per += ny * nx * (sum(a.dtype.itemsize for a in flds if a.ndim == 3) + (x.dtype.itemsize if has_x else 0))
-        if keep is not None:
-            return one(0, nslab)
-        return self._batched(nslab, per, one)
+            pc, tab, _, props = self._piece_records('props', a, s0, s1, flip)
+            return pc, tab, props
+        return self._batched(a.nslab, a.slab_bytes(), one)
+
+    def _ring_tables(self, stage, q, contours, w, f, periodic, flip):
+        """`contour_piece_interiors` / `contour_piece_tree`: the tables of stage 'interiors' / 'tree', batch by batch"""
+        a = _RecordArgs('xc_contour_piece_' + stage, q, contours, periodic=periodic, min_nx=3, labels32=True, w=w, f=f)
+        return self._batched(a.nslab, a.slab_bytes(), lambda s0, s1: self._piece_records(stage, a, s0, s1, flip)[:2])
+
+    # K21's columns behind a ring's record: the sums per field, net and gross, then the extremum of x and where it sits
+    _PROPS_X = [('x_min', np.float64), ('x_max', np.float64), ('at_min', np.int64), ('at_max', np.int64)]
+
+    def _labels_on_device(self, a, s0, s1, flip, dest):
+        """the 'labels' stage of `_piece_records` for a caller that keeps the map on the device: `dest` holds the map afterwards
+        -- -1 everywhere when the batch had no segments.  Returns (piece_count, table, rows)"""
+        pc, tab, rows, _ = self._piece_records('labels', a, s0, s1, flip, dest=dest)
+        if not rows.size:
+            dest.upload(np.full(pc.shape + (a.ny, a.nx), -1, dtype=np.int32))
+        return pc, tab, rows
+
+    def _piece_records(self, stage, a, s0, s1, flip, dest=None):
+        """The ring records of ONE batch, slabs [s0, s1) of the checked arguments `a`, through the entry point of `stage`: the
+        stages are cumulative -- 'interiors' (K18), 'tree' (K19: + the nesting), then 'labels' (K20: + the map, written to `dest`, a
+        DeviceBuffer or view of the caller's, where it stays) or 'props' (K21: + the sums and extrema of a.fields, a.x).  Returns
+        (piece_count (n, N), table, rows, props): the table of the stage (PIECE_INTERIOR_DTYPE, from 'tree' on PIECE_TREE_DTYPE),
+        every range sorted by first_edge; `rows` (`_row_map`), which turns what the device counts in its packed order -- the
+        labels in `dest` -- into rows of the table; `props` K21's columns in the table's order, None for the other stages.  A
+        batch without segments has no rows and leaves `dest` as it was (`_labels_on_device` fills it)."""
+        tree = stage != 'interiors'
+        qb, cb, wb, fb, fields, xb = a.batch(s0, s1)
+        ny, nx, N, periodic = a.ny, a.nx, a.N, a.periodic
+        nfld, has_w, has_f, has_x = len(fields), wb is not None, fb is not None, xb is not None
+        dt = self.PIECE_TREE_DTYPE if tree else self.PIECE_INTERIOR_DTYPE
+        # one piece record per segment at most: the table's 8-byte columns, then its others as 4-byte ones, then K21's
+        cols = [(k, dt[k]) for k in dt.names if dt[k].itemsize == 8] + [(k, np.int32) for k in dt.names if dt[k].itemsize != 8]
+        if stage == 'props':
+            cols += [('net', np.float64, nfld), ('gross', np.float64, nfld)] + self._PROPS_X
+
+        def records(cnt, total, dn, ins, outs, recs):
+            if total == 0:
+                return (np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt), np.empty(0, dtype=np.int64),
+                        self._ring_props(None, 0, 0, nfld, has_x, None) if stage == 'props' else None)
+            dw, df_ = (ins[0] if has_w else None), (ins[has_w] if has_f else None)
+            dpc, (df, dto, dp, drec) = outs[0], recs
+            at = _Columns(drec, total, cols)
+            p = at.ptr
+            args = [self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
+                    dw.ptr if has_w else None, 1 if has_w and wb.ndim == 3 else 0, df_.ptr if has_f else None,
+                    dtype_code(fb.dtype) if has_f else 0, total, dpc.ptr, p('first_edge'), p('nseg'), p('closed'), p('winding'),
+                    p('n_in'), p('sum_w'), p('sum_wf', has_f)]
+            if tree:
+                args += [p('parent'), p('depth'), p('nchild'), p('n_net'), p('net_w'), p('net_wf', has_f)]
+            if stage == 'labels':
+                args.append(dest.ptr)
+            if stage == 'props':
+                dflds = ins[has_w + has_f:has_w + has_f + nfld]
+                gp = (_vp * max(nfld, 1))(*[b.ptr for b in dflds])
+                gd = (C.c_int * max(nfld, 1))(*[dtype_code(v.dtype) for v in fields])
+                gs = (C.c_int * max(nfld, 1))(*[1 if v.ndim == 3 else 0 for v in fields])
+                args += [nfld, C.cast(gp, _vp), C.cast(gd, _vp), C.cast(gs, _vp), ins[-1].ptr if has_x else None,
+                         dtype_code(xb.dtype) if has_x else 0, p('net', nfld), p('gross', nfld)] + [p(k, has_x) for k, _ in self._PROPS_X]
+            self._check(getattr(self.lib, 'xc_contour_piece_%s_dev' % stage)(*args))
+            pc = dpc.download(cnt.shape, np.uint64)
+            out = np.empty(int(pc.sum()), dtype=dt)
+            nof = [k for k in ('sum_wf', 'net_wf') if not has_f and k in dt.names]
+            for k in nof:
+                out[k] = np.nan
+            at.into(out, skip=nof)
+            order, rows = _row_map(pc, out['first_edge'])
+            if tree:
+                _to_rows(out['parent'], 0, rows)                 # the entry's parent is an index into the rows as it packed them
+            return pc, out[order], rows, self._ring_props(at, out.size, total, nfld, has_x, order) if stage == 'props' else None
+        # beside K12's records: the weights, the integrand, the fields and the extremum field, the piece counts, and the piece records
+        ins = [v for v in (wb, fb) if v is not None] + fields + ([xb] if has_x else [])
+        return self._with_segment_records(periodic, qb, cb, records, inputs=ins, out_nbytes=((s1 - s0) * N * 8,),
+                                          per_segment=(_row_bytes(cols),))
+
+    def _ring_props(self, at, npiece, total, nfld, has_x, order):
+        """K21's per-piece columns out of the record block `at` (of capacity `total`), as rows in the table's sorted order"""
+        cols = {}
+        for name in ('net', 'gross'):                            # sub-column m of a per-field column starts at m * capacity
+            cols[name] = (np.ascontiguousarray(at.get(name, (nfld, total))[:, :npiece].T[order]) if nfld and npiece
+                          else np.empty((npiece, nfld)))
+        for name, t in self._PROPS_X:
+            cols[name] = None if not has_x else at.get(name, (npiece,))[order] if npiece else np.empty(0, dtype=t)
+        return cols
 
     # the rows of `label_overlap` and `contour_piece_overlap`: one per pair of labels that share a node
     OVERLAP_DTYPE = np.dtype([('a', np.int32), ('b', np.int32), ('n', np.int64), ('sum_w', np.float64), ('sum_wf', np.float64)])
@@ -1585,54 +1645,36 @@ class Context(object):
     def last_cpoverlap_profile(self):
         """device times of the last xc_label_overlap_dev call (the last batch of `label_overlap` / `contour_piece_overlap`) under
         set_kernel_timing(True): dict(runs_ms, accumulate_ms, finish_ms, rounds (0), groups)"""
-        ms = (C.c_double * 3)()
-        r, g = C.c_int(0), C.c_int(0)
-        self._check(self.lib.xc_last_cpoverlap_profile(self.handle, C.cast(ms, _vp), C.byref(r), C.byref(g)))
-        return dict(runs_ms=ms[0], accumulate_ms=ms[1], finish_ms=ms[2], rounds=r.value, groups=g.value)
+        return self._last_profile('cpoverlap', ('runs', 'accumulate', 'finish'))
 
-    def _overlap_rows(self, nrange, ny, nx, ncont, pa, pb, pw, w_per_slab, pf, f_code):
-        """K22 on two maps that lie on the device (pa, pb, pw, pf: device addresses, pw / pf or None): a count-only call, then a
-        sized one -> (pair_count uint64 (nrange,), the rows (OVERLAP_DTYPE) packed by range, in the call's own order)"""
-        head = (self.handle, nrange, ny, nx, ncont, pa, pb, pw, w_per_slab, pf, f_code)
-        dpc, drow = self.alloc(nrange * 8), None
-        try:
-            rc = self.lib.xc_label_overlap_dev(*head, 0, dpc.ptr, None, None, None, None, None)
-            if rc not in (XC_OK, 1):                             # (1: there are rows, and no room was given)
-                self._check(rc)
-            pc = dpc.download((nrange,), np.uint64)
-            total = int(pc.sum())
-            rows = np.empty(total, dtype=self.OVERLAP_DTYPE)
-            rows['sum_wf'] = np.nan
-            if total:
-                # the 4-byte columns, then the 8-byte ones
-                drow = self.alloc(total * 32)
-                at = {k: drow.ptr + j * total for k, j in (('a', 0), ('b', 4), ('n', 8), ('sum_w', 16), ('sum_wf', 24))}
-                self._check(self.lib.xc_label_overlap_dev(*head, total, dpc.ptr, at['a'], at['b'], at['n'], at['sum_w'],
-                                                          at['sum_wf'] if pf else None))
-                for k in rows.dtype.names:
-                    if k != 'sum_wf' or pf:
-                        rows[k] = drow.download((total,), rows.dtype[k], offset_bytes=at[k] - drow.ptr)
-            return pc, rows
-        finally:
-            for b in (dpc, drow):
-                if b is not None:
-                    b.free()
+    def _overlap_rows(self, nrange, ny, nx, ncont, pa, pb, wb=None, fb=None):
+        """K22 on two maps that lie on the device (pa, pb: device addresses), with the call's slices of w and f (host arrays or
+        None) staged for it: a count-only call, then a sized one -> (pair_count uint64 (nrange,), the rows (OVERLAP_DTYPE) packed
+        by range, in the call's own order)"""
+        dt = self.OVERLAP_DTYPE
+        cols = [(k, dt[k]) for k in dt.names]                    # the 4-byte columns, then the 8-byte ones
+        has_w, has_f = wb is not None, fb is not None
+        with self._temporaries([v for v in (wb, fb) if v is not None], [nrange * 8]) as bufs:
+            dpc = bufs[-1]
+            head = (self.handle, nrange, ny, nx, ncont, pa, pb, bufs[0].ptr if has_w else None, 1 if has_w and wb.ndim == 3 else 0,
+                    bufs[has_w].ptr if has_f else None, dtype_code(fb.dtype) if has_f else 0)
+            block = []                                           # the row block of the sized call, described once
+
+            def k22(total, outs):
+                block[:] = [_Columns(b, total, cols) for b in outs]
+                at = [block[0].ptr(k, k != 'sum_wf' or has_f) for k in dt.names] if outs else [None] * 5
+                return self.lib.xc_label_overlap_dev(*head, total, dpc.ptr, *at)
+            with self._two_pass(k22, dpc, (nrange,), lambda total: [total * _row_bytes(cols)]) as (pc, total, outs):
+                rows = np.empty(total, dtype=dt)
+                rows['sum_wf'] = np.nan
+                if total:
+                    block[0].into(rows, skip=() if has_f else ('sum_wf',))
+                return pc, rows
 
     @staticmethod
     def _sorted_overlap(pc, rows):
         """rows packed by range -> each range sorted by (a, b)"""
-        return rows[np.lexsort((rows['b'], rows['a'], np.repeat(np.arange(pc.size), pc.ravel().astype(np.int64))))]
-
-    def _overlap_weights(self, who, w, f, nslab, ny, nx):
-        if w is not None:
-            w = _contig(w, np.float64)
-            if w.shape not in ((ny, nx), (nslab, ny, nx)):
-                raise XContourHipError(XC_EBADARG, '%s: w must be (ny, nx) or (nslab, ny, nx)' % who)
-        if f is not None:
-            f = _contig(_f48(np.asarray(f)))
-            if f.shape != (nslab, ny, nx):
-                raise XContourHipError(XC_EBADARG, '%s: f must be (nslab, ny, nx)' % who)
-        return w, f
+        return rows[np.lexsort((rows['b'], rows['a'], _range_of(pc)))]
 
     def label_overlap(self, lab_a, lab_b, w=None, f=None):
         """Which labels of two maps share nodes (K22, xc_label_overlap_dev): the contingency table of two label maps, built on the
@@ -1650,19 +1692,13 @@ class Context(object):
         lead, (ny, nx) = lab_a.shape[:-2], lab_a.shape[-2:]
         nslab, N = lead[0], (lead[1] if len(lead) == 2 else 1)
         lab_a, lab_b = lab_a.reshape(nslab, N, ny, nx), lab_b.reshape(nslab, N, ny, nx)
-        w, f = self._overlap_weights(who, w, f, nslab, ny, nx)
-        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
+        wf = _RecordArgs(who, shape=(nslab, ny, nx), w=w, f=f)
 
         def one(s0, s1):
-            ins = [lab_a[s0:s1], lab_b[s0:s1]] + ([] if w is None else [_part(w, 3, s0, s1)]) + ([] if f is None else [f[s0:s1]])
-            with self._temporaries(ins, []) as bufs:
-                pw = bufs[2].ptr if w is not None else None
-                pf = bufs[-1].ptr if f is not None else None
-                pc, rows = self._overlap_rows((s1 - s0) * N, ny, nx, N, bufs[0].ptr, bufs[1].ptr, pw, w_per_slab, pf,
-                                              dtype_code(f.dtype) if f is not None else 0)
+            with self._temporaries([lab_a[s0:s1], lab_b[s0:s1]], []) as (da, db):
+                pc, rows = self._overlap_rows((s1 - s0) * N, ny, nx, N, da.ptr, db.ptr, _part(wf.w, 3, s0, s1), _part(wf.f, 3, s0, s1))
             return pc.reshape(s1 - s0, N), self._sorted_overlap(pc, rows)
-        per = ny * nx * (2 * 4 * N + (8 if w_per_slab else 0) + (f.dtype.itemsize if f is not None else 0))
-        pc, rows = self._batched(nslab, per, one)
+        pc, rows = self._batched(nslab, wf.slab_bytes(2 * 4 * N), one)
         return pc.reshape(lead), rows
 
     def contour_piece_overlap(self, qa, qb, contours, contours_b=None, w=None, f=None, periodic=False, flip=False):
@@ -1682,39 +1718,21 @@ class Context(object):
         cb, _, Nb = _levels_of(contours if contours_b is None else contours_b, nslab)
         if Nb != N:
             raise XContourHipError(XC_EBADARG, '%s: as many levels for the one field as for the other' % who)
-        w, f = self._overlap_weights(who, w, f, nslab, ny, nx)
-        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
-
-        def rows_of(a, first, rowmap):
-            has = a >= 0
-            a[has] = rowmap[first[has] + a[has]]
+        a = _RecordArgs(who, shape=(nslab, ny, nx), w=w, f=f)   # (a bad w or f is reported before a bad level)
+        a.plane(qa, ca, periodic=periodic, min_nx=3, labels32=True)
+        b = a.on(qb, cb)
+        slot = N * ny * nx * 4
 
         def one(s0, s1):
             n = s1 - s0
-            wp, fp = _part(w, 3, s0, s1), (None if f is None else f[s0:s1])
-            maps = [self.alloc(n * N * ny * nx * 4) for _ in range(2)]
-            try:
-                ta = self._piece_records(who, True, _stack_now(qa, s0, s1), _part(ca, 2, s0, s1), wp, fp, periodic, flip, labels=True,
-                                         keep=maps[0])
-                tb = self._piece_records(who, True, _stack_now(qb, s0, s1), _part(cb, 2, s0, s1), wp, fp, periodic, flip, labels=True,
-                                         keep=maps[1])
-                with self._temporaries([a for a in (wp, fp) if a is not None], []) as bufs:
-                    pw = bufs[0].ptr if wp is not None else None
-                    pf = bufs[-1].ptr if fp is not None else None
-                    pc, rows = self._overlap_rows(n * N, ny, nx, N, maps[0].ptr, maps[1].ptr, pw, w_per_slab, pf,
-                                                  dtype_code(f.dtype) if f is not None else 0)
-            finally:
-                for b in maps:
-                    b.free()
+            with self._temporaries([], [n * slot, n * slot]) as maps:
+                ta, tb = (self._labels_on_device(v, s0, s1, flip, m) for v, m in zip((a, b), maps))
+                pc, rows = self._overlap_rows(n * N, ny, nx, N, maps[0].ptr, maps[1].ptr, _part(a.w, 3, s0, s1), _part(a.f, 3, s0, s1))
             # the device labels are positions in each call's packed order: -> rows of the first_edge-sorted tables
-            rng = np.repeat(np.arange(pc.size), pc.astype(np.int64))
             for key, t in (('a', ta), ('b', tb)):
-                cnt = t[0].ravel().astype(np.int64)
-                rows_of(rows[key], (np.cumsum(cnt) - cnt)[rng], t[2])
+                _to_rows(rows[key], _scan(t[0])[1][_range_of(pc)], t[2])
             return ta[0], ta[1], tb[0], tb[1], pc.reshape(n, N), self._sorted_overlap(pc, rows)
-        per = ny * nx * (qa.dtype.itemsize + qb.dtype.itemsize + 2 * 4 * N + (8 if w_per_slab else 0)
-                         + (f.dtype.itemsize if f is not None else 0))
-        return self._batched(nslab, per, one)
+        return self._batched(nslab, a.slab_bytes(qb.dtype.itemsize + 2 * 4 * N), one)
 
     # the rows of `ring_tracks`: one per track
     TRACK_DTYPE = np.dtype([('first_ring', np.int64), ('first_step', np.int32), ('last_step', np.int32), ('nrings', np.int64),
@@ -1728,10 +1746,7 @@ class Context(object):
     def last_cptrack_profile(self):
         """the last xc_ring_tracks_dev call: dict(accept_ms, rounds_ms, finish_ms -- device times under set_kernel_timing(True) --,
         rounds: the hook / compress rounds, the last, unchanged one included)"""
-        ms = (C.c_double * 3)()
-        r = C.c_int(0)
-        self._check(self.lib.xc_last_cptrack_profile(self.handle, C.cast(ms, _vp), C.byref(r)))
-        return dict(accept_ms=ms[0], rounds_ms=ms[1], finish_ms=ms[2], rounds=r.value)
+        return self._last_profile('cptrack', ('accept', 'rounds', 'finish'), groups=False)
 
     def ring_tracks(self, ring_step, ring_size, link_a, link_b, link_n, min_overlap=0.0):
         """The connected components of a ring graph (K23, xc_ring_tracks_dev): ring_step int32 (nring,), ring_size int64 (nring,) or
@@ -1753,28 +1768,28 @@ class Context(object):
                 raise XContourHipError(XC_EBADARG, 'xc_ring_tracks: links without rings')
             return dict(root=np.empty(0, np.int64), track=np.empty(0, np.int64), nprev=np.empty(0, np.int32), nnext=np.empty(0, np.int32),
                         link_ok=np.empty(0, np.bool_), tracks=np.empty(0, dtype=self.TRACK_DTYPE))
+        # per ring root, track (8 bytes), nprev, nnext (4 bytes); per track four 8-byte and two 4-byte columns
+        ring_cols = [('root', np.int64), ('track', np.int64), ('nprev', np.int32), ('nnext', np.int32)]
+        dt = self.TRACK_DTYPE
+        track_cols = [(k, dt[k]) for k in ('first_ring', 'nrings', 'nsplit', 'nmerge', 'first_step', 'last_step')]
         ins = [ring_step] + ([ring_size] if ring_size is not None else []) + ([la, lb, ln] if nlink else [])
         with self._temporaries(ins, [8]) as bufs:
             dsize = bufs[1].ptr if ring_size is not None else None
             dl = [b.ptr for b in bufs[-4:-1]] if nlink else [None] * 3
             head = (self.handle, nring, nlink, bufs[0].ptr, dsize, *dl, float(min_overlap))
             dnt = bufs[-1]
-            rc = self.lib.xc_ring_tracks_dev(*head, *[None] * 5, 0, dnt.ptr, *[None] * 6)
-            if rc not in (XC_OK, 1):                             # (1: there are tracks, and no room was given)
-                self._check(rc)
-            nt = int(dnt.download((1,), np.uint64)[0])
-            # per ring root, track (8 bytes), nprev, nnext (4 bytes); link_ok; per track four 8-byte and two 4-byte columns
-            with self._temporaries([], [nring * 24, max(nlink, 1), nt * 40]) as (dring, dok, drow):
-                rat = [dring.ptr + j * nring for j in (0, 8, 16, 20)]
-                tat = [drow.ptr + j * nt for j in (0, 32, 36, 8, 16, 24)]          # in the entry's order: first_ring, the steps, the counts
-                self._check(self.lib.xc_ring_tracks_dev(*head, *rat, dok.ptr, nt, dnt.ptr, *tat))
-                out = {k: dring.download((nring,), t, offset_bytes=p - dring.ptr)
-                       for k, t, p in zip(('root', 'track', 'nprev', 'nnext'), (np.int64, np.int64, np.int32, np.int32), rat)}
+
+            def k23(nt, outs):
+                if not outs:
+                    return self.lib.xc_ring_tracks_dev(*head, *[None] * 5, 0, dnt.ptr, *[None] * 6)
+                rat = _Columns(outs[0], nring, ring_cols).ptrs(k for k, _ in ring_cols)
+                return self.lib.xc_ring_tracks_dev(*head, *rat, outs[1].ptr, nt, dnt.ptr, *_Columns(outs[2], nt, track_cols).ptrs(dt.names))
+            sizes = lambda nt: [nring * _row_bytes(ring_cols), max(nlink, 1), nt * _row_bytes(track_cols)]       # noqa: E731
+            with self._two_pass(k23, dnt, (1,), sizes, always=True) as (_, nt, (dring, dok, drow)):
+                ring = _Columns(dring, nring, ring_cols)
+                out = {k: ring.get(k, (nring,)) for k, _ in ring_cols}
                 out['link_ok'] = dok.download((nlink,), np.uint8).astype(np.bool_)
-                rows = np.empty(nt, dtype=self.TRACK_DTYPE)
-                for k, p in zip(rows.dtype.names, tat):
-                    rows[k] = drow.download((nt,), rows.dtype[k], offset_bytes=p - drow.ptr)
-                out['tracks'] = rows
+                out['tracks'] = _Columns(drow, nt, track_cols).into(np.empty(nt, dtype=dt))
         return out
 
     def contour_piece_tracks(self, q, contours, w=None, f=None, periodic=False, flip=False, min_overlap=0.0):
@@ -1798,67 +1813,53 @@ class Context(object):
         mo = float(min_overlap)
         if not 0.0 <= mo <= 1.0:
             raise XContourHipError(XC_EBADARG, '%s: min_overlap must lie in [0, 1]' % who)
-        w, f = self._overlap_weights(who, w, f, nstep, ny, nx)
-        w_per_slab = 1 if w is not None and w.ndim == 3 else 0
-        per = ny * nx * (q.dtype.itemsize + 4 * N + (8 if w_per_slab else 0) + (f.dtype.itemsize if f is not None else 0))
-        bt = self._batches(nstep, per)
+        a = _RecordArgs(who, shape=(nstep, ny, nx), w=w, f=f)   # (a bad w or f is reported before a bad level)
+        a.plane(q, contours, periodic=periodic, min_nx=3, labels32=True)
+        bt = self._batches(nstep, a.slab_bytes(4 * N))
         slot = N * ny * nx * 4
-        maps = self.alloc((bt[0][1] - bt[0][0] + 1) * slot)
+        nb0 = bt[0][1] - bt[0][0]
         pcs, tabs, lcs, lks = [], [], [], []
-        last = None                                              # of the step before the batch: (its piece counts (1, N), its rows' permutation)
-        try:
+        last = None                                              # of the step before the batch: (its piece counts (1, N), its rows)
+        with self._temporaries([], [(nb0 + 1) * slot]) as (maps,):
             for s0, s1 in bt:
                 n = s1 - s0
                 if last is not None:                             # the map of the step before: slot n of the batch before -> slot 0
                     self.comm_wait_compute()
-                    self.comm_memcpy_d2d(maps.ptr, maps.ptr + (bt[0][1] - bt[0][0]) * slot, slot)
+                    self.comm_memcpy_d2d(maps.ptr, maps.ptr + nb0 * slot, slot)
                     self.compute_wait_comm()
-                pc, tab, perm = self._piece_records(who, True, _stack_now(q, s0, s1), _part(contours, 2, s0, s1), _part(w, 3, s0, s1),
-                                                    None if f is None else f[s0:s1], periodic, flip, labels=True,
-                                                    keep=_DeviceView(maps, slot, n * slot))
+                pc, tab, rows = self._labels_on_device(a, s0, s1, flip, _DeviceView(maps, slot, n * slot))
                 pcs.append(pc)
                 tabs.append(tab)
-                cnt = pc.astype(np.int64).reshape(n, N)
                 first = 1 if last is None else 0                 # the slot of the earlier field of the batch's first pair
-                npair = n - first
-                if npair:
-                    wp = w if not w_per_slab else w[s0 + first - 1:s1 - 1]
-                    with self._temporaries([] if wp is None else [wp], []) as bufs:
-                        lc, rows = self._overlap_rows(npair * N, ny, nx, N, maps.ptr + first * slot, maps.ptr + (first + 1) * slot,
-                                                      bufs[0].ptr if bufs else None, w_per_slab, None, 0)
+                if n - first:
+                    # K22 runs without f and with w as given -- a per-step w: the earlier step's
+                    lc, lk = self._overlap_rows((n - first) * N, ny, nx, N, maps.ptr + first * slot, maps.ptr + (first + 1) * slot,
+                                                _part(a.w, 3, s0 + first - 1, s1 - 1))
                     # the device labels are positions in each step's packed order: -> rows of the first_edge-sorted tables
-                    scnt = cnt if last is None else np.concatenate([last[0], cnt])
-                    sperm = perm if last is None else np.concatenate([last[1], perm])
-                    start = (np.cumsum(scnt.ravel()) - scnt.ravel()).reshape(scnt.shape)
-                    rng = np.repeat(np.arange(lc.size), lc.astype(np.int64))
+                    spc = pc if last is None else np.concatenate([last[0], pc])
+                    srows = rows if last is None else np.concatenate([last[1], rows])
+                    start = _scan(spc)[1].reshape(spc.shape)
+                    rng = _range_of(lc)
                     for key, j in (('a', 0), ('b', 1)):
-                        has = rows[key] >= 0
-                        at = start[rng // N + j, rng % N]
-                        rows[key][has] = sperm[at[has] + rows[key][has]]
-                    rows = self._sorted_overlap(lc, rows)
-                    lk = np.empty(rows.size, dtype=self.TRACK_LINK_DTYPE)
-                    lk['step'] = s0 + first - 1 + np.repeat(np.arange(lc.size), lc.astype(np.int64)) // N
-                    for k in ('a', 'b', 'n', 'sum_w'):
-                        lk[k] = rows[k]
-                    lcs.append(lc.reshape(npair, N))
+                        _to_rows(lk[key], start[rng // N + j, rng % N], srows)
+                    lk = _named(self._sorted_overlap(lc, lk), self.TRACK_LINK_DTYPE)
+                    lk['step'] = s0 + first - 1 + rng // N
+                    lcs.append(lc.reshape(n - first, N))
                     lks.append(lk)
-                tail = int(cnt[:-1].sum())
-                last = (cnt[-1:], perm[tail:])
-        finally:
-            maps.free()
+                last = (pc[-1:], rows[int(pc[:-1].sum()):])
         pc, tab = np.concatenate(pcs), np.concatenate(tabs)
         lc = np.concatenate(lcs) if lcs else np.zeros((0, N), dtype=np.uint64)
         links = np.concatenate(lks) if lks else np.empty(0, dtype=self.TRACK_LINK_DTYPE)
         # ring indices, level-major: all steps of level 0, then level 1, ...: base[t, k] is the first ring of range (t, k)
         cnt = pc.astype(np.int64).reshape(nstep, N)
-        base = (np.cumsum(cnt.T.ravel()) - cnt.T.ravel()).reshape(N, nstep).T
+        base = _scan(cnt.T)[1].reshape(N, nstep).T
         lvl0 = np.concatenate([base[0], [cnt.sum()]])            # where every level starts
         npiece = tab.size
-        where = np.repeat(base.ravel(), cnt.ravel()) + np.arange(npiece) - np.repeat(np.cumsum(cnt.ravel()) - cnt.ravel(), cnt.ravel())
+        where = np.repeat(base.ravel(), cnt.ravel()) + np.arange(npiece) - np.repeat(_scan(cnt)[1], cnt.ravel())
         ring_step, ring_size = np.empty(npiece, dtype=np.int32), np.empty(npiece, dtype=np.int64)
-        ring_step[where] = np.repeat(np.repeat(np.arange(nstep), N), cnt.ravel())
+        ring_step[where] = _range_of(cnt) // N
         ring_size[where] = tab['n_net']
-        lrange = np.repeat(np.arange(lc.size), lc.ravel().astype(np.int64))
+        lrange = _range_of(lc)
         lstep, llev = lrange // N, lrange % N
         la = np.where(links['a'] >= 0, base[lstep, llev] + links['a'], -1) if links.size else np.empty(0, dtype=np.int64)
         lb = np.where(links['b'] >= 0, base[np.minimum(lstep + 1, nstep - 1), llev] + links['b'], -1) if links.size else np.empty(0, dtype=np.int64)
@@ -1868,14 +1869,10 @@ class Context(object):
         trows = got['tracks']
         tlev = np.searchsorted(lvl0, trows['first_ring'], side='right') - 1
         tcount = np.bincount(tlev, minlength=N)[:N].astype(np.uint64)
-        tbase = np.cumsum(tcount.astype(np.int64)) - tcount.astype(np.int64)
         ring = np.empty(npiece, dtype=self.RING_TRACK_DTYPE)
-        rlev = np.repeat(np.tile(np.arange(N), nstep), cnt.ravel())
-        ring['track'] = got['track'][where] - tbase[rlev]
+        ring['track'] = got['track'][where] - _scan(tcount)[1][_range_of(cnt) % N]
         ring['nprev'], ring['nnext'] = got['nprev'][where], got['nnext'][where]
-        tracks = np.empty(trows.size, dtype=self.PIECE_TRACK_DTYPE)
-        for k in ('first_step', 'last_step', 'nrings', 'nsplit', 'nmerge'):
-            tracks[k] = trows[k]
+        tracks = _named(trows, self.PIECE_TRACK_DTYPE)
         tracks['first_row'] = trows['first_ring'] - base[trows['first_step'], tlev]
         return pc, tab, ring, lc, links, tcount, tracks
 

@@ -28,6 +28,7 @@ Extensions over the reference (all optional, defaults follow the snapshot):
     cal_local_wave_activity / cal_local_APE on the band walk that sums in numpy's order (`exact=True`) for every plane size.
 """
 import ctypes as C
+import types
 
 import numpy as np
 
@@ -1100,7 +1101,9 @@ class Contour2D(object):
         term is skipped, an infinite one gives NaN.  An open piece bounds nothing: nodes -1, area and integral NaN.  A NaN
         level, or a level without segments, gives an empty array.
         """
-        return self._piece_tables('cal_integral_inside_pieces', False, contours, tracer, integrand, periodic, side)
+        p = self._piece_prep('cal_integral_inside_pieces', contours, tracer, integrand, periodic, side)
+        pc, tab = self.ctx.contour_piece_interiors(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, flip=p.flip)
+        return self._ring_tables(p, pc, tab)
 
     def cal_contour_piece_tree(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
         """
@@ -1122,7 +1125,9 @@ class Contour2D(object):
         nesting of such rings reverses with it.  An open piece bounds nothing and is transparent: parent -1, depth 0, nchild
         0, nodes_net -1, NaN net sums, and it is nobody's parent.
         """
-        return self._piece_tables('cal_contour_piece_tree', True, contours, tracer, integrand, periodic, side)
+        p = self._piece_prep('cal_contour_piece_tree', contours, tracer, integrand, periodic, side)
+        pc, tab = self.ctx.contour_piece_tree(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, flip=p.flip)
+        return self._ring_tables(p, pc, tab)
 
     def cal_contour_piece_labels(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
         """
@@ -1142,7 +1147,14 @@ class Contour2D(object):
         bound nothing and never appear.  The nodes labelled p are the nodes `nodes_net`, `area_net` and `integral_net` of row p
         sum over, and depth[label] + 1 rings hold a node.  A NaN level, or a level without segments, is -1 everywhere.
         """
-        return self._piece_tables('cal_contour_piece_labels', True, contours, tracer, integrand, periodic, side, labels=True)
+        p = self._piece_prep('cal_contour_piece_labels', contours, tracer, integrand, periodic, side)
+        pc, tab, lab = self.ctx.contour_piece_labels(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, flip=p.flip)
+        c = {d: np.asarray(p.coords[d]) for d in p.lead if d in p.coords}
+        c['contour'] = np.asarray(p.ccoord)
+        c[self.dimEqV], c[self._xdim] = np.asarray(p.dcoords[self.dimEqV]), np.asarray(p.dcoords[self._xdim])
+        m = _level_order(lab, p.order[:, :, None, None])
+        dims = tuple(p.lead) + ('contour', self.dimEqV, self._xdim)
+        return self._ring_tables(p, pc, tab), lb.wrap(m.reshape(tuple(p.lshape) + m.shape[1:]), dims, c, 'labels', p.data)
 
     def cal_contour_piece_props(self, contours, fields=None, extremum=None, tracer=None, latlon=False, periodic=False, side='upper',
                                 centroid=True):
@@ -1185,8 +1197,35 @@ class Contour2D(object):
                        NaN where the moments are NaN and where the vector (m0, m1, m2), (m1, m2) or `area` is zero.
         An open piece holds nothing: NaN everywhere.  More than 8 fields (the caller's plus the moments) raise.
         """
-        return self._piece_tables('cal_contour_piece_props', True, contours, tracer, None, periodic, side,
-                                  props=dict(fields=fields, extremum=extremum, latlon=latlon, centroid=centroid))
+        who = 'cal_contour_piece_props'
+        p = self._piece_prep(who, contours, tracer, None, periodic, side)
+        q, ny, nx = p.q, p.ny, p.nx
+        user = dict(fields or {})
+        moments = self._moment_planes(p.yg, p.xg, latlon, p.period) if centroid else []
+        names_g = list(user) + ['mom%d' % k for k in range(len(moments))]
+        if len(names_g) > self.ctx.XC_PROPS_MAXF:
+            raise Exception('%s: %d fields and %d moment planes are %d, more than the %d one call takes'
+                            % (who, len(user), len(moments), len(names_g), self.ctx.XC_PROPS_MAXF))
+        planes = []
+        for v in user.values():
+            v = self._float(self._plane_of(v)[0]) if lb.is_labeled(v) else nat._f48(np.asarray(v))
+            if v.ndim == 3 and v.shape[0] == 1 and v.shape != q.shape:
+                v = v[0]
+            if v.shape not in ((ny, nx), tuple(q.shape)):
+                raise Exception('%s: a field should lie over the tracer\'s dims or over the plane\'s two dims' % who)
+            planes.append(v)
+        if extremum is None:
+            xq = q[0:p.nslab] if getattr(q, '_xc_lazy_stack', False) else q
+        elif extremum is False:
+            xq = None
+        else:
+            xq = self._float(self._plane_of(extremum)[0])
+            if xq.shape != q.shape:
+                xq = np.ascontiguousarray(np.broadcast_to(np.asarray(xq), q.shape))
+        pc, tab, pr = self.ctx.contour_piece_props(q, p.bs, w=p.dA, fields=planes + moments, x=xq, periodic=p.ring, flip=p.flip)
+        rec = self._with_props(who, self._table([tab], self._PIECE_NAMES, p.drop), pc, pr, names_g, len(user), xq is not None,
+                               p.yg, p.xg, latlon, p.period)
+        return self._in_caller_order(p.order, p.lead, self._per_range(rec, pc))[0]
 
     def cal_contour_piece_overlap(self, contours, other, other_contours=None, tracer=None, integrand=None, periodic=False,
                                   side='upper'):
@@ -1217,8 +1256,27 @@ class Contour2D(object):
         sum over both subtrees (`parent`) and is left to the caller.  A level that is NaN or without segments in both fields
         gives an empty array.
         """
-        return self._piece_tables('cal_contour_piece_overlap', True, contours, tracer, integrand, periodic, side,
-                                  overlap=(other, other_contours))
+        who = 'cal_contour_piece_overlap'
+        p = self._piece_prep(who, contours, tracer, integrand, periodic, side)
+        if not lb.is_labeled(other):
+            raise Exception('%s: other should be a labelled array over the dims of the tracer' % who)
+        qb, lead_b, lshape_b, _ = self._float_plane(self._plane_dcoords(who, other)[0])
+        if tuple(qb.shape) != tuple(p.q.shape) or list(lead_b) != list(p.lead) or list(lshape_b) != list(p.lshape):
+            raise Exception('%s: other should have the dims and the shape of the tracer' % who)
+        if other_contours is None:
+            other_contours = p.contours
+        elif type(other_contours) in [int, list]:
+            other_contours = self.cal_contours(other_contours)
+        bs_b, order_b, _ = self._sorted_levels(other_contours, p.nslab, p.lead, p.lshape)
+        if not np.array_equal(p.order, order_b):
+            # range (slab, j) pairs the j-th SORTED level of either field: they must be the same level of the caller's
+            raise Exception('%s: other_contours should ascend where contours ascend (the levels of the two fields are paired '
+                            'in the order given, and both are traced in ascending order)' % who)
+        pc, tab, pc_b, tab_b, pairs, rows = self.ctx.contour_piece_overlap(p.q, qb, p.bs, contours_b=bs_b, w=p.dA, f=p.g,
+                                                                           periodic=p.ring, flip=p.flip)
+        packed = [(self._table([t], self._PIECE_NAMES, p.drop), n) for t, n in ((tab, pc), (tab_b, pc_b))]
+        packed.append((self._table([rows], self._PIECE_NAMES), pairs))
+        return tuple(self._in_caller_order(p.order, p.lead, *[self._per_range(rec, n) for rec, n in packed]))
 
     def cal_contour_piece_tracks(self, contours, along, tracer=None, integrand=None, periodic=False, side='upper', min_overlap=0.0):
         """
@@ -1254,8 +1312,37 @@ class Contour2D(object):
                  `nmerge` (its rings with nprev >= 2).  A track is a connected component of the accepted links: after a merger the
                  merged rings share one track.
         """
-        return self._piece_tables('cal_contour_piece_tracks', True, contours, tracer, integrand, periodic, side,
-                                  tracks=(along, min_overlap))
+        who = 'cal_contour_piece_tracks'
+        p = self._piece_prep(who, contours, tracer, integrand, periodic, side)
+        lead, lshape, order, nslab = p.lead, p.lshape, p.order, p.nslab
+        if along not in lead:
+            raise Exception('%s: along should name a leading dim of the tracer (one of %r), not %r' % (who, tuple(lead), along))
+        ax = list(lead).index(along)
+        # the slabs of every series, in step order: the other leading dims, flattened in the tracer's order, are the series
+        series = np.moveaxis(np.arange(nslab).reshape(tuple(lshape)), ax, -1).reshape(-1, lshape[ax])
+        if (order[series] != order[series[:, :1]]).any():
+            raise Exception('%s: the levels of a series should ascend in the same order at every step (level k of one step is '
+                            'followed into level k of the next, and every step is traced in ascending order)' % who)
+        qs = p.q[0:nslab] if getattr(p.q, '_xc_lazy_stack', False) else p.q
+        N = order.shape[1]
+        trees, links, rows = [None] * (nslab * N), [], []
+        for sl in series:
+            pc, tab, ring, lcount, lk, tcount, tr = self.ctx.contour_piece_tracks(
+                qs[sl], p.bs[sl], w=p.dA[sl] if p.dA.ndim == 3 else p.dA, f=None if p.g is None else p.g[sl], periodic=p.ring, flip=p.flip,
+                min_overlap=min_overlap)
+            by_step = self._per_range(self._table([tab, ring], self._PIECE_NAMES, p.drop), pc)
+            for t, s in enumerate(sl.tolist()):
+                trees[s * N:(s + 1) * N] = by_step[t * N:(t + 1) * N]
+            ov = self._table([lk], self._PIECE_NAMES)
+            by_range = self._per_range(ov, lcount)               # packed by (step, level): a level's ranges, joined, are sorted by step
+            per_level = [np.concatenate(by_range[j::N]) if by_range else ov[:0].copy() for j in range(N)]
+            where = order[sl[0]].tolist()                        # j: the sorted level; where[j]: where the caller put it
+            for vals, out in ((per_level, links), (self._per_range(tr, tcount), rows)):
+                out.append([None] * N)
+                for j, k in enumerate(where):
+                    out[-1][k] = vals[j]
+        tree = self._in_caller_order(order, lead, trees)[0]
+        return (tree, links[0], rows[0]) if len(lead) == 1 else (tree, links, rows)
 
     @staticmethod
     def _moment_planes(yg, xg, latlon, period):
@@ -1324,151 +1411,65 @@ class Contour2D(object):
             v[par], at[par], key[par], has[par] = v[best], at[best], key[best], True
         return v, at
 
-    def _piece_tables(self, who, tree, contours, tracer, integrand, periodic, side, labels=False, props=None, overlap=None, tracks=None):
-        """cal_integral_inside_pieces, with `tree` cal_contour_piece_tree, with `labels` too cal_contour_piece_labels, with
-        `props` cal_contour_piece_props, with `overlap` = (other, other_contours) cal_contour_piece_overlap, and with `tracks` =
-        (along, min_overlap) cal_contour_piece_tracks: one validation, one staging, one entry each"""
+    def _piece_prep(self, who, contours, tracer, integrand, periodic, side):
+        """what the six cal_*piece* methods do before their own call: contours from an int or list, `side`, the plane and its
+        coordinates, the period (at least three columns on a ring), the levels sorted, dA as a plane, the integrand, `flip`.
+        Returns them together: contours, data, dcoords, yg, xg, period, ring, q, lead, lshape, coords, nslab, ny, nx, bs, order,
+        ccoord, dA, g, flip, and `drop`: the fields of the ring tables that an absent integrand leaves out"""
+        p = types.SimpleNamespace()
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
+        p.contours = contours
         if side not in ('upper', 'lower'):
             raise Exception('%s: side should be \'upper\' or \'lower\', not %r' % (who, side))
-        data, dcoords = self._plane_dcoords(who, tracer)
-        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
-        ring = self._x_period(periodic, xg, False, who, plain=True) is not None
-        q, lead, lshape, coords = self._float_plane(data)
-        nslab, ny, nx = q.shape
-        if ring and nx < 3:
+        p.data, p.dcoords = self._plane_dcoords(who, tracer)
+        p.yg, p.xg = (np.asarray(p.dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
+        p.period = self._x_period(periodic, p.xg, False, who, plain=True)
+        p.ring = p.period is not None
+        p.q, p.lead, p.lshape, p.coords = self._float_plane(p.data)
+        p.nslab, p.ny, p.nx = p.q.shape
+        if p.ring and p.nx < 3:
             raise Exception('%s: periodic needs at least three columns along the periodic dim' % who)
-        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
-        dA = self._dA_array(ny, nx, nslab)[0]
-        if dA.ndim == 1:
-            dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
-        g = None
+        p.bs, p.order, p.ccoord = self._sorted_levels(contours, p.nslab, p.lead, p.lshape)
+        p.dA = self._dA_array(p.ny, p.nx, p.nslab)[0]
+        if p.dA.ndim == 1:
+            p.dA = np.ascontiguousarray(np.broadcast_to(p.dA[:, None], (p.ny, p.nx)))
+        p.g = None
         if integrand is not None:
-            g = self._integrand_plane(integrand)
-            if g.shape != q.shape:
-                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
-        ascends = yg.size < 2 or yg[-1] >= yg[0]
-        flip = (side == 'upper') != bool(ascends)
-        if props is not None:
-            period = self._x_period(periodic, xg, False, who, plain=True)
-            user = dict(props['fields'] or {})
-            moments = self._moment_planes(yg, xg, props['latlon'], period) if props['centroid'] else []
-            names_g = list(user) + ['mom%d' % k for k in range(len(moments))]
-            if len(names_g) > self.ctx.XC_PROPS_MAXF:
-                raise Exception('%s: %d fields and %d moment planes are %d, more than the %d one call takes'
-                                % (who, len(user), len(moments), len(names_g), self.ctx.XC_PROPS_MAXF))
-            planes = []
-            for v in user.values():
-                v = self._float(self._plane_of(v)[0]) if lb.is_labeled(v) else nat._f48(np.asarray(v))
-                if v.ndim == 3 and v.shape[0] == 1 and v.shape != q.shape:
-                    v = v[0]
-                if v.shape not in ((ny, nx), tuple(q.shape)):
-                    raise Exception('%s: a field should lie over the tracer\'s dims or over the plane\'s two dims' % who)
-                planes.append(v)
-            ext = props['extremum']
-            if ext is None:
-                xq = q[0:nslab] if getattr(q, '_xc_lazy_stack', False) else q
-            elif ext is False:
-                xq = None
-            else:
-                xq = self._float(self._plane_of(ext)[0])
-                if xq.shape != q.shape:
-                    xq = np.ascontiguousarray(np.broadcast_to(np.asarray(xq), q.shape))
-            pc, tab, pr = self.ctx.contour_piece_props(q, bs, w=dA, fields=planes + moments, x=xq, periodic=ring, flip=flip)
-            lab = []
-        elif overlap is not None:
-            other, ocontours = overlap
-            if not lb.is_labeled(other):
-                raise Exception('%s: other should be a labelled array over the dims of the tracer' % who)
-            qb, lead_b, lshape_b, _ = self._float_plane(self._plane_dcoords(who, other)[0])
-            if tuple(qb.shape) != tuple(q.shape) or list(lead_b) != list(lead) or list(lshape_b) != list(lshape):
-                raise Exception('%s: other should have the dims and the shape of the tracer' % who)
-            if ocontours is None:
-                ocontours = contours
-            elif type(ocontours) in [int, list]:
-                ocontours = self.cal_contours(ocontours)
-            bs_b, order_b, _ = self._sorted_levels(ocontours, nslab, lead, lshape)
-            if not np.array_equal(order, order_b):
-                # range (slab, j) pairs the j-th SORTED level of either field: they must be the same level of the caller's
-                raise Exception('%s: other_contours should ascend where contours ascend (the levels of the two fields are paired '
-                                'in the order given, and both are traced in ascending order)' % who)
-            pc, tab, pc_b, tab_b, pairs, rows = self.ctx.contour_piece_overlap(q, qb, bs, contours_b=bs_b, w=dA, f=g, periodic=ring,
-                                                                               flip=flip)
-        elif tracks is not None:
-            along, min_overlap = tracks
-            if along not in lead:
-                raise Exception('%s: along should name a leading dim of the tracer (one of %r), not %r' % (who, tuple(lead), along))
-            ax = list(lead).index(along)
-            # the slabs of every series, in step order: the other leading dims, flattened in the tracer's order, are the series
-            series = np.moveaxis(np.arange(nslab).reshape(tuple(lshape)), ax, -1).reshape(-1, lshape[ax])
-            if (order[series] != order[series[:, :1]]).any():
-                raise Exception('%s: the levels of a series should ascend in the same order at every step (level k of one step is '
-                                'followed into level k of the next, and every step is traced in ascending order)' % who)
-            qs = q[0:nslab] if getattr(q, '_xc_lazy_stack', False) else q
-            runs = [self.ctx.contour_piece_tracks(qs[sl], bs[sl], w=dA[sl] if dA.ndim == 3 else dA, f=None if g is None else g[sl],
-                                                  periodic=ring, flip=flip, min_overlap=min_overlap) for sl in series]
-        else:
-            call = self.ctx.contour_piece_labels if labels else self.ctx.contour_piece_tree if tree else self.ctx.contour_piece_interiors
-            pc, tab, *lab = call(q, bs, w=dA, f=g, periodic=ring, flip=flip)
-        names = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net', 'net_wf': 'integral_net'}
+            p.g = self._integrand_plane(integrand)
+            if p.g.shape != p.q.shape:
+                p.g = np.ascontiguousarray(np.broadcast_to(np.asarray(p.g), p.q.shape))
+        ascends = p.yg.size < 2 or p.yg[-1] >= p.yg[0]
+        p.flip = (side == 'upper') != bool(ascends)
+        p.drop = () if p.g is not None else ('sum_wf', 'net_wf')
+        return p
 
-        def named(tab):
-            fields = [(names.get(f, f), tab.dtype[f]) for f in tab.dtype.names if f not in ('sum_wf', 'net_wf') or g is not None]
-            rec = np.empty(tab.size, dtype=fields)
-            for f in tab.dtype.names:
-                if names.get(f, f) in rec.dtype.names:
-                    rec[names.get(f, f)] = tab[f]
-            return rec
+    # the fields of the library's tables under the names this class returns them by
+    _PIECE_NAMES = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net',
+                    'net_wf': 'integral_net', 'n': 'nodes'}
 
-        def per_range(rec, counts):
-            poff = np.concatenate([[0], np.cumsum(counts.ravel().astype(np.int64))])
-            return [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])]
-        if tracks is not None:
-            N = order.shape[1]
-            trees, links, rows = [None] * (nslab * N), [], []
-            for sl, (pc, tab, ring, lcount, lk, tcount, tr) in zip(series, runs):
-                rec = named(tab)
-                full = np.empty(rec.size, dtype=rec.dtype.descr + ring.dtype.descr)
-                for src in (rec, ring):
-                    for f in src.dtype.names:
-                        full[f] = src[f]
-                for t, s in enumerate(sl.tolist()):
-                    trees[s * N:(s + 1) * N] = per_range(full, pc)[t * N:(t + 1) * N]
-                ov = np.empty(lk.size, dtype=[('step', np.int32), ('a', np.int32), ('b', np.int32), ('nodes', np.int64), ('area', np.float64),
-                                              ('linked', np.bool_)])
-                for k, f in (('step', 'step'), ('a', 'a'), ('b', 'b'), ('nodes', 'n'), ('area', 'sum_w'), ('linked', 'linked')):
-                    ov[k] = lk[f]
-                by_range = per_range(ov, lcount)                 # packed by (step, level): a level's ranges, joined, are sorted by step
-                per_level = [np.concatenate(by_range[j::N]) if by_range else ov[:0].copy() for j in range(N)]
-                where = order[sl[0]].tolist()                    # j: the sorted level; where[j]: where the caller put it
-                for vals, out in ((per_level, links), (per_range(tr, tcount), rows)):
-                    out.append([None] * N)
-                    for j, k in enumerate(where):
-                        out[-1][k] = vals[j]
-            tree = self._in_caller_order(order, lead, trees)[0]
-            return (tree, links[0], rows[0]) if len(lead) == 1 else (tree, links, rows)
-        rec = named(tab)
-        poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
-        if props is not None:
-            rec = self._with_props(who, rec, poff, pr, names_g, len(user), xq is not None, yg, xg, props['latlon'], period)
-        if overlap is not None:
-            ov = np.empty(rows.size, dtype=[('a', np.int32), ('b', np.int32), ('nodes', np.int64), ('area', np.float64),
-                                            ('integral', np.float64)])
-            for k, f in (('a', 'a'), ('b', 'b'), ('nodes', 'n'), ('area', 'sum_w'), ('integral', 'sum_wf')):
-                ov[k] = rows[f]
-            return tuple(self._in_caller_order(order, lead, per_range(rec, pc), per_range(named(tab_b), pc_b), per_range(ov, pairs)))
-        tables = self._in_caller_order(order, lead, per_range(rec, pc))[0]
-        if not labels:
-            return tables
-        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
-        c['contour'] = np.asarray(ccoord)
-        c[self.dimEqV], c[self._xdim] = np.asarray(dcoords[self.dimEqV]), np.asarray(dcoords[self._xdim])
-        m = _level_order(lab[0], order[:, :, None, None])
-        dims = tuple(lead) + ('contour', self.dimEqV, self._xdim)
-        return tables, lb.wrap(m.reshape(tuple(lshape) + m.shape[1:]), dims, c, 'labels', data)
+    @staticmethod
+    def _table(srcs, names=None, drop=(), more=()):
+        """one structured array with the fields of `srcs` (structured arrays of one length) side by side -- renamed through `names`,
+        without those of `drop` --, then the fields `more` = [(name, dtype), ...], which are left to the caller to fill"""
+        names = names or {}
+        keep = [(s, f) for s in srcs for f in s.dtype.names if f not in drop]
+        out = np.empty(srcs[0].size, dtype=[(names.get(f, f), s.dtype[f]) for s, f in keep] + list(more))
+        for s, f in keep:
+            out[names.get(f, f)] = s[f]
+        return out
 
-    def _with_props(self, who, rec, poff, pr, names_g, nuser, has_x, yg, xg, latlon, period):
+    @staticmethod
+    def _per_range(rec, counts):
+        """records packed range by range, `counts` of them in each -> a list with every range's own array"""
+        poff = np.concatenate([[0], np.cumsum(counts.ravel().astype(np.int64))])
+        return [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])]
+
+    def _ring_tables(self, p, pc, tab):
+        """the packed table of a ring call under this class's field names -> nested per level, in the caller's order"""
+        return self._in_caller_order(p.order, p.lead, self._per_range(self._table([tab], self._PIECE_NAMES, p.drop), pc))[0]
+
+    def _with_props(self, who, rec, pc, pr, names_g, nuser, has_x, yg, xg, latlon, period):
         """the packed table of cal_contour_piece_tree with K21's columns beside it (cal_contour_piece_props names them)"""
         nx = xg.size
         cols = []
@@ -1476,8 +1477,8 @@ class Contour2D(object):
             cols += [(name, pr['gross'][:, m]), (name + '_net', pr['net'][:, m])]
         if has_x:
             # parent is a row of the piece's own range: -> a row of the packed table
-            start = np.repeat(poff[:-1], np.diff(poff))
-            gpar = np.where(rec['parent'] >= 0, rec['parent'] + start, -1)
+            c, start = nat._scan(pc)
+            gpar = np.where(rec['parent'] >= 0, rec['parent'] + np.repeat(start, c), -1)
             ext = {'vmin_net': (pr['x_min'], pr['at_min']), 'vmax_net': (pr['x_max'], pr['at_max']),
                    'vmin': self._gross_extrema(gpar, rec['depth'], pr['x_min'], pr['at_min'], False),
                    'vmax': self._gross_extrema(gpar, rec['depth'], pr['x_max'], pr['at_max'], True)}
@@ -1496,9 +1497,7 @@ class Contour2D(object):
             if name in taken:
                 raise Exception('%s: the field name %r is taken' % (who, name))
             taken.add(name)
-        out = np.empty(rec.size, dtype=rec.dtype.descr + [(name, np.float64) for name, _ in cols])
-        for name in rec.dtype.names:
-            out[name] = rec[name]
+        out = self._table([rec], more=[(name, np.float64) for name, _ in cols])
         for name, v in cols:
             out[name] = v
         return out
