@@ -9,6 +9,8 @@ import math
 
 import numpy as np
 
+import cinside_ref as IR
+
 DTYPE = np.dtype([('a', np.int32), ('b', np.int32), ('n', np.int64), ('sum_w', np.float64), ('sum_wf', np.float64)])
 
 
@@ -20,22 +22,29 @@ def terms(w, f, shape):
     return tw, tf
 
 
-def exact(v):
-    """K17's sum of the terms v: NaN terms skipped, an infinite term gives NaN, else the exact sum rounded once"""
+def exact(v, top=None):
+    """K17's sum of the terms v: NaN terms skipped, an infinite term gives NaN, else the exact sum rounded once -- of the terms as they are
+    (top None: every term lies wholly inside its window), or of the terms cut in the window under 2^top (cinside_ref.window_sum)"""
+    if top is not None:
+        return IR.window_sum(v, top)
     v = v[~np.isnan(v)]
     return math.nan if np.isinf(v).any() else math.fsum(v.tolist())
 
 
-def rows_of(table):
-    """{(a, b): (n, [terms of w], [terms of w f] or None)} -> the sorted rows"""
+def rows_of(table, tops=None):
+    """{(a, b): (n, [terms of w], [terms of w f] or None)} -> the sorted rows.  tops: (top_w, top_f) of the range's slab"""
+    top_w, top_f = (None, None) if tops is None else tops
     out = np.empty(len(table), dtype=DTYPE)
     for i, (a, b) in enumerate(sorted(table)):
         n, tw, tf = table[(a, b)]
-        out[i] = (a, b, n, exact(np.asarray(tw, dtype=np.float64)), math.nan if tf is None else exact(np.asarray(tf, dtype=np.float64)))
+        out[i] = (a, b, n, exact(np.asarray(tw, dtype=np.float64), top_w),
+                  math.nan if tf is None else exact(np.asarray(tf, dtype=np.float64), top_f))
     return out
 
 
-def overlap_of_maps(la, lb, w=None, f=None):
+def overlap_of_maps(la, lb, w=None, f=None, tops=None):
+    """tops: the windows (top_w, top_f) of the range's slab -- cinside_ref.window_tops of the slab's WHOLE plane, the nodes of the omitted
+    pair (-1, -1) included; None: no term is cut (every existing case keeps its terms wholly inside the window)"""
     la, lb = np.asarray(la), np.asarray(lb)
     a = np.where(la < 0, -1, la).astype(np.int64).ravel()
     b = np.where(lb < 0, -1, lb).astype(np.int64).ravel()
@@ -49,7 +58,7 @@ def overlap_of_maps(la, lb, w=None, f=None):
             continue
         at = np.flatnonzero(inv == i)
         table[(pa, pb)] = (at.size, tw[at], None if tf is None else tf[at])
-    return rows_of(table)
+    return rows_of(table, tops)
 
 
 def scan_of_maps(la, lb, w=None, f=None, chunk=16, broken=None):
@@ -166,7 +175,7 @@ def cases():
     a, b = np.full((40, 9), -1, dtype=np.int32), np.full((40, 9), -1, dtype=np.int32)
     a[3:5, 4], b[3:5, 4] = 1, 7
     out['one short run'] = (a, b, None, None)
-    # weights over 2^+-40 with cancellation: inside the 160-bit window
+    # weights over 2^+-40 with cancellation: inside the 160-bit window (its edges: test_gpu_ring_sums.py, on ring_sums_cases.py)
     a, b = blobs(rng, 33, 64, 4), blobs(rng, 33, 64, 3)
     w = scaled(rng, a.shape, spread=40)
     w[:, 1::2] = -w[:, 0::2]

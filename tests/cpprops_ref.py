@@ -39,8 +39,11 @@ def order_key(v):
     return (~b) & (2 ** 64 - 1) if b >> 63 else b | (1 << 63)
 
 
-def exact_sum(terms):
-    """math.fsum of the terms that are not NaN; NaN when one is infinite"""
+def exact_sum(terms, top=None):
+    """math.fsum of the terms that are not NaN; NaN when one is infinite.  top: the terms are first cut in the window under 2^top
+    (cinside_ref.window_sum)"""
+    if top is not None:
+        return TR.IR.window_sum(np.asarray(terms, dtype=np.float64), top)
     t = [float(v) for v in terms if v == v]
     return float('nan') if any(math.isinf(v) for v in t) else math.fsum(t)
 
@@ -53,7 +56,8 @@ def _planes(r, ncont, ny, nx, w, fields, x):
     prods = []
     for g in fields:
         g = np.asarray(g)
-        prods.append(wp * (g[s] if g.ndim == 3 else g).astype(np.float64))
+        with np.errstate(all='ignore'):
+            prods.append(wp * (g[s] if g.ndim == 3 else g).astype(np.float64))
     return prods, (None if x is None else np.asarray(x)[s].astype(np.float64))
 
 
@@ -80,7 +84,16 @@ def _empty(n, nf, has_x):
     return out
 
 
-def piece_props(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, w=None, fields=(), x=None):
+def field_tops(w, fields, nslab, ny, nx, bound=TR.IR.finite_bound):
+    """-> per slab the list of the tops of the nf windows: field m's is cinside_ref.window_tops' top of w g_m -- the bound taken over the
+    finite products of the slab's whole plane -- one window per (slab, field)"""
+    per_field = [TR.IR.window_tops(w, np.broadcast_to(np.asarray(g), (nslab, ny, nx)), nslab, ny, nx, bound) for g in fields]
+    return [[t[s][1] for t in per_field] for s in range(nslab)]
+
+
+def piece_props(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, w=None, fields=(), x=None, tops=None):
+    """tops: per slab the tops of the nf windows (field_tops) the net and gross sums are cut in; None: no term is cut (every term of the
+    records suites lies wholly inside its window)"""
     tables, masks = TR.piece_tree(count, e_from, e_to, pts, ny, nx, periodic, flip=flip, ncont=ncont, w=w, return_masks=True)
     ncont = len(tables) if ncont is None else int(ncont)
     props = []
@@ -92,7 +105,8 @@ def piece_props(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, 
             if m is None:
                 continue
             for k, pr in enumerate(prods):
-                out['net'][p, k], out['gross'][p, k] = exact_sum(pr[lab == p]), exact_sum(pr[m])
+                top = None if tops is None else tops[r // ncont][k]
+                out['net'][p, k], out['gross'][p, k] = exact_sum(pr[lab == p], top), exact_sum(pr[m], top)
             if xp is not None:
                 nodes = np.flatnonzero(lab.ravel() == p)
                 (out['x_min'][p], out['at_min'][p]), (out['x_max'][p], out['at_max'][p]) = _extremum(xp, nodes, False), _extremum(xp, nodes, True)

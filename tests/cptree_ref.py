@@ -4,8 +4,8 @@ for the tests, no tests here.  Input as for cpinside_ref.piece_interiors, on whi
 piece_tree(): brute force on sets, deliberately NOT the kernel's walk.  Per range the inside set of every ring is cpinside_ref's bool
 mask.  a encloses b iff mask_b is a subset of mask_a (asserted on the way: two rings are nested or disjoint, and no two rings have the
 same set); the parent is the enclosing ring of smallest cardinality; depth and nchild follow; the net set is the ring's mask minus its
-children's masks; the net sums are cpinside_ref's sums (cinside_ref.window_sum: math.fsum of the terms in K18's window, each product
-rounded once, NaN terms dropped) over the net set, NaN exactly where the gross sum is NaN.  Open pieces: parent -1, depth 0, nchild 0,
+children's masks; the net sums are cpinside_ref's sums (cinside_ref.window_sum: math.fsum of the terms in K18's window -- the slab's, or
+the `tops` handed in -- each product rounded once, NaN terms dropped) over the net set, NaN exactly where the gross sum is NaN.  Open pieces: parent -1, depth 0, nchild 0,
 n_net -1, NaN net sums.  Returns per range a structured array (DTYPE) sorted by first_edge, `parent` a row of that array."""
 import numpy as np
 
@@ -51,10 +51,11 @@ def tree_of_masks(masks):
     return parent, depth, nchild
 
 
-def piece_tree(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, w=None, f=None, return_masks=False):
-    """-> per range a DTYPE array sorted by first_edge[, per range the list of inside masks in the same order]"""
+def piece_tree(count, e_from, e_to, pts, ny, nx, periodic, flip=0, ncont=None, w=None, f=None, return_masks=False, tops=None):
+    """-> per range a DTYPE array sorted by first_edge[, per range the list of inside masks in the same order].  `tops`: per slab the
+    windows (top_w, top_f) to use instead of cinside_ref.window_tops' -- gross and net sums are cut in the same ones"""
     tables, masks, tops = PR.piece_interiors(count, e_from, e_to, pts, ny, nx, periodic, flip=flip, ncont=ncont, w=w, f=f,
-                                             return_masks=True, return_tops=True)
+                                             return_masks=True, return_tops=True, tops=tops)
     ncont = len(tables) if ncont is None else int(ncont)
     out = []
     for r, (t, ms) in enumerate(zip(tables, masks)):

@@ -80,15 +80,17 @@ def rows(ctx, la, lb, ncont=1, w=None, f=None, cap=None):
     return out, prof['groups']
 
 
-def reference(la, lb, ncont=1, w=None, f=None):
+def reference(la, lb, ncont=1, w=None, f=None, tops=None):
+    """tops: per slab the windows (top_w, top_f) the sums are cut in (None: no term is cut)"""
     la, lb = np.asarray(la), np.asarray(lb)
     return [OR.overlap_of_maps(la[r], lb[r], None if w is None else (w[r // ncont] if np.ndim(w) == 3 else w),
-                               None if f is None else f[r // ncont]) for r in range(la.shape[0])]
+                               None if f is None else f[r // ncont], tops=None if tops is None else tops[r // ncont])
+            for r in range(la.shape[0])]
 
 
-def check(ctx, la, lb, ncont=1, w=None, f=None, cap=None, what=''):
+def check(ctx, la, lb, ncont=1, w=None, f=None, cap=None, what='', tops=None):
     got, groups = rows(ctx, la, lb, ncont, w, f, cap)
-    ref = reference(la, lb, ncont, w, f)
+    ref = reference(la, lb, ncont, w, f, tops)
     for r, (g, t) in enumerate(zip(got, ref)):
         assert OR.same(g, t), '%s range %d' % (what, r)
         for key, m in (('a', la[r]), ('b', lb[r])):                          # the marginals: np.bincount of the map

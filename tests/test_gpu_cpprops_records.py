@@ -1,7 +1,8 @@
 """xc_contour_piece_props_dev (K21), the C entry on host records, against cpprops_ref.piece_props (sets of nodes and math.fsum, not the
 kernel's scan): every place equal, every sum and extremum equal BIT FOR BIT, and K19's thirteen columns equal byte for byte to what
 xc_contour_piece_tree_dev writes on the same records.  No tolerances.  The records are hand-built as in test_gpu_cplabel_records.py.  Weights
-and fields come from `scaled` (exponents in [-20, 20]): every term lies wholly inside its 160-bit window, so the rule is plain math.fsum.
+and fields come from `scaled` (exponents in [-20, 20]): every term lies wholly inside its 160-bit window; the windows' edges, the window per
+(slab, field), the wave sums and the fold at full mantissas are pinned in test_gpu_ring_sums.py.
 Every call hands the entry its outputs filled with a pattern and followed by guard elements: on XC_OK nothing is written behind the
 pieces of any column, on 1 or a refusal nothing but piece_count is touched."""
 import numpy as np
@@ -117,9 +118,9 @@ def results(ctx, rec, ny, nx, periodic, flip, ncont, cap=None, **kw):
     return tabs, props, groups
 
 
-def check(ctx, rec, ny, nx, periodic, flip, ncont, what='', cap=None, w=None, fields=(), x=None):
+def check(ctx, rec, ny, nx, periodic, flip, ncont, what='', cap=None, w=None, fields=(), x=None, tops=None):
     tabs, props, _ = results(ctx, rec, ny, nx, periodic, flip, ncont, cap=cap, w=w, fields=fields, x=x)
-    ref, rprops = QR.piece_props(*rec[:4], ny, nx, periodic, flip=flip, ncont=ncont, w=w, fields=fields, x=x)
+    ref, rprops = QR.piece_props(*rec[:4], ny, nx, periodic, flip=flip, ncont=ncont, w=w, fields=fields, x=x, tops=tops)
     assert len(tabs) == len(ref)
     for r, (g, t, p, q) in enumerate(zip(tabs, ref, props, rprops)):
         where = '%s (periodic %d, flip %d) range %d' % (what, periodic, flip, r)

@@ -2,7 +2,8 @@
 integer fields equal, the four sums equal to the header's rule BIT FOR BIT, and K18's seven fields equal to what
 xc_contour_piece_interiors_dev writes on the same records.  No tolerances.  The records are hand-built as in
 test_gpu_cpinside_records.py: the restatements of K12 trace the planes of cptree_cases and noise, stored in a shuffled order.  Weights and
-integrands have exponents in [-20, 20], so every term lies wholly inside its window and the rule is plain math.fsum (asserted below).
+integrands have exponents in [-20, 20], so every term lies wholly inside its window (asserted below); the windows' edges, the cut at the
+floor and the windows per slab are pinned in test_gpu_ring_sums.py.
 Every call hands the entry output arrays filled with a pattern and followed by guard elements: on XC_OK the records are written and
 every guard intact, on 1 or a refusal nothing but piece_count is touched."""
 import numpy as np
@@ -84,9 +85,9 @@ def tables(ctx, rec, ny, nx, periodic, flip, ncont, cap=None, **kw):
     return out, groups
 
 
-def check(ctx, rec, ny, nx, periodic, flip, ncont, what='', cap=None, w=None, f=None):
+def check(ctx, rec, ny, nx, periodic, flip, ncont, what='', cap=None, w=None, f=None, tops=None):
     got, _ = tables(ctx, rec, ny, nx, periodic, flip, ncont, cap=cap, w=w, f=f)
-    ref = TR.piece_tree(*rec[:4], ny, nx, periodic, flip=flip, ncont=ncont, w=w, f=f)
+    ref = TR.piece_tree(*rec[:4], ny, nx, periodic, flip=flip, ncont=ncont, w=w, f=f, tops=tops)
     assert len(got) == len(ref)
     for r, (g, t) in enumerate(zip(got, ref)):
         bad = TR.differences(g, t)
