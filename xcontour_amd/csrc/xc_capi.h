@@ -23,11 +23,14 @@ inline size_t dA_bytes(int rank, int64_t nslab, int64_t ny, int64_t nx)
 
 // Where the time of one launcher call goes (xc_set_kernel_timing): an event between its stages, and after the call the time between two
 // marks added to ms[kind of the later mark].  Nothing happens without ctx->timing; kind -1 opens an interval without booking it; an event
-// call that fails is ignored.
+// call that fails is ignored.  The times are booked and the events destroyed when the timer goes out of scope, on whichever return: an
+// interval whose events have not completed by then (a call that fails before its last wait) books nothing.
 struct StageTimer {
     xc_ctx* ctx; float* ms;
     std::vector<std::pair<hipEvent_t, int>> marks;
     StageTimer(xc_ctx* c, float* m) : ctx(c), ms(m) {}
+    StageTimer(const StageTimer&) = delete;
+    StageTimer& operator=(const StageTimer&) = delete;
     void mark(int kind)
     {
         if (!ctx->timing) return;
@@ -36,14 +39,17 @@ struct StageTimer {
         (void)hipEventRecord(ev, ctx->stream);
         marks.push_back({ev, kind});
     }
-    void settle()
+    ~StageTimer()
     {
+        bool pending = false;
         for (size_t k = 1; k < marks.size(); ++k) {
             float t = 0.f;
-            if (marks[k].second >= 0 && hipEventElapsedTime(&t, marks[k - 1].first, marks[k].first) == hipSuccess) ms[marks[k].second] += t;
+            if (marks[k].second < 0) continue;
+            if (hipEventElapsedTime(&t, marks[k - 1].first, marks[k].first) == hipSuccess) ms[marks[k].second] += t;
+            else pending = true;
         }
+        if (pending) (void)hipGetLastError();                           // "not ready" is no error of the next call
         for (auto& m : marks) (void)hipEventDestroy(m.first);
-        marks.clear();
     }
 };
 

@@ -211,19 +211,11 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     const int wrap = periodic ? 1 : 0;
     const int64_t nslab = nrange / ncont;
     if (nslab > 65535) return fail(ctx, XC_EBADARG, "xc_contour_interior: more than 65535 slabs");
-    for (int k = 0; k < 4; ++k) ctx->cinterior_ms[k] = 0.f;
-    ctx->cinterior_rounds = 0; ctx->cinterior_groups = 0;
+    CpProfile& prof = ctx->prof_cinterior;
+    profile_clear(prof);
 
-    std::vector<uint64_t> hc;
-    std::vector<long long> off;
-    XC_TRY(cp_read_counts(ctx, "xc_contour_interior", nrange, count, nullptr, hc, off));
-    const long long total = off[(size_t)nrange];
-    if (total > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_interior: segments without their records");
-
-    // groups of consecutive ranges [r0, r1) (xc_cpiece_link.h); none without segments
-    int64_t gmax = 0; long long nmax = 0;
-    std::vector<CpGroup> groups;
-    if (total > 0) groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
+    CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
+    XC_TRY(cp_plan(ctx, "xc_contour_interior", nrange, count, nullptr, e_from, e_to, pts, E, pl));
     // the scan's geometry: 256 columns x rc rows x one range per block
     const int64_t wpr = (nx + 31) / 32, ncb = (nx + CI_TPB - 1) / CI_TPB;
     int64_t nchunk = (CI_BLOCKS + ncb * nrange - 1) / (ncb * nrange);
@@ -231,14 +223,14 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     const int64_t rc = (ny + nchunk - 1) / nchunk;
     nchunk = (ny + rc - 1) / rc;
     const size_t plane = (size_t)ny * (size_t)wpr;
-    // workspace: off | key, nsel, mx, acc, cnt, flg (cleared together) | err | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | tab[gmax][E]
-    //            | rid[nmax] | label, next, prev x 2 [nmax]
+    // workspace: off | key, nsel, mx, acc, cnt, flg (cleared together) | err | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | the tail
+    //            (xc_cpiece_link.h)
     const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_nsel = al((size_t)nrange * 4);
     const size_t b_mx = al((size_t)nslab * 16), b_acc = al((size_t)nrange * 2 * CP_L * 8), b_cnt = al((size_t)nrange * 8), b_flg = al((size_t)nrange * 4);
     const size_t b_zero = b_key + b_nsel + b_mx + b_acc + b_cnt + b_flg, b_small = 256;
-    const size_t b_bits = al((size_t)gmax * plane * 4), b_cpar = al((size_t)gmax * (size_t)nchunk * (size_t)wpr * 4);
-    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_zero + b_small + b_bits + b_cpar + b_tab + 7 * b_n));
+    const size_t b_bits = al((size_t)pl.gmax * plane * 4), b_cpar = al((size_t)pl.gmax * (size_t)nchunk * (size_t)wpr * 4);
+    CpTail tail;
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_zero + b_small + b_bits + b_cpar + cp_carve_tail(nullptr, pl, 6, tail)));
     char* ws = (char*)ctx->cpiece_ws;
     long long* d_off = (long long*)ws;
     unsigned long long* key = (unsigned long long*)(ws + b_off);
@@ -250,12 +242,10 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     int* d_err = (int*)((char*)flg + b_flg);
     unsigned* bits = (unsigned*)((char*)d_err + b_small);
     unsigned* cpar = (unsigned*)((char*)bits + b_bits);
-    int* tab = (int*)((char*)cpar + b_cpar);
-    int* rid = (int*)((char*)tab + b_tab);
-    int* buf[6];
-    for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+    cp_carve_tail((char*)cpar + b_cpar, pl, 6, tail);
 
-    StageTimer tm(ctx, ctx->cinterior_ms);                                      // where the time goes (xc_set_kernel_timing)
+    StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
+    CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
 
     const dim3 blk(CP_TPB);
     const int64_t npl = ny * nx;
@@ -283,43 +273,24 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         XC_HIP(ctx, hipGetLastError());
     }
     tm.mark(3);
-    if (total > 0) {
-        XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
-    }
+    XC_TRY(run.upload_off());
+    XC_TRY(run.fill_table());
     tm.mark(0);
-    int rounds_total = 0;
     int64_t done = 0;                                                       // the ranges scanned so far
-    for (const CpGroup& g : groups) {
-        const long long s0 = off[(size_t)g.r0];
-        const int64_t n = off[(size_t)g.r1] - s0, ng = g.r1 - g.r0;
-        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
-        const dim3 grid(cp_blocks(n));
+    for (const CpGroup& g : pl.groups) {
+        const int64_t ng = g.r1 - g.r0;
         XC_HIP(ctx, hipMemsetAsync(bits, 0, (size_t)ng * plane * 4, ctx->stream));
         tm.mark(3);
-        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
-        b = cp_launch_rounds(ctx->stream, n, R, b);
-        XC_HIP(ctx, hipGetLastError());
-        rounds_total += R;
-        tm.mark(1);
-        // lab, prv: the labels and the ring marks; nxt, lab2, nxt2 are free from here on
-        int* root = b.nxt;
-        unsigned* pn = (unsigned*)b.lab2;
-        int* pw = b.nxt2;
-        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, root, pn, pw);
-        hipLaunchKernelGGL(k_co_piece, grid, blk, 0, ctx->stream, n, s0, wrap, nx, pts, root, pn, pw);
-        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, b.prv, b.lab, pn, pw, nsel, key);
+        run.begin(g);
+        XC_TRY(run.rounds());
+        const CoRoles s = co_launch_select(run, wrap, nx, pts, select, nsel, key);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(2);
-        hipLaunchKernelGGL(k_ci_mark, grid, blk, 0, ctx->stream, n, s0, g.r0, E, nx, wpr, plane, select, (const long long*)e_from,
-                           (const long long*)e_to, tab, rid, root, b.prv, b.lab, pn, pw, key, bits);
+        hipLaunchKernelGGL(k_ci_mark, run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, nx, wpr, plane, select, run.e_from, run.e_to,
+                           tail.tab, tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key, bits);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(3);
-        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
+        XC_TRY(run.end());
         if (nchunk > 1) {
             const int64_t nwords = ng * nchunk * wpr;
             hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, bits, cpar);
@@ -330,14 +301,12 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         tm.mark(3);
     }
     if (done < nrange) XC_TRY(scan(done, nrange, 0, 0));
-    ctx->cinterior_rounds = rounds_total; ctx->cinterior_groups = (int)groups.size();
+    run.report(prof);
     hipLaunchKernelGGL(k_ci_finish, dim3(cp_blocks(nrange)), blk, 0, ctx->stream, nrange, ncont, acc, cnt, flg, mx, (long long*)n_in, sum_w, sum_wf);
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
     int herr = 0;
-    XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    tm.settle();
+    XC_TRY(cp_read_err(ctx, d_err, &herr));
     if (herr) return fail(ctx, XC_EBADARG, "xc_contour_interior: an edge id outside [0, 2 ny nx)");
     return XC_OK;
 }
@@ -356,9 +325,5 @@ int xc_contour_interior_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
 
 int xc_last_cinterior_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = (double)ctx->cinterior_ms[k];
-    if (rounds) *rounds = ctx->cinterior_rounds;
-    if (groups) *groups = ctx->cinterior_groups;
-    return XC_OK;
+    return xc::profile_get(ctx, &xc_ctx::prof_cinterior, 4, ms, rounds, groups);
 }

@@ -285,26 +285,23 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
         return fail(ctx, XC_EBADARG, "xc_contour_polylines: capacity > 0 needs the polyline arrays");
     if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_polylines: plane too large for 32-bit labels (2 ny nx < 2^31)");
     const long long E = 2 * ny * nx;
-    for (int k = 0; k < CJ_STAGES; ++k) ctx->cjoin_ms[k] = 0.f;
-    ctx->cjoin_rounds = 0; ctx->cjoin_groups = 0;
+    CpProfile& prof = ctx->prof_cjoin;
+    profile_clear(prof);
 
-    std::vector<uint64_t> hc;
-    std::vector<long long> off;
-    XC_TRY(cp_read_counts(ctx, "xc_contour_polylines", nrange, count, poly_count, hc, off));
-    const long long total = off[(size_t)nrange];
+    CpPlan pl;
+    XC_TRY(cp_plan(ctx, "xc_contour_polylines", nrange, count, poly_count, e_from, e_to, pts, E, pl));
+    const long long total = pl.total;
     if (total == 0) return XC_OK;
-    if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, "xc_contour_polylines: segments without their records");
 
-    int64_t gmax = 1; long long nmax = 0;
-    const std::vector<CpGroup> groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
     const int64_t nchunk = (E + CJ_CHUNK - 1) / CJ_CHUNK;
-    if (gmax > (((int64_t)1 << 31) - 1) / nchunk)
+    if (pl.gmax > (((int64_t)1 << 31) - 1) / nchunk)
         return fail(ctx, XC_EBADARG, "xc_contour_polylines: too many ranges in one group (lower xc_set_cpiece_workspace)");
-    // workspace: off | poff | err | inv, gidx, gsz [total] | tab[gmax][E] | sums[gmax][nchunk] | rid and nine more [nmax]
+    // workspace: off | poff | err | inv, gidx, gsz [total] | sums[gmax][nchunk] | the tail with ten buffers (xc_cpiece_link.h)
     constexpr int NBUF = 10;
     const size_t b_off = al((size_t)(nrange + 1) * 8), b_small = 256, b_tot = al((size_t)total * 4);
-    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_sums = al((size_t)gmax * (size_t)nchunk * 8), b_n = al((size_t)nmax * 4);
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + 3 * b_tot + b_tab + b_sums + (NBUF + 1) * b_n));
+    const size_t b_sums = al((size_t)pl.gmax * (size_t)nchunk * 8);
+    CpTail tail;
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + 3 * b_tot + b_sums + cp_carve_tail(nullptr, pl, NBUF, tail)));
     char* ws = (char*)ctx->cpiece_ws;
     long long* d_off = (long long*)ws;
     long long* d_poff = (long long*)(ws + b_off);
@@ -312,48 +309,43 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
     int* inv = (int*)(ws + 2 * b_off + b_small);
     int* gidx = (int*)((char*)inv + b_tot);
     int* gsz = (int*)((char*)gidx + b_tot);
-    int* tab = (int*)((char*)gsz + b_tot);
-    unsigned long long* sums = (unsigned long long*)((char*)tab + b_tab);
-    int* rid = (int*)((char*)sums + b_sums);
-    int* buf[NBUF];
-    for (int k = 0; k < NBUF; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+    unsigned long long* sums = (unsigned long long*)((char*)gsz + b_tot);
+    cp_carve_tail((char*)sums + b_sums, pl, NBUF, tail);
+    int *const tab = tail.tab, *const rid = tail.rid;
 
-    StageTimer tm(ctx, ctx->cjoin_ms);                                      // where the time goes (xc_set_kernel_timing)
+    StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
+    CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
 
     tm.mark(-1);
-    XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    XC_TRY(run.upload_off());
     XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(inv, 0xff, (size_t)total * 4, ctx->stream));
-    XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
+    XC_TRY(run.fill_table());
     tm.mark(0);
-    int rounds_total = 0;
-    for (const CpGroup& g : groups) {
-        const long long s0 = off[(size_t)g.r0];
-        const int64_t n = off[(size_t)g.r1] - s0, rows = g.r1 - g.r0;
-        const int R = cp_rounds(hc, g);
-        const dim3 grid(cp_blocks(n)), blk(CP_TPB), sgrid((unsigned)(rows * nchunk));
-        int *p = buf[6], *root = buf[7];
-        unsigned* size = (unsigned*)buf[8];
-        int* pidx = buf[9];
-        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
-        hipLaunchKernelGGL(k_cj_check, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, (const long long*)e_to, tab, rid, b.nxt, b.prv, p, d_err);
-        hipLaunchKernelGGL(k_cj_unmark, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_to, tab, rid, b.nxt);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
-        b = cp_launch_rounds(ctx->stream, n, R, b);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(1);
+    for (const CpGroup& g : pl.groups) {
+        run.begin(g);
+        const long long s0 = run.s0;
+        const int64_t n = run.n, rows = g.r1 - g.r0;
+        const dim3 grid = run.grid, blk(CP_TPB), sgrid((unsigned)(rows * nchunk));
+        int *p = tail.buf[6], *root = tail.buf[7];
+        unsigned* size = (unsigned*)tail.buf[8];
+        int* pidx = tail.buf[9];
+        // behind the table, in its stage: the records are a join's input
+        hipLaunchKernelGGL(k_cj_check, grid, blk, 0, ctx->stream, n, s0, E, run.e_from, run.e_to, tab, rid, run.b.nxt, run.b.prv, p, d_err);
+        hipLaunchKernelGGL(k_cj_unmark, grid, blk, 0, ctx->stream, n, s0, E, run.e_to, tab, rid, run.b.nxt);
+        XC_TRY(run.rounds());
+        const CpRoles& b = run.b;
         // lab, prv: the labels and the ring marks; nxt, lab2, nxt2, prv2 are free from here on
         hipLaunchKernelGGL(k_cj_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, root, size);
         unsigned *rank = (unsigned*)b.nxt, *rank2 = (unsigned*)b.nxt2;
         int* p2 = b.lab2;
         hipLaunchKernelGGL(k_cj_rank_init, grid, blk, 0, ctx->stream, n, root, b.prv, p, rank, size);
-        for (int k = 0; k < R; ++k) {
+        for (int k = 0; k < run.R; ++k) {
             hipLaunchKernelGGL(k_cj_rank_round, grid, blk, 0, ctx->stream, n, p, rank, p2, rank2);
             std::swap(p, p2); std::swap(rank, rank2);
         }
         XC_HIP(ctx, hipGetLastError());
-        rounds_total += 2 * R;
+        run.rounds_total += run.R;                                           // the rank rounds: as many again
         tm.mark(2);
         unsigned* start = (unsigned*)b.prv2;
         hipLaunchKernelGGL(k_cj_chunk_sums, sgrid, blk, 0, ctx->stream, E, nchunk, n, tab, root, size, sums);
@@ -362,23 +354,20 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
         hipLaunchKernelGGL(k_cj_place, grid, blk, 0, ctx->stream, n, s0, d_off, g.r0, rid, root, rank, start, pidx, size, b.prv, inv, gidx, gsz, d_err);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(3);
-        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
+        XC_TRY(run.end());
     }
-    ctx->cjoin_rounds = rounds_total; ctx->cjoin_groups = (int)groups.size();
+    run.report(prof);
     // the second round trip: the polyline counts (and whether the records were a join's input)
     std::vector<uint64_t> hp((size_t)nrange);
     int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(hp.data(), poly_count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr & CP_ERR_EDGE) { tm.settle(); return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id outside [0, 2 ny nx)"); }
-    if (herr) { tm.settle(); return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id repeats among the e_from or the e_to of a range"); }
+    XC_TRY(cp_read_err(ctx, d_err, &herr));
+    if (herr & CP_ERR_EDGE) return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id outside [0, 2 ny nx)");
+    if (herr) return fail(ctx, XC_EBADARG, "xc_contour_polylines: an edge id repeats among the e_from or the e_to of a range");
     std::vector<long long> poff((size_t)nrange + 1);
     poff[0] = 0;
     for (int64_t r = 0; r < nrange; ++r) poff[(size_t)r + 1] = poff[(size_t)r] + (long long)hp[(size_t)r];
-    if (poff[(size_t)nrange] > capacity) { tm.settle(); return 1; }
+    if (poff[(size_t)nrange] > capacity) return 1;
     tm.mark(-1);
     XC_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_cj_emit, dim3(cp_blocks(total)), dim3(CP_TPB), 0, ctx->stream, (int64_t)total, d_off, nrange, d_poff,
@@ -386,9 +375,7 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
                        (int*)poly_closed, (long long*)poly_first_edge, pts_walk, (long long*)e_from_walk, (long long*)order, d_err);
     XC_HIP(ctx, hipGetLastError());
     tm.mark(4);
-    XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    tm.settle();
+    XC_TRY(cp_read_err(ctx, d_err, &herr));
     if (herr) return fail(ctx, XC_EBADARG, "xc_contour_polylines: the records are not those of one xc_contour_segments call");
     return XC_OK;
 }
@@ -407,9 +394,5 @@ int xc_contour_polylines_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
 
 int xc_last_cjoin_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    if (ms) for (int k = 0; k < 5; ++k) ms[k] = (double)ctx->cjoin_ms[k];
-    if (rounds) *rounds = ctx->cjoin_rounds;
-    if (groups) *groups = ctx->cjoin_groups;
-    return XC_OK;
+    return xc::profile_get(ctx, &xc_ctx::prof_cjoin, xc::CJ_STAGES, ms, rounds, groups);
 }

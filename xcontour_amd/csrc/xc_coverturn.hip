@@ -110,33 +110,23 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
     if (nrange > ((int64_t)1 << 38) / nx) return fail(ctx, XC_EBADARG, "xc_contour_overturning: nrange nx must stay below 2^38");
     const long long E = 2 * ny * nx;
     const int wrap = periodic ? 1 : 0;
-    for (int k = 0; k < 4; ++k) ctx->coverturn_ms[k] = 0.f;
-    ctx->coverturn_rounds = 0; ctx->coverturn_groups = 0;
+    CpProfile& prof = ctx->prof_coverturn;
+    profile_clear(prof);
 
-    std::vector<uint64_t> hc;
-    std::vector<long long> off;
-    XC_TRY(cp_read_counts(ctx, "xc_contour_overturning", nrange, count, nullptr, hc, off));
-    const long long total = off[(size_t)nrange];
-    if (total > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_overturning: segments without their records");
-
-    // groups of consecutive ranges [r0, r1) (xc_cpiece_link.h); none without segments
-    int64_t gmax = 0; long long nmax = 0;
-    std::vector<CpGroup> groups;
-    if (total > 0) groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
-    // workspace: off | key | err | tab[gmax][E] | rid[nmax] | label, next, prev x 2 [nmax]
+    CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
+    XC_TRY(cp_plan(ctx, "xc_contour_overturning", nrange, count, nullptr, e_from, e_to, pts, E, pl));
+    // workspace: off | key | err | the tail (xc_cpiece_link.h)
     const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_small = 256;
-    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_key + b_small + b_tab + 7 * b_n));
+    CpTail tail;
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_key + b_small + cp_carve_tail(nullptr, pl, 6, tail)));
     char* ws = (char*)ctx->cpiece_ws;
     long long* d_off = (long long*)ws;
     unsigned long long* key = (unsigned long long*)(ws + b_off);
     int* d_err = (int*)(ws + b_off + b_key);
-    int* tab = (int*)((char*)d_err + b_small);
-    int* rid = (int*)((char*)tab + b_tab);
-    int* buf[6];
-    for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+    cp_carve_tail((char*)d_err + b_small, pl, 6, tail);
 
-    StageTimer tm(ctx, ctx->coverturn_ms);                                      // where the time goes (xc_set_kernel_timing)
+    StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
+    CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
 
     const int64_t ncol = nrange * nx;
     const dim3 ogrid(cp_blocks(ncol)), blk(CP_TPB);
@@ -146,50 +136,28 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
     XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
-    if (total > 0) {
-        XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
-    }
+    XC_TRY(run.upload_off());
+    XC_TRY(run.fill_table());
     tm.mark(0);
-    int rounds_total = 0;
-    for (const CpGroup& g : groups) {
-        const long long s0 = off[(size_t)g.r0];
-        const int64_t n = off[(size_t)g.r1] - s0;
-        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
-        const dim3 grid(cp_blocks(n));
-        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
-        b = cp_launch_rounds(ctx->stream, n, R, b);
-        XC_HIP(ctx, hipGetLastError());
-        rounds_total += R;
-        tm.mark(1);
-        // lab, prv: the labels and the ring marks; nxt, lab2, nxt2 are free from here on
-        int* root = b.nxt;
-        unsigned* pn = (unsigned*)b.lab2;
-        int* pw = b.nxt2;
-        hipLaunchKernelGGL(k_co_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, root, pn, pw);
-        hipLaunchKernelGGL(k_co_piece, grid, blk, 0, ctx->stream, n, s0, wrap, nx, pts, root, pn, pw);
-        hipLaunchKernelGGL(k_co_pick, grid, blk, 0, ctx->stream, n, g.r0, select, rid, root, b.prv, b.lab, pn, pw, (int*)nsel, key);
+    for (const CpGroup& g : pl.groups) {
+        run.begin(g);
+        XC_TRY(run.rounds());
+        const CoRoles s = co_launch_select(run, wrap, nx, pts, select, (int*)nsel, key);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(2);
-        hipLaunchKernelGGL(k_co_count, grid, blk, 0, ctx->stream, n, s0, g.r0, E, nx, select, (const long long*)e_from, (const long long*)e_to, pts,
-                           tab, rid, root, b.prv, b.lab, pn, pw, key, (int*)ncross, row_lo, row_hi, (int*)main_winding);
+        hipLaunchKernelGGL(k_co_count, run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, nx, select, run.e_from, run.e_to, pts, tail.tab,
+                           tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key, (int*)ncross, row_lo, row_hi, (int*)main_winding);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(3);
-        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
+        XC_TRY(run.end());
     }
-    ctx->coverturn_rounds = rounds_total; ctx->coverturn_groups = (int)groups.size();
+    run.report(prof);
     hipLaunchKernelGGL(k_co_finish, ogrid, blk, 0, ctx->stream, ncol, nrange, select, (const int*)ncross, row_lo, row_hi, key, (int*)nsel,
                        (long long*)main_first_edge, (long long*)main_nseg);
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
     int herr = 0;
-    XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    tm.settle();
+    XC_TRY(cp_read_err(ctx, d_err, &herr));
     if (herr) return fail(ctx, XC_EBADARG, "xc_contour_overturning: an edge id outside [0, 2 ny nx)");
     return XC_OK;
 }
@@ -208,9 +176,5 @@ int xc_contour_overturning_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
 
 int xc_last_coverturn_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = (double)ctx->coverturn_ms[k];
-    if (rounds) *rounds = ctx->coverturn_rounds;
-    if (groups) *groups = ctx->coverturn_groups;
-    return XC_OK;
+    return xc::profile_get(ctx, &xc_ctx::prof_coverturn, 4, ms, rounds, groups);
 }

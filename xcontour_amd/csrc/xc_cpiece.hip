@@ -180,75 +180,57 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_pieces: plane too large for 32-bit labels (2 ny nx < 2^31)");
     const long long E = 2 * ny * nx;
     const int wrap = periodic ? 1 : 0, latlon = radius > 0.0;
-    for (int k = 0; k < 4; ++k) ctx->cpiece_ms[k] = 0.f;
-    ctx->cpiece_rounds = 0; ctx->cpiece_groups = 0;
+    CpProfile& prof = ctx->prof_cpiece;
+    profile_clear(prof);
 
-    std::vector<uint64_t> hc;
-    std::vector<long long> off;
-    XC_TRY(cp_read_counts(ctx, "xc_contour_pieces", nrange, count, piece_count, hc, off));
-    const long long total = off[(size_t)nrange];
+    CpPlan pl;
+    XC_TRY(cp_plan(ctx, "xc_contour_pieces", nrange, count, piece_count, e_from, e_to, pts, E, pl));
+    const long long total = pl.total;
     if (total == 0) return XC_OK;
-    if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, "xc_contour_pieces: segments without their records");
 
-    // groups of consecutive ranges [r0, r1) (xc_cpiece_link.h)
-    int64_t gmax = 1; long long nmax = 0;
-    const std::vector<CpGroup> groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
-    // workspace: off | poff | c0[2], err | pslot[total] | tab[gmax][E] | rid[nmax] | label, next, prev x 2 [nmax]
+    // workspace: off | poff | c0[2], err | pslot[total] | the tail (xc_cpiece_link.h)
     const size_t b_off = al((size_t)(nrange + 1) * 8), b_small = 256, b_slot = al((size_t)total * 4);
-    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + b_slot + b_tab + 7 * b_n));
+    CpTail tail;
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + b_slot + cp_carve_tail(nullptr, pl, 6, tail)));
     char* ws = (char*)ctx->cpiece_ws;
     long long* d_off = (long long*)ws;
     long long* d_poff = (long long*)(ws + b_off);
     int* d_c0 = (int*)(ws + 2 * b_off);
     int* d_err = d_c0 + 2;
     int* pslot = (int*)(ws + 2 * b_off + b_small);
-    int* tab = (int*)((char*)pslot + b_slot);
-    int* rid = (int*)((char*)tab + b_tab);
-    int* buf[6];
-    for (int k = 0; k < 6; ++k) buf[k] = (int*)((char*)rid + (size_t)(k + 1) * b_n);
+    cp_carve_tail((char*)pslot + b_slot, pl, 6, tail);
 
-    StageTimer tm(ctx, ctx->cpiece_ms);                                      // where the time goes (xc_set_kernel_timing)
+    StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
+    CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
 
     tm.mark(-1);
-    XC_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    XC_TRY(run.upload_off());
     XC_HIP(ctx, hipMemsetAsync(d_c0, 0, b_small, ctx->stream));
-    XC_HIP(ctx, hipMemsetAsync(tab, 0xff, (size_t)gmax * (size_t)E * 4, ctx->stream));
+    XC_TRY(run.fill_table());
     tm.mark(0);
-    int rounds_total = 0;
-    for (const CpGroup& g : groups) {
-        const long long s0 = off[(size_t)g.r0];
-        const int64_t n = off[(size_t)g.r1] - s0;
-        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
-        const dim3 grid(cp_blocks(n)), blk(CP_TPB);
-        CpRoles b = cp_launch_table(ctx->stream, n, s0, d_off, g, E, e_from, e_to, tab, rid, buf, d_err);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
-        b = cp_launch_rounds(ctx->stream, n, R, b);
-        XC_HIP(ctx, hipGetLastError());
-        rounds_total += R;
-        tm.mark(1);
-        hipLaunchKernelGGL(k_cp_root, grid, blk, 0, ctx->stream, n, E, tab, rid, b.lab, b.prv, g.r0, (unsigned long long*)piece_count, b.nxt2, b.lab2);
-        hipLaunchKernelGGL(k_cp_bcast, grid, blk, 0, ctx->stream, n, s0, b.nxt2, b.lab2, pslot);
+    for (const CpGroup& g : pl.groups) {
+        run.begin(g);
+        XC_TRY(run.rounds());
+        const CpRoles& b = run.b;
+        hipLaunchKernelGGL(k_cp_root, run.grid, dim3(CP_TPB), 0, ctx->stream, run.n, E, tail.tab, tail.rid, b.lab, b.prv, g.r0,
+                           (unsigned long long*)piece_count, b.nxt2, b.lab2);
+        hipLaunchKernelGGL(k_cp_bcast, run.grid, dim3(CP_TPB), 0, ctx->stream, run.n, run.s0, b.nxt2, b.lab2, pslot);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(2);
-        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, ctx->stream, n, s0, E, (const long long*)e_from, rid, tab);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
+        XC_TRY(run.end());
     }
-    ctx->cpiece_rounds = rounds_total; ctx->cpiece_groups = (int)groups.size();
+    run.report(prof);
     // the second round trip: the piece counts (and whether the records were K12's)
     std::vector<uint64_t> hp((size_t)nrange);
-    int herr[2] = {0, 0};
+    int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(hp.data(), piece_count, (size_t)nrange * 8, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr[0]) { tm.settle(); return fail(ctx, XC_EBADARG, "xc_contour_pieces: an edge id outside [0, 2 ny nx)"); }
+    XC_TRY(cp_read_err(ctx, d_err, &herr));
+    if (herr) return fail(ctx, XC_EBADARG, "xc_contour_pieces: an edge id outside [0, 2 ny nx)");
     std::vector<long long> poff((size_t)nrange + 1);
     poff[0] = 0;
     for (int64_t r = 0; r < nrange; ++r) poff[(size_t)r + 1] = poff[(size_t)r] + (long long)hp[(size_t)r];
     const long long np = poff[(size_t)nrange];
-    if (np > capacity) { tm.settle(); return 1; }
+    if (np > capacity) return 1;
     XC_TRY(grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, al((size_t)np * 2 * CP_L * 8) + al((size_t)np * 4)));
     unsigned long long* acc = (unsigned long long*)ctx->cpiece_acc;
     int* flags = (int*)((char*)ctx->cpiece_acc + al((size_t)np * 2 * CP_L * 8));
@@ -269,10 +251,8 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
 #undef XC_CP_RECORDS
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
-    XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
-    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    tm.settle();
-    if (herr[0]) return fail(ctx, XC_EBADARG, "xc_contour_pieces: the records are not those of one xc_contour_segments call (a repeated edge id)");
+    XC_TRY(cp_read_err(ctx, d_err, &herr));
+    if (herr) return fail(ctx, XC_EBADARG, "xc_contour_pieces: the records are not those of one xc_contour_segments call (a repeated edge id)");
     return XC_OK;
 }
 
@@ -299,9 +279,5 @@ int xc_set_cpiece_workspace(xc_ctx* ctx, uint64_t bytes)
 
 int xc_last_cpiece_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = (double)ctx->cpiece_ms[k];
-    if (rounds) *rounds = ctx->cpiece_rounds;
-    if (groups) *groups = ctx->cpiece_groups;
-    return XC_OK;
+    return xc::profile_get(ctx, &xc_ctx::prof_cpiece, 4, ms, rounds, groups);
 }

@@ -1,7 +1,11 @@
 // Phase A of the device joins, shared by K13 (xc_cpiece.hip), K14 (xc_cjoin.hip), K16 (xc_coverturn.hip), K17 (xc_cinside.hip) and
 // K18-K21 (xc_cprecords.hip): the dense edge tables of a GROUP of consecutive ranges, the next / prev links, the pointer-doubling rounds,
-// the plan that cuts the ranges into groups and the host steps every one of these launchers takes.  xc_cpiece.hip's header states the
-// rule.  Included inside namespace xc { namespace { ... } } after xc_capi.h, like xc_binning.h.
+// and the host frame every one of these launchers runs them in.  xc_cpiece.hip's header states the rule.  Written once here: the plan
+// (cp_plan: counts, scan, the refusal of segments without records, groups), the tail of the workspace (cp_carve_tail), the per-group
+// run (CpRun: offsets up, table filled, then begin / rounds / end per group with their stage marks and the sum of the rounds) and the
+// read of the error word (cp_read_err).  What stays with a launcher: the head of its workspace, its own stages between rounds() and
+// end(), the meaning of the error bits, and whether it returns on a call without segments (K13, K14, K18-K21) or goes on with an empty
+// plan (K16, K17).  Included inside namespace xc { namespace { ... } } after xc_capi.h, like xc_binning.h.
 #pragma once
 
 constexpr int CP_TPB = 256;
@@ -126,29 +130,105 @@ inline int cp_read_counts(xc_ctx* ctx, const char* who, int64_t nrange, const ui
     return XC_OK;
 }
 
+// The plan of a call: the counts, their scan, and the groups.  A call without segments has no group, no table row (gmax 0) and no
+// buffer (nmax 0): K13, K14 and K18-K21 return on total == 0, K16 and K17 go on and write their dense outputs.
+struct CpPlan {
+    std::vector<uint64_t> hc; std::vector<long long> off; long long total = 0, E = 0;
+    std::vector<CpGroup> groups; int64_t gmax = 0; long long nmax = 0;
+};
+// `who`: the entry, for the refusals; `clear` as for cp_read_counts; one wait for the stream
+inline int cp_plan(xc_ctx* ctx, const char* who, int64_t nrange, const uint64_t* count, uint64_t* clear, const int64_t* e_from,
+                   const int64_t* e_to, const double* pts, long long E, CpPlan& p)
+{
+    XC_TRY(cp_read_counts(ctx, who, nrange, count, clear, p.hc, p.off));
+    p.total = p.off[(size_t)nrange]; p.E = E;
+    if (p.total == 0) return XC_OK;
+    if (!e_from || !e_to || !pts) return fail(ctx, XC_EBADARG, std::string(who) + ": segments without their records");
+    p.groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, p.hc, p.off, &p.gmax, &p.nmax);
+    return XC_OK;
+}
+
+// The tail of every layout of ctx->cpiece_ws: tab[gmax][E] | rid[nmax] | nbuf buffers [nmax] (six: label, next, prev x 2; K14 ten),
+// carved from `p` (null: nothing is carved); -> its bytes.  What lies in front of it is the launcher's own.
+constexpr int CP_NBUF = 10;
+struct CpTail { int *tab, *rid, *buf[CP_NBUF]; };
+inline size_t cp_carve_tail(char* p, const CpPlan& pl, int nbuf, CpTail& t)
+{
+    const size_t b_tab = al((size_t)pl.gmax * (size_t)pl.E * 4), b_n = al((size_t)pl.nmax * 4);
+    if (p) {
+        t.tab = (int*)p; t.rid = (int*)(p + b_tab);
+        for (int k = 0; k < nbuf; ++k) t.buf[k] = (int*)(p + b_tab + (size_t)(k + 1) * b_n);
+    }
+    return b_tab + (size_t)(nbuf + 1) * b_n;
+}
+
+// the error word of a call on the host: one wait for the stream.  What its bits mean is the entry's.
+inline int cp_read_err(xc_ctx* ctx, const int* d_err, int* herr)
+{
+    XC_HIP(ctx, hipMemcpyAsync(herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return XC_OK;
+}
+
 // which of a group's six buffers [nmax] hold what: lab, nxt and prv stand, lab2, nxt2 and prv2 are free
 struct CpRoles { int *lab, *nxt, *prv, *lab2, *nxt2, *prv2; };
 
-// the edge table of group g (n segments from s0 on) and the links
-inline CpRoles cp_launch_table(hipStream_t stream, int64_t n, long long s0, const long long* d_off, const CpGroup& g, long long E,
-                               const int64_t* e_from, const int64_t* e_to, int* tab, int* rid, int* const* buf, int* d_err)
-{
-    const dim3 grid(cp_blocks(n)), blk(CP_TPB);
-    const CpRoles b = {buf[0], buf[1], buf[2], buf[3], buf[4], buf[5]};
-    hipLaunchKernelGGL(k_cp_scatter, grid, blk, 0, stream, n, s0, d_off, g.r0, g.r1, E, (const long long*)e_from, tab, rid, b.lab, b.prv, d_err);
-    hipLaunchKernelGGL(k_cp_link, grid, blk, 0, stream, n, s0, E, (const long long*)e_to, tab, rid, b.nxt, b.prv, d_err);
-    return b;
-}
+// Phase A of one call, group by group.  A launcher's loop is
+//     for (const CpGroup& g : plan.groups) { run.begin(g); [K14: its checks] XC_TRY(run.rounds()); its own stages; XC_TRY(run.end()); }
+// between upload_off() / fill_table() in front (nothing without groups) and report() behind.  Stage 0 takes the table (and whatever the
+// launcher put behind it), stage 1 the rounds, stage 0 again the unscatter; what lies between rounds() and end() the launcher marks.
+struct CpRun {
+    xc_ctx* ctx; StageTimer& tm; const CpPlan& pl; const long long *e_from, *e_to; long long* d_off; CpTail t; int* d_err;
+    // the group at hand: its first segment, its segments, its rounds, its grid of CP_TPB threads, the roles of its buffers
+    CpGroup g = {0, 0}; long long s0 = 0; int64_t n = 0; int R = 0; dim3 grid; CpRoles b = {};
+    int rounds_total = 0;
 
-// R doubling rounds; -> the roles after them
-inline CpRoles cp_launch_rounds(hipStream_t stream, int64_t n, int R, CpRoles b)
-{
-    for (int k = 0; k < R; ++k) {
-        hipLaunchKernelGGL(k_cp_round, dim3(cp_blocks(n)), dim3(CP_TPB), 0, stream, n, b.lab, b.nxt, b.prv, b.lab2, b.nxt2, b.prv2);
-        std::swap(b.lab, b.lab2); std::swap(b.nxt, b.nxt2); std::swap(b.prv, b.prv2);
+    CpRun(xc_ctx* c, StageTimer& timer, const CpPlan& plan, const int64_t* ef, const int64_t* et, long long* off, const CpTail& tail, int* err)
+        : ctx(c), tm(timer), pl(plan), e_from((const long long*)ef), e_to((const long long*)et), d_off(off), t(tail), d_err(err) {}
+    int upload_off()
+    {
+        if (pl.groups.empty()) return XC_OK;
+        XC_HIP(ctx, hipMemcpyAsync(d_off, pl.off.data(), pl.off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        return XC_OK;
     }
-    return b;
-}
+    int fill_table()
+    {
+        if (pl.groups.empty()) return XC_OK;
+        XC_HIP(ctx, hipMemsetAsync(t.tab, 0xff, (size_t)pl.gmax * (size_t)pl.E * 4, ctx->stream));
+        return XC_OK;
+    }
+    // the edge table of the group and the links
+    void begin(const CpGroup& group)
+    {
+        g = group; s0 = pl.off[(size_t)g.r0]; n = pl.off[(size_t)g.r1] - s0; R = cp_rounds(pl.hc, g); grid = dim3(cp_blocks(n));
+        b = {t.buf[0], t.buf[1], t.buf[2], t.buf[3], t.buf[4], t.buf[5]};
+        hipLaunchKernelGGL(k_cp_scatter, grid, dim3(CP_TPB), 0, ctx->stream, n, s0, d_off, g.r0, g.r1, pl.E, e_from, t.tab, t.rid, b.lab, b.prv, d_err);
+        hipLaunchKernelGGL(k_cp_link, grid, dim3(CP_TPB), 0, ctx->stream, n, s0, pl.E, e_to, t.tab, t.rid, b.nxt, b.prv, d_err);
+    }
+    // R doubling rounds: b holds the roles after them
+    int rounds()
+    {
+        XC_HIP(ctx, hipGetLastError());
+        tm.mark(0);
+        for (int k = 0; k < R; ++k) {
+            hipLaunchKernelGGL(k_cp_round, grid, dim3(CP_TPB), 0, ctx->stream, n, b.lab, b.nxt, b.prv, b.lab2, b.nxt2, b.prv2);
+            std::swap(b.lab, b.lab2); std::swap(b.nxt, b.nxt2); std::swap(b.prv, b.prv2);
+        }
+        XC_HIP(ctx, hipGetLastError());
+        rounds_total += R;
+        tm.mark(1);
+        return XC_OK;
+    }
+    // the table handed on clean
+    int end()
+    {
+        hipLaunchKernelGGL(k_cp_unscatter, grid, dim3(CP_TPB), 0, ctx->stream, n, s0, pl.E, e_from, t.rid, t.tab);
+        XC_HIP(ctx, hipGetLastError());
+        tm.mark(0);
+        return XC_OK;
+    }
+    void report(CpProfile& p) const { p.rounds = rounds_total; p.groups = (int)pl.groups.size(); }
+};
 
 // The row chunks of a column scan (K20, K21: xc_cpiece_label.h; K22: xc_cpoverlap.hip).
 constexpr int PL_ROWS = 16;                   // a chunk of a column has at least this many rows ...

@@ -84,3 +84,17 @@ __device__ __forceinline__ bool co_selected(int select, bool ring, int t, int la
     ismain = circ && co_key(pn[t], lab_i) == key_r;
     return select == 0 || (select == 1 ? circ : ismain);
 }
+
+// The three selection launches of the group `run` stands in, behind its rounds: root, pn and pw take the free buffers nxt, lab2 and nxt2
+struct CoRoles { int* root; unsigned* pn; int* pw; };
+inline CoRoles co_launch_select(const CpRun& run, int wrap, int64_t nx, const double* pts, int select, int* nsel, unsigned long long* key)
+{
+    const CpRoles& b = run.b;
+    const CoRoles s = {b.nxt, (unsigned*)b.lab2, b.nxt2};
+    const dim3 blk(CP_TPB);
+    hipStream_t stream = run.ctx->stream;
+    hipLaunchKernelGGL(k_co_root, run.grid, blk, 0, stream, run.n, run.pl.E, run.t.tab, run.t.rid, b.lab, s.root, s.pn, s.pw);
+    hipLaunchKernelGGL(k_co_piece, run.grid, blk, 0, stream, run.n, run.s0, wrap, nx, pts, s.root, s.pn, s.pw);
+    hipLaunchKernelGGL(k_co_pick, run.grid, blk, 0, stream, run.n, run.g.r0, select, run.t.rid, s.root, b.prv, b.lab, s.pn, s.pw, nsel, key);
+    return s;
+}

@@ -299,8 +299,8 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     if (ny > (((int64_t)1 << 31) - 1) / nx) return fail(ctx, XC_EBADARG, std::string(who) + ": plane too large (ny nx < 2^31)");
     const int64_t nslab = nrange / ncont;
     if (nslab > 65535) return fail(ctx, XC_EBADARG, std::string(who) + ": more than 65535 slabs");
-    for (int k = 0; k < 3; ++k) ctx->cpoverlap_ms[k] = 0.f;
-    ctx->cpoverlap_groups = 0;
+    CpProfile& prof = ctx->prof_cpoverlap;
+    profile_clear(prof);
     const int64_t npl = ny * nx;
     const int hasf = f ? 1 : 0;
     const int W = 3 + CP_L * (1 + hasf);
@@ -320,8 +320,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     long long* d_poff = (long long*)((char*)d_soff + b_r);
     unsigned long long* d_cur = (unsigned long long*)((char*)d_poff + b_r);
 
-    StageTimer tm(ctx, ctx->cpoverlap_ms);                                      // where the time goes (xc_set_kernel_timing)
-    auto bail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); tm.settle(); return rc; };
+    StageTimer tm(ctx, prof.ms);                                                // where the time goes (xc_set_kernel_timing)
 
     const dim3 blk(CP_TPB);
     const int* la = (const int*)lab_a;
@@ -351,7 +350,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         soff[(size_t)r + 1] = soff[(size_t)r] + s;
         total_runs += runs[(size_t)r];
     }
-    if (total_runs == 0) { tm.settle(); return XC_OK; }                       // both maps hold no ring: no rows (pair_count is cleared)
+    if (total_runs == 0) return XC_OK;                     // both maps hold no ring: no rows (pair_count is cleared)
     XC_HIP(ctx, hipMemcpyAsync(d_soff, soff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     // groups of consecutive ranges whose tables fit the cap (one range always does), no more than rmax ranges; ranges without runs in
     // front of a group cost nothing
@@ -370,13 +369,13 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         smax = std::max(smax, soff[(size_t)r1] - soff[(size_t)r]);
         r = r1;
     }
-    if (smax > ((1ull << 62) / ((unsigned long long)W * 8ull))) return tm.settle(), fail(ctx, XC_ENOMEM, std::string(who) + ": the table of one group is too large");
+    if (smax > ((1ull << 62) / ((unsigned long long)W * 8ull))) return fail(ctx, XC_ENOMEM, std::string(who) + ": the table of one group is too large");
     // the tables of one group, then the staged rows (a, b: 4 bytes; n, sum_w, sum_wf: 8 bytes) of min(capacity, all runs)
     const int64_t cap = (int64_t)std::min<uint64_t>((uint64_t)capacity, total_runs);
     const size_t b_tab = al((size_t)smax * (size_t)W * 8), b4 = al((size_t)cap * 4), b8 = al((size_t)cap * 8);
     {
         const int rc = grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, b_tab + 2 * b4 + 3 * b8);
-        if (rc != XC_OK) { tm.settle(); return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the pair tables"); }
+        if (rc != XC_OK) return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the pair tables");
     }
     unsigned long long* tab = (unsigned long long*)ctx->cpiece_acc;
     int* sa = (int*)((char*)tab + b_tab);
@@ -423,13 +422,13 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         tm.mark(2);
     }
     for (; done < nrange; ++done) poff[(size_t)done + 1] = poff[(size_t)done] + (long long)hp[(size_t)done];
-    ctx->cpoverlap_groups = (int)groups.size();
+    prof.groups = (int)groups.size();
     const long long np = poff[(size_t)nrange];
     int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr) { tm.settle(); return fail(ctx, XC_EHIP, std::string(who) + (herr & PO_ERR_FULL ? ": a pair found no slot in its range's table" : ": a pair found no row in its range")); }
-    if (np > capacity) { tm.settle(); return 1; }
+    if (herr) return fail(ctx, XC_EHIP, std::string(who) + (herr & PO_ERR_FULL ? ": a pair found no slot in its range's table" : ": a pair found no row in its range"));
+    if (np > capacity) return 1;
     if (np > 0) {
         XC_HIP(ctx, hipMemcpyAsync(a, sa, (size_t)np * 4, hipMemcpyDeviceToDevice, ctx->stream));
         XC_HIP(ctx, hipMemcpyAsync(b, sb, (size_t)np * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -438,7 +437,8 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
         if (hasf) XC_HIP(ctx, hipMemcpyAsync(sum_wf, swf, (size_t)np * 8, hipMemcpyDeviceToDevice, ctx->stream));
     }
     tm.mark(2);
-    return bail(XC_OK);
+    (void)hipStreamSynchronize(ctx->stream);
+    return XC_OK;
 }
 
 }  // namespace xc
@@ -455,9 +455,5 @@ int xc_label_overlap_dev(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
 
 int xc_last_cpoverlap_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    if (ms) for (int k = 0; k < 3; ++k) ms[k] = (double)ctx->cpoverlap_ms[k];
-    if (rounds) *rounds = 0;
-    if (groups) *groups = ctx->cpoverlap_groups;
-    return XC_OK;
+    return xc::profile_get(ctx, &xc_ctx::prof_cpoverlap, 3, ms, rounds, groups);
 }

@@ -35,7 +35,7 @@ namespace {
 // stages run: K18 none, K19 `tree`, K20 `tree` and `label`, K21 `tree` and `props`.
 struct PieceCall {
     const char* who;                                                       // the entry, for the error texts
-    float* ms; int nms; int* rounds; int* groups;                          // the entry's own profile fields of the context
+    CpProfile* prof;                                                       // the entry's own profile record of the context
     int64_t nrange; const uint64_t* count; const int64_t *e_from, *e_to; const double* pts; int64_t ny, nx; int periodic, flip, ncont;
     const double* w; int w_per_slab; const void* f; int f_dtype; int64_t capacity; uint64_t* piece_count;
     int64_t *first_edge, *nseg; int32_t *closed, *winding; int64_t* n_in; double *sum_w, *sum_wf;
@@ -45,29 +45,25 @@ struct PieceCall {
     double *net_g, *sum_g, *x_min, *x_max; int64_t *at_min, *at_max;
 };
 
-// The workspace of a call (ctx->cpiece_ws): off | poff | mx[nslab][2], err (cleared together: b_zero bytes) | tab[gmax][E] | rid[nmax] |
-// label, next, prev x 2 [nmax] | K20, K21: carry[gmax][nchunk][nx] | K21: mxg[nslab][nf] (b_mxg bytes) | fld[nf + 1]
+// The workspace of a call (ctx->cpiece_ws): off | poff | mx[nslab][2], err (cleared together: b_zero bytes) | the tail (xc_cpiece_link.h)
+// | K20, K21: carry[gmax][nchunk][nx] | K21: mxg[nslab][nf] (b_mxg bytes) | fld[nf + 1]
 struct PieceWs {
-    long long *off, *poff; unsigned long long* mx; int *err, *tab, *rid, *buf[6], *carry; unsigned long long* mxg; PpField* fld;
+    long long *off, *poff; unsigned long long* mx; int* err; CpTail t; int* carry; unsigned long long* mxg; PpField* fld;
     size_t b_zero, b_mxg;
 };
-int piece_ws_carve(xc_ctx* ctx, const PieceCall& c, int64_t nslab, long long E, int64_t gmax, long long nmax, int64_t nchunk, PieceWs& ws)
+int piece_ws_carve(xc_ctx* ctx, const PieceCall& c, int64_t nslab, const CpPlan& pl, int64_t nchunk, PieceWs& ws)
 {
-    const size_t b_off = al((size_t)(c.nrange + 1) * 8), b_mx = al((size_t)nslab * 16), b_small = 256;
-    const size_t b_tab = al((size_t)gmax * (size_t)E * 4), b_n = al((size_t)nmax * 4);
-    const size_t b_carry = nchunk > 1 ? al((size_t)gmax * (size_t)nchunk * (size_t)c.nx * 4) : 0;
+    const size_t b_off = al((size_t)(c.nrange + 1) * 8), b_mx = al((size_t)nslab * 16), b_small = 256, b_tail = cp_carve_tail(nullptr, pl, 6, ws.t);
+    const size_t b_carry = nchunk > 1 ? al((size_t)pl.gmax * (size_t)nchunk * (size_t)c.nx * 4) : 0;
     const size_t b_mxg = c.props ? al((size_t)nslab * (size_t)std::max(c.nf, 1) * 8) : 0;
     const size_t b_fld = c.props ? al((size_t)(XC_PROPS_MAXF + 1) * sizeof(PpField)) : 0;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_mx + b_small + b_tab + 7 * b_n + b_carry + b_mxg + b_fld));
+    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_mx + b_small + b_tail + b_carry + b_mxg + b_fld));
     char* p = (char*)ctx->cpiece_ws;
     ws.off = (long long*)p;
     ws.poff = (long long*)(p + b_off);
     ws.mx = (unsigned long long*)(p + 2 * b_off);
     ws.err = (int*)((char*)ws.mx + b_mx);
-    ws.tab = (int*)((char*)ws.err + b_small);
-    ws.rid = (int*)((char*)ws.tab + b_tab);
-    for (int k = 0; k < 6; ++k) ws.buf[k] = (int*)((char*)ws.rid + (size_t)(k + 1) * b_n);
-    ws.carry = (int*)((char*)ws.rid + 7 * b_n);
+    ws.carry = (int*)((char*)ws.err + b_small + cp_carve_tail((char*)ws.err + b_small, pl, 6, ws.t));
     ws.mxg = (unsigned long long*)((char*)ws.carry + b_carry);
     ws.fld = (PpField*)((char*)ws.mxg + b_mxg);
     ws.b_zero = b_mx + b_small; ws.b_mxg = b_mxg;
@@ -108,14 +104,12 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
     const long long E = 2 * ny * nx;
     const int wrap = c.periodic ? 1 : 0, nf = c.nf, hasx = c.x ? 1 : 0;
     if (nslab > 65535) return refuse(": more than 65535 slabs");
-    for (int k = 0; k < c.nms; ++k) c.ms[k] = 0.f;
-    *c.rounds = 0; *c.groups = 0;
+    profile_clear(*c.prof);
     hipStream_t stream = ctx->stream;
 
-    std::vector<uint64_t> hc;
-    std::vector<long long> off;
-    XC_TRY(cp_read_counts(ctx, c.who, nrange, c.count, c.piece_count, hc, off));
-    const long long total = off[(size_t)nrange];
+    CpPlan pl;
+    XC_TRY(cp_plan(ctx, c.who, nrange, c.count, c.piece_count, c.e_from, c.e_to, c.pts, E, pl));
+    const long long total = pl.total;
     if (total == 0) {
         if (c.label) {                                                       // no ring anywhere: -1 everywhere
             XC_HIP(ctx, pl_blank(stream, c.map, npl, 0, nrange));
@@ -123,15 +117,12 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
         }
         return XC_OK;
     }
-    if (!c.e_from || !c.e_to || !c.pts) return refuse(": segments without their records");
     const int64_t cap = std::min<int64_t>(c.capacity, total);             // a piece has a segment: no more pieces than segments
 
-    int64_t gmax = 1; long long nmax = 0;
-    const std::vector<CpGroup> groups = cp_plan_groups(ctx->cpiece_cap, E, nrange, hc, off, &gmax, &nmax);
     int64_t rows = 0, nchunk = 0;                                           // the row chunks of the scans (K20, K21)
     if (c.label || c.props) pl_geometry(ny, &rows, &nchunk);
     PieceWs ws;
-    XC_TRY(piece_ws_carve(ctx, c, nslab, E, gmax, nmax, nchunk, ws));
+    XC_TRY(piece_ws_carve(ctx, c, nslab, pl, nchunk, ws));
     // the staged records, K18's, then the tree's, then K21's: nothing reaches the caller's record arrays before all pieces are known to fit
     PiStage st = {};
     PtStage pt = {};
@@ -151,7 +142,8 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
     const bool pscan = c.props && (nf > 0 || hasx);                        // K21 without fields and without x is K19
 
     // the stages of the profiles: 0 table, 1 rounds, 2 roots, 3 walk, 4 tree, 5 label or props scan, 6 fold and finish
-    StageTimer tm(ctx, c.ms);
+    StageTimer tm(ctx, c.prof->ms);
+    CpRun run(ctx, tm, pl, c.e_from, c.e_to, ws.off, ws.t, ws.err);
     const dim3 blk(CP_TPB);
     tm.mark(-1);
     XC_HIP(ctx, hipMemsetAsync(ws.mx, 0, ws.b_zero, stream));
@@ -171,8 +163,8 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
         }
         tm.mark(5);
     }
-    XC_HIP(ctx, hipMemcpyAsync(ws.off, off.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, stream));
-    XC_HIP(ctx, hipMemsetAsync(ws.tab, 0xff, (size_t)gmax * (size_t)E * 4, stream));
+    XC_TRY(run.upload_off());
+    XC_TRY(run.fill_table());
     tm.mark(0);
 
     std::vector<uint64_t> hp((size_t)nrange, 0);
@@ -180,21 +172,14 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
     int64_t done = 0;                                                       // poff[0 .. done] stand
     int64_t mapped = 0;                                                     // K20: the map of ranges [0, mapped) is written
     bool over = cap == 0;                                                   // the pieces no longer fit: count only
-    int rounds_total = 0;
-    for (const CpGroup& g : groups) {
-        const long long s0 = off[(size_t)g.r0];
-        const int64_t n = off[(size_t)g.r1] - s0, ng = g.r1 - g.r0;
-        const int R = cp_rounds(hc, g);                                    // ceil(log2(largest count)) + 1
-        const dim3 grid(cp_blocks(n));
-        CpRoles b = cp_launch_table(stream, n, s0, ws.off, g, E, c.e_from, c.e_to, ws.tab, ws.rid, ws.buf, ws.err);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
-        b = cp_launch_rounds(stream, n, R, b);
-        XC_HIP(ctx, hipGetLastError());
-        rounds_total += R;
-        tm.mark(1);
-        int *root = b.nxt2, *slot = b.lab2;
-        hipLaunchKernelGGL(k_cp_root, grid, blk, 0, stream, n, E, ws.tab, ws.rid, b.lab, b.prv, g.r0, (unsigned long long*)c.piece_count, root, slot);
+    int* const tab = ws.t.tab; int* const rid = ws.t.rid;
+    for (const CpGroup& g : pl.groups) {
+        run.begin(g);
+        XC_TRY(run.rounds());
+        const long long s0 = run.s0;
+        const int64_t n = run.n, ng = g.r1 - g.r0;
+        int *root = run.b.nxt2, *slot = run.b.lab2;
+        hipLaunchKernelGGL(k_cp_root, run.grid, blk, 0, stream, n, E, tab, rid, run.b.lab, run.b.prv, g.r0, (unsigned long long*)c.piece_count, root, slot);
         XC_HIP(ctx, hipGetLastError());
         // the group's piece counts place its pieces in the table
         XC_HIP(ctx, hipMemcpyAsync(hp.data() + g.r0, c.piece_count + g.r0, (size_t)ng * 8, hipMemcpyDeviceToHost, stream));
@@ -203,17 +188,17 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
         const int64_t p0 = poff[(size_t)g.r0], p1 = poff[(size_t)g.r1];
         if (p1 > cap) over = true;
         if (!over && p1 > p0) {
-            const PlGroup pg = {n, s0, g.r0, E, ny, nx, c.flip, cap, (const long long*)c.e_from, (const long long*)c.e_to, ws.tab, root, slot,
+            const PlGroup pg = {n, s0, g.r0, E, ny, nx, c.flip, cap, (const long long*)c.e_from, (const long long*)c.e_to, tab, root, slot,
                                 (const unsigned long long*)c.piece_count, ws.poff};
             XC_HIP(ctx, hipMemcpyAsync(ws.poff + g.r0, poff.data() + g.r0, (size_t)(ng + 1) * 8, hipMemcpyHostToDevice, stream));
-            pi_launch_piece(stream, pg, p0, p1, wrap, c.pts, ws.rid, st, ws.err);
+            pi_launch_piece(stream, pg, p0, p1, wrap, c.pts, rid, st, ws.err);
             XC_HIP(ctx, hipGetLastError());
             tm.mark(2);
-            pi_launch_walk(stream, pg, c.ncont, ws.rid, c.w, c.w_per_slab, c.f, c.f_dtype, ws.mx, st, ws.err);
+            pi_launch_walk(stream, pg, c.ncont, rid, c.w, c.w_per_slab, c.f, c.f_dtype, ws.mx, st, ws.err);
             XC_HIP(ctx, hipGetLastError());
             tm.mark(3);
             if (c.tree) {
-                pt_launch_group(stream, pg, g.r1, p0, p1, ws.rid, st, pt, ws.err);
+                pt_launch_group(stream, pg, g.r1, p0, p1, rid, st, pt, ws.err);
                 XC_HIP(ctx, hipGetLastError());
                 tm.mark(4);
             }
@@ -238,21 +223,18 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
         } else {
             tm.mark(2);
         }
-        hipLaunchKernelGGL(k_cp_unscatter, grid, blk, 0, stream, n, s0, E, (const long long*)c.e_from, ws.rid, ws.tab);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(0);
+        XC_TRY(run.end());
     }
     for (; done < nrange; ++done) poff[(size_t)done + 1] = poff[(size_t)done] + (long long)hp[(size_t)done];
-    *c.rounds = rounds_total; *c.groups = (int)groups.size();
+    run.report(*c.prof);
     const long long np = poff[(size_t)nrange];
     int herr = 0;
-    XC_HIP(ctx, hipMemcpyAsync(&herr, ws.err, 4, hipMemcpyDeviceToHost, stream));
-    XC_HIP(ctx, hipStreamSynchronize(stream));
+    XC_TRY(cp_read_err(ctx, ws.err, &herr));
     // (a K18 call sets the first two bits only)
-    if (herr & CP_ERR_EDGE) { tm.settle(); return refuse(": an edge id outside [0, 2 ny nx)"); }
-    if (herr & CP_ERR_LINK) { tm.settle(); return refuse(": the records are not those of one xc_contour_segments call (a repeated edge id)"); }
-    if (herr) { tm.settle(); return refuse(": the records are not those of one xc_contour_segments call (rings that enclose each other)"); }
-    if (np > c.capacity) { tm.settle(); return 1; }
+    if (herr & CP_ERR_EDGE) return refuse(": an edge id outside [0, 2 ny nx)");
+    if (herr & CP_ERR_LINK) return refuse(": the records are not those of one xc_contour_segments call (a repeated edge id)");
+    if (herr) return refuse(": the records are not those of one xc_contour_segments call (rings that enclose each other)");
+    if (np > c.capacity) return 1;
     if (c.label) {
         if (!over) XC_HIP(ctx, pl_blank(stream, c.map, npl, mapped, nrange));   // the ranges without segments behind the last group
         tm.mark(5);
@@ -277,15 +259,6 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
         tm.mark(6);
     }
     XC_HIP(ctx, hipStreamSynchronize(stream));
-    tm.settle();
-    return XC_OK;
-}
-
-int profile_of(const float* src, int n, int src_rounds, int src_groups, double* ms, int* rounds, int* groups)
-{
-    if (ms) for (int k = 0; k < n; ++k) ms[k] = (double)src[k];
-    if (rounds) *rounds = src_rounds;
-    if (groups) *groups = src_groups;
     return XC_OK;
 }
 
@@ -299,7 +272,7 @@ int xc_contour_piece_interiors_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* 
                                    int64_t* nseg, int32_t* closed, int32_t* winding, int64_t* n_in, double* sum_w, double* sum_wf)
 {
     XC_CTX(ctx);
-    const xc::PieceCall c = {"xc_contour_piece_interiors", ctx->cpinside_ms, 4, &ctx->cpinside_rounds, &ctx->cpinside_groups, nrange, count,
+    const xc::PieceCall c = {"xc_contour_piece_interiors", &ctx->prof_cpinside, nrange, count,
                              e_from, e_to, pts, ny, nx, periodic, flip, ncont, w, w_per_slab, f, f_dtype, capacity, piece_count, first_edge,
                              nseg, closed, winding, n_in, sum_w, sum_wf};
     return xc::launch_piece_records(ctx, c);
@@ -312,7 +285,7 @@ int xc_contour_piece_tree_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count
                               int64_t* parent, int32_t* depth, int32_t* nchild, int64_t* n_net, double* net_w, double* net_wf)
 {
     XC_CTX(ctx);
-    const xc::PieceCall c = {"xc_contour_piece_tree", ctx->cptree_ms, 5, &ctx->cptree_rounds, &ctx->cptree_groups, nrange, count, e_from, e_to,
+    const xc::PieceCall c = {"xc_contour_piece_tree", &ctx->prof_cptree, nrange, count, e_from, e_to,
                              pts, ny, nx, periodic, flip, ncont, w, w_per_slab, f, f_dtype, capacity, piece_count, first_edge, nseg, closed,
                              winding, n_in, sum_w, sum_wf, true, parent, depth, nchild, n_net, net_w, net_wf};
     return xc::launch_piece_records(ctx, c);
@@ -326,7 +299,7 @@ int xc_contour_piece_labels_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* cou
                                 int32_t* label)
 {
     XC_CTX(ctx);
-    const xc::PieceCall c = {"xc_contour_piece_labels", ctx->cplabel_ms, 6, &ctx->cplabel_rounds, &ctx->cplabel_groups, nrange, count, e_from,
+    const xc::PieceCall c = {"xc_contour_piece_labels", &ctx->prof_cplabel, nrange, count, e_from,
                              e_to, pts, ny, nx, periodic, flip, ncont, w, w_per_slab, f, f_dtype, capacity, piece_count, first_edge, nseg,
                              closed, winding, n_in, sum_w, sum_wf, true, parent, depth, nchild, n_net, net_w, net_wf, true, label};
     return xc::launch_piece_records(ctx, c);
@@ -341,7 +314,7 @@ int xc_contour_piece_props_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
                                double* net_g, double* sum_g, double* x_min, double* x_max, int64_t* at_min, int64_t* at_max)
 {
     XC_CTX(ctx);
-    const xc::PieceCall c = {"xc_contour_piece_props", ctx->cpprops_ms, 7, &ctx->cpprops_rounds, &ctx->cpprops_groups, nrange, count, e_from,
+    const xc::PieceCall c = {"xc_contour_piece_props", &ctx->prof_cpprops, nrange, count, e_from,
                              e_to, pts, ny, nx, periodic, flip, ncont, w, w_per_slab, f, f_dtype, capacity, piece_count, first_edge, nseg,
                              closed, winding, n_in, sum_w, sum_wf, true, parent, depth, nchild, n_net, net_w, net_wf, false, nullptr,
                              true, nf, g, g_dtype, g_per_slab, x, x_dtype, net_g, sum_g, x_min, x_max, at_min, at_max};
@@ -350,24 +323,20 @@ int xc_contour_piece_props_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
 
 int xc_last_cpinside_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    return xc::profile_of(ctx->cpinside_ms, 4, ctx->cpinside_rounds, ctx->cpinside_groups, ms, rounds, groups);
+    return xc::profile_get(ctx, &xc_ctx::prof_cpinside, 4, ms, rounds, groups);
 }
 
 int xc_last_cptree_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    return xc::profile_of(ctx->cptree_ms, 5, ctx->cptree_rounds, ctx->cptree_groups, ms, rounds, groups);
+    return xc::profile_get(ctx, &xc_ctx::prof_cptree, 5, ms, rounds, groups);
 }
 
 int xc_last_cplabel_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    return xc::profile_of(ctx->cplabel_ms, 6, ctx->cplabel_rounds, ctx->cplabel_groups, ms, rounds, groups);
+    return xc::profile_get(ctx, &xc_ctx::prof_cplabel, 6, ms, rounds, groups);
 }
 
 int xc_last_cpprops_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    return xc::profile_of(ctx->cpprops_ms, 7, ctx->cpprops_rounds, ctx->cpprops_groups, ms, rounds, groups);
+    return xc::profile_get(ctx, &xc_ctx::prof_cpprops, 7, ms, rounds, groups);
 }

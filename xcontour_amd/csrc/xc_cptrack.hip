@@ -175,8 +175,8 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
     if (capacity > 0 && (!root || !track || !nprev || !nnext || (nlink > 0 && !link_ok) || !first_ring || !first_step || !last_step || !nrings
                          || !nsplit || !nmerge))
         return fail(ctx, XC_EBADARG, std::string(who) + ": capacity > 0 needs every output array");
-    for (int k = 0; k < 3; ++k) ctx->cptrack_ms[k] = 0.f;
-    ctx->cptrack_rounds = 0;
+    CpProfile& prof = ctx->prof_cptrack;
+    profile_clear(prof);
 
     // workspace: err, changed | parent[nring] | trk[nring] | nprev[nring], nnext[nring] | bcount[nb], boff[nb] | ok[nlink]
     const int64_t nb = (nring + RT_TPB - 1) / RT_TPB;
@@ -193,8 +193,8 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
     u64* d_boff = (u64*)((char*)d_bcount + b_b);
     unsigned char* d_ok = (unsigned char*)((char*)d_boff + b_b);
 
-    StageTimer tm(ctx, ctx->cptrack_ms);                                       // where the time goes (xc_set_kernel_timing)
-    auto bail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); tm.settle(); return rc; };
+    StageTimer tm(ctx, prof.ms);                                               // where the time goes (xc_set_kernel_timing)
+    auto bail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; };
     const dim3 blk(RT_TPB);
     const long long* la = (const long long*)link_a;
     const long long* lb = (const long long*)link_b;
@@ -211,12 +211,12 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
     int herr = 0;
     XC_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (herr) { tm.settle(); return fail(ctx, XC_EBADARG, std::string(who) + ": a link names a ring >= nring"); }
+    if (herr) return fail(ctx, XC_EBADARG, std::string(who) + ": a link names a ring >= nring");
 
     // the rounds: hook, compress, until nothing changed
     int rounds = 0;
     for (int changed = nlink > 0 ? 1 : 0; changed;) {
-        if ((int64_t)rounds > nring) { tm.settle(); return fail(ctx, XC_EHIP, std::string(who) + ": the rounds did not end within nring + 1"); }
+        if ((int64_t)rounds > nring) return fail(ctx, XC_EHIP, std::string(who) + ": the rounds did not end within nring + 1");
         XC_HIP(ctx, hipMemsetAsync(d_changed, 0, 4, ctx->stream));
         hipLaunchKernelGGL(k_rt_hook, dim3(rt_grid(nlink)), blk, 0, ctx->stream, nlink, la, lb, d_ok, parent, d_changed);
         hipLaunchKernelGGL(k_rt_compress, dim3(rt_grid(nring)), blk, 0, ctx->stream, nring, parent);
@@ -225,7 +225,7 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
         XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ++rounds;
     }
-    ctx->cptrack_rounds = rounds;
+    prof.rounds = rounds;
     tm.mark(1);
 
     // the dense rank of the roots: per-block counts, the host's scan, per-block ranks
@@ -244,7 +244,7 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
     const size_t b_t8 = al((size_t)nt * 8), b_t4 = al((size_t)nt * 4);
     {
         const int rc = grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, 4 * b_t8 + 2 * b_t4);
-        if (rc != XC_OK) { (void)hipStreamSynchronize(ctx->stream); tm.settle(); return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the track rows"); }
+        if (rc != XC_OK) return bail(fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the track rows"));
     }
     long long* s_first = (long long*)ctx->cpiece_acc;
     u64* s_nrings = (u64*)((char*)s_first + b_t8);
@@ -291,8 +291,5 @@ int xc_ring_tracks_dev(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
 
 int xc_last_cptrack_profile(xc_ctx* ctx, double* ms, int* rounds)
 {
-    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
-    if (ms) for (int k = 0; k < 3; ++k) ms[k] = (double)ctx->cptrack_ms[k];
-    if (rounds) *rounds = ctx->cptrack_rounds;
-    return XC_OK;
+    return xc::profile_get(ctx, &xc_ctx::prof_cptrack, 3, ms, rounds, nullptr);
 }

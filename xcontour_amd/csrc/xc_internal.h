@@ -98,16 +98,18 @@ struct xc_ctx {
     size_t cpiece_cap = (size_t)1 << 30;
     void*  cpiece_ws = nullptr;   size_t cpiece_ws_bytes = 0;    // offsets, slots, the edge tables, labels and links
     void*  cpiece_acc = nullptr;  size_t cpiece_acc_bytes = 0;   // per-piece fixed-point accumulators
-    float  cpiece_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpiece_rounds = 0, cpiece_groups = 0;   // table, rounds, roots, reductions (xc_set_kernel_timing)
-    float  cjoin_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cjoin_rounds = 0, cjoin_groups = 0;   // K14 (xc_cjoin.hip, on K13's workspace): table, label rounds, rank rounds, placement, emit
-    float  coverturn_ms[4] = {0.f, 0.f, 0.f, 0.f};  int coverturn_rounds = 0, coverturn_groups = 0;   // K16 (xc_coverturn.hip, on K13's workspace): table, rounds, pieces / select, count
-    float  cinterior_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cinterior_rounds = 0, cinterior_groups = 0;   // K17 (xc_cinside.hip, on K13's workspace): table, rounds, select, mark + scan
-    float  cpinside_ms[4] = {0.f, 0.f, 0.f, 0.f};  int cpinside_rounds = 0, cpinside_groups = 0;   // K18 (xc_cprecords.hip, on K13's workspaces): table, rounds, roots / slots / signs, walks
-    float  cptree_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  int cptree_rounds = 0, cptree_groups = 0;   // K19 (xc_cprecords.hip, on K13's workspaces): K18's four, then the tree stages
-    float  cplabel_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cplabel_rounds = 0, cplabel_groups = 0;   // K20 (xc_cprecords.hip, on K13's workspaces): K19's five, then the label scan
-    float  cpprops_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  int cpprops_rounds = 0, cpprops_groups = 0;   // K21 (xc_cprecords.hip, on K13's workspaces): K19's five, then the props scan, then the fold and the finish
-    float  cpoverlap_ms[3] = {0.f, 0.f, 0.f};  int cpoverlap_groups = 0;   // K22 (xc_cpoverlap.hip, on K13's workspaces): the run count, the accumulate pass, the finish
-    float  cptrack_ms[3] = {0.f, 0.f, 0.f};  int cptrack_rounds = 0;   // K23 (xc_cptrack.hip, on K13's workspaces): accept and degrees, the rounds, ranks and rows
+    // the last call of every entry on these workspaces: stage times (xc_set_kernel_timing), doubling rounds, groups; one record per entry
+    struct CpProfile { float ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; int rounds = 0, groups = 0; };
+    CpProfile prof_cpiece;      // K13 (xc_cpiece.hip): table, rounds, roots, reductions
+    CpProfile prof_cjoin;       // K14 (xc_cjoin.hip): table, label rounds, rank rounds, placement, emit
+    CpProfile prof_coverturn;   // K16 (xc_coverturn.hip): table, rounds, pieces / select, count
+    CpProfile prof_cinterior;   // K17 (xc_cinside.hip): table, rounds, select, mark + scan
+    CpProfile prof_cpinside;    // K18 (xc_cprecords.hip): table, rounds, roots / slots / signs, walks
+    CpProfile prof_cptree;      // K19 (xc_cprecords.hip): K18's four, then the tree stages
+    CpProfile prof_cplabel;     // K20 (xc_cprecords.hip): K19's five, then the label scan
+    CpProfile prof_cpprops;     // K21 (xc_cprecords.hip): K19's five, then the props scan, then the fold and the finish
+    CpProfile prof_cpoverlap;   // K22 (xc_cpoverlap.hip): the run count, the accumulate pass, the finish; no rounds
+    CpProfile prof_cptrack;     // K23 (xc_cptrack.hip): accept and degrees, the rounds, ranks and rows; no groups
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -117,6 +119,19 @@ int fail(xc_ctx* ctx, int code, const std::string& msg);
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set it once per (kernel, device)
 int ensure_big_lds(xc_ctx* ctx, const void* kernel, int bytes);
 int hipfail(xc_ctx* ctx, hipError_t e, const char* what);
+
+using CpProfile = xc_ctx::CpProfile;
+inline void profile_clear(CpProfile& p) { p = CpProfile(); }            // at the start of a call
+// behind every xc_last_*_profile: the first `nms` stage times, the rounds and the groups of the entry's record
+inline int profile_get(xc_ctx* ctx, CpProfile xc_ctx::* rec, int nms, double* ms, int* rounds, int* groups)
+{
+    if (!ctx) return fail(nullptr, XC_EBADARG, "null context");
+    const CpProfile& p = ctx->*rec;
+    if (ms) for (int k = 0; k < nms; ++k) ms[k] = (double)p.ms[k];
+    if (rounds) *rounds = p.rounds;
+    if (groups) *groups = p.groups;
+    return XC_OK;
+}
 
 #define XC_HIP(ctx, call)                                                     \
     do {                                                                      \
