@@ -1,12 +1,16 @@
-"""numpy / Python restatement of what K7's plan decides for the band walk, and of the band a wave of k_lwa_strip walks -- a helper for
+"""numpy / Python restatement of what K7's plan decides -- for the band walk, with the band a wave of k_lwa_strip walks, and for the
+interval kernel (fast_plan: the CG ladder, the virtual blocks, and the column groups every persistent workgroup visits) -- a helper for
 the tests, no tests here.
 
 Which staging chunk a call of k_lwa_strip took, or how many target rows a thread of k_lwa held, cannot be seen from outside the library:
 this restatement is the only witness, so test_lwa_plan_host.py pins it on a table worked out by hand from the LDS layout.
 
 Restated: lwa_strip_lds (xc_lwa_walk.h:241-255), the band-walk half of lwa_plan (xc_lwa.hip:86-110), and lwa_row_needed / lwa_span_add
-(xc_lwa_walk.h:35-52) as k_lwa_strip uses them (xc_lwa_walk.h:294-320).  The interval kernel (`want_fast`, xc_lwa.hip:68-85) is not: these
-are the calls that take the band walk -- planes of up to 512 rows, or exact=True.
+(xc_lwa_walk.h:35-52) as k_lwa_strip uses them (xc_lwa_walk.h:294-320) -- the calls that take the band walk: planes of up to 512
+rows, or exact=True.  And, for the calls that take the interval kernel, fast_plan: the interval half of lwa_plan (xc_lwa.hip:63-85),
+lwa_fast_lds (xc_lwa_fast.h:55-70), the XCD group order (xc_lwa_fast.h:98-105) and the persistent loop with its surplus skips
+(xc_lwa_fast.h:137-144); test_lwa_fast_host.py pins it on a hand-worked table.  Which plane takes the interval kernel (`want_fast`,
+xc_lwa.hip:68: the mode and the knobs) is not restated: the GPU tests ask ctx.last_lwa_path().
 """
 import numpy as np
 
@@ -15,6 +19,9 @@ LWA_SW = 8                # xc_lwa_walk.h:6: waves per workgroup of k_lwa_strip 
 LANES = 64                # columns of a strip: one per lane of a wave
 WCHUNKS = (64, 32, 16)    # xc_lwa.hip:88: staging chunks, in the order they are tried
 JT_SWITCH = 2.0e8         # xc_lwa.hip:107: ny^2 nx nslab from which a thread of k_lwa holds four target rows
+LWA_NB = 4096             # xc_lwa_fast.h:52: value buckets of the interval kernel's bracket table
+FAST_THREADS = 1024       # xc_lwa.hip:142: threads per workgroup of k_lwa_fast
+FAST_CPT = 8              # xc_lwa_fast.h:108: cells per thread and round of loads
 
 
 def strip_lds_bytes(ny, tsize, wplane, mplane, wchunk):
@@ -142,3 +149,58 @@ def workgroups(y0, y1, wchunk):
         out.append({'union': (Y0, Y1), 'chunks': -(-(Y1 - Y0) // wchunk) if Y1 > Y0 else 0, 'cut': bool(cut),
                     'late': bool(live.any() and (a[live] >= Y0 + wchunk).any())})
     return out
+
+
+# ---------------------------------------------------------------- the interval kernel
+def fast_lds_bytes(ny, CG):
+    """lwa_fast_lds(...).bytes (xc_lwa_fast.h:61-70): Q' [ny + 1] and the difference arrays D0, D1 [CG][ny + 1] in doubles, then the
+    bucket table [LWA_NB + 1] in ints"""
+    L = ny + 1
+    return (L + 2 * CG * L) * 8 + (LWA_NB + 1) * 4
+
+
+def fast_group_x0(vb, CG):
+    """group_x0 (xc_lwa_fast.h:102-105): the first column of virtual block vb = 8 k + xcd -- the 16 / CG groups of a 16-column line stay
+    on one XCD"""
+    GQ = 16 // CG
+    kq, xcd = vb >> 3, vb & 7
+    return (((kq // GQ) * 8 + xcd) * GQ + kq % GQ) * CG
+
+
+def fast_plan(nslab, ny, nx, cus=256):
+    """the interval kernel of one call -> None where no rung of the CG ladder fits (or the plane has 2^29 cells or more:
+    xc_lwa.hip:69), else a dict: 'CG' columns per workgroup, 'lds_bytes', 'nvb' virtual blocks, 'grid' (x, y), 'visits' -- for every
+    block of grid x the (x0, ncol) of the column groups it runs, in order -- and 'skips' -- for every block the surplus virtual blocks it
+    steps over, as ('entry' | 'mid', trip): on entry (xc_lwa_fast.h:138, before its first group) or in mid-loop (:144, behind one)"""
+    if cus <= 0:
+        cus = 256                                                                   # xc_lwa.hip:67
+    CG = 0
+    if ny * nx < (1 << 29):                                                         # xc_lwa.hip:69
+        for c in (4, 2, 1):                                                         # xc_lwa.hip:70-71
+            if not CG and fast_lds_bytes(ny, c) <= LDS_BUDGET:
+                CG = c
+    if not CG:
+        return None
+    ngrp, gq = (nx + CG - 1) // CG, 8 * (16 // CG)                                  # xc_lwa.hip:77
+    nvb = ((ngrp + gq - 1) // gq) * gq                                              # xc_lwa.hip:78
+    pw = max(8, (cus // 8) * 8)                                                     # xc_lwa.hip:81-82
+    gx = min(nvb, pw)                                                               # xc_lwa.hip:83
+    visits, skips = [], []
+    for b in range(gx):
+        v, sk = [], []
+        for trip, vb in enumerate(range(b, nvb, gx)):                               # xc_lwa_fast.h:137-144, 236
+            x0 = fast_group_x0(vb, CG)
+            if x0 >= nx:
+                sk.append(('mid' if v else 'entry', trip))
+            else:
+                v.append((x0, min(CG, nx - x0)))                                    # xc_lwa_fast.h:142
+        visits.append(v)
+        skips.append(sk)
+    return {'CG': CG, 'lds_bytes': fast_lds_bytes(ny, CG), 'nvb': nvb, 'grid': (gx, nslab), 'visits': visits, 'skips': skips}
+
+
+def fast_rounds(ny, CG):
+    """-> (cells of a group, rounds of FAST_CPT * FAST_THREADS cells its search loop makes (xc_lwa_fast.h:147), the `split` of its
+    prefix sums (xc_lwa_fast.h:203: 2 while four tasks per column fit the 16 waves))"""
+    ncell = ny * CG
+    return ncell, -(-ncell // (FAST_CPT * FAST_THREADS)), (2 if 4 * CG <= FAST_THREADS // 64 else 1)

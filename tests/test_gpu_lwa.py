@@ -12,6 +12,7 @@ import pytest
 import xcontour_oracle as O
 from test_gpu_parity import rel, RTOL, TIGHT, LMIN_FLOOR, _baro_da
 from gpu_common import GOLD, NINE, ROOT, bits, check_nine, check_nine_det, _clean_env
+from lwa_fast_cases import lwa_rows as _lwa_rows        # the oracle's loop body for chosen target rows (shared with test_gpu_lwa_fast.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -208,24 +209,6 @@ def test_lwa_interval_kernel_tall_planes_and_odd_reference_states(ctx, ny, nx, d
             ref = O.cal_local_wave_activity(qs[s], Qs[s], lat, dA if not da_row else dAu[:, None] * np.ones((1, nx)), True, 'all')
             scale = np.abs(ref).max()
             assert np.isfinite(scale) and np.abs(got[s] - ref).max() <= 1e-11 * max(scale, 1e-300), (k, s)
-
-
-def _lwa_rows(q, Q, coord, dA, rows, increase=True):
-    """core.py:752-791 for the target rows `rows` only (the oracle's own loop body, one j at a time: a full 1801-row plane has 1801
-    of them at ~0.2 s each)"""
-    q64 = q.astype(np.float64)
-    wei = dA / np.nanmax(dA)
-    cinc = not (coord[-1] < coord[0])
-    out = np.empty((len(rows), q.shape[1]))
-    for i, j in enumerate(rows):
-        qe = q64 - Q[j]                                                               # core.py:754
-        m = ((coord >= coord[j]) if cinc else (coord <= coord[j]))[:, None]
-        if increase:                                                                   # core.py:759-766
-            mask3 = np.where(np.logical_and(qe < 0, m), 1, np.where(m, 0, np.where(qe > 0, -1, 0)))
-        else:
-            mask3 = np.where(np.logical_and(qe > 0, m), 1, np.where(m, 0, np.where(qe < 0, -1, 0)))
-        out[i] = -np.nansum(qe * mask3.astype(np.float64) * wei * dA, axis=0)         # core.py:789 (M = dA)
-    return out
 
 
 def test_lwa_interval_kernel_at_the_full_cfg2_size(ctx):
