@@ -896,6 +896,67 @@ int xc_ring_tracks_dev(xc_ctx* ctx, int64_t nring, int64_t nlink,
                        int64_t* first_ring, int32_t* first_step, int32_t* last_step, int64_t* nrings, int64_t* nsplit, int64_t* nmerge);
 int xc_last_cptrack_profile(xc_ctx* ctx, double* ms, int* rounds);
 
+/* ------------------------------------------------------------------ K24 contour folds: wave-breaking events
+ * K16 says which meridians are overturned, K17 what the selected pieces bound.  The step after both (the Barnes and Hartmann 2012 kind
+ * of analysis, where the reference's Subroutines 3-5 were heading): which runs of overturned meridians form one EVENT, where it sits,
+ * how much has folded over in it, and which way it leans.  Build-defined; index space; the field is not read again.
+ * Input exactly as for K17: count[nrange], e_from, e_to, pts where the K12 _dev entry points left them, ny, nx, periodic, select, ncont,
+ * w, w_per_slab, f, f_dtype, with K17's limits and XC_EBADARG cases (2 ny nx < 2^31, edge ids in range, select != 0 needs periodic,
+ * nrange % ncont == 0, at most 65535 slabs); nrange nx < 2^38; and gap, 0 <= gap < nx, else XC_EBADARG.  There is no flip.
+ *   CROSSINGS      X[r][c], 0 <= r < ny - 1, and P[r][c] are K17's, bit for bit, under the same select.  For a column c:
+ *                  n[c] = sum_r X[r][c] (K16's ncross on K12's records), lo[c] / hi[c] the smallest / largest r with X[r][c] = 1.
+ *   FOLDED COLUMN  n[c] >= 3.
+ *   FOLD NODES     of a folded column: the nodes (r, c), lo[c] < r <= hi[c] -- those between its lowest and its highest crossed edge.
+ *                  Each belongs to a tongue t = P[r][c] ^ P[lo[c] + 1][c]: t = 0 'under' (air of the side beyond the lowest crossing,
+ *                  lying under air of the near side), t = 1 'over' (air of the side of row 0, lying over it).  Neither depends on K17's flip.
+ *   EVENT          a maximal set of folded columns in which consecutive folded columns are separated by at most `gap` unfolded columns;
+ *                  on a periodic plane column nx - 1 is followed by column 0.  c_west is its first column (the gap + 1 columns in front
+ *                  of it hold no folded column), c_east its last folded column.  A periodic range without such a first column (every
+ *                  cyclic gap <= `gap`) is ONE event, c_west its smallest folded column, c_east the last one reached going east.  The
+ *                  events of a range are ordered by c_west ascending; one that runs across the seam has c_east < c_west.
+ *                  dx(c) = (c - c_west) mod nx for a column of the event.
+ *   per (range, column), dense [nrange][nx], always fully written:
+ *     ncross int32            n[c]
+ *     row_lo, row_hi f64      K16's: the smallest / largest stored row (r1 of a start point, r2 of a tail) over the crossings of the
+ *                             column, bit for bit; NaN where ncross == 0
+ *     col_event int32         the index of the column's event within its range for a folded column, else -1 (an unfolded column
+ *                             bridged by `gap` too)
+ *   per event, packed by range (the events of range r are [eoff[r], eoff[r+1]), eoff the exclusive scan of event_count; inside a range
+ *   in the order above):
+ *     c_west, c_east int32    first column, last folded column
+ *     ncol int32              its folded columns;   ncross_max int32   the largest ncross over them
+ *     ev_row_lo, ev_row_hi f64   the min of row_lo / the max of row_hi over them, copied bit for bit
+ *     nodes int64 [.][2]      the fold nodes of tongue t: nodes[2 e + t]; the five below are laid out alike
+ *     area f64 [.][2]         the sum of w over them (w == NULL: weight 1); w as K17 reads it
+ *     mx f64 [.][2]           the sum of w * (double)dx(c), each product rounded once
+ *     my f64 [.][2]           the sum of w * (double)r, each product rounded once
+ *     integral f64 [.][2]     the sum of w * f, each product rounded once, f32 widened first; NULL exactly when f is
+ *   The float sums are K13's exact sums: every term whole into fixed-point limbs, rounded once -- independent of order, chunks, groups
+ *   and launch geometry.  Each has a window of 160 bits under 2^top, top = 12 + the frexp exponent of a bound on one term, never below
+ *   -800: with max |w| and max |w f| over the finite values of the range's slab as K17 takes them (all of the plane), the bound is
+ *   max |w| for area, max |w| * nx for mx, max |w| * ny for my (the float64 product; one that overflows counts as the largest finite
+ *   double), max |w f| for integral.  The bits of a term under 2^(top - 160) are cut off toward zero.  A NaN term is skipped; a +-inf
+ *   term makes THAT sum of THAT tongue of THAT event NaN, and no other.
+ *   event_count[nrange] and the dense column arrays are always written.  capacity >= sum(event_count): the event arrays are written,
+ *   XC_OK.  Otherwise nothing is written to the event arrays and 1 is returned (capacity 0 with NULL event arrays = count only: the
+ *   sums are then not computed, and w and f not read).  A range has at most ceil(nx / 2) events.
+ *   On records that are not K12's every access still stays in bounds and every loop ends, as K16 and K17 promise: n[c] counts flags
+ *   (an edge named twice counts once), the rows are taken over every crossing K16 would count.
+ * The call waits for the stream twice (K12's counts; the event counts, with the word that says whether the ids were in range).  It
+ * works in K13's groups of ranges under K13's cap and in K13's workspace (xc_set_cpiece_workspace; the result does not depend on it),
+ * with K17's bit planes, two int32 per (range, column), 112 bytes per (range, possible event) and 340 per (range of a group, possible
+ * event).  With xc_set_kernel_timing on, xc_last_cfold_profile returns the last call's device times in ms -- ms[0] edge tables, ms[1]
+ * the doubling rounds, ms[2] per-piece sums and the selection (as K17), ms[3] the marks and the column pass, ms[4] the run pass, ms[5]
+ * the fold scan and the finish (with the bounds of the windows and the compaction) -- the rounds summed over the groups, and the groups. */
+int xc_contour_folds_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                         int64_t ny, int64_t nx, int periodic, int select, int ncont, const double* w, int w_per_slab, const void* f,
+                         int f_dtype, int64_t gap,
+                         int32_t* ncross, double* row_lo, double* row_hi, int32_t* col_event,                     /* [nrange][nx] */
+                         int64_t capacity, uint64_t* event_count,                                                 /* [nrange] */
+                         int32_t* c_west, int32_t* c_east, int32_t* ncol, int32_t* ncross_max, double* ev_row_lo, double* ev_row_hi,
+                         int64_t* nodes, double* area, double* mx, double* my, double* integral);
+int xc_last_cfold_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -168,6 +168,9 @@ PROTOTYPES = {
     'xc_contour_interior_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                           _vp, C.c_int, _vp, _vp, _vp, _vp]),
     'xc_last_cinterior_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_folds_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64,
+                                       _vp, _vp, _vp, _vp, _i64, _vp] + [_vp] * 11),
+    'xc_last_cfold_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'xc_contour_piece_interiors_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                                  _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_last_cpinside_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -1463,6 +1466,73 @@ class Context(object):
             nb = [n * N * 8, n * N * 8] + ([n * N * 8] if has_f else []) + ([n * N * ny * nx] if want_mask else [])
             return self._with_segment_records(periodic, qb, cb, interior, inputs=[v for v in (wb, fb) if v is not None], out_nbytes=nb)
         return self._batched(a.nslab, a.slab_bytes(N if want_mask else 0), one)
+
+    # the per-event table of `contour_folds`: the library's record, the two tongues (0 under, 1 over) side by side
+    FOLD_DTYPE = np.dtype([('c_west', np.int32), ('c_east', np.int32), ('ncol', np.int32), ('ncross_max', np.int32),
+                           ('row_lo', np.float64), ('row_hi', np.float64), ('nodes', np.int64, (2,)), ('area', np.float64, (2,)),
+                           ('mx', np.float64, (2,)), ('my', np.float64, (2,)), ('integral', np.float64, (2,))])
+
+    def last_cfold_profile(self):
+        """device times of the last `contour_folds` call of the library under set_kernel_timing(True): dict(table_ms, rounds_ms,
+        select_ms, columns_ms, runs_ms, scan_ms, rounds, groups)"""
+        return self._last_profile('cfold', ('table', 'rounds', 'select', 'columns', 'runs', 'scan'))
+
+    def contour_folds(self, q, contours, w=None, f=None, periodic=False, select='main', gap=0):
+        """The folds of every contour gathered into events (K24, xc_contour_folds_dev, on the device records of K12: the segment
+        records are never downloaded).  q, contours, periodic, select, w and f as for `contour_interior`.  A column is FOLDED when
+        the selected pieces cross its grid line three times or more; its fold nodes are those between the lowest and the highest
+        crossed edge, of tongue 0 ('under') where the crossings between the lowest one and the node are even in number, else of
+        tongue 1 ('over').  An EVENT is a maximal run of folded columns with at most `gap` unfolded columns between consecutive
+        ones, round the seam on a periodic plane.  One K12 call, then a count-only call and a sized one.  Returns (ncross int32,
+        row_lo, row_hi float64 (nslab, N, nx): `contour_overturning`'s; col_event int32 (nslab, N, nx): the event of a folded
+        column within its contour, else -1; event_count uint64 (nslab, N); events: a structured array (FOLD_DTYPE) of all events
+        packed by (slab, contour), each range ordered by c_west -- c_west, c_east, ncol, ncross_max, row_lo, row_hi, and per tongue
+        nodes, area (the sum of w), mx, my (of w dx, w row; dx the columns east of c_west), integral (of w f; NaN without f) --
+        exact sums rounded once, NaN terms skipped, an infinite term makes that sum of that tongue of that event NaN)."""
+        a = _RecordArgs('xc_contour_folds', q, contours, select=select, periodic=periodic, min_nx=2, labels32=True, w=w, f=f)
+        ny, nx, N = a.ny, a.nx, a.N
+        if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)) or not 0 <= gap < nx:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_folds: gap must be an int in [0, nx), not %r' % (gap,))
+        has_w, has_f = a.w is not None, a.f is not None
+        dt = self.FOLD_DTYPE
+        cols = [(k,) + ((dt[k].base, 2) if dt[k].shape else (dt[k],)) for k in
+                ('row_lo', 'row_hi', 'nodes', 'area', 'mx', 'my', 'integral', 'c_west', 'c_east', 'ncol', 'ncross_max')]
+        dense = (np.int32, np.float64, np.float64, np.int32)
+
+        def folds(cnt, total, dn, ins, outs, recs):
+            n = cnt.shape[0]
+            dw, df_ = (ins[0] if has_w else None), (ins[-1] if has_f else None)
+            dec = outs[4]
+            rec = [b.ptr for b in recs] if total else [None, None, None]
+            head = (self.handle, cnt.size, dn.ptr, rec[0], rec[1], rec[2], ny, nx, 1 if periodic else 0, int(a.sel), N,
+                    dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, df_.ptr if has_f else None,
+                    dtype_code(a.f.dtype) if has_f else 0, int(gap)) + tuple(b.ptr for b in outs[:4])
+
+            def k24(cap, evs):
+                at = _Columns(evs[0], cap, cols) if evs else None
+                names = ('c_west', 'c_east', 'ncol', 'ncross_max', 'row_lo', 'row_hi', 'nodes', 'area', 'mx', 'my', 'integral')
+                ptrs = [at.ptr(k, k != 'integral' or has_f) for k in names] if evs else [None] * 11
+                return self.lib.xc_contour_folds_dev(*head, cap, dec.ptr, *ptrs)
+            with self._two_pass(k24, dec, (n, N), lambda ne: [ne * _row_bytes(cols)]) as (ec, ne, evs):
+                ev = np.empty(ne, dtype=dt)
+                if ne:
+                    at = _Columns(evs[0], ne, cols)
+                    for k in dt.names:
+                        if k == 'integral' and not has_f:
+                            ev[k] = np.nan
+                        elif dt[k].shape:
+                            ev[k] = at.buf.download((ne, 2), dt[k].base, offset_bytes=at.at[k])
+                        else:
+                            ev[k] = at.get(k, (ne,))
+                return tuple(b.download((n, N, nx), t) for b, t in zip(outs[:4], dense)) + (ec, ev)
+
+        def one(s0, s1):
+            # beside K12's records: the weights and the integrand, the four dense outputs -- 24 bytes per (contour, column) --, the event counts
+            n = s1 - s0
+            qb, cb, wb, fb = a.batch(s0, s1)[:4]
+            nb = [n * N * nx * 4, n * N * nx * 8, n * N * nx * 8, n * N * nx * 4, n * N * 8]
+            return self._with_segment_records(periodic, qb, cb, folds, inputs=[v for v in (wb, fb) if v is not None], out_nbytes=nb)
+        return self._batched(a.nslab, a.slab_bytes() + N * nx * 24, one)
 
     # the per-piece table of `contour_piece_interiors`: K13's key fields and what the piece encloses
     PIECE_INTERIOR_DTYPE = np.dtype([('first_edge', np.int64), ('nseg', np.int64), ('closed', np.bool_), ('winding', np.int32),

@@ -1075,6 +1075,123 @@ class Contour2D(object):
             out.append(lb.wrap(m.reshape(shape + (ny, nx)), dims + (self.dimEqV, self._xdim), cm, 'mask', data))
         return lb.merge(out, data)
 
+    # ------------------------------------------------------------------ contour folds
+    # an event as the facade returns it: where it sits, and what each tongue holds
+    FOLD_FIELDS = ([(k, np.int32) for k in ('c_west', 'c_east', 'ncol', 'ncross_max', 'width')] +
+                   [(k, np.float64) for k in ('x_west', 'x_east', 'y_lo', 'y_hi')] +
+                   [(k + t, d) for k, d in (('nodes', np.int64), ('area', np.float64), ('integral', np.float64), ('cy', np.float64),
+                                            ('cx', np.float64)) for t in ('_under', '_over')] + [('orientation', np.int8)])
+
+    @staticmethod
+    def _fold_x(col, xg, period):
+        """fractional columns -> the X coordinate: np.interp over the columns; on a ring column nx is xg[0] + period, and a column
+        past it runs on by the period"""
+        nx = xg.size
+        if period is None:
+            return np.interp(col, np.arange(nx), xg)
+        k = np.floor(col / nx)
+        return np.interp(col - k * nx, np.arange(nx + 1), np.append(xg, xg[0] + period)) + k * period
+
+    def cal_contour_folds(self, contours, tracer=None, integrand=None, periodic=False, select='main', gap=0):
+        """
+        The wave-breaking events of every contour, computed on the GPU (K12's segments, K13's pieces, K16's selection, K17's
+        crossing flags, K24, xc_contour_folds_dev): which runs of overturned meridians form one event, where it sits, how much
+        each event has folded over and which way it leans.  cal_contour_overturning says which columns are overturned and
+        cal_integral_inside_contours what the ring bounds; this is the step after both.  Build-defined: the reference has no
+        counterpart.  Only the per-column arrays and one small table per contour cross to the host.
+
+        `contours`, `tracer`, `periodic`, `select`, the order of the levels and the errors as for cal_contour_overturning;
+        `integrand` and the weight (this object's dA) as for cal_integral_inside_contours.  `gap`: an int >= 0 (and below the
+        number of columns).
+
+        A column is folded when the selected pieces cross its grid line three times or more (ncross >= 3).  Its fold nodes are
+        the nodes between the lowest and the highest crossed grid edge (in index space, rows counted from the first).  Walking up
+        from the lowest crossing, the nodes passed before the next crossing form the tongue `under`, those after it `over`, and
+        so on in turn: `under` is air from beyond the lowest crossing lying under air of the first row's side, `over` is air of
+        the first row's side lying over it.  An event is a maximal run of folded columns with at most `gap` unfolded columns
+        between consecutive ones; on a periodic plane the last column is followed by the first, and an event across the seam has
+        c_east < c_west.
+
+        Returns (cols, events).  `cols`: a Dataset over (..., contour, X) -- `ncross`, `y_lo`, `y_hi`: cal_contour_overturning's,
+        bit for bit; `event` (int32): the index of the column's event in its contour's table, -1 for none (an unfolded column
+        bridged by `gap` too).  `events`: per level a numpy structured array with one row per event, ordered by c_west -- out[k]
+        when the tracer has no leading dims, else out[slab][k] with the leading dims flattened, like cal_contour_pieces:
+          c_west, c_east  the first column, the last folded column;  ncol  its folded columns;  ncross_max  the most crossings;
+          width  (c_east - c_west) mod nx + 1;  x_west, x_east  the X coordinate at those columns;
+          y_lo, y_hi  the extent of the crossings along the equivalent dim, mapped and swapped like cal_contour_overturning's;
+          nodes_under, nodes_over  the fold nodes of each tongue;  area_*  the sum of dA over them;  integral_*  the sum of
+          dA * integrand, each product rounded once (NaN without an integrand);
+          cy_*  the dA-weighted mean row of the tongue mapped with np.interp onto the equivalent dim's coordinate;  cx_*  the
+          dA-weighted mean column, counted east from c_west, mapped onto the X coordinate (past the last column it runs on by
+          the period, like find_contours' rings);
+          orientation (int8)  the sign of the mean column of `over` minus that of `under`: +1 when the overlying tongue leans
+          east of the underlying one, -1 west, 0 where either tongue has area 0 or NaN.  Which sign is cyclonic and which
+          anticyclonic depends on the hemisphere and on whether the tracer increases towards the pole (`increase`): that is
+          left to the caller.
+        The sums are exact sums of their float64 terms rounded once: bit-reproducible, whatever the order; a NaN term is
+        skipped, an infinite one makes that sum of that tongue NaN.  A NaN level, or a level without segments, gives an empty array.
+        """
+        who = 'cal_contour_folds'
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        if select not in nat.Context.OVERTURN_SELECT:
+            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
+        if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, np.integer)) or gap < 0:
+            raise Exception('%s: gap should be an int >= 0, not %r' % (who, gap))
+        data, dcoords = self._plane_dcoords(who, tracer)
+        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
+        period = self._x_period(periodic, xg, False, who, plain=True)
+        ring = period is not None
+        if select != 'all' and not ring:
+            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
+                            'periodic=True or the period, or select=\'all\'' % (who, select))
+        q, lead, lshape, coords = self._float_plane(data)
+        nslab, ny, nx = q.shape
+        if gap >= nx:
+            raise Exception('%s: gap=%r should be below the %d columns of the plane' % (who, gap, nx))
+        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
+        dA = self._dA_array(ny, nx, nslab)[0]
+        if dA.ndim == 1:
+            dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
+        g = None
+        if integrand is not None:
+            g = self._integrand_plane(integrand)
+            if g.shape != q.shape:
+                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
+        ncross, row_lo, row_hi, cev, ec, tab = self.ctx.contour_folds(q, bs, w=dA, f=g, periodic=ring, select=select, gap=int(gap))
+        # the columns, every level where the caller put it
+        ncross, row_lo, row_hi, cev = (_level_order(v, order[:, :, None]) for v in (ncross, row_lo, row_hi, cev))
+        rows = np.arange(yg.size)
+        ya, yb = np.interp(row_lo, rows, yg), np.interp(row_hi, rows, yg)
+        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
+        c['contour'] = np.asarray(ccoord)
+        c[self._xdim] = np.asarray(dcoords[self._xdim])
+        dims = tuple(lead) + ('contour', self._xdim)
+        shape = tuple(lshape) + ncross.shape[1:]
+        cols = lb.merge([lb.wrap(v.reshape(shape), dims, c, name, data) for name, v in
+                         (('ncross', ncross), ('y_lo', np.minimum(ya, yb)), ('y_hi', np.maximum(ya, yb)), ('event', cev))], data)
+        # the events
+        rec = np.zeros(tab.size, dtype=self.FOLD_FIELDS)
+        for k in ('c_west', 'c_east', 'ncol', 'ncross_max'):
+            rec[k] = tab[k]
+        rec['width'] = (tab['c_east'] - tab['c_west']) % nx + 1
+        rec['x_west'], rec['x_east'] = xg[tab['c_west']], xg[tab['c_east']]
+        ea, eb = np.interp(tab['row_lo'], rows, yg), np.interp(tab['row_hi'], rows, yg)
+        rec['y_lo'], rec['y_hi'] = np.minimum(ea, eb), np.maximum(ea, eb)
+        with np.errstate(all='ignore'):
+            mcol = tab['mx'] / tab['area']                       # the mean column east of c_west, per tongue
+            mrow = tab['my'] / tab['area']
+            for t, name in enumerate(('_under', '_over')):
+                rec['nodes' + name], rec['area' + name], rec['integral' + name] = tab['nodes'][:, t], tab['area'][:, t], tab['integral'][:, t]
+                rec['cy' + name] = np.interp(mrow[:, t], rows, yg)
+                rec['cx' + name] = self._fold_x(tab['c_west'] + mcol[:, t], xg, period)
+            lean = mcol[:, 1] - mcol[:, 0]
+            ok = ~np.isnan(tab['area']).any(axis=1) & (tab['area'] != 0.0).all(axis=1) & ~np.isnan(lean)
+            rec['orientation'] = np.where(ok, np.sign(np.where(ok, lean, 0.0)), 0.0).astype(np.int8)
+        eoff = np.concatenate([[0], np.cumsum(ec.ravel().astype(np.int64))])
+        events = self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(eoff[:-1], eoff[1:])])[0]
+        return cols, events
+
     def cal_integral_inside_pieces(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
         """
         Area, node count and integral of what EVERY piece of every contour bounds, computed on the GPU in one call (K12's

@@ -21,7 +21,8 @@
 //   the group's bit planes are cleared: ny rows of wpr = ceil(nx / 32) 32-bit words per range, bit c & 31 of word c >> 5 of row r is
 //                   X[r][c] -- the 64 lanes of a wave of the scan (consecutive columns) read two consecutive words per row
 //   phase A (K13's kernels), k_co_root, k_co_piece, k_co_pick (K16's selection)
-//   k_ci_mark       one thread per segment of a selected piece: an atomic OR of its crossing bit(s); every id is checked first
+//   k_ci_mark       (xc_cinside_mark.h, shared with K24, like k_ci_chunk) one thread per segment of a selected piece: an atomic OR of its
+//                   crossing bit(s); every id is checked first
 //   k_cp_unscatter  the table is handed on clean
 //   k_ci_chunk      (only where the rows are cut into more than one chunk) the XOR of every bit-plane word over the rows of each chunk
 //   k_ci_scan       over the ranges from the end of the previous group to the end of this one (ranges without segments in front of the
@@ -47,61 +48,7 @@ namespace {
 #include "xc_cpiece_select.h"
 #include "xc_cpiece_sum.h"
 #include "xc_cinside_bound.h"
-
-constexpr int CI_MIN_ROWS = 4;                // a chunk of rows is never shorter (but for the last one) ...
-constexpr int CI_MAX_CHUNKS = 64;             // ... and a column is never cut into more chunks
-constexpr int64_t CI_BLOCKS = 4096;           // the rows are cut until the scan has about this many blocks
-
-template <typename T>
-__device__ __forceinline__ T ci_wave_sum(T v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__global__ __launch_bounds__(CP_TPB)
-void k_ci_mark(int64_t n, long long s0, int64_t r0, long long E, int64_t nx, int64_t wpr, size_t plane, int select,
-               const long long* __restrict__ e_from, const long long* __restrict__ e_to, const int* __restrict__ tab,
-               const int* __restrict__ rid, const int* __restrict__ root, const int* __restrict__ prv, const int* __restrict__ lab,
-               const unsigned* __restrict__ pn, const int* __restrict__ pw, const unsigned long long* __restrict__ key,
-               unsigned* __restrict__ bits)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= n) return;
-    const int t = root[i], r = rid[i];                                // (k_co_root left 0 <= t < n)
-    const bool ring = prv[i] >= 0;
-    int w; bool ismain;
-    if (!co_selected(select, ring, t, lab[i], pn, pw, key[r0 + r], w, ismain)) return;
-    auto cross = [&](long long e) {                                   // 0 <= e < E: the node e >> 1 lies on the plane
-        const long long node = e >> 1, row = node / nx, col = node - row * nx;
-        atomicOr(bits + (size_t)r * plane + (size_t)row * (size_t)wpr + (size_t)(col >> 5), 1u << (col & 31));
-    };
-    const long long ef = e_from[s0 + i];
-    if ((ef & 1) && ef >= 0 && ef < E) cross(ef);
-    if (!ring) {
-        const long long et = e_to[s0 + i];
-        if ((et & 1) && et >= 0 && et < E) {
-            const int j = tab[(size_t)r * E + et];
-            if (j < 0 || j >= n) cross(et);                           // no successor: the tail of its piece
-        }
-    }
-}
-
-// cpar[g][chunk][word] = the XOR of the bit plane's words over the rows of the chunk
-__global__ __launch_bounds__(CP_TPB)
-void k_ci_chunk(int64_t nwords, int64_t ny, int64_t wpr, int64_t rc, int64_t nchunk, const unsigned* __restrict__ bits,
-                unsigned* __restrict__ cpar)
-{
-    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (i >= nwords) return;
-    const int64_t word = i % wpr, ch = (i / wpr) % nchunk, g = i / (wpr * nchunk);
-    const int64_t ra = ch * rc, rb = ra + rc < ny ? ra + rc : ny;
-    const unsigned* bp = bits + (size_t)g * (size_t)ny * (size_t)wpr + (size_t)word;
-    unsigned x = 0u;
-    for (int64_t r = ra; r < rb; ++r) x ^= bp[(size_t)r * (size_t)wpr];
-    cpar[i] = x;
-}
+#include "xc_cinside_mark.h"
 
 // Ranges [ra, ra + nr): block b is (column block, chunk, range).  Ranges of [g0, g1) have the bit plane bits[range - g0]; the others none.
 template <typename FT, bool MASK>
@@ -217,11 +164,8 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
     XC_TRY(cp_plan(ctx, "xc_contour_interior", nrange, count, nullptr, e_from, e_to, pts, E, pl));
     // the scan's geometry: 256 columns x rc rows x one range per block
-    const int64_t wpr = (nx + 31) / 32, ncb = (nx + CI_TPB - 1) / CI_TPB;
-    int64_t nchunk = (CI_BLOCKS + ncb * nrange - 1) / (ncb * nrange);
-    nchunk = std::min<int64_t>(std::min<int64_t>(nchunk, CI_MAX_CHUNKS), std::max<int64_t>(1, ny / CI_MIN_ROWS));
-    const int64_t rc = (ny + nchunk - 1) / nchunk;
-    nchunk = (ny + rc - 1) / rc;
+    const CiGeom geo = ci_geometry(ny, nx, nrange);
+    const int64_t wpr = geo.wpr, ncb = geo.ncb, nchunk = geo.nchunk, rc = geo.rc;
     const size_t plane = (size_t)ny * (size_t)wpr;
     // workspace: off | key, nsel, mx, acc, cnt, flg (cleared together) | err | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | the tail
     //            (xc_cpiece_link.h)

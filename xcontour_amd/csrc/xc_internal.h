@@ -110,6 +110,7 @@ struct xc_ctx {
     CpProfile prof_cpprops;     // K21 (xc_cprecords.hip): K19's five, then the props scan, then the fold and the finish
     CpProfile prof_cpoverlap;   // K22 (xc_cpoverlap.hip): the run count, the accumulate pass, the finish; no rounds
     CpProfile prof_cptrack;     // K23 (xc_cptrack.hip): accept and degrees, the rounds, ranks and rows; no groups
+    CpProfile prof_cfold;       // K24 (xc_cfold.hip): table, rounds, select, mark + columns, runs, fold scan + finish
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -378,6 +379,12 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
 int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
                             int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
                             const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask);
+// K24: the folded columns of the selected pieces of K12's records (device pointers) gathered into events; waits for the stream twice
+int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                         int64_t ny, int64_t nx, int periodic, int select, int ncont, const double* w, int w_per_slab, const void* f,
+                         int f_dtype, int64_t gap, int32_t* ncross, double* row_lo, double* row_hi, int32_t* col_event, int64_t capacity,
+                         uint64_t* event_count, int32_t* c_west, int32_t* c_east, int32_t* ncol, int32_t* ncross_max, double* ev_row_lo,
+                         double* ev_row_hi, int64_t* nodes, double* area, double* mx, double* my, double* integral);
 // K18-K21 (xc_contour_piece_{interiors,tree,labels,props}_dev) have one launcher of their own file: xc_cprecords.hip
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
