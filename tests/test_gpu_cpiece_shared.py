@@ -16,7 +16,11 @@ order and compared as they are, guard elements included.
 The last case puts a K14 call that is refused for a repeated edge id between two K13 calls, under kernel timing.  A refused K14 call has
 run every group before the error word is read, so its profile holds its own groups and rounds (the library has always reported them;
 they are compared to the same refused call on a fresh context) -- what must not happen is that it touches K13's record or leaves a
-table behind on which the next call goes wrong."""
+table behind on which the next call goes wrong.
+
+The case behind it runs K24, K22 and K23 (contour_folds, label_overlap, ring_tracks) between K13, K16 and K17 through the package's
+methods, on inputs of two sizes: all six lay out the context's two grow-only workspaces, each in its own way, and a layout that is
+smaller than the one before it, or larger, must come out the same."""
 import itertools
 
 import numpy as np
@@ -160,3 +164,95 @@ def test_a_refused_polylines_call_between_two_pieces_calls(ctx):
         assert profile(ctx, 'polylines') == its_own
     finally:
         ctx.set_kernel_timing(False)
+
+
+# ------------------------------------------------------------------ K24, K22 and K23 between K13, K16 and K17: layouts of different sizes
+LEV3 = np.array([-0.4, 0.1, 0.5])
+SIZES = {'large': (2, 24, 40), 'small': (1, 6, 8)}
+ENTRIES = ('folds', 'pieces', 'overlap', 'overturning', 'tracks', 'interior')
+ORDERS = {'small then large': [(e, s) for s in ('small', 'large') for e in ENTRIES],
+          'large then small': [(e, s) for s in ('large', 'small') for e in ENTRIES],
+          'alternating': [(e, ('small', 'large')[(k + j) % 2]) for j in range(2) for k, e in enumerate(ENTRIES)]}
+
+
+def flat(out):
+    """the bytes of whatever a method returned: arrays, None, tuples and dicts of them"""
+    if isinstance(out, dict):
+        return [(k, flat(out[k])) for k in sorted(out)]
+    if isinstance(out, (tuple, list)):
+        return [flat(v) for v in out]
+    return b'' if out is None else np.ascontiguousarray(out).tobytes()
+
+
+def ring_graph(nring, nlink, seed):
+    """rings in steps of about eight, links between the rings of consecutive steps: ring_step, ring_size, link_a, link_b, link_n"""
+    rng = np.random.default_rng(seed)
+    step = (np.arange(nring) // 8).astype(np.int32)
+    size = rng.integers(1, 50, nring).astype(np.int64)
+    a = rng.integers(0, max(1, nring - 8), nlink).astype(np.int64)
+    b = np.minimum(a + rng.integers(1, 9, nlink), nring - 1).astype(np.int64)
+    return step, size, a, b, rng.integers(0, 40, nlink).astype(np.int64)
+
+
+def inputs(size, periodic):
+    """the fields, weights, label maps (K20's, made on a context of their own) and the ring graph of one size"""
+    ns, ny, nx = SIZES[size]
+    seed = 500 + ny
+    q, q2 = (np.stack([CS.smooth_noise(ny, nx, seed + 10 * k + s) for s in range(ns)]) for k in range(2))
+    rng = np.random.default_rng(seed)
+    d = {'q': q, 'w': scaled(rng, (ns, ny, nx)), 'f': scaled(rng, (ns, ny, nx), np.float32),
+         'yc': np.arange(ny, dtype=np.float64), 'xc': np.arange(nx, dtype=np.float64), 'ny': ny, 'nx': nx,
+         'graph': ring_graph(700, 900, seed) if size == 'large' else ring_graph(5, 4, seed)}
+    maker = nat.Context(0)
+    try:
+        d['la'], d['lb'] = (maker.contour_piece_labels(v, LEV3, periodic=bool(periodic))[2] for v in (q, q2))
+    finally:
+        maker.close()
+    return d
+
+
+def one_call(c, entry, d, periodic, rows):
+    """`entry` through the package's method under a cap of `rows` table rows of the call's own plane -> the bytes of all it returned"""
+    per, sel = bool(periodic), 'main' if periodic else 'all'
+    c.set_cpiece_workspace(rows * 2 * d['ny'] * d['nx'] * 4)
+    try:
+        if entry == 'folds':
+            out = c.contour_folds(d['q'], LEV3, w=d['w'], f=d['f'], periodic=per, select=sel, gap=1)
+        elif entry == 'pieces':
+            out = c.contour_pieces(d['q'], LEV3, d['yc'], d['xc'], period=float(d['nx']) if per else None)
+        elif entry == 'overlap':
+            out = c.label_overlap(d['la'], d['lb'], w=d['w'], f=d['f'])
+        elif entry == 'overturning':
+            out = c.contour_overturning(d['q'], LEV3, periodic=per, select=sel)
+        elif entry == 'tracks':
+            out = c.ring_tracks(*d['graph'], min_overlap=0.3)
+        else:
+            out = c.contour_interior(d['q'], LEV3, w=d['w'], f=d['f'], periodic=per, select=sel, return_mask=True)
+    finally:
+        c.set_cpiece_workspace(DEFAULT_CAP)
+    return flat(out)
+
+
+@pytest.mark.parametrize('periodic', [0, 1], ids=['plain', 'ring'])
+def test_folds_overlap_and_tracks_between_the_piece_entries_on_one_context(ctx, periodic):
+    """K24, K22 and K23 interleaved with K13, K16 and K17 on one context, on two slabs of 24 x 40 and on one of 6 x 8 at three levels,
+    under caps of 1 and 2 table rows: the grow-only workspaces are reused by layouts of different sizes, small after large and large
+    after small.  Every result is bitwise that of the same call on a context that has done nothing else."""
+    data = {size: inputs(size, periodic) for size in SIZES}
+    want = {}
+    for rows in (1, 2):
+        for size in SIZES:
+            for entry in ENTRIES:
+                fresh = nat.Context(0)
+                try:
+                    want[entry, size, rows] = one_call(fresh, entry, data[size], periodic, rows)
+                    if entry == 'folds' and size == 'large':                 # several groups, the rows cut into several chunks
+                        assert fresh.last_cfold_profile()['groups'] > 1
+                finally:
+                    fresh.close()
+    assert data['large']['ny'] >= 2 * 4                                      # (ci_geometry: chunks of four rows or more)
+    for rows in (1, 2):
+        for name, order in ORDERS.items():
+            for entry, size in order:
+                got = one_call(ctx, entry, data[size], periodic, rows)
+                assert got == want[entry, size, rows], '%s (%s) in the order "%s" under %d rows is not what it is alone' % (entry, size, name, rows)

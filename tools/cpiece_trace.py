@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""The launch sequence of K13, K14, K16 and K17 (the sibling of cprecords_trace.py, which does K18-K21): one call of
-xc_contour_pieces_dev, xc_contour_polylines_dev, xc_contour_overturning_dev and xc_contour_interior_dev each, twice (the first call warms
-up), on a 24 x 65 plane in three ranges of which the middle one has no segments, periodic X ('main' selected) and then plain ('all'), under
-a cap of ONE table row: two groups a call.  Meant to run under a kernel trace of its own (no counters):
+"""The launch sequence of K13, K14, K16, K17 and K24 (the sibling of cprecords_trace.py, which does K18-K21): one call of
+xc_contour_pieces_dev, xc_contour_polylines_dev, xc_contour_overturning_dev, xc_contour_interior_dev and xc_contour_folds_dev each, twice
+(the first call warms up), on a 24 x 65 plane in three ranges of which the middle one has no segments, periodic X ('main' selected) and
+then plain ('all'), under a cap of ONE table row: two groups a call.  Then K22 (xc_label_overlap_dev on two block maps of the same three
+ranges, the middle one without a ring: two groups under the same cap) and K23 (xc_ring_tracks_dev on 600 rings and 800 links), twice
+each.  Meant to run under a kernel trace of its own (no counters):
 
     rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/cpiece_trace.py
 
@@ -43,7 +45,7 @@ def main():
         cnt = np.array([cnt[0], 0, cnt[1]], dtype=np.uint64)                     # the records stay as they are: range 1 holds none
         dn = ctx.to_device(cnt)
         recs = (ctx.handle, N, dn.ptr, de.ptr, dt.ptr, dp.ptr, ny, nx)
-        out = [ctx.alloc(max(total * 32, N * ny * nx * 8)) for _ in range(8)]
+        out = [ctx.alloc(max(total * 32, N * ny * nx * 8)) for _ in range(15)]
         ptrs = [b.ptr for b in out]
         select = 2 if periodic else 0
         calls = (('pieces', 'cpiece', lambda: ctx.lib.xc_contour_pieces_dev(*recs, periodic, dy.ptr, dx.ptr, float(nx) if periodic else 0.0, 0.0,
@@ -51,7 +53,9 @@ def main():
                  ('polylines', 'cjoin', lambda: ctx.lib.xc_contour_polylines_dev(*recs, total, dpc.ptr, *ptrs[:6])),
                  ('overturning', 'coverturn', lambda: ctx.lib.xc_contour_overturning_dev(*recs, periodic, select, *ptrs[:7])),
                  ('interior', 'cinterior', lambda: ctx.lib.xc_contour_interior_dev(*recs, periodic, select, 0, N, dw.ptr, 0, df32.ptr, nat.XC_F32,
-                                                                                  *ptrs[:4])))
+                                                                                  *ptrs[:4])),
+                 ('folds', 'cfold', lambda: ctx.lib.xc_contour_folds_dev(*recs, periodic, select, N, dw.ptr, 0, df32.ptr, nat.XC_F32, 1, *ptrs[:4],
+                                                                         N * ((nx + 1) // 2), dpc.ptr, *ptrs[4:15])))
         for name, prof, call in calls:
             for _ in range(2):
                 ctx._check(call())
@@ -59,6 +63,27 @@ def main():
             print('periodic %d %-11s segments %s groups %d rounds %d' % (periodic, name, cnt.tolist(), p['groups'], p['rounds']))
         for b in [dn, de, dt, dp] + out:
             b.free()
+    # K22: blocks of 6 x 17 nodes against the same blocks shifted by (3, 5); range 1 holds no ring
+    la = np.broadcast_to((y // 6) * 4 + x // 17, (N, ny, nx)).astype(np.int32)
+    lb = np.broadcast_to(((y + 3) // 6) * 4 + (x + 5) // 17, (N, ny, nx)).astype(np.int32)
+    la[1] = lb[1] = -1
+    dla, dlb = ctx.to_device(la), ctx.to_device(lb)
+    cap = 4096
+    out = [ctx.alloc(cap * 8) for _ in range(5)]
+    for _ in range(2):
+        ctx._check(ctx.lib.xc_label_overlap_dev(ctx.handle, N, ny, nx, N, dla.ptr, dlb.ptr, dw.ptr, 0, df32.ptr, nat.XC_F32, cap, dpc.ptr,
+                                                *[b.ptr for b in out]))
+    print('overlap     pairs %s groups %d' % (dpc.download((N,), np.uint64).tolist(), ctx.last_cpoverlap_profile()['groups']))
+    # K23: rings in steps of eight, links between the rings of consecutive steps
+    nring, nlink = 600, 800
+    a = rng.integers(0, nring - 8, nlink).astype(np.int64)
+    graph = [ctx.to_device(v) for v in ((np.arange(nring) // 8).astype(np.int32), rng.integers(1, 50, nring).astype(np.int64), a,
+                                        a + rng.integers(1, 9, nlink).astype(np.int64), rng.integers(0, 40, nlink).astype(np.int64))]
+    rows = [ctx.alloc(nring * 8) for _ in range(11)]
+    for _ in range(2):
+        ctx._check(ctx.lib.xc_ring_tracks_dev(ctx.handle, nring, nlink, *[b.ptr for b in graph], 0.3, *[b.ptr for b in rows[:5]], nring, dpc.ptr,
+                                              *[b.ptr for b in rows[5:]]))
+    print('tracks      tracks %d rounds %d' % (int(dpc.download((1,), np.uint64)[0]), ctx.last_cptrack_profile()['rounds']))
 
 
 if __name__ == '__main__':

@@ -2,13 +2,13 @@
 // (pinned bounce buffers, xc_sync), xc_keff.hip (the Keff chain) and xc_forms.hip (the host forms of the other kernels).
 #pragma once
 #include "xc_internal.h"
+#include "xc_carve.h"
 #include <assert.h>
 #include <utility>
 #include <vector>
 
 namespace xc {
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 inline size_t esize(int dtype) { return dtype == XC_F32 ? 4 : 8; }
 // bytes of a weight array of the given rank (XC_DA_NONE: none)
 inline size_t dA_bytes(int rank, int64_t nslab, int64_t ny, int64_t nx)
@@ -55,6 +55,8 @@ struct StageTimer {
 
 // ---------------------------------------------------------------- xc_context.hip
 int grow(xc_ctx* ctx, void** p, size_t* have, size_t need);          // the grow-only rule of ensure_* for any device block of the context
+// a layout (xc_carve.h) over such a block: measured, the block grown to it, then placed
+template <typename Lay> int lay_out(xc_ctx* ctx, void** p, size_t* have, Lay&& lay) { XC_TRY(grow(ctx, p, have, lay(Carve()))); lay(Carve(*p)); return XC_OK; }
 void mm_touch(xc_ctx* ctx, const void* p, size_t bytes);             // a write into / the release of [p, p + bytes) drops chained min/max partials of it
 const void* resident_lookup(const xc_ctx* ctx, const void* h, size_t n);   // device mirror of the host bytes [h, h + n) (xc_keep_resident), or null
 int hist_ev_begin(xc_ctx* ctx);                                      // events around the dominant kernel (xc_set_kernel_timing, xc_set_hist_events)

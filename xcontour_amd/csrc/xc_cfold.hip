@@ -11,8 +11,8 @@
 // lowest crossing starts with t = 0, one that starts at a cut of the rows with !P.
 //
 // Per GROUP of consecutive ranges (xc_cpiece_link.h: K13's groups under K13's cap, indices group-local):
-//   the bit planes cleared, phase A (K13's kernels), k_co_root, k_co_piece, k_co_pick (K16's selection), k_ci_mark, k_ci_chunk (K17's:
-//   xc_cinside_mark.h)
+//   the bit planes cleared, phase A (K13's kernels), k_co_root, k_co_piece, k_co_pick (K16's selection: xc_cpiece_select.h, shared with
+//   K16 and K17) and k_ci_mark -- one step, ci_mark_group, shared with K17 like the planes' blocks and k_ci_chunk (xc_cinside_mark.h)
 //   k_cf_rows       one thread per segment of a selected piece: K16's atomic min / max of the crossing's row (its bit pattern) per column
 //   k_cf_cols       the column pass: a block is 256 consecutive columns x one chunk of rows x one range; a lane walks its rows of the bit
 //                   plane and adds its flags to ncross, their first and last row to lo / hi (integer atomics)
@@ -384,10 +384,6 @@ void k_cf_compact(int64_t total, int64_t nrange, int64_t emax, const long long* 
     }
 }
 
-// carve n elements of T from p
-template <typename T>
-inline T* cf_take(char*& p, size_t n) { T* out = (T*)p; p += al(n * sizeof(T)); return out; }
-
 }  // namespace
 
 // One xc_contour_folds_dev call.  Waits for the stream twice: for K12's counts (they size the groups and fix the rounds) and for the event
@@ -400,17 +396,14 @@ int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, con
 {
     if (!count || !ncross || !row_lo || !row_hi || !col_event || !event_count || nrange < 1 || ny < 1 || nx < 1 || capacity < 0)
         return fail(ctx, XC_EBADARG, "xc_contour_folds: bad arguments");
-    if (select < 0 || select > 2) return fail(ctx, XC_EBADARG, "xc_contour_folds: select is 0 (all), 1 (circumpolar) or 2 (main)");
-    if (select != 0 && !periodic)
-        return fail(ctx, XC_EBADARG, "xc_contour_folds: select != 0 needs periodic != 0 (no piece goes round a plain plane)");
+    XC_TRY(co_check_select(ctx, "xc_contour_folds", periodic, select));
     if (ncont < 1 || nrange % ncont != 0) return fail(ctx, XC_EBADARG, "xc_contour_folds: nrange must be a multiple of ncont >= 1");
     if (gap < 0 || gap >= nx) return fail(ctx, XC_EBADARG, "xc_contour_folds: gap must lie in [0, nx)");
     if (capacity > 0 && (!c_west || !c_east || !ncol || !ncross_max || !ev_row_lo || !ev_row_hi || !nodes || !area || !mx_ || !my_))
         return fail(ctx, XC_EBADARG, "xc_contour_folds: capacity > 0 needs the event arrays");
     if (capacity > 0 && (f == nullptr) != (integral == nullptr)) return fail(ctx, XC_EBADARG, "xc_contour_folds: f and integral go together");
     if (f && f_dtype != XC_F32 && f_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_folds: f_dtype is XC_F32 or XC_F64");
-    if (periodic && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_folds: a periodic plane needs nx >= 2");
-    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_folds: plane too large for 32-bit labels (2 ny nx < 2^31)");
+    XC_TRY(co_check_plane(ctx, "xc_contour_folds", periodic, ny, nx));
     if (nrange > ((int64_t)1 << 38) / nx) return fail(ctx, XC_EBADARG, "xc_contour_folds: nrange nx must stay below 2^38");
     const long long E = 2 * ny * nx;
     const int wrap = periodic ? 1 : 0;
@@ -422,43 +415,32 @@ int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, con
 
     CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
     XC_TRY(cp_plan(ctx, "xc_contour_folds", nrange, count, nullptr, e_from, e_to, pts, E, pl));
-    const CiGeom geo = ci_geometry(ny, nx, nrange);
-    const int64_t wpr = geo.wpr, ncb = geo.ncb, nchunk = geo.nchunk, rc = geo.rc;
-    const size_t plane = (size_t)ny * (size_t)wpr;
+    CiPlanes m(ny, nx, nrange);
+    const int64_t wpr = m.geo.wpr, ncb = m.geo.ncb, nchunk = m.geo.nchunk, rc = m.geo.rc;
     const int64_t emax = (nx + 1) / 2, ncol_all = nrange * nx;
     const size_t nslot = (size_t)nrange * (size_t)emax, gslot = (size_t)pl.gmax * (size_t)emax;
     // workspace: off | key, nsel, mx, err (cleared together) | eoff | lo, hi [nrange][nx] | the staging slots [nrange][emax] |
     //            acc, cnt, flg [gmax][emax] (cleared per group) | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | the tail (xc_cpiece_link.h)
-    const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_nsel = al((size_t)nrange * 4);
-    const size_t b_mx = al((size_t)nslab * 16), b_small = 256, b_zero = b_key + b_nsel + b_mx + b_small;
-    const size_t b_eoff = al((size_t)(nrange + 1) * 8), b_col = al((size_t)ncol_all * 4);
-    const size_t b_s4 = al(nslot * 4), b_s8 = al(nslot * 8), b_nodes = al(nslot * 16), b_sums = al(nslot * CF_NSUM * 16);
-    const size_t b_acc = al(gslot * CF_ACC * 8), b_cnt = al(gslot * 16), b_flg = al(gslot * 4), b_gzero = b_acc + b_cnt + b_flg;
-    const size_t b_bits = al((size_t)pl.gmax * plane * 4), b_cpar = al((size_t)pl.gmax * (size_t)nchunk * (size_t)wpr * 4);
-    CpTail tail;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_zero + b_eoff + 2 * b_col + 4 * b_s4 + 2 * b_s8 + b_nodes + b_sums +
-                                                                 b_gzero + b_bits + b_cpar + cp_carve_tail(nullptr, pl, 6, tail)));
-    char* p = (char*)ctx->cpiece_ws;
-    long long* d_off = cf_take<long long>(p, (size_t)nrange + 1);
-    char* zero0 = p;
-    unsigned long long* key = cf_take<unsigned long long>(p, (size_t)nrange);
-    int* nsel = cf_take<int>(p, (size_t)nrange);
-    unsigned long long* mx = cf_take<unsigned long long>(p, (size_t)nslab * 2);
-    int* d_err = cf_take<int>(p, b_small / 4);
-    long long* eoff = cf_take<long long>(p, (size_t)nrange + 1);
-    int* lo = cf_take<int>(p, (size_t)ncol_all);
-    int* hi = cf_take<int>(p, (size_t)ncol_all);
-    CfSlots S;
-    S.c_west = cf_take<int>(p, nslot); S.c_east = cf_take<int>(p, nslot); S.ncol = cf_take<int>(p, nslot); S.nmax = cf_take<int>(p, nslot);
-    S.row_lo = cf_take<unsigned long long>(p, nslot); S.row_hi = cf_take<unsigned long long>(p, nslot);
-    S.nodes = cf_take<long long>(p, nslot * 2); S.sums = cf_take<double>(p, nslot * CF_NSUM * 2);
-    char* gzero0 = p;
-    unsigned long long* acc = cf_take<unsigned long long>(p, gslot * CF_ACC);
-    unsigned long long* cnt = cf_take<unsigned long long>(p, gslot * 2);
-    int* flg = cf_take<int>(p, gslot);
-    unsigned* bits = (unsigned*)p; p += b_bits;
-    unsigned* cpar = (unsigned*)p; p += b_cpar;
-    cp_carve_tail(p, pl, 6, tail);
+    long long *d_off, *eoff; int *d_err, *lo, *hi, *flg; unsigned long long *acc, *cnt; size_t b_zero = 0, b_gzero = 0; CfSlots S; CpTail tail;
+    auto lay = [&](Carve c) {
+        d_off = c.take<long long>((size_t)nrange + 1);
+        b_zero = c.mark();
+        m.carve_words(c, nrange, nslab);
+        d_err = c.take<int>(CP_SMALL);
+        b_zero = c.mark() - b_zero;
+        eoff = c.take<long long>((size_t)nrange + 1);
+        lo = c.take<int>((size_t)ncol_all); hi = c.take<int>((size_t)ncol_all);
+        S.c_west = c.take<int>(nslot); S.c_east = c.take<int>(nslot); S.ncol = c.take<int>(nslot); S.nmax = c.take<int>(nslot);
+        S.row_lo = c.take<unsigned long long>(nslot); S.row_hi = c.take<unsigned long long>(nslot);
+        S.nodes = c.take<long long>(nslot * 2); S.sums = c.take<double>(nslot * CF_NSUM * 2);
+        b_gzero = c.mark();
+        acc = c.take<unsigned long long>(gslot * CF_ACC); cnt = c.take<unsigned long long>(gslot * 2); flg = c.take<int>(gslot);
+        b_gzero = c.mark() - b_gzero;
+        m.carve_planes(c, pl.gmax);
+        cp_carve_tail(c, pl, 6, tail);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
 
     StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
     CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
@@ -477,12 +459,12 @@ int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, con
     };
 
     tm.mark(-1);
-    XC_HIP(ctx, hipMemsetAsync(zero0, 0, b_zero, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(m.key, 0, b_zero, ctx->stream));
     hipLaunchKernelGGL(k_cf_init, dim3(cp_blocks(ncol_all)), blk, 0, ctx->stream, ncol_all, (int*)ncross, row_lo, row_hi, lo, hi);
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
     if (sums) {
-        ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, mx);
+        ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, m.mx);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(5);
     }
@@ -493,41 +475,34 @@ int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, con
     for (const CpGroup& g : pl.groups) {
         const int64_t ng = g.r1 - g.r0;
         if (ng * ncb * nchunk >= ((int64_t)1 << 31)) return fail(ctx, XC_EBADARG, "xc_contour_folds: a group of too many ranges (lower xc_set_cpiece_workspace)");
-        XC_HIP(ctx, hipMemsetAsync(bits, 0, (size_t)ng * plane * 4, ctx->stream));
-        tm.mark(3);
-        run.begin(g);
-        XC_TRY(run.rounds());
-        const CoRoles s = co_launch_select(run, wrap, nx, pts, select, nsel, key);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(2);
-        hipLaunchKernelGGL(k_ci_mark, run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, nx, wpr, plane, select, run.e_from, run.e_to,
-                           tail.tab, tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key, bits);
+        CoRoles s;
+        XC_TRY(ci_mark_group(run, g, m, wrap, nx, pts, select, s));
         hipLaunchKernelGGL(k_cf_rows, run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, nx, select, run.e_from, run.e_to, pts, tail.tab,
-                           tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key, row_lo, row_hi);
+                           tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, m.key, row_lo, row_hi);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(3);
         XC_TRY(run.end());
         const dim3 sgrid((unsigned)(ng * ncb * nchunk));
-        hipLaunchKernelGGL(k_cf_cols, sgrid, dim3(CI_TPB), 0, ctx->stream, g.r0, ny, nx, wpr, ncb, rc, nchunk, bits, (int*)ncross, lo, hi);
+        hipLaunchKernelGGL(k_cf_cols, sgrid, dim3(CI_TPB), 0, ctx->stream, g.r0, ny, nx, wpr, ncb, rc, nchunk, m.bits, (int*)ncross, lo, hi);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(3);
         XC_TRY(runs(done, g.r1));
         done = g.r1;
         tm.mark(4);
         if (!sums) continue;
-        XC_HIP(ctx, hipMemsetAsync(gzero0, 0, b_gzero, ctx->stream));
+        XC_HIP(ctx, hipMemsetAsync(acc, 0, b_gzero, ctx->stream));
         if (nchunk > 1) {
             const int64_t nwords = ng * nchunk * wpr;
-            hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, bits, cpar);
+            hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, m.bits, m.cpar);
             XC_HIP(ctx, hipGetLastError());
         }
-#define XC_CF_SCAN(FT_) hipLaunchKernelGGL((k_cf_scan<FT_>), sgrid, dim3(CI_TPB), 0, ctx->stream, g.r0, ny, nx, wpr, ncb, rc, nchunk, ncont, emax, bits, \
-                                           cpar, (const int*)col_event, lo, hi, S.c_west, w, w_per_slab, (const FT_*)f, mx, acc, cnt, flg)
+#define XC_CF_SCAN(FT_) hipLaunchKernelGGL((k_cf_scan<FT_>), sgrid, dim3(CI_TPB), 0, ctx->stream, g.r0, ny, nx, wpr, ncb, rc, nchunk, ncont, emax, m.bits, \
+                                           m.cpar, (const int*)col_event, lo, hi, S.c_west, w, w_per_slab, (const FT_*)f, m.mx, acc, cnt, flg)
         if (!f) XC_CF_SCAN(void); else if (f_dtype == XC_F32) XC_CF_SCAN(float); else XC_CF_SCAN(double);
 #undef XC_CF_SCAN
         XC_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_cf_finish, dim3(cp_blocks(ng * emax)), blk, 0, ctx->stream, g.r0, ng, ny, nx, ncont, emax, f ? 1 : 0,
-                           (const unsigned long long*)event_count, acc, cnt, flg, mx, S);
+                           (const unsigned long long*)event_count, acc, cnt, flg, m.mx, S);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(5);
     }

@@ -145,15 +145,12 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
                             const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask)
 {
     if (!count || !n_in || !sum_w || nrange < 1 || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_contour_interior: bad arguments");
-    if (select < 0 || select > 2) return fail(ctx, XC_EBADARG, "xc_contour_interior: select is 0 (all), 1 (circumpolar) or 2 (main)");
-    if (select != 0 && !periodic)
-        return fail(ctx, XC_EBADARG, "xc_contour_interior: select != 0 needs periodic != 0 (no piece goes round a plain plane)");
+    XC_TRY(co_check_select(ctx, "xc_contour_interior", periodic, select));
     if (flip != 0 && flip != 1) return fail(ctx, XC_EBADARG, "xc_contour_interior: flip is 0 or 1");
     if (ncont < 1 || nrange % ncont != 0) return fail(ctx, XC_EBADARG, "xc_contour_interior: nrange must be a multiple of ncont >= 1");
     if ((f == nullptr) != (sum_wf == nullptr)) return fail(ctx, XC_EBADARG, "xc_contour_interior: f and sum_wf go together");
     if (f && f_dtype != XC_F32 && f_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_interior: f_dtype is XC_F32 or XC_F64");
-    if (periodic && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_interior: a periodic plane needs nx >= 2");
-    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_interior: plane too large for 32-bit labels (2 ny nx < 2^31)");
+    XC_TRY(co_check_plane(ctx, "xc_contour_interior", periodic, ny, nx));
     const long long E = 2 * ny * nx;
     const int wrap = periodic ? 1 : 0;
     const int64_t nslab = nrange / ncont;
@@ -164,29 +161,23 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
     XC_TRY(cp_plan(ctx, "xc_contour_interior", nrange, count, nullptr, e_from, e_to, pts, E, pl));
     // the scan's geometry: 256 columns x rc rows x one range per block
-    const CiGeom geo = ci_geometry(ny, nx, nrange);
-    const int64_t wpr = geo.wpr, ncb = geo.ncb, nchunk = geo.nchunk, rc = geo.rc;
-    const size_t plane = (size_t)ny * (size_t)wpr;
-    // workspace: off | key, nsel, mx, acc, cnt, flg (cleared together) | err | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | the tail
+    CiPlanes m(ny, nx, nrange);
+    const int64_t wpr = m.geo.wpr, ncb = m.geo.ncb, nchunk = m.geo.nchunk, rc = m.geo.rc;
+    // workspace: off | key, nsel, mx, acc, cnt, flg, err (cleared together) | bits[gmax][ny][wpr] | cpar[gmax][nchunk][wpr] | the tail
     //            (xc_cpiece_link.h)
-    const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_nsel = al((size_t)nrange * 4);
-    const size_t b_mx = al((size_t)nslab * 16), b_acc = al((size_t)nrange * 2 * CP_L * 8), b_cnt = al((size_t)nrange * 8), b_flg = al((size_t)nrange * 4);
-    const size_t b_zero = b_key + b_nsel + b_mx + b_acc + b_cnt + b_flg, b_small = 256;
-    const size_t b_bits = al((size_t)pl.gmax * plane * 4), b_cpar = al((size_t)pl.gmax * (size_t)nchunk * (size_t)wpr * 4);
-    CpTail tail;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_zero + b_small + b_bits + b_cpar + cp_carve_tail(nullptr, pl, 6, tail)));
-    char* ws = (char*)ctx->cpiece_ws;
-    long long* d_off = (long long*)ws;
-    unsigned long long* key = (unsigned long long*)(ws + b_off);
-    int* nsel = (int*)((char*)key + b_key);
-    unsigned long long* mx = (unsigned long long*)((char*)nsel + b_nsel);
-    unsigned long long* acc = (unsigned long long*)((char*)mx + b_mx);
-    unsigned long long* cnt = (unsigned long long*)((char*)acc + b_acc);
-    int* flg = (int*)((char*)cnt + b_cnt);
-    int* d_err = (int*)((char*)flg + b_flg);
-    unsigned* bits = (unsigned*)((char*)d_err + b_small);
-    unsigned* cpar = (unsigned*)((char*)bits + b_bits);
-    cp_carve_tail((char*)cpar + b_cpar, pl, 6, tail);
+    long long* d_off; unsigned long long *acc, *cnt; int *flg, *d_err; size_t b_zero = 0; CpTail tail;
+    auto lay = [&](Carve c) {
+        d_off = c.take<long long>((size_t)nrange + 1);
+        b_zero = c.mark();
+        m.carve_words(c, nrange, nslab);
+        acc = c.take<unsigned long long>((size_t)nrange * 2 * CP_L); cnt = c.take<unsigned long long>((size_t)nrange); flg = c.take<int>((size_t)nrange);
+        d_err = c.take<int>(CP_SMALL);
+        b_zero = c.mark() - b_zero;
+        m.carve_planes(c, pl.gmax);
+        cp_carve_tail(c, pl, 6, tail);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
 
     StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
     CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
@@ -200,7 +191,7 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
             const int64_t nr = std::min<int64_t>(step, b - ra);
             const dim3 grid((unsigned)(nr * per));
 #define XC_CI_SCAN(FT_, M_) hipLaunchKernelGGL((k_ci_scan<FT_, M_>), grid, dim3(CI_TPB), 0, ctx->stream, ra, g0, g1, ny, nx, wpr, ncb, rc, nchunk, ncont, \
-                                               (unsigned)flip, bits, cpar, w, w_per_slab, (const FT_*)f, mx, acc, cnt, flg, (unsigned char*)mask)
+                                               (unsigned)flip, m.bits, m.cpar, w, w_per_slab, (const FT_*)f, m.mx, acc, cnt, flg, (unsigned char*)mask)
             if (!f) { if (mask) XC_CI_SCAN(void, true); else XC_CI_SCAN(void, false); }
             else if (f_dtype == XC_F32) { if (mask) XC_CI_SCAN(float, true); else XC_CI_SCAN(float, false); }
             else { if (mask) XC_CI_SCAN(double, true); else XC_CI_SCAN(double, false); }
@@ -211,11 +202,9 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     };
 
     tm.mark(-1);
-    XC_HIP(ctx, hipMemsetAsync(key, 0, b_zero + b_small, ctx->stream));
-    {
-        ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, mx);
-        XC_HIP(ctx, hipGetLastError());
-    }
+    XC_HIP(ctx, hipMemsetAsync(m.key, 0, b_zero, ctx->stream));
+    ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, m.mx);
+    XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
     XC_TRY(run.upload_off());
     XC_TRY(run.fill_table());
@@ -223,21 +212,14 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     int64_t done = 0;                                                       // the ranges scanned so far
     for (const CpGroup& g : pl.groups) {
         const int64_t ng = g.r1 - g.r0;
-        XC_HIP(ctx, hipMemsetAsync(bits, 0, (size_t)ng * plane * 4, ctx->stream));
-        tm.mark(3);
-        run.begin(g);
-        XC_TRY(run.rounds());
-        const CoRoles s = co_launch_select(run, wrap, nx, pts, select, nsel, key);
-        XC_HIP(ctx, hipGetLastError());
-        tm.mark(2);
-        hipLaunchKernelGGL(k_ci_mark, run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, nx, wpr, plane, select, run.e_from, run.e_to,
-                           tail.tab, tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key, bits);
+        CoRoles s;
+        XC_TRY(ci_mark_group(run, g, m, wrap, nx, pts, select, s));
         XC_HIP(ctx, hipGetLastError());
         tm.mark(3);
         XC_TRY(run.end());
         if (nchunk > 1) {
             const int64_t nwords = ng * nchunk * wpr;
-            hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, bits, cpar);
+            hipLaunchKernelGGL(k_ci_chunk, dim3(cp_blocks(nwords)), blk, 0, ctx->stream, nwords, ny, wpr, rc, nchunk, m.bits, m.cpar);
             XC_HIP(ctx, hipGetLastError());
         }
         XC_TRY(scan(done, g.r1, g.r0, g.r1));
@@ -246,7 +228,7 @@ int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     }
     if (done < nrange) XC_TRY(scan(done, nrange, 0, 0));
     run.report(prof);
-    hipLaunchKernelGGL(k_ci_finish, dim3(cp_blocks(nrange)), blk, 0, ctx->stream, nrange, ncont, acc, cnt, flg, mx, (long long*)n_in, sum_w, sum_wf);
+    hipLaunchKernelGGL(k_ci_finish, dim3(cp_blocks(nrange)), blk, 0, ctx->stream, nrange, ncont, acc, cnt, flg, m.mx, (long long*)n_in, sum_w, sum_wf);
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
     int herr = 0;

@@ -1,6 +1,8 @@
 // The crossing bit planes of K17, shared by K17 (xc_cinside.hip) and K24 (xc_cfold.hip); xc_cinside.hip's header states the rule: bit
 // c & 31 of word c >> 5 of row r of a range's plane is X[r][c], ny rows of wpr = ceil(nx / 32) words.  Here: the marks (k_ci_mark), the
-// XOR of the rows of every chunk (k_ci_chunk), the cut of the rows into chunks (ci_geometry) and the wave sum that closes a column scan.
+// XOR of the rows of every chunk (k_ci_chunk), the cut of the rows into chunks (ci_geometry), the wave sum that closes a column scan, and
+// on the host what the two launchers have in common: the blocks of the workspace both keep (CiPlanes) and the step of a group from the
+// clearing of its planes to the marks (ci_mark_group).
 // Included inside namespace xc { namespace { ... } } after xc_cpiece_select.h and xc_cinside_bound.h; the including file includes <algorithm>.
 #pragma once
 
@@ -71,4 +73,39 @@ void k_ci_chunk(int64_t nwords, int64_t ny, int64_t wpr, int64_t rc, int64_t nch
     unsigned x = 0u;
     for (int64_t r = ra; r < rb; ++r) x ^= bp[(size_t)r * (size_t)wpr];
     cpar[i] = x;
+}
+
+// The blocks of ctx->cpiece_ws that K17 and K24 both keep, with the scan's geometry: key, nsel [nrange] and mx[nslab][2], the first
+// blocks of the run the launcher clears with one fill (its own words follow them), and the planes bits[gmax][ny][wpr],
+// cpar[gmax][nchunk][wpr], which stand in front of the tail.  `plane`: the words of one range's bit plane.
+struct CiPlanes {
+    CiGeom geo; size_t plane;
+    unsigned long long* key; int* nsel; unsigned long long* mx; unsigned *bits, *cpar;
+    CiPlanes(int64_t ny, int64_t nx, int64_t nrange) : geo(ci_geometry(ny, nx, nrange)), plane((size_t)ny * (size_t)geo.wpr) {}
+    void carve_words(Carve& c, int64_t nrange, int64_t nslab)
+    {
+        key = c.take<unsigned long long>((size_t)nrange); nsel = c.take<int>((size_t)nrange); mx = c.take<unsigned long long>((size_t)nslab * 2);
+    }
+    void carve_planes(Carve& c, int64_t gmax)
+    {
+        bits = c.take<unsigned>((size_t)gmax * plane); cpar = c.take<unsigned>((size_t)gmax * (size_t)geo.nchunk * (size_t)geo.wpr);
+    }
+};
+
+// The step of the group `g` that K17 and K24 share: the group's bit planes cleared (stage 3), phase A up to its rounds, K16's selection
+// (stage 2) and the marks.  -> in `s` the roles of the selection.  The launcher goes on behind the k_ci_mark launch: it checks the
+// launch (K24 behind its k_cf_rows) and marks stage 3.
+inline int ci_mark_group(CpRun& run, const CpGroup& g, const CiPlanes& m, int wrap, int64_t nx, const double* pts, int select, CoRoles& s)
+{
+    xc_ctx* ctx = run.ctx;
+    XC_HIP(ctx, hipMemsetAsync(m.bits, 0, (size_t)(g.r1 - g.r0) * m.plane * 4, ctx->stream));
+    run.tm.mark(3);
+    run.begin(g);
+    XC_TRY(run.rounds());
+    s = co_launch_select(run, wrap, nx, pts, select, m.nsel, m.key);
+    XC_HIP(ctx, hipGetLastError());
+    run.tm.mark(2);
+    hipLaunchKernelGGL(k_ci_mark, run.grid, dim3(CP_TPB), 0, ctx->stream, run.n, run.s0, g.r0, run.pl.E, nx, m.geo.wpr, m.plane, select, run.e_from,
+                       run.e_to, run.t.tab, run.t.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, m.key, m.bits);
+    return XC_OK;
 }

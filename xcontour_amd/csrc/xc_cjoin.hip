@@ -298,19 +298,16 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
         return fail(ctx, XC_EBADARG, "xc_contour_polylines: too many ranges in one group (lower xc_set_cpiece_workspace)");
     // workspace: off | poff | err | inv, gidx, gsz [total] | sums[gmax][nchunk] | the tail with ten buffers (xc_cpiece_link.h)
     constexpr int NBUF = 10;
-    const size_t b_off = al((size_t)(nrange + 1) * 8), b_small = 256, b_tot = al((size_t)total * 4);
-    const size_t b_sums = al((size_t)pl.gmax * (size_t)nchunk * 8);
-    CpTail tail;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + 3 * b_tot + b_sums + cp_carve_tail(nullptr, pl, NBUF, tail)));
-    char* ws = (char*)ctx->cpiece_ws;
-    long long* d_off = (long long*)ws;
-    long long* d_poff = (long long*)(ws + b_off);
-    int* d_err = (int*)(ws + 2 * b_off);
-    int* inv = (int*)(ws + 2 * b_off + b_small);
-    int* gidx = (int*)((char*)inv + b_tot);
-    int* gsz = (int*)((char*)gidx + b_tot);
-    unsigned long long* sums = (unsigned long long*)((char*)gsz + b_tot);
-    cp_carve_tail((char*)sums + b_sums, pl, NBUF, tail);
+    long long *d_off, *d_poff; int *d_err, *inv, *gidx, *gsz; unsigned long long* sums; CpTail tail;
+    auto lay = [&](Carve c) {
+        d_off = c.take<long long>((size_t)nrange + 1); d_poff = c.take<long long>((size_t)nrange + 1);
+        d_err = c.take<int>(CP_SMALL);
+        inv = c.take<int>((size_t)total); gidx = c.take<int>((size_t)total); gsz = c.take<int>((size_t)total);
+        sums = c.take<unsigned long long>((size_t)pl.gmax * (size_t)nchunk);
+        cp_carve_tail(c, pl, NBUF, tail);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
     int *const tab = tail.tab, *const rid = tail.rid;
 
     StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
@@ -318,7 +315,7 @@ int launch_contour_polylines(xc_ctx* ctx, int64_t nrange, const uint64_t* count,
 
     tm.mark(-1);
     XC_TRY(run.upload_off());
-    XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(d_err, 0, CP_SMALL * 4, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(inv, 0xff, (size_t)total * 4, ctx->stream));
     XC_TRY(run.fill_table());
     tm.mark(0);

@@ -11,7 +11,7 @@
 // Per GROUP of consecutive ranges (xc_cpiece_link.h: K13's groups under K13's cap, indices group-local):
 //   phase A (K13's kernels)  k_cp_scatter, k_cp_link, R x k_cp_round: label = the piece's smallest e_from (its first_edge), prev >= 0 on
 //                   every member of a ring and -1 on every member of an open piece
-//   k_co_root, k_co_piece, k_co_pick  (xc_cpiece_select.h, shared with K17) the root of every piece, its nseg and winding, nsel, and
+//   k_co_root, k_co_piece, k_co_pick  (xc_cpiece_select.h, shared with K17 and K24) the root of every piece, its nseg and winding, nsel, and
 //                   the bid for the range's main ring under co_key
 //   k_co_count      one thread per segment of a selected piece ('main': the piece whose key won): a start point on a vertical edge
 //                   (e_from odd) is a crossing of column (e_from >> 1) % nx at row r1; the end point of a segment WITHOUT successor
@@ -102,11 +102,8 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
 {
     if (!count || !ncross || !row_lo || !row_hi || !nsel || !main_first_edge || !main_nseg || !main_winding || nrange < 1 || ny < 1 || nx < 1)
         return fail(ctx, XC_EBADARG, "xc_contour_overturning: bad arguments");
-    if (select < 0 || select > 2) return fail(ctx, XC_EBADARG, "xc_contour_overturning: select is 0 (all), 1 (circumpolar) or 2 (main)");
-    if (select != 0 && !periodic)
-        return fail(ctx, XC_EBADARG, "xc_contour_overturning: select != 0 needs periodic != 0 (no piece goes round a plain plane)");
-    if (periodic && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_overturning: a periodic plane needs nx >= 2");
-    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, "xc_contour_overturning: plane too large for 32-bit labels (2 ny nx < 2^31)");
+    XC_TRY(co_check_select(ctx, "xc_contour_overturning", periodic, select));
+    XC_TRY(co_check_plane(ctx, "xc_contour_overturning", periodic, ny, nx));
     if (nrange > ((int64_t)1 << 38) / nx) return fail(ctx, XC_EBADARG, "xc_contour_overturning: nrange nx must stay below 2^38");
     const long long E = 2 * ny * nx;
     const int wrap = periodic ? 1 : 0;
@@ -116,14 +113,13 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
     CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
     XC_TRY(cp_plan(ctx, "xc_contour_overturning", nrange, count, nullptr, e_from, e_to, pts, E, pl));
     // workspace: off | key | err | the tail (xc_cpiece_link.h)
-    const size_t b_off = al((size_t)(nrange + 1) * 8), b_key = al((size_t)nrange * 8), b_small = 256;
-    CpTail tail;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_off + b_key + b_small + cp_carve_tail(nullptr, pl, 6, tail)));
-    char* ws = (char*)ctx->cpiece_ws;
-    long long* d_off = (long long*)ws;
-    unsigned long long* key = (unsigned long long*)(ws + b_off);
-    int* d_err = (int*)(ws + b_off + b_key);
-    cp_carve_tail((char*)d_err + b_small, pl, 6, tail);
+    long long* d_off; unsigned long long* key; int* d_err; CpTail tail;
+    auto lay = [&](Carve c) {
+        d_off = c.take<long long>((size_t)nrange + 1); key = c.take<unsigned long long>((size_t)nrange); d_err = c.take<int>(CP_SMALL);
+        cp_carve_tail(c, pl, 6, tail);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
 
     StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
     CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
@@ -135,7 +131,7 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
                        (long long*)main_nseg, (int*)main_winding, key);
     XC_HIP(ctx, hipGetLastError());
     tm.mark(3);
-    XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(d_err, 0, CP_SMALL * 4, ctx->stream));
     XC_TRY(run.upload_off());
     XC_TRY(run.fill_table());
     tm.mark(0);

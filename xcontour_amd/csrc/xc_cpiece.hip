@@ -189,23 +189,22 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     if (total == 0) return XC_OK;
 
     // workspace: off | poff | c0[2], err | pslot[total] | the tail (xc_cpiece_link.h)
-    const size_t b_off = al((size_t)(nrange + 1) * 8), b_small = 256, b_slot = al((size_t)total * 4);
-    CpTail tail;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_small + b_slot + cp_carve_tail(nullptr, pl, 6, tail)));
-    char* ws = (char*)ctx->cpiece_ws;
-    long long* d_off = (long long*)ws;
-    long long* d_poff = (long long*)(ws + b_off);
-    int* d_c0 = (int*)(ws + 2 * b_off);
+    long long *d_off, *d_poff; int *d_c0, *pslot; CpTail tail;
+    auto lay = [&](Carve c) {
+        d_off = c.take<long long>((size_t)nrange + 1); d_poff = c.take<long long>((size_t)nrange + 1);
+        d_c0 = c.take<int>(CP_SMALL); pslot = c.take<int>((size_t)total);
+        cp_carve_tail(c, pl, 6, tail);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
     int* d_err = d_c0 + 2;
-    int* pslot = (int*)(ws + 2 * b_off + b_small);
-    cp_carve_tail((char*)pslot + b_slot, pl, 6, tail);
 
     StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
     CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
 
     tm.mark(-1);
     XC_TRY(run.upload_off());
-    XC_HIP(ctx, hipMemsetAsync(d_c0, 0, b_small, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(d_c0, 0, CP_SMALL * 4, ctx->stream));
     XC_TRY(run.fill_table());
     tm.mark(0);
     for (const CpGroup& g : pl.groups) {
@@ -231,9 +230,9 @@ int launch_contour_pieces(xc_ctx* ctx, int64_t nrange, const uint64_t* count, co
     for (int64_t r = 0; r < nrange; ++r) poff[(size_t)r + 1] = poff[(size_t)r] + (long long)hp[(size_t)r];
     const long long np = poff[(size_t)nrange];
     if (np > capacity) return 1;
-    XC_TRY(grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, al((size_t)np * 2 * CP_L * 8) + al((size_t)np * 4)));
-    unsigned long long* acc = (unsigned long long*)ctx->cpiece_acc;
-    int* flags = (int*)((char*)ctx->cpiece_acc + al((size_t)np * 2 * CP_L * 8));
+    unsigned long long* acc; int* flags;                                     // the limbs of both sums and the flags of every piece
+    auto lay_acc = [&](Carve c) { acc = c.take<unsigned long long>((size_t)np * 2 * CP_L); flags = c.take<int>((size_t)np); return c.at; };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, lay_acc));
     tm.mark(-1);
     XC_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(nrange + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     XC_TRY(launch_clen_window(ctx, ycoord, ny, xcoord, nx, wrap ? period : 0.0, latlon, 1, d_c0));

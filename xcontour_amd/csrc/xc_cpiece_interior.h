@@ -54,22 +54,14 @@ struct PiStage {
     int* flg;                     // 1: sum_w is NaN, 2: sum_wf is NaN
 };
 
-// the staged records of `cap` pieces carved from `a` (null: nothing is carved); -> their bytes, b_acc + 5 b8 + 3 b4
-inline size_t pi_carve(char* a, int64_t cap, PiStage& st)
+// the staged records of `cap` pieces, taken from the launcher's carve (xc_carve.h)
+inline void pi_carve(Carve& c, int64_t cap, PiStage& st)
 {
-    const size_t b8 = al((size_t)cap * 8), b4 = al((size_t)cap * 4), b_acc = al((size_t)cap * 2 * CP_L * 8);
-    if (a) {
-        st.acc = (unsigned long long*)a; a += b_acc;
-        st.cnt = (unsigned long long*)a; a += b8;
-        st.sa = (unsigned long long*)a; a += b8;
-        st.sb = (unsigned long long*)a; a += b8;
-        st.ns = (unsigned long long*)a; a += b8;
-        st.fe = (long long*)a; a += b8;
-        st.wd = (int*)a; a += b4;
-        st.cl = (int*)a; a += b4;
-        st.flg = (int*)a;
-    }
-    return b_acc + 5 * b8 + 3 * b4;
+    const size_t n = (size_t)cap;
+    st.acc = c.take<unsigned long long>(n * 2 * CP_L);
+    st.cnt = c.take<unsigned long long>(n); st.sa = c.take<unsigned long long>(n); st.sb = c.take<unsigned long long>(n);
+    st.ns = c.take<unsigned long long>(n); st.fe = c.take<long long>(n);
+    st.wd = c.take<int>(n); st.cl = c.take<int>(n); st.flg = c.take<int>(n);
 }
 
 // what the stages of a group need of it: n segments from s0 on, ranges from r0 on, the edge table, the roots and the slots (K20's and

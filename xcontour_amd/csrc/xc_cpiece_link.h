@@ -1,15 +1,16 @@
-// Phase A of the device joins, shared by K13 (xc_cpiece.hip), K14 (xc_cjoin.hip), K16 (xc_coverturn.hip), K17 (xc_cinside.hip) and
-// K18-K21 (xc_cprecords.hip): the dense edge tables of a GROUP of consecutive ranges, the next / prev links, the pointer-doubling rounds,
+// Phase A of the device joins, shared by K13 (xc_cpiece.hip), K14 (xc_cjoin.hip), K16 (xc_coverturn.hip), K17 (xc_cinside.hip),
+// K18-K21 (xc_cprecords.hip) and K24 (xc_cfold.hip): the dense edge tables of a GROUP of consecutive ranges, the next / prev links, the pointer-doubling rounds,
 // and the host frame every one of these launchers runs them in.  xc_cpiece.hip's header states the rule.  Written once here: the plan
 // (cp_plan: counts, scan, the refusal of segments without records, groups), the tail of the workspace (cp_carve_tail), the per-group
 // run (CpRun: offsets up, table filled, then begin / rounds / end per group with their stage marks and the sum of the rounds) and the
 // read of the error word (cp_read_err).  What stays with a launcher: the head of its workspace, its own stages between rounds() and
 // end(), the meaning of the error bits, and whether it returns on a call without segments (K13, K14, K18-K21) or goes on with an empty
-// plan (K16, K17).  Included inside namespace xc { namespace { ... } } after xc_capi.h, like xc_binning.h.
+// plan (K16, K17, K24).  Included inside namespace xc { namespace { ... } } after xc_capi.h, like xc_binning.h.
 #pragma once
 
 constexpr int CP_TPB = 256;
 constexpr int CP_ERR_EDGE = 1, CP_ERR_LINK = 2;
+constexpr size_t CP_SMALL = 64;               // the ints of the block that holds a call's error word (and K13's c0): 256 bytes
 
 // largest r in [lo, hi) with off[r] <= i (off ascending, off[lo] <= i < off[hi])
 __device__ __forceinline__ int64_t cp_range_of(const long long* __restrict__ off, int64_t lo, int64_t hi, long long i)
@@ -131,7 +132,7 @@ inline int cp_read_counts(xc_ctx* ctx, const char* who, int64_t nrange, const ui
 }
 
 // The plan of a call: the counts, their scan, and the groups.  A call without segments has no group, no table row (gmax 0) and no
-// buffer (nmax 0): K13, K14 and K18-K21 return on total == 0, K16 and K17 go on and write their dense outputs.
+// buffer (nmax 0): K13, K14 and K18-K21 return on total == 0, K16, K17 and K24 go on and write their dense outputs.
 struct CpPlan {
     std::vector<uint64_t> hc; std::vector<long long> off; long long total = 0, E = 0;
     std::vector<CpGroup> groups; int64_t gmax = 0; long long nmax = 0;
@@ -148,18 +149,15 @@ inline int cp_plan(xc_ctx* ctx, const char* who, int64_t nrange, const uint64_t*
     return XC_OK;
 }
 
-// The tail of every layout of ctx->cpiece_ws: tab[gmax][E] | rid[nmax] | nbuf buffers [nmax] (six: label, next, prev x 2; K14 ten),
-// carved from `p` (null: nothing is carved); -> its bytes.  What lies in front of it is the launcher's own.
+// The tail of every layout of ctx->cpiece_ws that runs phase A: tab[gmax][E] | rid[nmax] | nbuf buffers [nmax] (six: label, next,
+// prev x 2; K14 ten), taken from the launcher's carve (xc_carve.h).  What lies in front of it is the launcher's own.
 constexpr int CP_NBUF = 10;
 struct CpTail { int *tab, *rid, *buf[CP_NBUF]; };
-inline size_t cp_carve_tail(char* p, const CpPlan& pl, int nbuf, CpTail& t)
+inline void cp_carve_tail(Carve& c, const CpPlan& pl, int nbuf, CpTail& t)
 {
-    const size_t b_tab = al((size_t)pl.gmax * (size_t)pl.E * 4), b_n = al((size_t)pl.nmax * 4);
-    if (p) {
-        t.tab = (int*)p; t.rid = (int*)(p + b_tab);
-        for (int k = 0; k < nbuf; ++k) t.buf[k] = (int*)(p + b_tab + (size_t)(k + 1) * b_n);
-    }
-    return b_tab + (size_t)(nbuf + 1) * b_n;
+    t.tab = c.take<int>((size_t)pl.gmax * (size_t)pl.E);
+    t.rid = c.take<int>((size_t)pl.nmax);
+    for (int k = 0; k < nbuf; ++k) t.buf[k] = c.take<int>((size_t)pl.nmax);
 }
 
 // the error word of a call on the host: one wait for the stream.  What its bits mean is the entry's.

@@ -62,21 +62,14 @@ struct PpStage {
     int* gflg;                    // the same of the gross sum
 };
 
-// the staged records of K21 for `cap` pieces and nf fields carved from `a` (null: nothing is carved); -> their bytes, 2 b_g + 4 b8 + 2 b4
-inline size_t pp_carve(char* a, int64_t cap, int nf, PpStage& pp)
+// the staged records of K21 for `cap` pieces and nf fields, taken from the launcher's carve (xc_carve.h)
+inline void pp_carve(Carve& c, int64_t cap, int nf, PpStage& pp)
 {
-    const size_t b8 = al((size_t)cap * 8), b4 = al((size_t)cap * 4), b_g = al((size_t)cap * (size_t)nf * CP_L * 8);
-    if (a) {
-        pp.net = (unsigned long long*)a; a += b_g;
-        pp.gro = (unsigned long long*)a; a += b_g;
-        pp.kmin = (unsigned long long*)a; a += b8;
-        pp.kmax = (unsigned long long*)a; a += b8;
-        pp.amin = (unsigned long long*)a; a += b8;
-        pp.amax = (unsigned long long*)a; a += b8;
-        pp.flg = (int*)a; a += b4;
-        pp.gflg = (int*)a;
-    }
-    return 2 * b_g + 4 * b8 + 2 * b4;
+    const size_t n = (size_t)cap;
+    pp.net = c.take<unsigned long long>(n * (size_t)nf * CP_L); pp.gro = c.take<unsigned long long>(n * (size_t)nf * CP_L);
+    pp.kmin = c.take<unsigned long long>(n); pp.kmax = c.take<unsigned long long>(n);
+    pp.amin = c.take<unsigned long long>(n); pp.amax = c.take<unsigned long long>(n);
+    pp.flg = c.take<int>(n); pp.gflg = c.take<int>(n);
 }
 
 __device__ __forceinline__ double pp_load(const PpField& f, size_t slab, size_t node)

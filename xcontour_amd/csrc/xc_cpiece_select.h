@@ -1,4 +1,5 @@
-// The per-piece phase behind a SELECTION of pieces, shared by K16 (xc_coverturn.hip) and K17 (xc_cinside.hip): after phase A
+// The per-piece phase behind a SELECTION of pieces, shared by K16 (xc_coverturn.hip), K17 (xc_cinside.hip) and K24 (xc_cfold.hip), with
+// the refusals the three entries have in common (co_check_select, co_check_plane): after phase A
 // (xc_cpiece_link.h) has left label = the piece's smallest e_from and prev >= 0 on the members of a ring,
 //   k_co_root   root(i) = tab[range][label], the segment that carries its piece's sums; the sums start at 0
 //   k_co_piece  onto the root, integer atomic adds: nseg, and on a periodic plane the winding by K13's seam count (+1 where
@@ -12,6 +13,22 @@
 #pragma once
 
 constexpr unsigned long long CO_FE = 0x7fffffffull;          // the low 31 bits of a key: 2^31 - 1 - first_edge
+
+// The refusals of the entry `who` that every selected-piece entry has, each called where the entry's own checks stand: `select` ...
+inline int co_check_select(xc_ctx* ctx, const char* who, int periodic, int select)
+{
+    if (select < 0 || select > 2) return fail(ctx, XC_EBADARG, std::string(who) + ": select is 0 (all), 1 (circumpolar) or 2 (main)");
+    if (select != 0 && !periodic)
+        return fail(ctx, XC_EBADARG, std::string(who) + ": select != 0 needs periodic != 0 (no piece goes round a plain plane)");
+    return XC_OK;
+}
+// ... and the plane (nx >= 1)
+inline int co_check_plane(xc_ctx* ctx, const char* who, int periodic, int64_t ny, int64_t nx)
+{
+    if (periodic && nx < 2) return fail(ctx, XC_EBADARG, std::string(who) + ": a periodic plane needs nx >= 2");
+    if (ny > ((int64_t)1 << 30) / nx) return fail(ctx, XC_EBADARG, std::string(who) + ": plane too large for 32-bit labels (2 ny nx < 2^31)");
+    return XC_OK;
+}
 
 __global__ __launch_bounds__(CP_TPB)
 void k_co_root(int64_t n, long long E, const int* __restrict__ tab, const int* __restrict__ rid, const int* __restrict__ lab,

@@ -49,19 +49,13 @@ struct PtStage {
     int* dep;                     // depth
 };
 
-// the staged tree records of `cap` pieces carved from `a` (null: nothing is carved); -> their bytes, b_acc + 3 b8 + 2 b4
-inline size_t pt_carve(char* a, int64_t cap, PtStage& pt)
+// the staged tree records of `cap` pieces, taken from the launcher's carve (xc_carve.h)
+inline void pt_carve(Carve& c, int64_t cap, PtStage& pt)
 {
-    const size_t b8 = al((size_t)cap * 8), b4 = al((size_t)cap * 4), b_acc = al((size_t)cap * 2 * CP_L * 8);
-    if (a) {
-        pt.net = (unsigned long long*)a; a += b_acc;
-        pt.key = (unsigned long long*)a; a += b8;
-        pt.nnet = (unsigned long long*)a; a += b8;
-        pt.par = (long long*)a; a += b8;
-        pt.nch = (int*)a; a += b4;
-        pt.dep = (int*)a;
-    }
-    return b_acc + 3 * b8 + 2 * b4;
+    const size_t n = (size_t)cap;
+    pt.net = c.take<unsigned long long>(n * 2 * CP_L);
+    pt.key = c.take<unsigned long long>(n); pt.nnet = c.take<unsigned long long>(n); pt.par = c.take<long long>(n);
+    pt.nch = c.take<int>(n); pt.dep = c.take<int>(n);
 }
 
 __global__ __launch_bounds__(CP_TPB)

@@ -309,16 +309,16 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     // the ranges one launch of a scan takes: 2^30 threads (one range, PL_CHUNKS nx < 2^36 threads at most, is always taken)
     const int64_t rmax = std::max<int64_t>(1, ((int64_t)1 << 30) / (nchunk * nx));
 
-    // workspace: mx[nslab][2], err (cleared together) | runs[nrange] | soff[nrange + 1] | poff[nrange + 1] | cursor[nrange]
-    const size_t b_mx = al((size_t)nslab * 16), b_small = 256, b_r = al((size_t)(nrange + 1) * 8);
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_mx + b_small + 4 * b_r));
-    char* ws = (char*)ctx->cpiece_ws;
-    unsigned long long* mx = (unsigned long long*)ws;
-    int* d_err = (int*)(ws + b_mx);
-    unsigned long long* d_runs = (unsigned long long*)(ws + b_mx + b_small);
-    unsigned long long* d_soff = (unsigned long long*)((char*)d_runs + b_r);
-    long long* d_poff = (long long*)((char*)d_soff + b_r);
-    unsigned long long* d_cur = (unsigned long long*)((char*)d_poff + b_r);
+    // workspace: mx[nslab][2], err (cleared together) | runs, soff, poff, cursor: nrange + 1 words each (runs and cursor use nrange)
+    unsigned long long *mx, *d_runs, *d_soff, *d_cur; long long* d_poff; int* d_err; size_t b_zero = 0;
+    auto lay = [&](Carve c) {
+        mx = c.take<unsigned long long>((size_t)nslab * 2); d_err = c.take<int>(CP_SMALL);
+        b_zero = c.mark();                                                  // (from the first block on)
+        d_runs = c.take<unsigned long long>((size_t)nrange + 1); d_soff = c.take<unsigned long long>((size_t)nrange + 1);
+        d_poff = c.take<long long>((size_t)nrange + 1); d_cur = c.take<unsigned long long>((size_t)nrange + 1);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
 
     StageTimer tm(ctx, prof.ms);                                                // where the time goes (xc_set_kernel_timing)
 
@@ -326,7 +326,7 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     const int* la = (const int*)lab_a;
     const int* lb = (const int*)lab_b;
     tm.mark(-1);
-    XC_HIP(ctx, hipMemsetAsync(mx, 0, b_mx + b_small, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(mx, 0, b_zero, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(d_runs, 0, (size_t)nrange * 8, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(d_cur, 0, (size_t)nrange * 8, ctx->stream));
     XC_HIP(ctx, hipMemsetAsync(pair_count, 0, (size_t)nrange * 8, ctx->stream));
@@ -372,17 +372,15 @@ int launch_label_overlap(xc_ctx* ctx, int64_t nrange, int64_t ny, int64_t nx, in
     if (smax > ((1ull << 62) / ((unsigned long long)W * 8ull))) return fail(ctx, XC_ENOMEM, std::string(who) + ": the table of one group is too large");
     // the tables of one group, then the staged rows (a, b: 4 bytes; n, sum_w, sum_wf: 8 bytes) of min(capacity, all runs)
     const int64_t cap = (int64_t)std::min<uint64_t>((uint64_t)capacity, total_runs);
-    const size_t b_tab = al((size_t)smax * (size_t)W * 8), b4 = al((size_t)cap * 4), b8 = al((size_t)cap * 8);
-    {
-        const int rc = grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, b_tab + 2 * b4 + 3 * b8);
-        if (rc != XC_OK) return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the pair tables");
-    }
-    unsigned long long* tab = (unsigned long long*)ctx->cpiece_acc;
-    int* sa = (int*)((char*)tab + b_tab);
-    int* sb = (int*)((char*)sa + b4);
-    long long* sn = (long long*)((char*)sb + b4);
-    double* sw = (double*)((char*)sn + b8);
-    double* swf = (double*)((char*)sw + b8);
+    unsigned long long* tab; int *sa, *sb; long long* sn; double *sw, *swf;
+    auto lay_acc = [&](Carve c) {
+        tab = c.take<unsigned long long>((size_t)smax * (size_t)W);
+        sa = c.take<int>((size_t)cap); sb = c.take<int>((size_t)cap);
+        sn = c.take<long long>((size_t)cap); sw = c.take<double>((size_t)cap); swf = c.take<double>((size_t)cap);
+        return c.at;
+    };
+    if (lay_out(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, lay_acc) != XC_OK)
+        return fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the pair tables");
 
     ci_launch_bound(ctx->stream, npl, nslab, w, w_per_slab, f, f_dtype, mx);
     XC_HIP(ctx, hipGetLastError());

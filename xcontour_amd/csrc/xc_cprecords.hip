@@ -46,28 +46,24 @@ struct PieceCall {
 };
 
 // The workspace of a call (ctx->cpiece_ws): off | poff | mx[nslab][2], err (cleared together: b_zero bytes) | the tail (xc_cpiece_link.h)
-// | K20, K21: carry[gmax][nchunk][nx] | K21: mxg[nslab][nf] (b_mxg bytes) | fld[nf + 1]
+// | K20, K21: carry[gmax][nchunk][nx] | K21: mxg[nslab][nf] (b_mxg bytes) | fld[XC_PROPS_MAXF + 1]
 struct PieceWs {
     long long *off, *poff; unsigned long long* mx; int* err; CpTail t; int* carry; unsigned long long* mxg; PpField* fld;
     size_t b_zero, b_mxg;
 };
-int piece_ws_carve(xc_ctx* ctx, const PieceCall& c, int64_t nslab, const CpPlan& pl, int64_t nchunk, PieceWs& ws)
+size_t piece_ws_carve(Carve c, const PieceCall& pc, int64_t nslab, const CpPlan& pl, int64_t nchunk, PieceWs& ws)
 {
-    const size_t b_off = al((size_t)(c.nrange + 1) * 8), b_mx = al((size_t)nslab * 16), b_small = 256, b_tail = cp_carve_tail(nullptr, pl, 6, ws.t);
-    const size_t b_carry = nchunk > 1 ? al((size_t)pl.gmax * (size_t)nchunk * (size_t)c.nx * 4) : 0;
-    const size_t b_mxg = c.props ? al((size_t)nslab * (size_t)std::max(c.nf, 1) * 8) : 0;
-    const size_t b_fld = c.props ? al((size_t)(XC_PROPS_MAXF + 1) * sizeof(PpField)) : 0;
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, 2 * b_off + b_mx + b_small + b_tail + b_carry + b_mxg + b_fld));
-    char* p = (char*)ctx->cpiece_ws;
-    ws.off = (long long*)p;
-    ws.poff = (long long*)(p + b_off);
-    ws.mx = (unsigned long long*)(p + 2 * b_off);
-    ws.err = (int*)((char*)ws.mx + b_mx);
-    ws.carry = (int*)((char*)ws.err + b_small + cp_carve_tail((char*)ws.err + b_small, pl, 6, ws.t));
-    ws.mxg = (unsigned long long*)((char*)ws.carry + b_carry);
-    ws.fld = (PpField*)((char*)ws.mxg + b_mxg);
-    ws.b_zero = b_mx + b_small; ws.b_mxg = b_mxg;
-    return XC_OK;
+    ws.off = c.take<long long>((size_t)pc.nrange + 1); ws.poff = c.take<long long>((size_t)pc.nrange + 1);
+    ws.b_zero = c.mark();
+    ws.mx = c.take<unsigned long long>((size_t)nslab * 2); ws.err = c.take<int>(CP_SMALL);
+    ws.b_zero = c.mark() - ws.b_zero;
+    cp_carve_tail(c, pl, 6, ws.t);
+    ws.carry = c.take<int>(nchunk > 1 ? (size_t)pl.gmax * (size_t)nchunk * (size_t)pc.nx : 0);
+    ws.b_mxg = c.mark();
+    ws.mxg = c.take<unsigned long long>(pc.props ? (size_t)nslab * (size_t)std::max(pc.nf, 1) : 0);
+    ws.b_mxg = c.mark() - ws.b_mxg;
+    ws.fld = c.take<PpField>(pc.props ? XC_PROPS_MAXF + 1 : 0);
+    return c.at;
 }
 
 int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
@@ -122,18 +118,19 @@ int launch_piece_records(xc_ctx* ctx, const PieceCall& c)
     int64_t rows = 0, nchunk = 0;                                           // the row chunks of the scans (K20, K21)
     if (c.label || c.props) pl_geometry(ny, &rows, &nchunk);
     PieceWs ws;
-    XC_TRY(piece_ws_carve(ctx, c, nslab, pl, nchunk, ws));
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, [&](Carve a) { return piece_ws_carve(a, c, nslab, pl, nchunk, ws); }));
     // the staged records, K18's, then the tree's, then K21's: nothing reaches the caller's record arrays before all pieces are known to fit
     PiStage st = {};
     PtStage pt = {};
     PpStage pp = {};
     if (cap > 0) {
-        XC_TRY(grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes,
-                    pi_carve(nullptr, cap, st) + (c.tree ? pt_carve(nullptr, cap, pt) : 0) + (c.props ? pp_carve(nullptr, cap, nf, pp) : 0)));
-        char* a = (char*)ctx->cpiece_acc;
-        a += pi_carve(a, cap, st);
-        if (c.tree) a += pt_carve(a, cap, pt);
-        if (c.props) pp_carve(a, cap, nf, pp);
+        auto lay = [&](Carve a) {
+            pi_carve(a, cap, st);
+            if (c.tree) pt_carve(a, cap, pt);
+            if (c.props) pp_carve(a, cap, nf, pp);
+            return a.at;
+        };
+        XC_TRY(lay_out(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, lay));
     }
     // K21: the call's fields as the kernels read them; entry nf is the extremum field
     PpField hfld[XC_PROPS_MAXF + 1] = {};

@@ -180,18 +180,18 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
 
     // workspace: err, changed | parent[nring] | trk[nring] | nprev[nring], nnext[nring] | bcount[nb], boff[nb] | ok[nlink]
     const int64_t nb = (nring + RT_TPB - 1) / RT_TPB;
-    const size_t b_small = 256, b_r8 = al((size_t)nring * 8), b_r4 = al((size_t)nring * 4), b_b = al((size_t)nb * 8), b_ok = al((size_t)nlink + 1);
-    XC_TRY(grow(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, b_small + 2 * b_r8 + 2 * b_r4 + 2 * b_b + b_ok));
-    char* ws = (char*)ctx->cpiece_ws;
-    int* d_err = (int*)ws;
+    const size_t b_small = 256;
+    int *d_err, *d_prev, *d_next; u64 *parent, *trk, *d_bcount, *d_boff; unsigned char* d_ok; size_t b_degrees = 0;
+    auto lay = [&](Carve c) {
+        d_err = c.take<int>(b_small / 4); parent = c.take<u64>((size_t)nring); trk = c.take<u64>((size_t)nring);
+        b_degrees = c.mark();
+        d_prev = c.take<int>((size_t)nring); d_next = c.take<int>((size_t)nring);
+        b_degrees = c.mark() - b_degrees;
+        d_bcount = c.take<u64>((size_t)nb); d_boff = c.take<u64>((size_t)nb); d_ok = c.take<unsigned char>((size_t)nlink + 1);
+        return c.at;
+    };
+    XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
     int* d_changed = d_err + 1;
-    u64* parent = (u64*)(ws + b_small);
-    u64* trk = (u64*)((char*)parent + b_r8);
-    int* d_prev = (int*)((char*)trk + b_r8);
-    int* d_next = (int*)((char*)d_prev + b_r4);
-    u64* d_bcount = (u64*)((char*)d_next + b_r4);
-    u64* d_boff = (u64*)((char*)d_bcount + b_b);
-    unsigned char* d_ok = (unsigned char*)((char*)d_boff + b_b);
 
     StageTimer tm(ctx, prof.ms);                                               // where the time goes (xc_set_kernel_timing)
     auto bail = [&](int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; };
@@ -201,7 +201,7 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
 
     tm.mark(-1);
     XC_HIP(ctx, hipMemsetAsync(d_err, 0, b_small, ctx->stream));
-    XC_HIP(ctx, hipMemsetAsync(d_prev, 0, 2 * b_r4, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(d_prev, 0, b_degrees, ctx->stream));
     hipLaunchKernelGGL(k_rt_init, dim3(rt_grid(nring)), blk, 0, ctx->stream, nring, parent);
     if (nlink > 0)
         hipLaunchKernelGGL(k_rt_accept, dim3(rt_grid(nlink)), blk, 0, ctx->stream, nring, nlink, (const long long*)ring_size, la, lb,
@@ -241,19 +241,19 @@ int launch_ring_tracks(xc_ctx* ctx, int64_t nring, int64_t nlink, const int32_t*
     if ((int64_t)nt > capacity) { tm.mark(2); return bail(1); }
 
     // the staged rows: first_ring, nrings, nsplit, nmerge (8 bytes), first_step, last_step (4 bytes)
-    const size_t b_t8 = al((size_t)nt * 8), b_t4 = al((size_t)nt * 4);
-    {
-        const int rc = grow(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, 4 * b_t8 + 2 * b_t4);
-        if (rc != XC_OK) return bail(fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the track rows"));
-    }
-    long long* s_first = (long long*)ctx->cpiece_acc;
-    u64* s_nrings = (u64*)((char*)s_first + b_t8);
-    u64* s_nsplit = (u64*)((char*)s_nrings + b_t8);
-    u64* s_nmerge = (u64*)((char*)s_nsplit + b_t8);
-    int* s_fstep = (int*)((char*)s_nmerge + b_t8);
-    int* s_lstep = (int*)((char*)s_fstep + b_t4);
+    long long* s_first; u64 *s_nrings, *s_nsplit, *s_nmerge; int *s_fstep, *s_lstep; size_t b_counts = 0;
+    auto lay_acc = [&](Carve c) {
+        s_first = c.take<long long>((size_t)nt);
+        b_counts = c.mark();
+        s_nrings = c.take<u64>((size_t)nt); s_nsplit = c.take<u64>((size_t)nt); s_nmerge = c.take<u64>((size_t)nt);
+        b_counts = c.mark() - b_counts;
+        s_fstep = c.take<int>((size_t)nt); s_lstep = c.take<int>((size_t)nt);
+        return c.at;
+    };
+    if (lay_out(ctx, &ctx->cpiece_acc, &ctx->cpiece_acc_bytes, lay_acc) != XC_OK)
+        return bail(fail(ctx, XC_ENOMEM, std::string(who) + ": no memory for the track rows"));
     XC_HIP(ctx, hipMemcpyAsync(d_boff, bo.data(), (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream));
-    XC_HIP(ctx, hipMemsetAsync(s_nrings, 0, 3 * b_t8, ctx->stream));
+    XC_HIP(ctx, hipMemsetAsync(s_nrings, 0, b_counts, ctx->stream));
     XC_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)s_fstep, 0x7fffffff, (size_t)nt, ctx->stream));
     XC_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)s_lstep, (int)0x80000000u, (size_t)nt, ctx->stream));
     hipLaunchKernelGGL(k_rt_rank, dim3((unsigned)nb), blk, 0, ctx->stream, nring, parent, d_boff, (int64_t)nt, trk, s_first);
