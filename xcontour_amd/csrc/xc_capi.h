@@ -1,15 +1,16 @@
-// What the host-only translation units behind the C ABI share: xc_context.hip (context, device memory, events), xc_transport.hip
-// (pinned bounce buffers, xc_sync), xc_keff.hip (the Keff chain) and xc_forms.hip (the host forms of the other kernels).
+// What the translation units behind the C ABI share: xc_context.hip (context, device memory, events), xc_transport.hip (pinned bounce
+// buffers, xc_sync), xc_keff.hip (the Keff chain), xc_forms.hip (the host forms of the other kernels) and the launchers that lay out a
+// device block.  A layout is stated once: lay_out for the kernel scratch and the piece workspaces, lay_stage (xc_stage.h) for the arena.
 #pragma once
 #include "xc_internal.h"
-#include "xc_carve.h"
-#include <assert.h>
+#include "xc_stage.h"
 #include <utility>
 #include <vector>
 
 namespace xc {
 
 inline size_t esize(int dtype) { return dtype == XC_F32 ? 4 : 8; }
+inline bool is_float(int dtype) { return dtype == XC_F32 || dtype == XC_F64; }
 // bytes of a weight array of the given rank (XC_DA_NONE: none)
 inline size_t dA_bytes(int rank, int64_t nslab, int64_t ny, int64_t nx)
 {
@@ -67,29 +68,6 @@ int h2d(xc_ctx* ctx, void* d, const void* h, size_t n);                         
 int stage_in(xc_ctx* ctx, void* slot, const void* h, size_t n, const void** dev);       // big read-only input: *dev = its mirror, else `slot` after an upload
 int stage_small(xc_ctx* ctx, void* slot, const void* h, size_t n, const void** dev);    // small read-only input: mirror, content cache, else `slot`
 int flush_in(xc_ctx* ctx);                                                               // between the staging and the first launch
-int d2h(xc_ctx* ctx, void* h, const void* d, size_t n);                                  // result for the caller's array, handed over by xc_sync
-void* out_direct(xc_ctx* ctx, void* h, size_t n);                                        // pinned bytes the kernels may write `h`'s result into, or null
-
-// One host-form call: a bump allocator over the staging arena (sized up front by ensure_arena: the arena may not move inside a call) and
-// the results the call owes its caller.
-struct Stage {
-    struct Out { void* host; const void* dev; size_t bytes; };
-    xc_ctx* ctx; char* base; size_t off = 0; Out outs[10]; int nout = 0;
-    explicit Stage(xc_ctx* c) : ctx(c), base((char*)c->arena) {}
-    void* take(size_t bytes) { assert(off + al(bytes) <= ctx->arena_bytes); void* p = base + off; off += al(bytes); return p; }
-    // Where the kernels write a result the caller wants in `host`: for results written once and never read back by a kernel (`direct_ok`) a
-    // slot of the pinned output buffer where out_direct grants one, else arena bytes that deliver() fetches.  Null when `host` is null ...
-    template <typename T> T* out(T* host, size_t bytes, bool direct_ok = false) { return host ? keep(host, bytes, direct_ok) : nullptr; }
-    // ... or, for a buffer the kernels write whether or not the caller wants it back, arena bytes nobody fetches
-    template <typename T> T* keep(T* host, size_t bytes, bool direct_ok = false)
-    {
-        if (host && direct_ok) if (void* p = out_direct(ctx, host, bytes)) return (T*)p;
-        T* d = (T*)take(bytes);
-        if (host) { assert(nout < 10); outs[nout++] = {host, d, bytes}; }
-        return d;
-    }
-    // after the last launch: the copies of every arena-backed result, in the order they were asked for; the caller ends in xc_sync
-    int deliver() { for (int i = 0; i < nout; ++i) XC_TRY(d2h(ctx, outs[i].host, outs[i].dev, outs[i].bytes)); return XC_OK; }
-};
+// (d2h, out_direct and Stage, the arena blocks of one host-form call with lay_stage, its layout stated once: xc_stage.h)
 
 }  // namespace xc

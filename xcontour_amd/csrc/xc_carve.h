@@ -1,7 +1,8 @@
-// The layout of a device workspace, stated once.  A launcher writes the blocks of its workspace as one function lay(Carve) that takes them
-// in order, fills the launcher's pointers and returns the carve's `at`, and runs it twice (lay_out, xc_capi.h): over Carve() to measure
-// -- the total goes to grow(); every pointer comes back null, none is formed from the null base -- and over Carve(workspace) to place.
-// The bytes asked for and the bytes laid out are one statement.  Plain C++17, no HIP header (tests/test_carve_host.py runs it sanitized).
+// The layout of a device block, stated once: the piece workspaces, the kernel scratch (K3, K9, K10, K12, K15) and, under Stage
+// (xc_stage.h), the staging arena of the host forms.  A launcher writes the blocks as one function lay(Carve) that takes them in order,
+// fills the launcher's pointers and returns the carve's `at`, and runs it twice (lay_out, xc_capi.h): over Carve() to measure -- the total
+// goes to grow(); every pointer comes back null, none is formed from the null base -- and over Carve(block) to place.  The bytes asked
+// for and the bytes laid out are one statement.  Plain C++17, no HIP header (tests/test_carve_host.py runs it sanitized).
 #pragma once
 #include <stddef.h>
 

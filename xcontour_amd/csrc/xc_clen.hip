@@ -178,17 +178,13 @@ int launch_contour_lengths(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsla
         g.q_dtype = q_dtype; g.latlon = radius > 0.0; g.N = N; g.ncopy = ncopy; g.G = G; g.ngroup = ngroup;
         g.ntile = wg.ntile; g.bps = (int32_t)bps; g.bps_rule = wg.bps_rule; g.nslab = nslab;
     }
-    const size_t pl = al((size_t)nslab * bps * kDetLimbsX * N * 8), pc = al((size_t)nslab * bps * N * 4);
-    const size_t pw = al((size_t)nslab * 4), pn = out_nseg ? 0 : al((size_t)nslab * N * 8);
-    {
-        const int rc = ensure_scratch(ctx, pl + pc + pw + pn + 256);
-        if (rc != XC_OK) return rc;
-    }
-    char* sc = (char*)ctx->scratch;
-    unsigned long long* part_l = (unsigned long long*)sc;
-    unsigned* part_c = (unsigned*)(sc + pl);
-    int* c0 = (int*)(sc + pl + pc);
-    unsigned long long* nseg = out_nseg ? (unsigned long long*)out_nseg : (unsigned long long*)(sc + pl + pc + pw);
+    unsigned long long *part_l, *nseg; unsigned* part_c; int* c0;
+    XC_TRY(lay_out(ctx, &ctx->scratch, &ctx->scratch_bytes, [&](Carve c) {
+        part_l = c.take<unsigned long long>((size_t)nslab * bps * kDetLimbsX * N); part_c = c.take<unsigned>((size_t)nslab * bps * N);
+        c0 = c.take<int>((size_t)nslab);
+        nseg = out_nseg ? (unsigned long long*)out_nseg : c.take<unsigned long long>((size_t)nslab * N);
+        return c.at;
+    }));
     const int latlon = radius > 0.0;
     {
         const int rc = launch_clen_window(ctx, ycoord, ny, xcoord, nx, period, latlon, nslab, c0);

@@ -211,22 +211,14 @@ int launch_contour_line_integrals(xc_ctx* ctx, const void* q, int q_dtype, const
     constexpr int NL = CLINE_NCH * kDetLimbsX;
     const int64_t ncell = ny * nx;
     const int P = minmax_blocks(ncell, nslab);
-    const size_t pl = al((size_t)nslab * bps * NL * N * 8), pc = al((size_t)nslab * bps * N * 4);
-    const size_t pw = al((size_t)nslab * CLINE_NCH * 4), pr = al((size_t)nslab * CLINE_NCH * N * 8);
-    const size_t pn = out_nseg ? 0 : al((size_t)nslab * N * 8);
-    const size_t pm = al((size_t)nslab * P * 16), pf = al((size_t)nslab * 16);
-    {
-        const int rc = ensure_scratch(ctx, pl + pc + pw + pr + pn + pm + pf + 256);
-        if (rc != XC_OK) return rc;
-    }
-    char* sc = (char*)ctx->scratch;
-    unsigned long long* part_l = (unsigned long long*)sc;               sc += pl;
-    unsigned* part_c = (unsigned*)sc;                                   sc += pc;
-    int* c0 = (int*)sc;                                                 sc += pw;
-    double* red = (double*)sc;                                          sc += pr;
-    unsigned long long* nseg = out_nseg ? (unsigned long long*)out_nseg : (unsigned long long*)sc;   sc += pn;
-    double* mmpart = (double*)sc;                                       sc += pm;
-    double* mm = (double*)sc;
+    unsigned long long *part_l, *nseg; unsigned* part_c; int* c0; double *red, *mmpart, *mm;
+    XC_TRY(lay_out(ctx, &ctx->scratch, &ctx->scratch_bytes, [&](Carve c) {
+        part_l = c.take<unsigned long long>((size_t)nslab * bps * NL * N); part_c = c.take<unsigned>((size_t)nslab * bps * N);
+        c0 = c.take<int>((size_t)nslab * CLINE_NCH); red = c.take<double>((size_t)nslab * CLINE_NCH * N);
+        nseg = out_nseg ? (unsigned long long*)out_nseg : c.take<unsigned long long>((size_t)nslab * N);
+        mmpart = c.take<double>((size_t)nslab * P * 2); mm = c.take<double>((size_t)nslab * 2);
+        return c.at;
+    }));
     const int latlon = radius > 0.0;
     // the integrand's finite extrema (K1), then both window constants of every slab
     XC_TRY(launch_minmax_partial(ctx, f, f_dtype, nslab, ncell, mmpart, nullptr, 0, true));

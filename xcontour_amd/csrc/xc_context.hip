@@ -52,7 +52,7 @@ int grow(xc_ctx* ctx, void** p, size_t* have, size_t need)
 }
 
 int ensure_scratch(xc_ctx* ctx, size_t bytes) { return grow(ctx, &ctx->scratch, &ctx->scratch_bytes, bytes); }
-int ensure_arena(xc_ctx* ctx, size_t bytes)   { return grow(ctx, &ctx->arena, &ctx->arena_bytes, bytes); }
+int ensure_arena(xc_ctx* ctx, size_t bytes, void** base) { const int rc = grow(ctx, &ctx->arena, &ctx->arena_bytes, bytes); *base = ctx->arena; return rc; }
 int ensure_big(xc_ctx* ctx, size_t bytes)     { return grow(ctx, &ctx->big, &ctx->big_bytes, bytes); }
 
 int ensure_ones(xc_ctx* ctx, size_t n)

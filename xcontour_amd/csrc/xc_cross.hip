@@ -18,7 +18,7 @@
 // shared by consecutive boxes, so every corner row is loaded once per tile.  Sums live in LDS
 // (ds_add_f64 / ds_add_u32), one partial vector per block, reduced in fixed order afterwards.
 // HBM-bound: tracer (4|8 B) + area (4|8 B) per fine cell at stride 1, independent of N.
-#include "xc_internal.h"
+#include "xc_capi.h"
 #include <stdlib.h>
 
 namespace xc {
@@ -536,13 +536,11 @@ int launch_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int6
     const int64_t nti = cols ? ((nbi + nbw - 1) / nbw + 3) / 4 : (nbi + tw - 1) / tw;
     const int env_blocks = ctx->knobs.cross_blocks;                                                                // experiment knob (xc_create)
     int64_t bps = (env_blocks > 0 ? env_blocks : 2048) / nslab; if (bps < 8) bps = 8; if (bps > ntj * nti) bps = ntj * nti;
-    const size_t pl = (size_t)nslab * bps * N * 8, pc = (size_t)nslab * bps * N * 4;
-    {
-        const int rc = ensure_scratch(ctx, ((pl + 255) & ~(size_t)255) + pc);
-        if (rc != XC_OK) return rc;
-    }
-    double* part_len = (double*)ctx->scratch;
-    unsigned* part_cnt = (unsigned*)((char*)ctx->scratch + ((pl + 255) & ~(size_t)255));
+    double* part_len; unsigned* part_cnt;
+    XC_TRY(lay_out(ctx, &ctx->scratch, &ctx->scratch_bytes, [&](Carve c) {
+        part_len = c.take<double>((size_t)nslab * bps * N); part_cnt = c.take<unsigned>((size_t)nslab * bps * N);
+        return c.at;
+    }));
     const dim3 grid((unsigned)bps, (unsigned)nslab);
 #define XC_CROSS4(TQ_, TA_, C_, S_) do { \
         if (lds > 64 * 1024) XC_HIP(ctx, hipFuncSetAttribute((const void*)k_crossing<TQ_, TA_, C_, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \

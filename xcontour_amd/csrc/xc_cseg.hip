@@ -191,15 +191,12 @@ int launch_contour_segments(xc_ctx* ctx, const void* q, int q_dtype, int64_t nsl
     const int64_t ntj = wg.ntj, nti = wg.nti, bps = wg.bps;
     if (bps > 0x7fffffff) return fail(ctx, XC_EBADARG, "xc_contour_segments: plane too large");
     const int64_t M = nslab * (int64_t)N;
-    const size_t pc = al((size_t)nslab * bps * N * 4), po = al((size_t)nslab * bps * N * 8), pf = al((size_t)(M + 1) * 8);
-    {
-        const int rc = ensure_scratch(ctx, pc + po + pf + 256);
-        if (rc != XC_OK) return rc;
-    }
-    char* sc = (char*)ctx->scratch;
-    unsigned* part = (unsigned*)sc;
-    unsigned long long* part_off = (unsigned long long*)(sc + pc);
-    long long* off = (long long*)(sc + pc + po);
+    unsigned* part; unsigned long long* part_off; long long* off;
+    XC_TRY(lay_out(ctx, &ctx->scratch, &ctx->scratch_bytes, [&](Carve c) {
+        part = c.take<unsigned>((size_t)nslab * bps * N); part_off = c.take<unsigned long long>((size_t)nslab * bps * N);
+        off = c.take<long long>((size_t)(M + 1));
+        return c.at;
+    }));
     const dim3 grid((unsigned)bps, (unsigned)nslab, (unsigned)ngroup);
 #define XC_CSEG_ARGS(TQ_) (const TQ_*)q, ny, nx, contours, N, contours_per_slab, G, ntj, nti, (int)bps, part, part_off, off, (long long)capacity, \
                           (long long*)e_from, (long long*)e_to, pts

@@ -17,6 +17,20 @@ static bool check_ascending(const double* contours, int64_t nc, int ncont)
     return true;
 }
 
+// what several forms refuse alike, each under its own name: a coordinate that is not finite ...
+static int check_coords(xc_ctx* ctx, const char* who, const double* ycoord, int64_t ny, const double* xcoord, int64_t nx)
+{
+    for (int64_t i = 0; i < ny + nx; ++i)
+        if (!std::isfinite(i < ny ? ycoord[i] : xcoord[i - ny])) return fail(ctx, XC_EBADARG, std::string(who) + ": coordinates must be finite");
+    return XC_OK;
+}
+// ... and levels, one set (*nc = 1) or one per slab, that do not ascend
+static int check_levels(xc_ctx* ctx, const char* who, const double* contours, int contours_per_slab, int64_t nslab, int ncont, int64_t* nc)
+{
+    *nc = contours_per_slab ? nslab : 1;
+    return check_ascending(contours, *nc, ncont) ? XC_OK : fail(ctx, XC_EEDGES, std::string(who) + ": contours must be ascending without NaN");
+}
+
 // xc_last_clen_geometry: launch_contour_lengths writes the record where it picks the geometry; a call that fails leaves it cleared
 static int clen_recorded(xc_ctx* ctx, int rc)
 {
@@ -42,13 +56,10 @@ static int local_contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, i
 {
     if (!q || !ycoord || !xcoord || !out_len || nslab < 1 || ny < 1 || nx < 1)
         return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad dtype");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad dtype");
     if (wy < 2 || wx < 2) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: the window must be at least 2 x 2 nodes");
     if (sy < 1 || sx < 1) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: strides must be >= 1");
-    for (int64_t i = 0; i < ny; ++i)
-        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
-    for (int64_t i = 0; i < nx; ++i)
-        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: coordinates must be finite");
+    XC_TRY(check_coords(ctx, "xc_local_contour_lengths", ycoord, ny, xcoord, nx));
     if (periodic && !check_period(xcoord, nx, period))
         return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: period must be finite, non-zero, of the sign of "
                                      "xcoord[nx-1] - xcoord[0] and longer than that span, and nx >= 2");
@@ -56,11 +67,11 @@ static int local_contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, i
         return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: the window must not be wider than the ring (wx <= nx)");
     const size_t nwin = (size_t)((ny + sy - 1) / sy) * (size_t)((nx + sx - 1) / sx);
     const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, ob = (size_t)nslab * nwin * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + 4 * al(ob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb);
-    double* dv = levels ? (double*)st.take(ob) : nullptr;
-    double* dl = st.out(out_len, ob); double* de = st.out(out_level, ob); uint64_t* dn = st.out(out_nseg, ob);
+    Stage st(ctx); void* dq; double *dy, *dx, *dv, *dl, *de; uint64_t* dn;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); dy = s.take<double>(yb); dx = s.take<double>(xb); dv = levels ? s.take<double>(ob) : nullptr;
+        dl = s.out(out_len, ob); de = s.out(out_level, ob); dn = s.out(out_nseg, ob);
+    }));
     const void* pq;                                          // (a tracer with a device mirror is read where it is)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb));
     if (levels) XC_TRY(h2d(ctx, dv, levels, ob));
@@ -78,23 +89,20 @@ static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t
 {
     if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
         return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad dtype");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad dtype");
     if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: radius must be >= 0");
-    for (int64_t i = 0; i < ny; ++i)
-        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
-    for (int64_t i = 0; i < nx; ++i)
-        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_lengths: coordinates must be finite");
+    XC_TRY(check_coords(ctx, "xc_contour_lengths", ycoord, ny, xcoord, nx));
     if (periodic && !check_period(xcoord, nx, period))
         return fail(ctx, XC_EBADARG, "xc_contour_lengths_periodic: period must be finite, non-zero, of the sign of xcoord[nx-1] - xcoord[0] "
                                      "and longer than that span, and nx >= 2");
-    const int64_t nc = contours_per_slab ? nslab : 1;
-    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_lengths: contours must be ascending without NaN");
+    int64_t nc; XC_TRY(check_levels(ctx, "xc_contour_lengths", contours, contours_per_slab, nslab, ncont, &nc));
     const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
     const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(yb) + al(xb) + al(cb) + 2 * al(ob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb); double* dc = (double*)st.take(cb);
-    double* dl = st.out(out_len, ob); uint64_t* dn = st.out(out_nseg, ob);
+    Stage st(ctx); void* dq; double *dy, *dx, *dc, *dl; uint64_t* dn;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = s.take<double>(cb);
+        dl = s.out(out_len, ob); dn = s.out(out_nseg, ob);
+    }));
     const void* pq;                                          // (a tracer with a device mirror is read where it is)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
     XC_TRY(flush_in(ctx));
@@ -111,25 +119,20 @@ static int contour_line_integrals_host(xc_ctx* ctx, const void* q, int q_dtype, 
 {
     if (!q || !f || !ycoord || !xcoord || !contours || !out_integral || !out_length || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
         return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad arguments");
-    if ((q_dtype != XC_F32 && q_dtype != XC_F64) || (f_dtype != XC_F32 && f_dtype != XC_F64))
-        return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad dtype");
+    if (!is_float(q_dtype) || !is_float(f_dtype)) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad dtype");
     if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: radius must be >= 0");
-    for (int64_t i = 0; i < ny; ++i)
-        if (!std::isfinite(ycoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: coordinates must be finite");
-    for (int64_t i = 0; i < nx; ++i)
-        if (!std::isfinite(xcoord[i])) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: coordinates must be finite");
+    XC_TRY(check_coords(ctx, "xc_contour_line_integrals", ycoord, ny, xcoord, nx));
     if (period != 0.0 && !check_period(xcoord, nx, period))
         return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: period must be 0, or finite, of the sign of xcoord[nx-1] - xcoord[0] "
                                      "and longer than that span, and nx >= 2");
-    const int64_t nc = contours_per_slab ? nslab : 1;
-    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_line_integrals: contours must be ascending without NaN");
+    int64_t nc; XC_TRY(check_levels(ctx, "xc_contour_line_integrals", contours, contours_per_slab, nslab, ncont, &nc));
     const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype), fb = cells * esize(f_dtype);
     const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(fb) + al(yb) + al(xb) + al(cb) + 3 * al(ob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); void* df = st.take(fb);
-    double* dy = (double*)st.take(yb); double* dx = (double*)st.take(xb); double* dc = (double*)st.take(cb);
-    double* di = st.out(out_integral, ob); double* dl = st.out(out_length, ob); uint64_t* dn = st.out(out_nseg, ob);
+    Stage st(ctx); void *dq, *df; double *dy, *dx, *dc, *di, *dl; uint64_t* dn;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); df = s.take(fb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = s.take<double>(cb);
+        di = s.out(out_integral, ob); dl = s.out(out_length, ob); dn = s.out(out_nseg, ob);
+    }));
     const void* pq; const void* pf;                          // (a tracer / integrand with a device mirror is read where it is)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(stage_in(ctx, df, f, fb, &pf));
     XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
@@ -155,19 +158,17 @@ int xc_rowsum(xc_ctx* ctx, const void* mask, int mask_dtype, const double* dA, i
 {
     XC_CTX(ctx);
     if (!out_rows || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_rowsum: bad arguments");
-    if (mask && mask_dtype != XC_F32 && mask_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_rowsum: bad mask dtype");
+    if (mask && !is_float(mask_dtype)) return fail(ctx, XC_EBADARG, "xc_rowsum: bad mask dtype");
     const size_t mb = mask ? (size_t)ny * nx * esize(mask_dtype) : 0;
     const size_t dab = dA_rank == XC_DA_SLAB ? 0 : dA_bytes(dA_rank, 1, ny, nx);     // (per-slab weights: left to the launcher to reject)
     if (dab && !dA) return fail(ctx, XC_EBADARG, "xc_rowsum: dA is NULL");
-    XC_TRY(ensure_arena(ctx, al(mb) + al(dab) + al((size_t)ny * 8)));
-    Stage st(ctx);
-    void* dm = nullptr; double* dd = nullptr;
-    // (resident inputs are read where they are: no device-to-device copy into the arena)
-    if (mb) { const void* p; XC_TRY(stage_in(ctx, st.take(mb), mask, mb, &p)); dm = const_cast<void*>(p); }
-    if (dab) { const void* p; XC_TRY(stage_in(ctx, st.take(dab), dA, dab, &p)); dd = (double*)const_cast<void*>(p); }
-    double* dout = st.out(out_rows, (size_t)ny * 8, true);
+    Stage st(ctx); void *sm = nullptr, *sd = nullptr; double* dout;
+    XC_TRY(lay_stage(st, [&](Stage& s) { if (mb) sm = s.take(mb); if (dab) sd = s.take(dab); dout = s.out(out_rows, (size_t)ny * 8, true); }));
+    const void *dm = nullptr, *dd = nullptr;                 // (resident inputs are read where they are: no device-to-device copy into the arena)
+    if (mb) XC_TRY(stage_in(ctx, sm, mask, mb, &dm));
+    if (dab) XC_TRY(stage_in(ctx, sd, dA, dab, &dd));
     XC_TRY(flush_in(ctx));
-    XC_TRY(launch_rowsum(ctx, dm, mask_dtype, dd, dA_rank, ny, nx, multiply, dout));
+    XC_TRY(launch_rowsum(ctx, dm, mask_dtype, (const double*)dd, dA_rank, ny, nx, multiply, dout));
     XC_TRY(st.deliver());
     return xc_sync(ctx);
 }
@@ -185,11 +186,10 @@ int xc_grad2(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny,
 {
     XC_CTX(ctx);
     if (!q || !rdx || !rdy || !out || nslab < 1 || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_grad2: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_grad2: bad dtype");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_grad2: bad dtype");
     const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype), ob = cells * 8, rb = (size_t)ny * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(ob) + 2 * al(rb)));
-    Stage st(ctx);
-    void* dq = st.take(qb); double* dx = (double*)st.take(rb); double* dy = (double*)st.take(rb); double* dout = st.out(out, ob);
+    Stage st(ctx); void* dq; double *dx, *dy, *dout;
+    XC_TRY(lay_stage(st, [&](Stage& s) { dq = s.take(qb); dx = s.take<double>(rb); dy = s.take<double>(rb); dout = s.out(out, ob); }));
     const void* pq;                                          // (a tracer with a device mirror is read where it is)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dx, rdx, rb)); XC_TRY(h2d(ctx, dy, rdy, rb));
     XC_TRY(flush_in(ctx));
@@ -217,17 +217,13 @@ int xc_crossing(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t 
     XC_CTX(ctx);
     if (!q || !contours || !area || (!out_len && !out_cnt) || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
         return fail(ctx, XC_EBADARG, "xc_crossing: bad arguments");
-    if ((q_dtype != XC_F32 && q_dtype != XC_F64) || (area_dtype != XC_F32 && area_dtype != XC_F64))
-        return fail(ctx, XC_EBADARG, "xc_crossing: bad dtype");
-    const int64_t nc = contours_per_slab ? nslab : 1;
-    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_crossing: contours must be ascending without NaN");
+    if (!is_float(q_dtype) || !is_float(area_dtype)) return fail(ctx, XC_EBADARG, "xc_crossing: bad dtype");
+    int64_t nc; XC_TRY(check_levels(ctx, "xc_crossing", contours, contours_per_slab, nslab, ncont, &nc));
     const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
     const size_t ab = (area_per_slab ? cells : (size_t)ny * nx) * esize(area_dtype);
     const size_t cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(ab) + al(cb) + 2 * al(ob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); void* da = st.take(ab); double* dc = (double*)st.take(cb);
-    double* dl = st.out(out_len, ob); uint64_t* dn = st.out(out_cnt, ob);
+    Stage st(ctx); void *dq, *da; double *dc, *dl; uint64_t* dn;
+    XC_TRY(lay_stage(st, [&](Stage& s) { dq = s.take(qb); da = s.take(ab); dc = s.take<double>(cb); dl = s.out(out_len, ob); dn = s.out(out_cnt, ob); }));
     const void* pq; const void* pa;                          // (tracer / areas with a device mirror are read where they are)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(stage_in(ctx, da, area, ab, &pa)); XC_TRY(h2d(ctx, dc, contours, cb));
     XC_TRY(flush_in(ctx));
@@ -388,14 +384,12 @@ static int contour_segments_host(xc_ctx* ctx, const void* q, int q_dtype, int64_
     if (!q || !contours || !out_count || nslab < 1 || ny < 1 || nx < 1 || ncont < 1 || capacity < 0)
         return fail(ctx, XC_EBADARG, "xc_contour_segments: bad arguments");
     if (wrap && nx < 2) return fail(ctx, XC_EBADARG, "xc_contour_segments_periodic: nx >= 2");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contour_segments: bad dtype");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_contour_segments: bad dtype");
     if (capacity > 0 && (!e_from || !e_to || !pts)) return fail(ctx, XC_EBADARG, "xc_contour_segments: capacity > 0 needs the record arrays");
-    const int64_t nc = contours_per_slab ? nslab : 1;
-    if (!check_ascending(contours, nc, ncont)) return fail(ctx, XC_EEDGES, "xc_contour_segments: contours must be ascending without NaN");
+    int64_t nc; XC_TRY(check_levels(ctx, "xc_contour_segments", contours, contours_per_slab, nslab, ncont, &nc));
     const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(cb) + al(ob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); double* dc = (double*)st.take(cb); uint64_t* dn = st.out(out_count, ob);
+    Stage st(ctx); void* dq; double* dc; uint64_t* dn;
+    XC_TRY(lay_stage(st, [&](Stage& s) { dq = s.take(qb); dc = s.take<double>(cb); dn = s.out(out_count, ob); }));
     const void* pq;                                          // (a tracer with a device mirror is read where it is)
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dc, contours, cb));
     XC_TRY(flush_in(ctx));
@@ -458,7 +452,7 @@ int xc_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const doubl
 {
     XC_CTX(ctx);
     if (!q || !Q || !coord || !dA || !out_lwa || nslab < 1 || ny < 2 || nx < 1) return fail(ctx, XC_EBADARG, "xc_lwa: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_lwa: bad dtype");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_lwa: bad dtype");
     if (nmask < 0 || (nmask > 0 && (!mask_idx || !out_masks))) return fail(ctx, XC_EBADARG, "xc_lwa: mask arguments");
     for (int i = 0; i < nmask; ++i)
         if (mask_idx[i] < 0 || mask_idx[i] >= ny) return fail(ctx, XC_EBADARG, "indices in mask_idx out of boundary");
@@ -466,12 +460,11 @@ int xc_lwa(xc_ctx* ctx, const void* q, int q_dtype, const double* Q, const doubl
     const size_t qb = cells * esize(q_dtype), Qb = (size_t)nslab * ny * 8, cb = (size_t)ny * 8;
     const size_t dab = dA_bytes(dA_rank, 1, ny, nx), Mb = dA_bytes(M_rank, 1, ny, nx);      // (ROW or PLANE, checked by the launcher; M: or none)
     const size_t ob = cells * 8, mib = (size_t)nmask * 4, mob = (size_t)nmask * cells;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(Qb) + al(cb) + al(dab) + al(Mb) + al(ob) + al(mib) + al(mob)));
-    Stage st(ctx);
-    void* dq = st.take(qb); double* dQ = (double*)st.take(Qb); double* dc = (double*)st.take(cb);
-    double* dd = (double*)st.take(dab); double* dM = Mb ? (double*)st.take(Mb) : nullptr;
-    double* dout = st.out(out_lwa, ob);
-    int32_t* dmi = nmask ? (int32_t*)st.take(mib) : nullptr; int8_t* dmo = nmask ? st.out(out_masks, mob) : nullptr;
+    Stage st(ctx); void* dq; double *dQ, *dc, *dd, *dM, *dout; int32_t* dmi; int8_t* dmo;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); dQ = s.take<double>(Qb); dc = s.take<double>(cb); dd = s.take<double>(dab); dM = Mb ? s.take<double>(Mb) : nullptr;
+        dout = s.out(out_lwa, ob); dmi = nmask ? s.take<int32_t>(mib) : nullptr; dmo = nmask ? s.out(out_masks, mob) : nullptr;
+    }));
     // the read-only planes are used where they are when they have a device mirror (the weights of a resident object: no device-to-device
     // copy per call); Q and the coordinate are small (pinned buffer + copy kernel)
     const void* pq; const void* pd; const void* pM = nullptr;
@@ -507,29 +500,30 @@ int xc_sort_profile_batch(xc_ctx* ctx, const void* q, int q_dtype, const void* m
 {
     XC_CTX(ctx);
     if (!q || ny < 1 || nx < 1 || nslab < 1 || J < 0) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad dtype");
-    if (mask && mask_dtype != XC_F32 && mask_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad mask dtype");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad dtype");
+    if (mask && !is_float(mask_dtype)) return fail(ctx, XC_EBADARG, "xc_sort_profile: bad mask dtype");
     const size_t S = (size_t)nslab, n = (size_t)ny * nx;
     const size_t qb = S * n * esize(q_dtype), mb = mask ? (mask_per_slab ? S : 1) * n * esize(mask_dtype) : 0;
     const size_t dab = dA_bytes(dA_rank, nslab, ny, nx);
     if (dab && !dA) return fail(ctx, XC_EBADARG, "xc_sort_profile: dA is NULL");
     const size_t tb = (size_t)J * 8, Qb = S * tb, tbb = (out_bpe ? (size_t)ntbl * 8 : 0);
-    XC_TRY(ensure_arena(ctx, al(qb) + al(mb) + al(dab) + al(tb) + al(Qb) + 2 * al(tbb) + 2 * al(S * n * 8) + al(S * 4) + al(S * 8)));
-    Stage st(ctx);
-    void* dq = st.take(qb); XC_TRY(h2d(ctx, dq, q, qb));
-    void* dm = nullptr; if (mb) { dm = st.take(mb); XC_TRY(h2d(ctx, dm, mask, mb)); }
-    double* dd = nullptr; if (dab) { dd = (double*)st.take(dab); XC_TRY(h2d(ctx, dd, dA, dab)); }
-    double* dt = nullptr; double* dQ = nullptr;
-    if (J > 0 && out_Q) { dt = (double*)st.take(tb); dQ = st.out(out_Q, Qb); XC_TRY(h2d(ctx, dt, targets, tb)); }
-    double *dtbl = nullptr, *dcrd = nullptr;
+    Stage st(ctx); void *dq, *dm = nullptr; double *dd = nullptr, *dt = nullptr, *dQ = nullptr, *dtbl = nullptr, *dcrd = nullptr, *dqs, *dac, *dbpe; uint32_t* dnv;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); if (mb) dm = s.take(mb); if (dab) dd = s.take<double>(dab);
+        if (J > 0 && out_Q) { dt = s.take<double>(tb); dQ = s.out(out_Q, Qb); }
+        if (out_bpe) { dtbl = s.take<double>(tbb); dcrd = s.take<double>(tbb); }
+        dqs = s.out(out_qsorted, S * n * 8); dac = s.out(out_acum, S * n * 8);
+        dnv = s.keep(out_nvalid, S * 4);                     // (the kernel counts whether the caller asks or not)
+        dbpe = s.out(out_bpe, S * 8);
+    }));
+    XC_TRY(h2d(ctx, dq, q, qb));
+    if (mb) XC_TRY(h2d(ctx, dm, mask, mb));
+    if (dab) XC_TRY(h2d(ctx, dd, dA, dab));
+    if (J > 0 && out_Q) XC_TRY(h2d(ctx, dt, targets, tb));
     if (out_bpe) {
         if (!tbl || !coord || ntbl < 2) return fail(ctx, XC_EBADARG, "xc_sort_profile: BPE needs tbl/coord");
-        dtbl = (double*)st.take(tbb); dcrd = (double*)st.take(tbb);
         XC_TRY(h2d(ctx, dtbl, tbl, tbb)); XC_TRY(h2d(ctx, dcrd, coord, tbb));
     }
-    double* dqs = st.out(out_qsorted, S * n * 8); double* dac = st.out(out_acum, S * n * 8);
-    uint32_t* dnv = st.keep(out_nvalid, S * 4);              // (the kernel counts whether the caller asks or not)
-    double* dbpe = st.out(out_bpe, S * 8);
     XC_TRY(flush_in(ctx));
     XC_TRY(xc_sort_profile_batch_dev(ctx, dq, q_dtype, dm, mask_dtype, mask_per_slab, dd, dA_rank, nslab, ny, nx, negate,
                                      dt, dQ ? J : 0, dtbl, dcrd, ntbl, dQ, dqs, dac, dnv, dbpe));

@@ -142,7 +142,6 @@ inline int profile_get(xc_ctx* ctx, CpProfile xc_ctx::* rec, int nms, double* ms
 
 // grow-only scratch (never shrinks; pointer may change between calls, never within one)
 int ensure_scratch(xc_ctx* ctx, size_t bytes);
-int ensure_arena(xc_ctx* ctx, size_t bytes);
 int ensure_ones(xc_ctx* ctx, size_t n);
 int ensure_big(xc_ctx* ctx, size_t bytes);
 

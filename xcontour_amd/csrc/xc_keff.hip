@@ -31,7 +31,7 @@ static int check_hist_desc(xc_ctx* ctx, const xc_hist_desc* d)
 {
     if (!d) return fail(ctx, XC_EBADARG, "xc_hist: desc is NULL");
     if (!d->q || !d->edges) return fail(ctx, XC_EBADARG, "xc_hist: q / edges is NULL");
-    if (d->q_dtype != XC_F32 && d->q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_hist: q_dtype must be XC_F32 or XC_F64");
+    if (!is_float(d->q_dtype)) return fail(ctx, XC_EBADARG, "xc_hist: q_dtype must be XC_F32 or XC_F64");
     if (d->nslab < 1 || d->ny < 1 || d->nx < 1) return fail(ctx, XC_EBADARG, "xc_hist: nslab, ny, nx must be >= 1");
     if (d->nedge < 2) return fail(ctx, XC_EBADARG, "xc_hist: need at least 2 edges");
     if (d->dA_rank < XC_DA_NONE || d->dA_rank > XC_DA_SLAB) return fail(ctx, XC_EBADARG, "xc_hist: bad dA_rank");
@@ -39,7 +39,7 @@ static int check_hist_desc(xc_ctx* ctx, const xc_hist_desc* d)
     if (d->nint < 0 || d->nint > XC_MAX_INTEGRANDS) return fail(ctx, XC_EBADARG, "xc_hist: nint must be 0..2");
     for (int i = 0; i < d->nint; ++i) {
         if (!d->integrand[i]) return fail(ctx, XC_EBADARG, "xc_hist: integrand is NULL");
-        if (d->integrand_dtype[i] != XC_F32 && d->integrand_dtype[i] != XC_F64) return fail(ctx, XC_EBADARG, "xc_hist: bad integrand dtype");
+        if (!is_float(d->integrand_dtype[i])) return fail(ctx, XC_EBADARG, "xc_hist: bad integrand dtype");
     }
     if (d->grad && (!d->rdx || !d->rdy)) return fail(ctx, XC_EBADARG, "xc_hist: grad needs rdx and rdy");
     if (d->grad && d->negate) return fail(ctx, XC_EBADARG, "xc_hist: negate is not available together with grad");
@@ -47,38 +47,36 @@ static int check_hist_desc(xc_ctx* ctx, const xc_hist_desc* d)
     return XC_OK;
 }
 
-// The scratch of one K3 call, in this order: K1's min / max partials (the chain only), the blocks' partial sums and counts, the per-slab
-// reduced sums and counts (adjacent: the few-slab path clears both as acc_words() words from red_h()), and for the deterministic sums the
-// window constants and the bounds det_one_pass takes: K1 partials of one array at a time + (min, max) pairs of dA, the tracer, the integrands.
+// K1's min / max partials of `nslab` slabs as a block of a layout -- and as the whole scratch of a call that runs K1 alone (xc_minmax_dev, xc_contours)
+static double* k1_part(Carve& c, int64_t nslab) { return c.take<double>((size_t)nslab * kMinmaxBlocks * 2); }
+static int k1_scratch(xc_ctx* ctx, int64_t nslab, double** part)
+{
+    return lay_out(ctx, &ctx->scratch, &ctx->scratch_bytes, [&](Carve c) { *part = k1_part(c, nslab); return c.at; });
+}
+
+// The scratch of one K3 call, one layout in this order: K1's min / max partials (the chain only; the base of the block either way), the blocks'
+// partial sums and counts, the per-slab reduced sums and counts (adjacent: the few-slab path clears both as acc_words words from red_h), and
+// for the deterministic sums the window constants and the bounds det_one_pass takes: K1 partials of one array at a time + (min, max) pairs
+// of dA, the tracer, the integrands (det_pair 0, 1, 2..).  A block a mode does not use has no bytes.
 struct K3Scratch {
-    size_t o_ph, o_pc, o_rh, o_rc, o_c0, o_dp, o_dm, pair_bytes, total = 0;  char* base = nullptr;
-    size_t put(size_t bytes) { const size_t at = total; total += al(bytes); return at; }
-    // part_h = false: the partial sums are the caller's own array (the stand-alone epilogue reduces ONE partial per slab, the pdf)
-    K3Scratch(int64_t nslab, int bps, int nch, int nbin, int det, bool minmax_partials, bool part_h = true)
+    double *mmpart, *part_h, *red_h, *det_part, *det_pair[3 + XC_MAX_INTEGRANDS];
+    unsigned* part_c; unsigned long long* red_c; int* c0; size_t part_c_bytes; int64_t acc_words;
+    // own_part_h = false: the partial sums are the caller's own array (the stand-alone epilogue reduces ONE partial per slab, the pdf)
+    int reserve(xc_ctx* ctx, int64_t nslab, int bps, int nch, int nbin, int det, bool minmax_partials, bool own_part_h = true)
     {
-        const size_t S = (size_t)nslab, mmb = S * kMinmaxBlocks * 2 * sizeof(double);
-        put(minmax_partials ? mmb : 0);
-        // (deterministic sums: a block's partial is the limbs of its superaccumulators instead of one double per channel)
-        o_ph = put(part_h ? S * bps * (det ? det_limbs_total(nch) : nch) * nbin * sizeof(double) : 0);
-        o_pc = put(S * bps * nbin * sizeof(unsigned));
-        o_rh = put(S * nch * nbin * sizeof(double));
-        o_rc = put(S * nbin * sizeof(unsigned long long));
-        o_c0 = put(det ? S * nch * sizeof(int) : 0);
-        o_dp = put(det ? mmb : 0);
-        pair_bytes = al(S * 2 * sizeof(double));
-        o_dm = put(det ? (3 + XC_MAX_INTEGRANDS) * pair_bytes : 0);
+        const size_t S = (size_t)nslab;
+        return lay_out(ctx, &ctx->scratch, &ctx->scratch_bytes, [&](Carve c) {
+            mmpart = k1_part(c, minmax_partials ? nslab : 0);
+            // (deterministic sums: a block's partial is the limbs of its superaccumulators instead of one double per channel)
+            part_h = c.take<double>(own_part_h ? S * bps * (det ? det_limbs_total(nch) : nch) * nbin : 0);
+            const size_t m0 = c.mark(); part_c = c.take<unsigned>(S * bps * nbin); const size_t m1 = c.mark();
+            red_h = c.take<double>(S * nch * nbin); red_c = c.take<unsigned long long>(S * nbin);
+            part_c_bytes = m1 - m0; acc_words = (int64_t)((c.mark() - m1) / 8);
+            c0 = c.take<int>(det ? S * nch : 0); det_part = k1_part(c, det ? nslab : 0);
+            for (double*& p : det_pair) p = c.take<double>(det ? S * 2 : 0);
+            return c.at;
+        });
     }
-    int reserve(xc_ctx* ctx) { XC_TRY(ensure_scratch(ctx, total)); base = (char*)ctx->scratch; return XC_OK; }
-    double*   mmpart() const { return (double*)base; }
-    double*   part_h() const { return (double*)(base + o_ph); }
-    unsigned* part_c() const { return (unsigned*)(base + o_pc); }
-    size_t    part_c_bytes() const { return o_rh - o_pc; }
-    double*   red_h() const  { return (double*)(base + o_rh); }
-    unsigned long long* red_c() const { return (unsigned long long*)(base + o_rc); }
-    int64_t   acc_words() const { return (int64_t)((o_c0 - o_rh) / 8); }
-    int*      c0() const     { return (int*)(base + o_c0); }
-    double*   det_part() const { return (double*)(base + o_dp); }
-    double*   det_pair(int i) const { return (double*)(base + o_dm + i * pair_bytes); }     // 0 dA, 1 the tracer, 2.. the integrands
 };
 
 // the weights a kernel reads (HistArgs, SingleArgs): XC_DA_NONE becomes one 1.0 per row, finite and positive whatever the caller said
@@ -101,9 +99,9 @@ static int hist_common(xc_ctx* ctx, const Desc* d, int nch, int nbin, const Hist
     a.rdx = d->rdx; a.rdy = d->rdy; a.periodic_x = d->periodic_x;
     a.ny = d->ny; a.nx = d->nx; a.nstrip = g.nstrip; a.ncopy = g.ncopy; a.nbin = nbin;
     // nobody asked for counts: the histogram pass skips their LDS adds (a third of its atomics)
-    a.part_h = L.part_h(); a.part_c = (d->counts || d->deterministic) ? L.part_c() : nullptr;
+    a.part_h = L.part_h; a.part_c = (d->counts || d->deterministic) ? L.part_c : nullptr;
     f.part_h = a.part_h; f.part_c = a.part_c; f.bps = g.bps; f.nch = nch; f.nbin = nbin;
-    f.red_h = L.red_h(); f.red_c = L.red_c();
+    f.red_h = L.red_h; f.red_c = L.red_c;
     f.lt = d->lt; f.counts = d->counts;
     return XC_OK;
 }
@@ -128,7 +126,7 @@ static void keff_final(FinalArgs& f, const xc_keff_desc* d, int vstride, int ntb
 static int det_one_pass(xc_ctx* ctx, int q_dtype, int nint, int grad, const HistGeom& g, int64_t nslab, int64_t ny, int64_t nx,
                         HistArgs& a, const K3Scratch& L, double dA_max_host, const void* const* integ, const int* integ_dtype, FinalArgs& f)
 {
-    double* part = L.det_part();
+    double* part = L.det_part;
     auto extrema = [&](const void* p, int dtype, int64_t ns, int64_t ncell, double* out) -> int {
         // (the bounds of the accumulator windows: the largest FINITE magnitudes -- an infinite weight flags its own bin, it must not push
         // every finite one out of the window; the oracle takes its bounds the same way)
@@ -139,25 +137,25 @@ static int det_one_pass(xc_ctx* ctx, int q_dtype, int nint, int grad, const Hist
     if (dA_max_host > 0.0 && dA_max_host < __builtin_inf()) a.det_dA_max = dA_max_host;
     else if (a.dA == ctx->ones) a.det_dA_max = 1.0;
     else {
-        double* out = L.det_pair(0);
+        double* out = L.det_pair[0];
         const int64_t ns = a.dA_rank == XC_DA_SLAB ? nslab : 1, ncell = a.dA_rank == XC_DA_ROW ? ny : ny * nx;
         XC_TRY(extrema(a.dA, XC_F64, ns, ncell, out));
         a.det_dA_max_dev = out; a.det_dA_stride = a.dA_rank == XC_DA_SLAB ? 1 : 0;
     }
     a.det_q_mm = nullptr;
     if (grad && !a.levels_mode) {
-        double* out = L.det_pair(1);
+        double* out = L.det_pair[1];
         XC_TRY(extrema(a.q, q_dtype, nslab, ny * nx, out));
         a.det_q_mm = out;
     }
     for (int i = 0; i < nint; ++i) {
-        double* out = L.det_pair(2 + i);
+        double* out = L.det_pair[2 + i];
         XC_TRY(extrema(integ[i], integ_dtype[i], nslab, ny * nx, out));
         a.det_int_mm[i] = out;
     }
-    a.det_c0_out = L.c0();
+    a.det_c0_out = L.c0;
     XC_TRY(launch_hist_det3(ctx, q_dtype, nint, grad, g, nslab, a));
-    XC_TRY(launch_det3_reduce(ctx, nslab, g.bps, f.nch, f.nbin, a.part_h, a.part_c, L.c0(), f.red_h, f.red_c));
+    XC_TRY(launch_det3_reduce(ctx, nslab, g.bps, f.nch, f.nbin, a.part_h, a.part_c, L.c0, f.red_h, f.red_c));
     f.skip_reduce = 1;
     return XC_OK;
 }
@@ -177,8 +175,8 @@ static int hist_dev(xc_ctx* ctx, const xc_hist_desc* d)
     const int det = d->deterministic ? 1 : 0;
     XC_TRY(hist_geometry(ctx, d->q_dtype, d->nslab, d->ny, d->nx, nbin, nch,
                          vec_align_bits(d->q, d->q_dtype, nullptr, d->dA, d->dA_rank, d->integrand, d->integrand_dtype, d->nint), &g, 0, det));
-    K3Scratch L(d->nslab, g.bps, nch, nbin, det, false);
-    XC_TRY(L.reserve(ctx));
+    K3Scratch L;
+    XC_TRY(L.reserve(ctx, d->nslab, g.bps, nch, nbin, det, false));
     ctx->mm_valid = 0;                          // (the scratch may have moved)
     HistArgs a; memset(&a, 0, sizeof(a));
     FinalArgs f; memset(&f, 0, sizeof(f));
@@ -217,20 +215,22 @@ static int hist_host(xc_ctx* ctx, const xc_hist_desc* hd)
     for (int i = 0; i < hd->nint; ++i) ib[i] = cells * esize(hd->integrand_dtype[i]);
     const size_t rb = hd->grad ? (size_t)ny * 8 : 0;
     const size_t pb = (size_t)S * nch * nbin * 8, cb = (size_t)S * nbin * 8;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(eb) + al(dab) + al(ib[0]) + al(ib[1]) + 2 * al(rb) + 2 * al(pb) + al(cb)));
-    Stage st(ctx);
-    xc_hist_desc d = *hd;
-    XC_TRY(stage_in(ctx, st.take(qb), hd->q, qb, &d.q));
-    { const void* p; XC_TRY(stage_small(ctx, st.take(eb), hd->edges, eb, &p)); d.edges = (const double*)p; }
-    if (dab) { const void* p; XC_TRY(stage_in(ctx, st.take(dab), hd->dA, dab, &p)); d.dA = (const double*)p; }
-    for (int i = 0; i < hd->nint; ++i) XC_TRY(stage_in(ctx, st.take(ib[i]), hd->integrand[i], ib[i], &d.integrand[i]));
+    Stage st(ctx); xc_hist_desc d = *hd; void *sq, *se, *sd = nullptr, *si[XC_MAX_INTEGRANDS], *sx = nullptr, *sy = nullptr; const void* p;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        sq = s.take(qb); se = s.take(eb); if (dab) sd = s.take(dab);
+        for (int i = 0; i < hd->nint; ++i) si[i] = s.take(ib[i]);
+        if (hd->grad) { sx = s.take(rb); sy = s.take(rb); }
+        // (the finalize kernel writes the three results once and reads none of them back: small ones go straight to the pinned buffer)
+        d.pdf = s.out(hd->pdf, pb, true); d.cdf = s.out(hd->cdf, pb, true); d.counts = s.out(hd->counts, cb, true);
+    }));
+    XC_TRY(stage_in(ctx, sq, hd->q, qb, &d.q));
+    XC_TRY(stage_small(ctx, se, hd->edges, eb, &p)); d.edges = (const double*)p;
+    if (dab) { XC_TRY(stage_in(ctx, sd, hd->dA, dab, &p)); d.dA = (const double*)p; }
+    for (int i = 0; i < hd->nint; ++i) XC_TRY(stage_in(ctx, si[i], hd->integrand[i], ib[i], &d.integrand[i]));
     if (hd->grad) {
-        const void* p;
-        XC_TRY(stage_small(ctx, st.take(rb), hd->rdx, rb, &p)); d.rdx = (const double*)p;
-        XC_TRY(stage_small(ctx, st.take(rb), hd->rdy, rb, &p)); d.rdy = (const double*)p;
+        XC_TRY(stage_small(ctx, sx, hd->rdx, rb, &p)); d.rdx = (const double*)p;
+        XC_TRY(stage_small(ctx, sy, hd->rdy, rb, &p)); d.rdy = (const double*)p;
     }
-    // (the finalize kernel writes the three results once and reads none of them back: small ones go straight to the pinned buffer)
-    d.pdf = st.out(hd->pdf, pb, true); d.cdf = st.out(hd->cdf, pb, true); d.counts = st.out(hd->counts, cb, true);
     XC_TRY(flush_in(ctx));
     XC_TRY(xc_hist_dev(ctx, &d));
     XC_TRY(st.deliver());
@@ -288,8 +288,8 @@ static int keff_dev(xc_ctx* ctx, const xc_keff_desc* d)
 {
     if (!d) return fail(ctx, XC_EBADARG, "xc_keff: desc is NULL");
     if (!d->q || !d->ctr || !d->area || !d->tbl || !d->tbl_coord) return fail(ctx, XC_EBADARG, "xc_keff: q/ctr/area/tbl/tbl_coord must be given");
-    if (d->q_dtype != XC_F32 && d->q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_keff: bad q_dtype");
-    if (d->ctr_dtype != XC_F32 && d->ctr_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_keff: bad ctr_dtype");
+    if (!is_float(d->q_dtype)) return fail(ctx, XC_EBADARG, "xc_keff: bad q_dtype");
+    if (!is_float(d->ctr_dtype)) return fail(ctx, XC_EBADARG, "xc_keff: bad ctr_dtype");
     if (d->nslab < 1 || d->ny < 2 || d->nx < 1 || d->N < 2) return fail(ctx, XC_EBADARG, "xc_keff: need nslab>=1, ny>=2, nx>=1, N>=2");
     if (d->dA_rank < XC_DA_NONE || d->dA_rank > XC_DA_SLAB || (d->dA_rank != XC_DA_NONE && !d->dA)) return fail(ctx, XC_EBADARG, "xc_keff: bad dA");
     if (d->grad ? (!d->rdx || !d->rdy) : !d->grdS) return fail(ctx, XC_EBADARG, "xc_keff: need rdx/rdy (grad=1) or grdS (grad=0)");
@@ -320,9 +320,9 @@ static int keff_dev(xc_ctx* ctx, const xc_keff_desc* d)
                              vec_align_bits(d->q, d->q_dtype, d->q_next, d->dA, d->dA_rank, gi, gt, d->grad ? 0 : 1), &g,
                              fast_layout ? 1 : (supplied_f32 ? 2 : 0), det));
     }
-    K3Scratch L(d->nslab, g.bps, nch, N, det, true);
-    XC_TRY(L.reserve(ctx));
-    double* mmpart = L.mmpart();
+    K3Scratch L;
+    XC_TRY(L.reserve(ctx, d->nslab, g.bps, nch, N, det, true));
+    double* mmpart = L.mmpart;
     int mmP = minmax_blocks(d->ny * d->nx, d->nslab);
     bool accum = false;
 
@@ -335,7 +335,7 @@ static int keff_dev(xc_ctx* ctx, const xc_keff_desc* d)
         // this K1 launch, and the finalize kernel reads them directly -- three dependent launches instead of four
         accum = !det && g.bps > 64;
         XC_TRY(launch_minmax_partial(ctx, d->q, d->q_dtype, d->nslab, d->ny * d->nx, mmpart,
-                                     accum ? L.red_h() : nullptr, accum ? L.acc_words() : 0));
+                                     accum ? L.red_h : nullptr, accum ? L.acc_words : 0));
     }
     ctx->mm_valid = 0;
     double* mm_next = nullptr;
@@ -381,8 +381,8 @@ int xc_minmax_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_
 {
     XC_CTX(ctx);
     if (!q || !out_minmax || nslab < 1 || ncell < 1) return fail(ctx, XC_EBADARG, "xc_minmax: bad arguments");
-    XC_TRY(ensure_scratch(ctx, al((size_t)nslab * kMinmaxBlocks * 2 * sizeof(double))));
-    double* part = (double*)ctx->scratch;
+    double* part;
+    XC_TRY(k1_scratch(ctx, nslab, &part));
     XC_TRY(launch_minmax_partial(ctx, q, q_dtype, nslab, ncell, part));
     return launch_minmax_final(ctx, part, nslab, minmax_blocks(ncell, nslab), out_minmax);
 }
@@ -391,13 +391,11 @@ int xc_minmax(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t nc
 {
     XC_CTX(ctx);
     if (!q || !out_minmax || nslab < 1 || ncell < 1) return fail(ctx, XC_EBADARG, "xc_minmax: bad arguments");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_minmax: q_dtype must be XC_F32 or XC_F64");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_minmax: q_dtype must be XC_F32 or XC_F64");
     const size_t qb = (size_t)nslab * ncell * esize(q_dtype), ob = (size_t)nslab * 2 * sizeof(double);
-    XC_TRY(ensure_arena(ctx, al(qb) + al(ob)));
-    Stage st(ctx);
-    const void* dq;
-    XC_TRY(stage_in(ctx, st.take(qb), q, qb, &dq));
-    double* dout = st.out(out_minmax, ob);
+    Stage st(ctx); void* sq; const void* dq; double* dout;
+    XC_TRY(lay_stage(st, [&](Stage& s) { sq = s.take(qb); dout = s.out(out_minmax, ob); }));
+    XC_TRY(stage_in(ctx, sq, q, qb, &dq));
     XC_TRY(flush_in(ctx));
     XC_TRY(xc_minmax_dev(ctx, dq, q_dtype, nslab, ncell, dout));
     XC_TRY(st.deliver());
@@ -418,10 +416,8 @@ int xc_levels(xc_ctx* ctx, const double* minmax, int q_dtype, int64_t nslab, int
     XC_CTX(ctx);
     if (!minmax || !ctr || !edges || !status || N < 2 || nslab < 1) return fail(ctx, XC_EBADARG, "xc_levels: bad arguments (need N >= 2)");
     const size_t mb = (size_t)nslab * 2 * 8, cb = (size_t)nslab * N * 8, eb = (size_t)nslab * (N + 1) * 8, sb = (size_t)nslab * 4;
-    XC_TRY(ensure_arena(ctx, al(mb) + al(cb) + al(eb) + al(sb)));
-    Stage st(ctx);
-    double* dm = (double*)st.take(mb); double* dc = st.out(ctr, cb);
-    double* de = st.out(edges, eb); int32_t* ds = st.out(status, sb);
+    Stage st(ctx); double *dm, *dc, *de; int32_t* ds;
+    XC_TRY(lay_stage(st, [&](Stage& s) { dm = s.take<double>(mb); dc = s.out(ctr, cb); de = s.out(edges, eb); ds = s.out(status, sb); }));
     XC_TRY(h2d(ctx, dm, minmax, mb));
     XC_TRY(flush_in(ctx));
     XC_TRY(launch_levels(ctx, dm, q_dtype, nslab, N, increase, ctr_dtype, right_edge, dc, de, ds));
@@ -437,21 +433,21 @@ int xc_contours(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t 
 {
     XC_CTX(ctx);
     if (!q || !out_ctr || nslab < 1 || ncell < 1 || N < 2) return fail(ctx, XC_EBADARG, "xc_contours: bad arguments (need N >= 2)");
-    if (q_dtype != XC_F32 && q_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_contours: q_dtype must be XC_F32 or XC_F64");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_contours: q_dtype must be XC_F32 or XC_F64");
     const size_t qb = (size_t)nslab * ncell * esize(q_dtype);
     const size_t mb = (size_t)nslab * 2 * 8, cb = (size_t)nslab * N * 8, eb = (size_t)nslab * (N + 1) * 8, sb = (size_t)nslab * 4;
-    XC_TRY(ensure_arena(ctx, al(qb) + al(mb) + al(cb) + al(eb) + al(sb)));
-    Stage st(ctx);
-    const void* dq;
-    XC_TRY(stage_in(ctx, st.take(qb), q, qb, &dq));
-    double* dm = st.keep(out_minmax, mb);                    // (read by the level kernel: on the device whether it is wanted or not)
-    double* dc = st.out(out_ctr, cb, true); double* de = st.keep(out_edges, eb, true); int32_t* ds = st.keep(out_status, sb, true);
+    Stage st(ctx); void* sq; const void* dq; double *dm, *dc, *de, *part; int32_t* ds;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        sq = s.take(qb);
+        dm = s.keep(out_minmax, mb);                         // (read by the level kernel: on the device whether it is wanted or not)
+        dc = s.out(out_ctr, cb, true); de = s.keep(out_edges, eb, true); ds = s.keep(out_status, sb, true);
+    }));
+    XC_TRY(stage_in(ctx, sq, q, qb, &dq));
     XC_TRY(flush_in(ctx));
     // K1's partials are reduced by the level kernel itself: two launches for the whole call
-    XC_TRY(ensure_scratch(ctx, al((size_t)nslab * kMinmaxBlocks * 2 * sizeof(double))));
-    XC_TRY(launch_minmax_partial(ctx, dq, q_dtype, nslab, ncell, (double*)ctx->scratch));
-    XC_TRY(launch_levels(ctx, (const double*)ctx->scratch, q_dtype, nslab, N, increase, ctr_dtype, right_edge, dc, de, ds,
-                         minmax_blocks(ncell, nslab), dm));
+    XC_TRY(k1_scratch(ctx, nslab, &part));
+    XC_TRY(launch_minmax_partial(ctx, dq, q_dtype, nslab, ncell, part));
+    XC_TRY(launch_levels(ctx, part, q_dtype, nslab, N, increase, ctr_dtype, right_edge, dc, de, ds, minmax_blocks(ncell, nslab), dm));
     XC_TRY(st.deliver());
     return xc_sync(ctx);
 }
@@ -481,17 +477,17 @@ int xc_keff_epilogue_dev(xc_ctx* ctx, const double* pdf, const double* ctr, int 
     XC_CTX(ctx);
     if (!pdf || !ctr || !tbl || !tbl_coord) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: pdf / ctr / tbl / tbl_coord must be given");
     if (nslab < 1 || N < 2 || ntbl < 2 || npre < 0) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: need nslab >= 1, N >= 2, ntbl >= 2");
-    if (ctr_dtype != XC_F32 && ctr_dtype != XC_F64) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: bad ctr_dtype");
+    if (!is_float(ctr_dtype)) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: bad ctr_dtype");
     if (npre > 0 && interp && !preY) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: preY is NULL");
     // the reduce stage sums ONE "partial" per slab (the pdf itself); its count channel reads zeros
     const int nch = 2;
-    K3Scratch L(nslab, 1, nch, N, 0, false, false);
-    XC_TRY(L.reserve(ctx));
-    XC_HIP(ctx, hipMemsetAsync(L.part_c(), 0, L.part_c_bytes(), ctx->stream));
+    K3Scratch L;
+    XC_TRY(L.reserve(ctx, nslab, 1, nch, N, 0, false, false));
+    XC_HIP(ctx, hipMemsetAsync(L.part_c, 0, L.part_c_bytes, ctx->stream));
     ctx->mm_valid = 0;                          // the scratch may have moved
     FinalArgs f; memset(&f, 0, sizeof(f));
-    f.part_h = pdf; f.part_c = L.part_c(); f.bps = 1; f.nch = nch; f.nbin = N;
-    f.red_h = L.red_h(); f.red_c = L.red_c();
+    f.part_h = pdf; f.part_c = L.part_c; f.bps = 1; f.nch = nch; f.nbin = N;
+    f.red_h = L.red_h; f.red_c = L.red_c;
     xc_keff_desc d; memset(&d, 0, sizeof(d));       // the arguments in the form keff_final takes them
     d.lt = lt; d.increase = increase; d.ctr_dtype = ctr_dtype; d.ctr = const_cast<double*>(ctr);
     d.tbl = tbl; d.tbl_coord = tbl_coord; d.preY = preY; d.npre = npre; d.nkeff_mask = nkeff_mask; d.lmin_scale = lmin_scale;
@@ -511,18 +507,17 @@ int xc_keff_epilogue(xc_ctx* ctx, const double* pdf, const double* ctr, int ctr_
     if (!pdf || !ctr || !tbl || !tbl_coord || nslab < 1 || N < 2 || ntbl < 2 || npre < 0)
         return fail(ctx, XC_EBADARG, "xc_keff_epilogue: bad arguments");
     const size_t S = (size_t)nslab, vb = S * N * 8, pb = 2 * vb, tb = (size_t)ntbl * 8, yb = (size_t)npre * 8, ib = S * 9 * npre * 8;
-    XC_TRY(ensure_arena(ctx, al(pb) + al(vb) + 2 * al(tb) + al(yb) + 8 * al(vb) + al(ib)));
-    Stage st(ctx);
-    double* dp = (double*)st.take(pb); double* dc = (double*)st.take(vb);
-    double* dt = (double*)st.take(tb); double* dy = (double*)st.take(tb);
-    double* dpre = npre > 0 ? (double*)st.take(yb) : nullptr;
-    // (the kernel gets all eight vectors, wanted or not)
     double* host[8] = {area, intgrdS, latEq, dqdA, dintSdA, Leq2, Lmin, nkeff};
-    double* o[8]; for (int i = 0; i < 8; ++i) o[i] = st.keep(host[i], vb);
-    double* di = npre > 0 ? st.out(interp, ib) : nullptr;
+    Stage st(ctx); double *dp, *dc, *dt, *dy, *dpre, *o[8], *di;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dp = s.take<double>(pb); dc = s.take<double>(vb); dt = s.take<double>(tb); dy = s.take<double>(tb);
+        dpre = npre > 0 ? s.take<double>(yb) : nullptr;
+        for (int i = 0; i < 8; ++i) o[i] = s.keep(host[i], vb);      // (the kernel gets all eight vectors, wanted or not)
+        di = npre > 0 ? s.out(interp, ib) : nullptr;
+    }));
     XC_TRY(h2d(ctx, dp, pdf, pb)); XC_TRY(h2d(ctx, dc, ctr, vb));
     XC_TRY(h2d(ctx, dt, tbl, tb)); XC_TRY(h2d(ctx, dy, tbl_coord, tb));
-    if (dpre) { if (!preY) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: preY is NULL"); XC_TRY(h2d(ctx, dpre, preY, yb)); }
+    if (npre > 0) { if (!preY) return fail(ctx, XC_EBADARG, "xc_keff_epilogue: preY is NULL"); XC_TRY(h2d(ctx, dpre, preY, yb)); }
     XC_TRY(flush_in(ctx));
     XC_TRY(xc_keff_epilogue_dev(ctx, dp, dc, ctr_dtype, nslab, N, increase, lt, dt, dy, ntbl, dpre, npre, nkeff_mask, lmin_scale,
                                 o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], di));
