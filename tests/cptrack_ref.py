@@ -7,7 +7,9 @@ tracks_of()      the SET rule: a union-find over the accepted links whose root i
 rounds_of()      what the kernels do instead: parent[g] <= g, rounds of hook (every accepted link reads both roots from the parents as the
                  round found them and takes the minimum of the smaller root into the larger root's parent) and compress, until a round
                  changes nothing -> (root, rounds).  `broken` names a deliberate defect (test_cptrack_host.py shows that the cases of the
-                 GPU record test catch each of them).
+                 GPU record test catch each of BROKEN, test_cptrack_geometry_host.py that those of cptrack_geometry_cases.py catch each
+                 of BROKEN_GEOMETRY).
+refused()        the index check: which link arrays the call refuses.
 tracks_of_rows() the facade's view of one level of one series: K22's rows of every pair of consecutive steps -> per step the rings'
                  track / nprev / nnext, per step the rows' `linked`, and the track table.
 cases()          the hand-built graphs of tests/test_gpu_cptrack_records.py.
@@ -19,17 +21,28 @@ ROW_DTYPE = np.dtype([('first_ring', np.int64), ('first_step', np.int32), ('last
 TRACK_DTYPE = np.dtype([('first_step', np.int32), ('first_row', np.int64), ('last_step', np.int32), ('nrings', np.int64), ('nsplit', np.int64),
                         ('nmerge', np.int64)])
 BROKEN = ('no compression', 'smaller root under the larger', 'threshold > instead of >=', 'degrees counted on rejected links')
+# ... and those that only the graphs of cptrack_geometry_cases.py tell apart (test_cptrack_geometry_host.py names the case for each); kept
+# beside BROKEN, which test_cptrack_host.py walks with a table of its own.  The last one is a defect of refused(), not of tracks_of().
+BROKEN_GEOMETRY = ('first_step from the root', 'last_step from the last ring', 'nsplit counts links', 'max size in the threshold',
+                   'n >= 0 accepted', 'only a checked against nring')
 
 
 def accepted(size, la, lb, ln, min_overlap, broken=None):
     la, lb, ln = (np.asarray(v, dtype=np.int64) for v in (la, lb, ln))
-    ok = (la >= 0) & (lb >= 0) & (ln >= 1)
+    ok = (la >= 0) & (lb >= 0) & (ln >= (0 if broken == 'n >= 0 accepted' else 1))
     if min_overlap != 0:
         size = np.asarray(size, dtype=np.int64)
+        pick = max if broken == 'max size in the threshold' else min
         for i in np.flatnonzero(ok).tolist():
-            need = float(min_overlap) * float(min(int(size[la[i]]), int(size[lb[i]])))      # one float64 product
+            need = float(min_overlap) * float(pick(int(size[la[i]]), int(size[lb[i]])))     # one float64 product
             ok[i] = float(int(ln[i])) > need if broken == 'threshold > instead of >=' else float(int(ln[i])) >= need
     return ok
+
+
+def refused(nring, la, lb, broken=None):
+    """the index check: any link with a >= nring or b >= nring refuses the call, whatever its other index and its n are"""
+    la, lb = np.asarray(la, dtype=np.int64), np.asarray(lb, dtype=np.int64)
+    return bool((la >= nring).any()) if broken == 'only a checked against nring' else bool(((la >= nring) | (lb >= nring)).any())
 
 
 def degrees(nring, la, lb, ok, broken=None):
@@ -60,8 +73,9 @@ def union_find(nring, la, lb, ok):
     return np.array([find(g) for g in range(nring)], dtype=np.int64)
 
 
-def rows_of(root, step, nprev, nnext):
+def rows_of(root, step, nprev, nnext, broken=None):
     """-> (track (nring,), the rows (ROW_DTYPE)) from the roots, by their definitions"""
+    step, nnext = np.asarray(step), np.asarray(nnext)
     roots = np.unique(root)
     track = np.searchsorted(roots, root).astype(np.int64)
     rows = np.zeros(roots.size, dtype=ROW_DTYPE)
@@ -72,8 +86,16 @@ def rows_of(root, step, nprev, nnext):
     np.maximum.at(last, track, step)
     rows['first_step'], rows['last_step'] = first, last
     rows['nrings'] = np.bincount(track, minlength=roots.size)
-    rows['nsplit'] = np.bincount(track[np.asarray(nnext) >= 2], minlength=roots.size)
+    rows['nsplit'] = np.bincount(track[nnext >= 2], minlength=roots.size)
     rows['nmerge'] = np.bincount(track[np.asarray(nprev) >= 2], minlength=roots.size)
+    if broken == 'first_step from the root':
+        rows['first_step'] = step[roots]
+    if broken == 'last_step from the last ring':
+        largest = np.zeros(roots.size, dtype=np.int64)
+        np.maximum.at(largest, track, np.arange(track.size))
+        rows['last_step'] = step[largest]
+    if broken == 'nsplit counts links':
+        rows['nsplit'] = np.bincount(track[nnext >= 2], weights=nnext[nnext >= 2], minlength=roots.size).astype(np.int64)
     return track, rows
 
 
@@ -83,7 +105,7 @@ def tracks_of(nring, step, size, la, lb, ln, min_overlap=0.0, broken=None, root=
     nprev, nnext = degrees(nring, la, lb, ok, broken)
     if root is None:
         root = union_find(nring, la, lb, ok)
-    track, rows = rows_of(root, np.asarray(step), nprev, nnext)
+    track, rows = rows_of(root, np.asarray(step), nprev, nnext, broken)
     return dict(root=root, track=track, nprev=nprev, nnext=nnext, link_ok=ok, rows=rows)
 
 
