@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""K14 timing: the device join against the host join on the inputs of tools/cseg_time.py (one synthetic 1801 x 3600 float64 slab of
-xc_synth_dev, variant 0: PV-like, 1: pure noise; N levels over the field's range).  One ROUTE per process, each after one untimed call:
+"""K14 timing: the device join against the host join on one synthetic 1801 x 3600 float64 slab (record_timing.synth_plane(ny, nx,
+variant): variant 0 PV-like, 1 pure noise; only its host copy is kept) and N levels over the field's range (levels_over).  One ROUTE per process, each after one untimed call:
   --route device   Context.contour_polylines: K12, K14 (xc_contour_polylines_dev), the download of the walk-ordered records and the
-                   polyline table.  Then the stage times inside K14 from HIP events (xc_set_kernel_timing, xc_last_cjoin_profile).
+                   polyline table.  Then the stage times inside K14 from HIP events (record_timing.stage_times with warm=False: the
+                   calls before it have warmed up; xc_last_cjoin_profile).
   --route host     the parent commit's route: Context.contour_segments (K12, the records to the host, sorted per range), then
                    join_segments (xc_join_segments, one thread); the two are timed apart.
   --route facade-device   Contour2D.trace_contours(levels, index=True, join='device', packed=True)
@@ -13,14 +14,11 @@ xc_synth_dev, variant 0: PV-like, 1: pure noise; N levels over the field's range
     python tools/cjoin_time.py --route host --variant 0 --ncont 121 --reps 1
 """
 import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -33,20 +31,13 @@ def main():
     ap.add_argument('--nx', type=int, default=3600)
     ap.add_argument('--periodic', action='store_true', help='periodic X: the seam cell column is traced too')
     a = ap.parse_args()
+    nat, ctx = rt.open_context()
     import xcontour_amd as xa
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
     ny, nx, N = a.ny, a.nx, a.ncont
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    qh = q.download((ny, nx), np.float64)
-    for b in (q, dlat, dlon):
+    q, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant)
+    for b in (q, dlat, dlon):                                                 # every route starts from the host array
         b.free()
-    mm = ctx.minmax(qh.reshape(1, -1))[0]
-    lv = np.linspace(mm[0], mm[1], N)
+    lv = rt.levels_over(ctx, qh, N)
     what = 'variant %d ncont %d%s' % (a.variant, N, ' periodic' if a.periodic else '')
 
     def facade(field, y):
@@ -61,15 +52,13 @@ def main():
             t = time.perf_counter() - t0
             print('%s device route rep %d: %.4f s  (%d segments, %d polylines, %d rings; %.1f MB downloaded)'
                   % (what, rep, t, efw.size, closed.size, int(closed.sum()), (efw.nbytes + ptw.nbytes + closed.size * 12) / 1e6))
-        ctx.set_kernel_timing(True)
+        keys = ('table_ms', 'label_ms', 'rank_ms', 'place_ms', 'gather_ms')
+        acc, pr = rt.stage_times(ctx, lambda: ctx.contour_polylines(qh[None], lv, periodic=a.periodic), ctx.last_cjoin_profile, keys, a.reps,
+                                 sync_each=False, warm=False)
         for rep in range(a.reps):
-            ctx.contour_polylines(qh[None], lv, periodic=a.periodic)
-            pr = ctx.last_cjoin_profile()
+            ms = [acc[k][rep] for k in keys]
             print('  K14 stages rep %d (ms): table %.3f, label rounds %.3f, roots + rank rounds %.3f, placement %.3f, gather %.3f; '
-                  'sum %.3f; %d rounds over %d groups'
-                  % (rep, pr['table_ms'], pr['label_ms'], pr['rank_ms'], pr['place_ms'], pr['gather_ms'],
-                     sum(pr[k] for k in ('table_ms', 'label_ms', 'rank_ms', 'place_ms', 'gather_ms')), pr['rounds'], pr['groups']))
-        ctx.set_kernel_timing(False)
+                  'sum %.3f; %d rounds over %d groups' % ((rep,) + tuple(ms) + (sum(ms), pr['rounds'], pr['groups'])))
     elif a.route == 'host':
         def route():
             t0 = time.perf_counter()

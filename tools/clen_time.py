@@ -1,19 +1,16 @@
 #!/usr/bin/env python3
-"""K10 timing: xc_contour_lengths_dev on synthetic 3600 x 1801 float64 slabs made on the device (xc_synth_dev variant 0:
-PV-like, 1: pure noise), N levels from the field's range, lat / lon in radians.  Prints the event time per call; run it under
+"""K10 timing: xc_contour_lengths_dev on synthetic 3600 x 1801 float64 slabs made on the device (record_timing.synth_plane(ny, nx,
+variant, nslab=slabs): variant 0 PV-like, 1 pure noise), N levels from the range of slab 0 (levels_over), lat / lon in radians.  Prints the event time per call; run it under
 `rocprofv3 --kernel-trace --stats -- python tools/clen_time.py ...` for the per-kernel times.
 
     python tools/clen_time.py --slabs 64 --variant 0 --ncont 121 --reps 5
     python tools/clen_time.py --slabs 64 --periodic        # the longitude ring closed (xc_contour_lengths_periodic_dev)
 """
 import argparse
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -26,16 +23,10 @@ def main():
     ap.add_argument('--nx', type=int, default=3600)
     ap.add_argument('--periodic', action='store_true', help='periodic X: the period is 360 degrees (float32 radians)')
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.Context(0)
+    nat, ctx = rt.open_context()
     S, ny, nx = a.slabs, a.ny, a.nx
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(S * ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    mm = ctx.minmax(q.download((1, ny * nx), np.float64))[0]
-    lv = np.linspace(mm[0], mm[1], a.ncont)
+    q, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant, nslab=S)
+    lv = rt.levels_over(ctx, qh, a.ncont)
     y = np.deg2rad(lat.astype(np.float32)).astype(np.float64)
     x = np.deg2rad(lon.astype(np.float32)).astype(np.float64)
     dy, dx, dc = ctx.to_device(y), ctx.to_device(x), ctx.to_device(lv)
@@ -63,7 +54,6 @@ def main():
     cells = S * (ny - 1) * (nx if a.periodic else nx - 1)
     print('slabs %d variant %d ncont %d%s: %.1f us per call, %.2f us per slab, %.2f segments per cell, %.0f GB/s of tracer'
           % (S, a.variant, a.ncont, ' periodic' if a.periodic else '', ms * 1e3, ms * 1e3 / S, float(n.sum()) / cells, S * ny * nx * 8 / (ms * 1e-3) / 1e9))
-    ctx.close()
 
 
 if __name__ == '__main__':

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""K15 and K10 timing on the slabs of tools/clen_time.py: synthetic 3600 x 1801 float64 slabs made on the device (xc_synth_dev
-variant 0: PV-like, 1: pure noise), N levels from the field's range, lat / lon in radians; the integrand of K15 is a second
-synthetic slab (another seed).  Device events around `--reps` calls, `--rounds` times, K10 and K15 alternating; prints the
+"""K15 and K10 timing: synthetic 3600 x 1801 float64 slabs made on the device (record_timing.synth_fill into one buffer, every variant
+of --variants in turn: 0 PV-like, 1 pure noise), N levels from the range of slab 0 (levels_over), lat / lon in radians; the integrand
+of K15 is a second synthetic slab (synth_fill with variant 0, seed=7).  Device events around `--reps` calls, `--rounds` times, K10 and K15 alternating; prints the
 median and the range of the per-call times of each, one JSON line per variant.
 
     python tools/cline_time.py --variants 0 1 --ncont 121 --rounds 9
@@ -10,12 +10,10 @@ median and the range of the per-call times of each, one JSON line per variant.
 import argparse
 import json
 import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -29,22 +27,18 @@ def main():
     ap.add_argument('--nx', type=int, default=3600)
     ap.add_argument('--k10-only', action='store_true')
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.Context(0)
+    nat, ctx = rt.open_context()
     S, ny, nx, N = a.slabs, a.ny, a.nx, a.ncont
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
+    lat, lon, dlat, dlon = rt.lat_lon(ctx, ny, nx)
     y = np.deg2rad(lat.astype(np.float32)).astype(np.float64)
     x = np.deg2rad(lon.astype(np.float32)).astype(np.float64)
     dy, dx = ctx.to_device(y), ctx.to_device(x)
     q, f = ctx.alloc(S * ny * nx * 8), ctx.alloc(S * ny * nx * 8)
     out = [ctx.alloc(S * N * 8) for _ in range(3)]
     for variant in a.variants:
-        ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dlat.ptr, dlon.ptr, 1, variant))
-        ctx._check(ctx.lib.xc_synth_dev(ctx.handle, f.ptr, nat.XC_F64, S, ny, nx, dlat.ptr, dlon.ptr, 7, 0))
-        mm = ctx.minmax(q.download((1, ny * nx), np.float64))[0]
-        dc = ctx.to_device(np.linspace(mm[0], mm[1], N))
+        rt.synth_fill(ctx, nat, q, S, ny, nx, dlat, dlon, variant)
+        rt.synth_fill(ctx, nat, f, S, ny, nx, dlat, dlon, 0, seed=7)
+        dc = ctx.to_device(rt.levels_over(ctx, q.download((ny, nx), np.float64), N))
 
         def k10():
             ctx._check(ctx.lib.xc_contour_lengths_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dy.ptr, dx.ptr, 6371200.0,
@@ -75,8 +69,7 @@ def main():
         if 'K15' in times:
             rec['K15_over_K10'] = round(float(np.median(times['K15']) / np.median(times['K10'])), 2)
         print(json.dumps(rec), flush=True)
-        dc.free()
-    ctx.close()
+        dc.free()                                            # the next variant's levels take its place
 
 
 if __name__ == '__main__':

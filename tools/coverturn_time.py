@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""K16 timing: xc_contour_overturning_dev on the inputs of tools/cpiece_time.py (one synthetic 1801 x 3600 float64 slab of
-xc_synth_dev, variant 0: PV-like, 1: pure noise; N levels over the field's range; periodic X).  In ONE run, on the same records:
+"""K16 timing: xc_contour_overturning_dev on one synthetic 1801 x 3600 float64 slab (record_timing.synth_plane(ny, nx, variant):
+variant 0 PV-like, 1 pure noise), N levels over the field's range (levels_over) and K12's periodic records of them (SegmentRecords).  In
+ONE run, on the same records:
   K12      xc_contour_segments_periodic_dev into exactly sized device buffers (count + emit), wall clock;
   K16      xc_contour_overturning_dev (select 'main', or --select), wall clock, and inside it from HIP events (xc_set_kernel_timing):
            table     clearing the edge tables, scatter, link, and handing the tables on clean
@@ -11,20 +12,17 @@ xc_synth_dev, variant 0: PV-like, 1: pure noise; N levels over the field's range
   facade   Context.contour_overturning and Context.contour_pieces from a host array (upload, K12 twice, the call, download);
 with --user (variant 0 is what it is meant for) the route a user had before K16: trace_contours(join='device', packed=True,
 index=True) and a numpy count over its vertices (np.add.at on the vertices that lie on a grid line along Y).
-Every wall time is the minimum / median / maximum over --reps calls after one warm-up call.
+Every wall time is the minimum / median / maximum over --reps calls after one warm-up call, each synchronised (wall_times); the stage
+times come from stage_times with sync_each=False.
 
     python tools/coverturn_time.py --variant 0 --ncont 121 --reps 5 --user
     python tools/coverturn_time.py --variant 1 --ncont 121 --reps 5
 """
 import argparse
-import os
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -37,85 +35,57 @@ def main():
     ap.add_argument('--select', default='main', choices=['all', 'circumpolar', 'main'])
     ap.add_argument('--user', action='store_true', help='also time trace_contours(join=\'device\', packed=True) + a numpy count')
     a = ap.parse_args()
+    nat, ctx = rt.open_context()
     import xcontour_amd as xa
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
     ny, nx, N = a.ny, a.nx, a.ncont
     sel = nat.Context.OVERTURN_SELECT[a.select]
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    qh = q.download((ny, nx), np.float64)
-    mm = ctx.minmax(qh.reshape(1, -1))[0]
-    lv = np.linspace(mm[0], mm[1], N)
-    dc, dn, dpc = ctx.to_device(lv), ctx.alloc(N * 8), ctx.alloc(N * 8)
-    head = (ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, N, 0)
-    f = ctx.lib.xc_contour_segments_periodic_dev
+    q, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant)
+    lv = rt.levels_over(ctx, qh, N)
+    dc = ctx.to_device(lv)
 
     def timed(fn):
-        """-> 'min / median / max us' over the repeats, each one synchronised"""
-        fn()
-        ctx.sync()
-        ts = []
-        for _ in range(a.reps):
-            t0 = time.perf_counter()
-            fn()
-            ctx.sync()
-            ts.append((time.perf_counter() - t0) * 1e6)
-        return '%10.1f / %10.1f / %10.1f us' % (min(ts), float(np.median(ts)), max(ts))
+        return rt.min_med_max(rt.wall_times(ctx, fn, a.reps), 1e6)
 
     def phases(call, profile, names):
-        ctx.set_kernel_timing(True)
-        call()
-        acc = {k: [] for k in names}
-        for _ in range(a.reps):
-            call()
-            pr = profile()
-            for k in names:
-                acc[k].append(pr[k] * 1e3)
-        ctx.set_kernel_timing(False)
-        return {k: (min(v), float(np.median(v)), max(v)) for k, v in acc.items()}, pr
+        return rt.stage_times(ctx, call, profile, names, a.reps, sync_each=False)
 
-    rc = f(*head, 0, dn.ptr, None, None, None)
-    if rc not in (0, 1):
-        ctx._check(rc)
-    total = int(dn.download((N,), np.uint64).sum())
+    def median_us(v):
+        return float(np.median([t * 1e3 for t in v]))
+
+    seg = rt.SegmentRecords(ctx, nat, q, ny, nx, dc, N, True)
+    seg.count()
+    seg.size()
+    total = seg.total
     print('variant %d ncont %d periodic, select %s: %d segments (%.1f MB of records, kept on the device); min / median / max of %d calls'
           % (a.variant, N, a.select, total, total * 48 / 1e6, a.reps))
-    df, dt, dp = ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 32)
-    print('K12 count+emit    %s' % timed(lambda: ctx._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr))))
+    print('K12 count+emit    %s' % timed(seg.emit))
 
     # K16
     outs = [ctx.alloc(N * nx * b) for b in (4, 8, 8)] + [ctx.alloc(N * b) for b in (4, 8, 8, 4)]
-    k16 = lambda: ctx._check(ctx.lib.xc_contour_overturning_dev(ctx.handle, N, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, 1, sel,
-                                                                *[b.ptr for b in outs]))
+    k16 = lambda: ctx._check(ctx.lib.xc_contour_overturning_dev(ctx.handle, *seg.recs, sel, *[b.ptr for b in outs]))
     print('K16 overturning   %s' % timed(k16))
     ph, pr = phases(k16, ctx.last_coverturn_profile, ('table_ms', 'rounds_ms', 'select_ms', 'count_ms'))
     for k, what in (('table_ms', 'clear, scatter, link, hand on clean'), ('rounds_ms', '%d doubling rounds over %d groups' % (pr['rounds'], pr['groups'])),
                     ('select_ms', 'roots, per-piece sums, pick'), ('count_ms', 'init, count, finish')):
-        print('  %-8s        %10.1f / %10.1f / %10.1f us  (%s)' % ((k[:-3],) + ph[k] + (what,)))
-    print('  device sum      %10.1f us (medians)' % sum(v[1] for v in ph.values()))
+        print('  %-8s        %s  (%s)' % (k[:-3], rt.min_med_max(ph[k], 1e3), what))
+    print('  device sum      %10.1f us (medians)' % sum(median_us(v) for v in ph.values()))
     ncross = outs[0].download((N, nx), np.int32)
     mfe = outs[4].download((N,), np.int64)
     print('  %d levels have a main ring; %d (level, column) pairs are overturned (ncross >= 3), %d crossings in all'
           % (int((mfe >= 0).sum()), int((ncross >= 3).sum()), int(ncross.sum())))
 
     # K13 on the same records
-    args = (ctx.handle, N, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, 1, dlat.ptr, dlon.ptr, 360.0, 0.0)
-    rc = ctx.lib.xc_contour_pieces_dev(*args, 0, dpc.ptr, *([None] * 8))
-    if rc not in (0, 1):
-        ctx._check(rc)
-    npiece = int(dpc.download((N,), np.uint64).sum())
+    args = (ctx.handle,) + seg.recs + (dlat.ptr, dlon.ptr, 360.0, 0.0)
+    dpc = ctx.alloc(N * 8)
+    npiece = rt.count_then(ctx, lambda: ctx.lib.xc_contour_pieces_dev(*args, 0, dpc.ptr, *([None] * 8)), dpc, N)
     rec = [ctx.alloc(max(npiece, 1) * 8) for _ in range(8)]
     k13 = lambda: ctx._check(ctx.lib.xc_contour_pieces_dev(*args, npiece, dpc.ptr, *[b.ptr for b in rec]))
     print('K13 pieces        %s  (%d pieces)' % (timed(k13), npiece))
     ph, pr = phases(k13, ctx.last_cpiece_profile, ('table_ms', 'rounds_ms', 'roots_ms', 'reduce_ms'))
     for k in ph:
-        print('  %-8s        %10.1f / %10.1f / %10.1f us' % ((k[:-3],) + ph[k]))
-    print('  device sum      %10.1f us (medians)' % sum(v[1] for v in ph.values()))
-    for b in [df, dt, dp, dc, dn, dpc, q, dlat, dlon] + rec + outs:
+        print('  %-8s        %s' % (k[:-3], rt.min_med_max(ph[k], 1e3)))
+    print('  device sum      %10.1f us (medians)' % sum(median_us(v) for v in ph.values()))
+    for b in [seg.df, seg.dt, seg.dp, dc, seg.dn, dpc, q, dlat, dlon] + rec + outs:   # the host-array forms run with this memory released
         b.free()
 
     # the host-array forms

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""K13 timing: xc_contour_pieces_dev on the inputs of tools/cseg_time.py (one synthetic 1801 x 3600 float64 slab of xc_synth_dev,
-variant 0: PV-like, 1: pure noise; N levels over the field's range).  Reports, per call,
+"""K13 timing: xc_contour_pieces_dev on one synthetic 1801 x 3600 float64 slab (record_timing.synth_plane(ny, nx, variant): variant 0
+PV-like, 1 pure noise), N levels over the field's range (levels_over) and K12's records of them (SegmentRecords, periodic or not).  Reports, per call,
   K12      xc_contour_segments_dev into exactly sized device buffers (count + emit), wall clock around the synchronising call;
   K13      xc_contour_pieces_dev on those buffers, wall clock, and inside it from HIP events (xc_set_kernel_timing):
            table     clearing the edge tables, scatter, link, and handing the tables on clean
@@ -16,14 +16,11 @@ extents per polyline).  --periodic: the periodic forms.
     python tools/cpiece_time.py --variant 1 --ncont 121 --reps 3
 """
 import argparse
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def host_route(ctx, nat, qh, lv, lat, lon, periodic):
@@ -60,57 +57,27 @@ def main():
     ap.add_argument('--periodic', action='store_true', help='periodic X: the seam cell column is traced too')
     ap.add_argument('--host', action='store_true', help='also time the route through the host join')
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
+    nat, ctx = rt.open_context()
     ny, nx, N = a.ny, a.nx, a.ncont
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    qh = q.download((ny, nx), np.float64)
-    mm = ctx.minmax(qh.reshape(1, -1))[0]
-    lv = np.linspace(mm[0], mm[1], N)
-    dc, dn, dpc = ctx.to_device(lv), ctx.alloc(N * 8), ctx.alloc(N * 8)
-    head = (ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, N, 0)
-    f = ctx.lib.xc_contour_segments_periodic_dev if a.periodic else ctx.lib.xc_contour_segments_dev
-
-    def timed(fn):
-        fn()
-        ctx.sync()
-        t0 = time.perf_counter()
-        for _ in range(a.reps):
-            fn()
-        ctx.sync()
-        return (time.perf_counter() - t0) / a.reps
-
-    rc = f(*head, 0, dn.ptr, None, None, None)
-    if rc not in (0, 1):
-        ctx._check(rc)
-    total = int(dn.download((N,), np.uint64).sum())
+    q, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant)
+    lv = rt.levels_over(ctx, qh, N)
+    seg = rt.SegmentRecords(ctx, nat, q, ny, nx, ctx.to_device(lv), N, a.periodic)
+    seg.count()
+    seg.size()
+    total = seg.total
     print('variant %d ncont %d%s: %d segments (%.1f MB of records, kept on the device)'
           % (a.variant, N, ' periodic' if a.periodic else '', total, total * 48 / 1e6))
-    df, dt, dp = ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 32)
-    t12 = timed(lambda: ctx._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr)))
+    t12 = rt.wall_mean(ctx, seg.emit, a.reps)
     print('K12 count+emit   %10.1f us per call' % (t12 * 1e6))
     # K13: a count-only call sizes the record arrays
-    args = (ctx.handle, N, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, 1 if a.periodic else 0, dlat.ptr, dlon.ptr, 360.0, 0.0)
-    rc = ctx.lib.xc_contour_pieces_dev(*args, 0, dpc.ptr, *([None] * 8))
-    if rc not in (0, 1):
-        ctx._check(rc)
-    npiece = int(dpc.download((N,), np.uint64).sum())
+    args = (ctx.handle,) + seg.recs + (dlat.ptr, dlon.ptr, 360.0, 0.0)
+    dpc = ctx.alloc(N * 8)
+    npiece = rt.count_then(ctx, lambda: ctx.lib.xc_contour_pieces_dev(*args, 0, dpc.ptr, *([None] * 8)), dpc, N)
     rec = [ctx.alloc(max(npiece, 1) * 8) for _ in range(8)]
     call = lambda: ctx._check(ctx.lib.xc_contour_pieces_dev(*args, npiece, dpc.ptr, *[b.ptr for b in rec]))
-    t13 = timed(call)
-    ctx.set_kernel_timing(True)
-    call()
-    acc = dict(table_ms=0.0, rounds_ms=0.0, roots_ms=0.0, reduce_ms=0.0)
-    for _ in range(a.reps):
-        call()
-        pr = ctx.last_cpiece_profile()
-        for k in acc:
-            acc[k] += pr[k] / a.reps
-    ctx.set_kernel_timing(False)
+    t13 = rt.wall_mean(ctx, call, a.reps)
+    acc, pr = rt.stage_times(ctx, call, ctx.last_cpiece_profile, ('table_ms', 'rounds_ms', 'roots_ms', 'reduce_ms'), a.reps, sync_each=False)
+    acc = {k: rt.mean_of(v) for k, v in acc.items()}
     closed = rec[2].download((npiece,), np.int32)
     print('K13 pieces       %10.1f us per call  (%d pieces, %d of them rings; %d groups of ranges)'
           % (t13 * 1e6, npiece, int(closed.sum()), pr['groups']))
@@ -131,8 +98,6 @@ def main():
         assert npoly == npiece
     else:
         print('host route: not measured')
-    for b in [df, dt, dp, dc, dn, dpc, q, dlat, dlon] + rec:
-        b.free()
 
 
 if __name__ == '__main__':

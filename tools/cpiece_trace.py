@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The launch sequence of K13, K14, K16, K17 and K24 (the sibling of cprecords_trace.py, which does K18-K21): one call of
 xc_contour_pieces_dev, xc_contour_polylines_dev, xc_contour_overturning_dev, xc_contour_interior_dev and xc_contour_folds_dev each, twice
-(the first call warms up), on a 24 x 65 plane in three ranges of which the middle one has no segments, periodic X ('main' selected) and
+(the first call warms up), on a 24 x 65 plane in three ranges of which the middle one has no segments (K12 traces two levels,
+record_timing.segment_records; the empty range is put between them), periodic X ('main' selected) and
 then plain ('all'), under a cap of ONE table row: two groups a call.  Then K22 (xc_label_overlap_dev on two block maps of the same three
 ranges, the middle one without a ring: two groups under the same cap) and K23 (xc_ring_tracks_dev on 600 rings and 800 links), twice
 each.  Meant to run under a kernel trace of its own (no counters):
@@ -10,18 +11,13 @@ each.  Meant to run under a kernel trace of its own (no counters):
 
 The ordered (kernel, grid, block) lists of two builds of the library (XC_LIB_PATH names another one) are then compared line by line.
 Prints the groups and rounds every call reports."""
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
+    nat, ctx = rt.open_context()
     ny, nx, N = 24, 65, 3
     rng = np.random.default_rng(1)
     y, x = np.mgrid[0:ny, 0:nx]
@@ -30,21 +26,14 @@ def main():
     dq, dc = ctx.to_device(q), ctx.to_device(lv)
     dw, df32 = ctx.to_device(rng.uniform(0.5, 1.5, (ny, nx))), ctx.to_device(rng.standard_normal((ny, nx)).astype(np.float32))
     dy, dx = ctx.to_device(np.arange(ny, dtype=np.float64)), ctx.to_device(np.arange(nx, dtype=np.float64))
-    dn2, dpc = ctx.alloc(2 * 8), ctx.alloc(N * 8)
+    dpc = ctx.alloc(N * 8)
     ctx.set_cpiece_workspace(2 * ny * nx * 4)                                     # one row of the edge tables
     for periodic in (1, 0):
-        seg = ctx.lib.xc_contour_segments_periodic_dev if periodic else ctx.lib.xc_contour_segments_dev
-        head = (ctx.handle, dq.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, 2, 0)
-        rc = seg(*head, 0, dn2.ptr, None, None, None)
-        if rc not in (0, 1):
-            ctx._check(rc)
-        cnt = dn2.download((2,), np.uint64)
-        total = int(cnt.sum())
-        de, dt, dp = ctx.alloc(total * 8), ctx.alloc(total * 8), ctx.alloc(total * 32)
-        ctx._check(seg(*head, total, dn2.ptr, de.ptr, dt.ptr, dp.ptr))
-        cnt = np.array([cnt[0], 0, cnt[1]], dtype=np.uint64)                     # the records stay as they are: range 1 holds none
+        seg = rt.segment_records(ctx, nat, dq, ny, nx, dc, 2, periodic)
+        total = seg.total
+        cnt = np.array([seg.counts[0, 0], 0, seg.counts[0, 1]], dtype=np.uint64)  # the records stay as they are: range 1 holds none
         dn = ctx.to_device(cnt)
-        recs = (ctx.handle, N, dn.ptr, de.ptr, dt.ptr, dp.ptr, ny, nx)
+        recs = (ctx.handle, N, dn.ptr, seg.df.ptr, seg.dt.ptr, seg.dp.ptr, ny, nx)
         out = [ctx.alloc(max(total * 32, N * ny * nx * 8)) for _ in range(15)]
         ptrs = [b.ptr for b in out]
         select = 2 if periodic else 0
@@ -61,7 +50,7 @@ def main():
                 ctx._check(call())
             p = getattr(ctx, 'last_%s_profile' % prof)()
             print('periodic %d %-11s segments %s groups %d rounds %d' % (periodic, name, cnt.tolist(), p['groups'], p['rounds']))
-        for b in [dn, de, dt, dp] + out:
+        for b in [dn, seg.dn, seg.df, seg.dt, seg.dp] + out:                      # the plain pass starts from the memory the periodic one had
             b.free()
     # K22: blocks of 6 x 17 nodes against the same blocks shifted by (3, 5); range 1 holds no ring
     la = np.broadcast_to((y // 6) * 4 + x // 17, (N, ny, nx)).astype(np.int32)

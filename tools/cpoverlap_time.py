@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""K22 timing: xc_label_overlap_dev on the two maps of two K20 calls, beside K19, K20 and K21 on the same device records in one process
--- the inputs of tools/cpprops_time.py (one synthetic 1801 x 3600 float64 slab of xc_synth_dev, variant 0: PV-like, 1: pure noise; N
-levels over the field's range; periodic X; weight cos(latitude) per node, the integrand the field itself).  Field B is field A rolled by
---roll columns.  Every line is the mean of --reps calls after a warm-up: HIP events (xc_set_kernel_timing) for the stages of each entry's
+"""K22 timing: xc_label_overlap_dev on the two maps of two K20 calls, beside K19, K20 and K21 on the same device records in one process:
+field A is one synthetic 1801 x 3600 float64 slab (record_timing.synth_plane(ny, nx, variant): variant 0 PV-like, 1 pure noise), field B
+is field A rolled by --roll columns; N levels over A's range (levels_over), K12's periodic records of each field (segment_records), the
+weight cos_weights(lat, ny, nx), the integrand field A.  Every line is record_timing.report_means: the mean of --reps calls after a warm-up: HIP events (xc_set_kernel_timing) for the stages of each entry's
 own profile, and the wall clock around the synchronising call.  Then the accumulate pass against the bytes it must read, the pairs
 against the runs (on four levels, counted on the host from the downloaded maps: the load of the tables), and, for comparison only, the
 host route K22 replaces on ONE level: downloading both maps, np.unique over the pairs and np.bincount for the three columns -- whose
@@ -12,14 +12,12 @@ rows are checked against K22's (n equal, the sums to 1e-9 of the sum of |terms|)
     python tools/cpoverlap_time.py --variant 1 --ncont 121 --reps 3
 """
 import argparse
-import os
-import sys
+import functools
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -31,62 +29,25 @@ def main():
     ap.add_argument('--nx', type=int, default=3600)
     ap.add_argument('--roll', type=int, default=5)
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
+    nat, ctx = rt.open_context()
     ny, nx, N = a.ny, a.nx, a.ncont
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    qa = ctx.alloc(ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, qa.ptr, nat.XC_F64, 1, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    qh = qa.download((ny, nx), np.float64)
+    qa, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant)
     qb = ctx.to_device(np.ascontiguousarray(np.roll(qh, a.roll, axis=1)))
-    mm = ctx.minmax(qh.reshape(1, -1))[0]
-    lv = np.linspace(mm[0], mm[1], N)
-    wh = np.ascontiguousarray(np.broadcast_to(np.cos(np.deg2rad(lat))[:, None], (ny, nx)))
+    lv = rt.levels_over(ctx, qh, N)
+    wh = rt.cos_weights(lat, ny, nx)
     dw, dc = ctx.to_device(wh), ctx.to_device(lv)
-    seg = ctx.lib.xc_contour_segments_periodic_dev
     fields = []
     for name, q in (('A', qa), ('B', qb)):
-        dn, dpc = ctx.alloc(N * 8), ctx.alloc(N * 8)
-        head = (ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, N, 0)
-        rc = seg(*head, 0, dn.ptr, None, None, None)
-        if rc not in (0, 1):
-            ctx._check(rc)
-        total = int(dn.download((N,), np.uint64).sum())
-        df, dt, dp = ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 32)
-        ctx._check(seg(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr))
-        recs = (ctx.handle, N, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, 1, 0, N, dw.ptr, 0, qa.ptr, nat.XC_F64)
-        rc = ctx.lib.xc_contour_piece_tree_dev(*recs, 0, dpc.ptr, *([None] * 13))
-        if rc not in (0, 1):
-            ctx._check(rc)
-        npiece = int(dpc.download((N,), np.uint64).sum())
+        seg = rt.segment_records(ctx, nat, q, ny, nx, dc, N, True)
+        recs = (ctx.handle,) + seg.recs + (0, N, dw.ptr, 0, qa.ptr, nat.XC_F64)
+        dpc = ctx.alloc(N * 8)
+        npiece = rt.count_then(ctx, lambda: ctx.lib.xc_contour_piece_tree_dev(*recs, 0, dpc.ptr, *([None] * 13)), dpc, N)
         rec = [ctx.alloc(max(npiece, 1) * 8) for _ in range(13)]
         dlab = ctx.alloc(N * ny * nx * 4)
-        print('variant %d ncont %d periodic, field %s: %d segments, %d pieces' % (a.variant, N, name, total, npiece))
-        fields.append(dict(recs=recs, npiece=npiece, dpc=dpc, ptrs=[b.ptr for b in rec], dlab=dlab, keep=[dn, df, dt, dp, dpc] + rec))
+        print('variant %d ncont %d periodic, field %s: %d segments, %d pieces' % (a.variant, N, name, seg.total, npiece))
+        fields.append(dict(recs=recs, npiece=npiece, dpc=dpc, ptrs=[b.ptr for b in rec], dlab=dlab))
 
-    def report(name, call, profile, keys):
-        call()
-        ctx.sync()
-        t0 = time.perf_counter()
-        for _ in range(a.reps):
-            call()
-        ctx.sync()
-        wall = (time.perf_counter() - t0) / a.reps
-        ctx.set_kernel_timing(True)
-        call()
-        acc = dict.fromkeys(keys, 0.0)
-        for _ in range(a.reps):
-            call()
-            pr = profile()
-            for k in keys:
-                acc[k] += pr[k] / a.reps
-        ctx.set_kernel_timing(False)
-        print('%-22s wall %9.3f ms | %s | sum %8.3f | %d rounds, %d groups'
-              % (name, wall * 1e3, ', '.join('%s %8.3f' % (k, acc[k]) for k in keys), sum(acc.values()), pr['rounds'], pr['groups']))
-        return wall, acc
-
+    report = functools.partial(rt.report_means, ctx, reps=a.reps)
     keys = ('table_ms', 'rounds_ms', 'roots_ms', 'walk_ms', 'tree_ms')
     fa, fb = fields
     report('K19 piece tree A', lambda: ctx._check(ctx.lib.xc_contour_piece_tree_dev(*fa['recs'], fa['npiece'], fa['dpc'].ptr, *fa['ptrs'])),
@@ -112,10 +73,7 @@ def main():
     # K22 on the two maps
     dpair = ctx.alloc(N * 8)
     head = (ctx.handle, N, ny, nx, N, fa['dlab'].ptr, fb['dlab'].ptr, dw.ptr, 0, qa.ptr, nat.XC_F64)
-    rc = ctx.lib.xc_label_overlap_dev(*head, 0, dpair.ptr, None, None, None, None, None)
-    if rc not in (0, 1):
-        ctx._check(rc)
-    pairs = dpair.download((N,), np.uint64).astype(np.int64)
+    pairs = rt.counts_then(ctx, lambda: ctx.lib.xc_label_overlap_dev(*head, 0, dpair.ptr, None, None, None, None, None), dpair, N).astype(np.int64)
     npair = int(pairs.sum())
     rows = [ctx.alloc(max(npair, 1) * b) for b in (4, 4, 8, 8, 8)]
     okeys = ('runs_ms', 'accumulate_ms', 'finish_ms')
@@ -162,8 +120,6 @@ def main():
         bad = (uq.size != g[0].size) or int((g[2][o] != n).sum()) + int((np.abs(g[3][o] - sw) > 1e-9 * sw).sum()) \
             + int((np.abs(g[4][o] - swf) > 1e-9 * sa).sum())
         print('             rows that differ from the host route: %d' % int(bad))
-    for b in [qa, qb, dlat, dlon, dw, dc, dpair] + rows + dg + out + fa['keep'] + fb['keep'] + [fa['dlab'], fb['dlab']]:
-        b.free()
 
 
 if __name__ == '__main__':

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """K21 timing: xc_contour_piece_props_dev beside K19 (xc_contour_piece_tree_dev) and K20 (xc_contour_piece_labels_dev) on the same device
-records in one process -- the inputs of tools/cplabel_time.py (one synthetic 1801 x 3600 float64 slab of xc_synth_dev, variant 0:
-PV-like, 1: pure noise; N levels over the field's range; periodic X; weight cos(latitude) per node, the integrand the field itself).  K21 runs at nf = 3
-(the three lat-lon moment planes, shared float64 planes) with the tracer as x, and at nf = 8 (those and five per-slab float64 stacks)
-with the tracer as x.  Every line is the mean of --reps calls after a warm-up: HIP events (xc_set_kernel_timing) for the stages of each
-entry's own profile, and the wall clock around the synchronising call.  Then the props scan (scan_ms) against the bytes it must read,
+records in one process: one synthetic 1801 x 3600 float64 slab (record_timing.synth_plane(ny, nx, variant): variant 0 PV-like, 1 pure
+noise), N levels over the field's range (levels_over), K12's periodic records of them (segment_records), the weight
+cos_weights(lat, ny, nx), the integrand the field itself.  K21 runs at nf = 3 (the three lat-lon moment planes, shared float64 planes)
+with the tracer as x, and at nf = 8 (those and five per-slab float64 stacks) with the tracer as x.  Every line is
+record_timing.report_means: the mean of --reps calls after a warm-up: HIP events (xc_set_kernel_timing) for the stages of each entry's
+own profile, and the wall clock around the synchronising call.  Then the props scan (scan_ms) against the bytes it must read,
 and the checks against K20's map that need no reference: per ring the minimum and maximum of x over its label and the smallest flat node
 of the minimum (exact), and the first field's net sum against np.bincount(label, weights) (to 1e-9 of the sum of |terms|).
 
@@ -12,14 +13,11 @@ of the minimum (exact), and the first field's net sum against np.bincount(label,
     python tools/cpprops_time.py --variant 1 --ncont 121 --reps 3
 """
 import argparse
-import os
-import sys
-import time
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -30,54 +28,18 @@ def main():
     ap.add_argument('--ny', type=int, default=1801)
     ap.add_argument('--nx', type=int, default=3600)
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
+    nat, ctx = rt.open_context()
     ny, nx, N = a.ny, a.nx, a.ncont
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    mm = ctx.minmax(q.download((ny, nx), np.float64).reshape(1, -1))[0]
-    lv = np.linspace(mm[0], mm[1], N)
-    dw = ctx.to_device(np.ascontiguousarray(np.broadcast_to(np.cos(np.deg2rad(lat))[:, None], (ny, nx))))
-    dc, dn, dpc = ctx.to_device(lv), ctx.alloc(N * 8), ctx.alloc(N * 8)
-    head = (ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, N, 0)
-    f = ctx.lib.xc_contour_segments_periodic_dev
-    rc = f(*head, 0, dn.ptr, None, None, None)
-    if rc not in (0, 1):
-        ctx._check(rc)
-    total = int(dn.download((N,), np.uint64).sum())
-    print('variant %d ncont %d periodic: %d segments' % (a.variant, N, total))
-    df, dt, dp = ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 32)
-    ctx._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr))
-    recs = (ctx.handle, N, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, 1, 0, N, dw.ptr, 0, q.ptr, nat.XC_F64)
+    q, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant)
+    lv = rt.levels_over(ctx, qh, N)
+    dw = ctx.to_device(rt.cos_weights(lat, ny, nx))
+    seg = rt.segment_records(ctx, nat, q, ny, nx, ctx.to_device(lv), N, True)
+    print('variant %d ncont %d periodic: %d segments' % (a.variant, N, seg.total))
+    recs = (ctx.handle,) + seg.recs + (0, N, dw.ptr, 0, q.ptr, nat.XC_F64)
+    report = functools.partial(rt.report_means, ctx, reps=a.reps)
 
-    def report(name, call, profile, keys):
-        call()
-        ctx.sync()
-        t0 = time.perf_counter()
-        for _ in range(a.reps):
-            call()
-        ctx.sync()
-        wall = (time.perf_counter() - t0) / a.reps
-        ctx.set_kernel_timing(True)
-        call()
-        acc = dict.fromkeys(keys, 0.0)
-        for _ in range(a.reps):
-            call()
-            pr = profile()
-            for k in keys:
-                acc[k] += pr[k] / a.reps
-        ctx.set_kernel_timing(False)
-        print('%-22s wall %9.3f ms | %s | sum %8.3f | %d rounds, %d groups'
-              % (name, wall * 1e3, ', '.join('%s %8.3f' % (k, acc[k]) for k in keys), sum(acc.values()), pr['rounds'], pr['groups']))
-        return wall, acc
-
-    rc = ctx.lib.xc_contour_piece_tree_dev(*recs, 0, dpc.ptr, *([None] * 13))
-    if rc not in (0, 1):
-        ctx._check(rc)
-    npiece = int(dpc.download((N,), np.uint64).sum())
+    dpc = ctx.alloc(N * 8)
+    npiece = rt.count_then(ctx, lambda: ctx.lib.xc_contour_piece_tree_dev(*recs, 0, dpc.ptr, *([None] * 13)), dpc, N)
     cap = max(npiece, 1)
     rec = [ctx.alloc(cap * 8) for _ in range(13)]
     dlab = ctx.alloc(N * ny * nx * 4)
@@ -89,7 +51,6 @@ def main():
                     ctx.last_cplabel_profile, keys + ('label_ms',))
     fe20 = rec[0].download((npiece,), np.int64)                               # the order of the rows inside a range is the call's own
     # the fields: three shared moment planes, five per-slab stacks
-    qh = q.download((ny, nx), np.float64)
     la, lo = np.deg2rad(lat)[:, None], np.deg2rad(lon)[None, :]
     shared = [np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la) * np.ones_like(lo)]
     dg = [ctx.to_device(np.ascontiguousarray(p)) for p in shared] + [ctx.to_device(np.ascontiguousarray(qh * (k + 2.0))) for k in range(5)]
@@ -143,8 +104,6 @@ def main():
         bad_sum += int((np.abs(s - net0[sl])[cl] > 1e-9 * sa[cl]).sum())
     print('  %d pieces, %d rings; rings whose extremum of x differs from the map\'s: %d; whose place of the minimum differs: %d; '
           'whose first net sum differs from bincount by more than 1e-9: %d' % (npiece, int(closed.sum()), bad_x, bad_at, bad_sum))
-    for b in [df, dt, dp, dc, dn, dpc, q, dlat, dlon, dw, dlab] + rec + dg + out:
-        b.free()
 
 
 if __name__ == '__main__':

@@ -1,24 +1,19 @@
 #!/usr/bin/env python3
 """The launch sequence of K18-K21: one call of xc_contour_piece_{interiors,tree,labels,props}_dev each, twice (the first call warms up),
-on a 24 x 65 plane in three ranges of which the middle one has no segments (K12 traces two levels; the empty range is put between
-them), periodic X and then plain, flip 0, with a weight, an integrand, three fields and x.  Meant to run under a kernel trace of its own (no counters):
+on a 24 x 65 plane in three ranges of which the middle one has no segments (K12 traces two levels, record_timing.segment_records; the empty range is put
+between them), periodic X and then plain, flip 0, with a weight, an integrand, three fields and x.  Meant to run under a kernel trace of its own (no counters):
 
     rocprofv3 --kernel-trace --output-format csv -d OUT -- python tools/cprecords_trace.py
 
 Every call starts with its one k_ci_bound launch, so the trace splits into calls there; the ordered (kernel, grid, block) lists of two
 builds of the library (XC_LIB_PATH names another one) are then compared line by line.  Prints the piece counts of every call."""
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
+    nat, ctx = rt.open_context()
     ny, nx, N = 24, 65, 3
     rng = np.random.default_rng(1)
     y, x = np.mgrid[0:ny, 0:nx]
@@ -27,20 +22,13 @@ def main():
     dq, dc = ctx.to_device(q), ctx.to_device(lv)
     dw, df32 = ctx.to_device(rng.uniform(0.5, 1.5, (ny, nx))), ctx.to_device(rng.standard_normal((ny, nx)).astype(np.float32))
     dg = [ctx.to_device(rng.standard_normal((ny, nx))) for _ in range(3)]
-    dn2, dpc = ctx.alloc(2 * 8), ctx.alloc(N * 8)
+    dpc = ctx.alloc(N * 8)
     for periodic in (1, 0):
-        seg = ctx.lib.xc_contour_segments_periodic_dev if periodic else ctx.lib.xc_contour_segments_dev
-        head = (ctx.handle, dq.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, 2, 0)
-        rc = seg(*head, 0, dn2.ptr, None, None, None)
-        if rc not in (0, 1):
-            ctx._check(rc)
-        cnt = dn2.download((2,), np.uint64)
-        total = int(cnt.sum())
-        de, dt, dp = ctx.alloc(total * 8), ctx.alloc(total * 8), ctx.alloc(total * 32)
-        ctx._check(seg(*head, total, dn2.ptr, de.ptr, dt.ptr, dp.ptr))
-        cnt = np.array([cnt[0], 0, cnt[1]], dtype=np.uint64)                     # the records stay as they are: range 1 holds none
+        seg = rt.segment_records(ctx, nat, dq, ny, nx, dc, 2, periodic)
+        total = seg.total
+        cnt = np.array([seg.counts[0, 0], 0, seg.counts[0, 1]], dtype=np.uint64)  # the records stay as they are: range 1 holds none
         dn = ctx.to_device(cnt)
-        recs = (ctx.handle, N, dn.ptr, de.ptr, dt.ptr, dp.ptr, ny, nx, periodic, 0, N, dw.ptr, 0, df32.ptr, nat.XC_F32)
+        recs = (ctx.handle, N, dn.ptr, seg.df.ptr, seg.dt.ptr, seg.dp.ptr, ny, nx, periodic, 0, N, dw.ptr, 0, df32.ptr, nat.XC_F32)
         rec = [ctx.alloc(total * 8) for _ in range(13)]
         ptrs = [b.ptr for b in rec]
         dlab = ctx.alloc(N * ny * nx * 4)
@@ -57,7 +45,7 @@ def main():
             for _ in range(2):
                 ctx._check(call())
             print('periodic %d %-9s segments %s pieces %s' % (periodic, name, cnt.tolist(), dpc.download((N,), np.uint64).tolist()))
-        for b in [dn, de, dt, dp, dlab] + rec + out:
+        for b in [dn, seg.dn, seg.df, seg.dt, seg.dp, dlab] + rec + out:           # the plain pass starts from the memory the periodic one had
             b.free()
 
 

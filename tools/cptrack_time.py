@@ -1,19 +1,19 @@
 """Times Contour2D.cal_contour_piece_tracks (K23) on one PV-like stack and, beside it, in the same process, the loop of
 cal_contour_piece_overlap calls it replaces (every step traced and labelled twice, the union-find over the rows NOT included: the loop is
-charged less than it costs).  Prints one JSON line: wall times (the median of --repeat runs after one warm-up), the K23 stage times and
-the rounds.
+charged less than it costs).  Prints one JSON line: wall times (the median of record_timing.wall_times over --repeat runs after one
+warm-up; sync=False: every call ends in its own downloads), the K23 stage times and the rounds (stage_times of ONE call, warm=False).
 
     python tools/cptrack_time.py [--ny 181 --nx 360 --steps 24 --levels 5 --repeat 3]
 """
 import argparse
 import json
-import os
 import sys
-import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import record_timing as rt
+
+sys.path.insert(0, rt.ROOT)
 import xcontour_amd as xa  # noqa: E402
 
 
@@ -32,16 +32,6 @@ def pv_like(nstep, ny, nx, seed=23):
             f = f + amp * np.exp(-((lat[:, None] - cy) ** 2 + (dx * np.cos(y)) ** 2) / (2 * sig * sig))
         q[t] = f
     return q, lat, lon
-
-
-def median_time(fn, repeat):
-    fn()
-    ts = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts))
 
 
 def main():
@@ -69,11 +59,10 @@ def main():
     def loop():
         return [singles[t].cal_contour_piece_overlap(lv, steps[t + 1], periodic=True)[2] for t in range(a.steps - 1)]
 
-    t_tracks, t_loop = median_time(tracks, a.repeat), median_time(loop, a.repeat)
-    cm.ctx.set_kernel_timing(True)
-    tree, links, tr = tracks()
-    prof = cm.ctx.last_cptrack_profile()
-    cm.ctx.set_kernel_timing(False)
+    t_tracks, t_loop = (float(np.median(rt.wall_times(cm.ctx, fn, a.repeat, sync=False))) for fn in (tracks, loop))
+    got = []
+    _, prof = rt.stage_times(cm.ctx, lambda: got.append(tracks()), cm.ctx.last_cptrack_profile, (), 1, sync_each=False, warm=False)
+    tree, links, tr = got[0]
     pairs = loop()
     same = all(np.array_equal(links[k][links[k]['step'] == t][f], pairs[t][k][f]) for t in range(a.steps - 1) for k in range(a.levels)
                for f in ('a', 'b', 'nodes', 'area'))

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""K19 timing: xc_contour_piece_tree_dev beside K18 (xc_contour_piece_interiors_dev) on the same device records -- the inputs of
-tools/cpinside_time.py (one synthetic 1801 x 3600 float64 slab of xc_synth_dev, variant 0: PV-like, 1: pure noise; N levels over the
-field's range; periodic X; weight cos(latitude) per node, the integrand the field itself).  Every line is the mean of --reps calls
+"""K19 timing: xc_contour_piece_tree_dev beside K18 (xc_contour_piece_interiors_dev) on the same device records:
+one synthetic 1801 x 3600 float64 slab (record_timing.synth_plane(ny, nx, variant): variant 0 PV-like, 1 pure noise), N levels over
+the field's range (levels_over), K12's periodic records of them (segment_records), the weight cos_weights(lat, ny, nx), the integrand the
+field itself.  Every line is record_timing.report_means: the mean of --reps calls
 after a warm-up: HIP events (xc_set_kernel_timing) for the stages of each entry's own profile, and the wall clock around the
 synchronising call.  Then the shape of the tree: rings, rings with a parent, the largest depth, and the rows between the first edge of
 every ring WITHOUT a parent and row 0 -- the steps of those rings' parent walks to within one row each (flip 0: the walks go up), a lower
@@ -11,14 +12,11 @@ bound of all parent walks.
     python tools/cptree_time.py --variant 1 --ncont 121 --reps 3
 """
 import argparse
-import os
-import sys
-import time
+import functools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -29,60 +27,24 @@ def main():
     ap.add_argument('--ny', type=int, default=1801)
     ap.add_argument('--nx', type=int, default=3600)
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.default_context(0)
+    nat, ctx = rt.open_context()
     ny, nx, N = a.ny, a.nx, a.ncont
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
-    mm = ctx.minmax(q.download((ny, nx), np.float64).reshape(1, -1))[0]
-    lv = np.linspace(mm[0], mm[1], N)
-    dw = ctx.to_device(np.ascontiguousarray(np.broadcast_to(np.cos(np.deg2rad(lat))[:, None], (ny, nx))))
-    dc, dn, dpc = ctx.to_device(lv), ctx.alloc(N * 8), ctx.alloc(N * 8)
-    head = (ctx.handle, q.ptr, nat.XC_F64, 1, ny, nx, dc.ptr, N, 0)
-    f = ctx.lib.xc_contour_segments_periodic_dev
-    rc = f(*head, 0, dn.ptr, None, None, None)
-    if rc not in (0, 1):
-        ctx._check(rc)
-    total = int(dn.download((N,), np.uint64).sum())
-    print('variant %d ncont %d periodic: %d segments' % (a.variant, N, total))
-    df, dt, dp = ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 8), ctx.alloc(max(total, 1) * 32)
-    ctx._check(f(*head, total, dn.ptr, df.ptr, dt.ptr, dp.ptr))
-    recs = (ctx.handle, N, dn.ptr, df.ptr, dt.ptr, dp.ptr, ny, nx, 1, 0, N, dw.ptr, 0, q.ptr, nat.XC_F64)
+    q, qh, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant)
+    lv = rt.levels_over(ctx, qh, N)
+    dw = ctx.to_device(rt.cos_weights(lat, ny, nx))
+    seg = rt.segment_records(ctx, nat, q, ny, nx, ctx.to_device(lv), N, True)
+    print('variant %d ncont %d periodic: %d segments' % (a.variant, N, seg.total))
+    recs = (ctx.handle,) + seg.recs + (0, N, dw.ptr, 0, q.ptr, nat.XC_F64)
+    report = functools.partial(rt.report_means, ctx, reps=a.reps)
 
-    def report(name, call, profile, keys):
-        call()
-        ctx.sync()
-        t0 = time.perf_counter()
-        for _ in range(a.reps):
-            call()
-        ctx.sync()
-        wall = (time.perf_counter() - t0) / a.reps
-        ctx.set_kernel_timing(True)
-        call()
-        acc = dict.fromkeys(keys, 0.0)
-        for _ in range(a.reps):
-            call()
-            pr = profile()
-            for k in keys:
-                acc[k] += pr[k] / a.reps
-        ctx.set_kernel_timing(False)
-        print('%-22s wall %9.3f ms | %s | sum %8.3f | %d rounds, %d groups'
-              % (name, wall * 1e3, ', '.join('%s %8.3f' % (k, acc[k]) for k in keys), sum(acc.values()), pr['rounds'], pr['groups']))
-        return wall
-
-    rc = ctx.lib.xc_contour_piece_interiors_dev(*recs, 0, dpc.ptr, *([None] * 7))
-    if rc not in (0, 1):
-        ctx._check(rc)
-    npiece = int(dpc.download((N,), np.uint64).sum())
+    dpc = ctx.alloc(N * 8)
+    npiece = rt.count_then(ctx, lambda: ctx.lib.xc_contour_piece_interiors_dev(*recs, 0, dpc.ptr, *([None] * 7)), dpc, N)
     rec = [ctx.alloc(max(npiece, 1) * 8) for _ in range(13)]
     k18 = [b.ptr for b in rec[:7]]
-    w18 = report('K18 piece interiors', lambda: ctx._check(ctx.lib.xc_contour_piece_interiors_dev(*recs, npiece, dpc.ptr, *k18)),
-                 ctx.last_cpinside_profile, ('table_ms', 'rounds_ms', 'roots_ms', 'walk_ms'))
-    w19 = report('K19 piece tree', lambda: ctx._check(ctx.lib.xc_contour_piece_tree_dev(*recs, npiece, dpc.ptr, *[b.ptr for b in rec])),
-                 ctx.last_cptree_profile, ('table_ms', 'rounds_ms', 'roots_ms', 'walk_ms', 'tree_ms'))
+    w18, _ = report('K18 piece interiors', lambda: ctx._check(ctx.lib.xc_contour_piece_interiors_dev(*recs, npiece, dpc.ptr, *k18)),
+                    ctx.last_cpinside_profile, ('table_ms', 'rounds_ms', 'roots_ms', 'walk_ms'))
+    w19, _ = report('K19 piece tree', lambda: ctx._check(ctx.lib.xc_contour_piece_tree_dev(*recs, npiece, dpc.ptr, *[b.ptr for b in rec])),
+                    ctx.last_cptree_profile, ('table_ms', 'rounds_ms', 'roots_ms', 'walk_ms', 'tree_ms'))
     print('  K19 / K18 wall: %.3f' % (w19 / w18))
     first, closed = rec[0].download((npiece,), np.int64), rec[2].download((npiece,), np.int32) != 0
     parent, depth = rec[7].download((npiece,), np.int64), rec[8].download((npiece,), np.int32)
@@ -91,8 +53,6 @@ def main():
                                                                                  int(depth.max()) if npiece else 0))
     print('  rings without a parent: %d, rows from their first edges to row 0: %d (mean %.1f)'
           % (int(top.sum()), int(((first[top] >> 1) // nx).sum()), float(((first[top] >> 1) // nx).mean()) if top.any() else 0.0))
-    for b in [df, dt, dp, dc, dn, dpc, q, dlat, dlon, dw] + rec:
-        b.free()
 
 
 if __name__ == '__main__':

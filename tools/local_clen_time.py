@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""K11 timing: xc_local_contour_lengths_dev on synthetic 3600 x 1801 float64 slabs made on the device (xc_synth_dev variant 0:
-PV-like, 1: pure noise), a `--window` x `--window` window every `--stride` nodes at the windows' means, lat / lon in radians.
+"""K11 timing: xc_local_contour_lengths_dev on synthetic 3600 x 1801 float64 slabs made on the device (record_timing.synth_plane(ny,
+nx, variant, nslab=slabs, host=False): variant 0 PV-like, 1 pure noise; no host copy), a `--window` x `--window` window every `--stride` nodes at the windows' means, lat / lon in radians.
 Prints the event time per call; run it under `rocprofv3 --kernel-trace --stats -- python tools/local_clen_time.py ...` for the
 per-kernel times.
 
@@ -8,13 +8,10 @@ per-kernel times.
     python tools/local_clen_time.py --periodic             # windows run on round the longitude ring (xc_local_contour_lengths_periodic_dev)
 """
 import argparse
-import os
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import record_timing as rt
 
 
 def main():
@@ -29,14 +26,9 @@ def main():
     ap.add_argument('--periodic', action='store_true', help='periodic X: the period is 360 degrees (float32 radians)')
     ap.add_argument('--given', action='store_true', help='give the levels (the means of a first call): phase two alone')
     a = ap.parse_args()
-    from xcontour_amd import _native as nat
-    ctx = nat.Context(0)
+    nat, ctx = rt.open_context()
     S, ny, nx, w, st = a.slabs, a.ny, a.nx, a.window, a.stride
-    lat = np.linspace(-90.0, 90.0, ny)
-    lon = np.linspace(0.0, 360.0, nx, endpoint=False)
-    dlat, dlon = ctx.to_device(lat), ctx.to_device(lon)
-    q = ctx.alloc(S * ny * nx * 8)
-    ctx._check(ctx.lib.xc_synth_dev(ctx.handle, q.ptr, nat.XC_F64, S, ny, nx, dlat.ptr, dlon.ptr, 1, a.variant))
+    q, _, lat, lon, dlat, dlon = rt.synth_plane(ctx, nat, ny, nx, a.variant, nslab=S, host=False)
     y = np.deg2rad(lat.astype(np.float32)).astype(np.float64)
     x = np.deg2rad(lon.astype(np.float32)).astype(np.float64)
     dy, dx = ctx.to_device(y), ctx.to_device(x)
@@ -72,7 +64,6 @@ def main():
           '%.1f %% of the windows with a contour, %.0f G window nodes per s'
           % (S, a.variant, w, st, ' periodic' if a.periodic else '', ' (levels given)' if a.given else '', S * nwin, ms * 1e3, ms * 1e3 / S, float(n.sum()) / (S * nwin),
              100.0 * float(np.mean(~np.isnan(ln))), nodes / (ms * 1e-3) / 1e9))
-    ctx.close()
 
 
 if __name__ == '__main__':
