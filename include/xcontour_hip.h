@@ -957,6 +957,50 @@ int xc_contour_folds_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, con
                          int64_t* nodes, double* area, double* mx, double* my, double* integral);
 int xc_last_cfold_profile(xc_ctx* ctx, double* ms, int* rounds, int* groups);
 
+/* ------------------------------------------------------------------ K25 contour map: contour vectors back on the plane
+ * Everything above ends in contour space.  The way back -- the equivalent latitude of every node, nkeff painted onto the plane, the
+ * displacement of a node from its equivalent coordinate -- is var(contour) evaluated at the tracer value of every node: the reference's
+ * _interp1d(x, xf, yf, inc) (core.py:1405-1434) with x = q(node), xf = the levels, yf = the vector.  The reference only has the forward
+ * direction (interp_to_coords, core.py:1050-1100); this call is build-defined.  One streaming pass: the tracer is read once, nv planes
+ * are written.
+ * Input:
+ *   q            XC_F32 or XC_F64 [nslab][ny][nx]
+ *   xp           f64 levels, [N] for all slabs (xp_per_slab == 0) or [nslab][N]; N >= 2
+ *   nv           the number of value vectors, 1 <= nv <= XC_CMAP_MAXV
+ *   fp[nv]       HOST array of pointers (device pointers in the _dev form), each f64 [N] or [nslab][N]
+ *   fp_per_slab[nv]  HOST array: 0 one vector [N] shared by all slabs, non-zero [nslab][N]
+ *   out[nv]      HOST array of pointers to the nv output planes, out_dtype [nslab][ny][nx] each
+ *   out_dtype    XC_F64, or XC_F32: the float64 result rounded to float32 once
+ * RULE       per slab s, node (r, c) and vector v, everything promoted to float64:
+ *                rev = !(xp[s][0] < xp[s][N-1])                                          (core.py:1426-1430)
+ *                out_v[s][r][c] = np.interp(q[s][r][c], X, F),  X, F = xp[s], fp_v[s], both reversed when rev is set
+ *            bit for bit numpy's compiled arr_interp: below X[0] the result is F[0], above X[N-1] it is F[N-1]; a NaN q gives NaN;
+ *            with j the largest index with X[j] <= q: j == N - 1 or q == X[j] gives F[j] itself; else with
+ *            slope = (F[j+1] - F[j]) / (X[j+1] - X[j]) the result is slope * (q - X[j]) + F[j]; where that is NaN,
+ *            slope * (q - X[j+1]) + F[j+1]; where that is NaN too and F[j+1] == F[j], F[j].  Every operation rounds once (no FMA).
+ * LEVELS     strictly monotonic (either direction) and finite in every slab.  A slab whose xp[s][0] or xp[s][N-1] is NaN (the
+ *            levels of an all-NaN tracer) gets NaN on every node.  The host form checks this first: two adjacent equal levels are
+ *            XC_EEDGES with the reference's text 'non monotonic bins' (core.py:1233-1251); a slab that is not finite or not
+ *            monotonic in the direction of its ends is XC_EBADARG.  The _dev form cannot read the levels and trusts its caller: on
+ *            other levels the result is unspecified, but every access stays in bounds.
+ * LIMITS     The levels and the vectors of a slab live in LDS: (nv + 1) * N <= XC_CMAP_MAX_LDS_DOUBLES (64 KiB: N = 3000 with
+ *            nv <= 1, N = 201 with nv <= 8, N <= 4096 at all); more is XC_EBADARG.  At most 65535 slabs per call, as the other
+ *            entries.  A workgroup walks tiles of XC_CMAP_TILE cells.  No alignment is asked of any pointer beyond its element's.
+ * REFUSALS   XC_EBADARG with nothing written: a NULL pointer (q, xp, fp, fp_per_slab, out, or one of the first nv entries of fp or
+ *            out), nslab, ny or nx < 1, N < 2, nv outside [1, XC_CMAP_MAXV], a dtype code that is neither XC_F32 nor XC_F64, and the
+ *            two limits above.
+ * The _dev form takes device pointers and only enqueues; the host form stages through the context's arena (a tracer with a device
+ * mirror is read where it is) and returns with the planes in the caller's arrays.                                                    */
+#define XC_CMAP_MAXV 8
+#define XC_CMAP_MAX_LDS_DOUBLES 8192
+#define XC_CMAP_TILE 1024
+int xc_contour_map_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                       const double* xp, int N, int xp_per_slab,
+                       int nv, const double* const* fp, const int* fp_per_slab, void* const* out, int out_dtype);
+int xc_contour_map(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                   const double* xp, int N, int xp_per_slab,
+                   int nv, const double* const* fp, const int* fp_per_slab, void* const* out, int out_dtype);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -22,4 +22,18 @@ def label_overlap(lab_a, lab_b, w=None, f=None):
     that already hold two maps of `Contour2D.cal_contour_piece_labels`."""
     return default_context().label_overlap(lab_a, lab_b, w=w, f=f)
 
+
+def map_to_plane(q, levels, values, dtype='float64'):
+    """Per-contour vectors back on the plane (K25, `Context.contour_map` on the default context): numpy in, numpy out.  q (ny, nx)
+    or (nslab, ny, nx); levels (N,) or (nslab, N); values: one vector, or a sequence of up to eight, each (N,) or (nslab, N).
+    Returns np.interp(q, levels, vector) per slab -- the reference's _interp1d, decreasing levels included -- as one plane or a
+    list of planes of q's shape.  For callers that hold bare arrays; labelled ones go through `Contour2D.map_to_plane`."""
+    import numpy as np
+    q = np.asarray(q)
+    one = isinstance(values, np.ndarray) and values.ndim == 1
+    out = default_context().contour_map(q[None] if q.ndim == 2 else q, levels, [values] if one else values, out_dtype=dtype)
+    out = [p[0] for p in out] if q.ndim == 2 else out
+    return out[0] if one else out
+
+
 __version__ = "0.1.0"

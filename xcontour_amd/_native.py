@@ -171,6 +171,8 @@ PROTOTYPES = {
     'xc_contour_folds_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64,
                                        _vp, _vp, _vp, _vp, _i64, _vp] + [_vp] * 11),
     'xc_last_cfold_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_map_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
+    'xc_contour_map': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
     'xc_contour_piece_interiors_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
                                                  _vp, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'xc_last_cpinside_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -369,6 +371,19 @@ def _check_ascending(contours, who):
         raise XContourHipError(XC_EEDGES, '%s: contours must be ascending without NaN' % who)
 
 
+def _check_map_levels(levels):
+    """the levels of K25 as its host form checks them: per slab finite and strictly monotonic in the direction of the ends; a slab
+    with a NaN end (an all-NaN tracer's) is let through"""
+    x = levels.reshape(-1, levels.shape[-1])
+    x = x[~(np.isnan(x[:, 0]) | np.isnan(x[:, -1]))]
+    d = np.diff(x, axis=1)
+    if (d == 0).any():
+        raise XContourHipError(XC_EEDGES, 'non monotonic bins')
+    up = (x[:, :1] < x[:, -1:])
+    if not np.isfinite(x).all() or not np.where(up, d > 0, d < 0).all():
+        raise XContourHipError(XC_EBADARG, 'xc_contour_map: the levels of every slab must be finite and strictly monotonic')
+
+
 def _stack3(q):
     """a stack as the contour calls take it (an array, or a lazy stack) -> (the stack, (nslab, ny, nx))"""
     q = _stack_in(q)
@@ -485,6 +500,9 @@ class _Columns(object):
 
 OVERTURN_SELECT = {'all': 0, 'circumpolar': 1, 'main': 2}       # how K16 / K17 select pieces: the names and the library's codes
 XC_PROPS_MAXF = 8                                               # fields one K21 call takes (include/xcontour_hip.h)
+XC_CMAP_MAXV = 8                                                # value vectors one K25 call takes
+XC_CMAP_MAX_LDS_DOUBLES = 8192                                  # K25: (nv + 1) * N may not exceed this
+XC_CMAP_TILE = 1024                                             # K25: cells a workgroup takes per step
 _UNSET = object()
 
 
@@ -1089,6 +1107,51 @@ class Context(object):
                                           _ptr(rdx), _ptr(rdy), 1 if periodic_x else 0, _ptr(out)))
             return out
         return self._batched(nslab, ny * nx * (q.dtype.itemsize + 8), one)
+
+    def contour_map(self, q, levels, values, out_dtype=np.float64):
+        """Contour vectors back on the plane (K25, xc_contour_map).  q (nslab, ny, nx) f32/f64 (or a lazy stack); levels (N,) or
+        (nslab, N), N >= 2, strictly monotonic in either direction and finite per slab (a slab whose first or last level is NaN
+        gives NaN everywhere); values: a sequence of 1 .. XC_CMAP_MAXV arrays (N,) or (nslab, N).  Per slab and vector
+        out = np.interp(q, X, F) in float64, X, F the levels and the vector, both reversed when not levels[0] < levels[-1]
+        (the reference's _interp1d), bit for bit; out_dtype float32 rounds that once.  Returns the list of planes (nslab, ny, nx),
+        one per vector.  A tracer with a device mirror (keep_resident) is read in place through the _dev entry point."""
+        q, (nslab, ny, nx) = _stack3(q)
+        out_dtype = np.dtype(out_dtype)
+        qcode, ocode = dtype_code(q.dtype), dtype_code(out_dtype)
+        levels = _contig(levels, np.float64)
+        if levels.ndim not in (1, 2) or (levels.ndim == 2 and levels.shape[0] != nslab) or levels.shape[-1] < 2:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_map: levels must be (N,) or (nslab, N) with N >= 2')
+        N = levels.shape[-1]
+        values = [_contig(v, np.float64) for v in values]
+        nv = len(values)
+        if not 1 <= nv <= XC_CMAP_MAXV:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_map: 1 to %d value vectors, not %d' % (XC_CMAP_MAXV, nv))
+        for v in values:
+            if v.shape not in ((N,), (nslab, N)):
+                raise XContourHipError(XC_EBADARG, 'xc_contour_map: every value vector must be (N,) or (nslab, N) like the levels, N = %d' % N)
+        if (nv + 1) * N > XC_CMAP_MAX_LDS_DOUBLES:
+            raise XContourHipError(XC_EBADARG, 'xc_contour_map: (nv + 1) * N must not exceed %d' % XC_CMAP_MAX_LDS_DOUBLES)
+        flags =(C.c_int * nv)(*[1 if v.ndim == 2 else 0 for v in values])
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, lb_ = _stack_now(q, s0, s1), _part(levels, 2, s0, s1)
+            vb = [_part(v, 2, s0, s1) for v in values]
+            qp = self._mirror(qb)
+            if qp:
+                # the tracer is on the device already: only the vectors go up, and the planes come down from device memory.  The device
+                # entry point trusts its caller, so what the host form checks itself (xc_forms.hip, the same texts) is checked here
+                _check_map_levels(lb_)
+                with self._temporaries([lb_] + vb, [n * ny * nx * out_dtype.itemsize] * nv) as bufs:
+                    dl, dv, do = bufs[0], bufs[1:1 + nv], bufs[1 + nv:]
+                    self._check(self.lib.xc_contour_map_dev(self.handle, qp, qcode, n, ny, nx, dl.ptr, N, 1 if levels.ndim == 2 else 0, nv,
+                                                            (_vp * nv)(*[b.ptr for b in dv]), flags, (_vp * nv)(*[b.ptr for b in do]), ocode))
+                    return [b.download((n, ny, nx), out_dtype) for b in do]
+            outs = [np.empty((n, ny, nx), dtype=out_dtype) for _ in range(nv)]
+            self._check(self.lib.xc_contour_map(self.handle, _ptr(qb), qcode, n, ny, nx, _ptr(lb_), N, 1 if levels.ndim == 2 else 0, nv,
+                                                (_vp * nv)(*[_ptr(v) for v in vb]), flags, (_vp * nv)(*[_ptr(o) for o in outs]), ocode))
+            return outs
+        return self._batched(nslab, ny * nx * (q.dtype.itemsize + nv * out_dtype.itemsize), one)
 
     def crossing(self, q, contours, area, stride=1, pad_x=0, pad_mode='edge', full_width=False):
         """Box-counting contour crossing (xc_crossing).  q (nslab, ny, nx) f32/f64; contours (N,) or

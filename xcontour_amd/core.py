@@ -315,7 +315,11 @@ class Contour2D(object):
         (reference core.py:205-266).  int: N equally spaced levels per slab (GPU
         min/max + level kernel, exact dtype rules); array: given levels.
         """
-        q, lead, lshape, coords = self._plane(self.tracer)
+        return self._contours_of(self.tracer, levels)
+
+    def _contours_of(self, tracer, levels):
+        """cal_contours on any tracer of the object's plane (cal_equivalent_coordinate_map takes one)"""
+        q, lead, lshape, coords = self._plane(tracer)
         q = self._float(q)
         if type(levels) is int or isinstance(levels, np.integer):
             ctr = self.ctx.contours(q, int(levels), self.increase, self.dtype).astype(self.dtype)      # K1 + levels, one call, one sync
@@ -325,7 +329,7 @@ class Contour2D(object):
             mmin = self.ctx.minmax(q)[:, 0].astype(q.dtype)
             ctr = ((mmin - mmin)[:, None] + levs[None, :]).astype(self.dtype)   # core.py:254
             ccoord = levs
-        return self._wrap_contour(ctr, lead, lshape, coords, lb.unwrap(self.tracer, lazy=True)[3], self.tracer, ccoord)
+        return self._wrap_contour(ctr, lead, lshape, coords, lb.unwrap(tracer, lazy=True)[3], tracer, ccoord)
 
     def _contour_values(self, contour, nslab, lead, lshape):
         """-> ndarray (nslab, N) of levels (per slab or broadcast) in their own dtype"""
@@ -1808,6 +1812,99 @@ class Contour2D(object):
         tdims, g = self._in_dim_order(g, tracer, lead, lshape)
         name = lb.unwrap(tracer, lazy=True)[3]
         return lb.wrap(g, tdims, coords, 'grdS' + (name or ''), tracer)
+
+    def _map_vector(self, who, what, v, nslab, lead, lshape):
+        """levels or a per-contour vector of map_to_plane, through `_contour_values` like the levels of every contour call -> float64
+        (N,) when every slab shares it, else (nslab, N).  Leading dims are those of the tracer, or none"""
+        if lb.is_labeled(v):
+            raw, dims, _, _ = lb.unwrap(v, lazy=True)
+            if 'contour' not in dims:
+                raise Exception('%s: %s should have a "contour" dim' % (who, what))
+            shared = True
+            for d, n in zip(dims, raw.shape):
+                if d == 'contour' or n == 1:
+                    continue
+                shared = False
+                if d not in lead or lshape[list(lead).index(d)] != n:
+                    raise Exception('%s: the leading dims of %s do not match the tracer\'s %r' % (who, what, dict(zip(lead, lshape))))
+        else:
+            v, shared = np.asarray(v), True
+            if v.ndim != 1:
+                raise Exception('%s: %s should be a labelled array with a "contour" dim or a 1-D array' % (who, what))
+        b = self._contour_values(v, nslab, list(lead), list(lshape))
+        return np.ascontiguousarray(b[0] if shared else b, dtype=np.float64)
+
+    def map_to_plane(self, contour, vs, tracer=None, dtype=np.float64):
+        """
+        Per-contour quantities back on the plane (K25, xc_contour_map): every node gets var(contour) evaluated at its own
+        tracer value -- the equivalent latitude of every node, nkeff painted onto the plane.  This is the inverse of
+        interp_to_coords (reference core.py:1050-1100): the same _interp1d (core.py:1405-1434) with x = the tracer of the
+        node, xf = the contour levels, yf = the variable; the direction comes from levels[0] < levels[-1] per slab, nodes
+        outside the levels get the end values, a NaN node stays NaN.  Build-defined: the reference has no counterpart.
+
+        `contour`: what cal_contours returns (levels per leading index), or a 1-D array of levels for all slabs; at least
+        two levels, strictly monotonic.  `vs`: a labelled array with a 'contour' dim, or a Dataset / dict of up to eight of
+        them (the result of keff(), or a part of it); leading dims are those of the tracer, or none.  One pass over the
+        tracer serves all of them.  Returns a plane with the tracer's dims and coords in `dtype` (float64, or float32:
+        rounded once), or a Dataset of planes under the names of `vs`.
+        """
+        who = 'map_to_plane'
+        data = self.tracer if tracer is None else tracer
+        q, lead, lshape, coords = self._float_plane(data)
+        nslab = q.shape[0]
+        if np.dtype(dtype) not in _F48:
+            raise Exception('%s: dtype should be float32 or float64' % who)
+        levels = self._map_vector(who, 'contour', contour, nslab, lead, lshape)
+        single = lb.is_labeled(vs)
+        if single:
+            items = [(lb.unwrap(vs, lazy=True)[3], vs)]
+        elif isinstance(vs, dict):
+            items = list(vs.items())
+        elif hasattr(vs, 'data_vars'):
+            items = [(k, vs[k]) for k in vs.data_vars]
+        else:
+            raise Exception('%s: vs should be a labelled array with a "contour" dim, or a Dataset / dict of them' % who)
+        if not 1 <= len(items) <= nat.XC_CMAP_MAXV:
+            raise Exception('%s: one to %d variables per call, not %d' % (who, nat.XC_CMAP_MAXV, len(items)))
+        vals = [self._map_vector(who, 'variable %r' % (k,), v, nslab, lead, lshape) for k, v in items]
+        for (k, _), v in zip(items, vals):
+            if v.shape[-1] != levels.shape[-1]:
+                raise Exception('%s: variable %r has %d values along "contour", the contours %d' % (who, k, v.shape[-1], levels.shape[-1]))
+        try:
+            planes = self.ctx.contour_map(q, levels, vals, out_dtype=dtype)
+        except nat.XContourHipError as e:
+            if e.code == nat.XC_EEDGES:
+                raise Exception('non monotonic bins')                      # the reference's text (core.py:1233-1251)
+            raise
+        out = []
+        for (k, _), g in zip(items, planes):
+            tdims, g = self._in_dim_order(g, data, lead, lshape)
+            out.append(lb.wrap(g, tdims, coords, k, data))
+        return out[0] if single else lb.merge(out, out[0])
+
+    def cal_equivalent_coordinate_map(self, contour, table, tracer=None, displacement=False):
+        """
+        The equivalent coordinate of every node of the plane (the equivalent-latitude map), named '<eq dim>Eq': the chain
+        cal_contours -> cal_integral_within_contours_hist -> table.lookup_coordinates -> map_to_plane in one call.  Like
+        interp_to_coords this is the N-contour HISTOGRAM approximation: the area inside a contour is the histogram's, the
+        coordinate between two contours is linear in the tracer, and it converges to the exact map as N grows (the exact one
+        would come from the sort of cal_sorted_profile carrying cell indices; not provided).
+
+        `contour`: an int N (N equally spaced levels per slab) or levels as cal_contours takes them, or its result.
+        `table`: the A(Yeq) table.  displacement=True: also returns the row coordinate of every node minus the map (Y - Yeq,
+        the geometry behind local wave activity), named '<eq dim>Disp'; one host subtraction.
+        """
+        data = self.tracer if tracer is None else tracer
+        ctr = contour if lb.is_labeled(contour) else self._contours_of(data, contour)
+        area = self.cal_integral_within_contours_hist(ctr, tracer=data)
+        eq = table.lookup_coordinates(area).rename(self.dimEqV + 'Eq')
+        m = self.map_to_plane(ctr, eq, tracer=data)
+        if not displacement:
+            return m
+        v, dims, coords, _ = lb.unwrap(m)
+        y = np.asarray(self._eq_coord(data), dtype=np.float64)
+        shp = [len(y) if d == self.dimEqV else 1 for d in dims]
+        return m, lb.wrap(y.reshape(shp) - v, dims, coords, self.dimEqV + 'Disp', data)
 
     def cal_sorted_profile(self, table, tracer=None, mask=None, return_sorted=False):
         """

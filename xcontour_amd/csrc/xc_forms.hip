@@ -1,6 +1,6 @@
 // C ABI, part 4: the host forms of the kernels outside the Keff chain -- row sums (K2), the squared gradient (K4), the local wave
 // activity (K7, xc_lwa.hip), the sorted profile (K8, xc_sort.hip), crossings (K9, xc_cross.hip), contour lengths (K10, xc_clen.hip; K11, xc_lclen.hip), line integrals along contours (K15, xc_cline.hip), contour segments (K12, xc_cseg.hip),
-// synthetic slabs -- and the records of what they launched.
+// the contour map (K25, xc_cmap.hip), synthetic slabs -- and the records of what they launched.
 #include "xc_capi.h"
 #include <cmath>
 
@@ -29,6 +29,26 @@ static int check_levels(xc_ctx* ctx, const char* who, const double* contours, in
 {
     *nc = contours_per_slab ? nslab : 1;
     return check_ascending(contours, *nc, ncont) ? XC_OK : fail(ctx, XC_EEDGES, std::string(who) + ": contours must be ascending without NaN");
+}
+
+// the levels of K25, [nc][N]: finite and strictly monotonic in the direction of their ends, slab by slab; a slab with a NaN end is the
+// all-NaN tracer's and is let through.  Two adjacent equal levels anywhere come first, under the reference's own text
+static int check_map_levels(xc_ctx* ctx, const double* xp, int64_t nc, int N)
+{
+    for (int64_t s = 0; s < nc; ++s) {
+        const double* x = xp + s * N;
+        if (x[0] != x[0] || x[N - 1] != x[N - 1]) continue;
+        for (int k = 1; k < N; ++k) if (x[k] == x[k - 1]) return fail(ctx, XC_EEDGES, "non monotonic bins");
+    }
+    for (int64_t s = 0; s < nc; ++s) {
+        const double* x = xp + s * N;
+        if (x[0] != x[0] || x[N - 1] != x[N - 1]) continue;
+        const bool up = x[0] < x[N - 1];
+        for (int k = 0; k < N; ++k)
+            if (!std::isfinite(x[k]) || (k > 0 && (up ? !(x[k] > x[k - 1]) : !(x[k] < x[k - 1]))))
+                return fail(ctx, XC_EBADARG, "xc_contour_map: the levels of every slab must be finite and strictly monotonic");
+    }
+    return XC_OK;
 }
 
 // xc_last_clen_geometry: launch_contour_lengths writes the record where it picks the geometry; a call that fails leaves it cleared
@@ -194,6 +214,45 @@ int xc_grad2(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny,
     XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dx, rdx, rb)); XC_TRY(h2d(ctx, dy, rdy, rb));
     XC_TRY(flush_in(ctx));
     XC_TRY(launch_grad2(ctx, pq, q_dtype, nslab, ny, nx, dx, dy, periodic_x, dout));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// ------------------------------------------------------------------------------------ K25
+int xc_contour_map_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                       const double* xp, int N, int xp_per_slab,
+                       int nv, const double* const* fp, const int* fp_per_slab, void* const* out, int out_dtype)
+{
+    XC_CTX(ctx);
+    return launch_contour_map(ctx, q, q_dtype, nslab, ny, nx, xp, N, xp_per_slab, nv, fp, fp_per_slab, out, out_dtype);
+}
+
+int xc_contour_map(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                   const double* xp, int N, int xp_per_slab,
+                   int nv, const double* const* fp, const int* fp_per_slab, void* const* out, int out_dtype)
+{
+    XC_CTX(ctx);
+    if (!q || !xp || !fp || !fp_per_slab || !out || nslab < 1 || ny < 1 || nx < 1 || N < 2 || nv < 1 || nv > XC_CMAP_MAXV)
+        return fail(ctx, XC_EBADARG, "xc_contour_map: bad arguments");
+    for (int v = 0; v < nv; ++v)
+        if (!fp[v] || !out[v]) return fail(ctx, XC_EBADARG, "xc_contour_map: bad arguments");
+    if (!is_float(q_dtype) || !is_float(out_dtype)) return fail(ctx, XC_EBADARG, "xc_contour_map: bad dtype");
+    if (nslab > 65535 || (int64_t)(nv + 1) * N > XC_CMAP_MAX_LDS_DOUBLES)          // (the launcher's limits, before anything is staged)
+        return fail(ctx, XC_EBADARG, "xc_contour_map: at most 65535 slabs, and (nv + 1) * N <= XC_CMAP_MAX_LDS_DOUBLES");
+    XC_TRY(check_map_levels(ctx, xp, xp_per_slab ? nslab : 1, N));
+    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype), ob = cells * esize(out_dtype);
+    const size_t xb = (size_t)(xp_per_slab ? nslab : 1) * N * 8;
+    Stage st(ctx); void* dq; double* dx; const double* df[XC_CMAP_MAXV]; void* dout[XC_CMAP_MAXV];
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); dx = s.take<double>(xb);
+        for (int v = 0; v < nv; ++v) df[v] = s.take<double>((size_t)(fp_per_slab[v] ? nslab : 1) * N * 8);
+        for (int v = 0; v < nv; ++v) dout[v] = s.out((char*)out[v], ob);
+    }));
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dx, xp, xb));
+    for (int v = 0; v < nv; ++v) XC_TRY(h2d(ctx, (void*)df[v], fp[v], (size_t)(fp_per_slab[v] ? nslab : 1) * N * 8));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_contour_map(ctx, pq, q_dtype, nslab, ny, nx, dx, N, xp_per_slab, nv, df, fp_per_slab, dout, out_dtype));
     XC_TRY(st.deliver());
     return xc_sync(ctx);
 }

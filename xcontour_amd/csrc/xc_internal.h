@@ -387,5 +387,9 @@ int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, con
 // K18-K21 (xc_contour_piece_{interiors,tree,labels,props}_dev) have one launcher of their own file: xc_cprecords.hip
 int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                  const double* lat_deg, const double* lon_deg, uint64_t seed, int variant);
+// K25 (xc_cmap.hip): fp / fp_per_slab / out are HOST arrays of nv entries, the pointers in them device pointers
+int launch_contour_map(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                       const double* xp, int N, int xp_per_slab, int nv, const double* const* fp, const int* fp_per_slab,
+                       void* const* out, int out_dtype);
 
 }  // namespace xc
