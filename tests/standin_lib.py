@@ -15,7 +15,7 @@ _NSLAB_ARG = {'xc_minmax': 3, 'xc_levels': 3, 'xc_contours': 3, 'xc_grad2': 3, '
               'xc_contour_segments_dev': 3, 'xc_contour_segments_periodic_dev': 3, 'xc_contour_pieces_dev': 1,
               'xc_contour_polylines_dev': 1, 'xc_contour_overturning_dev': 1, 'xc_contour_interior_dev': 1,
               'xc_contour_piece_interiors_dev': 1, 'xc_contour_piece_tree_dev': 1, 'xc_contour_piece_labels_dev': 1,
-              'xc_contour_piece_props_dev': 1, 'xc_label_overlap_dev': 1, 'xc_ring_tracks_dev': 1}
+              'xc_contour_piece_props_dev': 1, 'xc_label_overlap_dev': 1, 'xc_ring_tracks_dev': 1, 'xc_contour_folds_dev': 1}
 _K12 = ('xc_contour_segments_dev', 'xc_contour_segments_periodic_dev')
 DEV = 1 << 40                           # where the stand-in's device allocations start
 RES = 1 << 44                           # where the stand-in's device mirror of a resident array starts

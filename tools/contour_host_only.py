@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""The Python around the library calls of the contour family (K10 - K20), alone: `Context` methods and `Contour2D` methods of
-K10 - K13 and of the record kernels K14, K16, K17, K19 and K20 on a small stack (4 x 24 x 48 float32, 8 levels) against a stand-in
+"""The Python around the library calls of the contour family (K10 - K24), alone: `Context` methods and `Contour2D` methods of
+K10 - K13 and of the record kernels K14, K16, K17, K19, K20 and K24 on a small stack (4 x 24 x 48 float32, 8 levels) against a stand-in
 library whose entry points return at once.  No GPU needed; a sibling of tools/facade_host_only.py, which does the same for the Keff
-sequence.  Every count download reads 2, so K12's and K13's second pass is staged too -- but zeros under find_contours, whose host
+sequence.  Every count download reads 2, so K12's, K13's and K24's second pass is staged too -- but zeros under find_contours, whose host
 join wants real records (the join is the library's own xc_join_segments: build it first), and under the label rows, where a label
 of 2 in a range of two pieces would point past the last range ("fill 0" in the row's name: the batch without segments, every label
 -1 and no map fetched).  `--package DIR`: time the xcontour_amd package under DIR instead of this tree's (an A/B against another
@@ -93,6 +93,10 @@ calls = [
     ('ctx.contour_piece_labels, fill 0', zeros(lambda: ctx.contour_piece_labels(q, lv, w=wgt, f=q, periodic=True))),
     ('cal_contour_piece_tree', lambda: cm.cal_contour_piece_tree(lv, integrand=tr, periodic=True)),
     ('cal_contour_piece_labels, fill 0', zeros(lambda: cm.cal_contour_piece_labels(lv, integrand=tr, periodic=True))),
+    ('ctx.contour_folds', lambda: ctx.contour_folds(q, lv, w=wgt, f=q, periodic=True, select='main')),
+    ('cal_contour_overturning', lambda: cm.cal_contour_overturning(lv, periodic=True)),
+    ('cal_integral_inside_contours', lambda: cm.cal_integral_inside_contours(lv, integrand=tr, periodic=True)),
+    ('cal_contour_folds', lambda: cm.cal_contour_folds(lv, integrand=tr, periodic=True)),
 ]
 tot = 0.0
 with np.errstate(all='ignore'):                # (the stand-in leaves host-form outputs as np.empty made them)

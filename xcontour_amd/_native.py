@@ -1325,6 +1325,14 @@ class Context(object):
             with self._two_pass(k12, dn, (n, N), lambda total: [total * b for b in (8, 8, 32) + tuple(per_segment)]) as (cnt, total, recs):
                 return use(cnt, total, dn, rest[1:1 + nin], rest[2 + nin:], recs)
 
+    @staticmethod
+    def _record_run(a, total, ins, recs):
+        """the arguments every entry point on K12's records takes, from what `_with_segment_records` hands to `use` -> ([e_from, e_to,
+        pts] -- three None without segments --, [w, w_per_slab, f, f_dtype]: the weights `a.w` and the integrand `a.f` lead `ins`)"""
+        has_w, has_f = a.w is not None, a.f is not None
+        return ([b.ptr for b in recs[:3]] if total else [None] * 3, [ins[0].ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0,
+                                                                     ins[has_w].ptr if has_f else None, dtype_code(a.f.dtype) if has_f else 0])
+
     def contour_segments(self, q, contours, periodic=False):
         """Marching-squares contour segments (K12, xc_contour_segments_dev; periodic=True: xc_contour_segments_periodic_dev).  q (nslab, ny, nx) f32/f64 (or a lazy stack); contours
         (N,) or (nslab, N) ASCENDING f64 without NaN.  Returns (count uint64 (nslab, N); e_from, e_to int64 (total,): the ids of the
@@ -1507,18 +1515,16 @@ class Context(object):
         --[, mask bool (nslab, N, ny, nx)]).  Only these cross to the host."""
         a = _RecordArgs('xc_contour_interior', q, contours, select=select, periodic=periodic, min_nx=2, labels32=True, w=w, f=f)
         ny, nx, N = a.ny, a.nx, a.N
-        has_w, has_f, want_mask = a.w is not None, a.f is not None, bool(return_mask)
+        has_f, want_mask = a.f is not None, bool(return_mask)
 
         def interior(cnt, total, dn, ins, outs, recs):
             n = cnt.shape[0]
-            dw, df_ = (ins[0] if has_w else None), (ins[-1] if has_f else None)
             dni, dsw = outs[:2]
             dsf, dm = (outs[2] if has_f else None), (outs[-1] if want_mask else None)
-            rec = [b.ptr for b in recs] if total else [None, None, None]
+            rec, wf = self._record_run(a, total, ins, recs)
             self._check(self.lib.xc_contour_interior_dev(
-                self.handle, cnt.size, dn.ptr, rec[0], rec[1], rec[2], ny, nx, 1 if periodic else 0, int(a.sel), 1 if flip else 0, N,
-                dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, df_.ptr if has_f else None,
-                dtype_code(a.f.dtype) if has_f else 0, dni.ptr, dsw.ptr, dsf.ptr if has_f else None, dm.ptr if want_mask else None))
+                self.handle, cnt.size, dn.ptr, *rec, ny, nx, 1 if periodic else 0, int(a.sel), 1 if flip else 0, N, *wf,
+                dni.ptr, dsw.ptr, dsf.ptr if has_f else None, dm.ptr if want_mask else None))
             res = (dni.download((n, N), np.int64), dsw.download((n, N), np.float64), dsf.download((n, N), np.float64) if has_f else None)
             return res + ((dm.download((n, N, ny, nx), np.uint8).view(np.bool_),) if want_mask else ())
 
@@ -1556,7 +1562,7 @@ class Context(object):
         ny, nx, N = a.ny, a.nx, a.N
         if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)) or not 0 <= gap < nx:
             raise XContourHipError(XC_EBADARG, 'xc_contour_folds: gap must be an int in [0, nx), not %r' % (gap,))
-        has_w, has_f = a.w is not None, a.f is not None
+        has_f = a.f is not None
         dt = self.FOLD_DTYPE
         cols = [(k,) + ((dt[k].base, 2) if dt[k].shape else (dt[k],)) for k in
                 ('row_lo', 'row_hi', 'nodes', 'area', 'mx', 'my', 'integral', 'c_west', 'c_east', 'ncol', 'ncross_max')]
@@ -1564,12 +1570,9 @@ class Context(object):
 
         def folds(cnt, total, dn, ins, outs, recs):
             n = cnt.shape[0]
-            dw, df_ = (ins[0] if has_w else None), (ins[-1] if has_f else None)
             dec = outs[4]
-            rec = [b.ptr for b in recs] if total else [None, None, None]
-            head = (self.handle, cnt.size, dn.ptr, rec[0], rec[1], rec[2], ny, nx, 1 if periodic else 0, int(a.sel), N,
-                    dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, df_.ptr if has_f else None,
-                    dtype_code(a.f.dtype) if has_f else 0, int(gap)) + tuple(b.ptr for b in outs[:4])
+            rec, wf = self._record_run(a, total, ins, recs)
+            head = (self.handle, cnt.size, dn.ptr, *rec, ny, nx, 1 if periodic else 0, int(a.sel), N, *wf, int(gap), *[b.ptr for b in outs[:4]])
 
             def k24(cap, evs):
                 at = _Columns(evs[0], cap, cols) if evs else None
@@ -1727,14 +1730,11 @@ class Context(object):
             if total == 0:
                 return (np.zeros(cnt.shape, dtype=np.uint64), np.empty(0, dtype=dt), np.empty(0, dtype=np.int64),
                         self._ring_props(None, 0, 0, nfld, has_x, None) if stage == 'props' else None)
-            dw, df_ = (ins[0] if has_w else None), (ins[has_w] if has_f else None)
-            dpc, (df, dto, dp, drec) = outs[0], recs
-            at = _Columns(drec, total, cols)
+            dpc, at = outs[0], _Columns(recs[3], total, cols)
             p = at.ptr
-            args = [self.handle, cnt.size, dn.ptr, df.ptr, dto.ptr, dp.ptr, ny, nx, 1 if periodic else 0, 1 if flip else 0, N,
-                    dw.ptr if has_w else None, 1 if has_w and wb.ndim == 3 else 0, df_.ptr if has_f else None,
-                    dtype_code(fb.dtype) if has_f else 0, total, dpc.ptr, p('first_edge'), p('nseg'), p('closed'), p('winding'),
-                    p('n_in'), p('sum_w'), p('sum_wf', has_f)]
+            rec, wf = self._record_run(a, total, ins, recs)
+            args = [self.handle, cnt.size, dn.ptr, *rec, ny, nx, 1 if periodic else 0, 1 if flip else 0, N, *wf, total, dpc.ptr,
+                    p('first_edge'), p('nseg'), p('closed'), p('winding'), p('n_in'), p('sum_w'), p('sum_wf', has_f)]
             if tree:
                 args += [p('parent'), p('depth'), p('nchild'), p('n_net'), p('net_w'), p('net_wf', has_f)]
             if stage == 'labels':

@@ -39,6 +39,7 @@ from .utils import Rearth, grad_metrics, table_from_rowsums, last_row_included
 
 _F48 = (np.dtype(np.float32), np.dtype(np.float64))
 _EDGE_CODES = {'numpy': nat.XC_EDGE_NUMPY, 'xhistogram': nat.XC_EDGE_XHISTOGRAM}
+_ABSENT = object()                       # an argument the method does not have (None is a value a caller can give)
 
 
 def _as_labeled_1d(arr, dim):
@@ -955,10 +956,8 @@ class Contour2D(object):
             if f in rec.dtype.names:
                 rec[f] = tab[f]
         if tab.size:
-            ya, yb = np.interp(tab['row_min'], np.arange(yg.size), yg), np.interp(tab['row_max'], np.arange(yg.size), yg)
-            rec['y_min'], rec['y_max'] = np.minimum(ya, yb), np.maximum(ya, yb)
-        poff = np.concatenate([[0], np.cumsum(pc.ravel().astype(np.int64))])
-        return self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(poff[:-1], poff[1:])])[0]
+            rec['y_min'], rec['y_max'] = self._rows_to_eq(yg, tab['row_min'], tab['row_max'])
+        return self._in_caller_order(order, lead, self._per_range(rec, pc))[0]
 
     # ------------------------------------------------------------------ contour overturning
     def cal_contour_overturning(self, contours, tracer=None, periodic=False, select='main'):
@@ -982,33 +981,15 @@ class Contour2D(object):
         (filled under every `select` on a periodic plane).  A column of the main ring with ncross >= 3 is overturned, and
         y_hi - y_lo there is the depth of the fold.  Every value is bit-reproducible.
         """
-        who = 'cal_contour_overturning'
-        if type(contours) in [int, list]:
-            contours = self.cal_contours(contours)
-        if select not in nat.Context.OVERTURN_SELECT:
-            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
-        data, dcoords = self._plane_dcoords(who, tracer)
-        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
-        ring = self._x_period(periodic, xg, False, who, plain=True) is not None
-        if select != 'all' and not ring:
-            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
-                            'periodic=True or the period, or select=\'all\'' % (who, select))
-        q, lead, lshape, coords = self._float_plane(data)
-        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
-        res = self.ctx.contour_overturning(q, bs, periodic=ring, select=select)
-        res = [_level_order(v, order if v.ndim == 2 else order[:, :, None]) for v in res]   # where the caller put each level
-        ncross, row_lo, row_hi, nsel, mfe, mns, mw = res
-        ya, yb = np.interp(row_lo, np.arange(yg.size), yg), np.interp(row_hi, np.arange(yg.size), yg)
-        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
-        c['contour'] = np.asarray(ccoord)
-        c[self._xdim] = np.asarray(dcoords[self._xdim])
-        dims = tuple(lead) + ('contour',)
-        shape = tuple(lshape) + ncross.shape[1:2]
-        out = [lb.wrap(v.reshape(shape + v.shape[2:]), dims + (self._xdim,), c, name, data)
-               for name, v in (('ncross', ncross), ('y_lo', np.minimum(ya, yb)), ('y_hi', np.maximum(ya, yb)))]
-        out += [lb.wrap(v.reshape(shape), dims, c, name, data)
+        p = self._piece_names('cal_contour_overturning', contours, select)
+        self._piece_plane(p, tracer, periodic)
+        self._piece_levels(p)
+        ncross, row_lo, row_hi, nsel, mfe, mns, mw = self.ctx.contour_overturning(p.q, p.bs, periodic=p.ring, select=select)
+        y_lo, y_hi = self._rows_to_eq(p.yg, row_lo, row_hi)
+        out = [self._on_contours(p, name, v, (self._xdim,)) for name, v in (('ncross', ncross), ('y_lo', y_lo), ('y_hi', y_hi))]
+        out += [self._on_contours(p, name, v)
                 for name, v in (('nsel', nsel), ('main_first_edge', mfe), ('main_nseg', mns), ('main_winding', mw))]
-        return lb.merge(out, data)
+        return lb.merge(out, p.data)
 
     def cal_integral_inside_contours(self, contours, tracer=None, integrand=None, periodic=False, select='main', side='upper',
                                      return_mask=False):
@@ -1037,47 +1018,12 @@ class Contour2D(object):
         return_mask=True also `mask`, bool over (..., contour, Y, X).  A NaN level, or one no contour follows, has the whole
         plane on one side.
         """
-        who = 'cal_integral_inside_contours'
-        if type(contours) in [int, list]:
-            contours = self.cal_contours(contours)
-        if select not in nat.Context.OVERTURN_SELECT:
-            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
-        if side not in ('upper', 'lower'):
-            raise Exception('%s: side should be \'upper\' or \'lower\', not %r' % (who, side))
-        data, dcoords = self._plane_dcoords(who, tracer)
-        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
-        ring = self._x_period(periodic, xg, False, who, plain=True) is not None
-        if select != 'all' and not ring:
-            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
-                            'periodic=True or the period, or select=\'all\'' % (who, select))
-        q, lead, lshape, coords = self._float_plane(data)
-        nslab, ny, nx = q.shape
-        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
-        dA = self._dA_array(ny, nx, nslab)[0]
-        if dA.ndim == 1:
-            dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
-        g = None
-        if integrand is not None:
-            g = self._integrand_plane(integrand)
-            if g.shape != q.shape:
-                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
-        ascends = yg.size < 2 or yg[-1] >= yg[0]
-        flip = (side == 'upper') != bool(ascends)
-        res = self.ctx.contour_interior(q, bs, w=dA, f=g, periodic=ring, select=select, flip=flip, return_mask=return_mask)
-        nodes, area, integral = (None if v is None else _level_order(v, order) for v in res[:3])
-        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
-        c['contour'] = np.asarray(ccoord)
-        dims = tuple(lead) + ('contour',)
-        shape = tuple(lshape) + nodes.shape[1:2]
-        out = [lb.wrap(area.reshape(shape), dims, c, 'area', data), lb.wrap(nodes.reshape(shape), dims, c, 'nodes', data)]
-        if integral is not None:
-            out.append(lb.wrap(integral.reshape(shape), dims, c, 'integral', data))
+        p = self._piece_prep('cal_integral_inside_contours', contours, tracer, integrand, periodic, side, select, min_nx=2)
+        res = self.ctx.contour_interior(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, select=select, flip=p.flip, return_mask=return_mask)
+        out = [self._on_contours(p, name, v) for name, v in (('area', res[1]), ('nodes', res[0]), ('integral', res[2])) if v is not None]
         if return_mask:
-            m = _level_order(res[3], order[:, :, None, None])
-            cm = dict(c)
-            cm[self.dimEqV], cm[self._xdim] = np.asarray(dcoords[self.dimEqV]), np.asarray(dcoords[self._xdim])
-            out.append(lb.wrap(m.reshape(shape + (ny, nx)), dims + (self.dimEqV, self._xdim), cm, 'mask', data))
-        return lb.merge(out, data)
+            out.append(self._on_contours(p, 'mask', res[3], (self.dimEqV, self._xdim)))
+        return lb.merge(out, p.data)
 
     # ------------------------------------------------------------------ contour folds
     # an event as the facade returns it: where it sits, and what each tongue holds
@@ -1136,65 +1082,39 @@ class Contour2D(object):
         skipped, an infinite one makes that sum of that tongue NaN.  A NaN level, or a level without segments, gives an empty array.
         """
         who = 'cal_contour_folds'
-        if type(contours) in [int, list]:
-            contours = self.cal_contours(contours)
-        if select not in nat.Context.OVERTURN_SELECT:
-            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
+        p = self._piece_names(who, contours, select)
         if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, np.integer)) or gap < 0:
             raise Exception('%s: gap should be an int >= 0, not %r' % (who, gap))
-        data, dcoords = self._plane_dcoords(who, tracer)
-        yg, xg = (np.asarray(dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
-        period = self._x_period(periodic, xg, False, who, plain=True)
-        ring = period is not None
-        if select != 'all' and not ring:
-            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
-                            'periodic=True or the period, or select=\'all\'' % (who, select))
-        q, lead, lshape, coords = self._float_plane(data)
-        nslab, ny, nx = q.shape
+        self._piece_plane(p, tracer, periodic)
+        yg, xg, nx = p.yg, p.xg, p.nx
         if gap >= nx:
             raise Exception('%s: gap=%r should be below the %d columns of the plane' % (who, gap, nx))
-        bs, order, ccoord = self._sorted_levels(contours, nslab, lead, lshape)
-        dA = self._dA_array(ny, nx, nslab)[0]
-        if dA.ndim == 1:
-            dA = np.ascontiguousarray(np.broadcast_to(dA[:, None], (ny, nx)))
-        g = None
-        if integrand is not None:
-            g = self._integrand_plane(integrand)
-            if g.shape != q.shape:
-                g = np.ascontiguousarray(np.broadcast_to(np.asarray(g), q.shape))
-        ncross, row_lo, row_hi, cev, ec, tab = self.ctx.contour_folds(q, bs, w=dA, f=g, periodic=ring, select=select, gap=int(gap))
+        self._piece_levels(p)
+        self._piece_weights(p, integrand)
+        ncross, row_lo, row_hi, cev, ec, tab = self.ctx.contour_folds(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, select=select, gap=int(gap))
         # the columns, every level where the caller put it
-        ncross, row_lo, row_hi, cev = (_level_order(v, order[:, :, None]) for v in (ncross, row_lo, row_hi, cev))
-        rows = np.arange(yg.size)
-        ya, yb = np.interp(row_lo, rows, yg), np.interp(row_hi, rows, yg)
-        c = {d: np.asarray(coords[d]) for d in lead if d in coords}
-        c['contour'] = np.asarray(ccoord)
-        c[self._xdim] = np.asarray(dcoords[self._xdim])
-        dims = tuple(lead) + ('contour', self._xdim)
-        shape = tuple(lshape) + ncross.shape[1:]
-        cols = lb.merge([lb.wrap(v.reshape(shape), dims, c, name, data) for name, v in
-                         (('ncross', ncross), ('y_lo', np.minimum(ya, yb)), ('y_hi', np.maximum(ya, yb)), ('event', cev))], data)
+        y_lo, y_hi = self._rows_to_eq(yg, row_lo, row_hi)
+        cols = lb.merge([self._on_contours(p, name, v, (self._xdim,))
+                         for name, v in (('ncross', ncross), ('y_lo', y_lo), ('y_hi', y_hi), ('event', cev))], p.data)
         # the events
         rec = np.zeros(tab.size, dtype=self.FOLD_FIELDS)
         for k in ('c_west', 'c_east', 'ncol', 'ncross_max'):
             rec[k] = tab[k]
         rec['width'] = (tab['c_east'] - tab['c_west']) % nx + 1
         rec['x_west'], rec['x_east'] = xg[tab['c_west']], xg[tab['c_east']]
-        ea, eb = np.interp(tab['row_lo'], rows, yg), np.interp(tab['row_hi'], rows, yg)
-        rec['y_lo'], rec['y_hi'] = np.minimum(ea, eb), np.maximum(ea, eb)
+        rec['y_lo'], rec['y_hi'] = self._rows_to_eq(yg, tab['row_lo'], tab['row_hi'])
+        rows = np.arange(yg.size)
         with np.errstate(all='ignore'):
             mcol = tab['mx'] / tab['area']                       # the mean column east of c_west, per tongue
             mrow = tab['my'] / tab['area']
             for t, name in enumerate(('_under', '_over')):
                 rec['nodes' + name], rec['area' + name], rec['integral' + name] = tab['nodes'][:, t], tab['area'][:, t], tab['integral'][:, t]
                 rec['cy' + name] = np.interp(mrow[:, t], rows, yg)
-                rec['cx' + name] = self._fold_x(tab['c_west'] + mcol[:, t], xg, period)
+                rec['cx' + name] = self._fold_x(tab['c_west'] + mcol[:, t], xg, p.period)
             lean = mcol[:, 1] - mcol[:, 0]
             ok = ~np.isnan(tab['area']).any(axis=1) & (tab['area'] != 0.0).all(axis=1) & ~np.isnan(lean)
             rec['orientation'] = np.where(ok, np.sign(np.where(ok, lean, 0.0)), 0.0).astype(np.int8)
-        eoff = np.concatenate([[0], np.cumsum(ec.ravel().astype(np.int64))])
-        events = self._in_caller_order(order, lead, [rec[a:b].copy() for a, b in zip(eoff[:-1], eoff[1:])])[0]
-        return cols, events
+        return cols, self._in_caller_order(p.order, p.lead, self._per_range(rec, ec))[0]
 
     def cal_integral_inside_pieces(self, contours, tracer=None, integrand=None, periodic=False, side='upper'):
         """
@@ -1270,12 +1190,7 @@ class Contour2D(object):
         """
         p = self._piece_prep('cal_contour_piece_labels', contours, tracer, integrand, periodic, side)
         pc, tab, lab = self.ctx.contour_piece_labels(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, flip=p.flip)
-        c = {d: np.asarray(p.coords[d]) for d in p.lead if d in p.coords}
-        c['contour'] = np.asarray(p.ccoord)
-        c[self.dimEqV], c[self._xdim] = np.asarray(p.dcoords[self.dimEqV]), np.asarray(p.dcoords[self._xdim])
-        m = _level_order(lab, p.order[:, :, None, None])
-        dims = tuple(p.lead) + ('contour', self.dimEqV, self._xdim)
-        return self._ring_tables(p, pc, tab), lb.wrap(m.reshape(tuple(p.lshape) + m.shape[1:]), dims, c, 'labels', p.data)
+        return self._ring_tables(p, pc, tab), self._on_contours(p, 'labels', lab, (self.dimEqV, self._xdim))
 
     def cal_contour_piece_props(self, contours, fields=None, extremum=None, tracer=None, latlon=False, periodic=False, side='upper',
                                 centroid=True):
@@ -1532,26 +1447,53 @@ class Contour2D(object):
             v[par], at[par], key[par], has[par] = v[best], at[best], key[best], True
         return v, at
 
-    def _piece_prep(self, who, contours, tracer, integrand, periodic, side):
-        """what the six cal_*piece* methods do before their own call: contours from an int or list, `side`, the plane and its
-        coordinates, the period (at least three columns on a ring), the levels sorted, dA as a plane, the integrand, `flip`.
-        Returns them together: contours, data, dcoords, yg, xg, period, ring, q, lead, lshape, coords, nslab, ny, nx, bs, order,
-        ccoord, dA, g, flip, and `drop`: the fields of the ring tables that an absent integrand leaves out"""
-        p = types.SimpleNamespace()
+    def _piece_prep(self, who, contours, tracer, integrand, periodic, side, select=_ABSENT, min_nx=3):
+        """the opening of the methods that run on K12's records, in one call: what the six cal_*piece* methods and
+        cal_integral_inside_contours do before their own call.  Four steps, which report a call's defects in this order; a method
+        with a check of its own between two of them (cal_contour_folds' `gap`) or without weights (cal_contour_overturning) takes
+        the steps one by one.  Returns the namespace they fill: who, contours, select, side; data, dcoords, yg, xg, period, ring, q,
+        lead, lshape, coords, nslab, ny, nx; bs, order, ccoord; dA, g, flip, and `drop`: the fields of the ring tables that an
+        absent integrand leaves out"""
+        p = self._piece_names(who, contours, select, side)
+        self._piece_plane(p, tracer, periodic, min_nx)
+        self._piece_levels(p)
+        self._piece_weights(p, integrand)
+        return p
+
+    def _piece_names(self, who, contours, select=_ABSENT, side=_ABSENT):
+        """step 1: contours from an int or list, then the names `select` and `side`, where the method has them"""
+        p = types.SimpleNamespace(who=who, select=select, side=side)
         if type(contours) in [int, list]:
             contours = self.cal_contours(contours)
         p.contours = contours
-        if side not in ('upper', 'lower'):
+        if select is not _ABSENT and select not in nat.Context.OVERTURN_SELECT:
+            raise Exception('%s: select should be one of %s, not %r' % (who, sorted(nat.Context.OVERTURN_SELECT), select))
+        if side is not _ABSENT and side not in ('upper', 'lower'):
             raise Exception('%s: side should be \'upper\' or \'lower\', not %r' % (who, side))
+        return p
+
+    def _piece_plane(self, p, tracer, periodic, min_nx=2):
+        """step 2: the plane and its coordinates, the period, a selection that needs a ring, the values the kernels read, the
+        ring's fewest columns (`_x_period` asks for two; the ring methods for three)"""
+        who = p.who
         p.data, p.dcoords = self._plane_dcoords(who, tracer)
         p.yg, p.xg = (np.asarray(p.dcoords[d], dtype=np.float64) for d in (self.dimEqV, self._xdim))
         p.period = self._x_period(periodic, p.xg, False, who, plain=True)
         p.ring = p.period is not None
+        if p.select not in (_ABSENT, 'all') and not p.ring:
+            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
+                            'periodic=True or the period, or select=\'all\'' % (who, p.select))
         p.q, p.lead, p.lshape, p.coords = self._float_plane(p.data)
         p.nslab, p.ny, p.nx = p.q.shape
-        if p.ring and p.nx < 3:
+        if p.ring and p.nx < min_nx:
             raise Exception('%s: periodic needs at least three columns along the periodic dim' % who)
-        p.bs, p.order, p.ccoord = self._sorted_levels(contours, p.nslab, p.lead, p.lshape)
+
+    def _piece_levels(self, p):
+        """step 3: the levels sorted"""
+        p.bs, p.order, p.ccoord = self._sorted_levels(p.contours, p.nslab, p.lead, p.lshape)
+
+    def _piece_weights(self, p, integrand):
+        """step 4: dA as a plane, the integrand, `flip` from `side` (nothing reads it where the method has none)"""
         p.dA = self._dA_array(p.ny, p.nx, p.nslab)[0]
         if p.dA.ndim == 1:
             p.dA = np.ascontiguousarray(np.broadcast_to(p.dA[:, None], (p.ny, p.nx)))
@@ -1561,9 +1503,26 @@ class Contour2D(object):
             if p.g.shape != p.q.shape:
                 p.g = np.ascontiguousarray(np.broadcast_to(np.asarray(p.g), p.q.shape))
         ascends = p.yg.size < 2 or p.yg[-1] >= p.yg[0]
-        p.flip = (side == 'upper') != bool(ascends)
+        p.flip = (p.side == 'upper') != bool(ascends)
         p.drop = () if p.g is not None else ('sum_wf', 'net_wf')
-        return p
+
+    def _on_contours(self, p, name, v, trailing=()):
+        """the closing: a result (nslab, N, ...) per SORTED level -> the labelled array `name` over (lead dims, 'contour', the plane
+        dims `trailing`), every level where the caller put it"""
+        if not hasattr(p, 'cc'):                                 # built once per call: lb.wrap takes from it what the dims name
+            p.cc = {d: np.asarray(p.coords[d]) for d in p.lead if d in p.coords}
+            p.cc['contour'] = np.asarray(p.ccoord)
+            p.cc.update((d, np.asarray(p.dcoords[d])) for d in (self.dimEqV, self._xdim))
+        v = _level_order(v, p.order.reshape(p.order.shape + (1,) * (v.ndim - 2)))
+        return lb.wrap(v.reshape(tuple(p.lshape) + v.shape[1:]), tuple(p.lead) + ('contour',) + tuple(trailing), p.cc, name, p.data)
+
+    @staticmethod
+    def _rows_to_eq(yg, lo, hi):
+        """index-space rows `lo` <= `hi` -> (the smaller, the larger) of their places on the equivalent dim's coordinate `yg` as
+        given: np.interp of either, swapped where the coordinate descends"""
+        rows = np.arange(yg.size)
+        ya, yb = np.interp(lo, rows, yg), np.interp(hi, rows, yg)
+        return np.minimum(ya, yb), np.maximum(ya, yb)
 
     # the fields of the library's tables under the names this class returns them by
     _PIECE_NAMES = {'n_in': 'nodes', 'sum_w': 'area', 'sum_wf': 'integral', 'n_net': 'nodes_net', 'net_w': 'area_net',
