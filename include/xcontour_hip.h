@@ -1001,6 +1001,63 @@ int xc_contour_map(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64
                    const double* xp, int N, int xp_per_slab,
                    int nv, const double* const* fp, const int* fp_per_slab, void* const* out, int out_dtype);
 
+/* ------------------------------------------------------------------ K26 contour lengths at coarsened resolutions
+ * The reference's fractal-dimension script (tests/test_fractal.py:60-73) measures every contour at the ruler strides 1, 2, 4, ... twice:
+ * box-counting crossings (K9, all strides on one upload) and cal_contour_lengths of the block-averaged tracer, once per ratio.  The
+ * `coarsen` it calls ships with neither project; this rule is build-defined.  One call coarsens the tracer on the GPU for every ratio and
+ * hands each coarse plane to K10, which is unchanged.
+ * RULE       ratio r >= 1, plane (ny, nx) -> coarse plane (ny / r, nx / r) (integer division): blocks start at index 0, trailing rows
+ *            and columns that fill no block are dropped (trim).  Coarse node (I, J) is the mean of the fine block
+ *            [I r, I r + r) x [J r, J r + r).  Every fine value is converted to float64 first (a float32 tracer too); the coarse plane
+ *            is float64 always.  The block sum is sequential: each block row is summed left to right starting FROM its first element,
+ *            then the row sums are added top to bottom starting FROM the first; the mean is that sum divided once by double(r r).
+ *            Additions and one division, each rounded once: no multiplication that contraction could fuse, no reassociation.
+ * NaN        skipna == 0: a block with a NaN node is NaN (land stays land).  skipna != 0: NaN nodes are left out of the same order, a
+ *            row without a node left adds nothing, the divisor is the number of nodes used, a block with none is NaN.  An infinite node
+ *            is an ordinary value in both modes.
+ * COORDS     Yc[I] = (ycoord[I r] + ... + ycoord[I r + r - 1]) / double(r), the sum sequential from the first, in float64; Xc[J] the same.
+ *            These are the coordinates as K10 gets them (the caller's casts and deg2rad done); nothing is cast again.
+ * RATIO 1    the plane and the coordinates themselves: K10 reads the caller's buffers, nothing is copied.
+ * PERIODIC   the period passes through unchanged and nx % r == 0 is required: otherwise the seam cell would swallow the trimmed columns.
+ * xc_coarsen[_dev]: the kernel alone.  out is f64 [nslab][ny / r][nx / r].  XC_EBADARG: a NULL pointer, nslab, ny or nx < 1, a dtype
+ *            that is neither XC_F32 nor XC_F64, a ratio outside 1 .. XC_CSCALE_MAXRATIO or one that leaves no coarse node, more than
+ *            65535 slabs.
+ * xc_contour_lengths_scales[_dev]: ratios[nratio] is a HOST array in both forms, 1 <= nratio <= XC_CSCALE_MAXR, in any order, repeats
+ *            allowed.  period == 0.0: two free edges (as K15 has it), else periodic X.  out_len f64 [nratio][nslab][ncont]; out_nseg
+ *            the same shape, may be NULL.  For every ratio they are, bit for bit, what xc_contour_lengths (xc_contour_lengths_periodic)
+ *            returns for the coarse plane and the coarse coordinates of the rule above: the sums are K10's and as reproducible.
+ *            Levels, coordinates, period and radius obey K10's conditions: the host form checks them as xc_contour_lengths does
+ *            (XC_EEDGES for levels that do not ascend), the device form checks what it can without reading device memory.
+ * REFUSALS   XC_EBADARG, the message naming the ratio, before anything is launched or written: a ratio outside
+ *            1 .. XC_CSCALE_MAXRATIO; one that leaves fewer than 2 coarse rows; on a plain plane one that leaves fewer than 2 coarse
+ *            columns; on a periodic plane one that does not divide nx.  Also nratio outside 1 .. XC_CSCALE_MAXR.
+ * The coarse planes live in a workspace of the context sized by the largest of them and reused ratio after ratio on the context's
+ * stream.  xc_last_clen_geometry reports the K10 launch of the last ratio.                                                           */
+#define XC_CSCALE_MAXR 8
+#define XC_CSCALE_MAXRATIO 64
+int xc_coarsen_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int ratio, int skipna, double* out);
+int xc_coarsen(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int ratio, int skipna, double* out);
+int xc_contour_lengths_scales_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                  const double* ycoord, const double* xcoord, double period, double radius,
+                                  const int* ratios, int nratio, int skipna,
+                                  const double* contours, int ncont, int contours_per_slab, double* out_len, uint64_t* out_nseg);
+int xc_contour_lengths_scales(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                              const double* ycoord, const double* xcoord, double period, double radius,
+                              const int* ratios, int nratio, int skipna,
+                              const double* contours, int ncont, int contours_per_slab, double* out_len, uint64_t* out_nseg);
+/* how the last xc_coarsen(_dev) (nratio = 1) or xc_contour_lengths_scales(_dev) call launched k_coarsen, ratio by ratio in the caller's
+ * order: a tile is tile_y x tile_x COARSE nodes, one workgroup of `block` threads each, grid (tiles in x, tiles in y, slabs).  A ratio
+ * of 1 inside xc_contour_lengths_scales launches nothing: its grid and tile are 0.  All zero when the last such call failed.        */
+typedef struct xc_cscale_geometry {
+    int32_t q_dtype;    /* XC_F32 / XC_F64 */
+    int32_t nratio;
+    int32_t block;      /* threads per workgroup */
+    int32_t ratio[XC_CSCALE_MAXR];
+    int32_t grid_x[XC_CSCALE_MAXR], grid_y[XC_CSCALE_MAXR], grid_z[XC_CSCALE_MAXR];
+    int32_t tile_y[XC_CSCALE_MAXR], tile_x[XC_CSCALE_MAXR];
+} xc_cscale_geometry;
+int xc_last_cscale_geometry(xc_ctx* ctx, xc_cscale_geometry* out);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

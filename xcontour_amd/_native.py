@@ -71,6 +71,12 @@ class ClenGeometry(C.Structure):
                 ('ntile', _i64), ('bps', _i32), ('bps_rule', _i32), ('nslab', _i64)]
 
 
+class CscaleGeometry(C.Structure):
+    """xc_cscale_geometry: how the last xc_coarsen(_dev) / xc_contour_lengths_scales(_dev) call launched k_coarsen, ratio by ratio"""
+    _fields_ = [('q_dtype', _i32), ('nratio', _i32), ('block', _i32), ('ratio', _i32 * 8), ('grid_x', _i32 * 8), ('grid_y', _i32 * 8),
+                ('grid_z', _i32 * 8), ('tile_y', _i32 * 8), ('tile_x', _i32 * 8)]
+
+
 CLEN_BPS_RULES = {0: None, 1: 'share', 2: 'floor', 3: 'capacity', 4: 'ntile'}
 
 
@@ -218,6 +224,13 @@ PROTOTYPES = {
     'xc_last_hist_ms': (C.c_int, [_vp, C.POINTER(C.c_float)]),
     'xc_last_hist_variant': (C.c_int, [_vp, C.POINTER(HistVariant)]),
     'xc_last_clen_geometry': (C.c_int, [_vp, C.POINTER(ClenGeometry)]),
+    'xc_coarsen_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp]),
+    'xc_coarsen': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, C.c_int, C.c_int, _vp]),
+    'xc_contour_lengths_scales_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int,
+                                                _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_contour_lengths_scales': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, _vp, _f64, _f64, _vp, C.c_int, C.c_int,
+                                            _vp, C.c_int, C.c_int, _vp, _vp]),
+    'xc_last_cscale_geometry': (C.c_int, [_vp, C.POINTER(CscaleGeometry)]),
     'xc_set_hist_events': (C.c_int, [_vp, _vp, _vp]),
     'xc_comm_unique_id': (C.c_int, [_vp, _vp]),
     'xc_comm_init': (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
@@ -503,6 +516,8 @@ XC_PROPS_MAXF = 8                                               # fields one K21
 XC_CMAP_MAXV = 8                                                # value vectors one K25 call takes
 XC_CMAP_MAX_LDS_DOUBLES = 8192                                  # K25: (nv + 1) * N may not exceed this
 XC_CMAP_TILE = 1024                                             # K25: cells a workgroup takes per step
+XC_CSCALE_MAXR = 8                                              # ratios one K26 call takes
+XC_CSCALE_MAXRATIO = 64                                         # K26: the largest coarsening ratio
 _UNSET = object()
 
 
@@ -820,6 +835,18 @@ class Context(object):
         'bps_rule' named ('share', 'floor', 'capacity', 'ntile'; None when the plane has no cells) and 'q_dtype' a numpy dtype (None
         after a failed call: then every field is 0)"""
         return self._last_record(self.lib.xc_last_clen_geometry, ClenGeometry(), 'bps_rule', CLEN_BPS_RULES, 'N')
+
+    def last_cscale_geometry(self):
+        """how the last coarsen / contour_lengths_scales call (its last batch) launched k_coarsen (xc_last_cscale_geometry): a dict
+        with 'q_dtype' (None after a failed call: then everything is 0), 'block' and, per ratio in the caller's order, the lists
+        'ratio', 'grid' ((x, y, z) workgroups; zeros for a ratio of 1 inside contour_lengths_scales) and 'tile' ((rows, columns)
+        of coarse nodes one workgroup takes)"""
+        rec = CscaleGeometry()
+        self._check(self.lib.xc_last_cscale_geometry(self.handle, C.byref(rec)))
+        n = rec.nratio
+        return {'q_dtype': (np.dtype(np.float32 if rec.q_dtype == XC_F32 else np.float64) if n else None), 'block': rec.block,
+                'ratio': list(rec.ratio[:n]), 'grid': [(rec.grid_x[k], rec.grid_y[k], rec.grid_z[k]) for k in range(n)],
+                'tile': [(rec.tile_y[k], rec.tile_x[k]) for k in range(n)]}
 
     def single_stamps(self, enable=True):
         """diagnostics: (device pointer, slots) of the single-read kernel's phase stamps; enable=False frees them"""
@@ -1247,6 +1274,81 @@ class Context(object):
                                1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
             return lens, cnts
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
+
+    def coarsen(self, q, ratio, skipna=False):
+        """The block means of K26 alone (xc_coarsen).  q (nslab, ny, nx) f32/f64 (or a lazy stack) -> float64 (nslab, ny // ratio,
+        nx // ratio): blocks from index 0, trailing rows and columns dropped, every value promoted to float64, each block summed row
+        by row, left to right, then top to bottom, and divided once by ratio * ratio.  skipna: NaN nodes are left out and the divisor
+        is the number of nodes used (a block of none is NaN); else a block with a NaN node is NaN.  1 <= ratio <= XC_CSCALE_MAXRATIO.
+        A tracer with a device mirror (keep_resident) is read in place through the _dev entry point."""
+        q, (nslab, ny, nx) = _stack3(q)
+        qcode, r = dtype_code(q.dtype), int(ratio)
+        if not 1 <= r <= XC_CSCALE_MAXRATIO or ny // r < 1 or nx // r < 1:
+            raise XContourHipError(XC_EBADARG, 'xc_coarsen: ratio %d is outside 1 .. %d or leaves no coarse node of a (%d, %d) plane'
+                                   % (r, XC_CSCALE_MAXRATIO, ny, nx))
+        cny, cnx = ny // r, nx // r
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb = _stack_now(q, s0, s1)
+            qp = self._mirror(qb)
+            if qp:
+                with self._temporaries([], [n * cny * cnx * 8]) as (do,):
+                    self._check(self.lib.xc_coarsen_dev(self.handle, qp, qcode, n, ny, nx, r, 1 if skipna else 0, do.ptr))
+                    return do.download((n, cny, cnx), np.float64)
+            out = np.empty((n, cny, cnx), dtype=np.float64)
+            self._check(self.lib.xc_coarsen(self.handle, _ptr(qb), qcode, n, ny, nx, r, 1 if skipna else 0, _ptr(out)))
+            return out
+        return self._batched(nslab, ny * nx * q.dtype.itemsize + cny * cnx * 8, one)
+
+    def contour_lengths_scales(self, q, contours, ycoord, xcoord, ratios, radius=0.0, period=None, skipna=False):
+        """Contour lengths at coarsened resolutions (K26, xc_contour_lengths_scales): `contour_lengths` of the block-averaged tracer
+        for every ratio of `ratios` (1 .. XC_CSCALE_MAXR of them, each in 1 .. XC_CSCALE_MAXRATIO, any order), the tracer uploaded
+        once and coarsened on the GPU (`coarsen`'s rule; the coordinates take the same block means in float64).  q, contours, ycoord,
+        xcoord, radius, period as for `contour_lengths`; a ratio must leave two coarse rows and, on a plain plane, two coarse columns;
+        on a periodic one it must divide nx.  Returns (lengths f64 (nratio, nslab, N), segment counts uint64 (nratio, nslab, N)),
+        row k bit for bit what `contour_lengths` returns for the coarse plane and coordinates of ratios[k]."""
+        who = 'xc_contour_lengths_scales'
+        q, (nslab, ny, nx) = _stack3(q)
+        contours, per_slab, N = _levels_of(contours, nslab)
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, who)
+        if period is not None:
+            _check_finite(who, xcoord)
+            period = _check_period(period, xcoord, who)
+        ratios = [int(r) for r in ratios]
+        nr = len(ratios)
+        if not 1 <= nr <= XC_CSCALE_MAXR:
+            raise XContourHipError(XC_EBADARG, '%s: 1 to %d ratios, not %d' % (who, XC_CSCALE_MAXR, nr))
+        for r in ratios:
+            if not 1 <= r <= XC_CSCALE_MAXRATIO:
+                raise XContourHipError(XC_EBADARG, '%s: ratio %d is outside 1 .. %d' % (who, r, XC_CSCALE_MAXRATIO))
+            if ny // r < 2 or (period is None and nx // r < 2):
+                raise XContourHipError(XC_EBADARG, '%s: ratio %d leaves fewer than 2 coarse rows or columns of a (%d, %d) plane' % (who, r, ny, nx))
+            if period is not None and nx % r:
+                raise XContourHipError(XC_EBADARG, '%s: ratio %d does not divide nx = %d of a periodic plane' % (who, r, nx))
+        rr = (C.c_int * nr)(*ratios)
+        mid = (0.0 if period is None else period, float(radius), rr, nr, 1 if skipna else 0)
+
+        def one(s0, s1):
+            n = s1 - s0
+            qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
+            qp = self._mirror(qb)
+            if qp:
+                # the tracer is on the device already.  The device entry point trusts its caller, so what the host form checks itself
+                # (xc_forms.hip, the same texts) is checked here
+                _check_ascending(cb, who)
+                _check_finite(who, ycoord, xcoord)
+                with self._temporaries([ycoord, xcoord, cb], [nr * n * N * 8] * 2) as (dy, dx, dc, dl, dn):
+                    self._check(self.lib.xc_contour_lengths_scales_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *mid,
+                                                                       dc.ptr, N, 1 if per_slab else 0, dl.ptr, dn.ptr))
+                    return list(dl.download((nr, n, N), np.float64)), list(dn.download((nr, n, N), np.uint64))
+            lens = np.empty((nr, n, N), dtype=np.float64)
+            cnts = np.empty((nr, n, N), dtype=np.uint64)
+            self._check(self.lib.xc_contour_lengths_scales(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord),
+                                                           *mid, _ptr(cb), N, 1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
+            return list(lens), list(cnts)
+        lens, cnts = self._batched(nslab, ny * nx * q.dtype.itemsize, one)       # (lists over the ratios: `_join` joins each along the slabs)
+        return np.stack(lens), np.stack(cnts)
 
     def contour_line_integrals(self, q, f, contours, ycoord, xcoord, radius=0.0, period=None):
         """Integrals of a field along contours (K15, xc_contour_line_integrals).  q and contours, ycoord, xcoord, radius, period as for

@@ -786,6 +786,54 @@ class Contour2D(object):
         lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
         return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
 
+    def cal_contour_lengths_coarsened(self, contours, ratios, tracer=None, latlon=False, periodic=False, skipna=False):
+        """
+        cal_contour_lengths of the block-averaged tracer at every ratio of `ratios` (K26, xc_contour_lengths_scales): the
+        marching-squares half of the reference's fractal-dimension script (tests/test_fractal.py:60-73), whose
+        cal_contour_lengths(ctr, tracer=coarsen(tracer, ratio)) runs once per ruler.  The tracer goes to the GPU once and is
+        coarsened there: coarse node (I, J) of ratio r is the mean of the block [I r, I r + r) x [J r, J r + r) -- trailing
+        rows and columns dropped, every value in float64, summed row by row, left to right and top to bottom, divided once --
+        and its coordinates are the float64 block means of the coordinates K10 gets (after the float32 cast and deg2rad of
+        cal_contour_lengths; nothing is cast again).  skipna=True leaves NaN nodes out of a block and divides by the nodes
+        used; else a block with a NaN node is NaN.  `contours`, `tracer`, `latlon`, `periodic` as for cal_contour_lengths; a
+        ratio (1 .. 64) must leave two coarse rows and columns and, with `periodic`, divide the number of columns.  Ratio 1
+        is cal_contour_lengths itself, bit for bit.  Returns a list with one (..., contour) array in `self.dtype` per
+        ratio, or one array for a bare int; any number of ratios (eight per GPU call).
+        """
+        from collections.abc import Iterable
+        who = 'cal_contour_lengths_coarsened'
+        isiterable = isinstance(ratios, Iterable)
+        rs = [int(r) for r in ratios] if isiterable else [int(ratios)]
+        if not rs or min(rs) < 1 or max(rs) > nat.XC_CSCALE_MAXRATIO:
+            raise Exception('%s: ratios should be integers in 1 .. %d' % (who, nat.XC_CSCALE_MAXRATIO))
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        data, _, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
+        q, lead, lshape, coords = self._float_plane(data)
+        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
+        m = nat.XC_CSCALE_MAXR
+        lens = [l for k in range(0, len(rs), m)
+                for l in self.ctx.contour_lengths_scales(q, bs, fdef[0], fdef[1], rs[k:k + m], radius=Rearth if latlon else 0.0,
+                                                         period=period, skipna=skipna)[0]]
+        re = [self._wrap_contour(_level_order(l, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord) for l in lens]
+        return re if isiterable else re[0]
+
+    def coarsen(self, ratio, tracer=None, skipna=False):
+        """
+        The block-averaged tracer of cal_contour_lengths_coarsened as a labelled array (K26's kernel alone, xc_coarsen): what
+        the reference's script passes on as `tracerS`.  float64, the dims in the tracer's order, the other dims' coordinates
+        and the name kept; the two plane dims carry the float64 block means of their coordinates AS GIVEN (no float32 cast).
+        """
+        data = self.tracer if tracer is None else tracer
+        q, lead, lshape, coords = self._float_plane(data)
+        r = int(ratio)
+        tdims, g = self._in_dim_order(self.ctx.coarsen(q, r, skipna=skipna), data, lead, lshape)
+        coords = dict(coords)
+        for d in (self.dimEqV, self._xdim):
+            if d in coords:
+                coords[d] = _block_means(coords[d], r)
+        return lb.wrap(g, tdims, coords, lb.unwrap(data, lazy=True)[3], data)
+
     def _aligned_plane(self, who, integrand, data, shape):
         """a labelled integrand over the dims of `data` (the tracer a contour method works on) in any order -> its values as
         (S, ny, nx), the slabs in the tracer's order; `shape`: the tracer's own (S, ny, nx)"""
@@ -2275,6 +2323,24 @@ def trace_contour(data, dims, level, period=[None, None], periodic=False, join='
         raise Exception('find_contour expects a 2-D field on the dims %s' % [ydim, xdim])
     cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
     return cm.trace_contours(np.array([float(level)]), periodic=periodic, join=join)[0]
+
+
+def coarsen(data, dims, ratio, skipna=False):
+    """The block-averaged field of `Contour2D.coarsen` (K26) for a labelled array that has no Contour2D yet: `dims` = (row dim,
+    column dim) of the plane, any further dims lead.  Returns the coarse labelled array with block-mean coordinates."""
+    ydim, xdim = dims
+    return Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64).coarsen(ratio, skipna=skipna)
+
+
+def _block_means(c, r):
+    """float64 means of the blocks [I r, I r + r) of a 1-D coordinate, summed in order from each block's first value (K26's rule
+    for coordinates); the values that fill no block are dropped"""
+    b = np.asarray(c, dtype=np.float64)
+    b = b[:b.size // r * r].reshape(-1, r)
+    s = b[:, 0].copy()
+    for k in range(1, r):
+        s = s + b[:, k]
+    return s / float(r)
 
 
 def _level_order(vals, order):

@@ -214,6 +214,7 @@ int xc_destroy(xc_ctx* ctx)
     if (ctx->big) (void)hipFree(ctx->big);
     if (ctx->cpiece_ws) (void)hipFree(ctx->cpiece_ws);
     if (ctx->cpiece_acc) (void)hipFree(ctx->cpiece_acc);
+    if (ctx->cscale_ws) (void)hipFree(ctx->cscale_ws);
     if (ctx->ones) (void)hipFree(ctx->ones);
     for (int i = 0; i < 2; ++i) if (ctx->mmnext[i]) (void)hipFree(ctx->mmnext[i]);
     if (ctx->ev_hist0) (void)hipEventDestroy(ctx->ev_hist0);

@@ -347,6 +347,85 @@ int xc_last_clen_geometry(xc_ctx* ctx, xc_clen_geometry* out)
     return XC_OK;
 }
 
+// ------------------------------------------------------------------------------------ K26
+int xc_coarsen_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int ratio, int skipna, double* out)
+{
+    XC_CTX(ctx);
+    return launch_coarsen(ctx, q, q_dtype, nslab, ny, nx, ratio, skipna, out);
+}
+
+int xc_coarsen(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int ratio, int skipna, double* out)
+{
+    XC_CTX(ctx);
+    ctx->last_cscale = xc_cscale_geometry{};
+    if (!q || !out || nslab < 1 || ny < 1 || nx < 1 || !is_float(q_dtype) || ratio < 1 || ratio > XC_CSCALE_MAXRATIO || ny / ratio < 1 || nx / ratio < 1)
+        return launch_coarsen(ctx, q, q_dtype, nslab, ny, nx, ratio, skipna, out);       // (refused there, under its texts, before anything is staged)
+    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), ob = (size_t)nslab * (ny / ratio) * (nx / ratio) * 8;
+    Stage st(ctx); void* dq; double* dout;
+    XC_TRY(lay_stage(st, [&](Stage& s) { dq = s.take(qb); dout = s.out(out, ob); }));
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(launch_coarsen(ctx, pq, q_dtype, nslab, ny, nx, ratio, skipna, dout));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+// (the device form cannot read the coordinates or the levels: its caller vouches for them, as for K10's device forms)
+int xc_contour_lengths_scales_dev(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                  const double* ycoord, const double* xcoord, double period, double radius,
+                                  const int* ratios, int nratio, int skipna,
+                                  const double* contours, int ncont, int contours_per_slab, double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    return clen_recorded(ctx, launch_contour_lengths_scales(ctx, q, q_dtype, nslab, ny, nx, ycoord, xcoord, period, radius, ratios, nratio,
+                                                            skipna, contours, ncont, contours_per_slab, out_len, out_nseg));
+}
+
+int xc_contour_lengths_scales(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                              const double* ycoord, const double* xcoord, double period, double radius,
+                              const int* ratios, int nratio, int skipna,
+                              const double* contours, int ncont, int contours_per_slab, double* out_len, uint64_t* out_nseg)
+{
+    XC_CTX(ctx);
+    ctx->last_clen = xc_clen_geometry{};
+    ctx->last_cscale = xc_cscale_geometry{};
+    const char* who = "xc_contour_lengths_scales";
+    if (!q || !ycoord || !xcoord || !ratios || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
+        return fail(ctx, XC_EBADARG, std::string(who) + ": bad arguments");
+    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, std::string(who) + ": bad dtype");
+    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, std::string(who) + ": radius must be >= 0");
+    if (nslab > 65535) return fail(ctx, XC_EBADARG, std::string(who) + ": at most 65535 slabs per call");
+    XC_TRY(cscale_check_ratios(ctx, ny, nx, ratios, nratio, period != 0.0));
+    XC_TRY(check_coords(ctx, who, ycoord, ny, xcoord, nx));
+    if (period != 0.0 && !check_period(xcoord, nx, period))
+        return fail(ctx, XC_EBADARG, std::string(who) + ": period must be finite, of the sign of xcoord[nx-1] - xcoord[0] and longer than "
+                                     "that span, and nx >= 2 (0: X has two free edges)");
+    int64_t nc; XC_TRY(check_levels(ctx, who, contours, contours_per_slab, nslab, ncont, &nc));
+    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8;
+    const size_t ob = (size_t)nratio * nslab * ncont * 8;
+    Stage st(ctx); void* dq; double *dy, *dx, *dc, *dl; uint64_t* dn;
+    XC_TRY(lay_stage(st, [&](Stage& s) {
+        dq = s.take(qb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = s.take<double>(cb);
+        dl = s.out(out_len, ob); dn = s.out(out_nseg, ob);
+    }));
+    const void* pq;                                          // (a tracer with a device mirror is read where it is)
+    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
+    XC_TRY(flush_in(ctx));
+    XC_TRY(clen_recorded(ctx, launch_contour_lengths_scales(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, period, radius, ratios, nratio, skipna,
+                                                            dc, ncont, contours_per_slab, dl, dn)));
+    XC_TRY(st.deliver());
+    return xc_sync(ctx);
+}
+
+int xc_last_cscale_geometry(xc_ctx* ctx, xc_cscale_geometry* out)
+{
+    if (!ctx || !out) return fail(ctx, XC_EBADARG, "xc_last_cscale_geometry: bad arguments");
+    *out = ctx->last_cscale;
+    return XC_OK;
+}
+
 // ------------------------------------------------------------------------------------ K15
 // (the device form cannot read the coordinates: its caller vouches for a period's sign and length)
 int xc_contour_line_integrals_dev(xc_ctx* ctx, const void* q, int q_dtype, const void* f, int f_dtype, int64_t nslab, int64_t ny, int64_t nx,

@@ -94,6 +94,8 @@ struct xc_ctx {
     int last_keff_path = 0;     // last xc_keff_dev call: 0 min/max pass + histogram pass (two reads of the tracer), 1 the single-read kernel
     xc_hist_variant last_hist = {};   // last xc_hist(_dev) / xc_keff_dev call: the histogram instantiation and geometry launched (launch_three, launch_s4)
     xc_clen_geometry last_clen = {};  // last xc_contour_lengths(_dev) / xc_contour_line_integrals(_dev) call: K10's / K15's launch geometry
+    xc_cscale_geometry last_cscale = {};   // last xc_coarsen(_dev) / xc_contour_lengths_scales(_dev) call: K26's coarsen launches
+    void*  cscale_ws = nullptr;   size_t cscale_ws_bytes = 0;    // K26 (xc_cscale.hip): the coarse plane and its coordinates (K10 lays out `scratch`)
     // K13 (xc_cpiece.hip): the cap on the edge tables of one group of ranges, the grow-only workspaces and the last call's stage times
     size_t cpiece_cap = (size_t)1 << 30;
     void*  cpiece_ws = nullptr;   size_t cpiece_ws_bytes = 0;    // offsets, slots, the edge tables, labels and links
@@ -391,5 +393,12 @@ int launch_synth(xc_ctx* ctx, void* out, int q_dtype, int64_t nslab, int64_t ny,
 int launch_contour_map(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                        const double* xp, int N, int xp_per_slab, int nv, const double* const* fp, const int* fp_per_slab,
                        void* const* out, int out_dtype);
+// K26 (xc_cscale.hip): the coarsen kernel alone, and per ratio (a HOST array) coarsen + K10; everything else device pointers
+int cscale_check_ratios(xc_ctx* ctx, int64_t ny, int64_t nx, const int* ratios, int nratio, bool wrap);
+int launch_coarsen(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx, int ratio, int skipna, double* out);
+int launch_contour_lengths_scales(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
+                                  const double* ycoord, const double* xcoord, double period, double radius,
+                                  const int* ratios, int nratio, int skipna, const double* contours, int N, int contours_per_slab,
+                                  double* out_len, uint64_t* out_nseg);
 
 }  // namespace xc

@@ -110,6 +110,27 @@ def cartesian_metrics(y, dx):
     return np.full(ny, 1.0 / (2.0 * dx)), 1.0 / (y[jn] - y[js])
 
 
+def _fit_slope(x, y, axis=0):
+    """the least-squares slope of y against x along `axis`, closed form: sum(dx dy) / sum(dx dx) about the means"""
+    dx = x - x.mean(axis=axis, keepdims=True)
+    return (dx * (y - y.mean(axis=axis, keepdims=True))).sum(axis=axis) / (dx * dx).sum(axis=axis)
+
+
+def fractal_dimension(lengths, rulers, axis=0):
+    """The fractal dimension of contours measured with several rulers (`Contour2D.cal_contour_lengths_coarsened`,
+    `cal_contour_crossing`): the least-squares slope of log(lengths / rulers) against -log(rulers) along `axis` -- the reference
+    script's np.polyfit(x, y, 1)[0] (tests/test_fractal.py:90-115).  `rulers`: 1-D along `axis`, or anything that broadcasts against
+    `lengths`.  NaN wherever a point of the fit is NaN or not positive."""
+    L, R = np.asarray(lengths, dtype=np.float64), np.asarray(rulers, dtype=np.float64)
+    if R.ndim == 1 and L.ndim > 1:
+        R = R.reshape([-1 if a == axis % L.ndim else 1 for a in range(L.ndim)])
+    L, R = np.broadcast_arrays(L, R)
+    ok = (L > 0) & (R > 0)
+    L, R = np.where(ok, L, 1.0), np.where(ok, R, 1.0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(ok.all(axis=axis), _fit_slope(-np.log(R), np.log(L / R), axis), np.nan)
+
+
 def last_row_included(coord, right_edge='xhistogram'):
     """Does the row on the LAST (largest) coordinate value enter the A(Yeq) table?
 
