@@ -1058,6 +1058,51 @@ typedef struct xc_cscale_geometry {
 } xc_cscale_geometry;
 int xc_last_cscale_geometry(xc_ctx* ctx, xc_cscale_geometry* out);
 
+/* ------------------------------------------------------------------ K27 contour distance: how far every node lies from a contour
+ * K25 brings contour vectors back onto the plane; this brings the contour's GEOMETRY back: per node the distance to the selected pieces
+ * of a contour, and which segment and which piece is nearest -- the cross-contour coordinate of front-relative composites.  The
+ * reference's scripts trace a level and query a KD-tree on the host (tests/test_breaking.py, scipy.spatial).  Build-defined.
+ * Input as for K13, K16 and K17: count[nrange], e_from, e_to, pts where the K12 _dev entry points left them, with ny, nx, periodic of that
+ * call; ycoord[ny], xcoord[nx], period, radius with K13's meaning; select (0 all, 1 circumpolar, 2 main), pieces, rings, winding and the
+ * tie rule of the main ring are K16's.  A record end point (rho, gamma) maps to coordinates exactly as K13 maps it: np.interp on the
+ * coordinates, column nx of a periodic plane at xcoord[0] + period.  Node (r, c) is (ycoord[r], xcoord[c]).
+ *   refused with XC_EBADARG, nothing written: select != 0 with periodic == 0; 2 ny nx >= 2^31; a range of 2^31 segments or more; an edge
+ *     id (e_from or e_to) outside [0, 2 ny nx); a periodic plane without a finite, non-zero period or with nx < 2; radius > 0 with
+ *     periodic != 0 and a period that is not +-(double)(float)(2 pi) = float64(deg2rad(float32(+-360))) -- the plane is then no sphere;
+ *     a NaN max_dist.
+ *   PLANE (radius == 0).  Segment a -> b, node p, every operation rounded once, in this order:
+ *     u = b - a;  w = p - a;  uu = uy uy + ux ux;  t = 0 if uu == 0, else (wy uy + wx ux) / uu clamped to [0, 1];  f = a + t u;
+ *     d2 = (py - fy) (py - fy) + (px - fx) (px - fx).
+ *     With periodic != 0, d2 is the minimum over px, px + period and px - period.  dist = sqrt(min over the selected segments of d2).
+ *   SPHERE (radius > 0, coordinates in radians).  Points are unit vectors (cos y cos x, cos y sin x, sin y); a candidate is compared by
+ *     its squared chord c2, from arithmetic and sqrt alone:  n = a x b, nn = n . n;
+ *     nn == 0: c2 = |p - a|^2;  else if (a x p) . n >= 0 and (p x b) . n >= 0 (the foot lies on the arc): s2 = (p . n)^2 / nn,
+ *     c2 = 2 s2 / (1 + sqrt(1 - min(s2, 1)));  else c2 = min(|p - a|^2, |p - b|^2).  Products first, sums from the left.
+ *     dist = radius * 2 asin(min(1, sqrt(min c2) / 2)): one asin per node.  No image shifts.
+ *   per range, dense [nrange][ny][nx]:
+ *     dist  f64    +inf where the range has no selected segment, and where max_dist > 0 (finite) and the distance exceeds it; max_dist
+ *                  is in the units of dist; <= 0 or +inf: no cap
+ *     edge  int64  (may be NULL) the e_from of the nearest selected segment -- unique within a range --; among segments whose d2 / c2 are
+ *                  equal as bit patterns the smallest id; -1 wherever dist is infinite.  Its cell: row (id >> 1) / nx, column
+ *                  (id >> 1) % nx; K14's e_from_walk turns it into the position along the polyline
+ *     piece int64  (may be NULL) K13's first_edge of the piece of that segment; -1 where edge is
+ *   negate_mask uint8 [nrange][ny][nx] or NULL: where it is 1, a finite dist changes sign (K17's mask makes the distance signed).
+ *   min is order-free: no output depends on the order of the segments or of arrival, on the launch geometry or on the workspace cap.
+ *   On XC_OK every output is fully written, whatever the records hold; there is no capacity protocol.
+ * The selected segments of a range are binned by blocks of 32 x 32 cells; a workgroup owns 16 x 16 nodes and skips every block whose
+ * conservative lower bound on the distance to its nodes exceeds what its nodes already have (or max_dist): the result is that of the
+ * unpruned rule, bit for bit.  xc_set_cdist_prune(ctx, 0) visits every block (default 1; same result; for tests and A/B).
+ * The call waits for the stream three times (K12's counts; the word that says whether the ids were in range, before anything is
+ * written; the pair counts).  It works in K13's groups of ranges under K13's cap and in K13's workspace (xc_set_cpiece_workspace; the
+ * result does not depend on it).  xc_last_cdist_profile returns of the last call: with xc_set_kernel_timing on the device times in ms --
+ * ms[0] edge tables, doubling rounds and the selection, ms[1] the binning (count, scan, segment table, boxes), ms[2] the distance
+ * pass --, then the (node, segment) pairs it evaluated, the pairs an unpruned call evaluates, and the number of groups.            */
+int xc_contour_distance_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
+                            int64_t ny, int64_t nx, int periodic, int select, const double* ycoord, const double* xcoord, double period,
+                            double radius, double max_dist, const uint8_t* negate_mask, double* dist, int64_t* edge, int64_t* piece);
+int xc_set_cdist_prune(xc_ctx* ctx, int on);
+int xc_last_cdist_profile(xc_ctx* ctx, double* ms, int64_t* pairs_visited, int64_t* pairs_total, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

@@ -9,6 +9,7 @@
     python tools/kernel_times.py ncontours       Keff pipeline time per cfg2 slab against the number of contours
     python tools/kernel_times.py shapes          every kernel on awkward shapes (per-cell cost; catches pathological regimes)
     python tools/kernel_times.py single          every operator on ONE cfg2 slab next to its per-slab time in a 16-slab launch
+    python tools/kernel_times.py cdist           K27: distance to 1 / 3 contours, select all / main, pruned / unpruned: barotropic field, one cfg2-sized slab
 
 The oracle is imported only by the sub-commands that spot-check a result (it is test infrastructure).
 """
@@ -334,7 +335,37 @@ def cmd_single(ctx, T):
         emit(operator=name, one_slab_us=out[name, 1] * 1e3, per_slab_of_16_us=out[name, 16] / 16 * 1e3)
 
 
-CMDS = {'sort': cmd_sort, 'lwa': cmd_lwa, 'cross': cmd_cross, 'pipe': cmd_pipe, 'land': cmd_land, 'ncontours': cmd_ncontours, 'shapes': cmd_shapes, 'single': cmd_single}
+# ----------------------------------------------------------------------------------------------------------------- K27
+def cmd_cdist(ctx, T):
+    """xc_contour_distance_dev through Context.contour_distance, the stage times from the library's own stage timer"""
+    g = os.path.join(ROOT, 'tests', 'golden')
+    q = np.load(g + '/baro_q.npy').astype(np.float64); lat = np.load(g + '/baro_lat.npy'); lon = np.load(g + '/baro_lon.npy')
+    lat2 = np.linspace(-89.95, 89.95, NY)
+    pv = np.sin(np.deg2rad(lat2))[:, None] + 0.15 * np.sin(np.deg2rad(lat2) * 3)[:, None] * np.cos(np.deg2rad(np.arange(NX) * 0.1) * 5)[None, :]
+    planes = [('barotropic 256x512', q, lat, lon), ('cfg2-sized 1801x3600 wavy jet', pv, lat2, np.arange(NX) * 0.1)]
+    if os.environ.get('XC_CDIST_SMALL'):
+        planes = planes[:1]
+    ctx.set_kernel_timing(True)
+    for name, f, y, x in planes:
+        fy, fx = np.deg2rad(y.astype(np.float32)).astype(np.float64), np.deg2rad(x.astype(np.float32)).astype(np.float64)
+        for nlev in (1, 3):
+            lv = np.quantile(f, [0.5] if nlev == 1 else [0.3, 0.5, 0.7])
+            for select in ('all', 'main'):
+                for prune in (True, False):
+                    if not prune and f.size > 1 << 20 and not os.environ.get('XC_CDIST_UNPRUNED_BIG'):
+                        continue                                   # nodes x segments unpruned on the big plane: asked for by name
+                    ctx.set_cdist_prune(prune)
+                    t0 = time.perf_counter()
+                    ctx.contour_distance(f[None], lv, fy, fx, radius=6371.2e3, period=nat.XC_CDIST_RING, select=select)
+                    wall = time.perf_counter() - t0
+                    p = ctx.last_cdist_profile()
+                    emit(kernel='K27 contour_distance', plane=name, levels=nlev, select=select, pruned=prune, wall_ms_with_transfers=wall * 1e3,
+                         pair_share=p['pairs_visited'] / max(1, p['pairs_total']), **p)
+    ctx.set_cdist_prune(True)
+    ctx.set_kernel_timing(False)
+
+
+CMDS = {'sort': cmd_sort, 'lwa': cmd_lwa, 'cross': cmd_cross, 'pipe': cmd_pipe, 'land': cmd_land, 'ncontours': cmd_ncontours, 'shapes': cmd_shapes, 'single': cmd_single, 'cdist': cmd_cdist}
 
 if __name__ == '__main__':
     if len(sys.argv) < 2 or any(c not in CMDS for c in sys.argv[1:]):

@@ -177,6 +177,10 @@ PROTOTYPES = {
     'xc_contour_folds_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _i64,
                                        _vp, _vp, _vp, _vp, _i64, _vp] + [_vp] * 11),
     'xc_last_cfold_profile': (C.c_int, [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'xc_contour_distance_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _f64,
+                                          _vp, _vp, _vp, _vp]),
+    'xc_set_cdist_prune': (C.c_int, [_vp, C.c_int]),
+    'xc_last_cdist_profile': (C.c_int, [_vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int)]),
     'xc_contour_map_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
     'xc_contour_map': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
     'xc_contour_piece_interiors_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
@@ -518,6 +522,7 @@ XC_CMAP_MAX_LDS_DOUBLES = 8192                                  # K25: (nv + 1) 
 XC_CMAP_TILE = 1024                                             # K25: cells a workgroup takes per step
 XC_CSCALE_MAXR = 8                                              # ratios one K26 call takes
 XC_CSCALE_MAXRATIO = 64                                         # K26: the largest coarsening ratio
+XC_CDIST_RING = float(np.float64(np.deg2rad(np.float32(360.0))))   # K27: the one period of a sphere, float64(deg2rad(float32(360)))
 _UNSET = object()
 
 
@@ -1637,6 +1642,86 @@ class Context(object):
             nb = [n * N * 8, n * N * 8] + ([n * N * 8] if has_f else []) + ([n * N * ny * nx] if want_mask else [])
             return self._with_segment_records(periodic, qb, cb, interior, inputs=[v for v in (wb, fb) if v is not None], out_nbytes=nb)
         return self._batched(a.nslab, a.slab_bytes(N if want_mask else 0), one)
+
+    def set_cdist_prune(self, on):
+        """whether `contour_distance` skips the blocks of segments that cannot hold a node's nearest one (xc_set_cdist_prune;
+        default on; the result does not depend on it: for tests and A/B timing)"""
+        self._check(self.lib.xc_set_cdist_prune(self.handle, 1 if on else 0))
+
+    def last_cdist_profile(self):
+        """the last xc_contour_distance_dev call: dict(table_ms, binning_ms, distance_ms -- device times under
+        set_kernel_timing(True) --, pairs_visited, pairs_total: the (node, segment) pairs it evaluated / an unpruned call
+        evaluates, groups)"""
+        ms = (C.c_double * 3)()
+        pv, pt, g = _i64(0), _i64(0), C.c_int(0)
+        self._check(self.lib.xc_last_cdist_profile(self.handle, C.cast(ms, _vp), C.byref(pv), C.byref(pt), C.byref(g)))
+        return {'table_ms': ms[0], 'binning_ms': ms[1], 'distance_ms': ms[2], 'pairs_visited': pv.value, 'pairs_total': pt.value,
+                'groups': g.value}
+
+    def contour_distance(self, q, contours, ycoord, xcoord, radius=0.0, period=None, select='all', max_distance=None, signed=False,
+                         flip=False, return_nearest=False):
+        """How far every node lies from every contour (K27, xc_contour_distance_dev, on the device records of K12: the segment
+        records are never downloaded).  q, contours, ycoord, xcoord, radius and period as for `contour_pieces` (period not None: X
+        is a ring; with radius > 0 the period must be that of the sphere, XC_CDIST_RING, of either sign); select as for
+        `contour_overturning`.  Plane (radius 0): the Euclidean distance to the nearest point of the selected pieces' segments, on
+        a ring the shortest over the images one period either way; sphere: the great-circle distance times radius.
+        max_distance (None, <= 0 or inf: no cap): nodes farther away get +inf.  signed: the distance is negative where K17's
+        mask (`contour_interior` with the same select and `flip`) is set -- the mask is made and used on the device.  Returns dist
+        float64 (nslab, N, ny, nx), +inf where a contour has no selected segment[, edge, piece int64 (nslab, N, ny, nx): the e_from
+        of the nearest segment (ties: the smallest) and the first_edge of its piece, -1 where dist is infinite].  The contours are
+        taken in groups, so that the device holds no more output planes than one batch may stage."""
+        periodic = period is not None
+        a = _RecordArgs('xc_contour_distance', q, contours, select=select, periodic=periodic, min_nx=2, labels32=True)
+        ny, nx, N = a.ny, a.nx, a.N
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_distance')
+        _check_finite('xc_contour_distance', ycoord, xcoord)
+        radius = float(radius)
+        if not (np.isfinite(radius) and radius >= 0.0):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_distance: radius must be finite and >= 0')
+        if periodic:
+            period = _check_period(period, xcoord, 'xc_contour_distance')
+            if radius > 0.0 and abs(period) != XC_CDIST_RING:
+                raise XContourHipError(XC_EBADARG, 'xc_contour_distance: on the sphere the period is float64(deg2rad(float32(+-360))), '
+                                       'not %r: the plane is a sphere or none' % period)
+        cap = 0.0 if max_distance is None else float(max_distance)
+        if np.isnan(cap):
+            raise XContourHipError(XC_EBADARG, 'xc_contour_distance: max_distance is NaN')
+        signed, near = bool(signed), bool(return_nearest)
+        per_node = 8 + (16 if near else 0) + (1 if signed else 0)            # the bytes of one node's outputs, per contour
+        ncg = max(1, min(N, int(self.max_batch_bytes) // (ny * nx * per_node)))
+
+        def group(k0, k1):
+            g = a.on(a.q, np.ascontiguousarray(a.contours[..., k0:k1]))
+            g.N = Ng = k1 - k0
+
+            def distance(cnt, total, dn, ins, outs, recs):
+                n = cnt.shape[0]
+                (dy, dx), dd = ins, outs[0]
+                rec = [b.ptr for b in recs[:3]] if total else [None] * 3
+                head = (self.handle, cnt.size, dn.ptr, *rec, ny, nx, 1 if periodic else 0, int(a.sel))
+                dm = outs[-1] if signed else None
+                if signed:                                       # K17's mask, made where it is used
+                    self._check(self.lib.xc_contour_interior_dev(*head, 1 if flip else 0, Ng, None, 0, None, 0, outs[-3].ptr, outs[-2].ptr,
+                                                                 None, dm.ptr))
+                self._check(self.lib.xc_contour_distance_dev(*head, dy.ptr, dx.ptr, period if periodic else 0.0, radius, cap,
+                                                             dm.ptr if signed else None, dd.ptr, *([b.ptr for b in outs[1:3]] if near else [None] * 2)))
+                res = (dd.download((n, Ng, ny, nx), np.float64),)
+                return res + tuple(b.download((n, Ng, ny, nx), np.int64) for b in outs[1:3]) if near else res[0]
+
+            def one(s0, s1):
+                # beside K12's records: the coordinates, the planes of dist[, edge, piece], and for the sign K17's two sums and its mask
+                n = s1 - s0
+                plane = n * Ng * ny * nx
+                nb = [plane * 8] * (3 if near else 1) + ([n * Ng * 8, n * Ng * 8, plane] if signed else [])
+                return self._with_segment_records(periodic, *g.batch(s0, s1)[:2], distance, inputs=(ycoord, xcoord), out_nbytes=nb)
+            return self._batched(a.nslab, g.slab_bytes(Ng * per_node), one)
+
+        parts = [group(k0, min(N, k0 + ncg)) for k0 in range(0, N, ncg)]
+        if len(parts) == 1:
+            return parts[0]
+        if near:
+            return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(3))
+        return np.concatenate(parts, axis=1)
 
     # the per-event table of `contour_folds`: the library's record, the two tongues (0 under, 1 over) side by side
     FOLD_DTYPE = np.dtype([('c_west', np.int32), ('c_east', np.int32), ('ncol', np.int32), ('ncross_max', np.int32),

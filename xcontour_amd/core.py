@@ -1073,6 +1073,60 @@ class Contour2D(object):
             out.append(self._on_contours(p, 'mask', res[3], (self.dimEqV, self._xdim)))
         return lb.merge(out, p.data)
 
+    # ------------------------------------------------------------------ distance to contours
+    def cal_distance_to_contours(self, contours, tracer=None, latlon=False, periodic=False, select='all', side='upper', signed=False,
+                                 max_distance=None, return_nearest=False):
+        """
+        How far every node of the plane lies from every contour, computed on the GPU (K12's segments, K13's pieces, K16's
+        selection, K27, xc_contour_distance_dev): the cross-contour coordinate of front-relative and edge-relative composites
+        -- distance from the vortex edge, from a jet axis, from an SSH front; "within 500 km of the main ring" as a mask.  The
+        reference's scripts trace a level and query a KD-tree on the host (tests/test_breaking.py).  Build-defined.
+
+        `contours`, the coordinates (float32 cast; float32 radians with latlon=True), `periodic` and the order of the levels
+        are handled exactly as in cal_contour_pieces; `select` as in cal_contour_overturning ('circumpolar' and 'main' need
+        `periodic`).  The distance is to the nearest point of the selected pieces' segments: Euclidean in the coordinates'
+        units -- on a periodic plane the shortest over the images one period either way --, or with latlon=True the
+        great-circle distance in metres (Rearth; `periodic` is then True or 360).  `max_distance` (same units; None: no cap):
+        nodes farther away get NaN.  signed=True: negative on the `side` that cal_integral_inside_contours marks for the same
+        `select` (the mask is made and used on the device).
+
+        Returns a labelled (..., contour, Y, X) array in `self.dtype`, the levels where the caller put them; NaN where the
+        level is NaN or has no selected piece, and beyond `max_distance`.  With return_nearest=True a Dataset of `distance`,
+        `edge` (int64: the grid-edge id of the nearest segment's start -- its cell is row (id >> 1) // nx, column (id >> 1) % nx;
+        among equally near segments the smallest id) and `piece` (int64: the row of that segment's piece in the level's
+        cal_contour_pieces table); both -1 where the distance is NaN.  The Cartesian distance is bit-reproducible.
+
+        The result is N full planes per slab: this is meant for a few levels, not for a whole contour set.
+        """
+        who = 'cal_distance_to_contours'
+        p = self._piece_names(who, contours, select, side)
+        p.data, p.dcoords, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
+        if select != 'all' and period is None:
+            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
+                            'periodic=True or the period, or select=\'all\'' % (who, select))
+        p.q, p.lead, p.lshape, p.coords = self._float_plane(p.data)
+        p.bs, p.order, p.ccoord = self._sorted_levels(p.contours, p.q.shape[0], p.lead, p.lshape)
+        ascends = fdef[0].size < 2 or fdef[0][-1] >= fdef[0][0]
+        radius = Rearth if latlon else 0.0
+        res = self.ctx.contour_distance(p.q, p.bs, fdef[0], fdef[1], radius=radius, period=period, select=select,
+                                        max_distance=max_distance, signed=signed, flip=(side == 'upper') != bool(ascends),
+                                        return_nearest=return_nearest)
+        dist = res[0] if return_nearest else res
+        dist = np.where(np.isinf(dist), np.nan, dist).astype(self.dtype)
+        plane = (self.dimEqV, self._xdim)
+        if not return_nearest:
+            return self._on_contours(p, None, dist, plane)
+        edge, piece = res[1], res[2]
+        # the piece as the row of the level's cal_contour_pieces table: the tables list a range's pieces by ascending first_edge
+        pc, tab = self.ctx.contour_pieces(p.q, p.bs, fdef[0], fdef[1], radius=radius, period=period)
+        c, start = nat._scan(pc)
+        flat = piece.reshape((c.size,) + piece.shape[2:])
+        for r in range(c.size):
+            has = flat[r] >= 0
+            flat[r][has] = np.searchsorted(tab['first_edge'][start[r]:start[r] + c[r]], flat[r][has])
+        out = [self._on_contours(p, name, v, plane) for name, v in (('distance', dist), ('edge', edge), ('piece', piece))]
+        return lb.merge(out, p.data)
+
     # ------------------------------------------------------------------ contour folds
     # an event as the facade returns it: where it sits, and what each tongue holds
     FOLD_FIELDS = ([(k, np.int32) for k in ('c_west', 'c_east', 'ncol', 'ncross_max', 'width')] +
@@ -2323,6 +2377,23 @@ def trace_contour(data, dims, level, period=[None, None], periodic=False, join='
         raise Exception('find_contour expects a 2-D field on the dims %s' % [ydim, xdim])
     cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
     return cm.trace_contours(np.array([float(level)]), periodic=periodic, join=join)[0]
+
+
+def distance_to_contour(data, dims, level, period=[None, None], periodic=False, latlon=False):
+    """
+    The distance from every node of a 2-D labelled field to ONE of its levels, beside `find_contour` and in its call shape:
+    `dims` = [ydim, xdim], `period` must be [None, None], a periodic X direction goes through `periodic`.  Returns the labelled
+    (ydim, xdim) array Contour2D.cal_distance_to_contours([level], latlon=latlon, periodic=periodic) gives for that level, which
+    states the rule (coordinate units; metres with latlon=True; NaN when nothing is at that level).
+    """
+    if period is not None and any(p is not None for p in period):
+        raise NotImplementedError('distance_to_contour: period=%r is not supported (only [None, None]: use `periodic`)' % (period,))
+    ydim, xdim = dims
+    ddims = lb.unwrap(data, lazy=True)[1]
+    if len(ddims) != 2 or set(ddims) != {ydim, xdim}:
+        raise Exception('distance_to_contour expects a 2-D field on the dims %s' % [ydim, xdim])
+    cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
+    return cm.cal_distance_to_contours(np.array([float(level)]), latlon=latlon, periodic=periodic).isel({'contour': 0})
 
 
 def coarsen(data, dims, ratio, skipna=False):
