@@ -1075,7 +1075,7 @@ int xc_last_cscale_geometry(xc_ctx* ctx, xc_cscale_geometry* out);
  *     d2 = (py - fy) (py - fy) + (px - fx) (px - fx).
  *     With periodic != 0, d2 is the minimum over px, px + period and px - period.  dist = sqrt(min over the selected segments of d2).
  *   SPHERE (radius > 0, coordinates in radians).  Points are unit vectors (cos y cos x, cos y sin x, sin y); a candidate is compared by
- *     its squared chord c2, from arithmetic and sqrt alone:  n = a x b, nn = n . n;
+ *     its squared chord c2, from arithmetic and sqrt alone:  n = a x (b - a) (the difference first: a short arc keeps its direction), nn = n . n;
  *     nn == 0: c2 = |p - a|^2;  else if (a x p) . n >= 0 and (p x b) . n >= 0 (the foot lies on the arc): s2 = (p . n)^2 / nn,
  *     c2 = 2 s2 / (1 + sqrt(1 - min(s2, 1)));  else c2 = min(|p - a|^2, |p - b|^2).  Products first, sums from the left.
  *     dist = radius * 2 asin(min(1, sqrt(min c2) / 2)): one asin per node.  No image shifts.

@@ -12,7 +12,9 @@ d2 / c2 the smallest id wins.  `nodes` = (rows, cols) restricts the nodes to a s
   'no shift'     no periodic images on the plane
   'tie larger'   among equal d2 / c2 the LARGEST id wins
 pruned(): the tile / block walk of the kernel on the plane with the box-to-box bounds of xc_cdist_metric.h, or with
-bound='centre' -- the distance of the box centres, which is no lower bound and prunes too much.
+bound='centre' -- the distance of the box centres, which is no lower bound and prunes too much --, or with bound='gap skip ties'
+-- the right bound under a skip rule that is not strict, which loses a tying block.  It counts the pairs it visits as the kernel
+counts pairs_visited, and with nearest=True names the winner.
 """
 import numpy as np
 
@@ -22,6 +24,7 @@ SELECT = {'all': 0, 'circumpolar': 1, 'main': 2}
 WRONG = ('no clamp', 'line', 'no shift', 'tie larger')
 RING = float(np.float64(np.deg2rad(np.float32(360.0))))
 TILE, BLOCK = 16, 32
+NODES_AT_ONCE = 1024
 
 
 def selected(count, e_from, e_to, pts, ny, nx, periodic, select):
@@ -97,7 +100,7 @@ def _chord2(p, a):
 def c2_sphere(p, a, b, wrong=None):
     """unit vectors p (n, 1, 3) against arcs a -> b (1, m, 3) -> the squared chord (n, m)"""
     with np.errstate(all='ignore'):
-        n = _cross(a, b)
+        n = _cross(a, b - a)
         nn = _dot(n, n)
         ca, cb = _chord2(p, a), _chord2(p, b)
         pn = _dot(p, n)
@@ -123,6 +126,10 @@ def best_of(D, ids, wrong=None):
 def metric(py, px, Y1, X1, Y2, X2, periodic, period, radius, wrong=None, chunk=256):
     """nodes (n,) against segments (m,) of ascending ids 0 .. m-1 -> (min d2 / c2 (n,), the winner's position (n,), -1 without one)"""
     n, m = py.size, Y1.size
+    if n > NODES_AT_ONCE:                                    # (element-wise throughout: slabs of nodes that stay in the cache give the same bits)
+        parts = [metric(py[i:i + NODES_AT_ONCE], px[i:i + NODES_AT_ONCE], Y1, X1, Y2, X2, periodic, period, radius, wrong, chunk)
+                 for i in range(0, n, NODES_AT_ONCE)]
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
     best, at = np.full(n, np.inf), np.full(n, -1, dtype=np.int64)
     if radius > 0.0:
         P = unit(py, px)[:, None, :]
@@ -151,8 +158,10 @@ def finish(best, radius):
 
 
 def distance(count, e_from, e_to, pts, ny, nx, periodic, select, ycoord, xcoord, period=0.0, radius=0.0, max_dist=0.0,
-             negate_mask=None, wrong=None, nodes=None):
-    """-> dict(dist float64, edge, piece int64 (nrange, rows, cols), best: the winning d2 / c2)"""
+             negate_mask=None, wrong=None, nodes=None, winners=None):
+    """-> dict(dist float64, edge, piece int64 (nrange, rows, cols), best: the winning d2 / c2, at: the winner's place among the
+    range's selected segments).  winners: the result of an earlier call on the same records, select, nodes and rule -- its best and
+    at are taken over and only the cap and the mask, which come after the search, are applied anew."""
     ef = np.asarray(e_from, dtype=np.int64).ravel()
     ycoord, xcoord = np.asarray(ycoord, dtype=np.float64), np.asarray(xcoord, dtype=np.float64)
     period = np.float64(period if periodic else 0.0)
@@ -162,9 +171,12 @@ def distance(count, e_from, e_to, pts, ny, nx, periodic, select, ycoord, xcoord,
     sel = selected(count, e_from, e_to, pts, ny, nx, periodic, select)
     shape = (len(sel), rows.size, cols.size)
     out = dict(dist=np.full(shape, np.inf), edge=np.full(shape, -1, dtype=np.int64), piece=np.full(shape, -1, dtype=np.int64),
-               best=np.full(shape, np.inf))
+               best=np.full(shape, np.inf), at=np.full(shape, -1, dtype=np.int64))
     for r, (idx, first) in enumerate(sel):
-        best, at = metric(PY, PX, Y1[idx], X1[idx], Y2[idx], X2[idx], periodic, period, radius, wrong)
+        if winners is not None:
+            best, at = winners['best'][r].ravel(), winners['at'][r].ravel()
+        else:
+            best, at = metric(PY, PX, Y1[idx], X1[idx], Y2[idx], X2[idx], periodic, period, radius, wrong)
         d = finish(best, radius)
         has = at >= 0
         if max_dist > 0.0 and np.isfinite(max_dist):
@@ -175,6 +187,7 @@ def distance(count, e_from, e_to, pts, ny, nx, periodic, select, ycoord, xcoord,
             d = np.where(m & has, -d, d)
         out['dist'][r] = d.reshape(shape[1:])
         out['best'][r] = best.reshape(shape[1:])
+        out['at'][r] = at.reshape(shape[1:])
         out['edge'][r] = np.where(has, ef[idx][np.maximum(at, 0)] if idx.size else -1, -1).reshape(shape[1:])
         out['piece'][r] = np.where(has, first[np.maximum(at, 0)] if idx.size else -1, -1).reshape(shape[1:])
     return out
@@ -185,11 +198,14 @@ def same_bits(a, b):
     return a.shape == b.shape and bool((a.view(np.int64) == b.view(np.int64)).all())
 
 
-def pruned(e_from, pts, ny, nx, ycoord, xcoord, periodic=False, period=0.0, bound='gap'):
+def pruned(e_from, pts, ny, nx, ycoord, xcoord, periodic=False, period=0.0, bound='gap', nearest=False):
     """The kernel's walk on the plane for ONE range with every segment selected: tiles of TILE x TILE nodes, blocks of BLOCK x BLOCK
-    cells by the cell of e_from, a block's box the hull of a and fl(a + fl(b - a)); a tile takes W = the smallest far distance to
-    a block, then every block whose bound does not exceed min(W, its worst best-distance so far).  -> (min d2 (ny, nx), pairs
-    visited).  bound 'gap': the box-to-box gap; 'centre': the distance of the box centres (no lower bound)."""
+    cells by the cell of e_from, in ascending block order, a block's box the hull of a and fl(a + fl(b - a)); a tile takes W = the
+    smallest far distance to a block, then every block whose bound does not exceed min(W, its worst best-distance so far).
+    -> (min d2 (ny, nx), pairs visited), with `nearest` -> (min d2, pairs visited, the winner's id (ny, nx), its position in the
+    records as given (ny, nx)): among equal d2 the smallest id, as best_of; -1 without a winner.
+    bound 'gap': the box-to-box gap, a block skipped only where it EXCEEDS W; 'gap skip ties': the same gap, a block skipped where it
+    reaches W (a tying block is lost); 'centre': the distance of the box centres (no lower bound)."""
     ef = np.asarray(e_from, dtype=np.int64).ravel()
     ycoord, xcoord = np.asarray(ycoord, dtype=np.float64), np.asarray(xcoord, dtype=np.float64)
     period = np.float64(period if periodic else 0.0)
@@ -207,6 +223,7 @@ def pruned(e_from, pts, ny, nx, ycoord, xcoord, periodic=False, period=0.0, boun
     gap = lambda tlo, thi, blo, bhi: max(0.0, tlo - bhi, blo - thi)
     far = lambda tlo, thi, blo, bhi: max(thi - blo, bhi - tlo)
     out, pairs = np.full((ny, nx), np.inf), 0
+    edge, pos = np.full((ny, nx), -1, dtype=np.int64), np.full((ny, nx), -1, dtype=np.int64)
     for r0 in range(0, ny, TILE):
         for c0 in range(0, nx, TILE):
             rows, cols = np.arange(r0, min(ny, r0 + TILE)), np.arange(c0, min(nx, c0 + TILE))
@@ -221,14 +238,21 @@ def pruned(e_from, pts, ny, nx, ycoord, xcoord, periodic=False, period=0.0, boun
                 gy = gap(tyl, tyh, b[1], b[2])
                 return min(gy * gy + gap(lo, hi, b[3], b[4]) ** 2 for lo, hi in tx)
             W = min(min(far(tyl, tyh, b[1], b[2]) ** 2 + far(lo, hi, b[3], b[4]) ** 2 for lo, hi in tx) for b in blocks) if blocks else np.inf
-            best = np.full(PY.size, np.inf)
+            best, at = np.full(PY.size, np.inf), np.full(PY.size, -1, dtype=np.int64)
             for b in blocks:
-                if lower(b) > W:
+                lb = lower(b)
+                if lb >= W if bound == 'gap skip ties' else lb > W:
                     continue
                 g = b[0]
-                d, _ = metric(PY, PX, Y1[g], X1[g], Y2[g], X2[g], periodic, period, 0.0)
-                best = np.minimum(best, d)
+                d, j = metric(PY, PX, Y1[g], X1[g], Y2[g], X2[g], periodic, period, 0.0)
+                take = (j >= 0) & ((d < best) | ((d == best) & (g[np.maximum(j, 0)] < at)))       # (positions ascend with the ids)
+                best, at = np.where(take, d, best), np.where(take, g[np.maximum(j, 0)], at)
                 pairs += PY.size * g.size
                 W = min(W, best.max())
             out[np.ix_(rows, cols)] = best.reshape(rows.size, cols.size)
-    return out, pairs
+            if not blocks:
+                continue
+            has = at >= 0
+            edge[np.ix_(rows, cols)] = np.where(has, ef[np.maximum(at, 0)], -1).reshape(rows.size, cols.size)
+            pos[np.ix_(rows, cols)] = np.where(has, o[np.maximum(at, 0)], -1).reshape(rows.size, cols.size)
+    return (out, pairs, edge, pos) if nearest else (out, pairs)

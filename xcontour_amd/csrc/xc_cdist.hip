@@ -196,7 +196,7 @@ void k_cd_fill(int64_t n, long long s0, int64_t r0, long long E, int64_t ny, int
     if constexpr (SPHERE) {
         const double c1 = cos(y1), c2 = cos(y2);
         const CdV a = {__dmul_rn(c1, cos(x1)), __dmul_rn(c1, sin(x1)), sin(y1)}, b = {__dmul_rn(c2, cos(x2)), __dmul_rn(c2, sin(x2)), sin(y2)};
-        const CdV nv = cd_cross(a, b);
+        const CdV nv = cd_cross(a, {__dsub_rn(b.x, a.x), __dsub_rn(b.y, a.y), __dsub_rn(b.z, a.z)});     // (xc_cdist_metric.h: why not a x b)
         o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = b.x; o[4] = b.y; o[5] = b.z; o[6] = nv.x; o[7] = nv.y; o[8] = nv.z; o[9] = cd_dot(nv, nv);
     } else {
         const double uy = __dsub_rn(y2, y1), ux = __dsub_rn(x2, x1);

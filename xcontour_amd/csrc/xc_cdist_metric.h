@@ -39,7 +39,10 @@ __device__ __forceinline__ double cd_far(double tlo, double thi, double blo, dou
 __device__ __forceinline__ double cd_sq2(double y, double x) { return __dadd_rn(__dmul_rn(y, y), __dmul_rn(x, x)); }
 
 // ---------------------------------------------------------------- the unit sphere
-// A segment is stored as (a[3], b[3], n[3], nn): unit vectors (cos y cos x, cos y sin x, sin y), n = a x b, nn = n . n.  Node p:
+// A segment is stored as (a[3], b[3], n[3], nn): unit vectors (cos y cos x, cos y sin x, sin y), n = a x (b - a), nn = n . n.
+// (a x b in exact arithmetic; but the products of a x b are of size 1 and cancel down to |n|, the arc's length, which leaves n off its
+// direction by ulp(1) / |n| -- 1e-12 for a segment that cuts a cell's corner, more than the distance's stated accuracy --, whereas
+// b - a is exact for an arc that short and its products are of the size of |n| themselves.)  Node p:
 //   nn == 0:                                   c2 = |p - a|^2
 //   (a x p) . n >= 0 and (p x b) . n >= 0:     s2 = (p . n)^2 / nn;  c2 = 2 s2 / (1 + sqrt(1 - min(s2, 1)))   (the foot lies on the arc)
 //   else:                                      c2 = min(|p - a|^2, |p - b|^2)
