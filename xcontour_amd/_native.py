@@ -432,6 +432,26 @@ def _check_finite(who, *coords):
         raise XContourHipError(XC_EBADARG, '%s: coordinates must be finite' % who)
 
 
+def _lengths_open(q, contours, ycoord, xcoord, period, who, period_who=None, shaped=None):
+    """what K10, K15 and K26 open with, every refusal under the name it has in that form (`period_who`: the period's, where it is
+    another; shaped(shape): the form's own refusal behind the stack's, K15's integrand) -> (the stack, its shape, the levels,
+    per_slab, N, ycoord, xcoord, the checked period or None)"""
+    q, shape = _stack3(q)
+    if shaped is not None:
+        shaped(shape)
+    contours, per_slab, N = _levels_of(contours, shape[0])
+    ycoord, xcoord = _plane_coords(ycoord, xcoord, shape[1], shape[2], who)
+    if period is not None:
+        _check_finite(who, xcoord)
+        period = _check_period(period, xcoord, period_who or who)
+    return q, shape, contours, per_slab, N, ycoord, xcoord, period
+
+
+def _lengths_trusted(who, cb, ycoord, xcoord):
+    """what the device forms of K10, K15 and K26 trust their caller with, for a batch's levels `cb`: the checks, in their order"""
+    return (lambda: _check_ascending(cb, who), lambda: _check_finite(who, ycoord, xcoord))
+
+
 def _scan(counts):
     """counts of any shape and integer type -> (the counts, their exclusive scan -- where every range starts in the packed
     order): both flat int64"""
@@ -982,6 +1002,27 @@ class Context(object):
             for b in bufs:
                 b.free()
 
+    def _twin(self, f_host, f_dev, qb, inputs, outs, args, checks=()):
+        """One batch of a call that has a host form and a `_dev` twin with the same argument list.  qb: the batch of the tracer;
+        inputs: the further arrays in argument order (an absent optional one is None and stays None); outs: (shape, dtype) of every
+        output; args(tracer pointer, input pointers, output pointers) -> the arguments behind the handle, stated once for both forms.
+        A tracer with a device mirror is read in place: `checks` -- what the host form checks itself (xc_forms.hip, the same texts)
+        and the device form leaves to its caller -- are run, the inputs, then the outputs, are staged on the device, `f_dev` is called
+        and the outputs come down from device memory.  Else `f_host` gets host pointers.  Returns the outputs, a list."""
+        qp = self._mirror(qb)
+        if not qp:
+            res = [np.empty(shape, dtype=t) for shape, t in outs]
+            self._check(f_host(self.handle, *args(_ptr(qb), [_ptr(a) for a in inputs], [_ptr(o) for o in res])))
+            return res
+        for check in checks:
+            check()
+        there = [a for a in inputs if a is not None]
+        with self._temporaries(there, [int(np.prod(shape, dtype=np.int64)) * np.dtype(t).itemsize for shape, t in outs]) as bufs:
+            din, dout = iter(bufs[:len(there)]), bufs[len(there):]
+            ins = [None if a is None else next(din).ptr for a in inputs]
+            self._check(f_dev(self.handle, *args(qp, ins, [b.ptr for b in dout])))
+            return [b.download(shape, t) for b, (shape, t) in zip(dout, outs)]
+
     def _minmax_of(self, q):
         nslab = q.shape[0]
         out = np.empty((nslab, 2), dtype=np.float64)
@@ -1169,20 +1210,10 @@ class Context(object):
             n = s1 - s0
             qb, lb_ = _stack_now(q, s0, s1), _part(levels, 2, s0, s1)
             vb = [_part(v, 2, s0, s1) for v in values]
-            qp = self._mirror(qb)
-            if qp:
-                # the tracer is on the device already: only the vectors go up, and the planes come down from device memory.  The device
-                # entry point trusts its caller, so what the host form checks itself (xc_forms.hip, the same texts) is checked here
-                _check_map_levels(lb_)
-                with self._temporaries([lb_] + vb, [n * ny * nx * out_dtype.itemsize] * nv) as bufs:
-                    dl, dv, do = bufs[0], bufs[1:1 + nv], bufs[1 + nv:]
-                    self._check(self.lib.xc_contour_map_dev(self.handle, qp, qcode, n, ny, nx, dl.ptr, N, 1 if levels.ndim == 2 else 0, nv,
-                                                            (_vp * nv)(*[b.ptr for b in dv]), flags, (_vp * nv)(*[b.ptr for b in do]), ocode))
-                    return [b.download((n, ny, nx), out_dtype) for b in do]
-            outs = [np.empty((n, ny, nx), dtype=out_dtype) for _ in range(nv)]
-            self._check(self.lib.xc_contour_map(self.handle, _ptr(qb), qcode, n, ny, nx, _ptr(lb_), N, 1 if levels.ndim == 2 else 0, nv,
-                                                (_vp * nv)(*[_ptr(v) for v in vb]), flags, (_vp * nv)(*[_ptr(o) for o in outs]), ocode))
-            return outs
+            return self._twin(self.lib.xc_contour_map, self.lib.xc_contour_map_dev, qb, [lb_] + vb, [((n, ny, nx), out_dtype)] * nv,
+                              lambda pq, ins, outs: (pq, qcode, n, ny, nx, ins[0], N, 1 if levels.ndim == 2 else 0, nv,
+                                                     (_vp * nv)(*ins[1:]), flags, (_vp * nv)(*outs), ocode),
+                              checks=[lambda: _check_map_levels(lb_)])
         return self._batched(nslab, ny * nx * (q.dtype.itemsize + nv * out_dtype.itemsize), one)
 
     def crossing(self, q, contours, area, stride=1, pad_x=0, pad_mode='edge', full_width=False):
@@ -1251,33 +1282,19 @@ class Context(object):
         entry point.  period: None -- the plane has two free edges in X --, or the period of the X coordinate (in its units:
         radians when radius > 0; of the sign of xcoord[-1] - xcoord[0] and longer than that span): the cell between the last and
         the first column is traced too (xc_contour_lengths_periodic), as on the plane with column 0 appended one period on."""
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, per_slab, N = _levels_of(contours, nslab)
-        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_lengths')
-        if period is not None:
-            _check_finite('xc_contour_lengths', xcoord)
-            period = _check_period(period, xcoord, 'xc_contour_lengths_periodic')
-        f_host, f_dev, ring = self._ring_forms('xc_contour_lengths', period)
+        who = 'xc_contour_lengths'
+        q, (nslab, ny, nx), contours, per_slab, N, ycoord, xcoord, period = _lengths_open(q, contours, ycoord, xcoord, period, who,
+                                                                                           'xc_contour_lengths_periodic')
+        f_host, f_dev, ring = self._ring_forms(who, period)
         mid = ring + (float(radius),)
 
         def one(s0, s1):
             n = s1 - s0
             qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
-            qp = self._mirror(qb)
-            if qp:
-                # the tracer is on the device already: only the small arrays cross.  The device entry point trusts its caller, so
-                # what the host form checks itself (xc_forms.hip, the same texts) is checked here
-                _check_ascending(cb, 'xc_contour_lengths')
-                _check_finite('xc_contour_lengths', ycoord, xcoord)
-                with self._temporaries([ycoord, xcoord, cb], [n * N * 8, n * N * 8]) as (dy, dx, dc, dl, dn):
-                    self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *mid, dc.ptr, N,
-                                      1 if per_slab else 0, dl.ptr, dn.ptr))
-                    return dl.download((n, N), np.float64), dn.download((n, N), np.uint64)
-            lens = np.empty((n, N), dtype=np.float64)
-            cnts = np.empty((n, N), dtype=np.uint64)
-            self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord), *mid, _ptr(cb), N,
-                               1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
-            return lens, cnts
+            return tuple(self._twin(f_host, f_dev, qb, [ycoord, xcoord, cb], [((n, N), np.float64), ((n, N), np.uint64)],
+                                    lambda pq, ins, outs: (pq, dtype_code(q.dtype), n, ny, nx, *ins[:2], *mid, ins[2], N,
+                                                           1 if per_slab else 0, *outs),
+                                    checks=_lengths_trusted(who, cb, ycoord, xcoord)))
         return self._batched(nslab, ny * nx * q.dtype.itemsize, one)
 
     def coarsen(self, q, ratio, skipna=False):
@@ -1295,15 +1312,8 @@ class Context(object):
 
         def one(s0, s1):
             n = s1 - s0
-            qb = _stack_now(q, s0, s1)
-            qp = self._mirror(qb)
-            if qp:
-                with self._temporaries([], [n * cny * cnx * 8]) as (do,):
-                    self._check(self.lib.xc_coarsen_dev(self.handle, qp, qcode, n, ny, nx, r, 1 if skipna else 0, do.ptr))
-                    return do.download((n, cny, cnx), np.float64)
-            out = np.empty((n, cny, cnx), dtype=np.float64)
-            self._check(self.lib.xc_coarsen(self.handle, _ptr(qb), qcode, n, ny, nx, r, 1 if skipna else 0, _ptr(out)))
-            return out
+            return self._twin(self.lib.xc_coarsen, self.lib.xc_coarsen_dev, _stack_now(q, s0, s1), [], [((n, cny, cnx), np.float64)],
+                              lambda pq, ins, outs: (pq, qcode, n, ny, nx, r, 1 if skipna else 0, *outs))[0]
         return self._batched(nslab, ny * nx * q.dtype.itemsize + cny * cnx * 8, one)
 
     def contour_lengths_scales(self, q, contours, ycoord, xcoord, ratios, radius=0.0, period=None, skipna=False):
@@ -1314,12 +1324,7 @@ class Context(object):
         on a periodic one it must divide nx.  Returns (lengths f64 (nratio, nslab, N), segment counts uint64 (nratio, nslab, N)),
         row k bit for bit what `contour_lengths` returns for the coarse plane and coordinates of ratios[k]."""
         who = 'xc_contour_lengths_scales'
-        q, (nslab, ny, nx) = _stack3(q)
-        contours, per_slab, N = _levels_of(contours, nslab)
-        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, who)
-        if period is not None:
-            _check_finite(who, xcoord)
-            period = _check_period(period, xcoord, who)
+        q, (nslab, ny, nx), contours, per_slab, N, ycoord, xcoord, period = _lengths_open(q, contours, ycoord, xcoord, period, who)
         ratios = [int(r) for r in ratios]
         nr = len(ratios)
         if not 1 <= nr <= XC_CSCALE_MAXR:
@@ -1337,21 +1342,11 @@ class Context(object):
         def one(s0, s1):
             n = s1 - s0
             qb, cb = _stack_now(q, s0, s1), _part(contours, 2, s0, s1)
-            qp = self._mirror(qb)
-            if qp:
-                # the tracer is on the device already.  The device entry point trusts its caller, so what the host form checks itself
-                # (xc_forms.hip, the same texts) is checked here
-                _check_ascending(cb, who)
-                _check_finite(who, ycoord, xcoord)
-                with self._temporaries([ycoord, xcoord, cb], [nr * n * N * 8] * 2) as (dy, dx, dc, dl, dn):
-                    self._check(self.lib.xc_contour_lengths_scales_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *mid,
-                                                                       dc.ptr, N, 1 if per_slab else 0, dl.ptr, dn.ptr))
-                    return list(dl.download((nr, n, N), np.float64)), list(dn.download((nr, n, N), np.uint64))
-            lens = np.empty((nr, n, N), dtype=np.float64)
-            cnts = np.empty((nr, n, N), dtype=np.uint64)
-            self._check(self.lib.xc_contour_lengths_scales(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord),
-                                                           *mid, _ptr(cb), N, 1 if per_slab else 0, _ptr(lens), _ptr(cnts)))
-            return list(lens), list(cnts)
+            res = self._twin(self.lib.xc_contour_lengths_scales, self.lib.xc_contour_lengths_scales_dev, qb, [ycoord, xcoord, cb],
+                             [((nr, n, N), np.float64), ((nr, n, N), np.uint64)],
+                             lambda pq, ins, outs: (pq, dtype_code(q.dtype), n, ny, nx, *ins[:2], *mid, ins[2], N, 1 if per_slab else 0, *outs),
+                             checks=_lengths_trusted(who, cb, ycoord, xcoord))
+            return tuple(list(a) for a in res)
         lens, cnts = self._batched(nslab, ny * nx * q.dtype.itemsize, one)       # (lists over the ratios: `_join` joins each along the slabs)
         return np.stack(lens), np.stack(cnts)
 
@@ -1362,37 +1357,24 @@ class Context(object):
         whose F(u) and F(v) are not NaN, nseg their number.  Returns (integral f64 (nslab, N), length f64 (nslab, N), nseg uint64
         (nslab, N)); integral and length are NaN where the length is 0, and a level that met an infinite term has a NaN integral.
         A tracer with a device mirror (keep_resident) is read in place through the _dev entry point."""
-        q, (nslab, ny, nx) = _stack3(q)
+        who = 'xc_contour_line_integrals'
         f = _f48(_contig(f))
-        if tuple(f.shape) != (nslab, ny, nx):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_line_integrals: the integrand must have the shape of q, %r' % ((nslab, ny, nx),))
-        contours, per_slab, N = _levels_of(contours, nslab)
-        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_line_integrals')
-        if period is not None:
-            _check_finite('xc_contour_line_integrals', xcoord)
-            period = _check_period(period, xcoord, 'xc_contour_line_integrals')
+
+        def shaped(shape):
+            if tuple(f.shape) != shape:
+                raise XContourHipError(XC_EBADARG, '%s: the integrand must have the shape of q, %r' % (who, shape))
+        q, (nslab, ny, nx), contours, per_slab, N, ycoord, xcoord, period = _lengths_open(q, contours, ycoord, xcoord, period, who,
+                                                                                           shaped=shaped)
         mid = (0.0 if period is None else period, float(radius))
 
         def one(s0, s1):
             n = s1 - s0
             qb, fb, cb = _stack_now(q, s0, s1), _part(f, 3, s0, s1), _part(contours, 2, s0, s1)
-            qp = self._mirror(qb)
-            if qp:
-                # the tracer is on the device already.  The device entry point trusts its caller, so what the host form checks itself
-                # (xc_forms.hip, the same texts) is checked here
-                _check_ascending(cb, 'xc_contour_line_integrals')
-                _check_finite('xc_contour_line_integrals', ycoord, xcoord)
-                with self._temporaries([fb, ycoord, xcoord, cb], [n * N * 8] * 3) as (df, dy, dx, dc, di, dl, dn):
-                    self._check(self.lib.xc_contour_line_integrals_dev(self.handle, qp, dtype_code(q.dtype), df.ptr, dtype_code(f.dtype),
-                                                                       n, ny, nx, dy.ptr, dx.ptr, *mid, dc.ptr, N, 1 if per_slab else 0,
-                                                                       di.ptr, dl.ptr, dn.ptr))
-                    return di.download((n, N), np.float64), dl.download((n, N), np.float64), dn.download((n, N), np.uint64)
-            integ, lens = np.empty((n, N), dtype=np.float64), np.empty((n, N), dtype=np.float64)
-            cnts = np.empty((n, N), dtype=np.uint64)
-            self._check(self.lib.xc_contour_line_integrals(self.handle, _ptr(qb), dtype_code(q.dtype), _ptr(fb), dtype_code(f.dtype),
-                                                           n, ny, nx, _ptr(ycoord), _ptr(xcoord), *mid, _ptr(cb), N, 1 if per_slab else 0,
-                                                           _ptr(integ), _ptr(lens), _ptr(cnts)))
-            return integ, lens, cnts
+            return tuple(self._twin(self.lib.xc_contour_line_integrals, self.lib.xc_contour_line_integrals_dev, qb, [fb, ycoord, xcoord, cb],
+                                    [((n, N), np.float64), ((n, N), np.float64), ((n, N), np.uint64)],
+                                    lambda pq, ins, outs: (pq, dtype_code(q.dtype), ins[0], dtype_code(f.dtype), n, ny, nx, *ins[1:3], *mid,
+                                                           ins[3], N, 1 if per_slab else 0, *outs),
+                                    checks=_lengths_trusted(who, cb, ycoord, xcoord)))
         return self._batched(nslab, ny * nx * (q.dtype.itemsize + f.dtype.itemsize), one)
 
     @contextlib.contextmanager
@@ -1697,8 +1679,7 @@ class Context(object):
             def distance(cnt, total, dn, ins, outs, recs):
                 n = cnt.shape[0]
                 (dy, dx), dd = ins, outs[0]
-                rec = [b.ptr for b in recs[:3]] if total else [None] * 3
-                head = (self.handle, cnt.size, dn.ptr, *rec, ny, nx, 1 if periodic else 0, int(a.sel))
+                head = (self.handle, cnt.size, dn.ptr, *self._record_run(g, total, ins, recs)[0], ny, nx, 1 if periodic else 0, int(a.sel))
                 dm = outs[-1] if signed else None
                 if signed:                                       # K17's mask, made where it is used
                     self._check(self.lib.xc_contour_interior_dev(*head, 1 if flip else 0, Ng, None, 0, None, 0, outs[-3].ptr, outs[-2].ptr,
@@ -2231,21 +2212,9 @@ class Context(object):
         def one(s0, s1):
             n = s1 - s0
             qb, lb = _stack_now(q, s0, s1), _part(levels, 3, s0, s1)
-            qp = self._mirror(qb)
-            if qp:
-                # the tracer is on the device already: only the small arrays cross
-                with self._temporaries([ycoord, xcoord] + ([lb] if lb is not None else []), [n * ob] * 3) as bufs:
-                    dy, dx = bufs[:2]
-                    dl, de, dn = bufs[-3:]
-                    self._check(f_dev(self.handle, qp, dtype_code(q.dtype), n, ny, nx, dy.ptr, dx.ptr, *rest,
-                                      bufs[2].ptr if lb is not None else None, dl.ptr, de.ptr, dn.ptr))
-                    return (dl.download((n, nwy, nwx), np.float64), de.download((n, nwy, nwx), np.float64),
-                            dn.download((n, nwy, nwx), np.uint64))
-            lens, lvls = np.empty((n, nwy, nwx), dtype=np.float64), np.empty((n, nwy, nwx), dtype=np.float64)
-            cnts = np.empty((n, nwy, nwx), dtype=np.uint64)
-            self._check(f_host(self.handle, _ptr(qb), dtype_code(q.dtype), n, ny, nx, _ptr(ycoord), _ptr(xcoord), *rest, _ptr(lb),
-                               _ptr(lens), _ptr(lvls), _ptr(cnts)))
-            return lens, lvls, cnts
+            wins = (n, nwy, nwx)
+            return tuple(self._twin(f_host, f_dev, qb, [ycoord, xcoord, lb], [(wins, np.float64), (wins, np.float64), (wins, np.uint64)],
+                                    lambda pq, ins, outs: (pq, dtype_code(q.dtype), n, ny, nx, *ins[:2], *rest, ins[2], *outs)))
         return self._batched(nslab, ny * nx * q.dtype.itemsize + 4 * ob, one)
 
     def lwa(self, q, Q, coord, dA, dA_max, M=None, increase=True, part=0, mask_idx=None, variant=0, exact=None):

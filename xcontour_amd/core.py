@@ -757,6 +757,21 @@ class Contour2D(object):
             outs.append(out if lead else out[0])
         return outs
 
+    def _length_open(self, who, contours, tracer, latlon, periodic, integrand=_ABSENT):
+        """what the length family (K10, K15, K26) opens with, its steps in the order a call's defects are reported in -> (q, K15's
+        integrand on the tracer's dims or None, the sorted levels, fdef, the period, the radius, wrap: a (nslab, N) array per SORTED
+        level -> the labelled result in the caller's level order).  K27 has a refusal of its own between these steps and takes them itself"""
+        if type(contours) in [int, list]:
+            contours = self.cal_contours(contours)
+        data, _, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
+        q, lead, lshape, coords = self._float_plane(data)
+        g = None if integrand is _ABSENT else self._aligned_plane(who, integrand, data, q.shape)
+        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
+
+        def wrap(v):
+            return self._wrap_contour(_level_order(v, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
+        return q, g, bs, fdef, period, Rearth if latlon else 0.0, wrap
+
     def cal_contour_lengths(self, contours, tracer=None, latlon=False, periodic=False):
         """
         Perimeter of every contour (reference core.py:969-1014, _contour_lengths 1437-1487 and
@@ -778,13 +793,8 @@ class Contour2D(object):
         tracer's dim order (the reference would read longitude as latitude on an (X, Y) tracer).
         Sums are bit-reproducible.  Returns (..., contour) in `self.dtype`.
         """
-        if type(contours) in [int, list]:
-            contours = self.cal_contours(contours)
-        data, _, fdef, period = self._contour_coords('cal_contour_lengths', tracer, latlon, periodic)
-        q, lead, lshape, coords = self._float_plane(data)
-        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
-        lens, _ = self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
-        return self._wrap_contour(_level_order(lens, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
+        q, _, bs, fdef, period, radius, wrap = self._length_open('cal_contour_lengths', contours, tracer, latlon, periodic)
+        return wrap(self.ctx.contour_lengths(q, bs, fdef[0], fdef[1], radius=radius, period=period)[0])
 
     def cal_contour_lengths_coarsened(self, contours, ratios, tracer=None, latlon=False, periodic=False, skipna=False):
         """
@@ -806,16 +816,10 @@ class Contour2D(object):
         rs = [int(r) for r in ratios] if isiterable else [int(ratios)]
         if not rs or min(rs) < 1 or max(rs) > nat.XC_CSCALE_MAXRATIO:
             raise Exception('%s: ratios should be integers in 1 .. %d' % (who, nat.XC_CSCALE_MAXRATIO))
-        if type(contours) in [int, list]:
-            contours = self.cal_contours(contours)
-        data, _, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
-        q, lead, lshape, coords = self._float_plane(data)
-        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
+        q, _, bs, fdef, period, radius, wrap = self._length_open(who, contours, tracer, latlon, periodic)
         m = nat.XC_CSCALE_MAXR
-        lens = [l for k in range(0, len(rs), m)
-                for l in self.ctx.contour_lengths_scales(q, bs, fdef[0], fdef[1], rs[k:k + m], radius=Rearth if latlon else 0.0,
-                                                         period=period, skipna=skipna)[0]]
-        re = [self._wrap_contour(_level_order(l, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord) for l in lens]
+        re = [wrap(l) for k in range(0, len(rs), m)
+              for l in self.ctx.contour_lengths_scales(q, bs, fdef[0], fdef[1], rs[k:k + m], radius=radius, period=period, skipna=skipna)[0]]
         return re if isiterable else re[0]
 
     def coarsen(self, ratio, tracer=None, skipna=False):
@@ -854,16 +858,8 @@ class Contour2D(object):
     def _line_integrals(self, who, contours, integrand, tracer, latlon, periodic):
         """one K15 call behind cal_contour_line_integral / cal_contour_line_mean, opened like cal_contour_lengths -> (integral, length,
         both (nslab, N) float64 per SORTED level, wrap: such an array -> the labelled result in the caller's level order)"""
-        if type(contours) in [int, list]:
-            contours = self.cal_contours(contours)
-        data, _, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
-        q, lead, lshape, coords = self._float_plane(data)
-        g = self._aligned_plane(who, integrand, data, q.shape)
-        bs, order, ccoord = self._sorted_levels(contours, q.shape[0], lead, lshape)
-        integ, lens, _ = self.ctx.contour_line_integrals(q, g, bs, fdef[0], fdef[1], radius=Rearth if latlon else 0.0, period=period)
-
-        def wrap(v):
-            return self._wrap_contour(_level_order(v, order).astype(self.dtype), lead, lshape, coords, None, data, ccoord)
+        q, g, bs, fdef, period, radius, wrap = self._length_open(who, contours, tracer, latlon, periodic, integrand)
+        integ, lens, _ = self.ctx.contour_line_integrals(q, g, bs, fdef[0], fdef[1], radius=radius, period=period)
         return integ, lens, wrap
 
     def cal_contour_line_integral(self, contours, integrand, tracer=None, latlon=False, periodic=False, return_length=False):

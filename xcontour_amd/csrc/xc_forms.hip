@@ -68,38 +68,71 @@ static bool check_period(const double* xcoord, int64_t nx, double period)
     return std::fabs(period) > std::fabs(span);
 }
 
+// The frame the host forms of K10, K11, K15 and K26 share: the refusals they have in common, the byte sizes, and the tracer, the coordinates
+// and the levels staged.  A form names itself, calls the steps in the order its refusals are tested in, with its own refusals between them, and
+// states its further inputs, its outputs and its launch.
+struct Frame {
+    xc_ctx* ctx; const char* who; const void* q; int q_dtype; int64_t nslab, ny, nx; const double *ycoord, *xcoord;
+    const double* levels;                                    // null: none are staged (K11 at the window means)
+    Stage st; const void *pq = nullptr, *pf = nullptr; double *dy = nullptr, *dx = nullptr, *dc = nullptr;
+    Frame(xc_ctx* c, const char* w, const void* q_, int dt, int64_t ns, int64_t ny_, int64_t nx_, const double* y, const double* x, const double* lv)
+        : ctx(c), who(w), q(q_), q_dtype(dt), nslab(ns), ny(ny_), nx(nx_), ycoord(y), xcoord(x), levels(lv), st(c) {}
+    int refuse(const char* what) const { return fail(ctx, XC_EBADARG, std::string(who) + what); }
+    size_t cells() const { return (size_t)nslab * ny * nx; }
+    // the first two refusals.  more: the form's further pointers and counts are there; dtypes: its further dtypes are floats
+    int arguments(bool more, bool dtypes = true)
+    {
+        if (!more || !q || !ycoord || !xcoord || nslab < 1 || ny < 1 || nx < 1) return refuse(": bad arguments");
+        return dtypes && is_float(q_dtype) ? XC_OK : refuse(": bad dtype");
+    }
+    // finite coordinates, then the period of a ring under the form's own text
+    int coordinates(bool ring, double period, const char* text)
+    {
+        XC_TRY(check_coords(ctx, who, ycoord, ny, xcoord, nx));
+        return ring && !check_period(xcoord, nx, period) ? fail(ctx, XC_EBADARG, text) : XC_OK;
+    }
+    // the levels, one set or one per slab, ascend without NaN
+    int ascending(int ncont, int per_slab) { int64_t nc; return check_levels(ctx, who, levels, per_slab, nslab, ncont, &nc); }
+    // The arena laid out -- the tracer, a second plane `f` of `fb` bytes (K15's integrand; null: none), the coordinates, the levels of `lb`
+    // bytes, then what `outs` takes -- and the inputs staged and flushed: pq / pf, dy, dx, dc are what the launch reads
+    template <typename Lay> int stage(const void* f, size_t fb, size_t lb, Lay&& outs)
+    {
+        const size_t qb = cells() * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8;
+        void *dq, *df = nullptr;
+        XC_TRY(lay_stage(st, [&](Stage& s) {
+            dq = s.take(qb); if (f) df = s.take(fb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = levels ? s.take<double>(lb) : nullptr;
+            outs(s);
+        }));
+        XC_TRY(stage_in(ctx, dq, q, qb, &pq));              // (a tracer / integrand with a device mirror is read where it is)
+        if (f) XC_TRY(stage_in(ctx, df, f, fb, &pf));
+        XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb));
+        if (levels) XC_TRY(h2d(ctx, dc, levels, lb));
+        return flush_in(ctx);
+    }
+    // behind the launch: the results handed over
+    int finish(int launched) { XC_TRY(launched); XC_TRY(st.deliver()); return xc_sync(ctx); }
+};
+static size_t level_bytes(int contours_per_slab, int64_t nslab, int ncont) { return (size_t)(contours_per_slab ? nslab : 1) * ncont * 8; }
+
 // `periodic` == 0: `period` is not read and X does not wrap
 static int local_contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
                                       const double* ycoord, const double* xcoord, int periodic, double period, double radius,
                                       int64_t wy, int64_t wx, int64_t sy, int64_t sx, int64_t min_periods,
                                       const double* levels, double* out_len, double* out_level, uint64_t* out_nseg)
 {
-    if (!q || !ycoord || !xcoord || !out_len || nslab < 1 || ny < 1 || nx < 1)
-        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad arguments");
-    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: bad dtype");
+    Frame fr(ctx, "xc_local_contour_lengths", q, q_dtype, nslab, ny, nx, ycoord, xcoord, levels);
+    XC_TRY(fr.arguments(out_len));
     if (wy < 2 || wx < 2) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: the window must be at least 2 x 2 nodes");
     if (sy < 1 || sx < 1) return fail(ctx, XC_EBADARG, "xc_local_contour_lengths: strides must be >= 1");
-    XC_TRY(check_coords(ctx, "xc_local_contour_lengths", ycoord, ny, xcoord, nx));
-    if (periodic && !check_period(xcoord, nx, period))
-        return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: period must be finite, non-zero, of the sign of "
-                                     "xcoord[nx-1] - xcoord[0] and longer than that span, and nx >= 2");
+    XC_TRY(fr.coordinates(periodic, period, "xc_local_contour_lengths_periodic: period must be finite, non-zero, of the sign of "
+                                            "xcoord[nx-1] - xcoord[0] and longer than that span, and nx >= 2"));
     if (periodic && wx > nx)
         return fail(ctx, XC_EBADARG, "xc_local_contour_lengths_periodic: the window must not be wider than the ring (wx <= nx)");
-    const size_t nwin = (size_t)((ny + sy - 1) / sy) * (size_t)((nx + sx - 1) / sx);
-    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, ob = (size_t)nslab * nwin * 8;
-    Stage st(ctx); void* dq; double *dy, *dx, *dv, *dl, *de; uint64_t* dn;
-    XC_TRY(lay_stage(st, [&](Stage& s) {
-        dq = s.take(qb); dy = s.take<double>(yb); dx = s.take<double>(xb); dv = levels ? s.take<double>(ob) : nullptr;
-        dl = s.out(out_len, ob); de = s.out(out_level, ob); dn = s.out(out_nseg, ob);
-    }));
-    const void* pq;                                          // (a tracer with a device mirror is read where it is)
-    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb));
-    if (levels) XC_TRY(h2d(ctx, dv, levels, ob));
-    XC_TRY(flush_in(ctx));
-    XC_TRY(launch_local_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, periodic ? period : 0.0, radius, wy, wx, sy, sx, min_periods,
-                                        dv, dl, de, dn));
-    XC_TRY(st.deliver());
-    return xc_sync(ctx);
+    const size_t ob = (size_t)nslab * (size_t)((ny + sy - 1) / sy) * (size_t)((nx + sx - 1) / sx) * 8;        // (results and levels: one per window)
+    double *dl, *de; uint64_t* dn;
+    XC_TRY(fr.stage(nullptr, 0, ob, [&](Stage& s) { dl = s.out(out_len, ob); de = s.out(out_level, ob); dn = s.out(out_nseg, ob); }));
+    return fr.finish(launch_local_contour_lengths(ctx, fr.pq, q_dtype, nslab, ny, nx, fr.dy, fr.dx, periodic ? period : 0.0, radius, wy, wx, sy, sx,
+                                                  min_periods, fr.dc, dl, de, dn));
 }
 
 static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t nslab, int64_t ny, int64_t nx,
@@ -107,28 +140,16 @@ static int contour_lengths_host(xc_ctx* ctx, const void* q, int q_dtype, int64_t
                                 const double* contours, int ncont, int contours_per_slab,
                                 double* out_len, uint64_t* out_nseg)
 {
-    if (!q || !ycoord || !xcoord || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
-        return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad arguments");
-    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: bad dtype");
+    Frame fr(ctx, "xc_contour_lengths", q, q_dtype, nslab, ny, nx, ycoord, xcoord, contours);
+    XC_TRY(fr.arguments(contours && out_len && ncont >= 1));
     if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_lengths: radius must be >= 0");
-    XC_TRY(check_coords(ctx, "xc_contour_lengths", ycoord, ny, xcoord, nx));
-    if (periodic && !check_period(xcoord, nx, period))
-        return fail(ctx, XC_EBADARG, "xc_contour_lengths_periodic: period must be finite, non-zero, of the sign of xcoord[nx-1] - xcoord[0] "
-                                     "and longer than that span, and nx >= 2");
-    int64_t nc; XC_TRY(check_levels(ctx, "xc_contour_lengths", contours, contours_per_slab, nslab, ncont, &nc));
-    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype);
-    const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
-    Stage st(ctx); void* dq; double *dy, *dx, *dc, *dl; uint64_t* dn;
-    XC_TRY(lay_stage(st, [&](Stage& s) {
-        dq = s.take(qb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = s.take<double>(cb);
-        dl = s.out(out_len, ob); dn = s.out(out_nseg, ob);
-    }));
-    const void* pq;                                          // (a tracer with a device mirror is read where it is)
-    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
-    XC_TRY(flush_in(ctx));
-    XC_TRY(launch_contour_lengths(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, periodic ? period : 0.0, radius, dc, ncont, contours_per_slab, dl, dn));
-    XC_TRY(st.deliver());
-    return xc_sync(ctx);
+    XC_TRY(fr.coordinates(periodic, period, "xc_contour_lengths_periodic: period must be finite, non-zero, of the sign of xcoord[nx-1] - xcoord[0] "
+                                            "and longer than that span, and nx >= 2"));
+    XC_TRY(fr.ascending(ncont, contours_per_slab));
+    const size_t ob = (size_t)nslab * ncont * 8; double* dl; uint64_t* dn;
+    XC_TRY(fr.stage(nullptr, 0, level_bytes(contours_per_slab, nslab, ncont), [&](Stage& s) { dl = s.out(out_len, ob); dn = s.out(out_nseg, ob); }));
+    return fr.finish(launch_contour_lengths(ctx, fr.pq, q_dtype, nslab, ny, nx, fr.dy, fr.dx, periodic ? period : 0.0, radius, fr.dc, ncont,
+                                            contours_per_slab, dl, dn));
 }
 
 // period == 0.0: X has two free edges
@@ -137,30 +158,17 @@ static int contour_line_integrals_host(xc_ctx* ctx, const void* q, int q_dtype, 
                                        const double* contours, int ncont, int contours_per_slab,
                                        double* out_integral, double* out_length, uint64_t* out_nseg)
 {
-    if (!q || !f || !ycoord || !xcoord || !contours || !out_integral || !out_length || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
-        return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad arguments");
-    if (!is_float(q_dtype) || !is_float(f_dtype)) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: bad dtype");
+    Frame fr(ctx, "xc_contour_line_integrals", q, q_dtype, nslab, ny, nx, ycoord, xcoord, contours);
+    XC_TRY(fr.arguments(f && contours && out_integral && out_length && ncont >= 1, is_float(f_dtype)));
     if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: radius must be >= 0");
-    XC_TRY(check_coords(ctx, "xc_contour_line_integrals", ycoord, ny, xcoord, nx));
-    if (period != 0.0 && !check_period(xcoord, nx, period))
-        return fail(ctx, XC_EBADARG, "xc_contour_line_integrals: period must be 0, or finite, of the sign of xcoord[nx-1] - xcoord[0] "
-                                     "and longer than that span, and nx >= 2");
-    int64_t nc; XC_TRY(check_levels(ctx, "xc_contour_line_integrals", contours, contours_per_slab, nslab, ncont, &nc));
-    const size_t cells = (size_t)nslab * ny * nx, qb = cells * esize(q_dtype), fb = cells * esize(f_dtype);
-    const size_t yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8, ob = (size_t)nslab * ncont * 8;
-    Stage st(ctx); void *dq, *df; double *dy, *dx, *dc, *di, *dl; uint64_t* dn;
-    XC_TRY(lay_stage(st, [&](Stage& s) {
-        dq = s.take(qb); df = s.take(fb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = s.take<double>(cb);
-        di = s.out(out_integral, ob); dl = s.out(out_length, ob); dn = s.out(out_nseg, ob);
-    }));
-    const void* pq; const void* pf;                          // (a tracer / integrand with a device mirror is read where it is)
-    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(stage_in(ctx, df, f, fb, &pf));
-    XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
-    XC_TRY(flush_in(ctx));
-    XC_TRY(launch_contour_line_integrals(ctx, pq, q_dtype, pf, f_dtype, nslab, ny, nx, dy, dx, period, radius, dc, ncont, contours_per_slab,
-                                         di, dl, dn));
-    XC_TRY(st.deliver());
-    return xc_sync(ctx);
+    XC_TRY(fr.coordinates(period != 0.0, period, "xc_contour_line_integrals: period must be 0, or finite, of the sign of xcoord[nx-1] - xcoord[0] "
+                                                 "and longer than that span, and nx >= 2"));
+    XC_TRY(fr.ascending(ncont, contours_per_slab));
+    const size_t ob = (size_t)nslab * ncont * 8; double *di, *dl; uint64_t* dn;
+    XC_TRY(fr.stage(f, fr.cells() * esize(f_dtype), level_bytes(contours_per_slab, nslab, ncont), [&](Stage& s) {
+        di = s.out(out_integral, ob); dl = s.out(out_length, ob); dn = s.out(out_nseg, ob); }));
+    return fr.finish(launch_contour_line_integrals(ctx, fr.pq, q_dtype, fr.pf, f_dtype, nslab, ny, nx, fr.dy, fr.dx, period, radius, fr.dc, ncont,
+                                                   contours_per_slab, di, dl, dn));
 }
 
 extern "C" {
@@ -392,31 +400,18 @@ int xc_contour_lengths_scales(xc_ctx* ctx, const void* q, int q_dtype, int64_t n
     ctx->last_clen = xc_clen_geometry{};
     ctx->last_cscale = xc_cscale_geometry{};
     const char* who = "xc_contour_lengths_scales";
-    if (!q || !ycoord || !xcoord || !ratios || !contours || !out_len || nslab < 1 || ny < 1 || nx < 1 || ncont < 1)
-        return fail(ctx, XC_EBADARG, std::string(who) + ": bad arguments");
-    if (!is_float(q_dtype)) return fail(ctx, XC_EBADARG, std::string(who) + ": bad dtype");
-    if (!(radius >= 0.0)) return fail(ctx, XC_EBADARG, std::string(who) + ": radius must be >= 0");
-    if (nslab > 65535) return fail(ctx, XC_EBADARG, std::string(who) + ": at most 65535 slabs per call");
+    Frame fr(ctx, who, q, q_dtype, nslab, ny, nx, ycoord, xcoord, contours);
+    XC_TRY(fr.arguments(ratios && contours && out_len && ncont >= 1));
+    if (!(radius >= 0.0)) return fr.refuse(": radius must be >= 0");
+    if (nslab > 65535) return fr.refuse(": at most 65535 slabs per call");
     XC_TRY(cscale_check_ratios(ctx, ny, nx, ratios, nratio, period != 0.0));
-    XC_TRY(check_coords(ctx, who, ycoord, ny, xcoord, nx));
-    if (period != 0.0 && !check_period(xcoord, nx, period))
-        return fail(ctx, XC_EBADARG, std::string(who) + ": period must be finite, of the sign of xcoord[nx-1] - xcoord[0] and longer than "
-                                     "that span, and nx >= 2 (0: X has two free edges)");
-    int64_t nc; XC_TRY(check_levels(ctx, who, contours, contours_per_slab, nslab, ncont, &nc));
-    const size_t qb = (size_t)nslab * ny * nx * esize(q_dtype), yb = (size_t)ny * 8, xb = (size_t)nx * 8, cb = (size_t)nc * ncont * 8;
-    const size_t ob = (size_t)nratio * nslab * ncont * 8;
-    Stage st(ctx); void* dq; double *dy, *dx, *dc, *dl; uint64_t* dn;
-    XC_TRY(lay_stage(st, [&](Stage& s) {
-        dq = s.take(qb); dy = s.take<double>(yb); dx = s.take<double>(xb); dc = s.take<double>(cb);
-        dl = s.out(out_len, ob); dn = s.out(out_nseg, ob);
-    }));
-    const void* pq;                                          // (a tracer with a device mirror is read where it is)
-    XC_TRY(stage_in(ctx, dq, q, qb, &pq)); XC_TRY(h2d(ctx, dy, ycoord, yb)); XC_TRY(h2d(ctx, dx, xcoord, xb)); XC_TRY(h2d(ctx, dc, contours, cb));
-    XC_TRY(flush_in(ctx));
-    XC_TRY(clen_recorded(ctx, launch_contour_lengths_scales(ctx, pq, q_dtype, nslab, ny, nx, dy, dx, period, radius, ratios, nratio, skipna,
-                                                            dc, ncont, contours_per_slab, dl, dn)));
-    XC_TRY(st.deliver());
-    return xc_sync(ctx);
+    XC_TRY(fr.coordinates(period != 0.0, period, "xc_contour_lengths_scales: period must be finite, of the sign of xcoord[nx-1] - xcoord[0] and "
+                                                 "longer than that span, and nx >= 2 (0: X has two free edges)"));
+    XC_TRY(fr.ascending(ncont, contours_per_slab));
+    const size_t ob = (size_t)nratio * nslab * ncont * 8; double* dl; uint64_t* dn;
+    XC_TRY(fr.stage(nullptr, 0, level_bytes(contours_per_slab, nslab, ncont), [&](Stage& s) { dl = s.out(out_len, ob); dn = s.out(out_nseg, ob); }));
+    return fr.finish(clen_recorded(ctx, launch_contour_lengths_scales(ctx, fr.pq, q_dtype, nslab, ny, nx, fr.dy, fr.dx, period, radius, ratios, nratio,
+                                                                      skipna, fr.dc, ncont, contours_per_slab, dl, dn)));
 }
 
 int xc_last_cscale_geometry(xc_ctx* ctx, xc_cscale_geometry* out)
