@@ -1103,6 +1103,51 @@ int xc_contour_distance_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
 int xc_set_cdist_prune(xc_ctx* ctx, int on);
 int xc_last_cdist_profile(xc_ctx* ctx, double* ms, int64_t* pairs_visited, int64_t* pairs_total, int* groups);
 
+/* ------------------------------------------------------------------ K28 contour distance profile: composites by distance
+ * K27 gives the cross-contour coordinate as planes; the composite taken of it -- the mean of a field as a function of the (signed)
+ * distance from the vortex edge -- is a histogram of those planes with weights.  This call bins every node's distance where it is made
+ * and returns per (range, bin) the node count, the area and up to XC_PROPS_MAXF area-weighted field sums: no plane is an output, only
+ * nrange x M numbers per quantity reach the caller.  Build-defined.
+ * Input: everything xc_contour_distance_dev takes up to negate_mask, with the same meaning, limits and XC_EBADARG cases.  The distance d
+ * of a node is K27's, bit for bit: the same search (one device function serves both kernels), after sqrt / asin, after the cap, after
+ * the sign.  Further input:
+ *   nedge, edges HOST array float64[nedge]: the bin edges in the units of dist; finite, strictly ascending, 2 <= nedge <= 4097, else
+ *                XC_EBADARG before anything is written.  M = nedge - 1 bins per range.
+ *   ncont        ranges per slab: range = s ncont + k; nrange is a multiple of ncont, nrange / ncont (at most 65535) the slabs of w and
+ *                of the fields
+ *   w, w_per_slab  K17's weights: double[ny][nx], or [nslab][ny][nx] with w_per_slab != 0; NULL is weight 1
+ *   nf, f[nf], f_dtype[nf], f_per_slab[nf]  K21's fields: HOST arrays of device pointers, of XC_F32 / XC_F64, and of 0 (one plane
+ *                [ny][nx] for all slabs) or non-zero ([nslab][ny][nx]); 0 <= nf <= XC_PROPS_MAXF
+ *   BIN RULE     a node with distance d belongs to bin b when edges[b] <= d < edges[b + 1]; d == edges[M] belongs to bin M - 1
+ *                (np.histogram's rule).  A node with d = +inf (a range without selected segment; beyond max_dist) belongs nowhere, and
+ *                so does one outside [edges[0], edges[M]].
+ *   per (range, bin), dense:
+ *     nodes int64 [nrange][M]      the nodes of the bin, whatever their weights and fields hold
+ *     area  f64   [nrange][M]      the sum of w over them
+ *     sums  f64   [nf][nrange][M]  the sum of w f_m, each product rounded once (float32 fields widened first); NULL exactly when nf == 0
+ *     flags int32 [nrange][1 + nf] channel 0 the area, 1 + m field m: 1 where a term of that channel of that range was not finite
+ *   The sums are K17's: the exact sum of the float64 terms rounded once, a window of 160 bits under 2^top, top = 12 + the frexp exponent
+ *   of max |w| (max |w f_m|) over the finite values of the range's slab.  A NaN term is skipped; a +-inf term makes THAT channel of THAT
+ *   bin NaN (and sets the flag of its range and channel), and no other.  No output depends on the order of the segments or of arrival,
+ *   on the launch geometry, on the workspace cap, on pruning or on the path below.  Ranges without segments have zero counts and sums.
+ * The tile pass is K27's with an epilogue: a workgroup's 16 x 16 nodes find their bins by binary search (the edges in LDS up to 512 of
+ * them, else through the cache); where they span at most 16 bins the terms are added to a window of LDS words with LDS integer atomics
+ * and every non-zero word is flushed with one global 64-bit atomic; a wider tile adds every term to the global words.  The window and
+ * the edges live in the LDS the search staged its segments in.  xc_set_cdprofile_global(ctx, 1) sends every tile down the global path
+ * (default 0; same result; for tests and A/B); xc_set_cdist_prune applies as in K27.
+ * Stream waits, groups and workspace are K27's; the words take 40 (1 + nf) + 12 bytes per (range, bin).  xc_last_cdprofile_profile
+ * returns of the last call: with xc_set_kernel_timing on the device times in ms -- ms[0] to ms[2] as xc_last_cdist_profile (the
+ * distance pass with the accumulation), ms[3] the bounds of the windows, ms[4] the finish pass --, K27's pair counts, the tiles that
+ * took the LDS window and the tiles that took the global path (tiles without a node in any bin count in neither), and the groups.   */
+int xc_contour_distance_profile_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                                    const double* pts, int64_t ny, int64_t nx, int periodic, int select, const double* ycoord,
+                                    const double* xcoord, double period, double radius, double max_dist, const uint8_t* negate_mask,
+                                    int nedge, const double* edges, int ncont, const double* w, int w_per_slab, int nf, const void* const* f,
+                                    const int* f_dtype, const int* f_per_slab, int64_t* nodes, double* area, double* sums, int32_t* flags);
+int xc_set_cdprofile_global(xc_ctx* ctx, int on);
+int xc_last_cdprofile_profile(xc_ctx* ctx, double* ms, int64_t* pairs_visited, int64_t* pairs_total, int64_t* tiles_window,
+                              int64_t* tiles_global, int* groups);
+
 /* ------------------------------------------------------------------ fused, batched Keff pipeline
  * The reference's call sequence SURVEY 3.1 steps 2-10 for a batch of slabs resident
  * in HBM: min/max -> levels/edges -> one histogram pass (dA, |grad q|^2 dA or grdS dA)

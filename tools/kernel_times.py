@@ -9,6 +9,7 @@
     python tools/kernel_times.py ncontours       Keff pipeline time per cfg2 slab against the number of contours
     python tools/kernel_times.py shapes          every kernel on awkward shapes (per-cell cost; catches pathological regimes)
     python tools/kernel_times.py single          every operator on ONE cfg2 slab next to its per-slab time in a 16-slab launch
+    python tools/kernel_times.py cdprofile       K28: composites by distance, 16 bins, 2 fields, beside K27 + np.histogram on the host: barotropic field with 3 / 41 levels, one cfg2-sized slab with 1
     python tools/kernel_times.py cdist           K27: distance to 1 / 3 contours, select all / main, pruned / unpruned: barotropic field, one cfg2-sized slab
 
 The oracle is imported only by the sub-commands that spot-check a result (it is test infrastructure).
@@ -365,7 +366,49 @@ def cmd_cdist(ctx, T):
     ctx.set_kernel_timing(False)
 
 
-CMDS = {'sort': cmd_sort, 'lwa': cmd_lwa, 'cross': cmd_cross, 'pipe': cmd_pipe, 'land': cmd_land, 'ncontours': cmd_ncontours, 'shapes': cmd_shapes, 'single': cmd_single, 'cdist': cmd_cdist}
+# ----------------------------------------------------------------------------------------------------------------- K28
+def cmd_cdprofile(ctx, T):
+    """xc_contour_distance_profile_dev through Context.contour_distance_profile (each call twice: the second is the one reported), and for
+    the same inputs what it replaces: Context.contour_distance, its planes downloaded, np.histogram with weights per level and field"""
+    g = os.path.join(ROOT, 'tests', 'golden')
+    q = np.load(g + '/baro_q.npy').astype(np.float64); lat = np.load(g + '/baro_lat.npy'); lon = np.load(g + '/baro_lon.npy')
+    lat2 = np.linspace(-89.95, 89.95, NY)
+    pv = np.sin(np.deg2rad(lat2))[:, None] + 0.15 * np.sin(np.deg2rad(lat2) * 3)[:, None] * np.cos(np.deg2rad(np.arange(NX) * 0.1) * 5)[None, :]
+    cases = [('barotropic 256x512', q, lat, lon, 3), ('barotropic 256x512', q, lat, lon, 41)]
+    if not os.environ.get('XC_CDIST_SMALL'):
+        cases.append(('cfg2-sized 1801x3600 wavy jet', pv, lat2, np.arange(NX) * 0.1, 1))
+    edges = np.linspace(0.0, 3.0e6, 17)
+    ctx.set_kernel_timing(True)
+    for name, f, y, x, nlev in cases:
+        fy, fx = np.deg2rad(y.astype(np.float32)).astype(np.float64), np.deg2rad(x.astype(np.float32)).astype(np.float64)
+        lv = np.quantile(f, [0.5] if nlev == 1 else np.linspace(0.3, 0.7, nlev))
+        w = np.ascontiguousarray(np.broadcast_to(np.cos(np.deg2rad(y))[:, None], f.shape))
+        flds = [f, f * f]
+        kw = dict(radius=6371.2e3, period=nat.XC_CDIST_RING, select='all')
+        for rep in range(2):
+            t0 = time.perf_counter()
+            ctx.contour_distance_profile(f[None], lv, fy, fx, edges, w=w, fields=flds, **kw)
+            wall = time.perf_counter() - t0
+        p = ctx.last_cdprofile_profile()
+        for rep in range(2):
+            t0 = time.perf_counter()
+            d = ctx.contour_distance(f[None], lv, fy, fx, **kw)
+            t1 = time.perf_counter()
+            for k in range(nlev):
+                for wt in [w] + [w * v for v in flds]:
+                    np.histogram(d[0, k].ravel(), bins=edges, weights=wt.ravel())
+            t2 = time.perf_counter()
+        p27 = ctx.last_cdist_profile()
+        tiles = max(1, p['tiles_window'] + p['tiles_global'])
+        emit(kernel='K28 contour_distance_profile', plane=name, levels=nlev, bins=edges.size - 1, fields=len(flds), wall_ms_with_transfers=wall * 1e3,
+             k27_wall_ms_with_transfers=(t1 - t0) * 1e3, host_histogram_ms=(t2 - t1) * 1e3, k27_distance_ms=p27['distance_ms'],
+             distance_ratio_k28_over_k27=p['distance_ms'] / p27['distance_ms'] if p27['distance_ms'] else float('nan'),
+             window_share=p['tiles_window'] / tiles, global_share=p['tiles_global'] / tiles, **p)
+    ctx.set_kernel_timing(False)
+
+
+CMDS = {'sort': cmd_sort, 'lwa': cmd_lwa, 'cross': cmd_cross, 'pipe': cmd_pipe, 'land': cmd_land, 'ncontours': cmd_ncontours, 'shapes': cmd_shapes, 'single': cmd_single, 'cdist': cmd_cdist,
+        'cdprofile': cmd_cdprofile}
 
 if __name__ == '__main__':
     if len(sys.argv) < 2 or any(c not in CMDS for c in sys.argv[1:]):

@@ -8,7 +8,7 @@ The cell-touching work (min/max, weighted multi-channel histogram with in-kernel
 hand-written HIP kernels reached through the C ABI of include/xcontour_hip.h.
 There is no CPU fallback.
 """
-from .core import Contour2D, Table, find_contour, trace_contour, contour_polylines, coarsen, distance_to_contour
+from .core import Contour2D, Table, find_contour, trace_contour, contour_polylines, coarsen, distance_to_contour, distance_profile
 from .utils import equivalent_latitudes, latitude_lengths_at, cell_area, grad_metrics, \
     cartesian_metrics, Rearth, polyline_length, contour_area, fractal_dimension
 from .labeled import DataArray, Dataset

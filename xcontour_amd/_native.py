@@ -181,6 +181,10 @@ PROTOTYPES = {
                                           _vp, _vp, _vp, _vp]),
     'xc_set_cdist_prune': (C.c_int, [_vp, C.c_int]),
     'xc_last_cdist_profile': (C.c_int, [_vp, _vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int)]),
+    'xc_contour_distance_profile_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _f64, _f64, _f64,
+                                                  _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'xc_set_cdprofile_global': (C.c_int, [_vp, C.c_int]),
+    'xc_last_cdprofile_profile': (C.c_int, [_vp, _vp] + [C.POINTER(_i64)] * 4 + [C.POINTER(C.c_int)]),
     'xc_contour_map_dev': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
     'xc_contour_map': (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _i64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int]),
     'xc_contour_piece_interiors_dev': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, C.c_int,
@@ -543,6 +547,7 @@ XC_CMAP_TILE = 1024                                             # K25: cells a w
 XC_CSCALE_MAXR = 8                                              # ratios one K26 call takes
 XC_CSCALE_MAXRATIO = 64                                         # K26: the largest coarsening ratio
 XC_CDIST_RING = float(np.float64(np.deg2rad(np.float32(360.0))))   # K27: the one period of a sphere, float64(deg2rad(float32(360)))
+XC_CDPROFILE_MAX_EDGES = 4097                                   # K28: the most bin edges one call takes
 _UNSET = object()
 
 
@@ -1640,6 +1645,27 @@ class Context(object):
         return {'table_ms': ms[0], 'binning_ms': ms[1], 'distance_ms': ms[2], 'pairs_visited': pv.value, 'pairs_total': pt.value,
                 'groups': g.value}
 
+    def _cdist_args(self, who, q, contours, ycoord, xcoord, radius, period, select, max_distance, **more):
+        """the argument check K27 and K28 share (`more`: the weights and fields of `_RecordArgs`) -> (the checked arguments,
+        ycoord, xcoord, radius, period, the cap as the library takes it)"""
+        periodic = period is not None
+        a = _RecordArgs(who, q, contours, select=select, periodic=periodic, min_nx=2, labels32=True, **more)
+        ny, nx = a.ny, a.nx
+        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, who)
+        _check_finite(who, ycoord, xcoord)
+        radius = float(radius)
+        if not (np.isfinite(radius) and radius >= 0.0):
+            raise XContourHipError(XC_EBADARG, '%s: radius must be finite and >= 0' % who)
+        if periodic:
+            period = _check_period(period, xcoord, who)
+            if radius > 0.0 and abs(period) != XC_CDIST_RING:
+                raise XContourHipError(XC_EBADARG, '%s: on the sphere the period is float64(deg2rad(float32(+-360))), '
+                                       'not %r: the plane is a sphere or none' % (who, period))
+        cap = 0.0 if max_distance is None else float(max_distance)
+        if np.isnan(cap):
+            raise XContourHipError(XC_EBADARG, '%s: max_distance is NaN' % who)
+        return a, ycoord, xcoord, radius, period, cap
+
     def contour_distance(self, q, contours, ycoord, xcoord, radius=0.0, period=None, select='all', max_distance=None, signed=False,
                          flip=False, return_nearest=False):
         """How far every node lies from every contour (K27, xc_contour_distance_dev, on the device records of K12: the segment
@@ -1652,22 +1678,10 @@ class Context(object):
         float64 (nslab, N, ny, nx), +inf where a contour has no selected segment[, edge, piece int64 (nslab, N, ny, nx): the e_from
         of the nearest segment (ties: the smallest) and the first_edge of its piece, -1 where dist is infinite].  The contours are
         taken in groups, so that the device holds no more output planes than one batch may stage."""
+        a, ycoord, xcoord, radius, period, cap = self._cdist_args('xc_contour_distance', q, contours, ycoord, xcoord, radius, period, select,
+                                                                  max_distance)
         periodic = period is not None
-        a = _RecordArgs('xc_contour_distance', q, contours, select=select, periodic=periodic, min_nx=2, labels32=True)
         ny, nx, N = a.ny, a.nx, a.N
-        ycoord, xcoord = _plane_coords(ycoord, xcoord, ny, nx, 'xc_contour_distance')
-        _check_finite('xc_contour_distance', ycoord, xcoord)
-        radius = float(radius)
-        if not (np.isfinite(radius) and radius >= 0.0):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_distance: radius must be finite and >= 0')
-        if periodic:
-            period = _check_period(period, xcoord, 'xc_contour_distance')
-            if radius > 0.0 and abs(period) != XC_CDIST_RING:
-                raise XContourHipError(XC_EBADARG, 'xc_contour_distance: on the sphere the period is float64(deg2rad(float32(+-360))), '
-                                       'not %r: the plane is a sphere or none' % period)
-        cap = 0.0 if max_distance is None else float(max_distance)
-        if np.isnan(cap):
-            raise XContourHipError(XC_EBADARG, 'xc_contour_distance: max_distance is NaN')
         signed, near = bool(signed), bool(return_nearest)
         per_node = 8 + (16 if near else 0) + (1 if signed else 0)            # the bytes of one node's outputs, per contour
         ncg = max(1, min(N, int(self.max_batch_bytes) // (ny * nx * per_node)))
@@ -1703,6 +1717,92 @@ class Context(object):
         if near:
             return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(3))
         return np.concatenate(parts, axis=1)
+
+    def set_cdprofile_global(self, on):
+        """whether every tile of `contour_distance_profile` adds its terms straight to the global words instead of an LDS window
+        (xc_set_cdprofile_global; default off; the result does not depend on it: for tests and A/B timing)"""
+        self._check(self.lib.xc_set_cdprofile_global(self.handle, 1 if on else 0))
+
+    def last_cdprofile_profile(self):
+        """the last xc_contour_distance_profile_dev call: dict(table_ms, binning_ms, distance_ms, bound_ms, finish_ms -- device
+        times under set_kernel_timing(True) --, pairs_visited, pairs_total as `last_cdist_profile`, tiles_window, tiles_global:
+        the tiles that accumulated in the LDS window / on the global words, groups)"""
+        ms = (C.c_double * 5)()
+        n, g = [_i64(0) for _ in range(4)], C.c_int(0)
+        self._check(self.lib.xc_last_cdprofile_profile(self.handle, C.cast(ms, _vp), *[C.byref(v) for v in n], C.byref(g)))
+        out = {k + '_ms': v for k, v in zip(('table', 'binning', 'distance', 'bound', 'finish'), ms)}
+        out.update(zip(('pairs_visited', 'pairs_total', 'tiles_window', 'tiles_global'), (v.value for v in n)))
+        out['groups'] = g.value
+        return out
+
+    def contour_distance_profile(self, q, contours, ycoord, xcoord, edges, w=None, fields=(), radius=0.0, period=None, select='all',
+                                 max_distance=None, signed=False, flip=False):
+        """Composites by distance from every contour (K28, xc_contour_distance_profile_dev, on the device records of K12): the
+        distance of `contour_distance` -- same arguments, same bits -- binned on the device into `edges` (float64, finite,
+        strictly ascending, 2 to XC_CDPROFILE_MAX_EDGES of them; M = len(edges) - 1 bins; in the distance's units, negative
+        values with `signed`), and reduced there.  A node with distance d lies in bin b when edges[b] <= d < edges[b + 1], and
+        d == edges[M] in bin M - 1 (np.histogram's rule); nodes with an infinite distance or outside the edges lie in none.
+        w: None (weight 1), (ny, nx) or (nslab, ny, nx) float64; fields: at most XC_PROPS_MAXF f32 / f64 arrays, (ny, nx) or
+        (nslab, ny, nx).  Returns (nodes int64 (nslab, N, M), area float64 (nslab, N, M): the sum of w, sums float64
+        (nslab, N, nf, M): the sums of w f_m, each product rounded once, flags int32 (nslab, N, 1 + nf): where a term of the area
+        or of field m was not finite).  The sums are exact sums rounded once (NaN terms skipped, an infinite term makes that
+        bin's sum NaN): the same bits whatever the order, the workspace or the batches.  No plane crosses to the host; the only
+        per-node buffer beside the inputs is K17's mask with `signed`, and the contours are taken in groups under it."""
+        who = 'xc_contour_distance_profile'
+        edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))
+        if (edges.ndim != 1 or not 2 <= edges.size <= XC_CDPROFILE_MAX_EDGES or not np.isfinite(edges).all()
+                or not (np.diff(edges) > 0.0).all()):
+            raise XContourHipError(XC_EBADARG, '%s: edges must be 2 to 4097 finite, strictly ascending float64 values' % who)
+        fields = tuple(fields)
+        if len(fields) > XC_PROPS_MAXF:
+            raise XContourHipError(XC_EBADARG, '%s: at most 8 fields (XC_PROPS_MAXF)' % who)
+        a, ycoord, xcoord, radius, period, cap = self._cdist_args(who, q, contours, ycoord, xcoord, radius, period, select, max_distance,
+                                                                  w=w, fields=fields)
+        periodic = period is not None
+        ny, nx, N, M, nf = a.ny, a.nx, a.N, edges.size - 1, len(a.fields)
+        signed, has_w = bool(signed), a.w is not None
+        # a contour takes one byte per node on the device (K17's mask) when signed, and no plane at all when not
+        ncg = max(1, min(N, int(self.max_batch_bytes) // (ny * nx))) if signed else N
+
+        def group(k0, k1):
+            g = a.on(a.q, np.ascontiguousarray(a.contours[..., k0:k1]))
+            g.N = Ng = k1 - k0
+
+            def profile(cnt, total, dn, ins, outs, recs):
+                n = cnt.shape[0]
+                (dy, dx), dw, dfl = ins[:2], (ins[2] if has_w else None), ins[2 + has_w:]
+                dnod, dar, dflag = outs[:3]
+                dsum = outs[3] if nf else None
+                head = (self.handle, cnt.size, dn.ptr, *self._record_run(g, total, ins, recs)[0], ny, nx, 1 if periodic else 0, int(a.sel))
+                dm = outs[-1] if signed else None
+                if signed:                                       # K17's mask, made where it is used
+                    self._check(self.lib.xc_contour_interior_dev(*head, 1 if flip else 0, Ng, None, 0, None, 0, outs[-3].ptr, outs[-2].ptr,
+                                                                 None, dm.ptr))
+                fp = (_vp * max(nf, 1))(*[b.ptr for b in dfl])
+                fd = (C.c_int * max(nf, 1))(*[dtype_code(v.dtype) for v in a.fields])
+                fs = (C.c_int * max(nf, 1))(*[1 if v.ndim == 3 else 0 for v in a.fields])
+                self._check(self.lib.xc_contour_distance_profile_dev(
+                    *head, dy.ptr, dx.ptr, period if periodic else 0.0, radius, cap, dm.ptr if signed else None, edges.size, _ptr(edges),
+                    Ng, dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, nf, C.cast(fp, _vp), C.cast(fd, _vp),
+                    C.cast(fs, _vp), dnod.ptr, dar.ptr, dsum.ptr if nf else None, dflag.ptr))
+                sums = (np.ascontiguousarray(np.moveaxis(dsum.download((nf, n, Ng, M), np.float64), 0, 2)) if nf
+                        else np.empty((n, Ng, 0, M), dtype=np.float64))
+                return (dnod.download((n, Ng, M), np.int64), dar.download((n, Ng, M), np.float64), sums,
+                        dflag.download((n, Ng, 1 + nf), np.int32))
+
+            def one(s0, s1):
+                # beside K12's records: the coordinates, the weights and the fields; the tables of nodes, area, flags and sums; and
+                # for the sign K17's two sums and its mask
+                n = s1 - s0
+                qb, cb, wb, _, fb, _ = g.batch(s0, s1)
+                nb = [n * Ng * M * 8, n * Ng * M * 8, n * Ng * (1 + nf) * 4] + ([nf * n * Ng * M * 8] if nf else [])
+                nb += [n * Ng * 8, n * Ng * 8, n * Ng * ny * nx] if signed else []
+                return self._with_segment_records(periodic, qb, cb, profile, inputs=[ycoord, xcoord] + ([wb] if has_w else []) + fb,
+                                                  out_nbytes=nb)
+            return self._batched(a.nslab, g.slab_bytes(Ng if signed else 0), one)
+
+        parts = [group(k0, min(N, k0 + ncg)) for k0 in range(0, N, ncg)]
+        return parts[0] if len(parts) == 1 else tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(4))
 
     # the per-event table of `contour_folds`: the library's record, the two tongues (0 under, 1 over) side by side
     FOLD_DTYPE = np.dtype([('c_west', np.int32), ('c_east', np.int32), ('ncol', np.int32), ('ncross_max', np.int32),

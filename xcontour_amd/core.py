@@ -1070,6 +1070,23 @@ class Contour2D(object):
         return lb.merge(out, p.data)
 
     # ------------------------------------------------------------------ distance to contours
+    def _distance_open(self, who, contours, tracer, latlon, periodic, select, side):
+        """the opening of the two distance methods: the names, the plane with the coordinates the kernels take, a selection that
+        needs a ring, the values, the levels sorted, and `flip` from `side` -> (the namespace `_on_contours` closes with, the
+        coordinates as the kernels take them, the period, the radius)"""
+        p = self._piece_names(who, contours, select, side)
+        p.data, p.dcoords, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
+        if select != 'all' and period is None:
+            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
+                            'periodic=True or the period, or select=\'all\'' % (who, select))
+        p.q, p.lead, p.lshape, p.coords = self._float_plane(p.data)
+        p.nslab, p.ny, p.nx = p.q.shape
+        p.bs, p.order, p.ccoord = self._sorted_levels(p.contours, p.nslab, p.lead, p.lshape)
+        p.yg = np.asarray(fdef[0])
+        ascends = p.yg.size < 2 or p.yg[-1] >= p.yg[0]
+        p.flip = (side == 'upper') != bool(ascends)
+        return p, fdef, period, (Rearth if latlon else 0.0)
+
     def cal_distance_to_contours(self, contours, tracer=None, latlon=False, periodic=False, select='all', side='upper', signed=False,
                                  max_distance=None, return_nearest=False):
         """
@@ -1095,18 +1112,9 @@ class Contour2D(object):
         The result is N full planes per slab: this is meant for a few levels, not for a whole contour set.
         """
         who = 'cal_distance_to_contours'
-        p = self._piece_names(who, contours, select, side)
-        p.data, p.dcoords, fdef, period = self._contour_coords(who, tracer, latlon, periodic)
-        if select != 'all' and period is None:
-            raise Exception('%s: select=%r needs periodic (no contour goes round a plane with two free edges): give '
-                            'periodic=True or the period, or select=\'all\'' % (who, select))
-        p.q, p.lead, p.lshape, p.coords = self._float_plane(p.data)
-        p.bs, p.order, p.ccoord = self._sorted_levels(p.contours, p.q.shape[0], p.lead, p.lshape)
-        ascends = fdef[0].size < 2 or fdef[0][-1] >= fdef[0][0]
-        radius = Rearth if latlon else 0.0
+        p, fdef, period, radius = self._distance_open(who, contours, tracer, latlon, periodic, select, side)
         res = self.ctx.contour_distance(p.q, p.bs, fdef[0], fdef[1], radius=radius, period=period, select=select,
-                                        max_distance=max_distance, signed=signed, flip=(side == 'upper') != bool(ascends),
-                                        return_nearest=return_nearest)
+                                        max_distance=max_distance, signed=signed, flip=p.flip, return_nearest=return_nearest)
         dist = res[0] if return_nearest else res
         dist = np.where(np.isinf(dist), np.nan, dist).astype(self.dtype)
         plane = (self.dimEqV, self._xdim)
@@ -1122,6 +1130,70 @@ class Contour2D(object):
             flat[r][has] = np.searchsorted(tab['first_edge'][start[r]:start[r] + c[r]], flat[r][has])
         out = [self._on_contours(p, name, v, plane) for name, v in (('distance', dist), ('edge', edge), ('piece', piece))]
         return lb.merge(out, p.data)
+
+    def cal_contour_distance_profile(self, contours, bins, fields=None, tracer=None, latlon=False, periodic=False, select='all',
+                                     side='upper', signed=False, max_distance=None):
+        """
+        Composites by distance from every contour, computed on the GPU in one call (K12's segments, K13's pieces, K16's
+        selection, K27's search, K28, xc_contour_distance_profile_dev): per contour and distance bin the number of nodes, their
+        area and the area-weighted integrals of up to eight fields -- the mean of a field as a function of the (signed) distance
+        from the vortex edge, from a jet axis, from a front.  It is np.histogram(distance, bins, weights=dA * field) of
+        cal_distance_to_contours, level by level, without the planes: the distance of every node is binned where it is made
+        and only (contours x bins) numbers per quantity cross to the host, so a whole contour set and a stack are fine.
+        Build-defined.
+
+        `contours`, the coordinates, `periodic`, `select`, `side`, `signed`, `max_distance` and the order of the levels are
+        handled exactly as in cal_distance_to_contours, and the distance is that method's, bit for bit.  `bins`: the bin
+        edges, ascending, in the distance's units (metres with latlon=True; negative values with signed=True).  The bin rule
+        is np.histogram's: a node with distance d lies in bin b when bins[b] <= d < bins[b + 1], and d == bins[-1] lies in the
+        last bin; a node with no distance (NaN in cal_distance_to_contours: no selected piece, beyond `max_distance`) or outside
+        the edges lies in none.  `fields`: a dict name -> labelled array over the tracer's dims (or over the plane's two dims,
+        or a 2-D numpy plane), or one labelled array (named by its name, else 'field'), as in cal_contour_piece_props.  The
+        weight is this object's dA.
+
+        Returns a Dataset over (..., contour, distance_bin); the coordinate `distance_bin` holds the bin centres, `bin_lo` and
+        `bin_hi` the edges of every bin.  `nodes` (int64): the nodes of the bin; `area`: the sum of dA over them; per field
+        `<name>`: the sum of dA * field, each product rounded once; `<name>_mean`: that integral over `area`, NaN where
+        `area` is 0.  The sums are exact sums of their float64 terms rounded once: in the Cartesian case every number is
+        bit-reproducible, whatever the launch geometry or the batches (with latlon=True the sums are exact too, of the
+        distances that device's asin gives).  A NaN term is skipped and an infinite one makes that bin's sum NaN; `nodes` and
+        `area` count the node all the same, so `<name>_mean` is a true mean only for a field without NaN: for a field with
+        gaps, put the mask into dA.  A NaN level, or one no contour follows, has zeros.
+        """
+        who = 'cal_contour_distance_profile'
+        p, fdef, period, radius = self._distance_open(who, contours, tracer, latlon, periodic, select, side)
+        edges = np.asarray(bins, dtype=np.float64)
+        if edges.ndim != 1 or edges.size < 2 or not np.isfinite(edges).all() or not (np.diff(edges) > 0).all():
+            raise Exception('%s: bins should be at least two finite, ascending edges' % who)
+        if fields is None:
+            user = {}
+        elif isinstance(fields, dict):
+            user = dict(fields)
+        else:
+            user = {getattr(fields, 'name', None) or 'field': fields}
+        if len(user) > self.ctx.XC_PROPS_MAXF:
+            raise Exception('%s: %d fields, more than the %d one call takes' % (who, len(user), self.ctx.XC_PROPS_MAXF))
+        clash = [k for k in user if k in ('nodes', 'area') or k + '_mean' in user]
+        if clash:
+            raise Exception('%s: the field name %r collides with a variable of the result' % (who, clash[0]))
+        planes = self._field_planes(who, user, p.q)
+        self._piece_weights(p, None)
+        nodes, area, sums, _ = self.ctx.contour_distance_profile(p.q, p.bs, fdef[0], fdef[1], edges, w=p.dA, fields=planes, radius=radius,
+                                                                 period=period, select=select, max_distance=max_distance,
+                                                                 signed=signed, flip=p.flip)
+        lo, hi = edges[:-1], edges[1:]
+        p.dcoords = dict(p.dcoords)
+        p.dcoords['distance_bin'] = 0.5 * (lo + hi)
+        out = [('nodes', nodes), ('area', area)]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            for m, name in enumerate(user):
+                out += [(name, sums[:, :, m]), (name + '_mean', np.where(area == 0.0, np.nan, sums[:, :, m] / area))]
+        arrs = [self._on_contours(p, name, np.ascontiguousarray(v), ('distance_bin',)) for name, v in out]
+        if lb.is_xarray(p.data):
+            arrs = [a.assign_coords(bin_lo=('distance_bin', lo), bin_hi=('distance_bin', hi)) for a in arrs]
+        else:
+            arrs = [a.assign_coords({'bin_lo': lo, 'bin_hi': hi}) for a in arrs]
+        return lb.merge(arrs, p.data)
 
     # ------------------------------------------------------------------ contour folds
     # an event as the facade returns it: where it sits, and what each tongue holds
@@ -1290,6 +1362,19 @@ class Contour2D(object):
         pc, tab, lab = self.ctx.contour_piece_labels(p.q, p.bs, w=p.dA, f=p.g, periodic=p.ring, flip=p.flip)
         return self._ring_tables(p, pc, tab), self._on_contours(p, 'labels', lab, (self.dimEqV, self._xdim))
 
+    def _field_planes(self, who, user, q):
+        """the caller's fields (name -> labelled array over the tracer's dims or over the plane's two dims, or a 2-D numpy plane)
+        as the kernels read them: (nslab, ny, nx), or (ny, nx) for one plane that every slab shares"""
+        planes = []
+        for v in user.values():
+            v = self._float(self._plane_of(v)[0]) if lb.is_labeled(v) else nat._f48(np.asarray(v))
+            if v.ndim == 3 and v.shape[0] == 1 and v.shape != q.shape:
+                v = v[0]
+            if v.shape not in (tuple(q.shape[1:]), tuple(q.shape)):
+                raise Exception('%s: a field should lie over the tracer\'s dims or over the plane\'s two dims' % who)
+            planes.append(v)
+        return planes
+
     def cal_contour_piece_props(self, contours, fields=None, extremum=None, tracer=None, latlon=False, periodic=False, side='upper',
                                 centroid=True):
         """
@@ -1340,14 +1425,7 @@ class Contour2D(object):
         if len(names_g) > self.ctx.XC_PROPS_MAXF:
             raise Exception('%s: %d fields and %d moment planes are %d, more than the %d one call takes'
                             % (who, len(user), len(moments), len(names_g), self.ctx.XC_PROPS_MAXF))
-        planes = []
-        for v in user.values():
-            v = self._float(self._plane_of(v)[0]) if lb.is_labeled(v) else nat._f48(np.asarray(v))
-            if v.ndim == 3 and v.shape[0] == 1 and v.shape != q.shape:
-                v = v[0]
-            if v.shape not in ((ny, nx), tuple(q.shape)):
-                raise Exception('%s: a field should lie over the tracer\'s dims or over the plane\'s two dims' % who)
-            planes.append(v)
+        planes = self._field_planes(who, user, q)
         if extremum is None:
             xq = q[0:p.nslab] if getattr(q, '_xc_lazy_stack', False) else q
         elif extremum is False:
@@ -1611,6 +1689,7 @@ class Contour2D(object):
             p.cc = {d: np.asarray(p.coords[d]) for d in p.lead if d in p.coords}
             p.cc['contour'] = np.asarray(p.ccoord)
             p.cc.update((d, np.asarray(p.dcoords[d])) for d in (self.dimEqV, self._xdim))
+        p.cc.update((d, np.asarray(p.dcoords[d])) for d in trailing if d not in p.cc)    # (a dim of the result alone: distance_bin)
         v = _level_order(v, p.order.reshape(p.order.shape + (1,) * (v.ndim - 2)))
         return lb.wrap(v.reshape(tuple(p.lshape) + v.shape[1:]), tuple(p.lead) + ('contour',) + tuple(trailing), p.cc, name, p.data)
 
@@ -2390,6 +2469,28 @@ def distance_to_contour(data, dims, level, period=[None, None], periodic=False, 
         raise Exception('distance_to_contour expects a 2-D field on the dims %s' % [ydim, xdim])
     cm = Contour2D(data, 1.0, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
     return cm.cal_distance_to_contours(np.array([float(level)]), latlon=latlon, periodic=periodic).isel({'contour': 0})
+
+
+def distance_profile(data, dims, level, bins, fields=None, dA=1.0, period=[None, None], periodic=False, latlon=False, signed=False,
+                     side='upper', max_distance=None):
+    """
+    Composites by distance from ONE level of a 2-D labelled field, beside `distance_to_contour` and in its call shape: `dims` =
+    [ydim, xdim], `period` must be [None, None], a periodic X direction goes through `periodic`.  `bins`, `fields`, `signed`, `side`
+    and `max_distance` as in Contour2D.cal_contour_distance_profile, which states the bin rule; `dA`: the weight, a labelled array
+    on the plane or a number (1.0: `area` counts nodes).  Returns that method's Dataset for the level, over (distance_bin,).
+    """
+    if period is not None and any(p is not None for p in period):
+        raise NotImplementedError('distance_profile: period=%r is not supported (only [None, None]: use `periodic`)' % (period,))
+    ydim, xdim = dims
+    ddims = lb.unwrap(data, lazy=True)[1]
+    if len(ddims) != 2 or set(ddims) != {ydim, xdim}:
+        raise Exception('distance_profile expects a 2-D field on the dims %s' % [ydim, xdim])
+    if np.ndim(dA) == 0:                                             # a number: the same weight on every row
+        dA = np.full(lb.unwrap(data, lazy=True)[0].shape[ddims.index(ydim)], float(dA))
+    cm = Contour2D(data, dA, {'X': xdim, 'Y': ydim}, {'Y': ydim}, dtype=np.float64)
+    ds = cm.cal_contour_distance_profile(np.array([float(level)]), bins, fields=fields, latlon=latlon, periodic=periodic, signed=signed,
+                                         side=side, max_distance=max_distance)
+    return lb.merge([v.isel({'contour': 0}) for v in ds.values()], data)
 
 
 def coarsen(data, dims, ratio, skipna=False):

@@ -27,7 +27,8 @@
 //                   whatever the atomics gave: nothing depends on it.
 //   k_cd_box        one thread per non-empty block: the box that holds every foot the metric can compute on its segments
 //   k_cp_unscatter  the table is handed on clean
-//   k_cd_dist       one workgroup per tile of CD_T x CD_T nodes per range, one node per lane.  The tile's own box; with pruning an upper
+//   k_cd_dist       one workgroup per tile of CD_T x CD_T nodes per range, one node per lane (the search is the device function
+//                   cd_search, which K28's k_cd_profile calls too).  The tile's own box; with pruning an upper
 //                   bound W on every node's result from the far distance to the nearest block; then every non-empty block whose lower
 //                   bound does not exceed W (or max_dist) is staged through LDS in chunks of CD_CHUNK segments and every lane takes the
 //                   minimum; W shrinks to the tile's worst best-distance after every block.  The bounds are conservative
@@ -35,9 +36,17 @@
 //                   results are the same bits.
 // Ranges outside every group have no segment: k_cd_none writes their planes.  Every index taken from a record is checked before any
 // output is written (k_cd_check): a refusal writes nothing.
+//
+// K28 -- composites by distance (xc_contour_distance_profile_dev; the rule is in include/xcontour_hip.h, K28 section).  The same launcher
+// and the same phases up to the tile pass; k_cd_profile runs cd_search and then bins the lane's distance into the caller's edges and adds
+// the node, its weight and its weighted fields to the (range, bin)'s words -- K17's exact sums (xc_cpiece_sum.h), through an LDS window
+// laid into the search's segment chunk, or straight to memory where the tile spans more than CDP_SPAN bins; k_cd_profile_finish rounds
+// the words once.  No plane is written.
 #include "xc_capi.h"
 #include <algorithm>
 #include <cmath>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 namespace xc {
@@ -48,6 +57,9 @@ namespace {
 
 #include "xc_cpiece_link.h"
 #include "xc_cpiece_select.h"
+#include "xc_cpiece_sum.h"
+#include "xc_cinside_bound.h"
+#include "xc_cpiece_field.h"
 #include "xc_cdist_metric.h"
 
 constexpr int CD_T = 16;                      // a tile of nodes is CD_T x CD_T: one node per lane of a CD_TPB workgroup
@@ -55,6 +67,16 @@ constexpr int CD_TPB = CD_T * CD_T;
 constexpr int CD_CHUNK = 256;                 // segments of a block staged through LDS at a time
 constexpr int CD_B = 32;                      // a coarse block is CD_B x CD_B cells
 constexpr int CD_NBOX_PLANE = 4, CD_NBOX_SPHERE = 6;
+
+// K28's accumulation.  Its LDS is the segment chunk of the search (sseg), free once the search is over: the smaller one, the plane's
+// CD_CHUNK * CD_ND_PLANE = 1280 64-bit words, holds CDP_EDGES_LDS edges, the window of CDP_SPAN bins x CDP_MAXCH channels x CP_L words and
+// the window's counts -- the profile kernel has the LDS footprint of k_cd_dist and its occupancy.
+//   CDP_SPAN 16: the distances of a 16 x 16 tile span at most its diagonal, so a tile touches more than 16 bins only where the bins are
+//   narrower than 1/11 of a tile (the wide-span fallback); 16 x 9 x 5 = 720 words, with 512 edges 1232 + 8 words of counts <= 1280.
+constexpr int CDP_SPAN = 16;                  // bins of the LDS window
+constexpr int CDP_MAXCH = 1 + XC_PROPS_MAXF;  // channels: the area, then the fields
+constexpr int CDP_EDGES_LDS = 512;            // edges kept in LDS; a longer table is read through the cache
+constexpr int CDP_MAX_EDGES = 4097;
 
 __global__ __launch_bounds__(CP_TPB)
 void k_cd_check(int64_t total, long long E, const long long* __restrict__ e_from, const long long* __restrict__ e_to, int* __restrict__ err)
@@ -270,14 +292,19 @@ struct CdArgs {
     const unsigned char* mask; double* dist; long long *edge, *piece; unsigned long long* pairs;
 };
 
+// what the search leaves a lane: its node, and the node's result as K27 stores it
+struct CdHit {
+    bool valid; int64_t r, row, col; size_t at;                            // the lane has a node; its range, the node, its place in a plane stack
+    double d; int bid, bslot; long long base;                              // the final distance (sign and cap applied); the winner and its slot
+};
+
+// The per-tile search of K27, for K27 (k_cd_dist) and K28 (k_cd_profile): the node set-up, the bounds, the pruned walk over the blocks
+// staged through LDS, and the finish to d.  sseg [CD_CHUNK * ND], sid [CD_CHUNK] and sred [CD_TPB / 64] are the workgroup's; every lane
+// of the workgroup calls it (it holds barriers).  Lanes may still read sseg when it returns.
 template <bool SPHERE>
-__global__ __launch_bounds__(CD_TPB)
-void k_cd_dist(const CdArgs A)
+__device__ __forceinline__ CdHit cd_search(const CdArgs& A, double* sseg, int* sid, double* sred)
 {
     constexpr int ND = SPHERE ? CD_ND_SPHERE : CD_ND_PLANE, NBOX = SPHERE ? CD_NBOX_SPHERE : CD_NBOX_PLANE;
-    __shared__ double sseg[CD_CHUNK * ND];
-    __shared__ int sid[CD_CHUNK];
-    __shared__ double sred[CD_TPB / 64];
     const int64_t ntile = A.nty * A.ntx;
     const int64_t tile = (int64_t)blockIdx.x % ntile, r = A.ra + (int64_t)blockIdx.x / ntile, g = r - A.g0;
     const int64_t tr = tile / A.ntx, tc = tile - tr * A.ntx;
@@ -400,22 +427,139 @@ void k_cd_dist(const CdArgs A)
         atomicAdd(A.pairs, visited * (unsigned long long)(vr * vc));
         atomicAdd(A.pairs + 1, nsel * (unsigned long long)(vr * vc));
     }
-    if (!valid) return;
+    CdHit h = {valid, r, row, col, 0, inf, bid, -1, base};
+    if (!valid) return h;
     double d = inf;
     if (bslot >= 0) {
         if constexpr (SPHERE) {
-            const double h = __dmul_rn(__dsqrt_rn(best), 0.5);
-            d = __dmul_rn(A.radius, __dmul_rn(2.0, asin(h < 1.0 ? h : 1.0)));
+            const double hc = __dmul_rn(__dsqrt_rn(best), 0.5);
+            d = __dmul_rn(A.radius, __dmul_rn(2.0, asin(hc < 1.0 ? hc : 1.0)));
         } else {
             d = __dsqrt_rn(best);
         }
         if (A.cap > 0.0 && d > A.cap) { d = inf; bslot = -1; }
     }
-    const size_t at = ((size_t)r * (size_t)A.ny + (size_t)row) * (size_t)A.nx + (size_t)col;
-    if (A.mask && bslot >= 0 && A.mask[at]) d = -d;
-    A.dist[at] = d;
-    if (A.edge) A.edge[at] = bslot >= 0 ? (long long)bid : -1ll;
-    if (A.piece) A.piece[at] = bslot >= 0 ? (long long)A.tpiece[base + bslot] : -1ll;
+    h.at = ((size_t)r * (size_t)A.ny + (size_t)row) * (size_t)A.nx + (size_t)col;
+    if (A.mask && bslot >= 0 && A.mask[h.at]) d = -d;
+    h.d = d; h.bslot = bslot;
+    return h;
+}
+
+template <bool SPHERE>
+__global__ __launch_bounds__(CD_TPB)
+void k_cd_dist(const CdArgs A)
+{
+    constexpr int ND = SPHERE ? CD_ND_SPHERE : CD_ND_PLANE;
+    __shared__ double sseg[CD_CHUNK * ND];
+    __shared__ int sid[CD_CHUNK];
+    __shared__ double sred[CD_TPB / 64];
+    const CdHit h = cd_search<SPHERE>(A, sseg, sid, sred);
+    if (!h.valid) return;
+    A.dist[h.at] = h.d;
+    if (A.edge) A.edge[h.at] = h.bslot >= 0 ? (long long)h.bid : -1ll;
+    if (A.piece) A.piece[h.at] = h.bslot >= 0 ? (long long)A.tpiece[h.base + h.bslot] : -1ll;
+}
+
+// ---------------------------------------------------------------------------------- K28: composites by distance
+// What K28 adds to a tile pass.  A node with the final distance d belongs to bin b when edges[b] <= d < edges[b + 1]; d == edges[M]
+// belongs to bin M - 1 (np.histogram's rule); a node with d = +inf, or outside [edges[0], edges[M]], belongs nowhere.  Per (range, bin):
+// the nodes, and per channel (0: the area w; 1 + m: w f_m, the product rounded once) the CP_L words of the exact sum (xc_cpiece_sum.h).
+struct CdProf {
+    int nedge, nf, ncont, global;                                          // edges; fields; ranges per slab; every tile takes the global path
+    const double *edges, *w; int w_per_slab; const PpField* fld;
+    const unsigned long long *mxw, *mxg;                                   // the bounds: mxw[2 s] of |w|, mxg[s nf + m] of |w f_m|
+    unsigned long long *acc, *cnt; int* bflag;                             // acc[range][bin][channel][CP_L], cnt[range][bin], bflag[range][bin][channel]
+    unsigned long long* tiles;                                             // tiles that took the LDS window, the global path
+};
+
+// the bin of d among the nedge ascending edges e, -1 for none: the number of edges <= d, less one, the last edge closed
+__device__ __forceinline__ int cdp_bin(double d, const double* e, int nedge)
+{
+    if (!(d >= e[0]) || !(d <= e[nedge - 1])) return -1;
+    int lo = 0, hi = nedge;
+    while (lo < hi) {                                                      // at most 13 steps
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= d) lo = mid + 1; else hi = mid;
+    }
+    return lo == nedge ? nedge - 2 : lo - 1;
+}
+
+// One workgroup per tile per range, as k_cd_dist: K27's search, then the accumulation.  The workgroup's lanes span bins [bmin, bmax].
+// Up to CDP_SPAN bins (and unless P.global): every term is added whole to a window of LDS words with LDS integer atomics, then every
+// non-zero word goes to the global words with one 64-bit atomic.  More: every term goes to the global words (cp_add).  Integer sums of
+// the same chunks either way: the same words.
+template <bool SPHERE>
+__global__ __launch_bounds__(CD_TPB)
+void k_cd_profile(const CdArgs A, const CdProf P)
+{
+    constexpr int ND = SPHERE ? CD_ND_SPHERE : CD_ND_PLANE;
+    constexpr int WIN = CDP_SPAN * CDP_MAXCH * CP_L;
+    static_assert(CDP_EDGES_LDS + WIN + (CDP_SPAN + 1) / 2 <= CD_CHUNK * CD_ND_PLANE, "K28's window lives in the search's segment chunk");
+    __shared__ double sseg[CD_CHUNK * ND];
+    __shared__ int sid[CD_CHUNK];
+    __shared__ double sred[CD_TPB / 64];
+    __shared__ int stop[CDP_MAXCH];
+    const CdHit h = cd_search<SPHERE>(A, sseg, sid, sred);
+    const int t = threadIdx.x;
+    const int nch = 1 + P.nf, M = P.nedge - 1;
+    const size_t sl = (size_t)(h.r / P.ncont);
+    double* sedge = sseg;                                                  // the chunk is free once every lane has left the search
+    unsigned long long* swin = reinterpret_cast<unsigned long long*>(sseg) + CDP_EDGES_LDS;
+    unsigned* scnt = reinterpret_cast<unsigned*>(swin + WIN);
+    const bool lds_edges = P.nedge <= CDP_EDGES_LDS;
+    __syncthreads();
+    if (lds_edges) for (int i = t; i < P.nedge; i += CD_TPB) sedge[i] = P.edges[i];
+    if (t < nch) stop[t] = t == 0 ? ci_top(P.mxw[2 * sl]) : ci_top(P.mxg[sl * (size_t)P.nf + (size_t)(t - 1)]);
+    __syncthreads();
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    const int b = h.valid && h.bslot >= 0 ? cdp_bin(h.d, lds_edges ? sedge : P.edges, P.nedge) : -1;
+    const double dmin = cd_wg_min(b >= 0 ? (double)b : inf, sred), dmax = cd_wg_max(b >= 0 ? (double)b : -inf, sred);
+    if (!(dmin <= dmax)) return;                                           // no node of the tile lies in a bin (uniform)
+    const int bmin = (int)dmin, span = (int)dmax - bmin + 1;
+    const bool window = span <= CDP_SPAN && !P.global;
+    if (t == 0) atomicAdd(P.tiles + (window ? 0 : 1), 1ull);
+    if (window) {
+        for (int i = t; i < span * nch * CP_L; i += CD_TPB) swin[i] = 0ull;
+        if (t < span) scnt[t] = 0u;
+        __syncthreads();
+    }
+    if (b >= 0) {
+        const size_t node = (size_t)h.row * (size_t)A.nx + (size_t)h.col, npl = (size_t)A.ny * (size_t)A.nx;
+        const size_t gbin = (size_t)h.r * (size_t)M + (size_t)b;
+        unsigned long long* words = window ? swin + (size_t)(b - bmin) * (size_t)nch * CP_L : P.acc + gbin * (size_t)nch * CP_L;
+        if (window) atomicAdd(scnt + (b - bmin), 1u); else atomicAdd(P.cnt + gbin, 1ull);
+        const double wv = P.w ? P.w[(P.w_per_slab ? sl * npl : 0) + node] : 1.0;
+        for (int ch = 0; ch < nch; ++ch) {
+            const double v = ch == 0 ? wv : __dmul_rn(wv, pp_load(P.fld[ch - 1], sl, node));
+            if (v == v) cp_add(words + ch * CP_L, P.bflag + gbin * (size_t)nch + (size_t)ch, 1, v, stop[ch]);
+        }
+    }
+    if (!window) return;
+    __syncthreads();
+    unsigned long long* dst = P.acc + ((size_t)h.r * (size_t)M + (size_t)bmin) * (size_t)nch * CP_L;
+    for (int i = t; i < span * nch * CP_L; i += CD_TPB) { const unsigned long long v = swin[i]; if (v) atomicAdd(dst + i, v); }
+    if (t < span && scnt[t]) atomicAdd(P.cnt + (size_t)h.r * (size_t)M + (size_t)(bmin + t), (unsigned long long)scnt[t]);
+}
+
+// one thread per (range, bin, channel): the words carried and rounded once; a flagged sum is NaN and sets the caller's flag word of its
+// (range, channel)
+__global__ __launch_bounds__(CP_TPB)
+void k_cd_profile_finish(int64_t nrange, int M, int nf, int ncont, const unsigned long long* __restrict__ acc,
+                         const unsigned long long* __restrict__ cnt, const int* __restrict__ bflag, const unsigned long long* __restrict__ mxw,
+                         const unsigned long long* __restrict__ mxg, long long* __restrict__ nodes, double* __restrict__ area,
+                         double* __restrict__ sums, int* __restrict__ flags)
+{
+    const int nch = 1 + nf;
+    const int64_t i = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (i >= nrange * M * nch) return;
+    const int ch = (int)(i % nch);
+    const int64_t rb = i / nch, r = rb / M, s = r / ncont;
+    const int top = ch == 0 ? ci_top(mxw[2 * s]) : ci_top(mxg[(size_t)s * nf + (ch - 1)]);
+    const bool bad = bflag[i] != 0;
+    const double v = bad ? __longlong_as_double(0x7ff8000000000000ll) : cp_to_double(acc + (size_t)i * CP_L, top);
+    if (bad) atomicOr(flags + r * nch + ch, 1);
+    if (ch == 0) { nodes[rb] = (long long)cnt[rb]; area[rb] = v; }
+    else sums[(size_t)(ch - 1) * (size_t)(nrange * M) + (size_t)rb] = v;
 }
 
 }  // namespace
@@ -423,84 +567,130 @@ void k_cd_dist(const CdArgs A)
 // the period of a longitude ring in radians as the facade hands it over: float64(deg2rad(float32(360)))
 static const double CD_RING = (double)6.2831855f;
 
-// One xc_contour_distance_dev call.  Waits for the stream three times: for K12's counts (they size the groups and fix the rounds), for
-// the word that says whether the ids were in range (before anything is written), and for the pair counts of the profile.
-int launch_contour_distance(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
-                            int64_t ny, int64_t nx, int periodic, int select, const double* ycoord, const double* xcoord, double period,
-                            double radius, double max_dist, const uint8_t* negate_mask, double* dist, int64_t* edge, int64_t* piece)
+// One call of xc_contour_distance_dev or xc_contour_distance_profile_dev: the caller's pointers and scalars in the order of the C ABI.
+// `profile` says which: K27 writes planes, K28 bins them where they are made.
+struct CdCall {
+    const char* who; CpProfile* prof;
+    int64_t nrange; const uint64_t* count; const int64_t *e_from, *e_to; const double* pts; int64_t ny, nx; int periodic, select;
+    const double *ycoord, *xcoord; double period, radius, max_dist; const uint8_t* negate_mask;
+    double* dist; int64_t *edge, *piece;
+    bool profile; int nedge; const double* edges; int ncont; const double* w; int w_per_slab; int nf; const void* const* f;
+    const int *f_dtype, *f_per_slab; int64_t* nodes; double *area, *sums; int32_t* flags;
+};
+
+// One call.  Waits for the stream three times: for K12's counts (they size the groups and fix the rounds), for the word that says whether
+// the ids were in range (before anything is written), and for the pair counts of the profile.
+static int launch_cdist(xc_ctx* ctx, const CdCall& c)
 {
-    const char* who = "xc_contour_distance";
-    if (!count || !dist || !ycoord || !xcoord || nrange < 1 || ny < 1 || nx < 1) return fail(ctx, XC_EBADARG, "xc_contour_distance: bad arguments");
-    XC_TRY(co_check_select(ctx, who, periodic, select));
-    if (!(radius >= 0.0) || !std::isfinite(radius)) return fail(ctx, XC_EBADARG, "xc_contour_distance: radius must be finite and >= 0");
-    if (periodic && (!std::isfinite(period) || period == 0.0 || nx < 2))
-        return fail(ctx, XC_EBADARG, "xc_contour_distance: a periodic plane needs a finite, non-zero period and nx >= 2");
+    const std::string who_s(c.who);
+    auto refuse = [&](const char* what) { return fail(ctx, XC_EBADARG, who_s + what); };
+    const char* who = c.who;
+    const int64_t nrange = c.nrange, ny = c.ny, nx = c.nx;
+    const int periodic = c.periodic;
+    const double period = c.period, radius = c.radius, max_dist = c.max_dist;
+    if (!c.count || !c.ycoord || !c.xcoord || nrange < 1 || ny < 1 || nx < 1) return refuse(": bad arguments");
+    if (c.profile ? (!c.nodes || !c.area || !c.flags) : !c.dist) return refuse(": bad arguments");
+    XC_TRY(co_check_select(ctx, who, periodic, c.select));
+    if (!(radius >= 0.0) || !std::isfinite(radius)) return refuse(": radius must be finite and >= 0");
+    if (periodic && (!std::isfinite(period) || period == 0.0 || nx < 2)) return refuse(": a periodic plane needs a finite, non-zero period and nx >= 2");
     if (radius > 0.0 && periodic && period != CD_RING && period != -CD_RING)
-        return fail(ctx, XC_EBADARG, "xc_contour_distance: on the sphere the period is float64(deg2rad(float32(+-360))): the plane is a sphere or none");
-    if (max_dist != max_dist) return fail(ctx, XC_EBADARG, "xc_contour_distance: max_dist is NaN");
+        return refuse(": on the sphere the period is float64(deg2rad(float32(+-360))): the plane is a sphere or none");
+    if (max_dist != max_dist) return refuse(": max_dist is NaN");
     XC_TRY(co_check_plane(ctx, who, periodic, ny, nx));
-    if (nrange > ((int64_t)1 << 40) / (ny * nx)) return fail(ctx, XC_EBADARG, "xc_contour_distance: nrange ny nx must stay below 2^40");
+    if (nrange > ((int64_t)1 << 40) / (ny * nx)) return refuse(": nrange ny nx must stay below 2^40");
+    const int nf = c.profile ? c.nf : 0, M = c.profile ? c.nedge - 1 : 0, nch = 1 + nf;
+    int64_t nslab = 1;
+    if (c.profile) {
+        bool ok = c.edges && c.nedge >= 2 && c.nedge <= CDP_MAX_EDGES;
+        for (int i = 0; ok && i < c.nedge; ++i) ok = std::isfinite(c.edges[i]) && (i == 0 || c.edges[i] > c.edges[i - 1]);
+        if (!ok) return refuse(": edges must be 2 to 4097 finite, strictly ascending float64 values");
+        if (nf < 0 || nf > XC_PROPS_MAXF) return refuse(": at most 8 fields (XC_PROPS_MAXF)");
+        if (nf > 0 && (!c.f || !c.f_dtype || !c.f_per_slab || !c.sums)) return refuse(": the fields, their dtypes and sums go together");
+        for (int m = 0; m < nf; ++m)
+            if (!c.f[m] || (c.f_dtype[m] != XC_F32 && c.f_dtype[m] != XC_F64)) return refuse(": a field is a device plane of XC_F32 or XC_F64");
+        if (c.ncont < 1 || nrange % c.ncont != 0) return refuse(": nrange must be a multiple of ncont >= 1");
+        nslab = nrange / c.ncont;
+        if (nslab > 65535) return refuse(": more than 65535 slabs");
+    }
     const long long E = 2 * ny * nx;
     const int wrap = periodic ? 1 : 0;
     const bool sphere = radius > 0.0;
-    CpProfile& prof = ctx->prof_cdist;
+    CpProfile& prof = *c.prof;
     profile_clear(prof);
-    ctx->cdist_pairs[0] = ctx->cdist_pairs[1] = 0;
+    unsigned long long* hstat = c.profile ? ctx->cdprofile_stat : ctx->cdist_pairs;
+    for (int i = 0; i < (c.profile ? 4 : 2); ++i) hstat[i] = 0;
 
     CpPlan pl;                                                               // (no group without segments: the outputs are written all the same)
-    XC_TRY(cp_plan(ctx, who, nrange, count, nullptr, e_from, e_to, pts, E, pl));
+    XC_TRY(cp_plan(ctx, who, nrange, c.count, nullptr, c.e_from, c.e_to, c.pts, E, pl));
     const int64_t nbr = (ny + CD_B - 1) / CD_B, nbc = (nx + CD_B - 1) / CD_B, nb = nbr * nbc;
     const int64_t nty = (ny + CD_T - 1) / CD_T, ntx = (nx + CD_T - 1) / CD_T, ntile = nty * ntx;
     const int nd = sphere ? CD_ND_SPHERE : CD_ND_PLANE, nbox = sphere ? CD_NBOX_SPHERE : CD_NBOX_PLANE;
-    // workspace: off | key, nsel, err, pairs (cleared together) | trig | per group: bcnt, lcount, lstart, lcnt, box | the segment table
-    //            (tseg, tid, tpiece) | the tail (xc_cpiece_link.h)
-    long long* d_off; unsigned long long *key, *pairs; int *nsel, *d_err, *bcnt, *lcount, *lstart, *lcnt, *tid, *tpiece;
-    double *trig, *box, *tseg; size_t b_zero = 0; CpTail tail;
-    auto lay = [&](Carve c) {
-        d_off = c.take<long long>((size_t)nrange + 1);
-        b_zero = c.mark();
-        key = c.take<unsigned long long>((size_t)nrange); nsel = c.take<int>((size_t)nrange); d_err = c.take<int>(CP_SMALL);
-        pairs = c.take<unsigned long long>(2);
-        b_zero = c.mark() - b_zero;
-        trig = c.take<double>(sphere ? (size_t)(2 * ny + 2 * nx) : 0);
+    // workspace: off | key, nsel, err, pairs and tiles; K28: mxw, mxg, acc, cnt, bflag (cleared together) | K28: edges, fld | trig | per
+    //            group: bcnt, lcount, lstart, lcnt, box | the segment table (tseg, tid, tpiece) | the tail (xc_cpiece_link.h)
+    long long* d_off; unsigned long long *key, *pairs, *mxw, *mxg, *acc, *cnt; int *nsel, *d_err, *bflag, *bcnt, *lcount, *lstart, *lcnt, *tid, *tpiece;
+    double *d_edges, *trig, *box, *tseg; PpField* d_fld; size_t b_zero = 0; CpTail tail;
+    auto lay = [&](Carve a) {
+        d_off = a.take<long long>((size_t)nrange + 1);
+        b_zero = a.mark();
+        key = a.take<unsigned long long>((size_t)nrange); nsel = a.take<int>((size_t)nrange); d_err = a.take<int>(CP_SMALL);
+        pairs = a.take<unsigned long long>(4);
+        const size_t nbin = c.profile ? (size_t)nrange * (size_t)M : 0;
+        mxw = a.take<unsigned long long>(c.profile ? (size_t)nslab * 2 : 0);
+        mxg = a.take<unsigned long long>(c.profile ? (size_t)nslab * (size_t)std::max(nf, 1) : 0);
+        acc = a.take<unsigned long long>(nbin * (size_t)nch * CP_L); cnt = a.take<unsigned long long>(nbin); bflag = a.take<int>(nbin * (size_t)nch);
+        b_zero = a.mark() - b_zero;
+        d_edges = a.take<double>(c.profile ? (size_t)c.nedge : 0); d_fld = a.take<PpField>(c.profile ? XC_PROPS_MAXF : 0);
+        trig = a.take<double>(sphere ? (size_t)(2 * ny + 2 * nx) : 0);
         const size_t gb = (size_t)pl.gmax * (size_t)nb;
-        bcnt = c.take<int>(gb); lcount = c.take<int>((size_t)pl.gmax); lstart = c.take<int>(gb); lcnt = c.take<int>(gb);
-        box = c.take<double>(gb * (size_t)nbox);
-        tseg = c.take<double>((size_t)pl.nmax * (size_t)nd); tid = c.take<int>((size_t)pl.nmax); tpiece = c.take<int>((size_t)pl.nmax);
-        cp_carve_tail(c, pl, 6, tail);
-        return c.at;
+        bcnt = a.take<int>(gb); lcount = a.take<int>((size_t)pl.gmax); lstart = a.take<int>(gb); lcnt = a.take<int>(gb);
+        box = a.take<double>(gb * (size_t)nbox);
+        tseg = a.take<double>((size_t)pl.nmax * (size_t)nd); tid = a.take<int>((size_t)pl.nmax); tpiece = a.take<int>((size_t)pl.nmax);
+        cp_carve_tail(a, pl, 6, tail);
+        return a.at;
     };
     XC_TRY(lay_out(ctx, &ctx->cpiece_ws, &ctx->cpiece_ws_bytes, lay));
 
+    // the stages of the profiles: 0 table, 1 rounds, 2 select, 3 binning, 4 distance; K28: 5 bound, 6 finish
     StageTimer tm(ctx, prof.ms);                                             // where the time goes (xc_set_kernel_timing)
-    CpRun run(ctx, tm, pl, e_from, e_to, d_off, tail, d_err);
+    CpRun run(ctx, tm, pl, c.e_from, c.e_to, d_off, tail, d_err);
     const dim3 blk(CP_TPB);
     const size_t npl = (size_t)ny * (size_t)nx;
 
     tm.mark(-1);
     XC_HIP(ctx, hipMemsetAsync(key, 0, b_zero, ctx->stream));
     if (pl.total > 0) {                                                      // the ids first: a refusal writes nothing
-        hipLaunchKernelGGL(k_cd_check, dim3(cp_blocks(pl.total)), blk, 0, ctx->stream, (int64_t)pl.total, E, (const long long*)e_from,
-                           (const long long*)e_to, d_err);
+        hipLaunchKernelGGL(k_cd_check, dim3(cp_blocks(pl.total)), blk, 0, ctx->stream, (int64_t)pl.total, E, (const long long*)c.e_from,
+                           (const long long*)c.e_to, d_err);
         XC_HIP(ctx, hipGetLastError());
         int herr = 0;
         XC_TRY(cp_read_err(ctx, d_err, &herr));
-        if (herr) return fail(ctx, XC_EBADARG, "xc_contour_distance: an edge id outside [0, 2 ny nx)");
+        if (herr) return refuse(": an edge id outside [0, 2 ny nx)");
     }
     if (sphere) {
-        hipLaunchKernelGGL(k_cd_trig, dim3(cp_blocks(std::max(ny, nx))), blk, 0, ctx->stream, ny, nx, ycoord, xcoord, trig);
+        hipLaunchKernelGGL(k_cd_trig, dim3(cp_blocks(std::max(ny, nx))), blk, 0, ctx->stream, ny, nx, c.ycoord, c.xcoord, trig);
         XC_HIP(ctx, hipGetLastError());
     }
     tm.mark(3);
+    PpField hfld[XC_PROPS_MAXF] = {};
+    if (c.profile) {                                                         // the edges and the fields as the kernels read them; the windows' tops
+        for (int m = 0; m < nf; ++m) hfld[m] = {c.f[m], c.f_per_slab[m] ? (unsigned long long)npl : 0ull, c.f_dtype[m] == XC_F32 ? 1 : 0, 0};
+        XC_HIP(ctx, hipMemcpyAsync(d_edges, c.edges, (size_t)c.nedge * 8, hipMemcpyHostToDevice, ctx->stream));
+        XC_HIP(ctx, hipMemcpyAsync(d_fld, hfld, sizeof(hfld), hipMemcpyHostToDevice, ctx->stream));
+        ci_launch_bound(ctx->stream, (int64_t)npl, nslab, c.w, c.w_per_slab, nullptr, 0, mxw);
+        if (nf > 0) pp_launch_bound(ctx->stream, (int64_t)npl, nslab, nf, c.w, c.w_per_slab, d_fld, mxg);
+        XC_HIP(ctx, hipGetLastError());
+        tm.mark(5);
+    }
     XC_TRY(run.upload_off());
     XC_TRY(run.fill_table());
     tm.mark(0);
 
-    // the planes of the ranges [a, b) without any segment
+    // K27: the planes of the ranges [a, b) without any segment (K28's words of such a range stay zero)
     auto none = [&](int64_t a, int64_t b) -> int {
+        if (c.profile) return XC_OK;
         for (int64_t r = a; r < b; ++r) {
-            hipLaunchKernelGGL(k_cd_none, dim3((unsigned)((npl + CP_TPB - 1) / CP_TPB)), blk, 0, ctx->stream, (size_t)r * npl, npl, dist,
-                               (long long*)edge, (long long*)piece);
+            hipLaunchKernelGGL(k_cd_none, dim3((unsigned)((npl + CP_TPB - 1) / CP_TPB)), blk, 0, ctx->stream, (size_t)r * npl, npl, c.dist,
+                               (long long*)c.edge, (long long*)c.piece);
         }
         XC_HIP(ctx, hipGetLastError());
         return XC_OK;
@@ -508,8 +698,13 @@ int launch_contour_distance(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     CdArgs A;
     A.ny = ny; A.nx = nx; A.nty = nty; A.ntx = ntx; A.nb = nb; A.wrap = wrap; A.prune = ctx->cdist_prune; A.period = wrap ? period : 0.0;
     A.radius = radius; A.cap = (max_dist > 0.0 && std::isfinite(max_dist)) ? max_dist : 0.0;
-    A.fy = ycoord; A.fx = xcoord; A.trig = trig; A.off = d_off; A.lcount = lcount; A.lstart = lstart; A.lcnt = lcnt; A.box = box; A.tseg = tseg;
-    A.tid = tid; A.tpiece = tpiece; A.mask = negate_mask; A.dist = dist; A.edge = (long long*)edge; A.piece = (long long*)piece; A.pairs = pairs;
+    A.fy = c.ycoord; A.fx = c.xcoord; A.trig = trig; A.off = d_off; A.lcount = lcount; A.lstart = lstart; A.lcnt = lcnt; A.box = box; A.tseg = tseg;
+    A.tid = tid; A.tpiece = tpiece; A.mask = c.negate_mask; A.dist = c.dist; A.edge = (long long*)c.edge; A.piece = (long long*)c.piece; A.pairs = pairs;
+    CdProf P = {};
+    if (c.profile) {
+        P.nedge = c.nedge; P.nf = nf; P.ncont = c.ncont; P.global = ctx->cdprofile_global; P.edges = d_edges; P.w = c.w; P.w_per_slab = c.w_per_slab;
+        P.fld = d_fld; P.mxw = mxw; P.mxg = mxg; P.acc = acc; P.cnt = cnt; P.bflag = bflag; P.tiles = pairs + 2;
+    }
 
     int64_t done = 0;                                                       // the ranges written so far
     for (const CpGroup& g : pl.groups) {
@@ -519,20 +714,20 @@ int launch_contour_distance(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         tm.mark(3);
         run.begin(g);
         XC_TRY(run.rounds());
-        const CoRoles s = co_launch_select(run, wrap, nx, pts, select, nsel, key);
+        const CoRoles s = co_launch_select(run, wrap, nx, c.pts, c.select, nsel, key);
         XC_HIP(ctx, hipGetLastError());
         tm.mark(2);
-#define XC_CD_SEL_ARGS select, run.e_from, tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key
+#define XC_CD_SEL_ARGS c.select, run.e_from, tail.rid, s.root, run.b.prv, run.b.lab, s.pn, s.pw, key
         hipLaunchKernelGGL(k_cd_count, run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, nx, nbc, nb, XC_CD_SEL_ARGS, bcnt);
         hipLaunchKernelGGL(k_cd_scan, dim3((unsigned)ng), blk, 0, ctx->stream, nb, bcnt, lcount, lstart, lcnt);
         const dim3 bgrid(cp_blocks(ng * nb));
         if (sphere) {
             hipLaunchKernelGGL((k_cd_fill<true>), run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, ny, nx, nbc, nb, wrap, A.period,
-                               XC_CD_SEL_ARGS, d_off, pts, ycoord, xcoord, bcnt, tseg, tid, tpiece);
+                               XC_CD_SEL_ARGS, d_off, c.pts, c.ycoord, c.xcoord, bcnt, tseg, tid, tpiece);
             hipLaunchKernelGGL((k_cd_box<true>), bgrid, blk, 0, ctx->stream, ng, nb, run.s0, g.r0, d_off, lcount, lstart, lcnt, tseg, box);
         } else {
             hipLaunchKernelGGL((k_cd_fill<false>), run.grid, blk, 0, ctx->stream, run.n, run.s0, g.r0, E, ny, nx, nbc, nb, wrap, A.period,
-                               XC_CD_SEL_ARGS, d_off, pts, ycoord, xcoord, bcnt, tseg, tid, tpiece);
+                               XC_CD_SEL_ARGS, d_off, c.pts, c.ycoord, c.xcoord, bcnt, tseg, tid, tpiece);
             hipLaunchKernelGGL((k_cd_box<false>), bgrid, blk, 0, ctx->stream, ng, nb, run.s0, g.r0, d_off, lcount, lstart, lcnt, tseg, box);
         }
 #undef XC_CD_SEL_ARGS
@@ -545,8 +740,13 @@ int launch_contour_distance(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
         for (int64_t ra = g.r0; ra < g.r1; ra += step) {
             A.ra = ra;
             const dim3 grid((unsigned)(std::min<int64_t>(step, g.r1 - ra) * ntile));
-            if (sphere) hipLaunchKernelGGL((k_cd_dist<true>), grid, dim3(CD_TPB), 0, ctx->stream, A);
-            else hipLaunchKernelGGL((k_cd_dist<false>), grid, dim3(CD_TPB), 0, ctx->stream, A);
+            if (c.profile) {
+                if (sphere) hipLaunchKernelGGL((k_cd_profile<true>), grid, dim3(CD_TPB), 0, ctx->stream, A, P);
+                else hipLaunchKernelGGL((k_cd_profile<false>), grid, dim3(CD_TPB), 0, ctx->stream, A, P);
+            } else {
+                if (sphere) hipLaunchKernelGGL((k_cd_dist<true>), grid, dim3(CD_TPB), 0, ctx->stream, A);
+                else hipLaunchKernelGGL((k_cd_dist<false>), grid, dim3(CD_TPB), 0, ctx->stream, A);
+            }
             XC_HIP(ctx, hipGetLastError());
         }
         done = g.r1;
@@ -554,8 +754,16 @@ int launch_contour_distance(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
     }
     XC_TRY(none(done, nrange));
     tm.mark(4);
+    if (c.profile) {
+        const int64_t nout = nrange * M * nch;
+        XC_HIP(ctx, hipMemsetAsync(c.flags, 0, (size_t)nrange * (size_t)nch * 4, ctx->stream));
+        hipLaunchKernelGGL(k_cd_profile_finish, dim3(cp_blocks(nout)), blk, 0, ctx->stream, nrange, M, nf, c.ncont, acc, cnt, bflag, mxw, mxg,
+                           (long long*)c.nodes, c.area, c.sums, (int*)c.flags);
+        XC_HIP(ctx, hipGetLastError());
+        tm.mark(6);
+    }
     run.report(prof);
-    XC_HIP(ctx, hipMemcpyAsync(ctx->cdist_pairs, pairs, 16, hipMemcpyDeviceToHost, ctx->stream));
+    XC_HIP(ctx, hipMemcpyAsync(hstat, pairs, c.profile ? 32 : 16, hipMemcpyDeviceToHost, ctx->stream));
     XC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return XC_OK;
 }
@@ -568,14 +776,42 @@ int xc_contour_distance_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, 
                             double radius, double max_dist, const uint8_t* negate_mask, double* dist, int64_t* edge, int64_t* piece)
 {
     XC_CTX(ctx);
-    return xc::launch_contour_distance(ctx, nrange, count, e_from, e_to, pts, ny, nx, periodic, select, ycoord, xcoord, period, radius, max_dist,
-                                       negate_mask, dist, edge, piece);
+    xc::CdCall c = {};
+    c.who = "xc_contour_distance"; c.prof = &ctx->prof_cdist;
+    c.nrange = nrange; c.count = count; c.e_from = e_from; c.e_to = e_to; c.pts = pts; c.ny = ny; c.nx = nx; c.periodic = periodic;
+    c.select = select; c.ycoord = ycoord; c.xcoord = xcoord; c.period = period; c.radius = radius; c.max_dist = max_dist;
+    c.negate_mask = negate_mask; c.dist = dist; c.edge = edge; c.piece = piece;
+    return xc::launch_cdist(ctx, c);
+}
+
+int xc_contour_distance_profile_dev(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to,
+                                    const double* pts, int64_t ny, int64_t nx, int periodic, int select, const double* ycoord,
+                                    const double* xcoord, double period, double radius, double max_dist, const uint8_t* negate_mask,
+                                    int nedge, const double* edges, int ncont, const double* w, int w_per_slab, int nf, const void* const* f,
+                                    const int* f_dtype, const int* f_per_slab, int64_t* nodes, double* area, double* sums, int32_t* flags)
+{
+    XC_CTX(ctx);
+    xc::CdCall c = {};
+    c.who = "xc_contour_distance_profile"; c.prof = &ctx->prof_cdprofile;
+    c.nrange = nrange; c.count = count; c.e_from = e_from; c.e_to = e_to; c.pts = pts; c.ny = ny; c.nx = nx; c.periodic = periodic;
+    c.select = select; c.ycoord = ycoord; c.xcoord = xcoord; c.period = period; c.radius = radius; c.max_dist = max_dist;
+    c.negate_mask = negate_mask;
+    c.profile = true; c.nedge = nedge; c.edges = edges; c.ncont = ncont; c.w = w; c.w_per_slab = w_per_slab; c.nf = nf; c.f = f;
+    c.f_dtype = f_dtype; c.f_per_slab = f_per_slab; c.nodes = nodes; c.area = area; c.sums = sums; c.flags = flags;
+    return xc::launch_cdist(ctx, c);
 }
 
 int xc_set_cdist_prune(xc_ctx* ctx, int on)
 {
     if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
     ctx->cdist_prune = on ? 1 : 0;
+    return XC_OK;
+}
+
+int xc_set_cdprofile_global(xc_ctx* ctx, int on)
+{
+    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
+    ctx->cdprofile_global = on ? 1 : 0;
     return XC_OK;
 }
 
@@ -586,6 +822,23 @@ int xc_last_cdist_profile(xc_ctx* ctx, double* ms, int64_t* pairs_visited, int64
     if (ms) { ms[0] = (double)p.ms[0] + (double)p.ms[1] + (double)p.ms[2]; ms[1] = (double)p.ms[3]; ms[2] = (double)p.ms[4]; }
     if (pairs_visited) *pairs_visited = (int64_t)ctx->cdist_pairs[0];
     if (pairs_total) *pairs_total = (int64_t)ctx->cdist_pairs[1];
+    if (groups) *groups = p.groups;
+    return XC_OK;
+}
+
+int xc_last_cdprofile_profile(xc_ctx* ctx, double* ms, int64_t* pairs_visited, int64_t* pairs_total, int64_t* tiles_window,
+                              int64_t* tiles_global, int* groups)
+{
+    if (!ctx) return xc::fail(nullptr, XC_EBADARG, "null context");
+    const xc::CpProfile& p = ctx->prof_cdprofile;
+    if (ms) {
+        ms[0] = (double)p.ms[0] + (double)p.ms[1] + (double)p.ms[2]; ms[1] = (double)p.ms[3]; ms[2] = (double)p.ms[4];
+        ms[3] = (double)p.ms[5]; ms[4] = (double)p.ms[6];
+    }
+    if (pairs_visited) *pairs_visited = (int64_t)ctx->cdprofile_stat[0];
+    if (pairs_total) *pairs_total = (int64_t)ctx->cdprofile_stat[1];
+    if (tiles_window) *tiles_window = (int64_t)ctx->cdprofile_stat[2];
+    if (tiles_global) *tiles_global = (int64_t)ctx->cdprofile_stat[3];
     if (groups) *groups = p.groups;
     return XC_OK;
 }

@@ -43,12 +43,7 @@ constexpr int PP_PASS = 4;                    // fields of one pass of the scan
 constexpr unsigned long long PP_NOKEY = ~0ull;  // no key yet (minimum), no place yet; the key of no value: a NaN's
 constexpr unsigned long long PP_SIGN = 1ull << 63;
 
-// one field plane as the kernels read it (a table of the call's fields on the device; the extremum field is entry nf)
-struct PpField {
-    const void* p;
-    unsigned long long stride;    // elements between two slabs: ny nx, or 0 for a plane all slabs share
-    int f32, pad;
-};
+#include "xc_cpiece_field.h"
 
 // the staged records of K21 (behind K19's in ctx->cpiece_acc), `cap` of each
 struct PpStage {
@@ -72,12 +67,6 @@ inline void pp_carve(Carve& c, int64_t cap, int nf, PpStage& pp)
     pp.flg = c.take<int>(n); pp.gflg = c.take<int>(n);
 }
 
-__device__ __forceinline__ double pp_load(const PpField& f, size_t slab, size_t node)
-{
-    const size_t i = (size_t)f.stride * slab + node;
-    return f.f32 ? (double)((const float*)f.p)[i] : ((const double*)f.p)[i];
-}
-
 // the usual monotone key of a double: unsigned order of the keys = order of the values, -0.0 below +0.0
 __device__ __forceinline__ unsigned long long pp_key(double v)
 {
@@ -87,25 +76,6 @@ __device__ __forceinline__ unsigned long long pp_key(double v)
 __device__ __forceinline__ double pp_unkey(unsigned long long k)
 {
     return __longlong_as_double((long long)((k & PP_SIGN) ? (k & ~PP_SIGN) : ~k));
-}
-
-// mxg[s][m]: the bit pattern of max |w g_m| over the finite values of slab s (0 at the start); grid (blocks, nslab, nf)
-__global__ __launch_bounds__(CI_TPB)
-void k_pp_bound(int64_t npl, int nf, const double* __restrict__ w, int w_per_slab, const PpField* __restrict__ fld,
-                unsigned long long* __restrict__ mxg)
-{
-    const int64_t s = blockIdx.y;
-    const int m = blockIdx.z;
-    const PpField f = fld[m];
-    const double* wp = w ? w + (w_per_slab ? (size_t)s * (size_t)npl : 0) : nullptr;
-    unsigned long long mf = 0ull;
-    for (int64_t i = (int64_t)blockIdx.x * CI_TPB + threadIdx.x; i < npl; i += (int64_t)gridDim.x * CI_TPB) {
-        const double t = __dmul_rn(wp ? wp[i] : 1.0, pp_load(f, (size_t)s, (size_t)i));
-        const unsigned long long bt = (unsigned long long)__double_as_longlong(fabs(t));
-        if (bt < CI_INF && bt > mf) mf = bt;
-    }
-    mf = ci_wave_max(mf);
-    if ((threadIdx.x & 63) == 0 && mf) atomicMax(mxg + (size_t)s * nf + m, mf);
 }
 
 __global__ __launch_bounds__(CP_TPB)
@@ -327,14 +297,6 @@ void pp_launch_pass(int n_pass, dim3 grid, hipStream_t stream, int64_t ng, int64
 }
 
 // ---------------------------------------------------------------- the host steps of K21, each launched from one place (xc_cprecords.hip)
-// the tops of the windows of the nf fields; at most 1024 blocks a slab and field
-inline void pp_launch_bound(hipStream_t stream, int64_t npl, int64_t nslab, int nf, const double* w, int w_per_slab, const PpField* fld,
-                            unsigned long long* mxg)
-{
-    const dim3 ggrid((unsigned)std::min<int64_t>((npl + CI_TPB - 1) / CI_TPB, 1024), (unsigned)nslab, (unsigned)nf);
-    hipLaunchKernelGGL(k_pp_bound, ggrid, dim3(CI_TPB), 0, stream, npl, nf, w, w_per_slab, fld, mxg);
-}
-
 // the scan of the ng ranges of a group.  Pass 1: the first PP_PASS fields and the keys of x; pass 2: the other fields and the places of
 // the keys
 inline void pp_launch_scan(hipStream_t stream, int64_t ng, int64_t rows, int64_t nchunk, int ncont, const PlGroup& g, const PiStage& st,

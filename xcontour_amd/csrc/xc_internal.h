@@ -116,6 +116,9 @@ struct xc_ctx {
     CpProfile prof_cdist;       // K27 (xc_cdist.hip): table, rounds, select, binning, distance
     int cdist_prune = 1;                                         // K27: skip the blocks that cannot hold a winner (xc_set_cdist_prune)
     unsigned long long cdist_pairs[2] = {0ull, 0ull};           // K27: (node, segment) pairs the last call evaluated / would have without pruning
+    CpProfile prof_cdprofile;   // K28 (xc_cdist.hip): K27's five, then the bounds of the windows, then the finish
+    int cdprofile_global = 0;                                    // K28: every tile adds straight to the global words (xc_set_cdprofile_global)
+    unsigned long long cdprofile_stat[4] = {0ull, 0ull, 0ull, 0ull};   // K28: K27's pair counts, then the tiles that took the LDS window / the global path
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
@@ -383,10 +386,6 @@ int launch_contour_overturning(xc_ctx* ctx, int64_t nrange, const uint64_t* coun
 int launch_contour_interior(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
                             int64_t ny, int64_t nx, int periodic, int select, int flip, int ncont, const double* w, int w_per_slab,
                             const void* f, int f_dtype, int64_t* n_in, double* sum_w, double* sum_wf, uint8_t* mask);
-// K27: distance from every node to the selected pieces of K12's records (device pointers), the nearest segment and its piece; waits for the stream three times
-int launch_contour_distance(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
-                            int64_t ny, int64_t nx, int periodic, int select, const double* ycoord, const double* xcoord, double period,
-                            double radius, double max_dist, const uint8_t* negate_mask, double* dist, int64_t* edge, int64_t* piece);
 // K24: the folded columns of the selected pieces of K12's records (device pointers) gathered into events; waits for the stream twice
 int launch_contour_folds(xc_ctx* ctx, int64_t nrange, const uint64_t* count, const int64_t* e_from, const int64_t* e_to, const double* pts,
                          int64_t ny, int64_t nx, int periodic, int select, int ncont, const double* w, int w_per_slab, const void* f,
