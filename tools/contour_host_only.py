@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """The Python around the library calls of the contour family (K10 - K24), alone: `Context` methods and `Contour2D` methods of
-K10 - K13 and of the record kernels K14, K16, K17, K19, K20 and K24 on a small stack (4 x 24 x 48 float32, 8 levels) against a stand-in
+K10 - K13 and of the record kernels K14, K16, K17, K19, K20, K24, K27 and K28 on a small stack (4 x 24 x 48 float32, 8 levels) against a stand-in
 library whose entry points return at once.  No GPU needed; a sibling of tools/facade_host_only.py, which does the same for the Keff
 sequence.  Every count download reads 2, so K12's, K13's and K24's second pass is staged too -- but zeros under find_contours, whose host
 join wants real records (the join is the library's own xc_join_segments: build it first), and under the label rows, where a label
 of 2 in a range of two pieces would point past the last range ("fill 0" in the row's name: the batch without segments, every label
 -1 and no map fetched).  `--package DIR`: time the xcontour_amd package under DIR instead of this tree's (an A/B against another
-revision's Python; point XC_LIB_PATH at a built library if DIR has none).  Prints us per call, the best of `--rounds R` (default 5)
+revision's Python; point XC_LIB_PATH at a built library if DIR has none).  `--only WORD`: the rows whose name holds WORD.  Prints us per call, the best of `--rounds R` (default 5)
 rounds of 400 calls.  On a shared host the figures drift by tens of percent from one process to the next whatever R: alternate the
 two sides and compare medians and minima (profiles/contour_host_ab.md, profiles/ring_host_ab.md)."""
 import ctypes as C
@@ -97,7 +97,12 @@ calls = [
     ('cal_contour_overturning', lambda: cm.cal_contour_overturning(lv, periodic=True)),
     ('cal_integral_inside_contours', lambda: cm.cal_integral_inside_contours(lv, integrand=tr, periodic=True)),
     ('cal_contour_folds', lambda: cm.cal_contour_folds(lv, integrand=tr, periodic=True)),
+    ('ctx.contour_distance', lambda: ctx.contour_distance(q, lv, y, x, period=P, select='main', signed=True, return_nearest=True)),
+    ('ctx.contour_distance_profile', lambda: ctx.contour_distance_profile(q, lv, y, x, [-2.0, -0.5, 0.5, 2.0], w=wgt, fields=(q, wgt), period=P,
+                                                                          select='main', signed=True)),
 ]
+if '--only' in args:                           # the rows whose name holds the word
+    calls = [c for c in calls if args[args.index('--only') + 1] in c[0]]
 tot = 0.0
 with np.errstate(all='ignore'):                # (the stand-in leaves host-form outputs as np.empty made them)
     for name, fn in calls:

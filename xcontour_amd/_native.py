@@ -1666,6 +1666,41 @@ class Context(object):
             raise XContourHipError(XC_EBADARG, '%s: max_distance is NaN' % who)
         return a, ycoord, xcoord, radius, period, cap
 
+    def _cdist_groups(self, a, ncg, coords, out_nbytes, per_node, payload, periodic, signed, flip):
+        """the frame K27 and K28 share.  The contours of the checked arguments `a` go `ncg` at a time; a group of Ng stages, beside
+        K12's records, `coords`, then a's weights and fields, and allocates out_nbytes(n, Ng) for a batch of n slabs -- a slab
+        counts per_node bytes per node and contour toward the batch cap.  With `signed` three more buffers trail them: K17's two
+        sums and its mask, made there with the same select and `flip`.  payload(head, inputs, outputs, mask pointer or None, n,
+        Ng) makes the entry's call behind `head`, the arguments up to `select`, and downloads; the groups' results are joined
+        along the contour axis."""
+        ny, nx, N = a.ny, a.nx, a.N
+
+        def group(k0, k1):
+            g = a.on(a.q, np.ascontiguousarray(a.contours[..., k0:k1]))
+            g.N = Ng = k1 - k0
+
+            def call(cnt, total, dn, ins, outs, recs):
+                head = (self.handle, cnt.size, dn.ptr, *self._record_run(g, total, ins, recs)[0], ny, nx, 1 if periodic else 0, int(a.sel))
+                if signed:                                       # K17's mask, made where it is used
+                    self._check(self.lib.xc_contour_interior_dev(*head, 1 if flip else 0, Ng, None, 0, None, 0, outs[-3].ptr, outs[-2].ptr,
+                                                                 None, outs[-1].ptr))
+                return payload(head, ins, outs, outs[-1].ptr if signed else None, cnt.shape[0], Ng)
+
+            def one(s0, s1):
+                n = s1 - s0
+                qb, cb, wb, _, fb, _ = g.batch(s0, s1)
+                nb = out_nbytes(n, Ng) + ([n * Ng * 8, n * Ng * 8, n * Ng * ny * nx] if signed else [])
+                return self._with_segment_records(periodic, qb, cb, call, inputs=list(coords) + ([wb] if wb is not None else []) + fb,
+                                                  out_nbytes=nb)
+            return self._batched(a.nslab, g.slab_bytes(Ng * per_node), one)
+
+        parts = [group(k0, min(N, k0 + ncg)) for k0 in range(0, N, ncg)]
+        if len(parts) == 1:
+            return parts[0]
+        if isinstance(parts[0], tuple):
+            return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(len(parts[0])))
+        return np.concatenate(parts, axis=1)
+
     def contour_distance(self, q, contours, ycoord, xcoord, radius=0.0, period=None, select='all', max_distance=None, signed=False,
                          flip=False, return_nearest=False):
         """How far every node lies from every contour (K27, xc_contour_distance_dev, on the device records of K12: the segment
@@ -1680,43 +1715,21 @@ class Context(object):
         taken in groups, so that the device holds no more output planes than one batch may stage."""
         a, ycoord, xcoord, radius, period, cap = self._cdist_args('xc_contour_distance', q, contours, ycoord, xcoord, radius, period, select,
                                                                   max_distance)
-        periodic = period is not None
-        ny, nx, N = a.ny, a.nx, a.N
+        ny, nx = a.ny, a.nx
         signed, near = bool(signed), bool(return_nearest)
         per_node = 8 + (16 if near else 0) + (1 if signed else 0)            # the bytes of one node's outputs, per contour
-        ncg = max(1, min(N, int(self.max_batch_bytes) // (ny * nx * per_node)))
+        ncg = max(1, min(a.N, int(self.max_batch_bytes) // (ny * nx * per_node)))
 
-        def group(k0, k1):
-            g = a.on(a.q, np.ascontiguousarray(a.contours[..., k0:k1]))
-            g.N = Ng = k1 - k0
+        def distance(head, ins, outs, mask, n, Ng):
+            (dy, dx), dd = ins, outs[0]
+            self._check(self.lib.xc_contour_distance_dev(*head, dy.ptr, dx.ptr, period if period is not None else 0.0, radius, cap, mask,
+                                                         dd.ptr, *([b.ptr for b in outs[1:3]] if near else [None] * 2)))
+            res = (dd.download((n, Ng, ny, nx), np.float64),)
+            return res + tuple(b.download((n, Ng, ny, nx), np.int64) for b in outs[1:3]) if near else res[0]
 
-            def distance(cnt, total, dn, ins, outs, recs):
-                n = cnt.shape[0]
-                (dy, dx), dd = ins, outs[0]
-                head = (self.handle, cnt.size, dn.ptr, *self._record_run(g, total, ins, recs)[0], ny, nx, 1 if periodic else 0, int(a.sel))
-                dm = outs[-1] if signed else None
-                if signed:                                       # K17's mask, made where it is used
-                    self._check(self.lib.xc_contour_interior_dev(*head, 1 if flip else 0, Ng, None, 0, None, 0, outs[-3].ptr, outs[-2].ptr,
-                                                                 None, dm.ptr))
-                self._check(self.lib.xc_contour_distance_dev(*head, dy.ptr, dx.ptr, period if periodic else 0.0, radius, cap,
-                                                             dm.ptr if signed else None, dd.ptr, *([b.ptr for b in outs[1:3]] if near else [None] * 2)))
-                res = (dd.download((n, Ng, ny, nx), np.float64),)
-                return res + tuple(b.download((n, Ng, ny, nx), np.int64) for b in outs[1:3]) if near else res[0]
-
-            def one(s0, s1):
-                # beside K12's records: the coordinates, the planes of dist[, edge, piece], and for the sign K17's two sums and its mask
-                n = s1 - s0
-                plane = n * Ng * ny * nx
-                nb = [plane * 8] * (3 if near else 1) + ([n * Ng * 8, n * Ng * 8, plane] if signed else [])
-                return self._with_segment_records(periodic, *g.batch(s0, s1)[:2], distance, inputs=(ycoord, xcoord), out_nbytes=nb)
-            return self._batched(a.nslab, g.slab_bytes(Ng * per_node), one)
-
-        parts = [group(k0, min(N, k0 + ncg)) for k0 in range(0, N, ncg)]
-        if len(parts) == 1:
-            return parts[0]
-        if near:
-            return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(3))
-        return np.concatenate(parts, axis=1)
+        # beside K12's records: the coordinates, the planes of dist[, edge, piece] (and for the sign what `_cdist_groups` adds)
+        return self._cdist_groups(a, ncg, (ycoord, xcoord), lambda n, Ng: [n * Ng * ny * nx * 8] * (3 if near else 1), per_node, distance,
+                                  period is not None, signed, flip)
 
     def set_cdprofile_global(self, on):
         """whether every tile of `contour_distance_profile` adds its terms straight to the global words instead of an LDS window
@@ -1758,51 +1771,33 @@ class Context(object):
             raise XContourHipError(XC_EBADARG, '%s: at most 8 fields (XC_PROPS_MAXF)' % who)
         a, ycoord, xcoord, radius, period, cap = self._cdist_args(who, q, contours, ycoord, xcoord, radius, period, select, max_distance,
                                                                   w=w, fields=fields)
-        periodic = period is not None
         ny, nx, N, M, nf = a.ny, a.nx, a.N, edges.size - 1, len(a.fields)
         signed, has_w = bool(signed), a.w is not None
         # a contour takes one byte per node on the device (K17's mask) when signed, and no plane at all when not
         ncg = max(1, min(N, int(self.max_batch_bytes) // (ny * nx))) if signed else N
 
-        def group(k0, k1):
-            g = a.on(a.q, np.ascontiguousarray(a.contours[..., k0:k1]))
-            g.N = Ng = k1 - k0
+        def profile(head, ins, outs, mask, n, Ng):
+            (dy, dx), dw, dfl = ins[:2], (ins[2] if has_w else None), ins[2 + has_w:]
+            dnod, dar, dflag = outs[:3]
+            dsum = outs[3] if nf else None
+            fp = (_vp * max(nf, 1))(*[b.ptr for b in dfl])
+            fd = (C.c_int * max(nf, 1))(*[dtype_code(v.dtype) for v in a.fields])
+            fs = (C.c_int * max(nf, 1))(*[1 if v.ndim == 3 else 0 for v in a.fields])
+            self._check(self.lib.xc_contour_distance_profile_dev(
+                *head, dy.ptr, dx.ptr, period if period is not None else 0.0, radius, cap, mask, edges.size, _ptr(edges),
+                Ng, dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, nf, C.cast(fp, _vp), C.cast(fd, _vp),
+                C.cast(fs, _vp), dnod.ptr, dar.ptr, dsum.ptr if nf else None, dflag.ptr))
+            sums = (np.ascontiguousarray(np.moveaxis(dsum.download((nf, n, Ng, M), np.float64), 0, 2)) if nf
+                    else np.empty((n, Ng, 0, M), dtype=np.float64))
+            return (dnod.download((n, Ng, M), np.int64), dar.download((n, Ng, M), np.float64), sums,
+                    dflag.download((n, Ng, 1 + nf), np.int32))
 
-            def profile(cnt, total, dn, ins, outs, recs):
-                n = cnt.shape[0]
-                (dy, dx), dw, dfl = ins[:2], (ins[2] if has_w else None), ins[2 + has_w:]
-                dnod, dar, dflag = outs[:3]
-                dsum = outs[3] if nf else None
-                head = (self.handle, cnt.size, dn.ptr, *self._record_run(g, total, ins, recs)[0], ny, nx, 1 if periodic else 0, int(a.sel))
-                dm = outs[-1] if signed else None
-                if signed:                                       # K17's mask, made where it is used
-                    self._check(self.lib.xc_contour_interior_dev(*head, 1 if flip else 0, Ng, None, 0, None, 0, outs[-3].ptr, outs[-2].ptr,
-                                                                 None, dm.ptr))
-                fp = (_vp * max(nf, 1))(*[b.ptr for b in dfl])
-                fd = (C.c_int * max(nf, 1))(*[dtype_code(v.dtype) for v in a.fields])
-                fs = (C.c_int * max(nf, 1))(*[1 if v.ndim == 3 else 0 for v in a.fields])
-                self._check(self.lib.xc_contour_distance_profile_dev(
-                    *head, dy.ptr, dx.ptr, period if periodic else 0.0, radius, cap, dm.ptr if signed else None, edges.size, _ptr(edges),
-                    Ng, dw.ptr if has_w else None, 1 if has_w and a.w.ndim == 3 else 0, nf, C.cast(fp, _vp), C.cast(fd, _vp),
-                    C.cast(fs, _vp), dnod.ptr, dar.ptr, dsum.ptr if nf else None, dflag.ptr))
-                sums = (np.ascontiguousarray(np.moveaxis(dsum.download((nf, n, Ng, M), np.float64), 0, 2)) if nf
-                        else np.empty((n, Ng, 0, M), dtype=np.float64))
-                return (dnod.download((n, Ng, M), np.int64), dar.download((n, Ng, M), np.float64), sums,
-                        dflag.download((n, Ng, 1 + nf), np.int32))
+        def out_nbytes(n, Ng):
+            return [n * Ng * M * 8, n * Ng * M * 8, n * Ng * (1 + nf) * 4] + ([nf * n * Ng * M * 8] if nf else [])
 
-            def one(s0, s1):
-                # beside K12's records: the coordinates, the weights and the fields; the tables of nodes, area, flags and sums; and
-                # for the sign K17's two sums and its mask
-                n = s1 - s0
-                qb, cb, wb, _, fb, _ = g.batch(s0, s1)
-                nb = [n * Ng * M * 8, n * Ng * M * 8, n * Ng * (1 + nf) * 4] + ([nf * n * Ng * M * 8] if nf else [])
-                nb += [n * Ng * 8, n * Ng * 8, n * Ng * ny * nx] if signed else []
-                return self._with_segment_records(periodic, qb, cb, profile, inputs=[ycoord, xcoord] + ([wb] if has_w else []) + fb,
-                                                  out_nbytes=nb)
-            return self._batched(a.nslab, g.slab_bytes(Ng if signed else 0), one)
-
-        parts = [group(k0, min(N, k0 + ncg)) for k0 in range(0, N, ncg)]
-        return parts[0] if len(parts) == 1 else tuple(np.concatenate([p[i] for p in parts], axis=1) for i in range(4))
+        # beside K12's records: the coordinates, the weights and the fields; the tables of nodes, area, flags and sums (and for the
+        # sign what `_cdist_groups` adds)
+        return self._cdist_groups(a, ncg, (ycoord, xcoord), out_nbytes, 1 if signed else 0, profile, period is not None, signed, flip)
 
     # the per-event table of `contour_folds`: the library's record, the two tongues (0 under, 1 over) side by side
     FOLD_DTYPE = np.dtype([('c_west', np.int32), ('c_east', np.int32), ('ncol', np.int32), ('ncross_max', np.int32),

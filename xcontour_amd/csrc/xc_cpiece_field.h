@@ -1,4 +1,4 @@
-// The field table of K21, shared by K21 (xc_cpiece_props.h, xc_cprecords.hip) and K28 (xc_cdist.hip): how a call's fields reach the
+// The field table of K21, shared by K21 (xc_cpiece_props.h, xc_cprecords.hip) and K28 (xc_cdist_profile.h): how a call's fields reach the
 // kernels, how a kernel reads one, and the pass that leaves max |w g_m| over the finite values of every (slab, field) -- the tops of the
 // windows of the fields' sums.  Included inside namespace xc { namespace { ... } } after xc_cpiece_sum.h and xc_cinside_bound.h.
 #pragma once

@@ -113,12 +113,12 @@ struct xc_ctx {
     CpProfile prof_cpoverlap;   // K22 (xc_cpoverlap.hip): the run count, the accumulate pass, the finish; no rounds
     CpProfile prof_cptrack;     // K23 (xc_cptrack.hip): accept and degrees, the rounds, ranks and rows; no groups
     CpProfile prof_cfold;       // K24 (xc_cfold.hip): table, rounds, select, mark + columns, runs, fold scan + finish
-    CpProfile prof_cdist;       // K27 (xc_cdist.hip): table, rounds, select, binning, distance
-    int cdist_prune = 1;                                         // K27: skip the blocks that cannot hold a winner (xc_set_cdist_prune)
-    unsigned long long cdist_pairs[2] = {0ull, 0ull};           // K27: (node, segment) pairs the last call evaluated / would have without pruning
-    CpProfile prof_cdprofile;   // K28 (xc_cdist.hip): K27's five, then the bounds of the windows, then the finish
-    int cdprofile_global = 0;                                    // K28: every tile adds straight to the global words (xc_set_cdprofile_global)
-    unsigned long long cdprofile_stat[4] = {0ull, 0ull, 0ull, 0ull};   // K28: K27's pair counts, then the tiles that took the LDS window / the global path
+    // K27, K28 (xc_cdist.hip), the last call of each: table, rounds, select, binning, distance; K28: then the bounds of the windows, then
+    // the finish.  stat: the (node, segment) pairs evaluated / an unpruned call evaluates; K28: then the tiles of the LDS window / the global path
+    struct CdLast { CpProfile prof; unsigned long long stat[4] = {0ull, 0ull, 0ull, 0ull}; };
+    CdLast last_cdist, last_cdprofile;
+    int cdist_prune = 1;        // K27, K28: skip the blocks that cannot hold a winner (xc_set_cdist_prune)
+    int cdprofile_global = 0;   // K28: every tile adds straight to the global words (xc_set_cdprofile_global)
     unsigned long long* single_stamps = nullptr;   // diagnostics (xc_dbg_single_stamps): wall-clock stamps of every workgroup at the phase boundaries
 };
 
