@@ -1125,7 +1125,8 @@ int xc_last_cdist_profile(xc_ctx* ctx, double* ms, int64_t* pairs_visited, int64
  *     nodes int64 [nrange][M]      the nodes of the bin, whatever their weights and fields hold
  *     area  f64   [nrange][M]      the sum of w over them
  *     sums  f64   [nf][nrange][M]  the sum of w f_m, each product rounded once (float32 fields widened first); NULL exactly when nf == 0
- *     flags int32 [nrange][1 + nf] channel 0 the area, 1 + m field m: 1 where a term of that channel of that range was not finite
+ *     flags int32 [nrange][1 + nf] channel 0 the area, 1 + m field m: 1 where a term of that channel at a node in a bin of that range was
+ *                                  +-inf (a NaN term sets nothing, nor does a node in no bin)
  *   The sums are K17's: the exact sum of the float64 terms rounded once, a window of 160 bits under 2^top, top = 12 + the frexp exponent
  *   of max |w| (max |w f_m|) over the finite values of the range's slab.  A NaN term is skipped; a +-inf term makes THAT channel of THAT
  *   bin NaN (and sets the flag of its range and channel), and no other.  No output depends on the order of the segments or of arrival,

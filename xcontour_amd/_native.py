@@ -1758,7 +1758,7 @@ class Context(object):
         w: None (weight 1), (ny, nx) or (nslab, ny, nx) float64; fields: at most XC_PROPS_MAXF f32 / f64 arrays, (ny, nx) or
         (nslab, ny, nx).  Returns (nodes int64 (nslab, N, M), area float64 (nslab, N, M): the sum of w, sums float64
         (nslab, N, nf, M): the sums of w f_m, each product rounded once, flags int32 (nslab, N, 1 + nf): where a term of the area
-        or of field m was not finite).  The sums are exact sums rounded once (NaN terms skipped, an infinite term makes that
+        or of field m, at a node inside a bin, was +-inf -- a NaN term sets nothing).  The sums are exact sums rounded once (NaN terms skipped, an infinite term makes that
         bin's sum NaN): the same bits whatever the order, the workspace or the batches.  No plane crosses to the host; the only
         per-node buffer beside the inputs is K17's mask with `signed`, and the contours are taken in groups under it."""
         who = 'xc_contour_distance_profile'
